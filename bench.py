@@ -23,6 +23,9 @@ or plainly as `python bench.py --gpus N` -- then this process spawns the N ranks
 `python bench.py --dry-dist N` rehearses that multi-rank path on CPU (gloo, stub engine): the driver's 8-GPU run is the first time
 RCCL sees more than one rank, but not the first time the harness around it runs.
 
+`--dump-outputs DIR` writes the latents the timed path returned in its last job as DIR/latent.npy (float32, <= 64 MB), so that two
+builds can be compared output for output on the same seeded inputs.
+
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement), with
   roofline      dominant kernel family (implicit GEMM: gemm4 + fused feed-forward + row chains) vs the dense MFMA peak;
                 `achieved` = the family's share of the TIMED loop, `isolated` = its launches timed back to back with HIP events
@@ -89,6 +92,9 @@ def parse():
                     "references are extra and unbudgeted: one batch-B forward + the sampled latent of 2 utterances)")
     ap.add_argument("--ops", default="", help="write the per-launch table (name, kind, ms, GFLOP, MB) to this file")
     ap.add_argument("--detail", action="store_true", help="print the per-kernel-family table to stderr")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed jobs, write what the timed path returned in its last job "
+                    "(the sampled latents, gathered over the ranks) as DIR/<name>.npy, float32, at most 64 MB in all (beyond that a fixed, "
+                    "seeded sample of utterances); the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--cpu-worker", type=float, default=0.0, help=argparse.SUPPRESS)     # internal: one all-core baseline worker
     ap.add_argument("--cpu-threads", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-frames", type=int, default=0, help=argparse.SUPPRESS)
@@ -466,6 +472,24 @@ def write_detail(path: str, d: dict) -> None:
         print(f"bench.py: could not write {path}: {ex!r}", file=sys.stderr)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """name -> array as path/<name>.npy in float32.  If they exceed DUMP_BUDGET_BYTES together, every array keeps the same fixed,
+    seeded, sorted sample of its leading-axis items (utterances), so that runs of the same arguments dump the same rows."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        if total > DUMP_BUDGET_BYTES and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * DUMP_BUDGET_BYTES // total))
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], size=keep, replace=False))
+            v = np.ascontiguousarray(v[rows])
+            print(f"bench.py: {name}: dumped items {rows.tolist()} of {arrays[name].shape[0]} (64 MB budget)", file=sys.stderr)
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
 class DryEngine:
     """--dry-dist: stands in for ns2vc_amd.engine.Engine with the same call sequence.  A job sleeps ~0.2 ms per step and utterance
     and returns x_T / 2 (deterministic, so the gathered latents can be checked on every rank)."""
@@ -671,6 +695,11 @@ def main():
             eng.sample(x, use_graph=False, stream=stream, tail=tail_eng, tail_steps=a.tail_fp32)
             stream.synchronize()
             loop_check = {"graph_loop_equals_eager_loop": bool(torch.equal(x, x_timed)), "steps": K}
+    if a.dump_outputs:
+        # what a caller of the timed path receives: the latents of the last timed job (with N ranks, gathered as the timed job gathers them)
+        latent = gather_latents(x_timed, B * world) if world > 1 else x_timed
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"latent": latent.cpu().numpy()})
     per_rank_ms = [wall * 1e3 / K]
     gather_ms = 0.0
     if world > 1:

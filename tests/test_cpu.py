@@ -582,6 +582,41 @@ def test_bench_default_line_is_compact_and_single():
     assert c["value"] == pytest.approx(c["n_gpus"] * 1e3 / c["ms_per_step"], rel=1e-4)
 
 
+@pytest.mark.parametrize("n", [1, 2])
+def test_bench_dump_outputs_dry_run(n, tmp_path):
+    """`--dump-outputs DIR` writes the latents the timed path returned in its last job (gathered over the ranks), float32, the same
+    from run to run; the stdout line stays the single JSON line.  The stub engine returns x_T / 2 on every rank."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"dump{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-dist", str(n), "--steps", "3", "--warmup", "1", "--reps", "2",
+                            "--batch", "2", "--seconds", "1", "--detail-json", "", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len([ln for ln in r.stdout.splitlines() if ln.startswith("{")]) == 1
+        assert sorted(os.listdir(d)) == ["latent.npy"]
+        dumps.append(np.load(d / "latent.npy"))
+    y = dumps[0]
+    assert y.dtype == np.float32 and y.shape == (2 * n, 100, 94) and np.isfinite(y).all() and np.abs(y).max() > 0
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_dump_outputs_budget(tmp_path):
+    """above 64 MB in all, every array keeps the same fixed, seeded sample of its items and the dump fits the budget"""
+    import bench
+    big = np.arange(72 * 64 * 4096, dtype=np.float64).reshape(72, 64, 4096)           # 72 MB as float32
+    small = np.ones((72, 3), dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b) and 0 < a.shape[0] < 72 and a.shape[1:] == (64, 4096)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BUDGET_BYTES + 1024
+    rows = a[:, 0, 0] / (64 * 4096)                                                        # item index of every kept row, ascending
+    assert np.array_equal(rows, np.sort(rows)) and np.array_equal(a, big[rows.astype(np.int64)].astype(np.float32))
+    assert np.load(tmp_path / "a" / "small.npy").shape[0] == a.shape[0]
+    bench.dump_outputs(str(tmp_path / "c"), {"small": small})                             # under budget: whole
+    assert np.array_equal(np.load(tmp_path / "c" / "small.npy"), small)
+
+
 def test_repeat_expand_matches_reference_golden():
     """ns2vc_amd.audio.repeat_expand_2d (index map + one gather) against outputs of the reference's own utils.repeat_expand_2d
     (utils.py:482-496): bit-identical, including non-integer ratios, target shorter than source, and batched input."""
