@@ -90,7 +90,9 @@ int ns2vc_unet_num_missing_weights(ns2vc_unet* h, char* first_missing, int bufle
  *   "fold_ff"   1|0  ff.net.2 folded into proj_out at pack time (default 1) vs two launches
  *   "fuse_ffn"  1|0  GEGLU feed-forward + proj_out in ONE launch where eligible (16-bit precisions, dim <= 256; needs
  *                    ln_linear and fold_ff; default 1) vs the GEGLU GEMM + the folded GEMM
- * The environment variables NS2VC_LN_LINEAR / NS2VC_FOLD_FF / NS2VC_FUSE_FFN set the defaults at ns2vc_unet_create. */
+ * The environment variables NS2VC_LN_LINEAR / NS2VC_FOLD_FF / NS2VC_FUSE_FFN set the defaults at ns2vc_unet_create.
+ *   "temb_join_skip" n  (tests, not a plan option) record the fork_temb join at the (n+1)-th reader of the time scale /
+ *                    shift rows instead of the first; the plan build then refuses the fork (ns2vc_unet_op_info which = 2) */
 int ns2vc_unet_set_option(ns2vc_unet* h, const char* name, int value);
 /* LayerNorm-by-linearity health: the largest |mean| / std over every LayerNorm input row seen since the last read-out
  * (or since prepare).  The 16-bit modes round the raw row before centring, so their error on a row grows ~linearly
@@ -162,7 +164,11 @@ int ns2vc_unet_tap_info(ns2vc_unet* h, int idx, char* name, int buflen, int* row
 int ns2vc_unet_tap_read(ns2vc_unet* h, int idx, float* host_dst);   /* synchronous, [rows][cols] channels-last */
 int ns2vc_unet_num_launches(ns2vc_unet* h, int* per_forward, int* per_condition);
 /* which: 0 = per-step forward plan, 1 = condition plan.  kind: 0 other, 1 implicit GEMM, 2 attention,
- * 3 norm statistics, 4 copy.  flops / bytes: algorithmic work of that launch. */
+ * 3 norm statistics, 4 copy.  flops / bytes: algorithmic work of that launch.
+ * which = 2: the timestep-embedding branch of the per-step plan (option fork_temb), idx 0..5 -> name = "begin" (its first launch),
+ * "end" (one past its last), "join" (the launch a captured step joins it in front of), "first_reader" (the first launch that reads
+ * its scale / shift rows), "readers" (how many do), "forks" (1 if a captured step forks the branch), value in *kind.  The plan
+ * build refuses the fork ("forks" 0) unless first_reader >= join. */
 int ns2vc_unet_op_info(ns2vc_unet* h, int which, int idx, char* name, int buflen, int* kind, double* flops, double* bytes);
 /* Per-launch timing of the per-step plan: each launch repeated `reps` times between one hipEvent pair on
  * `stream`; ms[i] = average milliseconds of launch i (n_ms >= launches). Leaves garbage in the workspace. Synchronous. */

@@ -189,6 +189,9 @@ struct ns2vc_unet {
                                // r6: inside the captured step graph the timestep-embedding branch (time_embed + time_emb_proj.all: two small launches that depend on the step
                                // counter only) runs BESIDE conv_in and the first resnet's conv1 on a forked stream and joins in front of the first consumer of the scale / shift rows
   int temb_begin = -1, temb_end = -1, temb_join = -1;        // ... their places in fwd_ops (build_plan)
+  int temb_first = -1, temb_readers = 0;     // the first launch that reads the scale / shift rows (fused GEMM prologue OR stand-alone gn_apply) and how many do
+  bool temb_ok = false;                      // plan-build invariant: no reader sits in front of temb_join (otherwise the fork is refused; ns2vc_unet_op_info which = 2)
+  int temb_join_skip = 0;                    // tests (set_option "temb_join_skip"): readers passed over when the join is recorded -- forces the refusal
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool fuse_xattn = false;     // the prompt cross-attention of attn2 runs inside the fused feed-forward kernel (ffn.hip ATT, r6): no attn2.sdpa launch at dim 128 / 256.
@@ -808,6 +811,15 @@ struct Planner {
     op.name = name; op.fn = std::move(fn); op.kind = kind; op.flops = flops; op.bytes = bytes;
     ops->push_back(std::move(op));
   }
+  // every launch that reads the time scale / shift rows (h->temb) -- a GEMM with a GroupNorm prologue or a stand-alone gn_apply -- is planned
+  // through here: the captured step's side branch that computes them (fork_temb) joins in front of the FIRST of them
+  void temb_reader() {
+    if (sizing || ops != &h->fwd_ops) return;
+    const int idx = (int)ops->size();
+    if (h->temb_first < 0) h->temb_first = idx;
+    if (h->temb_join < 0 && h->temb_readers >= h->temb_join_skip) h->temb_join = idx;
+    ++h->temb_readers;
+  }
   void tap(const std::string& name, const float* src, int rows, int cols) {
     if (!h->debug) return;
     float* cp = alloc<float>((size_t)rows * cols);
@@ -832,7 +844,7 @@ struct Planner {
     // (a GroupNorm prologue reads the fp32 rows and writes + re-reads the operand rows it builds)
     const double pro = g.gnp_x ? in_rows * cgn * (4.0 + osz * (g.gnp_raw ? 2.0 : 1.0)) : 0.0;
     if (g.taps == 3 && g.tmode == TMODE_SAME && !g.conv_bn) g.conv_bn = convts_bn_for(g, h->bn128_min);     // the column tile is a PLAN decision (this engine's device)
-    if (!sizing && g.gnp_temb && ops == &h->fwd_ops && h->temb_join < 0) h->temb_join = (int)ops->size();    // first launch that reads the time scale / shift rows
+    if (g.gnp_temb) temb_reader();
     add(g.gnp_x ? name + "[+norm]" : name, [=](hipStream_t s) { return launch_gemm(g, pr, s); }, 1, flops, bytes + pro);
     if (!sizing && g.gnp_x && g.gnp_sync) {
       unsigned* words = g.gnp_sync;
@@ -906,6 +918,7 @@ struct Planner {
       add(name + ".gn_stats", [=](hipStream_t s) { return launch_gn_partial(a0, lda0, c0, a1, lda1, c1, Bq, Tl, Gq, part, nchunk, rows, s); },
           3, 3.0 * n, 4.0 * n);
     }
+    if (temb) temb_reader();
     add(name + ".gn_apply", [=](hipStream_t s) {
       return launch_gn_apply(a0, lda0, c0, a1, lda1, c1, Bq, Tl, Gq, eps, part, nchunk, st0, st1, gamma, beta, temb, ldt, temb_off, silu, dst,
                              raw, pr, s, pair);                  // (pair: the rows as a hi + lo operand pair, split_io's conv_out)
@@ -1252,7 +1265,7 @@ int build_plan(ns2vc_unet* h, bool sizing) {
     void* emb_act = xio ? (void*)h->emb_act_f32 : h->emb_act_op;
     const int eprec = xio ? PREC_F32 : prec;                    // type SiLU(emb) is written in
     const int tdim = c0;
-    if (!sizing) { h->temb_begin = (int)h->fwd_ops.size(); h->temb_join = -1; }
+    if (!sizing) { h->temb_begin = (int)h->fwd_ops.size(); h->temb_join = h->temb_first = -1; h->temb_readers = 0; }
     P.add("time_embed", [=](hipStream_t s) {
       // sampling loop: the MLP of every step's timestep was evaluated once for the table (ns2vc_sampler_run), a step adds aug
       if (hh->use_step_table) return launch_emb_from_table(hh->temb_table, hh->step_dev, aug, emb, emb_act, eprec, B, E, s);
@@ -1372,7 +1385,17 @@ int build_plan(ns2vc_unet* h, bool sizing) {
   }
   h->arena_used = P.off;
   h->stats_bytes = std::max<size_t>(P.stats_used, 1) * sizeof(long long);
+  // the fork of the timestep-embedding branch is only correct if every reader of its result is at or after the join
+  h->temb_ok = !sizing && h->temb_begin > 0 && h->temb_end > h->temb_begin && h->temb_join >= h->temb_end && h->temb_first >= h->temb_join;
+  if (!sizing && h->fork_temb && !h->temb_ok)
+    fprintf(stderr, "ns2vc: fork_temb refused for this plan (join at launch %d, first reader of the time scale / shift rows at %d): the step graph stays linear\n",
+            h->temb_join, h->temb_first);
   return 0;
+}
+
+// does a captured step run the timestep-embedding branch on a forked stream (fork_temb)?  `last`: end of the fwd_ops range the step launches
+bool temb_forks(const ns2vc_unet* h, size_t last) {
+  return h->fork_temb && !h->debug && h->temb_ok && (size_t)h->temb_join <= last;
 }
 
 int run_ops(const std::vector<Op>& ops, hipStream_t s, size_t first = 0, size_t last = (size_t)-1) {
@@ -1411,6 +1434,7 @@ void drop_plan(ns2vc_unet* h) {
   h->next_step = -1;           // the solver state lived in the arena
   h->ln_posted = false;
   h->attn_fallbacks = nullptr; // (the counters lived in the arena too)
+  h->temb_ok = false;
   h->ln_health = nullptr;
 }
 
@@ -1613,6 +1637,10 @@ int ns2vc_unet_set_debug(ns2vc_unet* h, int enable) {
 int ns2vc_unet_set_option(ns2vc_unet* h, const char* name, int value) {
   if (!h || !name) return fail("null argument");
   if (bind_device(h)) return 1;
+  if (!strcmp(name, "temb_join_skip")) {      // (a test knob, not a plan option: see ns2vc_unet_op_info which = 2)
+    if (h->temb_join_skip != std::max(value, 0)) { h->temb_join_skip = std::max(value, 0); drop_plan(h); }
+    return 0;
+  }
   bool* opt = option_ptr(h, name);
   if (!opt) return fail("unknown option '%s' (ln_linear, fold_ff, fuse_ffn, fuse_ffn_pre, fuse_geglu, fuse_rows, fuse_rows_gn, fuse_gn_gemm, fuse_gn_cat, gn_coop, slice_rows, attn_fp8, attn_optimistic, conv_ts, conv_wtiled, gn_inloop, fuse_solver, fuse_xattn, fork_temb, exact_io, split_io)", name);
   // the cooperative GroupNorm prologue only where the placement probe of this device came back positive (r5)
@@ -1777,7 +1805,7 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
   size_t first = 0;
   // r6: under capture the timestep-embedding branch becomes a parallel branch of the graph (fork after the statistics clear, which advances the step counter
   // the branch reads; join in front of the first launch that reads the scale / shift rows).  Eager loops keep one stream: same launches, same results.
-  if (capturing && h->fork_temb && !h->debug && h->temb_begin > 0 && h->temb_end > h->temb_begin && h->temb_join >= h->temb_end && (size_t)h->temb_join <= last) {
+  if (capturing && temb_forks(h, last)) {
     if (!h->side_stream) HIPCHK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
     if (!h->ev_fork) HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     if (!h->ev_join) HIPCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
@@ -1948,6 +1976,17 @@ int ns2vc_unet_num_launches(ns2vc_unet* h, int* per_forward, int* per_condition)
 
 int ns2vc_unet_op_info(ns2vc_unet* h, int which, int idx, char* name, int buflen, int* kind, double* flops, double* bytes) {
   if (!h) return fail("null engine handle");
+  if (which == 2) {      // the record of the timestep-embedding branch (fork_temb): field `idx` -> its name and, in *kind, its value
+    static const char* const field[6] = {"begin", "end", "join", "first_reader", "readers", "forks"};
+    if (!h->arena) return fail("engine not prepared (call ns2vc_unet_prepare)");
+    if (idx < 0 || idx >= 6) return fail("op index out of range");
+    GemmArgs g;
+    const int v[6] = {h->temb_begin, h->temb_end, h->temb_join, h->temb_first, h->temb_readers,
+                      temb_forks(h, solver_in_conv_out(h, g) ? (size_t)h->conv_out_idx : h->fwd_ops.size()) ? 1 : 0};
+    snprintf(name, buflen, "%s", field[idx]);
+    *kind = v[idx]; *flops = 0.0; *bytes = 0.0;
+    return 0;
+  }
   const std::vector<Op>& ops = which ? h->cond_ops : h->fwd_ops;
   if (idx < 0 || idx >= (int)ops.size()) return fail("op index out of range");
   snprintf(name, buflen, "%s", ops[idx].name.c_str());

@@ -374,6 +374,17 @@ class Engine:
             out.append((name.value.decode(), int(kind.value), float(fl.value), float(by.value)))
         return out
 
+    def temb_fork(self) -> Dict[str, int]:
+        """Where the per-step plan's timestep-embedding branch sits (option fork_temb): its launches [begin, end), the launch a captured
+        step joins it in front of, the first of the `readers` launches that read its scale / shift rows, and whether a captured step forks."""
+        out = {}
+        name = C.create_string_buffer(32)
+        v, fl, by = C.c_int(), C.c_double(), C.c_double()
+        for i in range(6):
+            check(self.lib.ns2vc_unet_op_info(self.h, 2, i, name, 32, C.byref(v), C.byref(fl), C.byref(by)), "op_info(2)")
+            out[name.value.decode()] = int(v.value)
+        return out
+
     def profile_forward(self, reps: int = 5, stream=None) -> np.ndarray:
         """Per-launch HIP-event timing of the per-step plan (average ms per launch over `reps` back-to-back launches)."""
         nf, _ = self.launches()

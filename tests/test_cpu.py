@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import rel_l2
+from util import local_errors, rel_l2
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -37,6 +37,34 @@ def inputs(tag, B, T, Lp):
 
 
 # ---- spec / weights -------------------------------------------------------------------
+def test_local_error_metric_sees_what_one_rel_l2_dilutes():
+    """Why the engine tests gate frame / channel errors and not only one relative L2 over the whole tensor.  A (32, 100, 938)
+    result -- the bench shape -- with i.i.d. noise at 7e-4 relative (the fp16 engine's error level) passes the 1e-3 bar.  So do
+    (a) the same result with ONE frame, the last of item 0 next to item 1's first (a batch seam), 10 % wrong: it adds 0.10 /
+    sqrt(32 * 938) = 5.8e-4 in quadrature, and (b) one channel of one item 3 % wrong over all its frames: 0.03 / sqrt(32 * 100) =
+    5.3e-4.  (A 15 % frame would add 8.7e-4: still below the bar without the noise.)  The localized figures of util.local_errors
+    flag each by more than an order of magnitude, and stay near the noise level when nothing is corrupted."""
+    B, C, T, eps = 32, 100, 938, 7e-4
+    rng = np.random.default_rng(5)
+    r = rng.standard_normal((B, C, T)) * (1.0 + 0.5 * np.sin(np.arange(T) / 37.0))[None, None, :] * rng.uniform(0.5, 2.0, (B, 1, 1))
+    noisy = r + eps * np.sqrt((r * r).mean(axis=(1, 2), keepdims=True)) * rng.standard_normal(r.shape)
+    clean = local_errors(noisy, r)
+    assert rel_l2(noisy, r) < 1e-3
+    assert clean["frame"] < 2 * eps and clean["chan"] < 2 * eps and clean["item"] < 1.2 * eps and clean["frame_ratio"] < 2.0, clean
+    seam = noisy.copy()
+    seam[0, :, T - 1] += 0.10 * r[0, :, T - 1] * rng.choice([-1.0, 1.0], C)
+    chan = noisy.copy()
+    chan[17, 42, :] += 0.03 * r[17, 42, :]
+    for y, what in ((seam, "frame"), (chan, "chan")):
+        m = local_errors(y, r)
+        assert rel_l2(y, r) < 1e-3, (what, rel_l2(y, r))       # the whole-tensor gate passes ...
+        assert m[what] > 20 * clean[what], (what, m, clean)    # ... the localized one does not
+    assert local_errors(seam, r)["frame_ratio"] > 20 * clean["frame_ratio"]
+    assert local_errors(chan, r)["item"] > 1.5 * clean["item"]
+    exact = local_errors(r, r)
+    assert exact["frame"] == exact["chan"] == exact["item"] == exact["frame_ratio"] == 0.0
+
+
 def test_param_spec_matches_reference_state_dict():
     from ns2vc_amd.spec import UNetConfig, param_spec
     ref = json.load(open(os.path.join(GOLD, "unet_state_keys.json")))

@@ -12,6 +12,8 @@ from util import rel_l2
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_v1.npz")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FP32_TOL = 1e-5            # the fp32 engine at its own accuracy (measured 1.45e-6 here; test_engine_gpu.py)
+FP32_SAMPLED_TOL = 5e-5    # ... and its sampled latents (measured 1.5e-6)
 
 
 def _inputs(tag, B, T, Lp):
@@ -44,7 +46,7 @@ def test_dropin_module_forward_matches_reference_golden(state, diag):
         tup = m(torch.cat([x, content], dim=1), 499.50003, prompt, encoder_attention_mask=mask, return_dict=False)
     e = rel_l2(out.sample.cpu().numpy(), gold["g3b.y"])
     diag(f"drop-in nn.Module forward (fp32 engine) vs reference golden: {e:.3e}")
-    assert e < 1e-3 and isinstance(tup, tuple) and rel_l2(tup[0].cpu().numpy(), gold["g3b.y"]) < 1e-3
+    assert e < FP32_TOL and isinstance(tup, tuple) and rel_l2(tup[0].cpu().numpy(), gold["g3b.y"]) < FP32_TOL
     assert m.engine_calls == 2 and m.autograd_calls == 0          # inference ran on the HIP engine, not on the training path
     y_train = m(torch.cat([x, content], dim=1), torch.tensor([499.50003, 499.50003]).cuda(), prompt, encoder_attention_mask=mask).sample
     assert m.autograd_calls == 1 and y_train.requires_grad        # autograd recording -> PyTorch-ROCm ops (train.py drop-in)
@@ -130,7 +132,7 @@ def test_pipeline_sampler_matches_reference_golden(state, diag):
         y = d.sample(content, prompt, mask, noise=xT, solver=solver, steps=steps)
         e = rel_l2(y.cpu().numpy(), gold[f"g5.{tag}.y"])
         diag(f"pipeline.Denoiser.sample {tag}: {e:.3e}")
-        assert e < 1e-3
+        assert e < FP32_SAMPLED_TOL
     y1 = d.denoise(xT, torch.full((3,), 666.0).cuda(), content, prompt, mask)
     assert y1.shape == xT.shape and bool(torch.isfinite(y1).all())
     d16 = Denoiser(state)                                     # default precision (fp16), LayerNorm guard on

@@ -82,6 +82,8 @@ def test_grouped_converter_equals_per_segment_runs(pre_model, precision, tol, di
         errs.append(rel_l2(a.cpu().numpy(), b.cpu().numpy()))
     diag(f"grouped converter ({precision}) vs per-segment runs: max rel {max(errs):.3e}")
     assert max(errs) < tol
+    if precision == "fp32":
+        assert max(errs) < 1e-5        # the fp32 engine at its own accuracy (measured 1.8e-6), tighter than the parameter's bound
 
 
 def test_grouped_converter_segment_vs_oracle(pre_model, weights, diag):
@@ -106,7 +108,7 @@ def test_grouped_converter_segment_vs_oracle(pre_model, weights, diag):
     ref = sampler_ref.unipc_bh2(lambda xx, tt: unet_ref.denoiser(P, UNetConfig(), xx, tc, tp, tm, tt), sampler_ref.linear_betas(1000), xT, 5)
     e = rel_l2(out[i].cpu().numpy(), ref[0].numpy())
     diag(f"grouped converter segment vs oracle sampler (fp32 engine): {e:.3e}")
-    assert e < 1e-4
+    assert e < 5e-5                                       # the fp32 engine's sampled-latent bound (measured 1.5e-6)
 
 
 def test_pipeline_with_real_front_end_end_to_end_rtf(pre_model, diag):

@@ -10,6 +10,31 @@ def rel_l2(a, b) -> float:
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
+def local_errors(y, r) -> dict:
+    """Localized error figures of a (B, C, T) result `y` against its reference `r` (float64).  One whole-tensor rel_l2 dilutes an
+    error confined to one frame or one channel by sqrt(B T) or sqrt(B C); these do not:
+      frame       max over (b, t) of |y[b,:,t] - r[b,:,t]| / rms_b, rms_b = |r[b]| / sqrt(T)  (the item's RMS frame norm: quiet frames do not inflate it)
+      chan        max over (b, c) of |y[b,c,:] - r[b,c,:]| / (|r[b]| / sqrt(C))
+      item        max over b of rel_l2(y[b], r[b])
+      frame_ratio worst frame error / median frame error (spread-out rounding noise: ~1 + a few / sqrt(C); a local defect: large)"""
+    y = np.asarray(y, dtype=np.float64)
+    r = np.asarray(r, dtype=np.float64)
+    assert y.shape == r.shape and y.ndim == 3, (y.shape, r.shape)
+    _, C, T = r.shape
+    d = y - r
+    nr = np.maximum(np.sqrt((r * r).sum(axis=(1, 2))), 1e-30)                 # |r[b]|
+    fe = np.sqrt((d * d).sum(axis=1)) / (nr / np.sqrt(T))[:, None]            # (B, T)
+    ce = np.sqrt((d * d).sum(axis=2)) / (nr / np.sqrt(C))[:, None]            # (B, C)
+    item = np.sqrt((d * d).sum(axis=(1, 2))) / nr
+    med = float(np.median(fe))
+    return {"frame": float(fe.max()), "chan": float(ce.max()), "item": float(item.max()),
+            "frame_ratio": float(fe.max() / med) if med > 0 else (0.0 if fe.max() == 0 else float("inf"))}
+
+
+def fmt_local(m: dict) -> str:
+    return " ".join(f"{k} {m[k]:.3e}" if k != "frame_ratio" else f"{k} {m[k]:.2f}" for k in ("frame", "chan", "item", "frame_ratio"))
+
+
 def bf16_round(a: np.ndarray) -> np.ndarray:
     """round-to-nearest-even to bfloat16, returned as float32"""
     u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
