@@ -123,6 +123,16 @@ int ns2vc_unet_set_condition(ns2vc_unet* h, const float* content_bct, const floa
 int ns2vc_unet_set_content(ns2vc_unet* h, const float* content_bct, void* stream);
 int ns2vc_unet_set_prompt(ns2vc_unet* h, const float* prompt_blc, const uint8_t* mask_bl, void* stream);
 int ns2vc_unet_set_mask(ns2vc_unet* h, const uint8_t* mask_bl, void* stream);
+/* Per-item valid lengths (backward-compatible addition to ABI v7): lengths_b = HOST array [B] with 1 <= L_b <= T, or NULL = dense (every item T
+ * frames).  Item b of the padded batch then gives on frames [0, L_b) what the engine gives for that item alone at T = L_b (to the precision's
+ * rounding), and exactly 0 on frames >= L_b; per level the valid length is ceil(L / 2) per stride-2 level (ns2vc_amd.spec.level_lengths).  An out-of-range
+ * value returns an error and changes nothing; ns2vc_unet_prepare resets to dense.  Call it BEFORE set_condition / set_content for the batch (the
+ * content's padded frames are zeroed there).  The first non-NULL call after dense rebuilds the plan as a masked plan (and drops a captured step graph):
+ * GroupNorm statistics from their own pass, the fused GroupNorm prologues, row chains, LayerNorm by linearity and fused feed-forward replaced by their
+ * unfused launches, the rows past an item's end zeroed after every launch that writes them, the self-attention keys there masked, the nearest upsampling
+ * materialised.  Later calls with other lengths only copy the (levels x B) table and the key-mask rows on `stream` (from pinned staging: lengths_b may be reused
+ * on return, and the host waits for nothing but the previous call's copy; a repeat of the current lengths copies nothing): a captured graph stays valid. */
+int ns2vc_unet_set_lengths(ns2vc_unet* h, const int32_t* lengths_b, void* stream);
 
 /* One denoiser evaluation = Diffusion_Encoder.forward (model.py:403-415) ->
  * UNet1DConditionModel.forward (unet_1d_condition.py:743-1037) for the condition set above.

@@ -139,6 +139,7 @@ PROTOTYPES = {
     "ns2vc_unet_set_content": (_I, [_P, _P, _P]),
     "ns2vc_unet_set_prompt": (_I, [_P, _P, _P, _P]),
     "ns2vc_unet_set_mask": (_I, [_P, _P, _P]),
+    "ns2vc_unet_set_lengths": (_I, [_P, _P, _P]),
     "ns2vc_unet_forward": (_I, [_P, _P, _P, _P, _P]),
     "ns2vc_sampler_load": (_I, [_P, _I, C.POINTER(C.c_float)]),
     "ns2vc_sampler_run": (_I, [_P, _P, _I, _P]),

@@ -274,7 +274,12 @@ hipError_t launch_gn_partial(const float* a0, int lda0, int c0, const float* a1,
 hipError_t launch_gn_apply(const float* a0, int lda0, int c0, const float* a1, int lda1, int c1, int B, int T, int G, float eps,
                            const double* partial, int nchunk, const long long* st0, const long long* st1, const float* gamma,
                            const float* beta, const float* temb, int ldtemb, int temb_off, int silu, void* out_op, void* raw_op,
-                           int prec, hipStream_t s, int pair = 0);      // pair (16-bit): out_op rows are [hi(C) | lo(C)] (op_rest)
+                           int prec, hipStream_t s, int pair = 0,       // pair (16-bit): out_op rows are [hi(C) | lo(C)] (op_rest)
+                           const int* lens = nullptr);                  // per-item valid rows [B] (device) or NULL = all T
+// per-item valid lengths: zero rows t >= lens[b] of a [B*T] row tensor in place, or (src set) copy row (b, t) from src row (b, t >> up) and
+// zero the rest; pointers, strides and row_bytes 16-byte multiples
+hipError_t launch_mask_rows(void* dst, size_t ldd_bytes, size_t row_bytes, int B, int T, const int* lens, hipStream_t s, const void* src = nullptr,
+                            size_t lds_bytes = 0, int Tsrc = 0, int up = 0);
 hipError_t launch_ln_apply_op(const float* x, int ldx, int M, int C, float eps, void* out_op, int prec, hipStream_t s);
 hipError_t launch_cast_op(const float* x, size_t n, void* out_op, int prec, hipStream_t s, int split = 0);   // split: as launch_solver_update
 hipError_t launch_time_embed(const float* t_ptr, int t_stride, const int* step_ptr, int coef_stride,

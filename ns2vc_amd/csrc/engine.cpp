@@ -216,6 +216,20 @@ struct ns2vc_unet {
   unsigned long long coef_hash = 0;       // FNV-1a of the loaded solver table (handoff compares)
   std::vector<Tap> taps;
   bool has_mask = false;
+  // Per-item valid lengths (ns2vc_unet_set_lengths).  `masked`: the plan was built for them -- GroupNorm statistics by their own pass over
+  // rows whose padding is zero (no epilogue sums, so no fused GroupNorm prologue, row chain or LayerNorm by linearity), every activation's
+  // rows past an item's end zeroed after the launch that writes them, the self-attention keys there masked by an additive bias row, the
+  // nearest upsampling materialised.  The tables live in the arena at a place that does not depend on the plan, so new lengths for the same
+  // padded shape are a copy on the caller's stream: a captured step graph stays valid.
+  bool masked = false;
+  int* lens_dev = nullptr;                 // [n_levels][B] valid frames per level and item
+  size_t lens_off = 0;                     // arena offset of the two tables
+  float* selfbias_dev = nullptr;           // per level l: [B][T_l] additive self-attention key bias (0 | -10000), levels back to back
+  std::vector<int32_t> lens_applied;       // the lengths the tables hold (a repeat of them copies nothing)
+  void* lens_stage = nullptr;              // pinned staging of both tables for the asynchronous copies, and the event of the last copy out of it
+  size_t lens_stage_bytes = 0;
+  hipEvent_t lens_event = nullptr;
+  bool lens_staged = false;
 
   // named persistent buffers
   float *xe = nullptr, *xbar = nullptr, *d1 = nullptr, *mprev = nullptr, *x0 = nullptr;
@@ -242,6 +256,9 @@ struct ns2vc_unet {
   hipGraphExec_t step_graph = nullptr;
 
   ~ns2vc_unet() {
+    if (lens_staged) (void)hipEventSynchronize(lens_event);
+    if (lens_event) (void)hipEventDestroy(lens_event);
+    if (lens_stage) (void)hipHostFree(lens_stage);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     if (side_stream) (void)hipStreamDestroy(side_stream);
@@ -768,13 +785,40 @@ struct Planner {
   void *xn = nullptr, *xr = nullptr;     // GroupNorm-applied / raw operand copies of a resnet input
   float *rs1 = nullptr, *rs2 = nullptr, *rs3 = nullptr;   // LayerNorm-by-linearity row statistics [M][C/64][2] (norm1/2/3)
   int gn_rows = 64;
+  // per-item valid lengths (h->masked): level lengths of the plan, and the zeroing of padded rows after every launch that writes a frame tensor
+  bool masked = false;
+  std::vector<int> Ts;
+  int level_of(int Tl) const {
+    for (size_t l = 0; l < Ts.size(); ++l) if (Ts[l] == Tl) return (int)l;
+    return -1;
+  }
+  const int* lens_of(int Tl) const {
+    const int l = level_of(Tl);
+    return (masked && l >= 0 && !sizing) ? h->lens_dev + (size_t)l * B : nullptr;
+  }
+  const float* selfbias_of(int Tl) const {
+    const int l = level_of(Tl);
+    if (!masked || l < 0) return nullptr;
+    size_t o = 0;
+    for (int k = 0; k < l; ++k) o += (size_t)B * Ts[k];
+    return sizing ? nullptr : h->selfbias_dev + o;
+  }
+  // rows t >= lens[b] of a frame tensor [B*Tl][ld] (elements of `esz` bytes, the first `cols` of each row) -> 0 after the launch planned last
+  void mask(const std::string& name, void* p, int ld, int cols, size_t esz, int Tl) {
+    if (!masked || !p || ops != &h->fwd_ops || level_of(Tl) < 0) return;
+    const int* lens = lens_of(Tl);
+    const int Bq = B;
+    const size_t ldb = (size_t)ld * esz, rb = (size_t)cols * esz;
+    add(name + ".mask", [=](hipStream_t s) { return launch_mask_rows(p, ldb, rb, Bq, Tl, lens, s); }, 4, 0.0, 0.0);
+  }
   // GroupNorm statistics accumulated by the producing GEMM's epilogue (int64 fixed point, [B][C/16][2]);
   // one zeroed slab per produced tensor, all carved from stats_pool (cleared by one memset per forward)
   long long* stats_pool = nullptr;
   size_t stats_cap = 0, stats_used = 0;
   std::map<const void*, long long*> stats_of;
   long long* new_stats(const float* tensor, int Tl, int C) {
-    if (Tl < 64 || (C & 15)) { stats_of.erase(tensor); return nullptr; }
+    // (masked: the epilogue would also sum the padded rows it has not zeroed yet -- the statistics come from gn_partial over the masked rows)
+    if (Tl < 64 || (C & 15) || masked) { stats_of.erase(tensor); return nullptr; }
     const size_t n = (size_t)B * (C / 16) * 2;
     if (stats_used + n > stats_cap) { stats_of.erase(tensor); return nullptr; }
     long long* p = stats_pool ? stats_pool + stats_used : reinterpret_cast<long long*>(sizeof(long long) * (stats_used + 1));  // sizing pass: non-null token
@@ -851,6 +895,11 @@ struct Planner {
       const size_t nbytes = (((size_t)g.B * g.Tin + 63) / 64) * 8;
       ops->back().rearm = [=](hipStream_t s) { return launch_zero(words, (nbytes + 15) & ~(size_t)15, s); };
     }
+    if (g.Tout > 1) {
+      const int nc = g.geglu ? g.N / 2 : g.N;
+      mask(name, g.out_f32, g.ldo_f32, nc, 4, g.Tout);
+      mask(name, g.out_op, g.ldo_op, nc, operand_bytes(pr), g.Tout);
+    }
   }
   // A = operand tensor [B*Tin][c0]; results to out_f32 and/or out_op (row stride = logical width)
   GemmArgs base(const void* a0, int lda0, int c0, int Tin, int Tout, const PackedW& w, float* out_f32, void* out_op, int ldo) {
@@ -919,9 +968,10 @@ struct Planner {
           3, 3.0 * n, 4.0 * n);
     }
     if (temb) temb_reader();
+    const int* lens = masked ? lens_of(Tl) : nullptr;             // (masked: statistics over the valid rows, zero rows past them)
     add(name + ".gn_apply", [=](hipStream_t s) {
       return launch_gn_apply(a0, lda0, c0, a1, lda1, c1, Bq, Tl, Gq, eps, part, nchunk, st0, st1, gamma, beta, temb, ldt, temb_off, silu, dst,
-                             raw, pr, s, pair);                  // (pair: the rows as a hi + lo operand pair, split_io's conv_out)
+                             raw, pr, s, pair, lens);            // (pair: the rows as a hi + lo operand pair, split_io's conv_out)
     }, 3, 4.0 * n, n * (4.0 + opsz * (raw ? 2.0 : 1.0) + opsz * (pair ? 1.0 : 0.0)));
     return GnPro();
   }
@@ -967,13 +1017,14 @@ struct Planner {
     const int pr = prec;
     add(name, [=](hipStream_t s) { return launch_attention(a, hd, pr, s); }, 2, 4.0 * B * a.H * (double)Lq * Lk * hd,
         (double)opsz * B * a.H * hd * (2.0 * Lq + 2.0 * Lk));
+    mask(name, out, ldo, a.H * hd, opsz, Lq);
   }
 
   // r6: does this block run its prompt cross-attention inside the fused feed-forward kernel?  (the plan of the pre-stage form, 8 heads of 16 / 32 channels)
   std::map<std::string, void*> xattn_vt;      // per transformer block: the k | v fragment image of its hoisted rows (built by the condition plan)
   bool xattn_fused(const AttnW& a, int Tl) const {
     const int d = a.dim;
-    const bool lin = h->ln_linear && (d % 128 == 0) && d <= 512;
+    const bool lin = h->ln_linear && (d % 128 == 0) && d <= 512 && !masked;
     return h->fuse_xattn && lin && h->fold_ff && h->fuse_ffn && a.ffn_stream && ffn_eligible(d, Tl, prec) && h->fuse_ffn_pre && a.ffn_pre_stream &&
            h->cfg.heads == 8 && (d == 128 || d == 256);
   }
@@ -988,7 +1039,9 @@ struct Planner {
     };
     // LayerNorm by linearity (h->ln_linear): the producer of every LayerNorm input also writes the raw operand copy
     // `yn` and per-row statistics; the consumer GEMM reads yn and normalises in its epilogue -- no ln_apply pass
-    const bool lin = h->ln_linear && (d % 128 == 0) && d <= 512;
+    // (masked: the row statistics of LayerNorm by linearity come from epilogues that see the padded rows before they are zeroed, and its health
+    //  guard would count them: the explicit normalisation pass over the zeroed rows instead -- LayerNorm of a zero row is zero)
+    const bool lin = h->ln_linear && (d % 128 == 0) && d <= 512 && !masked;
     auto consume = [&](GemmArgs& gg, float* rs, const PackedW& w) {
       if (rs) { gg.ln_stats = rs; gg.ln_wsum = w.wsum; gg.ln_eps = 1e-5f; gg.ln_dim = d; gg.ln_health = h->ln_health; }
     };
@@ -1028,7 +1081,7 @@ struct Planner {
       consume(g, r1, a.qkv);
       gemm(t + ".attn1.qkv", g);
     }
-    attention(t + ".attn1.sdpa", qkv, 3 * d, op_off(qkv, d), 3 * d, op_off(qkv, 2 * d), 3 * d, Tl, Tl, nullptr, hd, ao, d);
+    attention(t + ".attn1.sdpa", qkv, 3 * d, op_off(qkv, d), 3 * d, op_off(qkv, 2 * d), 3 * d, Tl, Tl, selfbias_of(Tl), hd, ao, d);
     float* r2 = lin ? rs2 : nullptr;
     if (rows_ok) {
       rowchain(t + ".rows[attn1.to_out+attn2.to_q]", ao, nullptr, a.chain_mid, a.o1.bias, a.chain_mid_consts, y, qb, d);
@@ -1181,6 +1234,19 @@ int build_plan(ns2vc_unet* h, bool sizing) {
   h->step_dev = P.alloc<int>(64);
   h->ln_health = P.alloc<unsigned>(64);
   h->attn_fallbacks = h->ln_health + 32;          // (same zero-initialised block; the LayerNorm read-out uses words 0 and 16, the cooperative GroupNorm prologue's counter word 48)
+  // per-item valid lengths: the two tables sit BEHIND everything the dense plan of this shape carves (h->lens_off, measured by prepare's sizing
+  // pass), so the dense plan's layout is the one it had without them, and a masked rebuild (which carves no more) finds them where they were
+  size_t lens_bytes = 0;
+  {
+    size_t nb = 0;
+    for (int l = 0; l < nl; ++l) nb += (size_t)B * Ts[l];
+    const size_t lb = (((size_t)nl * B * sizeof(int)) + 255) & ~(size_t)255;
+    lens_bytes = lb + ((nb * sizeof(float) + 255) & ~(size_t)255);
+    h->lens_dev = sizing ? nullptr : reinterpret_cast<int*>(static_cast<char*>(h->arena) + h->lens_off);
+    h->selfbias_dev = sizing ? nullptr : reinterpret_cast<float*>(static_cast<char*>(h->arena) + h->lens_off + lb);
+  }
+  P.masked = h->masked;
+  P.Ts = Ts;
   // ---- shared scratch
   P.gn_rows = 32;
   P.gn_partial = P.alloc<double>((size_t)B * ((T + P.gn_rows - 1) / P.gn_rows) * c.norm_num_groups * 2);
@@ -1354,6 +1420,18 @@ int build_plan(ns2vc_unet* h, bool sizing) {
         float* us = (cur == uc) ? ua : uc;
         GemmArgs g = P.base(samp_in, curC, curC, Tl, Ts[l - 1], b.samp, us, nullptr, b.channels);
         g.taps = 3; g.tmode = TMODE_UP2;
+        if (P.masked) {
+          // (the fused form would read source row L >> 1 -- a valid row when the finer level's length L is odd -- as the halo of output row L - 1:
+          //  the upsampled rows are materialised in P.xn, zero past every item's end, and convolved like any stride-1 input)
+          const int Td = Ts[l - 1], Bq = B;
+          const size_t rb = (size_t)curC * P.opsz;
+          void* dst = P.xn;
+          const void* src = samp_in;
+          const int* lens = P.lens_of(Td);
+          P.add(tag + ".upsample.nearest", [=](hipStream_t s) { return launch_mask_rows(dst, rb, rb, Bq, Td, lens, s, src, rb, Tl, 1); }, 4, 0.0, 3.0 * Bq * Td * rb);
+          g = P.base(P.xn, curC, curC, Td, Td, b.samp, us, nullptr, b.channels);
+          g.taps = 3;
+        }
         g.stats = P.new_stats(us, Ts[l - 1], b.channels);
         P.gemm(tag + ".upsample", g);
         P.tap(tag + ".us", us, B * Ts[l - 1], b.channels);
@@ -1374,10 +1452,16 @@ int build_plan(ns2vc_unet* h, bool sizing) {
     g.taps = 3;
     P.gn_fuse(g, pno);
     if (h->conv_out.N != CP) return fail("internal: conv_out padded width %d != %d", h->conv_out.N, CP);
+    const int conv_out_at = (int)h->fwd_ops.size();      // (the conv_out launch itself: a masked plan appends the zeroing of x0's padded rows behind it)
     P.gemm("conv_out", g, xo ? PREC_F32 : -1);
-    if (!sizing) { h->conv_out_g = g; h->conv_out_idx = (int)h->fwd_ops.size() - 1; h->conv_out_prec = xo ? PREC_F32 : prec; }
+    if (!sizing) { h->conv_out_g = g; h->conv_out_idx = conv_out_at; h->conv_out_prec = xo ? PREC_F32 : prec; }
     P.tap("out", h->x0, B * T, CP);
   }
+  if (sizing) { h->lens_off = P.off; P.off += lens_bytes; }
+  else if (P.off > h->lens_off) {       // (the tables' place: a rebuild must carve no more than the plan that measured it)
+    h->cond_ops.clear(); h->fwd_ops.clear(); h->taps.clear();
+    return fail("internal: plan needs %zu bytes in front of the length tables at %zu (re-run ns2vc_unet_prepare)", P.off, h->lens_off);
+  } else P.off = h->lens_off + lens_bytes;
   if (sizing) h->arena_bytes = P.off;
   else if (P.off > h->arena_bytes) {    // a rebuild must never carve past the allocation the sizing pass measured
     h->cond_ops.clear(); h->fwd_ops.clear(); h->taps.clear();
@@ -1699,6 +1783,8 @@ int ns2vc_unet_prepare(ns2vc_unet* h, int B, int T, int Lp) {
   drop_plan(h);
   h->B = B; h->T = T; h->Lp = Lp;
   h->has_mask = false;
+  h->masked = false;         // a new shape starts dense (ns2vc_unet_set_lengths)
+  h->lens_applied.clear();
   if (build_plan(h, true)) return 1;
   HIPCHK(hipMalloc(&h->arena, h->arena_bytes));
   HIPCHK(hipMemset(h->arena, 0, h->arena_bytes));
@@ -1719,7 +1805,12 @@ int ns2vc_unet_set_content(ns2vc_unet* h, const float* content_bct, void* stream
   const auto& c = h->cfg;
   { const int pw = h->prec != PREC_F32 ? 2 : 1;      // (16-bit: the hi + lo pair, see prepare)
     HIPCHK(launch_nct_to_btc(content_bct, c.content_channels, h->T, h->B, h->content_f32, h->content_op, h->prec, c.content_channels, c.content_channels, s,
-                             pw * c.content_channels, pw == 2 ? c.content_channels : 0)); }
+                             pw * c.content_channels, pw == 2 ? c.content_channels : 0));
+    if (h->masked) {    // content frames past an item's end read as the zero padding of an unpadded run (conv_in's halo)
+      const size_t ob = (size_t)pw * c.content_channels * operand_bytes(h->prec);
+      HIPCHK(launch_mask_rows(h->content_op, ob, ob, h->B, h->T, h->lens_dev, s));
+      if (h->content_f32) HIPCHK(launch_mask_rows(h->content_f32, c.content_channels * 4, c.content_channels * 4, h->B, h->T, h->lens_dev, s));
+    } }
   return run_ops(h->cond_ops, s, 0, h->cond_split);
 }
 
@@ -1755,6 +1846,77 @@ int ns2vc_unet_set_condition(ns2vc_unet* h, const float* content_bct, const floa
   return ns2vc_unet_set_content(h, content_bct, stream);
 }
 
+// masked plans: the fp32 state rows and their operand copy (16-bit: the hi + lo pair) past every item's end -> 0
+static int mask_state_rows(ns2vc_unet* h, hipStream_t s) {
+  if (!h->masked) return 0;
+  const size_t ob = (size_t)(h->prec != PREC_F32 ? 2 : 1) * h->CP * operand_bytes(h->prec);
+  HIPCHK(launch_mask_rows(h->xe, (size_t)h->CP * 4, (size_t)h->CP * 4, h->B, h->T, h->lens_dev, s));
+  HIPCHK(launch_mask_rows(h->xe_op, ob, ob, h->B, h->T, h->lens_dev, s));
+  return 0;
+}
+
+// the plan for the current shape again, dense or masked (h->masked), in the arena it already has: the persistent state (condition, solver
+// state, the length tables) sits at the same offsets in both, so nothing but the launch list and the captured step graph changes
+static int rebuild_plan(ns2vc_unet* h) {
+  if (h->step_graph) { (void)hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
+  return build_plan(h, false);
+}
+
+int ns2vc_unet_set_lengths(ns2vc_unet* h, const int32_t* lengths_b, void* stream) {
+  if (check_ready(h, true)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (!lengths_b) {
+    if (!h->masked) return 0;
+    h->masked = false;
+    h->lens_applied.clear();
+    return rebuild_plan(h);
+  }
+  const int nl = h->cfg.n_levels, B = h->B;
+  for (int b = 0; b < B; ++b)
+    if (lengths_b[b] < 1 || lengths_b[b] > h->T) return fail("lengths[%d] = %d outside [1, T = %d]", b, (int)lengths_b[b], h->T);
+  if (h->masked && h->lens_applied.size() == (size_t)B && std::equal(lengths_b, lengths_b + B, h->lens_applied.begin())) return 0;   // (tables already hold them)
+  std::vector<int> Ts(nl);
+  Ts[0] = h->T;
+  for (int l = 1; l < nl; ++l) Ts[l] = (Ts[l - 1] + 1) / 2;
+  std::vector<int32_t> lens((size_t)nl * B);
+  size_t nb = 0;
+  for (int l = 0; l < nl; ++l) nb += (size_t)B * Ts[l];
+  std::vector<float> bias(nb, 0.f);
+  size_t o = 0;
+  for (int l = 0; l < nl; ++l) {
+    for (int b = 0; b < B; ++b) {
+      const int L = l == 0 ? lengths_b[b] : (lens[(size_t)(l - 1) * B + b] + 1) / 2;      // spec.level_lengths: ceil(L / 2) per stride-2 level
+      lens[(size_t)l * B + b] = L;
+      for (int t = L; t < Ts[l]; ++t) bias[o + (size_t)b * Ts[l] + t] = -10000.f;   // (the cross-attention mask's value: its exp is 0 in fp32)
+    }
+    o += (size_t)B * Ts[l];
+  }
+  if (!h->masked) {
+    h->masked = true;
+    if (rebuild_plan(h)) { h->masked = false; (void)rebuild_plan(h); return 1; }
+  }
+  // Pinned staging, so the copies are truly asynchronous: the host waits only for the PREVIOUS call's copy out of the buffer (enqueued in front of
+  // whatever the caller launched since, so normally long done) -- never for the stream's work behind it
+  const size_t lb = lens.size() * sizeof(int32_t), bb = bias.size() * sizeof(float);
+  if (!h->lens_event) HIPCHK(hipEventCreateWithFlags(&h->lens_event, hipEventDisableTiming));
+  if (h->lens_staged) { HIPCHK(hipEventSynchronize(h->lens_event)); h->lens_staged = false; }
+  if (h->lens_stage_bytes < lb + bb) {
+    if (h->lens_stage) HIPCHK(hipHostFree(h->lens_stage));
+    h->lens_stage = nullptr; h->lens_stage_bytes = 0;
+    HIPCHK(hipHostMalloc(&h->lens_stage, lb + bb, hipHostMallocDefault));
+    h->lens_stage_bytes = lb + bb;
+  }
+  char* st = static_cast<char*>(h->lens_stage);
+  memcpy(st, lens.data(), lb);
+  memcpy(st + lb, bias.data(), bb);
+  HIPCHK(hipMemcpyAsync(h->lens_dev, st, lb, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(h->selfbias_dev, st + lb, bb, hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(h->lens_event, s));
+  h->lens_staged = true;
+  h->lens_applied.assign(lengths_b, lengths_b + B);
+  return 0;
+}
+
 int ns2vc_unet_forward(ns2vc_unet* h, const float* x_bct, const float* t_b, float* out_bct, void* stream) {
   if (check_ready(h, true)) return 1;
   if (!x_bct || !t_b || !out_bct) return fail("null tensor");
@@ -1762,6 +1924,7 @@ int ns2vc_unet_forward(ns2vc_unet* h, const float* x_bct, const float* t_b, floa
   const auto& c = h->cfg;
   h->use_step_table = false;
   HIPCHK(launch_nct_to_btc(x_bct, c.latent_channels, h->T, h->B, h->xe, h->xe_op, h->prec, h->CP, h->CP, s, h->prec != PREC_F32 ? 2 * h->CP : h->CP, h->prec != PREC_F32 ? h->CP : 0));
+  if (mask_state_rows(h, s)) return 1;
   HIPCHK(hipMemcpyAsync(h->t_dev, t_b, (size_t)h->B * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (run_ops(h->fwd_ops, s)) return 1;
   HIPCHK(launch_btc_to_nct(h->x0, h->CP, c.latent_channels, h->T, h->B, out_bct, s));
@@ -1791,6 +1954,8 @@ int ns2vc_sampler_load(ns2vc_unet* h, int steps, const float* coef_host) {
 // (same arithmetic, element for element: common.h solver_upd) -- x0 is never written, the state tensors are read and written once instead of twice
 static bool solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
   if (!h->fuse_solver || h->debug || h->conv_out_idx < 0 || h->conv_out_idx != (int)h->fwd_ops.size() - 1) return false;
+  // (masked plan: the update must see x0 with its padded rows zeroed -- conv_out's epilogue has not zeroed them -- so it stays a launch of its own)
+  if (h->masked) return false;
   if (h->conv_out_prec != h->prec) return false;      // (exact_io: conv_out runs in fp32 there, the operand copy of the state is 16-bit)
   g = h->conv_out_g;
   g.out_f32 = nullptr;
@@ -1838,6 +2003,7 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   const auto& c = h->cfg;
   const size_t n = (size_t)h->B * h->T * h->CP;
   HIPCHK(launch_nct_to_btc(x_T_bct, c.latent_channels, h->T, h->B, h->xe, h->xe_op, h->prec, h->CP, h->CP, s, h->prec != PREC_F32 ? 2 * h->CP : h->CP, h->prec != PREC_F32 ? h->CP : 0));
+  if (mask_state_rows(h, s)) return 1;      // x_T is zero past every item's end; the solver update (linear in its inputs) keeps it so
   HIPCHK(launch_copy16(h->xe, h->xbar, n * sizeof(float), s));
   HIPCHK(launch_zero(h->d1, n * sizeof(float), s));
   HIPCHK(launch_zero(h->mprev, n * sizeof(float), s));

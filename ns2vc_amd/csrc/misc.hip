@@ -74,16 +74,20 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
   }
 }
 
-template <typename TM>
+// MASK (per-item valid lengths, ns2vc_unet_set_lengths): statistics over the lens[b] valid rows of item b, and exact zeros written
+// for rows >= lens[b] (what an unpadded run's conv zero padding reads there; GN(0) != 0).  The dense instantiation is the one above it.
+template <typename TM, bool MASK = false>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ a0, int lda0, int c0, const float* __restrict__ a1,
                                                        int lda1, int c1, int T, int G, float eps, const double* __restrict__ partial,
                                                        int nchunk, const long long* __restrict__ st0, const long long* __restrict__ st1,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        const float* __restrict__ temb, int ldtemb, int temb_off, int silu,
-                                                       TM* __restrict__ out, TM* __restrict__ raw, int rows, int pair) {
+                                                       TM* __restrict__ out, TM* __restrict__ raw, int rows, int pair,
+                                                       const int* __restrict__ lens) {
   op_mode_init<TM>();
   __shared__ float s_mean[8], s_rstd[8];
   const int tid = threadIdx.x, b = blockIdx.y, lane = tid & 63, wave = tid >> 6;
+  const int nv = MASK ? lens[b] : T;            // valid rows of this item
   const int C = c0 + c1, nq = C >> 2, Cg = C / G;
   // streaming coordinates first: the activation loads do not depend on the statistics, so the first batch is in
   // flight while the block finalises mean / rstd (a chain of dependent global loads, shuffles and a double sqrt)
@@ -141,8 +145,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
     if (lane == 0) {
       // double only where it matters (E[x^2] - mean^2 cancels); reciprocal and rsqrt in fp32 (+1 Newton step): a double
       // divide / sqrt is a ~300-cycle software sequence and every workgroup sits on this chain before it can store
-      const float inv_nf = 1.0f / ((float)T * (float)Cg);
-      const double inv_n = (double)inv_nf * (2.0 - (double)inv_nf * ((double)T * (double)Cg));   // refine to ~double accuracy
+      const float inv_nf = 1.0f / ((float)nv * (float)Cg);
+      const double inv_n = (double)inv_nf * (2.0 - (double)inv_nf * ((double)nv * (double)Cg));   // refine to ~double accuracy
       const double mean = ds * inv_n;
       double var = dq * inv_n - mean * mean;
       if (var < 0.0) var = 0.0;
@@ -183,6 +187,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
         const size_t row = (size_t)b * T + r;
         float y0 = w[k].x * sc[0] + sh[0], y1 = w[k].y * sc[1] + sh[1], y2 = w[k].z * sc[2] + sh[2], y3 = w[k].w * sc[3] + sh[3];
         if (silu) { y0 = silu_f(y0); y1 = silu_f(y1); y2 = silu_f(y2); y3 = silu_f(y3); }
+        if (MASK && r >= nv) { y0 = y1 = y2 = y3 = 0.f; w[k] = make_float4(0.f, 0.f, 0.f, 0.f); }
         if (pair) {                                         // hi + lo operand pair (GemmArgs.gnp_pair writes the same): rows of 2 C columns
           out_op4<TM>(out + row * 2 * C + c, y0, y1, y2, y3);
           out_op4<TM>(out + row * 2 * C + C + c, op_rest<TM>(y0), op_rest<TM>(y1), op_rest<TM>(y2), op_rest<TM>(y3));
@@ -588,7 +593,7 @@ hipError_t launch_gn_partial(const float* a0, int lda0, int c0, const float* a1,
 hipError_t launch_gn_apply(const float* a0, int lda0, int c0, const float* a1, int lda1, int c1, int B, int T, int G, float eps,
                            const double* partial, int nchunk, const long long* st0, const long long* st1, const float* gamma,
                            const float* beta, const float* temb, int ldtemb, int temb_off, int silu, void* out_op, void* raw_op,
-                           int prec, hipStream_t s, int pair) {
+                           int prec, hipStream_t s, int pair, const int* lens) {
   const int C = c0 + c1;
   if (C > 1024 || (C & 3) || (c0 & 3) || G > 8 || (pair && prec == PREC_F32)) return hipErrorInvalidValue;
   if (st0 && (((C / G) & 15) || (c0 & 15) || (c1 && !st1))) return hipErrorInvalidValue;
@@ -599,8 +604,13 @@ hipError_t launch_gn_apply(const float* a0, int lda0, int c0, const float* a1, i
   while (rows > 4 * rl && (long)((T + rows - 1) / rows) * B < 1500) rows >>= 1;
   if (rows < 4 * rl) rows = 4 * rl;
   dim3 grid((T + rows - 1) / rows, B);
-  NS2VC_BY_PREC(prec, hipLaunchKernelGGL(gn_apply_kernel<TMX>, grid, dim3(256), 0, s, a0, lda0, c0, a1, lda1, c1, T, G, eps, partial, nchunk,
-                                         st0, st1, gamma, beta, temb, ldtemb, temb_off, silu, (TMX*)out_op, (TMX*)raw_op, rows, pair));
+  if (lens) {
+    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((gn_apply_kernel<TMX, true>), grid, dim3(256), 0, s, a0, lda0, c0, a1, lda1, c1, T, G, eps, partial, nchunk,
+                                           st0, st1, gamma, beta, temb, ldtemb, temb_off, silu, (TMX*)out_op, (TMX*)raw_op, rows, pair, lens));
+  } else {
+    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((gn_apply_kernel<TMX, false>), grid, dim3(256), 0, s, a0, lda0, c0, a1, lda1, c1, T, G, eps, partial, nchunk,
+                                           st0, st1, gamma, beta, temb, ldtemb, temb_off, silu, (TMX*)out_op, (TMX*)raw_op, rows, pair, lens));
+  }
   return hipGetLastError();
 }
 template <typename TM> static hipError_t launch_ln_t(const float* x, int ldx, int M, int C, float eps, TM* out, hipStream_t s) {
@@ -732,6 +742,35 @@ __global__ __launch_bounds__(256) void zero_kernel(uint4* __restrict__ p, size_t
 }
 __global__ __launch_bounds__(256) void copy_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
+}
+// Per-item valid lengths (ns2vc_unet_set_lengths): rows t >= lens[b] of item b of a [B*T] row tensor become exact zeros, so that every
+// convolution halo, GroupNorm sum and attention key past an item's end reads what an unpadded run of that item reads.  One wave per
+// row, 16-byte stores.  With `src` set the kernel instead COPIES row (b, t) from src row (b, t >> up) -- the nearest upsampling
+// (upsamplers.0, resnet.py Upsample1D) materialised with its padded rows zeroed: the fused stride-1/2 upsampling conv would read
+// source row L >> 1 (a valid row for odd L) as the halo of output row L - 1.
+__global__ __launch_bounds__(256) void mask_rows_kernel(uint4* __restrict__ dst, size_t ldd16, const uint4* __restrict__ src, size_t lds16, int row16,
+                                                        int B, int T, int Tsrc, int up, const int* __restrict__ lens) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= B * T) return;
+  const int b = row / T, t = row - b * T;
+  const bool valid = t < lens[b];
+  if (valid && !src) return;
+  uint4* d = dst + (size_t)row * ldd16;
+  if (valid) {
+    const uint4* sp = src + ((size_t)b * Tsrc + (t >> up)) * lds16;
+    for (int i = lane; i < row16; i += 64) d[i] = sp[i];
+  } else {
+    for (int i = lane; i < row16; i += 64) d[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+hipError_t launch_mask_rows(void* dst, size_t ldd_bytes, size_t row_bytes, int B, int T, const int* lens, hipStream_t s, const void* src,
+                            size_t lds_bytes, int Tsrc, int up) {
+  if (!dst || !lens || B <= 0 || T <= 0 || ((uintptr_t)dst & 15) || (ldd_bytes & 15) || (row_bytes & 15) || row_bytes > ldd_bytes) return hipErrorInvalidValue;
+  if (src && (((uintptr_t)src & 15) || (lds_bytes & 15) || row_bytes > lds_bytes || Tsrc <= 0 || up < 0 || up > 1 || ((T - 1) >> up) >= Tsrc)) return hipErrorInvalidValue;
+  const int rows = B * T;
+  hipLaunchKernelGGL(mask_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (uint4*)dst, ldd_bytes / 16, (const uint4*)src, lds_bytes / 16,
+                     (int)(row_bytes / 16), B, T, Tsrc, up, lens);
+  return hipGetLastError();
 }
 hipError_t launch_zero(void* p, size_t bytes, hipStream_t s, int* counter) {
   if (((uintptr_t)p & 15) != 0) return hipErrorInvalidValue;

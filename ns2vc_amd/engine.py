@@ -197,6 +197,7 @@ class Engine:
         check(self.lib.ns2vc_unet_create(C.byref(c), C.byref(h)), "ns2vc_unet_create")
         self.h = h
         self.shape: Optional[Tuple[int, int, int]] = None
+        self.lengths: Optional[np.ndarray] = None      # per-item valid frames (set_lengths), None = dense
         self.table: Optional[SolverTable] = None
         self._weights_ready = False
         self._debug = False
@@ -272,6 +273,7 @@ class Engine:
     def prepare(self, B: int, T: int, Lp: int) -> None:
         check(self.lib.ns2vc_unet_prepare(self.h, B, T, Lp), "ns2vc_unet_prepare")
         self.shape = (B, T, Lp)
+        self.lengths = None
 
     def workspace_bytes(self) -> int:
         n = C.c_size_t()
@@ -299,6 +301,21 @@ class Engine:
     def set_mask(self, mask=None, stream=None) -> None:
         """only the keep-mask -> additive-bias conversion (None = no mask)"""
         check(self.lib.ns2vc_unet_set_mask(self.h, _ptr(mask), _stream_ptr(stream)), "set_mask")
+
+    def set_lengths(self, lengths=None, stream=None) -> None:
+        """Per-item valid frames of the prepared (B, T) batch: a sequence / array / tensor of B ints in [1, T], or None = dense.  Item b then
+        gives on frames [0, L_b) what it gives alone at T = L_b, and 0 beyond.  Call before set_condition / set_content; prepare() resets it."""
+        if lengths is None:
+            check(self.lib.ns2vc_unet_set_lengths(self.h, None, _stream_ptr(stream)), "set_lengths")
+            self.lengths = None
+            return
+        if hasattr(lengths, "detach"):
+            lengths = lengths.detach().cpu().numpy()
+        a = np.ascontiguousarray(np.asarray(lengths).reshape(-1), dtype=np.int32)
+        if self.shape is not None and a.shape[0] != self.shape[0]:
+            raise ValueError(f"lengths has {a.shape[0]} entries, the prepared batch {self.shape[0]}")
+        check(self.lib.ns2vc_unet_set_lengths(self.h, a.ctypes.data, _stream_ptr(stream)), "set_lengths")
+        self.lengths = a.copy()
 
     def forward(self, x, t, out, stream=None) -> None:
         """x (B,100,T), t (B,) fp32, out (B,100,T): one denoiser evaluation."""

@@ -94,9 +94,12 @@ class _EncSALayer(nn.Module):
         self.layer_norm2 = nn.LayerNorm(c)
         self.ffn = _ConvFFN(c)
 
-    def forward(self, x, keep, key_keep):
+    def forward(self, x, keep, key_keep, halo_keep=None):
         x = (x + self.self_attn(self.layer_norm1(x), key_keep)) * keep
-        return (x + self.ffn(self.layer_norm2(x))) * keep
+        # (the reference feeds LayerNorm(0) = beta at padded frames into the k = 9 conv's halo, so a segment's last 4 frames depend on its
+        #  padding; `halo_keep` zeroes them first, so that a padded segment reads what the conv's zero padding gives it alone)
+        n = self.layer_norm2(x)
+        return (x + self.ffn(n if halo_keep is None else n * halo_keep)) * keep
 
 
 class _Layer(nn.Module):                      # the reference wraps every layer as TransformerEncoderLayer(...).op
@@ -104,8 +107,8 @@ class _Layer(nn.Module):                      # the reference wraps every layer 
         super().__init__()
         self.op = _EncSALayer(c)
 
-    def forward(self, x, keep, key_keep):
-        return self.op(x, keep, key_keep)
+    def forward(self, x, keep, key_keep, halo_keep=None):
+        return self.op(x, keep, key_keep, halo_keep)
 
 
 class _Encoder(nn.Module):
@@ -118,8 +121,8 @@ class _Encoder(nn.Module):
         if speaker:
             self.spk_proj = nn.Conv1d(100, hidden_channels, 1)
 
-    def forward(self, x_bct: torch.Tensor, lengths: torch.Tensor, g: torch.Tensor = None) -> torch.Tensor:
-        """x (B, C, T) -> (B, T, out_channels); frames at or beyond `lengths` come out as zeros"""
+    def forward(self, x_bct: torch.Tensor, lengths: torch.Tensor, g: torch.Tensor = None, exact_lengths: bool = False) -> torch.Tensor:
+        """x (B, C, T) -> (B, T, out_channels); frames at or beyond `lengths` come out as zeros.  ``exact_lengths``: every item as if alone"""
         if g is not None:
             x_bct = x_bct + self.spk_proj(g)
         x = x_bct.transpose(1, 2)
@@ -127,7 +130,7 @@ class _Encoder(nn.Module):
         keep = key_keep[:, :, None].to(x.dtype)
         x = self.pre(x, keep) * keep
         for layer in self.layers:
-            x = layer(x, keep, key_keep)
+            x = layer(x, keep, key_keep, keep if exact_lengths else None)
         return self.layer_norm(self.out_proj(x, keep)) * keep
 
 
@@ -143,15 +146,17 @@ class PreModel(nn.Module):
 
     @torch.no_grad()
     def infer(self, c_padded: torch.Tensor, refer_padded: torch.Tensor, lengths: torch.Tensor, refer_lengths: torch.Tensor,
-              autocast: Optional[torch.dtype] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+              autocast: Optional[torch.dtype] = None, exact_lengths: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """c_padded (B, 256, T) ContentVec features, refer_padded (B, 100, Lp) reference mel, lengths / refer_lengths (B,).
         Returns content (B, 256, T), prompt (B, Lp, 256), prompt_mask (B, Lp) bool -- what ``Denoiser.sample`` takes.
         ``autocast`` = torch.float16 / torch.bfloat16 runs the GEMMs, convolutions and attention of the two encoders with
-        16-bit operands (``torch.autocast``; LayerNorm and the outputs stay fp32) -- the reference's own inference runs fp32."""
+        16-bit operands (``torch.autocast``; LayerNorm and the outputs stay fp32) -- the reference's own inference runs fp32.
+        ``exact_lengths``: the content of item b is what segment b gives ALONE (its conv feed-forward reads zeros past its end); the default
+        keeps the reference's batched arithmetic, where padding reaches a segment's last frames.  Prompts are not affected (one Lp per batch)."""
         with torch.autocast(c_padded.device.type, dtype=autocast, enabled=autocast is not None):
             g = self.ref_enc(refer_padded.transpose(1, 2)).unsqueeze(-1)               # (B, 100, 1)
             prompt = self.prompt_encoder(refer_padded, refer_lengths)
-            content = self.phoneme_encoder(c_padded, lengths, g).transpose(1, 2)
+            content = self.phoneme_encoder(c_padded, lengths, g, exact_lengths).transpose(1, 2)
         mask = torch.arange(refer_padded.shape[2], device=refer_padded.device)[None, :] < refer_lengths[:, None]
         return content.float().contiguous(), prompt.float().contiguous(), mask
 

@@ -213,16 +213,17 @@ class Denoiser:
         self.serving_fp32 = False
         self._attn_checked = False
 
-    def _self_check(self, points, c32, p32, mask, stream, keep_fp32: bool) -> None:
+    def _self_check(self, points, c32, p32, mask, stream, keep_fp32: bool, lengths=None) -> None:
         """once per set of weights: the same evaluations on the 16-bit and on the fp32 engine (class docstring, ``precision_check``);
-        ``points`` = [(x, t)] with x (B,100,T) fp32 and t (B,) fp32"""
+        ``points`` = [(x, t)] with x (B,100,T) fp32 and t (B,) fp32.  With ``lengths`` both engines return exact zeros past every item's
+        end, so the per-utterance figures cover its valid frames only."""
         import torch
         if self.precision_check is None or self._precision_checked:
             return
         self._precision_checked = True
         e32 = self._fp32_engine()
-        self.engine.set_condition(c32, p32, mask, stream=stream)
-        e32.set_condition(c32, p32, mask, stream=stream)
+        self._condition(self.engine, c32, p32, mask, stream, lengths)
+        self._condition(e32, c32, p32, mask, stream, lengths)
         self.precision_errors = []
         err, worst = 0.0, 0.0
         for x, t in points:
@@ -250,6 +251,12 @@ class Denoiser:
             self._tail_shape = None
             self._tail_table_key = None
 
+    @staticmethod
+    def _condition(eng, c32, p32, mask, stream, lengths) -> None:
+        """per-item valid frames (None = dense) first -- the content's padded frames are zeroed by set_condition -- then the condition"""
+        eng.set_lengths(lengths, stream=stream)
+        eng.set_condition(c32, p32, mask, stream=stream)
+
     def _trajectory_points(self, x_T, use_graph, stream):
         """(x_e, t) at the first, middle and last evaluation of the loaded table, from a preliminary loop on the 16-bit engine
         (its condition must be set)"""
@@ -270,8 +277,10 @@ class Denoiser:
         self.engine.sample_end(scratch, stream=stream)
         return pts
 
-    def denoise(self, x, t, content, prompt, prompt_mask=None):
-        """One evaluation: x (B,100,T), t (B,), content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool -> x0_pred."""
+    def denoise(self, x, t, content, prompt, prompt_mask=None, lengths=None):
+        """One evaluation: x (B,100,T), t (B,), content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool -> x0_pred.
+        ``lengths`` (B,) ints in [1, T] or None: item b is a segment of lengths[b] frames padded to T (``Engine.set_lengths``); its
+        result on those frames is what it gives alone, and 0 beyond."""
         import torch
         B, _, T = x.shape
         self._guard_before()
@@ -279,9 +288,9 @@ class Denoiser:
         s = torch.cuda.current_stream(x.device)
         mask = None if prompt_mask is None else prompt_mask.to(torch.uint8).contiguous()
         c32, p32, x32, t32 = content.float().contiguous(), prompt.float().contiguous(), x.float().contiguous(), t.float().contiguous()
-        self._self_check([(x32, t32)], c32, p32, mask, s, keep_fp32=bool(self.tail_fp32))
+        self._self_check([(x32, t32)], c32, p32, mask, s, keep_fp32=bool(self.tail_fp32), lengths=lengths)
         eng = self._fp32_engine() if self.serving_fp32 else self.engine
-        eng.set_condition(c32, p32, mask, stream=s)
+        self._condition(eng, c32, p32, mask, s, lengths)
         out = torch.empty_like(x, dtype=torch.float32)
         first_attn = not self.serving_fp32 and not self._attn_checked and self.attn_fallback_limit is not None
         if first_attn:
@@ -289,15 +298,16 @@ class Denoiser:
         eng.forward(x32, t32, out, stream=s)
         if self.serving_fp32:
             return out
-        redone = self._guard_after(s, lambda: self.denoise(x, t, content, prompt, prompt_mask))
+        redone = self._guard_after(s, lambda: self.denoise(x, t, content, prompt, prompt_mask, lengths))
         if first_attn and redone is None:
             self._attn_check(1, s)                            # (after the guard's read-out: a switch drops the plan)
         return out if redone is None else redone
 
     def sample(self, content, prompt, prompt_mask=None, noise=None, solver: str = "unipc", steps: int = 20, order: int = 2,
-               use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None):
+               use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None):
         """content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool; ``noise`` (B,100,T) = x_T (drawn with
         torch.randn like model.py:635 if None).  Returns the sampled latent (B,100,T) fp32.
+        ``lengths`` (B,) ints in [1, T] or None: per-item valid frames of a padded batch (see ``denoise``); x_T is zeroed past them.
         ``tail_fp32`` overrides the instance's setting for this call (see the class docstring)."""
         import torch
         B, _, T = content.shape
@@ -316,27 +326,27 @@ class Denoiser:
         mask = None if prompt_mask is None else prompt_mask.to(device=dev, dtype=torch.uint8).contiguous()
         c32, p32 = content.float().contiguous(), prompt.float().contiguous()
         if self.precision_check is not None and not self._precision_checked:
-            self.engine.set_condition(c32, p32, mask, stream=s)
-            self._self_check(self._trajectory_points(x, use_graph, s), c32, p32, mask, s, keep_fp32=n_tail > 0)
+            self._condition(self.engine, c32, p32, mask, s, lengths)
+            self._self_check(self._trajectory_points(x, use_graph, s), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths)
         tail = self._tail(solver, steps, order, n_tail)
         if self.serving_fp32:            # a failed precision check: the whole loop on the fp32 engine
-            tail.set_condition(c32, p32, mask, stream=s)
+            self._condition(tail, c32, p32, mask, s, lengths)
             tail.sample(x, use_graph=use_graph, stream=s)
             return x
-        self.engine.set_condition(c32, p32, mask, stream=s)
+        self._condition(self.engine, c32, p32, mask, s, lengths)
         if tail is not None:
-            tail.set_condition(c32, p32, mask, stream=s)
+            self._condition(tail, c32, p32, mask, s, lengths)
         first_attn = not self._attn_checked and self.attn_fallback_limit is not None
         if first_attn:
             self.engine.attn_fallbacks(reset=True, stream=s)      # count this loop alone (the self-check's evaluations are behind us)
         self.engine.sample(x, use_graph=use_graph, stream=s, tail=tail, tail_steps=n_tail if tail is not None else 0)
         redone = self._guard_after(s, lambda: self.sample(content, prompt, prompt_mask, noise, solver, steps, order, use_graph,
-                                                          tail_fp32=tail_fp32))
+                                                          tail_fp32=tail_fp32, lengths=lengths))
         if first_attn and redone is None:
             self._attn_check(steps - (n_tail if tail is not None else 0), s)      # (after the guard's read-out: a switch drops the plan)
         return x if redone is None else redone
 
-    def sample_sharded(self, content, prompt, prompt_mask, noise, **kw):
+    def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, **kw):
         """Data-parallel: every rank receives the GLOBAL batch description, runs its contiguous slice and the
         finished latents are all-gathered (RCCL).  The noise is drawn for the global batch and sliced, so an utterance's
         result does not depend on the world size beyond the precision's rounding noise (fp32: ~1e-6; 16-bit: a shard of
@@ -351,7 +361,8 @@ class Denoiser:
             local = torch.zeros((0, self.cfg.latent_channels, content.shape[2]), dtype=torch.float32, device=content.device)
         else:
             pm = None if prompt_mask is None else prompt_mask[lo:hi]
-            local = self.sample(content[lo:hi], prompt[lo:hi], pm, noise[lo:hi], **kw)
+            ln = None if lengths is None else lengths[lo:hi]
+            local = self.sample(content[lo:hi], prompt[lo:hi], pm, noise[lo:hi], lengths=ln, **kw)
         return _dist.gather_latents(local, n)
 
 
@@ -432,7 +443,8 @@ class OverlappedPipeline:
                         v.record_stream(self.s_den)
                         if v.device != self.device:          # front end on another device: peer copy, ordered behind its event on the denoiser's stream
                             cond[k_] = v.to(self.device, non_blocking=True)
-                latent = self.denoiser.sample(cond["content"], cond["prompt"], cond.get("prompt_mask"), cond.get("noise"), **self.kw)
+                latent = self.denoiser.sample(cond["content"], cond["prompt"], cond.get("prompt_mask"), cond.get("noise"), lengths=cond.get("lengths"),
+                                              **self.kw)
                 ev_den = torch.cuda.Event()
                 ev_den.record(self.s_den)
             with torch.cuda.device(self.post_device), torch.cuda.stream(self.s_post):

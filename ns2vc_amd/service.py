@@ -11,6 +11,11 @@ The reference's ``Svc.infer`` (``inference/infer_tool.py:189-206``) converts ONE
   EQUAL shapes keeps every segment's result what the reference's batch-1 call gives, to within the precision's rounding
   noise.  A conversion job normally shares ONE reference clip over all its segments (``infer.py:92-122``: the segment loop sits inside the loop over reference clips), so Lp rarely
   splits a group.
+* ``ragged=True``: segments are grouped by prompt length only, sorted longest first and packed into batches of at most
+  ``max_batch``, each padded to its longest segment.  The denoiser runs the batch with per-item lengths
+  (``Denoiser.sample(lengths=...)``, ``ns2vc_unet_set_lengths``): every GroupNorm statistic, self-attention softmax and
+  convolution halo sees an item's own frames only, so a segment's result is what it gives alone, to the precision's rounding.
+  Each segment's x_T is drawn as in the default mode, at its own length, then zero-padded.
 * each group runs ``PreModel.infer`` -> ``Denoiser.sample`` -> ``decode_fn`` through ``OverlappedPipeline``: the
   PyTorch-ROCm front / back end of group k+1 / k-1 overlaps the HIP denoiser of group k on their own streams.
 
@@ -48,14 +53,26 @@ def segment_from_audio(content_encoder, wav16k: torch.Tensor, samples_at_target_
 
 
 class GroupedConverter:
+    ragged = False      # the default mode (exact-shape groups), also for an instance that only plans (built without __init__)
+
     def __init__(self, pre_model: PreModel, denoiser: Denoiser, decode_fn: Optional[Callable] = None, max_batch: int = 32,
-                 solver: str = "unipc", steps: int = 30, order: int = 2, seed: int = 1234):
+                 solver: str = "unipc", steps: int = 30, order: int = 2, seed: int = 1234, ragged: bool = False):
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
-        self.max_batch, self.seed = max_batch, seed
+        self.max_batch, self.seed, self.ragged = max_batch, seed, ragged
         self.kw = dict(solver=solver, steps=steps, order=order)
 
     def plan(self, segments: Sequence[Segment]) -> List[List[int]]:
-        """indices of `segments` grouped by (latent length, prompt length), groups of at most ``max_batch``, longest first"""
+        """indices of `segments` grouped by (latent length, prompt length), groups of at most ``max_batch``, longest first;
+        ``ragged``: grouped by prompt length only, each group's segments longest first (stable), cut into batches of at most ``max_batch``"""
+        if self.ragged:
+            by_lp: Dict[int, List[int]] = defaultdict(list)
+            for i, s in enumerate(segments):
+                by_lp[int(s.refer.shape[-1])].append(i)
+            groups = []
+            for lp in sorted(by_lp, reverse=True):
+                idx = sorted(by_lp[lp], key=lambda i: -int(segments[i].content.shape[-1]))
+                groups += [idx[k:k + self.max_batch] for k in range(0, len(idx), self.max_batch)]
+            return groups
         by_len: Dict[tuple, List[int]] = defaultdict(list)
         for i, s in enumerate(segments):
             by_len[(int(s.content.shape[-1]), int(s.refer.shape[-1]))].append(i)
@@ -71,6 +88,8 @@ class GroupedConverter:
         groups = self.plan(segments)
 
         def pre_fn(idx):
+            if self.ragged:
+                return ragged_pre(idx)
             T, Lp = int(segments[idx[0]].content.shape[-1]), int(segments[idx[0]].refer.shape[-1])
             c = torch.stack([segments[i].content.to(dev, torch.float32) for i in idx])
             refer = torch.stack([segments[i].refer.to(dev, torch.float32) for i in idx])
@@ -79,7 +98,24 @@ class GroupedConverter:
             noise = torch.stack([torch.randn((self.den.cfg.latent_channels, T), generator=torch.Generator().manual_seed(self.seed + i)) for i in idx]).to(dev)
             return {"content": content, "prompt": prompt, "prompt_mask": mask, "noise": noise}
 
+        def ragged_pre(idx):
+            lens = [int(segments[i].content.shape[-1]) for i in idx]
+            T, Lp = max(lens), int(segments[idx[0]].refer.shape[-1])
+            c = torch.zeros((len(idx), segments[idx[0]].content.shape[0], T), dtype=torch.float32, device=dev)
+            noise = torch.zeros((len(idx), self.den.cfg.latent_channels, T), dtype=torch.float32)
+            for b, i in enumerate(idx):
+                c[b, :, :lens[b]] = segments[i].content.to(dev, torch.float32)
+                # x_T per SEGMENT at its own length (as in the default mode), zero-padded: its result does not depend on its batch
+                noise[b, :, :lens[b]] = torch.randn((self.den.cfg.latent_channels, lens[b]), generator=torch.Generator().manual_seed(self.seed + i))
+            refer = torch.stack([segments[i].refer.to(dev, torch.float32) for i in idx])
+            content, prompt, mask = self.pre.infer(c, refer, torch.tensor(lens, device=dev), torch.full((len(idx),), Lp, device=dev),
+                                                   exact_lengths=True)
+            return {"content": content, "prompt": prompt, "prompt_mask": mask, "noise": noise.to(dev), "lengths": lens}
+
         def post_fn(latent, idx):
+            if self.ragged:     # one tensor per segment, cut to its own frames
+                lat = [latent[b, :, :int(segments[i].content.shape[-1])] for b, i in enumerate(idx)]
+                return lat if self.decode is None else [self.decode(x[None])[0] for x in lat]
             return latent if self.decode is None else self.decode(latent)
 
         outs = OverlappedPipeline(self.den, pre_fn, post_fn, **self.kw).run(groups)

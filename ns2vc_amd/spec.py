@@ -233,6 +233,17 @@ def level_lengths(T: int, n_levels: int) -> List[int]:
     return out
 
 
+def item_level_lengths(lengths, T: int, n_levels: int) -> List[List[int]]:
+    """Valid frames per (level, batch item) of a batch padded to ``T`` frames whose item b holds ``lengths[b]`` (1 <= L <= T): the
+    table ``ns2vc_unet_set_lengths`` derives, row l = ``level_lengths(L, n_levels)[l]`` of every item."""
+    lens = [int(L) for L in lengths]
+    for b, L in enumerate(lens):
+        if not 1 <= L <= T:
+            raise ValueError(f"lengths[{b}] = {L} outside [1, T = {T}]")
+    per_item = [level_lengths(L, n_levels) for L in lens]
+    return [[p[l] for p in per_item] for l in range(n_levels)]
+
+
 def frames_for_seconds(seconds: float, sr: int = 24000, hop: int = 256) -> int:
     """Vocos mel frames for an utterance: floor(sr*s/hop)+1."""
     return int(sr * seconds) // hop + 1

@@ -1,0 +1,71 @@
+"""Throughput of a mixed-length conversion job (32 segments, lengths spread over 470..938 frames, UniPC-20, fp16, captured loop), three ways:
+  (a) dense     -- one B = 32 batch, every segment 938 frames (the benchmark's best case);
+  (b) ragged    -- one B = 32 batch padded to 938 with per-item lengths (ns2vc_unet_set_lengths);
+  (c) per-shape -- equal-shape grouping without padding, which for 32 distinct lengths is 32 batch-1 loops.
+Each figure is the median of `--reps` timed sampling loops (hipGraph replays, condition set outside the timing) after a warm-up loop.
+Usage: python tools/ragged_bench.py [--reps 5] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    import torch
+    from ns2vc_amd.engine import Engine
+    from ns2vc_amd.weights import hash_normal, procedural_state_dict
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    B, T, Lp = 32, 938, 469
+    lens = [int(v) for v in np.linspace(470, 938, B).round()]
+    dev = torch.device("cuda", 0)
+    c = torch.from_numpy(hash_normal("rb.c", (B, 256, T))).to(dev)
+    p = torch.from_numpy(hash_normal("rb.p", (1, Lp, 256))).expand(B, -1, -1).contiguous().to(dev)
+    xT = torch.from_numpy(hash_normal("rb.x", (B, 100, T))).to(dev)
+    e = Engine(precision="fp16")
+    e.load_state_dict(procedural_state_dict(seed=0))
+
+    def loop_ms(bsz, tl, lengths=None, sl=slice(None)):
+        if e.shape != (bsz, tl, Lp):
+            e.prepare(bsz, tl, Lp)
+            e.load_sampler("unipc", a.steps)
+        e.set_lengths(lengths)
+        e.set_condition(c[sl, :, :tl].contiguous(), p[sl].contiguous(), None)
+        x0 = xT[sl, :, :tl].contiguous()
+        x = x0.clone()
+        e.sample(x, use_graph=True)            # capture + warm-up
+        ts = []
+        for _ in range(a.reps):
+            x.copy_(x0)
+            s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s0.record()
+            e.sample(x, use_graph=True)
+            s1.record()
+            torch.cuda.synchronize()
+            ts.append(s0.elapsed_time(s1))
+        return float(np.median(ts))
+
+    dense = loop_ms(B, T)
+    ragged = loop_ms(B, T, lens)
+    per = sum(loop_ms(1, L, None, slice(i, i + 1)) for i, L in enumerate(lens))
+    e.close()
+    r = {"segments": B, "lengths": [min(lens), max(lens)], "solver": f"unipc-{a.steps}", "precision": "fp16",
+         "a_dense_ms": round(dense, 3), "b_ragged_ms": round(ragged, 3), "c_per_shape_ms": round(per, 3),
+         "b_over_a": round(ragged / dense, 3), "c_over_b": round(per / ragged, 2),
+         "ms_per_step": {"a": round(dense / a.steps, 3), "b": round(ragged / a.steps, 3), "c": round(per / a.steps, 3)}}
+    line = json.dumps(r)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
