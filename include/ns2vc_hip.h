@@ -155,7 +155,14 @@ int ns2vc_sampler_run(ns2vc_unet* h, float* x_inout_bct, int use_graph, void* st
 int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream);
 int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream);
 int ns2vc_sampler_end(ns2vc_unet* h, float* x_out_bct, void* stream);
-int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream);   /* both engines must hold the SAME table (compared by hash) */
+int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream);   /* both engines must hold the SAME table (compared by hash); the seeds go along */
+/* Stochastic samplers (backward-compatible addition to ABI v7): DDPM and DDIM with eta > 0 (ns2vc_amd.schedule.build_table) put a nonzero
+ * noise coefficient in column 9 of a table row; the update then adds noise * z, z drawn on the device by Philox4x32-10 keyed by the item's
+ * seed with counter (t, c / 4, step, 0) (ns2vc_amd/noise.py states the stream), on frames t < L_b and channels c < latent_channels only.
+ * A row whose coefficient is 0 adds nothing, so noise-free tables keep their bits.  seeds_b = HOST array [B] of 64-bit seeds, copied on
+ * `stream` from pinned staging (a captured step graph stays valid; seeds_b may be reused on return).  ns2vc_unet_prepare clears them, and
+ * ns2vc_sampler_begin refuses a stochastic table without them.  Stochastic tables never run the update in conv_out's epilogue (fuse_solver). */
+int ns2vc_sampler_set_seeds(ns2vc_unet* h, const uint64_t* seeds_b, void* stream);
 /* x_e of a loop in progress (the point the next evaluation is taken at) without ending the loop: what a precision self-check
  * evaluates two engines on (ns2vc_amd.pipeline.Denoiser) */
 int ns2vc_sampler_peek(ns2vc_unet* h, float* x_out_bct, void* stream);
@@ -440,6 +447,9 @@ int ns2vc_k_groupnorm_stats2(const float* a0, int lda0, int c0, const long long*
 int ns2vc_k_layernorm_apply(const float* x, int ldx, int M, int C, float eps, void* out_op, int precision, void* stream);
 int ns2vc_k_nct_to_btc(const float* src, int C, int T, int B, float* dst, int ldd, int cpad, void* stream);
 int ns2vc_k_btc_to_nct(const float* src, int lds, int C, int T, int B, float* dst, void* stream);
+/* the normals a stochastic update adds at table row `step`: out = fp32 rows [B*T][ld] (ld % 4 == 0) channels-last, out[(b*T + t)*ld + c] = z for
+ * c < C and t < lens_dev[b] (lens_dev = DEVICE [B] or NULL = all T), 0 elsewhere; seeds_dev = DEVICE [B] */
+int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -239,6 +239,35 @@ __device__ __forceinline__ void solver_upd(const SolverCoef& k, float vx0, float
   oxb = nb; od1 = nd; oxe = nb - k.pc * nd; om = m;
 }
 
+// Device noise of the stochastic samplers (DDPM, DDIM with eta > 0; ns2vc_amd/noise.py is the host statement of the stream):
+// Philox4x32-10 (Salmon et al., SC 2011) keyed by the item's 64-bit seed, counter (t, c / 4, step, 0) -> the four normals of
+// channels 4q..4q+3 at frame t by two Box-Muller pairs.  Precise logf / sincosf (not the __ intrinsics): the host agrees to ulps.
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+    const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
+    const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
+    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+  }
+  return c;
+}
+__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
+  const float u1 = ((float)a + 1.0f) * 0x1p-32f;       // (0, 1]: r stays finite
+  const float u2 = (float)b * 0x1p-32f;
+  const float r = sqrtf(-2.0f * logf(u1));
+  float sn, cs;
+  sincosf(u2 * 6.2831853071795864769f, &sn, &cs);
+  z0 = r * cs; z1 = r * sn;
+}
+__device__ __forceinline__ float4 philox_gauss4(unsigned long long seed, uint32_t t, uint32_t q, uint32_t step) {
+  const uint4 x = philox4x32_10(make_uint4(t, q, step, 0u), (uint32_t)seed, (uint32_t)(seed >> 32));
+  float4 z;
+  box_muller(x.x, x.y, z.x, z.y);
+  box_muller(x.z, x.w, z.z, z.w);
+  return z;
+}
+
 constexpr double GN_SUM_SCALE = 268435456.0;   // 2^28
 constexpr double GN_SQ_SCALE = 65536.0;        // 2^16
 
@@ -306,9 +335,15 @@ hipError_t launch_pool_cls(float* seq, int B, int L, int C, const float* pos, hi
 hipError_t launch_pool_attn(const float* qkv, int B, int L1, int C, int heads, float* pooled, hipStream_t s);
 hipError_t launch_pool_proj(const float* pooled, int B, int C, const float* wt, const float* b, int E,
                             const float* gamma, const float* beta, float eps, float* out, hipStream_t s);
+// noise (optional): column 9 of the table row; where it is nonzero, state element (b, t, c) of rows of `ld` columns gains noise * z with
+// z = philox_gauss4(seeds[b], t, c / 4, step), for c < nc and t < lens[b] (lens NULL: every t < T) -- the other elements get nothing
+struct SolverNoise { const unsigned long long* seeds = nullptr; const int* lens = nullptr; int T = 0, ld = 0, nc = 0; };
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0,
                                 float* xe, void* xe_op, int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s,
-                                int split = 0);                 // split > 0 (16-bit): xe_op rows are [hi(split) | lo(split)] of state rows of `split` columns
+                                int split = 0,                  // split > 0 (16-bit): xe_op rows are [hi(split) | lo(split)] of state rows of `split` columns
+                                const SolverNoise& noise = SolverNoise());
+// the normals a stochastic update adds at table row `step` (ns2vc_k_noise): out rows [B*T][ld] fp32, zeros where no noise goes
+hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s);
 hipError_t launch_fill_i32(int* p, int v, hipStream_t s);
 hipError_t launch_placement(unsigned* dev_out, int n_blocks, int spin, hipStream_t s);
 hipError_t launch_snapshot_u32(unsigned* src, unsigned* dst, hipStream_t s);   // *dst = atomicExch(src, 0)

@@ -230,6 +230,16 @@ struct ns2vc_unet {
   size_t lens_stage_bytes = 0;
   hipEvent_t lens_event = nullptr;
   bool lens_staged = false;
+  // Per-item noise seeds of the stochastic samplers (ns2vc_sampler_set_seeds): a buffer of its own (the captured step graph reads it, so new
+  // seeds are a copy into it), pinned staging + event as for the lengths.  `stochastic`: the loaded table has a nonzero noise column.
+  unsigned long long* seeds_dev = nullptr;
+  int seeds_cap = 0;
+  bool seeds_set = false;                  // set since the last prepare
+  void* seeds_stage = nullptr;
+  int seeds_stage_cap = 0;
+  hipEvent_t seeds_event = nullptr;
+  bool seeds_staged = false;
+  bool stochastic = false;
 
   // named persistent buffers
   float *xe = nullptr, *xbar = nullptr, *d1 = nullptr, *mprev = nullptr, *x0 = nullptr;
@@ -259,6 +269,10 @@ struct ns2vc_unet {
     if (lens_staged) (void)hipEventSynchronize(lens_event);
     if (lens_event) (void)hipEventDestroy(lens_event);
     if (lens_stage) (void)hipHostFree(lens_stage);
+    if (seeds_staged) (void)hipEventSynchronize(seeds_event);
+    if (seeds_event) (void)hipEventDestroy(seeds_event);
+    if (seeds_stage) (void)hipHostFree(seeds_stage);
+    if (seeds_dev) (void)hipFree(seeds_dev);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     if (side_stream) (void)hipStreamDestroy(side_stream);
@@ -1785,6 +1799,7 @@ int ns2vc_unet_prepare(ns2vc_unet* h, int B, int T, int Lp) {
   h->has_mask = false;
   h->masked = false;         // a new shape starts dense (ns2vc_unet_set_lengths)
   h->lens_applied.clear();
+  h->seeds_set = false;      // ... and without noise seeds (ns2vc_sampler_set_seeds)
   if (build_plan(h, true)) return 1;
   HIPCHK(hipMalloc(&h->arena, h->arena_bytes));
   HIPCHK(hipMemset(h->arena, 0, h->arena_bytes));
@@ -1947,6 +1962,44 @@ int ns2vc_sampler_load(ns2vc_unet* h, int steps, const float* coef_host) {
   h->steps = steps;
   h->temb_table_valid = false;
   h->next_step = -1;
+  bool stochastic = false;
+  for (int i = 0; i < steps; ++i) stochastic |= coef_host[(size_t)i * NS2VC_NCOEF + 9] != 0.f;
+  if (stochastic != h->stochastic && h->step_graph) { (void)hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }   // (the update's noise arguments are baked in)
+  h->stochastic = stochastic;
+  return 0;
+}
+
+// a seeds buffer for at least n items; a new one invalidates the captured step graph (its update reads the old pointer)
+static int ensure_seeds(ns2vc_unet* h, int n) {
+  if (h->seeds_dev && h->seeds_cap >= n) return 0;
+  if (h->step_graph) { (void)hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
+  if (h->seeds_dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->seeds_dev)); h->seeds_dev = nullptr; h->seeds_cap = 0; }
+  const int cap = (n + 1) & ~1;            // 16-byte multiple (launch_copy16)
+  HIPCHK(hipMalloc((void**)&h->seeds_dev, (size_t)cap * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(h->seeds_dev, 0, (size_t)cap * sizeof(unsigned long long)));
+  h->seeds_cap = cap;
+  return 0;
+}
+
+int ns2vc_sampler_set_seeds(ns2vc_unet* h, const uint64_t* seeds_b, void* stream) {
+  if (check_ready(h, true)) return 1;
+  if (!seeds_b) return fail("null seeds");
+  hipStream_t s = (hipStream_t)stream;
+  const int B = h->B;
+  if (ensure_seeds(h, B)) return 1;
+  if (!h->seeds_event) HIPCHK(hipEventCreateWithFlags(&h->seeds_event, hipEventDisableTiming));
+  if (h->seeds_staged) { HIPCHK(hipEventSynchronize(h->seeds_event)); h->seeds_staged = false; }
+  if (h->seeds_stage_cap < B) {
+    if (h->seeds_stage) HIPCHK(hipHostFree(h->seeds_stage));
+    h->seeds_stage = nullptr; h->seeds_stage_cap = 0;
+    HIPCHK(hipHostMalloc(&h->seeds_stage, (size_t)h->seeds_cap * sizeof(uint64_t), hipHostMallocDefault));
+    h->seeds_stage_cap = h->seeds_cap;
+  }
+  memcpy(h->seeds_stage, seeds_b, (size_t)B * sizeof(uint64_t));
+  HIPCHK(hipMemcpyAsync(h->seeds_dev, h->seeds_stage, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(h->seeds_event, s));
+  h->seeds_staged = true;
+  h->seeds_set = true;
   return 0;
 }
 
@@ -1957,6 +2010,7 @@ static bool solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
   // (masked plan: the update must see x0 with its padded rows zeroed -- conv_out's epilogue has not zeroed them -- so it stays a launch of its own)
   if (h->masked) return false;
   if (h->conv_out_prec != h->prec) return false;      // (exact_io: conv_out runs in fp32 there, the operand copy of the state is 16-bit)
+  if (h->stochastic) return false;                     // (the epilogue has no noise term: a stochastic table runs the stand-alone update)
   g = h->conv_out_g;
   g.out_f32 = nullptr;
   g.sol_coef = h->coef_dev; g.sol_step = h->step_dev; g.sol_ncoef = NS2VC_NCOEF;
@@ -1989,7 +2043,11 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
     return 0;
   }
   const size_t n = (size_t)h->B * h->T * h->CP;
-  HIPCHK(launch_solver_update(h->coef_dev, h->step_dev, NS2VC_NCOEF, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s, h->prec != PREC_F32 ? h->CP : 0));
+  SolverNoise nz;
+  if (h->stochastic) {       // noise on the item's valid frames and real channels only (masked plan: level-0 lengths = the first B entries)
+    nz.seeds = h->seeds_dev; nz.lens = h->masked ? h->lens_dev : nullptr; nz.T = h->T; nz.ld = h->CP; nz.nc = h->cfg.latent_channels;
+  }
+  HIPCHK(launch_solver_update(h->coef_dev, h->step_dev, NS2VC_NCOEF, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s, h->prec != PREC_F32 ? h->CP : 0, nz));
   return 0;
 }
 
@@ -1999,11 +2057,12 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   if (check_ready(h, true)) return 1;
   if (!x_T_bct) return fail("null tensor");
   if (!h->coef_dev || h->steps <= 0) return fail("no solver table loaded (call ns2vc_sampler_load)");
+  if (h->stochastic && !h->seeds_set) return fail("the loaded solver table adds noise: set per-item seeds first (ns2vc_sampler_set_seeds)");
   hipStream_t s = (hipStream_t)stream;
   const auto& c = h->cfg;
   const size_t n = (size_t)h->B * h->T * h->CP;
   HIPCHK(launch_nct_to_btc(x_T_bct, c.latent_channels, h->T, h->B, h->xe, h->xe_op, h->prec, h->CP, h->CP, s, h->prec != PREC_F32 ? 2 * h->CP : h->CP, h->prec != PREC_F32 ? h->CP : 0));
-  if (mask_state_rows(h, s)) return 1;      // x_T is zero past every item's end; the solver update (linear in its inputs) keeps it so
+  if (mask_state_rows(h, s)) return 1;      // x_T is zero past every item's end; the solver update keeps it so (its noise term skips those rows)
   HIPCHK(launch_copy16(h->xe, h->xbar, n * sizeof(float), s));
   HIPCHK(launch_zero(h->d1, n * sizeof(float), s));
   HIPCHK(launch_zero(h->mprev, n * sizeof(float), s));
@@ -2075,6 +2134,11 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   HIPCHK(launch_copy16(src->d1, dst->d1, n * sizeof(float), s));
   HIPCHK(launch_copy16(src->mprev, dst->mprev, n * sizeof(float), s));
   HIPCHK(launch_cast_op(dst->xe, n, dst->xe_op, dst->prec, s, dst->prec != PREC_F32 ? dst->CP : 0));
+  if (src->seeds_set) {      // the tail continues the same noise stream
+    if (ensure_seeds(dst, src->B)) return 1;
+    HIPCHK(launch_copy16(src->seeds_dev, dst->seeds_dev, (size_t)((src->B + 1) & ~1) * sizeof(unsigned long long), s));
+    dst->seeds_set = true;
+  }
   HIPCHK(launch_fill_i32(dst->step_dev, src->next_step - 1, s));
   dst->next_step = src->next_step;
   src->next_step = -1;
@@ -2548,6 +2612,11 @@ int ns2vc_k_nct_to_btc(const float* src, int C, int T, int B, float* dst, int ld
 int ns2vc_k_btc_to_nct(const float* src, int lds, int C, int T, int B, float* dst, void* stream) {
   hipError_t e = launch_btc_to_nct(src, lds, C, T, B, dst, (hipStream_t)stream);
   if (e != hipSuccess) return fail("btc_to_nct launch: %s", hipGetErrorString(e));
+  return 0;
+}
+int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream) {
+  hipError_t e = launch_noise(reinterpret_cast<const unsigned long long*>(seeds_dev), B, C, T, ld, step, lens_dev, out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail("noise launch: %s", hipGetErrorString(e));
   return 0;
 }
 

@@ -539,9 +539,13 @@ template <typename TM>
 __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
                                                             const float* __restrict__ x0, float* __restrict__ xe, TM* __restrict__ xe_op,
                                                             float* __restrict__ xbar, float* __restrict__ d1,
-                                                            float* __restrict__ mprev, size_t n4, int split) {
+                                                            float* __restrict__ mprev, size_t n4, int split, SolverNoise nz) {
   op_mode_init<TM>();
-  const SolverCoef k = solver_coef(coef + (size_t)(*step_ptr) * ncoef);
+  const int step = *step_ptr;
+  const SolverCoef k = solver_coef(coef + (size_t)step * ncoef);
+  // noise coefficient of this row (column 9): uniform per launch.  0 = no term at all (adding 0*z would turn -0 into +0), so
+  // every noise-free table keeps its bits
+  const float knz = nz.seeds ? coef[(size_t)step * ncoef + 9] : 0.f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     const float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
     const float4 vxe = reinterpret_cast<const float4*>(xe)[i];
@@ -553,6 +557,18 @@ __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restr
     solver_upd(k, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
     solver_upd(k, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
     solver_upd(k, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
+    if (knz != 0.f) {      // xbar' += noise * z on the live elements (the state is zero elsewhere and stays so): ld % 4 == 0, one quad per thread
+      const size_t e = 4 * i, r = e / (size_t)nz.ld;
+      const int c = (int)(e - r * (size_t)nz.ld), b = (int)(r / (size_t)nz.T), t = (int)(r - (size_t)b * nz.T);
+      if (c < nz.nc && (!nz.lens || t < nz.lens[b])) {
+        const float4 z = philox_gauss4(nz.seeds[b], (uint32_t)t, (uint32_t)(c >> 2), (uint32_t)step);
+        oxb.x += knz * z.x;
+        if (c + 1 < nz.nc) oxb.y += knz * z.y;
+        if (c + 2 < nz.nc) oxb.z += knz * z.z;
+        if (c + 3 < nz.nc) oxb.w += knz * z.w;
+        oxe = make_float4(oxb.x - k.pc * od1.x, oxb.y - k.pc * od1.y, oxb.z - k.pc * od1.z, oxb.w - k.pc * od1.w);
+      }
+    }
     out_f4(xe + 4 * i, oxe.x, oxe.y, oxe.z, oxe.w);
     if (split) {                                            // hi + lo operand pair: rows of 2 * split columns, the lo plane `split` columns further
       const size_t r = (4 * i) / (size_t)split;
@@ -566,6 +582,23 @@ __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restr
     out_f4(d1 + 4 * i, od1.x, od1.y, od1.z, od1.w);
     out_f4(mprev + 4 * i, om.x, om.y, om.z, om.w);
   }
+}
+// the normals of ns2vc_k_noise: one thread per (row, channel quad), the same philox_gauss4 the update adds
+__global__ __launch_bounds__(256) void noise_kernel(const unsigned long long* __restrict__ seeds, int B, int nc, int T, int ld, int step,
+                                                    const int* __restrict__ lens, float* __restrict__ out) {
+  const int nq = ld >> 2;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)B * T * nq) return;
+  const size_t r = i / nq;
+  const int c = (int)(i - r * nq) * 4, b = (int)(r / T), t = (int)(r - (size_t)b * T);
+  float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (c < nc && (!lens || t < lens[b])) {
+    z = philox_gauss4(seeds[b], (uint32_t)t, (uint32_t)(c >> 2), (uint32_t)step);
+    if (c + 1 >= nc) z.y = 0.f;
+    if (c + 2 >= nc) z.z = 0.f;
+    if (c + 3 >= nc) z.w = 0.f;
+  }
+  reinterpret_cast<float4*>(out)[i] = z;
 }
 __global__ void fill_i32_kernel(int* p, int v) { if (threadIdx.x == 0 && blockIdx.x == 0) *p = v; }
 // read-and-reset of a device maximum (LayerNorm health, ns2vc_unet_ln_ratio*): stream-ordered with the launches that raise it
@@ -720,12 +753,19 @@ hipError_t launch_mask_bias(const uint8_t* mask, int n, float* bias, hipStream_t
   return hipGetLastError();
 }
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0, float* xe, void* xe_op, int prec,
-                                float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split) {
+                                float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise) {
   if ((n & 3) || (split && (prec == PREC_F32 || (split & 3) || n % (size_t)split))) return hipErrorInvalidValue;
+  if (noise.seeds && (noise.ld <= 0 || (noise.ld & 3) || noise.T <= 0 || noise.nc > noise.ld || n % ((size_t)noise.ld * noise.T))) return hipErrorInvalidValue;
   const size_t n4 = n >> 2;
   const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
   NS2VC_BY_PREC(prec, hipLaunchKernelGGL(solver_update_kernel<TMX>, dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op,
-                                         xbar, d1, mprev, n4, split));
+                                         xbar, d1, mprev, n4, split, noise));
+  return hipGetLastError();
+}
+hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s) {
+  if (!seeds || !out || B <= 0 || T <= 0 || ld <= 0 || (ld & 3) || nc < 0 || nc > ld || step < 0) return hipErrorInvalidValue;
+  const size_t nth = (size_t)B * T * (ld >> 2);
+  hipLaunchKernelGGL(noise_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s, seeds, B, nc, T, ld, step, lens, out);
   return hipGetLastError();
 }
 // Plain kernels for clearing / copying workspace buffers.  The step loop is replayed from a captured hipGraph; memset /

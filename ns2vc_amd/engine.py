@@ -317,12 +317,24 @@ class Engine:
         check(self.lib.ns2vc_unet_set_lengths(self.h, a.ctypes.data, _stream_ptr(stream)), "set_lengths")
         self.lengths = a.copy()
 
+    def set_seeds(self, seeds, stream=None) -> None:
+        """(B,) 64-bit seeds of the per-item noise streams of a stochastic table (ns2vc_amd.noise), for the prepared batch;
+        cleared by ``prepare``.  Asynchronous on ``stream``: a captured step graph stays valid."""
+        if hasattr(seeds, "detach"):
+            seeds = seeds.detach().cpu().numpy()
+        a = np.ascontiguousarray(np.asarray(seeds).reshape(-1).astype(np.uint64))
+        if self.shape is None or a.shape[0] != self.shape[0]:
+            raise ValueError(f"seeds has {a.shape[0]} entries, the prepared batch {None if self.shape is None else self.shape[0]}")
+        check(self.lib.ns2vc_sampler_set_seeds(self.h, a.ctypes.data, _stream_ptr(stream)), "set_seeds")
+
     def forward(self, x, t, out, stream=None) -> None:
         """x (B,100,T), t (B,) fp32, out (B,100,T): one denoiser evaluation."""
         check(self.lib.ns2vc_unet_forward(self.h, _ptr(x), _ptr(t), _ptr(out), _stream_ptr(stream)), "forward")
 
-    def load_sampler(self, solver: str, steps: int, betas: Optional[np.ndarray] = None, order: int = 2) -> SolverTable:
-        table = build_table(solver, steps, betas, order)
+    def load_sampler(self, solver: str, steps: int, betas: Optional[np.ndarray] = None, order: int = 2, eta: float = 0.0) -> SolverTable:
+        """``build_table(solver, steps, betas, order, eta)`` -> the engine.  A stochastic table (``ddpm``, ``ddim`` with eta > 0) needs
+        ``set_seeds`` before the loop begins."""
+        table = build_table(solver, steps, betas, order, eta)
         coef = np.ascontiguousarray(table.coef, dtype=np.float32)
         assert coef.shape == (steps, NCOEF)
         check(self.lib.ns2vc_sampler_load(self.h, steps, coef.ctypes.data_as(C.POINTER(C.c_float))), "sampler_load")

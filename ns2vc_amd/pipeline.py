@@ -14,7 +14,8 @@ import numpy as np
 
 from . import dist as _dist
 from .engine import DEFAULT_PRECISION, Engine
-from .schedule import linear_betas
+from .noise import draw_seeds
+from .schedule import DISCRETE_SOLVERS, SOLVERS, linear_betas
 from .spec import UNetConfig, attention_workgroups_per_forward
 
 
@@ -22,8 +23,11 @@ from .spec import UNetConfig, attention_workgroups_per_forward
 # DPM-Solver++(2M) takes its LAST update at second order over the largest log-SNR step of the schedule (no lower_order_final
 # for steps >= 10, dpm_solver.py:1198-1201), which amplifies the rounding noise of the last two evaluations ~2.7x (50 steps:
 # fp16 1.7e-3 on the sampled latent, with the last two evaluations in fp32 ~2e-4); UniPC-bh2 ends at first order and keeps
-# the single-evaluation noise (8.6e-4 at 20 steps), so it stays pure 16-bit unless asked.
-DEFAULT_TAIL_FP32 = {"dpmsolver++": 2, "unipc": 0}
+# the single-evaluation noise (8.6e-4 at 20 steps), so it stays pure 16-bit unless asked.  DDPM and DDIM end on x_start of their
+# last evaluation (weight ~1), so that evaluation's rounding is the latent's: at the bench shape fp16 DDPM-1000 / DDIM-100 are
+# 7.7e-4 from the fp32 engine with no tail (worst item 8.0e-4), 1.4e-4 / 1.3e-4 with one fp32 evaluation, 6.7e-5 / 7.5e-5 with two
+# (profiles/r08_stochastic.txt): one is the smallest tail that holds the 1e-3 bar with margin.
+DEFAULT_TAIL_FP32 = {"dpmsolver++": 2, "unipc": 0, "ddim": 1, "ddpm": 1}
 # LayerNorm-by-linearity guard thresholds on max |mean|/std (see Denoiser): 16-bit modes lose ~ratio * 2^-11 on a row,
 # fp32 loses ~ratio^2 * 2^-24 in the variance E[x^2] - mean^2
 LN_GUARD_DEFAULT = {"fp16": 8.0, "bf16": 8.0, "fp32": 32.0}
@@ -80,6 +84,8 @@ class Denoiser:
         self.engine.load_state_dict(state)
         self._state = state
         self.betas = linear_betas() if betas is None else np.asarray(betas, dtype=np.float32)
+        # ddim / ddpm index the model's own float32 buffers, which the reference derives from the float64 betas
+        self.betas64 = linear_betas(dtype=np.float64) if betas is None else np.asarray(betas, dtype=np.float64)
         self._shape = None
         self._table_key = None
         self.ln_guard = LN_GUARD_DEFAULT[self.precision] if (ln_guard is not None and ln_guard < 0) else ln_guard
@@ -160,10 +166,13 @@ class Denoiser:
         self._shape = None
         self._table_key = None
 
-    def _table(self, solver: str, steps: int, order: int) -> None:
-        key = (solver, steps, order)
+    def _betas_for(self, solver: str) -> np.ndarray:
+        return self.betas64 if solver in DISCRETE_SOLVERS else self.betas
+
+    def _table(self, solver: str, steps: int, order: int, eta: float = 0.0) -> None:
+        key = (solver, steps, order, eta)
         if self._table_key != key:
-            self.engine.load_sampler(solver, steps, self.betas, order)
+            self.engine.load_sampler(solver, steps, self._betas_for(solver), order, eta)
             self._table_key = key
 
     def _fp32_engine(self) -> Engine:
@@ -182,14 +191,14 @@ class Denoiser:
             self._tail_shape = self._shape
         return self.tail_engine
 
-    def _tail(self, solver: str, steps: int, order: int, n_tail: int) -> Optional[Engine]:
+    def _tail(self, solver: str, steps: int, order: int, n_tail: int, eta: float = 0.0) -> Optional[Engine]:
         """the fp32 engine that finishes a 16-bit loop (or runs all of it after a failed precision check), with the table loaded"""
         if (n_tail <= 0 and not self.serving_fp32) or self.precision == "fp32":
             return None
         e = self._fp32_engine()
-        key = (solver, steps, order)
+        key = (solver, steps, order, eta)
         if self._tail_table_key != key:
-            e.load_sampler(solver, steps, self.betas, order)
+            e.load_sampler(solver, steps, self._betas_for(solver), order, eta)
             self._tail_table_key = key
         return e
 
@@ -303,18 +312,39 @@ class Denoiser:
             self._attn_check(1, s)                            # (after the guard's read-out: a switch drops the plan)
         return out if redone is None else redone
 
-    def sample(self, content, prompt, prompt_mask=None, noise=None, solver: str = "unipc", steps: int = 20, order: int = 2,
-               use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None):
+    def _check_sampler_args(self, solver: str, steps: Optional[int], eta: float, B: int, seeds) -> int:
+        """the argument errors of ``sample``, raised before anything runs; returns the step count"""
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        if eta != 0.0 and solver != "ddim":
+            raise ValueError(f"eta is DDIM's noise scale (ddim_sampling_eta); solver {solver!r} takes none")
+        if eta < 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
+        if steps is None:
+            steps = {"ddim": 100, "ddpm": len(self.betas64)}.get(solver, 20)   # model.py sample(): sampling_timesteps=100; p_sample_loop: every timestep
+        if solver == "ddpm" and steps != len(self.betas64):
+            raise ValueError(f"ddpm runs every timestep of the schedule: steps must be {len(self.betas64)} (or None), got {steps}")
+        if seeds is not None and np.asarray(seeds.detach().cpu() if hasattr(seeds, "detach") else seeds).reshape(-1).shape[0] != B:
+            raise ValueError(f"seeds must hold one seed per item ({B})")
+        return int(steps)
+
+    def sample(self, content, prompt, prompt_mask=None, noise=None, solver: str = "unipc", steps: Optional[int] = None, order: int = 2,
+               use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None):
         """content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool; ``noise`` (B,100,T) = x_T (drawn with
         torch.randn like model.py:635 if None).  Returns the sampled latent (B,100,T) fp32.
+        ``solver``: ``unipc`` | ``dpmsolver++`` (``order`` 1 | 2) or the reference's discrete samplers ``ddim`` (``eta`` =
+        ddim_sampling_eta) | ``ddpm`` (p_sample_loop: steps = every timestep).  ``steps`` None: 20, ddim 100, ddpm len(betas).
+        ``seeds`` (B,) ints: the per-item noise streams of ddpm / ddim with eta > 0 (ns2vc_amd.noise; item b's noise depends on
+        seeds[b] alone), drawn from ``generator`` after x_T if None, so ``generator=`` reproduces a run.
         ``lengths`` (B,) ints in [1, T] or None: per-item valid frames of a padded batch (see ``denoise``); x_T is zeroed past them.
         ``tail_fp32`` overrides the instance's setting for this call (see the class docstring)."""
         import torch
         B, _, T = content.shape
         dev = content.device
+        steps = self._check_sampler_args(solver, steps, eta, B, seeds)
         self._guard_before()
         self._prepare(B, T, prompt.shape[1])
-        self._table(solver, steps, order)
+        self._table(solver, steps, order, eta)
         n_tail = tail_fp32 if tail_fp32 is not None else self.tail_fp32
         if n_tail is None:
             n_tail = DEFAULT_TAIL_FP32.get(solver, 0) if self.precision != "fp32" else 0
@@ -323,12 +353,19 @@ class Denoiser:
             noise = torch.randn((B, self.cfg.latent_channels, T), device=dev, generator=generator)
         x = noise.to(device=dev, dtype=torch.float32).contiguous().clone()
         s = torch.cuda.current_stream(dev)
+        stochastic = bool((self.engine.table.coef[:, 9] != 0).any())
+        if stochastic:
+            if seeds is None:
+                seeds = draw_seeds(B, generator)
+            self.engine.set_seeds(seeds, stream=s)
         mask = None if prompt_mask is None else prompt_mask.to(device=dev, dtype=torch.uint8).contiguous()
         c32, p32 = content.float().contiguous(), prompt.float().contiguous()
         if self.precision_check is not None and not self._precision_checked:
             self._condition(self.engine, c32, p32, mask, s, lengths)
             self._self_check(self._trajectory_points(x, use_graph, s), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths)
-        tail = self._tail(solver, steps, order, n_tail)
+        tail = self._tail(solver, steps, order, n_tail, eta)
+        if tail is not None and stochastic:
+            tail.set_seeds(seeds, stream=s)
         if self.serving_fp32:            # a failed precision check: the whole loop on the fp32 engine
             self._condition(tail, c32, p32, mask, s, lengths)
             tail.sample(x, use_graph=use_graph, stream=s)
@@ -341,14 +378,15 @@ class Denoiser:
             self.engine.attn_fallbacks(reset=True, stream=s)      # count this loop alone (the self-check's evaluations are behind us)
         self.engine.sample(x, use_graph=use_graph, stream=s, tail=tail, tail_steps=n_tail if tail is not None else 0)
         redone = self._guard_after(s, lambda: self.sample(content, prompt, prompt_mask, noise, solver, steps, order, use_graph,
-                                                          tail_fp32=tail_fp32, lengths=lengths))
+                                                          tail_fp32=tail_fp32, lengths=lengths, eta=eta, seeds=seeds))
         if first_attn and redone is None:
             self._attn_check(steps - (n_tail if tail is not None else 0), s)      # (after the guard's read-out: a switch drops the plan)
         return x if redone is None else redone
 
-    def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, **kw):
+    def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, seeds=None, **kw):
         """Data-parallel: every rank receives the GLOBAL batch description, runs its contiguous slice and the
-        finished latents are all-gathered (RCCL).  The noise is drawn for the global batch and sliced, so an utterance's
+        finished latents are all-gathered (RCCL).  The noise (and ``seeds``, for ddpm / ddim with eta > 0: drawn for the global
+        batch from ``generator`` if None) is drawn for the global batch and sliced, so an utterance's
         result does not depend on the world size beyond the precision's rounding noise (fp32: ~1e-6; 16-bit: a shard of
         3 and a shard of 2 round differently, ~7e-4 -- tests/test_dropin_gpu.py::test_sample_sharded_rccl_*)."""
         import torch
@@ -362,7 +400,10 @@ class Denoiser:
         else:
             pm = None if prompt_mask is None else prompt_mask[lo:hi]
             ln = None if lengths is None else lengths[lo:hi]
-            local = self.sample(content[lo:hi], prompt[lo:hi], pm, noise[lo:hi], lengths=ln, **kw)
+            if seeds is None and kw.get("solver") in DISCRETE_SOLVERS:
+                seeds = draw_seeds(n, kw.get("generator"))
+            sd = None if seeds is None else seeds[lo:hi]
+            local = self.sample(content[lo:hi], prompt[lo:hi], pm, noise[lo:hi], lengths=ln, seeds=sd, **kw)
         return _dist.gather_latents(local, n)
 
 
@@ -379,8 +420,8 @@ class OverlappedPipeline:
     blocks until the end of ``run`` -- and the denoiser still replays one captured hipGraph per step on its own stream.
     """
 
-    def __init__(self, denoiser: Denoiser, pre_fn, post_fn, solver: str = "unipc", steps: int = 20, order: int = 2,
-                 use_graph: bool = True, pre_device=None, post_device=None, stage_cus=None, denoiser_cus=None):
+    def __init__(self, denoiser: Denoiser, pre_fn, post_fn, solver: str = "unipc", steps: Optional[int] = 20, order: int = 2,
+                 use_graph: bool = True, pre_device=None, post_device=None, stage_cus=None, denoiser_cus=None, eta: float = 0.0):
         """``pre_device`` / ``post_device`` (r4): run the front / back end on ANOTHER ROCm device of the node.  On one GPU the three streams
         serialise (the denoiser's launches hold every CU: 7.8 % of the stages' kernel time overlaps, profiles/r03_overlap_trace.txt); a stage
         on its own device overlaps by construction and only its tensors cross xGMI -- content + prompt 35 MB per 32 x 10 s batch in, the
@@ -391,7 +432,7 @@ class OverlappedPipeline:
         if not torch.cuda.is_available():
             raise RuntimeError("OverlappedPipeline needs a ROCm device (there is no CPU path)")
         self.denoiser, self.pre_fn, self.post_fn = denoiser, pre_fn, post_fn
-        self.kw = dict(solver=solver, steps=steps, order=order, use_graph=use_graph)
+        self.kw = dict(solver=solver, steps=steps, order=order, use_graph=use_graph, eta=eta)
         dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         self.pre_device = torch.device(pre_device) if pre_device is not None else dev
@@ -444,7 +485,7 @@ class OverlappedPipeline:
                         if v.device != self.device:          # front end on another device: peer copy, ordered behind its event on the denoiser's stream
                             cond[k_] = v.to(self.device, non_blocking=True)
                 latent = self.denoiser.sample(cond["content"], cond["prompt"], cond.get("prompt_mask"), cond.get("noise"), lengths=cond.get("lengths"),
-                                              **self.kw)
+                                              seeds=cond.get("seeds"), **self.kw)
                 ev_den = torch.cuda.Event()
                 ev_den.record(self.s_den)
             with torch.cuda.device(self.post_device), torch.cuda.stream(self.s_post):

@@ -24,6 +24,17 @@ Unified recurrence executed by the engine after the i-th denoiser evaluation
 with xbar = xe = x_T, d1 = m_prev = 0 before the first evaluation.  After the
 last evaluation ``xe'`` is the sample.  For DPM-Solver++(2M): g0 = previous pc,
 g1 = 0.  For UniPC: g0 = alpha_t*B_h*rho_0, g1 = alpha_t*B_h*rho_1, pc = alpha*B_h/2.
+
+The two discrete samplers of the reference (model.py: ``ddim_sample``, ``p_sample_loop`` / ``p_sample``) are first-order
+rows of the same recurrence (g0 = g1 = d1c = pc = 0, so xe' = xbar' = A*xe - Bc*m), plus a Gaussian term:
+
+    xbar' += noise * z        z = ns2vc_amd.noise.gauss(seed_b, i, ...)  (the engine draws it on the device)
+
+  DDIM   A = c*sqrt(1/a)/sqrt(1/a - 1),  Bc = c/sqrt(1/a - 1) - sqrt(a_next),  noise = eta*sqrt((1 - a/a_next)(1 - a_next)/(1 - a)),
+         c = sqrt(1 - a_next - noise^2), a = alphas_cumprod[time]; the final pair (0, -1) returns x_start (A = 0, Bc = -1)
+  DDPM   A = posterior_mean_coef2[t], Bc = -posterior_mean_coef1[t], noise = exp(0.5*posterior_log_variance_clipped[t]) (0 at t = 0)
+
+A row with noise == 0 adds nothing at all (not 0*z), so every noise-free table keeps its bits.
 """
 from __future__ import annotations
 
@@ -33,15 +44,17 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 # column layout of the per-step coefficient table (float32, NCOEF per row)
-COEF_COLUMNS = ("t_model", "alpha", "sigma", "g0", "g1", "A", "Bc", "d1c", "pc", "_pad0", "_pad1", "_pad2")
+COEF_COLUMNS = ("t_model", "alpha", "sigma", "g0", "g1", "A", "Bc", "d1c", "pc", "noise", "_pad1", "_pad2")
 NCOEF = len(COEF_COLUMNS)
-SOLVERS = ("dpmsolver++", "unipc")
+SOLVERS = ("dpmsolver++", "unipc", "ddim", "ddpm")
+DISCRETE_SOLVERS = ("ddim", "ddpm")      # tables over the integer timesteps of the model's own buffers; `order` does not apply
 
 
-def linear_betas(n: int = 1000) -> np.ndarray:
-    """reference model.py:426-433: linspace in float64, stored as a float32 buffer (:471-473)."""
+def linear_betas(n: int = 1000, dtype=np.float32) -> np.ndarray:
+    """reference model.py:426-433: linspace in float64, stored as a float32 buffer (:471-473).  ``dtype=np.float64``: the
+    betas the reference derives its other buffers from (alphas_cumprod, the posterior coefficients) before storing them."""
     scale = 1000.0 / n
-    return np.linspace(scale * 1e-4, scale * 0.02, n, dtype=np.float64).astype(np.float32)
+    return np.linspace(scale * 1e-4, scale * 0.02, n, dtype=np.float64).astype(dtype)
 
 
 class VPSchedule:
@@ -93,10 +106,18 @@ class SolverTable:
         return self.coef[:, 0]
 
 
-def build_table(solver: str, steps: int, betas: Optional[np.ndarray] = None, order: int = 2) -> SolverTable:
-    """Coefficient table for ``steps`` denoiser evaluations (NFE == steps)."""
+def build_table(solver: str, steps: int, betas: Optional[np.ndarray] = None, order: int = 2, eta: float = 0.0) -> SolverTable:
+    """Coefficient table for ``steps`` denoiser evaluations (NFE == steps).
+
+    ``ddim`` / ``ddpm`` need ``betas``, the model's own discrete schedule (pass the float64 betas, e.g.
+    ``linear_betas(n, np.float64)``, to reproduce the reference's float32 buffers bit for bit); ``order`` does not apply to
+    them.  ``eta`` is DDIM's noise scale (the reference's ``ddim_sampling_eta``); ``ddpm`` takes ``steps == len(betas)``."""
     if solver not in SOLVERS:
         raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    if solver in DISCRETE_SOLVERS:
+        return _discrete_table(solver, steps, betas, eta)
+    if eta != 0.0:
+        raise ValueError(f"eta applies to ddim only, not {solver!r}")
     if order not in (1, 2):
         raise ValueError("order must be 1 or 2")
     if steps < order:
@@ -162,10 +183,77 @@ def build_table(solver: str, steps: int, betas: Optional[np.ndarray] = None, ord
     return SolverTable(solver, steps, coef.astype(np.float32), ts, det)
 
 
+def _discrete_buffers(betas: np.ndarray) -> Dict[str, np.ndarray]:
+    """the float32 buffers the reference registers (model.py NaturalSpeech2.__init__), computed in float64 as it does"""
+    b = np.asarray(betas, dtype=np.float64)
+    ac = np.cumprod(1.0 - b)
+    ac_prev = np.concatenate([[1.0], ac[:-1]])
+    pv = b * (1.0 - ac_prev) / (1.0 - ac)
+    f = lambda v: np.asarray(v, dtype=np.float32)   # noqa: E731
+    return {"alphas_cumprod": f(ac), "sqrt_recip_alphas_cumprod": f(np.sqrt(1.0 / ac)), "sqrt_recipm1_alphas_cumprod": f(np.sqrt(1.0 / ac - 1.0)),
+            "posterior_log_variance_clipped": f(np.log(np.maximum(pv, 1e-20))),
+            "posterior_mean_coef1": f(b * np.sqrt(ac_prev) / (1.0 - ac)), "posterior_mean_coef2": f((1.0 - ac_prev) * np.sqrt(1.0 - b) / (1.0 - ac))}
+
+
+def ddim_times(steps: int, num_timesteps: int) -> List[int]:
+    """model.py ddim_sample: torch.linspace(-1, T-1, steps+1) in float32, truncated, reversed -- the float32 grid truncates
+    differently from a float64 one for 139 of the step counts 1..1000, so torch computes it"""
+    import torch
+    return list(reversed(torch.linspace(-1, num_timesteps - 1, steps=steps + 1).int().tolist()))
+
+
+def _discrete_table(solver: str, steps: int, betas: Optional[np.ndarray], eta: float) -> SolverTable:
+    if betas is None:
+        raise ValueError(f"{solver} tables index the model's own discrete schedule: pass its betas (e.g. linear_betas(1000, np.float64))")
+    bf = _discrete_buffers(betas)
+    N = len(bf["alphas_cumprod"])
+    if solver == "ddpm":
+        if eta != 0.0:
+            raise ValueError("eta applies to ddim only")
+        if steps != N:
+            raise ValueError(f"ddpm runs every timestep of the schedule: steps must be len(betas) = {N}, got {steps}")
+        pairs = [(t, t - 1) for t in reversed(range(N))]
+    else:
+        if not 1 <= steps <= N:
+            raise ValueError(f"ddim steps must be in [1, {N}], got {steps}")
+        if eta < 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
+        times = ddim_times(steps, N)
+        pairs = list(zip(times[:-1], times[1:]))
+    d = np.float64
+    coef = np.zeros((steps, NCOEF), dtype=np.float64)
+    for i, (t, tn) in enumerate(pairs):
+        row = coef[i]
+        a = d(bf["alphas_cumprod"][t])
+        row[0] = t
+        row[1], row[2] = np.sqrt(a), np.sqrt(1.0 - a)     # the x_start round trip (any alpha, sigma != 0 reproduce x0 to rounding)
+        if solver == "ddpm":
+            row[5] = bf["posterior_mean_coef2"][t]
+            row[6] = -d(bf["posterior_mean_coef1"][t])
+            if t > 0:
+                row[9] = np.exp(0.5 * d(bf["posterior_log_variance_clipped"][t]))
+        elif tn < 0:
+            row[5], row[6] = 0.0, -1.0                      # img = x_start
+        else:
+            # sigma and c in float32, as the reference evaluates them on its float32 buffers (1 - a/a_next cancels: float64 would
+            # differ by ~1e-4 relative on 1000-step grids)
+            f, a32, an32 = np.float32, bf["alphas_cumprod"][t], bf["alphas_cumprod"][tn]
+            sig = f(eta) * np.sqrt((f(1) - a32 / an32) * (f(1) - an32) / (f(1) - a32))
+            c = np.sqrt(np.maximum(f(1) - an32 - sig * sig, f(0)))
+            r1, r2 = d(bf["sqrt_recip_alphas_cumprod"][t]), d(bf["sqrt_recipm1_alphas_cumprod"][t])
+            # x_start*sqrt(a_next) + c*(r1*x - x_start)/r2 + sig*z   (predict_noise_from_start)
+            row[5] = d(c) * r1 / r2
+            row[6] = d(c) / r2 - d(np.sqrt(an32))
+            row[9] = sig
+    times_out = np.array([p[0] for p in pairs] + [pairs[-1][1]], dtype=np.float64)
+    return SolverTable(solver, steps, coef.astype(np.float32), times_out, {"pairs": np.array(pairs, dtype=np.int64)})
+
+
 def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarray], x_T: np.ndarray,
-                    trace: Optional[List[np.ndarray]] = None) -> np.ndarray:
+                    trace: Optional[List[np.ndarray]] = None, noise_fn: Optional[Callable[[int], np.ndarray]] = None) -> np.ndarray:
     """Host executor of the unified recurrence (float32), used by CPU tests to pin
-    the tables against the oracle samplers.  ``x0_fn(x, t_model[B]) -> x0``."""
+    the tables against the oracle samplers.  ``x0_fn(x, t_model[B]) -> x0``.  ``noise_fn(i)`` -> the standard normals of
+    step i, shaped like x_T (ns2vc_amd.noise.gauss), for tables with a nonzero noise column."""
     f = np.float32
     xbar = x_T.astype(f).copy()
     xe = xbar.copy()
@@ -179,6 +267,10 @@ def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray]
         m = (xe - sigma * eps) / alpha
         x = xbar - g0 * d1 - g1 * (m - m_prev)
         xbar = A * x - Bc * m
+        if table.coef[i, 9] != 0:
+            if noise_fn is None:
+                raise ValueError(f"step {i} of this {table.solver} table adds noise: pass noise_fn")
+            xbar = xbar + f(table.coef[i, 9]) * np.asarray(noise_fn(i), dtype=f)
         d1 = d1c * (m_prev - m)
         xe = xbar - pc * d1
         m_prev = m

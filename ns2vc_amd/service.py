@@ -16,6 +16,8 @@ The reference's ``Svc.infer`` (``inference/infer_tool.py:189-206``) converts ONE
   (``Denoiser.sample(lengths=...)``, ``ns2vc_unet_set_lengths``): every GroupNorm statistic, self-attention softmax and
   convolution halo sees an item's own frames only, so a segment's result is what it gives alone, to the precision's rounding.
   Each segment's x_T is drawn as in the default mode, at its own length, then zero-padded.
+* ``solver="ddim"`` (with ``eta``) / ``"ddpm"``: the reference's discrete samplers.  Their per-step noise comes from the segment's own
+  seed (``noise.derive_seed(seed, index)``), so a segment's result does not depend on its group in either mode.
 * each group runs ``PreModel.infer`` -> ``Denoiser.sample`` -> ``decode_fn`` through ``OverlappedPipeline``: the
   PyTorch-ROCm front / back end of group k+1 / k-1 overlaps the HIP denoiser of group k on their own streams.
 
@@ -30,7 +32,10 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import torch
 
+import numpy as np
+
 from .frontend import PreModel
+from .noise import derive_seed
 from .pipeline import Denoiser, OverlappedPipeline
 
 
@@ -56,10 +61,16 @@ class GroupedConverter:
     ragged = False      # the default mode (exact-shape groups), also for an instance that only plans (built without __init__)
 
     def __init__(self, pre_model: PreModel, denoiser: Denoiser, decode_fn: Optional[Callable] = None, max_batch: int = 32,
-                 solver: str = "unipc", steps: int = 30, order: int = 2, seed: int = 1234, ragged: bool = False):
+                 solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, ragged: bool = False, eta: float = 0.0):
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
         self.max_batch, self.seed, self.ragged = max_batch, seed, ragged
-        self.kw = dict(solver=solver, steps=steps, order=order)
+        if solver == "ddpm" and steps == 30:      # (the constructor's default step count is the continuous solvers'; ddpm runs every timestep)
+            steps = None
+        self.kw = dict(solver=solver, steps=steps, order=order, eta=eta)
+
+    def _seeds(self, idx) -> np.ndarray:
+        """per-SEGMENT noise seeds of the stochastic samplers, from the converter's seed and the segment's position in the input"""
+        return np.array([derive_seed(self.seed, i) for i in idx], dtype=np.uint64)
 
     def plan(self, segments: Sequence[Segment]) -> List[List[int]]:
         """indices of `segments` grouped by (latent length, prompt length), groups of at most ``max_batch``, longest first;
@@ -96,7 +107,7 @@ class GroupedConverter:
             content, prompt, mask = self.pre.infer(c, refer, torch.full((len(idx),), T, device=dev), torch.full((len(idx),), Lp, device=dev))
             # x_T per SEGMENT (seeded by its position in the input), so a segment's result does not depend on its group
             noise = torch.stack([torch.randn((self.den.cfg.latent_channels, T), generator=torch.Generator().manual_seed(self.seed + i)) for i in idx]).to(dev)
-            return {"content": content, "prompt": prompt, "prompt_mask": mask, "noise": noise}
+            return {"content": content, "prompt": prompt, "prompt_mask": mask, "noise": noise, "seeds": self._seeds(idx)}
 
         def ragged_pre(idx):
             lens = [int(segments[i].content.shape[-1]) for i in idx]
@@ -110,7 +121,7 @@ class GroupedConverter:
             refer = torch.stack([segments[i].refer.to(dev, torch.float32) for i in idx])
             content, prompt, mask = self.pre.infer(c, refer, torch.tensor(lens, device=dev), torch.full((len(idx),), Lp, device=dev),
                                                    exact_lengths=True)
-            return {"content": content, "prompt": prompt, "prompt_mask": mask, "noise": noise.to(dev), "lengths": lens}
+            return {"content": content, "prompt": prompt, "prompt_mask": mask, "noise": noise.to(dev), "lengths": lens, "seeds": self._seeds(idx)}
 
         def post_fn(latent, idx):
             if self.ragged:     # one tensor per segment, cut to its own frames
