@@ -151,7 +151,10 @@ int ns2vc_sampler_run(ns2vc_unet* h, float* x_inout_bct, int use_graph, void* st
  * second-order update of DPM-Solver++(2M), dpm_solver.py:796-831, extrapolates over a large log-SNR step), so a 16-bit
  * engine runs steps [0, N-k) and an fp32 engine, prepared for the same shape / condition / table, runs the last k:
  *   begin(h16, x_T); steps(h16, N-k); handoff(h32, h16); steps(h32, k); end(h32, x_out).
- * handoff copies the fp32 solver state (x_e, x_bar, d1, m_prev, loop position) on `stream`. */
+ * handoff copies the fp32 solver state (x_e, x_bar, d1, m_prev, loop position) on `stream`.
+ * Order-3 tables (a nonzero column 10 or 11: d2c, pe) also keep m_{i-2}, in a buffer of the engine allocated by the first begin (or
+ * handoff) that needs it, zeroed by begin and copied by handoff; a change between such a table and any other rebuilds the captured step
+ * graph, and these tables never run the update in conv_out's epilogue (fuse_solver). */
 int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream);
 int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream);
 int ns2vc_sampler_end(ns2vc_unet* h, float* x_out_bct, void* stream);
@@ -450,6 +453,14 @@ int ns2vc_k_btc_to_nct(const float* src, int lds, int C, int T, int B, float* ds
 /* the normals a stochastic update adds at table row `step`: out = fp32 rows [B*T][ld] (ld % 4 == 0) channels-last, out[(b*T + t)*ld + c] = z for
  * c < C and t < lens_dev[b] (lens_dev = DEVICE [B] or NULL = all T), 0 elsewhere; seeds_dev = DEVICE [B] */
 int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream);
+/* One solver update of the sampling loop (backward-compatible addition to ABI v7), the launch ns2vc_sampler_steps makes after every
+ * evaluation: row *step_dev of coef_dev (DEVICE [steps][NS2VC_NCOEF], ns2vc_amd.schedule.build_table) applied to x0 and the fp32 state
+ * xe, xbar, d1, mprev (rows [n / ld][ld], updated in place; ns2vc_amd/schedule.py states the recurrence).  xe_op receives the new xe in the
+ * operand type: fp32 rows [n / ld][ld], or for 16-bit precisions the hi + lo pair [hi(ld) | lo(ld)], row stride 2 * ld.
+ * mprev2 = NULL: the order <= 2 update (columns 10-11 ignored).  Non-NULL: the history-2 update of order-3 tables, which reads m_{i-2}
+ * there and leaves m_{i-1}.  No noise term (stochastic tables run only inside the loop). */
+int ns2vc_k_solver_update(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
+                          float* d1, float* mprev, float* mprev2, size_t n, int ld, void* stream);
 
 #ifdef __cplusplus
 }

@@ -209,6 +209,7 @@ PROTOTYPES = {
     "ns2vc_k_nct_to_btc": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
     "ns2vc_k_btc_to_nct": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "ns2vc_k_noise": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "ns2vc_k_solver_update": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

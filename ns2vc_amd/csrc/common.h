@@ -238,6 +238,18 @@ __device__ __forceinline__ void solver_upd(const SolverCoef& k, float vx0, float
   const float nd = k.d1c * (vmp - m);
   oxb = nb; od1 = nd; oxe = nb - k.pc * nd; om = m;
 }
+// The same element with the second history term of order-3 rows (columns 10-11 of the table: d2c, pe; vmp2 = m_{i-2}).  Only tables with
+// a nonzero column 10 or 11 run it (solver_update_kernel<TM, true>); every other table keeps solver_upd's arithmetic.
+__device__ __forceinline__ void solver_upd2(const SolverCoef& k, float d2c, float pe, float vx0, float vxe, float vxb, float vd1, float vmp, float vmp2,
+                                            float& oxe, float& oxb, float& od1, float& om) {
+  const float eps = (vxe - k.alpha * vx0) / k.sigma;
+  const float m = (vxe - k.sigma * eps) / k.alpha;
+  const float x = vxb - k.g0 * vd1 - k.g1 * (m - vmp);
+  const float nb = k.A * x - k.Bc * m;
+  const float dm2 = vmp2 - m;
+  const float nd = k.d1c * (vmp - m) + d2c * dm2;
+  oxb = nb; od1 = nd; oxe = nb - k.pc * nd - pe * dm2; om = m;
+}
 
 // Device noise of the stochastic samplers (DDPM, DDIM with eta > 0; ns2vc_amd/noise.py is the host statement of the stream):
 // Philox4x32-10 (Salmon et al., SC 2011) keyed by the item's 64-bit seed, counter (t, c / 4, step, 0) -> the four normals of
@@ -341,7 +353,8 @@ struct SolverNoise { const unsigned long long* seeds = nullptr; const int* lens 
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0,
                                 float* xe, void* xe_op, int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s,
                                 int split = 0,                  // split > 0 (16-bit): xe_op rows are [hi(split) | lo(split)] of state rows of `split` columns
-                                const SolverNoise& noise = SolverNoise());
+                                const SolverNoise& noise = SolverNoise(),
+                                float* mprev2 = nullptr);       // non-NULL: the history-2 update (order-3 tables; m_{i-2} in, m_{i-1} out); no noise with it
 // the normals a stochastic update adds at table row `step` (ns2vc_k_noise): out rows [B*T][ld] fp32, zeros where no noise goes
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s);
 hipError_t launch_fill_i32(int* p, int v, hipStream_t s);

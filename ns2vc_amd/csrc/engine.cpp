@@ -240,6 +240,11 @@ struct ns2vc_unet {
   hipEvent_t seeds_event = nullptr;
   bool seeds_staged = false;
   bool stochastic = false;
+  // History 2 (order-3 tables: a nonzero column 10 or 11, detected by ns2vc_sampler_load): the update also keeps m_{i-2}, in a buffer
+  // of its own outside the plan arena, allocated on the first loop that needs it -- the dense plan's layout and launches do not change.
+  bool hist2 = false;
+  float* mprev2 = nullptr;
+  size_t mprev2_n = 0;
 
   // named persistent buffers
   float *xe = nullptr, *xbar = nullptr, *d1 = nullptr, *mprev = nullptr, *x0 = nullptr;
@@ -273,6 +278,7 @@ struct ns2vc_unet {
     if (seeds_event) (void)hipEventDestroy(seeds_event);
     if (seeds_stage) (void)hipHostFree(seeds_stage);
     if (seeds_dev) (void)hipFree(seeds_dev);
+    if (mprev2) (void)hipFree(mprev2);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     if (side_stream) (void)hipStreamDestroy(side_stream);
@@ -1964,8 +1970,24 @@ int ns2vc_sampler_load(ns2vc_unet* h, int steps, const float* coef_host) {
   h->next_step = -1;
   bool stochastic = false;
   for (int i = 0; i < steps; ++i) stochastic |= coef_host[(size_t)i * NS2VC_NCOEF + 9] != 0.f;
-  if (stochastic != h->stochastic && h->step_graph) { (void)hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }   // (the update's noise arguments are baked in)
+  bool hist2 = false;
+  for (int i = 0; i < steps; ++i) hist2 |= coef_host[(size_t)i * NS2VC_NCOEF + 10] != 0.f || coef_host[(size_t)i * NS2VC_NCOEF + 11] != 0.f;
+  if (stochastic && hist2) { h->steps = 0; return fail("a solver table with both a noise column and history 2 (columns 10-11) is not supported"); }
+  // (the update's noise arguments and its history-2 form are baked into the captured step graph)
+  if ((stochastic != h->stochastic || hist2 != h->hist2) && h->step_graph) { (void)hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
   h->stochastic = stochastic;
+  h->hist2 = hist2;
+  return 0;
+}
+
+// the m_{i-2} buffer of history-2 tables for the prepared shape; a new one invalidates the captured step graph (its update reads the old pointer)
+static int ensure_mprev2(ns2vc_unet* h) {
+  const size_t n = (size_t)h->B * h->T * h->CP;
+  if (h->mprev2 && h->mprev2_n >= n) return 0;
+  if (h->step_graph) { (void)hipGraphExecDestroy(h->step_graph); h->step_graph = nullptr; }
+  if (h->mprev2) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->mprev2)); h->mprev2 = nullptr; h->mprev2_n = 0; }
+  HIPCHK(hipMalloc((void**)&h->mprev2, n * sizeof(float)));
+  h->mprev2_n = n;
   return 0;
 }
 
@@ -2011,6 +2033,7 @@ static bool solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
   if (h->masked) return false;
   if (h->conv_out_prec != h->prec) return false;      // (exact_io: conv_out runs in fp32 there, the operand copy of the state is 16-bit)
   if (h->stochastic) return false;                     // (the epilogue has no noise term: a stochastic table runs the stand-alone update)
+  if (h->hist2) return false;                          // (nor an m_{i-2}: history-2 tables too)
   g = h->conv_out_g;
   g.out_f32 = nullptr;
   g.sol_coef = h->coef_dev; g.sol_step = h->step_dev; g.sol_ncoef = NS2VC_NCOEF;
@@ -2047,7 +2070,8 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
   if (h->stochastic) {       // noise on the item's valid frames and real channels only (masked plan: level-0 lengths = the first B entries)
     nz.seeds = h->seeds_dev; nz.lens = h->masked ? h->lens_dev : nullptr; nz.T = h->T; nz.ld = h->CP; nz.nc = h->cfg.latent_channels;
   }
-  HIPCHK(launch_solver_update(h->coef_dev, h->step_dev, NS2VC_NCOEF, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s, h->prec != PREC_F32 ? h->CP : 0, nz));
+  HIPCHK(launch_solver_update(h->coef_dev, h->step_dev, NS2VC_NCOEF, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s, h->prec != PREC_F32 ? h->CP : 0, nz,
+                              h->hist2 ? h->mprev2 : nullptr));
   return 0;
 }
 
@@ -2066,6 +2090,10 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   HIPCHK(launch_copy16(h->xe, h->xbar, n * sizeof(float), s));
   HIPCHK(launch_zero(h->d1, n * sizeof(float), s));
   HIPCHK(launch_zero(h->mprev, n * sizeof(float), s));
+  if (h->hist2) {
+    if (ensure_mprev2(h)) return 1;
+    HIPCHK(launch_zero(h->mprev2, n * sizeof(float), s));
+  }
   HIPCHK(launch_fill_i32(h->step_dev, -1, s));      // the first launch of every step advances it (gn_stats.clear)
   h->next_step = 0;
   return 0;
@@ -2075,6 +2103,7 @@ int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream)
   if (check_ready(h, true)) return 1;
   if (!h->coef_dev || h->steps <= 0) return fail("no solver table loaded (call ns2vc_sampler_load)");
   if (h->next_step < 0) return fail("no sampling loop in progress (call ns2vc_sampler_begin or ns2vc_sampler_handoff)");
+  if (h->hist2 && !h->mprev2) return fail("history-2 table without its m_prev2 buffer (begin the loop after loading the table)");
   if (n_steps < 0 || h->next_step + n_steps > h->steps) return fail("steps %d..%d outside the loaded table of %d", h->next_step, h->next_step + n_steps, h->steps);
   hipStream_t s = (hipStream_t)stream;
   const auto& c = h->cfg;
@@ -2116,7 +2145,7 @@ int ns2vc_sampler_end(ns2vc_unet* h, float* x_out_bct, void* stream) {
   return 0;
 }
 
-// Solver state of `src` (x_e, x_bar, d1, m_prev, loop position) -> `dst`, which continues the SAME table from there: the
+// Solver state of `src` (x_e, x_bar, d1, m_prev, m_prev2 of history-2 tables, loop position) -> `dst`, which continues the SAME table from there: the
 // engines may differ in precision (the state is fp32 in every mode; dst's operand copy of x_e is rebuilt in its own type).
 // Both must be prepared for the same (B, T) and hold the same solver table and condition.
 int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
@@ -2133,6 +2162,10 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   HIPCHK(launch_copy16(src->xbar, dst->xbar, n * sizeof(float), s));
   HIPCHK(launch_copy16(src->d1, dst->d1, n * sizeof(float), s));
   HIPCHK(launch_copy16(src->mprev, dst->mprev, n * sizeof(float), s));
+  if (src->hist2) {          // (same table hash: dst->hist2 too)
+    if (ensure_mprev2(dst)) return 1;
+    HIPCHK(launch_copy16(src->mprev2, dst->mprev2, n * sizeof(float), s));
+  }
   HIPCHK(launch_cast_op(dst->xe, n, dst->xe_op, dst->prec, s, dst->prec != PREC_F32 ? dst->CP : 0));
   if (src->seeds_set) {      // the tail continues the same noise stream
     if (ensure_seeds(dst, src->B)) return 1;
@@ -2612,6 +2645,15 @@ int ns2vc_k_nct_to_btc(const float* src, int C, int T, int B, float* dst, int ld
 int ns2vc_k_btc_to_nct(const float* src, int lds, int C, int T, int B, float* dst, void* stream) {
   hipError_t e = launch_btc_to_nct(src, lds, C, T, B, dst, (hipStream_t)stream);
   if (e != hipSuccess) return fail("btc_to_nct launch: %s", hipGetErrorString(e));
+  return 0;
+}
+int ns2vc_k_solver_update(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
+                          float* d1, float* mprev, float* mprev2, size_t n, int ld, void* stream) {
+  if (!coef_dev || !step_dev || !x0 || !xe || !xe_op || !xbar || !d1 || !mprev) return fail("null argument");
+  if (ld <= 0 || (ld & 3) || n % (size_t)ld) return fail("n (%zu) must be a multiple of ld (%d), ld a multiple of 4", n, ld);
+  hipError_t e = launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n, (hipStream_t)stream,
+                                      precision != PREC_F32 ? ld : 0, SolverNoise(), mprev2);
+  if (e != hipSuccess) return fail("solver_update launch: %s", hipGetErrorString(e));
   return 0;
 }
 int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream) {

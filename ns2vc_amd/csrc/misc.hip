@@ -533,19 +533,22 @@ __global__ void mask_bias_kernel(const uint8_t* __restrict__ mask, int n, float*
 // Fused solver update (ns2vc_amd/schedule.py documents the recurrence and cites
 // sampler/dpm_solver.py + sampler/uni_pc.py).  Scalars come from row *step of
 // the device-resident coefficient table, so the same captured graph serves
-// every step.
+// every step.  H2 (compile time): the history-2 form of order-3 tables, which also reads m_{i-2} from mprev2 and
+// writes m_{i-1} there; H2 = false is the order <= 2 update, arithmetic unchanged (mprev2 unused).
 // ---------------------------------------------------------------------------
-template <typename TM>
+template <typename TM, bool H2>
 __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
                                                             const float* __restrict__ x0, float* __restrict__ xe, TM* __restrict__ xe_op,
                                                             float* __restrict__ xbar, float* __restrict__ d1,
-                                                            float* __restrict__ mprev, size_t n4, int split, SolverNoise nz) {
+                                                            float* __restrict__ mprev, size_t n4, int split, SolverNoise nz,
+                                                            float* __restrict__ mprev2) {
   op_mode_init<TM>();
   const int step = *step_ptr;
   const SolverCoef k = solver_coef(coef + (size_t)step * ncoef);
   // noise coefficient of this row (column 9): uniform per launch.  0 = no term at all (adding 0*z would turn -0 into +0), so
-  // every noise-free table keeps its bits
-  const float knz = nz.seeds ? coef[(size_t)step * ncoef + 9] : 0.f;
+  // every noise-free table keeps its bits.  (History-2 tables carry no noise: the launcher refuses the pair.)
+  const float knz = (!H2 && nz.seeds) ? coef[(size_t)step * ncoef + 9] : 0.f;
+  const float d2c = H2 ? coef[(size_t)step * ncoef + 10] : 0.f, pe = H2 ? coef[(size_t)step * ncoef + 11] : 0.f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     const float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
     const float4 vxe = reinterpret_cast<const float4*>(xe)[i];
@@ -553,11 +556,20 @@ __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restr
     const float4 vd1 = reinterpret_cast<const float4*>(d1)[i];
     const float4 vmp = reinterpret_cast<const float4*>(mprev)[i];
     float4 oxe, oxb, od1, om;
-    solver_upd(k, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, oxe.x, oxb.x, od1.x, om.x);
-    solver_upd(k, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
-    solver_upd(k, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
-    solver_upd(k, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
-    if (knz != 0.f) {      // xbar' += noise * z on the live elements (the state is zero elsewhere and stays so): ld % 4 == 0, one quad per thread
+    if constexpr (H2) {
+      const float4 vm2 = reinterpret_cast<const float4*>(mprev2)[i];
+      solver_upd2(k, d2c, pe, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxe.x, oxb.x, od1.x, om.x);
+      solver_upd2(k, d2c, pe, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxe.y, oxb.y, od1.y, om.y);
+      solver_upd2(k, d2c, pe, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxe.z, oxb.z, od1.z, om.z);
+      solver_upd2(k, d2c, pe, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxe.w, oxb.w, od1.w, om.w);
+      out_f4(mprev2 + 4 * i, vmp.x, vmp.y, vmp.z, vmp.w);
+    } else {
+      solver_upd(k, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, oxe.x, oxb.x, od1.x, om.x);
+      solver_upd(k, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
+      solver_upd(k, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
+      solver_upd(k, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
+    }
+    if (!H2 && knz != 0.f) {      // xbar' += noise * z on the live elements (the state is zero elsewhere and stays so): ld % 4 == 0, one quad per thread
       const size_t e = 4 * i, r = e / (size_t)nz.ld;
       const int c = (int)(e - r * (size_t)nz.ld), b = (int)(r / (size_t)nz.T), t = (int)(r - (size_t)b * nz.T);
       if (c < nz.nc && (!nz.lens || t < nz.lens[b])) {
@@ -753,13 +765,19 @@ hipError_t launch_mask_bias(const uint8_t* mask, int n, float* bias, hipStream_t
   return hipGetLastError();
 }
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0, float* xe, void* xe_op, int prec,
-                                float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise) {
+                                float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise, float* mprev2) {
   if ((n & 3) || (split && (prec == PREC_F32 || (split & 3) || n % (size_t)split))) return hipErrorInvalidValue;
   if (noise.seeds && (noise.ld <= 0 || (noise.ld & 3) || noise.T <= 0 || noise.nc > noise.ld || n % ((size_t)noise.ld * noise.T))) return hipErrorInvalidValue;
+  if (mprev2 && (noise.seeds || ncoef < 12)) return hipErrorInvalidValue;
   const size_t n4 = n >> 2;
   const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  NS2VC_BY_PREC(prec, hipLaunchKernelGGL(solver_update_kernel<TMX>, dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op,
-                                         xbar, d1, mprev, n4, split, noise));
+  if (mprev2) {
+    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_kernel<TMX, true>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op,
+                                           xbar, d1, mprev, n4, split, noise, mprev2));
+  } else {
+    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_kernel<TMX, false>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op,
+                                           xbar, d1, mprev, n4, split, noise, mprev2));
+  }
   return hipGetLastError();
 }
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s) {

@@ -331,13 +331,16 @@ class Engine:
         """x (B,100,T), t (B,) fp32, out (B,100,T): one denoiser evaluation."""
         check(self.lib.ns2vc_unet_forward(self.h, _ptr(x), _ptr(t), _ptr(out), _stream_ptr(stream)), "forward")
 
-    def load_sampler(self, solver: str, steps: int, betas: Optional[np.ndarray] = None, order: int = 2, eta: float = 0.0) -> SolverTable:
-        """``build_table(solver, steps, betas, order, eta)`` -> the engine.  A stochastic table (``ddpm``, ``ddim`` with eta > 0) needs
+    def load_sampler(self, solver: str, steps: int, betas: Optional[np.ndarray] = None, order: int = 2, eta: float = 0.0,
+                     **options) -> SolverTable:
+        """``build_table(solver, steps, betas, order, eta, **options)`` -> the engine (``options``: the keyword-only ``skip_type``,
+        ``lower_order_final``, ``denoise_to_zero``, ``variant``, ``solver_type``, ``t_start``, ``t_end``, ``method``).  The loop runs
+        ``table.steps`` evaluations (steps + 1 with ``denoise_to_zero``).  A stochastic table (``ddpm``, ``ddim`` with eta > 0) needs
         ``set_seeds`` before the loop begins."""
-        table = build_table(solver, steps, betas, order, eta)
+        table = build_table(solver, steps, betas, order, eta, **options)
         coef = np.ascontiguousarray(table.coef, dtype=np.float32)
-        assert coef.shape == (steps, NCOEF)
-        check(self.lib.ns2vc_sampler_load(self.h, steps, coef.ctypes.data_as(C.POINTER(C.c_float))), "sampler_load")
+        assert coef.shape == (table.steps, NCOEF)
+        check(self.lib.ns2vc_sampler_load(self.h, table.steps, coef.ctypes.data_as(C.POINTER(C.c_float))), "sampler_load")
         self.table = table
         return table
 

@@ -15,7 +15,7 @@ import numpy as np
 from . import dist as _dist
 from .engine import DEFAULT_PRECISION, Engine
 from .noise import draw_seeds
-from .schedule import DISCRETE_SOLVERS, SOLVERS, linear_betas
+from .schedule import DISCRETE_SOLVERS, SOLVERS, linear_betas, table_options
 from .spec import UNetConfig, attention_workgroups_per_forward
 
 
@@ -28,6 +28,18 @@ from .spec import UNetConfig, attention_workgroups_per_forward
 # 7.7e-4 from the fp32 engine with no tail (worst item 8.0e-4), 1.4e-4 / 1.3e-4 with one fp32 evaluation, 6.7e-5 / 7.5e-5 with two
 # (profiles/r08_stochastic.txt): one is the smallest tail that holds the 1e-3 bar with margin.
 DEFAULT_TAIL_FP32 = {"dpmsolver++": 2, "unipc": 0, "ddim": 1, "ddpm": 1}
+# ... and for order-3 tables, from tools/solver_bench.py at the bench shape, 20 steps, fp16 against the fp32 engine (profiles/r08_order3_solvers.txt).
+# UniPC-3 ends at first order like UniPC-2 and has its rounding: 7.6e-4 with no tail, but 1.4e-3 on the worst frame; one fp32 evaluation
+# gives 1.6e-4 (worst frame 3.6e-4), the smallest tail with margin, as for DDPM / DDIM.  DPM-Solver++(3M) takes its last updates at third
+# order over the largest log-SNR steps (no lower_order_final for steps >= 10, as the reference), and each extrapolates from three model
+# values, so the rounding of the last four evaluations reaches the latent: tail 0 / 1 / 2 / 3 / 4 give 7.6e-3 / 7.5e-3 / 4.5e-3 / 1.2e-3 /
+# 3.1e-4 (worst item 3.3e-4, worst frame 7.4e-4).  Four is the smallest tail inside the bar.
+DEFAULT_TAIL_FP32_ORDER3 = {"dpmsolver++": 4, "unipc": 1}
+
+
+def default_tail_fp32(solver: str, order: int) -> int:
+    """trailing fp32 evaluations of a 16-bit loop when the caller sets none"""
+    return (DEFAULT_TAIL_FP32_ORDER3 if order == 3 and solver in DEFAULT_TAIL_FP32_ORDER3 else DEFAULT_TAIL_FP32).get(solver, 0)
 # LayerNorm-by-linearity guard thresholds on max |mean|/std (see Denoiser): 16-bit modes lose ~ratio * 2^-11 on a row,
 # fp32 loses ~ratio^2 * 2^-24 in the variance E[x^2] - mean^2
 LN_GUARD_DEFAULT = {"fp16": 8.0, "bf16": 8.0, "fp32": 32.0}
@@ -39,7 +51,7 @@ class Denoiser:
 
     ``tail_fp32``: evaluations at the END of every sampling loop that run on a second, fp32 engine (the solver state is
     handed over on the device, ``Engine.sample(tail=...)``).  None = ``DEFAULT_TAIL_FP32[solver]`` for the 16-bit
-    precisions (2 for DPM-Solver++, 0 for UniPC), 0 = never.  The fp32 engine (weights + workspace) is built on first use.
+    precisions (2 for DPM-Solver++, 0 for UniPC; order 3: ``DEFAULT_TAIL_FP32_ORDER3``, 4 and 1), 0 = never.  The fp32 engine (weights + workspace) is built on first use.
 
     ``ln_guard``: LayerNorm by linearity (the default plan) lets the 16-bit modes round a LayerNorm's RAW input before
     centring, so their error on a row grows with |mean| / std of that row (and the fp32 variance E[x^2] - mean^2 with its
@@ -169,10 +181,10 @@ class Denoiser:
     def _betas_for(self, solver: str) -> np.ndarray:
         return self.betas64 if solver in DISCRETE_SOLVERS else self.betas
 
-    def _table(self, solver: str, steps: int, order: int, eta: float = 0.0) -> None:
-        key = (solver, steps, order, eta)
+    def _table(self, solver: str, steps: int, order: int, eta: float = 0.0, **options) -> None:
+        key = (solver, steps, order, eta, table_options(options))
         if self._table_key != key:
-            self.engine.load_sampler(solver, steps, self._betas_for(solver), order, eta)
+            self.engine.load_sampler(solver, steps, self._betas_for(solver), order, eta, **options)
             self._table_key = key
 
     def _fp32_engine(self) -> Engine:
@@ -191,14 +203,14 @@ class Denoiser:
             self._tail_shape = self._shape
         return self.tail_engine
 
-    def _tail(self, solver: str, steps: int, order: int, n_tail: int, eta: float = 0.0) -> Optional[Engine]:
+    def _tail(self, solver: str, steps: int, order: int, n_tail: int, eta: float = 0.0, **options) -> Optional[Engine]:
         """the fp32 engine that finishes a 16-bit loop (or runs all of it after a failed precision check), with the table loaded"""
         if (n_tail <= 0 and not self.serving_fp32) or self.precision == "fp32":
             return None
         e = self._fp32_engine()
-        key = (solver, steps, order, eta)
+        key = (solver, steps, order, eta, table_options(options))
         if self._tail_table_key != key:
-            e.load_sampler(solver, steps, self._betas_for(solver), order, eta)
+            e.load_sampler(solver, steps, self._betas_for(solver), order, eta, **options)
             self._tail_table_key = key
         return e
 
@@ -312,10 +324,11 @@ class Denoiser:
             self._attn_check(1, s)                            # (after the guard's read-out: a switch drops the plan)
         return out if redone is None else redone
 
-    def _check_sampler_args(self, solver: str, steps: Optional[int], eta: float, B: int, seeds) -> int:
+    def _check_sampler_args(self, solver: str, steps: Optional[int], eta: float, B: int, seeds, order: int = 2, **options) -> int:
         """the argument errors of ``sample``, raised before anything runs; returns the step count"""
         if solver not in SOLVERS:
             raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        table_options(options)                  # unknown option names
         if eta != 0.0 and solver != "ddim":
             raise ValueError(f"eta is DDIM's noise scale (ddim_sampling_eta); solver {solver!r} takes none")
         if eta < 0.0:
@@ -326,29 +339,37 @@ class Denoiser:
             raise ValueError(f"ddpm runs every timestep of the schedule: steps must be {len(self.betas64)} (or None), got {steps}")
         if seeds is not None and np.asarray(seeds.detach().cpu() if hasattr(seeds, "detach") else seeds).reshape(-1).shape[0] != B:
             raise ValueError(f"seeds must hold one seed per item ({B})")
+        if (options or order != 2) and (solver, int(steps), order, eta, table_options(options)) != self._table_key:
+            from .schedule import build_table      # the table's own checks (order, skip_type, ...) before anything runs, host only
+            build_table(solver, int(steps), self._betas_for(solver), order, eta, **options)
         return int(steps)
 
     def sample(self, content, prompt, prompt_mask=None, noise=None, solver: str = "unipc", steps: Optional[int] = None, order: int = 2,
-               use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None):
+               use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None,
+               **options):
         """content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool; ``noise`` (B,100,T) = x_T (drawn with
         torch.randn like model.py:635 if None).  Returns the sampled latent (B,100,T) fp32.
-        ``solver``: ``unipc`` | ``dpmsolver++`` (``order`` 1 | 2) or the reference's discrete samplers ``ddim`` (``eta`` =
+        ``solver``: ``unipc`` | ``dpmsolver++`` (``order`` 1 | 2 | 3, multistep) or the reference's discrete samplers ``ddim`` (``eta`` =
         ddim_sampling_eta) | ``ddpm`` (p_sample_loop: steps = every timestep).  ``steps`` None: 20, ddim 100, ddpm len(betas).
         ``seeds`` (B,) ints: the per-item noise streams of ddpm / ddim with eta > 0 (ns2vc_amd.noise; item b's noise depends on
         seeds[b] alone), drawn from ``generator`` after x_T if None, so ``generator=`` reproduces a run.
         ``lengths`` (B,) ints in [1, T] or None: per-item valid frames of a padded batch (see ``denoise``); x_T is zeroed past them.
-        ``tail_fp32`` overrides the instance's setting for this call (see the class docstring)."""
+        ``tail_fp32`` overrides the instance's setting for this call (see the class docstring).
+        ``options`` (keyword-only): the reference's ``UniPC.sample`` / ``DPM_Solver.sample`` keywords that ``schedule.build_table`` serves
+        -- ``skip_type``, ``lower_order_final``, ``denoise_to_zero`` (one more evaluation), ``variant`` (UniPC), ``solver_type``
+        (DPM-Solver++), ``t_start``, ``t_end``, ``method`` ("multistep" only)."""
         import torch
         B, _, T = content.shape
         dev = content.device
-        steps = self._check_sampler_args(solver, steps, eta, B, seeds)
+        steps = self._check_sampler_args(solver, steps, eta, B, seeds, order, **options)
         self._guard_before()
         self._prepare(B, T, prompt.shape[1])
-        self._table(solver, steps, order, eta)
+        self._table(solver, steps, order, eta, **options)
+        nfe = self.engine.table.steps               # (steps + 1 with denoise_to_zero)
         n_tail = tail_fp32 if tail_fp32 is not None else self.tail_fp32
         if n_tail is None:
-            n_tail = DEFAULT_TAIL_FP32.get(solver, 0) if self.precision != "fp32" else 0
-        n_tail = max(0, min(int(n_tail), steps))
+            n_tail = default_tail_fp32(solver, order) if self.precision != "fp32" else 0
+        n_tail = max(0, min(int(n_tail), nfe))
         if noise is None:
             noise = torch.randn((B, self.cfg.latent_channels, T), device=dev, generator=generator)
         x = noise.to(device=dev, dtype=torch.float32).contiguous().clone()
@@ -363,7 +384,7 @@ class Denoiser:
         if self.precision_check is not None and not self._precision_checked:
             self._condition(self.engine, c32, p32, mask, s, lengths)
             self._self_check(self._trajectory_points(x, use_graph, s), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths)
-        tail = self._tail(solver, steps, order, n_tail, eta)
+        tail = self._tail(solver, steps, order, n_tail, eta, **options)
         if tail is not None and stochastic:
             tail.set_seeds(seeds, stream=s)
         if self.serving_fp32:            # a failed precision check: the whole loop on the fp32 engine
@@ -378,9 +399,9 @@ class Denoiser:
             self.engine.attn_fallbacks(reset=True, stream=s)      # count this loop alone (the self-check's evaluations are behind us)
         self.engine.sample(x, use_graph=use_graph, stream=s, tail=tail, tail_steps=n_tail if tail is not None else 0)
         redone = self._guard_after(s, lambda: self.sample(content, prompt, prompt_mask, noise, solver, steps, order, use_graph,
-                                                          tail_fp32=tail_fp32, lengths=lengths, eta=eta, seeds=seeds))
+                                                          tail_fp32=tail_fp32, lengths=lengths, eta=eta, seeds=seeds, **options))
         if first_attn and redone is None:
-            self._attn_check(steps - (n_tail if tail is not None else 0), s)      # (after the guard's read-out: a switch drops the plan)
+            self._attn_check(nfe - (n_tail if tail is not None else 0), s)      # (after the guard's read-out: a switch drops the plan)
         return x if redone is None else redone
 
     def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, seeds=None, **kw):
@@ -421,18 +442,20 @@ class OverlappedPipeline:
     """
 
     def __init__(self, denoiser: Denoiser, pre_fn, post_fn, solver: str = "unipc", steps: Optional[int] = 20, order: int = 2,
-                 use_graph: bool = True, pre_device=None, post_device=None, stage_cus=None, denoiser_cus=None, eta: float = 0.0):
+                 use_graph: bool = True, pre_device=None, post_device=None, stage_cus=None, denoiser_cus=None, eta: float = 0.0, **options):
         """``pre_device`` / ``post_device`` (r4): run the front / back end on ANOTHER ROCm device of the node.  On one GPU the three streams
         serialise (the denoiser's launches hold every CU: 7.8 % of the stages' kernel time overlaps, profiles/r03_overlap_trace.txt); a stage
         on its own device overlaps by construction and only its tensors cross xGMI -- content + prompt 35 MB per 32 x 10 s batch in, the
         latent 12 MB out, stream-ordered peer copies behind the stage's event.  ``pre_fn`` then runs with ``pre_device`` current and must
         return tensors on it; ``post_fn`` receives the latent on ``post_device``.  None = the denoiser's device (the one-GPU pipeline).
-        NOT measured on two devices yet (no multi-GPU box this round)."""
+        NOT measured on two devices yet (no multi-GPU box this round).
+        ``options``: the keyword-only sampler options of ``Denoiser.sample`` (``skip_type``, ``denoise_to_zero``, ...), passed through."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("OverlappedPipeline needs a ROCm device (there is no CPU path)")
         self.denoiser, self.pre_fn, self.post_fn = denoiser, pre_fn, post_fn
-        self.kw = dict(solver=solver, steps=steps, order=order, use_graph=use_graph, eta=eta)
+        table_options(options)
+        self.kw = dict(solver=solver, steps=steps, order=order, use_graph=use_graph, eta=eta, **options)
         dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         self.pre_device = torch.device(pre_device) if pre_device is not None else dev

@@ -8,22 +8,34 @@ indexes the table by step and contains no host synchronisation.
 Reference math restated here:
   schedule      sampler/dpm_solver.py:100-154 (discrete VP, piecewise-linear log alpha)
   time grid     sampler/dpm_solver.py:474,1159-1160 (time_uniform), model time :278
-  DPM-Solver++  sampler/dpm_solver.py:547-580 (1st order), :796-831 (2M), loop :1171-1213
-  UniPC-bh2     sampler/uni_pc.py:471-567 (update), loop :606-658
+  time grids    sampler/dpm_solver.py:453-479, sampler/uni_pc.py:305-320 (logSNR | time_uniform | time_quadratic)
+  DPM-Solver++  sampler/dpm_solver.py:547-580 (1st order), :796-831 (2M), :854-904 (3M), loop :1171-1213
+  UniPC-bh      sampler/uni_pc.py:471-588 (update), loop :606-658
 
 Unified recurrence executed by the engine after the i-th denoiser evaluation
-(i = 0 .. steps-1), all tensors elementwise, scalars from row i of the table:
+(i = 0 .. rows-1), all tensors elementwise, scalars from row i of the table:
 
     eps   = (xe - alpha*x0) / sigma ;  m = (xe - sigma*eps) / alpha      # x_start wrapper round trip
     x     = xbar - g0*d1 - g1*(m - m_prev)                               # (corrected) state at t_i
     xbar' = A*x - Bc*m                                                   # first-order part towards t_{i+1}
-    d1'   = d1c*(m_prev - m)                                             # scaled backward difference
-    xe'   = xbar' - pc*d1'                                               # point where the next evaluation happens
-    m_prev' = m
+    d1'   = d1c*(m_prev - m) + d2c*(m_prev2 - m)                         # stored residual (backward differences)
+    xe'   = xbar' - pc*d1' - pe*(m_prev2 - m)                            # point where the next evaluation happens
+    m_prev2' = m_prev ;  m_prev' = m
 
-with xbar = xe = x_T, d1 = m_prev = 0 before the first evaluation.  After the
-last evaluation ``xe'`` is the sample.  For DPM-Solver++(2M): g0 = previous pc,
-g1 = 0.  For UniPC: g0 = alpha_t*B_h*rho_0, g1 = alpha_t*B_h*rho_1, pc = alpha*B_h/2.
+with xbar = xe = x_T, d1 = m_prev = m_prev2 = 0 before the first evaluation.  After the
+last evaluation ``xe'`` is the sample.  Rows of order <= 2 have d2c = pe = 0 (columns 10-11): a table whose
+columns 10-11 are all zero runs without the m_prev2 history at all (the engine's update keeps its order-2 arithmetic).
+Update k (landing on t_k, computed by row k-1, corrected by row k), h = lam_k - lam_{k-1},
+rk_j = (lam_{k-1-j} - lam_{k-1}) / h:
+  DPM-Solver++  g0 = previous pc, g1 = 0.  Order 2: d1c = 1/rk_1, pc = alpha_k*phi1/2 ('dpmsolver') or -alpha_k*(phi1/h + 1)
+                ('taylor', dpm_solver.py:824-829).  Order 3 (3M, dpm_solver.py:854-904): alpha*phi2*D1 - alpha*phi3*D2 written as
+                c_u*(m_prev - m) + c_v*(m_prev2 - m); pc = alpha_k*phi1/2, d1c = -c_u/pc, d2c = -c_v/pc, pe = 0, so xe' is the
+                3M state and the next row's x = xbar - pc*d1 = xe.
+  UniPC-bh      aB = alpha_k*B_h (B_h = expm1(-h) for bh2, -h for bh1, uni_pc.py:509-514).  Order 2: g0 = aB*rho_0,
+                g1 = aB*rho_1, pc = aB/2, d1c = 1/rk_1.  Order 3: rc = the 3x3 ``rhos_c`` solve, rp = the 2x2 ``rhos_p`` solve
+                (uni_pc.py:516-541); d1c = 1/rk_1, d2c = (rc_1/rc_0)/rk_2 (so rc_0*d1' is the corrector residual),
+                pc = aB*rp_0, pe = aB*rp_1/rk_2 - pc*d2c; the correcting row has g0 = aB*rc_0, g1 = aB*rc_2.
+``denoise_to_zero``: one more row at t_0 (A = 0, Bc = -1: xe' = x_start of that evaluation), so the table has steps + 1 rows.
 
 The two discrete samplers of the reference (model.py: ``ddim_sample``, ``p_sample_loop`` / ``p_sample``) are first-order
 rows of the same recurrence (g0 = g1 = d1c = pc = 0, so xe' = xbar' = A*xe - Bc*m), plus a Gaussian term:
@@ -44,7 +56,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 # column layout of the per-step coefficient table (float32, NCOEF per row)
-COEF_COLUMNS = ("t_model", "alpha", "sigma", "g0", "g1", "A", "Bc", "d1c", "pc", "noise", "_pad1", "_pad2")
+COEF_COLUMNS = ("t_model", "alpha", "sigma", "g0", "g1", "A", "Bc", "d1c", "pc", "noise", "d2c", "pe")
 NCOEF = len(COEF_COLUMNS)
 SOLVERS = ("dpmsolver++", "unipc", "ddim", "ddpm")
 DISCRETE_SOLVERS = ("ddim", "ddpm")      # tables over the integer timesteps of the model's own buffers; `order` does not apply
@@ -85,9 +97,17 @@ class VPSchedule:
         la = self.log_alpha_at(t)
         return float(la - 0.5 * np.log(1.0 - np.exp(2.0 * la)))
 
-    def timesteps(self, steps: int) -> np.ndarray:
+    def timesteps(self, steps: int, t_T: float = 1.0, t_0: Optional[float] = None) -> np.ndarray:
         # the reference builds the grid with torch.linspace in float32
-        return np.linspace(1.0, 1.0 / self.N, steps + 1, dtype=np.float32).astype(np.float64)
+        return np.linspace(t_T, 1.0 / self.N if t_0 is None else t_0, steps + 1, dtype=np.float32).astype(np.float64)
+
+    def inverse_lambda(self, lam: np.ndarray) -> np.ndarray:
+        """t of a half-logSNR lambda (dpm_solver.py:156-167, discrete): log alpha = -logaddexp(0, -2 lambda) / 2, then the
+        piecewise-linear inverse of log_alpha(t) over the same knots (extrapolated from the end segments, as interpolate_fn)"""
+        la = -0.5 * np.logaddexp(0.0, -2.0 * np.asarray(lam, dtype=np.float64))
+        xp, yp = self.log_alpha[::-1], self.knots[::-1]
+        i = np.clip(np.searchsorted(xp, la, side="left") - 1, 0, self.N - 2)
+        return yp[i] + (la - xp[i]) * (yp[i + 1] - yp[i]) / (xp[i + 1] - xp[i])
 
     def model_time(self, t: float) -> float:
         return float(np.float32((np.float32(t) - np.float32(1.0 / self.N)) * np.float32(self.N)))
@@ -106,37 +126,119 @@ class SolverTable:
         return self.coef[:, 0]
 
 
-def build_table(solver: str, steps: int, betas: Optional[np.ndarray] = None, order: int = 2, eta: float = 0.0) -> SolverTable:
-    """Coefficient table for ``steps`` denoiser evaluations (NFE == steps).
+SKIP_TYPES = ("logSNR", "time_uniform", "time_quadratic")
+# the keyword-only options of build_table and their defaults (the settings the reference's model.py hard-codes): callers
+# (Engine.load_sampler, Denoiser.sample, GroupedConverter, ...) pass them through unchanged and key their table caches on them
+TABLE_OPTIONS = {"skip_type": "time_uniform", "lower_order_final": True, "denoise_to_zero": False, "variant": "bh2",
+                 "solver_type": "dpmsolver", "t_start": None, "t_end": None, "method": "multistep"}
+
+
+def table_options(opts: Dict[str, object]) -> Tuple[Tuple[str, object], ...]:
+    """``opts`` checked against TABLE_OPTIONS -> a hashable cache key (options at their default left out)"""
+    bad = sorted(set(opts) - set(TABLE_OPTIONS))
+    if bad:
+        raise TypeError(f"unknown sampler option(s) {bad}; known: {sorted(TABLE_OPTIONS)}")
+    return tuple(sorted((k, v) for k, v in opts.items() if v != TABLE_OPTIONS[k] or type(v) is not type(TABLE_OPTIONS[k])))
+
+
+def _grid_f32(sched: VPSchedule, skip_type: str, t_T: float, t_0: float, steps: int) -> np.ndarray:
+    """the logSNR and time_quadratic grids as get_time_steps computes them (dpm_solver.py:453-479): float32 torch throughout,
+    the logSNR end points through ``.item()``.  (A float64 logSNR grid moves the final latent by ~1e-5.)"""
+    import torch
+    f = torch.float32
+    if skip_type == "time_quadratic":
+        return torch.linspace(t_T ** 0.5, t_0 ** 0.5, steps + 1).pow(2).to(torch.float64).numpy()
+    xs = torch.from_numpy(sched.knots.astype(np.float32))
+    ys = torch.from_numpy(sched.log_alpha.astype(np.float32))
+
+    def interp(x, xp, yp):        # interpolate_fn (dpm_solver.py:1241-1285): piecewise linear, end segments extrapolated
+        i = torch.clamp(torch.searchsorted(xp, x) - 1, 0, xp.shape[0] - 2)
+        return yp[i] + (x - xp[i]) * (yp[i + 1] - yp[i]) / (xp[i + 1] - xp[i])
+
+    def lam(t):                   # marginal_lambda
+        la = interp(torch.tensor([t], dtype=f), xs, ys)
+        return (la - 0.5 * torch.log(1.0 - torch.exp(2.0 * la))).item()
+
+    lams = torch.linspace(lam(t_T), lam(t_0), steps + 1)
+    la = -0.5 * torch.logaddexp(torch.zeros((1,), dtype=f), -2.0 * lams)      # inverse_lambda
+    return interp(la, torch.flip(ys, [0]), torch.flip(xs, [0])).to(torch.float64).numpy()
+
+
+def build_table(solver: str, steps: int, betas: Optional[np.ndarray] = None, order: int = 2, eta: float = 0.0, *,
+                skip_type: str = "time_uniform", lower_order_final: bool = True, denoise_to_zero: bool = False, variant: str = "bh2",
+                solver_type: str = "dpmsolver", t_start: Optional[float] = None, t_end: Optional[float] = None,
+                method: str = "multistep") -> SolverTable:
+    """Coefficient table for ``steps`` denoiser evaluations (NFE == steps; ``denoise_to_zero``: steps + 1 evaluations and rows).
+
+    ``unipc`` / ``dpmsolver++`` take the keyword options of the reference's ``UniPC.sample`` / ``DPM_Solver.sample``
+    (uni_pc.py:590, dpm_solver.py:1047) that a captured loop can serve: ``order`` 1-3, ``skip_type`` (SKIP_TYPES),
+    ``lower_order_final``, ``denoise_to_zero``, ``t_start`` / ``t_end`` (default T = 1 and 1/N), ``variant`` (UniPC: ``bh1`` |
+    ``bh2``) and ``solver_type`` (DPM-Solver++ order 2: ``dpmsolver`` | ``taylor``).  ``method`` must be ``multistep``.
 
     ``ddim`` / ``ddpm`` need ``betas``, the model's own discrete schedule (pass the float64 betas, e.g.
-    ``linear_betas(n, np.float64)``, to reproduce the reference's float32 buffers bit for bit); ``order`` does not apply to
-    them.  ``eta`` is DDIM's noise scale (the reference's ``ddim_sampling_eta``); ``ddpm`` takes ``steps == len(betas)``."""
+    ``linear_betas(n, np.float64)``, to reproduce the reference's float32 buffers bit for bit); ``order`` and the keyword options
+    do not apply to them.  ``eta`` is DDIM's noise scale (the reference's ``ddim_sampling_eta``); ``ddpm`` takes ``steps == len(betas)``."""
     if solver not in SOLVERS:
         raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    opts = dict(skip_type=skip_type, lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero, variant=variant,
+                solver_type=solver_type, t_start=t_start, t_end=t_end, method=method)
     if solver in DISCRETE_SOLVERS:
+        given = table_options(opts)
+        if given:
+            raise ValueError(f"{solver} takes none of the continuous solvers' options, got {dict(given)}")
         return _discrete_table(solver, steps, betas, eta)
     if eta != 0.0:
         raise ValueError(f"eta applies to ddim only, not {solver!r}")
-    if order not in (1, 2):
-        raise ValueError("order must be 1 or 2")
+    if method != "multistep":
+        raise ValueError(f"method must be 'multistep' (singlestep / adaptive solvers are not served by the captured loop), got {method!r}")
+    if order not in (1, 2, 3):
+        raise ValueError(f"order must be 1, 2 or 3, got {order!r}")
     if steps < order:
         raise ValueError(f"steps ({steps}) must be >= order ({order})")   # dpm_solver.py:1172 / uni_pc.py:607
+    if skip_type not in SKIP_TYPES:
+        raise ValueError(f"skip_type must be one of {SKIP_TYPES}, got {skip_type!r}")
+    if variant not in ("bh1", "bh2") or (solver != "unipc" and variant != "bh2"):
+        raise ValueError(f"variant must be 'bh1' or 'bh2' (UniPC only; vary_coeff is not served), got {variant!r} for {solver!r}")
+    if solver_type not in ("dpmsolver", "taylor") or (solver != "dpmsolver++" and solver_type != "dpmsolver"):
+        raise ValueError(f"solver_type must be 'dpmsolver' or 'taylor' (DPM-Solver++ only), got {solver_type!r} for {solver!r}")
     sched = VPSchedule(linear_betas() if betas is None else betas)
-    ts = sched.timesteps(steps)
+    t_T = 1.0 if t_start is None else float(t_start)
+    t_0 = 1.0 / sched.N if t_end is None else float(t_end)
+    if not 0.0 < t_0 < t_T <= 1.0:
+        raise ValueError(f"need 0 < t_end < t_start <= 1, got t_start={t_T}, t_end={t_0}")
+    ts = sched.timesteps(steps, t_T, t_0) if skip_type == "time_uniform" else _grid_f32(sched, skip_type, t_T, t_0, steps)
     lam = np.array([sched.lam(t) for t in ts])
     alpha = np.array([sched.alpha(t) for t in ts])
     sigma = np.array([sched.sigma(t) for t in ts])
-    coef = np.zeros((steps, NCOEF), dtype=np.float64)
+    rows = steps + 1 if denoise_to_zero else steps
+    coef = np.zeros((rows, NCOEF), dtype=np.float64)
     det = {k: np.zeros(steps + 1) for k in ("h", "rk", "B_h", "rho0", "rho1", "order")}
+    unipc = solver == "unipc"
 
     def step_order(k: int) -> int:
         """order of the update that lands on ts[k], k = 1..steps"""
         if k < order:
             return k
-        if solver == "unipc":
-            return min(order, steps + 1 - k)                  # lower_order_final always, uni_pc.py:636-637
-        return min(order, steps + 1 - k) if steps < 10 else order   # dpm_solver.py:1198-1201
+        if lower_order_final and (unipc or steps < 10):        # uni_pc.py:636-637 (any steps) / dpm_solver.py:1198-1201 (< 10)
+            return min(order, steps + 1 - k)
+        return order
+
+    def unipc_rhos(k: int, so: int):
+        """B_h and the UniPC-bh rhos of update k at order so >= 2 (uni_pc.py:499-541): rk, rhos_p, rhos_c"""
+        h = lam[k] - lam[k - 1]
+        hh = -h
+        h_phi_1 = np.expm1(hh)
+        B_h = np.expm1(hh) if variant == "bh2" else hh
+        rks = [(lam[k - 1 - j] - lam[k - 1]) / h for j in range(1, so)] + [1.0]
+        b, h_phi_k, fac = [], h_phi_1 / hh - 1.0, 1
+        for i in range(1, so + 1):
+            b.append(h_phi_k * fac / B_h)
+            fac *= i + 1
+            h_phi_k = h_phi_k / hh - 1.0 / fac
+        R = np.array([[r ** (i - 1) for r in rks] for i in range(1, so + 1)])
+        rc = np.linalg.solve(R, np.array(b))
+        rp = np.linalg.solve(R[:-1, :-1], np.array(b[:-1])) if so == 3 else np.array([0.5])
+        return B_h, rks, rp, rc
 
     prev_pc = 0.0
     for i in range(steps):
@@ -146,41 +248,84 @@ def build_table(solver: str, steps: int, betas: Optional[np.ndarray] = None, ord
         # ---- correction of the state at t_i (uses the update that landed on ts[i])
         if i == 0:
             row[3] = row[4] = 0.0
-        elif solver == "dpmsolver++":
+        elif not unipc:
             row[3], row[4] = prev_pc, 0.0
         else:
             k = i
-            h = lam[k] - lam[k - 1]
-            hh = -h
-            h_phi_1 = np.expm1(hh)
-            B_h = np.expm1(hh)
-            ab = alpha[k] * B_h
-            if step_order(k) == 1:
-                rho0, rho1 = 0.0, 0.5                            # uni_pc.py:541-542
+            so = step_order(k)
+            if so <= 2:
+                h = lam[k] - lam[k - 1]
+                hh = -h
+                h_phi_1 = np.expm1(hh)
+                B_h = np.expm1(hh) if variant == "bh2" else hh
+                if so == 1:
+                    rho0, rho1 = 0.0, 0.5                        # uni_pc.py:541-542
+                else:
+                    rk = (lam[k - 2] - lam[k - 1]) / h
+                    h_phi_k = h_phi_1 / hh - 1.0
+                    b0 = h_phi_k / B_h
+                    b1 = (h_phi_k / hh - 0.5) * 2.0 / B_h
+                    rho0, rho1 = np.linalg.solve(np.array([[1.0, 1.0], [rk, 1.0]]), np.array([b0, b1]))   # :544
             else:
-                rk = (lam[k - 2] - lam[k - 1]) / h
-                h_phi_k = h_phi_1 / hh - 1.0
-                b0 = h_phi_k / B_h
-                b1 = (h_phi_k / hh - 0.5) * 2.0 / B_h
-                rho0, rho1 = np.linalg.solve(np.array([[1.0, 1.0], [rk, 1.0]]), np.array([b0, b1]))   # :544
+                B_h, _, _, rc = unipc_rhos(k, 3)
+                rho0, rho1 = rc[0], rc[2]                        # rc_1 went into d1 (d2c of row k-1)
+            ab = alpha[k] * B_h
             row[3], row[4] = ab * rho0, ab * rho1
             det["rho0"][k], det["rho1"][k] = rho0, rho1
         # ---- move towards t_{i+1}
         k = i + 1
         h = lam[k] - lam[k - 1]
         phi = np.expm1(-h)                                       # = h_phi_1 = B_h (bh2) with hh = -h
+        so = step_order(k)
         row[5] = sigma[k] / sigma[k - 1]
         row[6] = alpha[k] * phi
-        det["h"][k], det["B_h"][k], det["order"][k] = h, phi, step_order(k)
-        if step_order(k) == 2:
+        B_h = phi if (not unipc or variant == "bh2") else -h
+        det["h"][k], det["B_h"][k], det["order"][k] = h, B_h, so
+        if so == 2:
             rk = (lam[k - 2] - lam[k - 1]) / h                   # = -r0 of dpm_solver.py:822
             row[7] = 1.0 / rk
-            row[8] = 0.5 * alpha[k] * phi
+            if not unipc and solver_type == "taylor":
+                row[8] = -alpha[k] * (phi / h + 1.0)             # dpm_solver.py:826-829
+            else:
+                row[8] = 0.5 * alpha[k] * B_h
             det["rk"][k] = rk
+        elif so == 3 and unipc:
+            B_h, rks, rp, rc = unipc_rhos(k, 3)
+            ab = alpha[k] * B_h
+            row[7] = 1.0 / rks[0]
+            row[10] = (rc[1] / rc[0]) / rks[1]
+            row[8] = ab * rp[0]
+            row[11] = ab * rp[1] / rks[1] - row[8] * row[10]
+            det["rk"][k] = rks[0]
+        elif so == 3:
+            # dpm_solver.py:871-889 with u = m_prev - m = -(model_prev_0 - model_prev_1), v = m_prev2 - m:
+            # D1_0 = -u/r0, D1_1 = (u - v)/r1, x_t = xbar' + a*phi2*D1 - a*phi3*D2 = xbar' + c_u*u + c_v*v
+            r0 = (lam[k - 1] - lam[k - 2]) / h
+            r1 = (lam[k - 2] - lam[k - 3]) / h
+            phi2 = phi / h + 1.0
+            phi3 = phi2 / h - 0.5
+
+            def x_minus_xbar(u, v):
+                d10, d11 = -u / r0, (u - v) / r1
+                D1 = d10 + (r0 / (r0 + r1)) * (d10 - d11)
+                D2 = (1.0 / (r0 + r1)) * (d10 - d11)
+                return alpha[k] * phi2 * D1 - alpha[k] * phi3 * D2
+
+            c_u, c_v = x_minus_xbar(1.0, 0.0), x_minus_xbar(0.0, 1.0)
+            row[8] = 0.5 * alpha[k] * phi
+            row[7] = -c_u / row[8]
+            row[10] = -c_v / row[8]
+            det["rk"][k] = -r0
         else:
             row[7] = row[8] = 0.0
         prev_pc = row[8]
-    return SolverTable(solver, steps, coef.astype(np.float32), ts, det)
+    if denoise_to_zero:              # uni_pc.py:660-665 / dpm_solver.py:1228-1233: x_start of one more evaluation at t_0
+        row = coef[steps]
+        t0 = float(np.float32(t_0))
+        row[0] = sched.model_time(t0)
+        row[1], row[2] = sched.alpha(t0), sched.sigma(t0)
+        row[5], row[6] = 0.0, -1.0
+    return SolverTable(solver, rows, coef.astype(np.float32), ts, det)
 
 
 def _discrete_buffers(betas: np.ndarray) -> Dict[str, np.ndarray]:
@@ -249,6 +394,11 @@ def _discrete_table(solver: str, steps: int, betas: Optional[np.ndarray], eta: f
     return SolverTable(solver, steps, coef.astype(np.float32), times_out, {"pairs": np.array(pairs, dtype=np.int64)})
 
 
+def has_history2(table: SolverTable) -> bool:
+    """the table needs m_prev2 (some row of order 3): what the engine's ns2vc_sampler_load detects from columns 10-11"""
+    return bool((np.asarray(table.coef)[:, 10:12] != 0).any())
+
+
 def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarray], x_T: np.ndarray,
                     trace: Optional[List[np.ndarray]] = None, noise_fn: Optional[Callable[[int], np.ndarray]] = None) -> np.ndarray:
     """Host executor of the unified recurrence (float32), used by CPU tests to pin
@@ -259,6 +409,8 @@ def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray]
     xe = xbar.copy()
     d1 = np.zeros_like(xbar)
     m_prev = np.zeros_like(xbar)
+    m_prev2 = np.zeros_like(xbar)
+    hist2 = has_history2(table)
     B = x_T.shape[0]
     for i in range(table.steps):
         t_model, alpha, sigma, g0, g1, A, Bc, d1c, pc = (f(v) for v in table.coef[i, :9])
@@ -271,8 +423,14 @@ def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray]
             if noise_fn is None:
                 raise ValueError(f"step {i} of this {table.solver} table adds noise: pass noise_fn")
             xbar = xbar + f(table.coef[i, 9]) * np.asarray(noise_fn(i), dtype=f)
-        d1 = d1c * (m_prev - m)
-        xe = xbar - pc * d1
+        if hist2:
+            d2c, pe = f(table.coef[i, 10]), f(table.coef[i, 11])
+            d1 = d1c * (m_prev - m) + d2c * (m_prev2 - m)
+            xe = xbar - pc * d1 - pe * (m_prev2 - m)
+            m_prev2 = m_prev
+        else:
+            d1 = d1c * (m_prev - m)
+            xe = xbar - pc * d1
         m_prev = m
         if trace is not None:
             trace.append(xe.copy())

@@ -37,6 +37,7 @@ import numpy as np
 from .frontend import PreModel
 from .noise import derive_seed
 from .pipeline import Denoiser, OverlappedPipeline
+from .schedule import table_options
 
 
 @dataclass
@@ -61,12 +62,14 @@ class GroupedConverter:
     ragged = False      # the default mode (exact-shape groups), also for an instance that only plans (built without __init__)
 
     def __init__(self, pre_model: PreModel, denoiser: Denoiser, decode_fn: Optional[Callable] = None, max_batch: int = 32,
-                 solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, ragged: bool = False, eta: float = 0.0):
+                 solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, ragged: bool = False, eta: float = 0.0,
+                 **options):
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
         self.max_batch, self.seed, self.ragged = max_batch, seed, ragged
         if solver == "ddpm" and steps == 30:      # (the constructor's default step count is the continuous solvers'; ddpm runs every timestep)
             steps = None
-        self.kw = dict(solver=solver, steps=steps, order=order, eta=eta)
+        table_options(options)           # the keyword-only sampler options of Denoiser.sample (skip_type, denoise_to_zero, ...)
+        self.kw = dict(solver=solver, steps=steps, order=order, eta=eta, **options)
 
     def _seeds(self, idx) -> np.ndarray:
         """per-SEGMENT noise seeds of the stochastic samplers, from the converter's seed and the segment's position in the input"""
