@@ -1616,21 +1616,37 @@ int ns2vc_device_xcd_round_robin(int* out) {
 
 int ns2vc_unet_create(const ns2vc_unet_cfg* cfg, ns2vc_unet** out) {
   if (!cfg || !out) return fail("null argument");
-  if (cfg->n_levels < 2 || cfg->n_levels > NS2VC_MAX_LEVELS) return fail("n_levels out of range");
-  if (cfg->latent_channels <= 0 || cfg->latent_channels > 128) return fail("latent_channels must be in 1..128");
-  if (cfg->content_channels % 64) return fail("content_channels must be a multiple of 64");
-  if (cfg->cross_attention_dim % 128) return fail("cross_attention_dim must be a multiple of 128");
-  if (cfg->block_out_channels[0] != 128) return fail("block_out_channels[0] must be 128 (padded latent width)");
+  // every message names the offending field (ns2vc_amd.spec.engine_supports states the same predicate); the divisors are range-checked
+  // before they divide
+  if (cfg->n_levels < 2 || cfg->n_levels > NS2VC_MAX_LEVELS) return fail("n_levels=%d out of range (2..%d)", cfg->n_levels, NS2VC_MAX_LEVELS);
+  if (cfg->latent_channels <= 0 || cfg->latent_channels > 128) return fail("latent_channels=%d must be in 1..128", cfg->latent_channels);
+  if (cfg->content_channels <= 0 || cfg->content_channels % 64)
+    return fail("content_channels=%d must be a positive multiple of 64", cfg->content_channels);
+  if (cfg->cross_attention_dim <= 0 || cfg->cross_attention_dim % 128)
+    return fail("cross_attention_dim=%d must be a positive multiple of 128", cfg->cross_attention_dim);
+  if (cfg->heads < 1) return fail("heads=%d must be >= 1", cfg->heads);
+  if (cfg->norm_num_groups < 1 || cfg->norm_num_groups > 8) return fail("norm_num_groups=%d unsupported (1..8)", cfg->norm_num_groups);
+  if (cfg->layers_per_block < 1) return fail("layers_per_block=%d must be >= 1", cfg->layers_per_block);
+  if (cfg->pool_heads < 1 || cfg->cross_attention_dim % cfg->pool_heads || cfg->cross_attention_dim / cfg->pool_heads > 8)
+    return fail("cross_attention_dim=%d over pool_heads=%d: the pool head width must be a whole number <= 8", cfg->cross_attention_dim, cfg->pool_heads);
+  if (cfg->block_out_channels[0] != 128) return fail("block_out_channels[0]=%d must be 128 (padded latent width)", cfg->block_out_channels[0]);
   for (int l = 0; l < cfg->n_levels; ++l) {
     const int c = cfg->block_out_channels[l];
-    if (c % 64 || c > 512) return fail("block_out_channels[%d]=%d must be a multiple of 64 and <= 512", l, c);
-    if (c % cfg->heads) return fail("channels %d not divisible by heads %d", c, cfg->heads);
+    // (a multiple of 128: the transformer's LayerNorm -- by linearity or explicit, ln_apply_op -- takes rows of 128k <= 512 channels)
+    if (c <= 0 || c % 128 || c > 512) return fail("block_out_channels[%d]=%d must be a multiple of 128 in 128..512", l, c);
+    if (c % cfg->heads) return fail("block_out_channels[%d]=%d not divisible by heads=%d", l, c, cfg->heads);
     const int hd = c / cfg->heads;
-    if (hd != 16 && hd != 32 && hd != 48 && hd != 64) return fail("head_dim %d unsupported (16/32/48/64)", hd);
-    if (c % cfg->norm_num_groups || (c / cfg->norm_num_groups) % 4) return fail("channels %d incompatible with %d groups", c, cfg->norm_num_groups);
+    if (hd != 16 && hd != 32 && hd != 48 && hd != 64)
+      return fail("heads=%d gives head width %d at block_out_channels[%d]=%d (16/32/48/64 supported)", cfg->heads, hd, l, c);
+    if (c % cfg->norm_num_groups || (c / cfg->norm_num_groups) % 4)
+      return fail("block_out_channels[%d]=%d incompatible with norm_num_groups=%d (group width must be a multiple of 4)", l, c, cfg->norm_num_groups);
   }
-  if (cfg->norm_num_groups < 1 || cfg->norm_num_groups > 8) return fail("norm_num_groups=%d unsupported (1..8)", cfg->norm_num_groups);
-  if (cfg->cross_attention_dim % cfg->pool_heads || cfg->cross_attention_dim / cfg->pool_heads > 8) return fail("pool heads unsupported");
+  // the GroupNorm kernels take groups of at most 128 channels: the widest GroupNorm input is an up block's concat [h ; skip]
+  for (const BlockW& b : make_topology(*cfg))
+    for (const ResnetW& r : b.res)
+      if (r.cin / cfg->norm_num_groups > 128)
+        return fail("norm_num_groups=%d: the GroupNorm over the %d input channels of %s has groups of %d channels (<= 128 supported)",
+                    cfg->norm_num_groups, r.cin, r.prefix.c_str(), r.cin / cfg->norm_num_groups);
   hipError_t e = init_gemm_attributes();
   if (e == hipSuccess) e = init_convts_attributes();
   if (e == hipSuccess) e = init_attn_attributes();
@@ -2353,7 +2369,7 @@ int ns2vc_pack_weight(const float* rows_host, int N, int K, int precision, void*
   static bool inited = false;
   if (!inited) {
     hipError_t e = init_gemm_attributes();
-  if (e == hipSuccess) e = init_convts_attributes();
+    if (e == hipSuccess) e = init_convts_attributes();
     if (e == hipSuccess) e = init_attn_attributes();
     if (e == hipSuccess) e = init_ffn_attributes();
     if (e == hipSuccess) e = init_geglu_attributes();

@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import Ns2vcError, PREC_BF16, PREC_F16, PREC_F32, check
 from .schedule import NCOEF, SolverTable, build_table
-from .spec import UNetConfig, param_spec
+from .spec import UNetConfig, engine_block_types, engine_supports, param_spec
 
 # operand precision of the MFMAs (include/ns2vc_hip.h): fp16 is the default 16-bit mode -- same speed and bytes as bf16,
 # 7e-4 end-to-end error (inside the 1e-3 parity gate) instead of 5.7e-3
@@ -179,6 +179,8 @@ class Engine:
         cfg.validate()
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
+        if (tuple(cfg.down_block_types), tuple(cfg.up_block_types)) != engine_block_types(len(cfg.block_out_channels)):
+            raise ValueError(engine_supports(cfg))     # the C ABI does not carry block types: the engine would build another topology
         self.cfg = cfg
         self.precision = precision
         self.lib = _lib.load()

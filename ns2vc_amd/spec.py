@@ -74,6 +74,57 @@ class UNetConfig:
                 raise ValueError(f"channels {c} not divisible by groups/heads")
 
 
+def engine_block_types(n_levels: int) -> Tuple[Tuple[str, ...], Tuple[str, ...]]:
+    """The (down, up) block types the HIP engine builds for ``n_levels`` levels (csrc/engine.cpp make_topology): cross-attention at every
+    level but the deepest."""
+    return (("CrossAttnDownBlock2D",) * (n_levels - 1) + ("DownBlock2D",),
+            ("UpBlock2D",) + ("CrossAttnUpBlock2D",) * (n_levels - 1))
+
+
+def engine_supports(cfg: UNetConfig) -> str | None:
+    """None when the HIP engine accepts ``cfg``, else the reason, naming the field.  The same predicate as ``ns2vc_unet_create``
+    (csrc/engine.cpp) plus the block types, which the C ABI does not carry; ``validate()`` accepts more (e.g. 4 heads on the stock
+    channels, 16 groups, cross_attention_dim 192)."""
+    chans, n = cfg.block_out_channels, len(cfg.block_out_channels)
+    heads, groups, cross, pool = cfg.heads, cfg.norm_num_groups, cfg.cross_attention_dim, cfg.addition_embed_heads
+    if not 2 <= n <= 8:
+        return f"n_levels={n} out of range (2..8)"
+    if not 1 <= cfg.latent_channels <= 128:
+        return f"latent_channels={cfg.latent_channels} must be in 1..128"
+    if cfg.content_channels <= 0 or cfg.content_channels % 64:
+        return f"content_channels={cfg.content_channels} must be a positive multiple of 64"
+    if cross <= 0 or cross % 128:
+        return f"cross_attention_dim={cross} must be a positive multiple of 128"
+    if heads < 1:
+        return f"heads={heads} must be >= 1"
+    if not 1 <= groups <= 8:
+        return f"norm_num_groups={groups} unsupported (1..8)"
+    if cfg.layers_per_block < 1:
+        return f"layers_per_block={cfg.layers_per_block} must be >= 1"
+    if pool < 1 or cross % pool or cross // pool > 8:
+        return f"cross_attention_dim={cross} over pool_heads={pool}: the pool head width must be a whole number <= 8"
+    if chans[0] != 128:
+        return f"block_out_channels[0]={chans[0]} must be 128 (padded latent width)"
+    for l, c in enumerate(chans):
+        if c <= 0 or c % 128 or c > 512:
+            return f"block_out_channels[{l}]={c} must be a multiple of 128 in 128..512"
+        if c % heads:
+            return f"block_out_channels[{l}]={c} not divisible by heads={heads}"
+        if c // heads not in (16, 32, 48, 64):
+            return f"heads={heads} gives head width {c // heads} at block_out_channels[{l}]={c} (16/32/48/64 supported)"
+        if c % groups or (c // groups) % 4:
+            return f"block_out_channels[{l}]={c} incompatible with norm_num_groups={groups} (group width must be a multiple of 4)"
+    down, up = engine_block_types(n)
+    if tuple(cfg.down_block_types) != down or tuple(cfg.up_block_types) != up:
+        return f"down_block_types / up_block_types must be {down} / {up} (cross-attention at every level but the deepest)"
+    for b in topology(cfg):
+        for r in b.resnets:
+            if r.cin // groups > 128:
+                return (f"norm_num_groups={groups}: the GroupNorm over the {r.cin} input channels of {r.prefix} has groups of "
+                        f"{r.cin // groups} channels (<= 128 supported)")
+    return None
+
+
 # ----------------------------------------------------------------------------
 # Topology: a flat description of the blocks, shared by spec / oracle / engine
 # ----------------------------------------------------------------------------

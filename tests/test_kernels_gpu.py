@@ -417,11 +417,14 @@ def test_gemm_groupnorm_prologue_of_a_concat(tile, prec, diag):
     from ns2vc_amd._lib import GemmArgs, check
     from ns2vc_amd.engine import DevBuf, sync
     lib = _lib()
-    for (B, T, c0, c1, N, taps) in ((3, 167, 128, 128, 128, 3), (2, 131, 512, 384, 512, 3), (3, 70, 512, 512, 256, 3), (2, 140, 256, 384, 384, 1)):
+    # (the last two: the 128 + 256 / 256 + 128 concats of the non-default configurations, tests/configs.py, in 4 groups of 96 -- the
+    #  seam inside the second / third group)
+    for (B, T, c0, c1, N, taps, Gn) in ((3, 167, 128, 128, 128, 3, 8), (2, 131, 512, 384, 512, 3, 8), (3, 70, 512, 512, 256, 3, 8), (2, 140, 256, 384, 384, 1, 8),
+                                        (2, 131, 128, 256, 128, 3, 4), (3, 70, 256, 128, 256, 3, 4)):
         if tile[2] in TS_STAGES and (taps != 3 or N % tile[1]):
             continue
         rng = np.random.default_rng(B * 1000 + T + c0 + c1)
-        Cc, Gn = c0 + c1, 8
+        Cc = c0 + c1
         M, K = B * T, taps * Cc
         x0 = (rng.standard_normal((B, T, c0)) * (1.0 + rng.random((B, 1, c0))) + rng.standard_normal((B, 1, c0))).astype(np.float32)
         x1 = (rng.standard_normal((B, T, c1)) * 0.5 + rng.standard_normal((B, 1, c1))).astype(np.float32)
@@ -1547,13 +1550,17 @@ def test_attention_fallback_rate_and_cost_at_the_bench_shape(diag):
 
 
 @pytest.mark.parametrize("prec", PRECS, ids=PREC_IDS)
-@pytest.mark.parametrize("shape", [(2, 37, 128, 0), (2, 90, 512, 384), (3, 200, 384, 256), (1, 5, 128, 128), (2, 938, 128, 0)], ids=str)
+@pytest.mark.parametrize("shape", [(2, 37, 128, 0), (2, 90, 512, 384), (3, 200, 384, 256), (1, 5, 128, 128), (2, 938, 128, 0),
+                                   # (B, T, c0, c1, G) of the non-default configurations (tests/configs.py): 24- and 40-wide groups (192 / 8,
+                                   # 320 / 8, the seam at 192 inside a group), 1 / 2 / 4 groups, 80-wide groups across a 192 + 128 seam
+                                   (2, 37, 192, 0, 8), (2, 45, 192, 128, 8), (2, 45, 128, 192, 8), (2, 45, 128, 0, 1), (2, 45, 128, 0, 2),
+                                   (3, 45, 256, 0, 4), (2, 45, 192, 128, 4), (2, 23, 256, 0, 2)], ids=str)
 def test_groupnorm(shape, prec, diag):
     """group_norm (+ the resnet's time scale/shift, + SiLU) over a two-source concat whose groups straddle the seam."""
     from ns2vc_amd._lib import check
     lib = _lib()
-    B, T, c0, c1 = shape
-    G = 8
+    B, T, c0, c1 = shape[:4]
+    G = shape[4] if len(shape) > 4 else 8
     C_ = c0 + c1
     rng = np.random.default_rng(B * 1000 + T)
     a0 = (rng.standard_normal((B, T, c0)) * 2 + 0.7).astype(np.float32)
@@ -1703,6 +1710,19 @@ def test_rowchain_fused(dim, mult, M, res, nt, prec, diag):
 @pytest.mark.parametrize("dim,B,T,nt", [(128, 3, 150, 1), (128, 5, 64, 2), (256, 2, 97, 1), (128, 2, 300, 2), (256, 4, 64, 1), (384, 3, 97, 1),
                                         (384, 2, 235, 1), (384, 3, 235, -2)], ids=str)
 def test_rowchain_groupnorm_prologue(dim, B, T, nt, prec, diag):
+    _rowchain_groupnorm_prologue(dim, B, T, nt, 8, prec, diag)
+
+
+@pytest.mark.parametrize("prec", [1, 2], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("dim,B,T,nt,G", [(128, 3, 150, 1, 4), (256, 2, 97, 1, 4), (384, 3, 97, 1, 4), (128, 2, 300, 2, 2), (128, 4, 64, 1, 1),
+                                          (256, 3, 235, 1, 2)], ids=str)
+def test_rowchain_groupnorm_prologue_groups(dim, B, T, nt, G, prec, diag):
+    """the same with the group counts of the non-default configurations (tests/configs.py: 4 groups of lpb1_g4, and 1 / 2; groups of at
+    most 128 channels, what ns2vc_unet_create admits)"""
+    _rowchain_groupnorm_prologue(dim, B, T, nt, G, prec, diag)
+
+
+def _rowchain_groupnorm_prologue(dim, B, T, nt, Gn, prec, diag):
     """The row-chain kernel with the transformer's GroupNorm in its prologue: A = GroupNorm(x) (8 groups, affine, eps 1e-6) is
     built inside the kernel from the fp32 rows and the int64 per-(item, 16-channel block) statistics a producer's epilogue
     leaves, for token blocks that straddle up to three batch items and both workgroup sizes.  Reference: numpy fp64 with the
@@ -1712,7 +1732,7 @@ def test_rowchain_groupnorm_prologue(dim, B, T, nt, prec, diag):
     from ns2vc_amd.engine import DevBuf, sync
     lib = _lib()
     rng = np.random.default_rng(dim + 7 * B + T)
-    d, M, Gn = dim, B * T, 8
+    d, M = dim, B * T
     x = (rng.standard_normal((B, T, d)) * (1.0 + rng.random((B, 1, d))) + rng.standard_normal((B, 1, d))).astype(np.float32)
     gam, bet = (1.0 + 0.2 * rng.standard_normal(d)).astype(np.float32), (0.2 * rng.standard_normal(d)).astype(np.float32)
     blk = x.astype(np.float64).reshape(B, T, d // 16, 16)
@@ -1761,7 +1781,7 @@ def test_rowchain_groupnorm_prologue(dim, B, T, nt, prec, diag):
             lib.ns2vc_debug_set_rowchain_tokens(0)
         yo, zo = d_y.to_numpy((M, d)), d_z.read()
         e_y, e_z = rel_l2(yo, y), rel_l2(zo, z)
-        diag(f"rowchain+GroupNorm dim={d} B={B} T={T} nt={nt} n2={n2} prec={prec}: y {e_y:.3e} z {e_z:.3e}")
+        diag(f"rowchain+GroupNorm dim={d} G={Gn} B={B} T={T} nt={nt} n2={n2} prec={prec}: y {e_y:.3e} z {e_z:.3e}")
         # (ns2vc_k_groupnorm finalises its statistics from a separate fp64 pass, the prologue from the int64 epilogue sums: the two
         # normalised rows agree except where a value sits on a rounding boundary of the operand type -- a ~1e-4 fraction of
         # elements, one operand ulp each; inside the engine both paths read the same int64 sums and are bit-identical,
