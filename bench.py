@@ -26,15 +26,20 @@ RCCL sees more than one rank, but not the first time the harness around it runs.
 `--dump-outputs DIR` writes the latents the timed path returned in its last job as DIR/latent.npy (float32, <= 64 MB), so that two
 builds can be compared output for output on the same seeded inputs.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement), with
+Prints ONE JSON line on rank 0 (see the driver contract in the task statement).  A plain run does only what that line's headline
+needs: set up, warm up, time the jobs, write --dump-outputs, print the line (`roofline`, `parity`, `cpu_baseline` and
+`graph_equals_eager` are null in it).  `--full` adds everything else the benchmark measures or checks:
+  graph_equals_eager  the timed (captured) loop against the same loop launched eagerly, bit for bit; the kernel counters
+                (attention fall-backs, cooperative GroupNorm prologue workgroups alone)
   roofline      dominant kernel family (implicit GEMM: gemm4 + fused feed-forward + row chains) vs the dense MFMA peak;
                 `achieved` = the family's share of the TIMED loop, `isolated` = its launches timed back to back with HIP events
   parity        rel-L2 of the timed precision's predicted latent vs the oracle AT THE BENCH SHAPE (B=32), and
                 `sampled_latent`: the timed solver's output (captured loop, B=32) vs oracle.sampler_ref on the first utterances
-  fp32_parity_mode   the same job and roofline in the exact-fp32 precision
+  cpu_baseline  the oracle on the host cores: all cores (P processes x T threads) and one process, at B=32
+  and the long legs, whose results go to the detail file only (each can be left out with its --skip-* option):
+  self_check, fp32_parity_mode   the served Denoiser's precision self-check; the same job and roofline in the exact-fp32 precision
   other_configs BASELINE configs 2 and 5 (default and --attn-fp8) timed the same way, with parity against the fp32 engine
   strong_scaling     BASELINE config 4's global batch (256) split over the N ranks
-  cpu_baseline  the oracle on the host cores: all cores (P processes x T threads) and one process, at B=32
 """
 from __future__ import annotations
 
@@ -73,12 +78,13 @@ def parse():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--attn-fp8", action="store_true", help="PV product of every attention on the fp8 MFMA (BASELINE config 5's fp8 path; "
                     "costs parity, see DESIGN.md section 4)")
-    ap.add_argument("--full", action="store_true", help="also run the long legs (self_check, fp32_parity_mode, bf16_as_stated, other_configs = BASELINE configs 2 and 5, "
-                    "strong_scaling, the larger CPU grid); their results go to the detail file, the stdout line stays the compact one "
-                    "(printed before the long legs start and again as the last line)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: the graph-vs-eager loop check and "
+                    "kernel counters, the per-kernel family table and roofline, the CPU baseline and parity vs the oracle (all in the stdout line), "
+                    "and the long legs (self_check, fp32_parity_mode, bf16_as_stated, other_configs = BASELINE configs 2 and 5, strong_scaling, the "
+                    "larger CPU grid; their results go to the detail file, the line is printed before they start and again as the last line)")
     ap.add_argument("--detail-json", default=os.path.join(ROOT, "bench_detail.json"), help="where rank 0 writes the full record (every block of the compact line "
                     "unabridged + the --full legs); '' = do not write")
-    ap.add_argument("--skip-cpu", action="store_true", help="skip the CPU-baseline / parity legs")
+    ap.add_argument("--skip-cpu", action="store_true", help="(--full) skip the CPU-baseline / parity legs")
     ap.add_argument("--skip-fp32", action="store_true", help="(--full) skip the fp32_parity_mode block")
     ap.add_argument("--skip-others", action="store_true", help="(--full) skip the other_configs block (BASELINE configs 2 and 5)")
     ap.add_argument("--skip-strong", action="store_true", help="(--full) skip the strong_scaling block (global batch 256 split over the ranks)")
@@ -88,10 +94,10 @@ def parse():
     ap.add_argument("--dry-dist", type=int, default=0, metavar="N", help="harness rehearsal WITHOUT GPUs: N ranks on the gloo backend, the engine replaced by "
                     "a sleep + deterministic fill; exercises the spawn, every barrier, the all-gather of latents, the per-rank reduction, the "
                     "strong_scaling block and the JSON line exactly as --gpus N does (tests/test_cpu.py runs it at N = 2 and 8)")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of TIMED CPU work for the baseline grid (split over its legs; the parity "
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="(--full) seconds of TIMED CPU work for the baseline grid (split over its legs; the parity "
                     "references are extra and unbudgeted: one batch-B forward + the sampled latent of 2 utterances)")
-    ap.add_argument("--ops", default="", help="write the per-launch table (name, kind, ms, GFLOP, MB) to this file")
-    ap.add_argument("--detail", action="store_true", help="print the per-kernel-family table to stderr")
+    ap.add_argument("--ops", default="", help="(--full) write the per-launch table (name, kind, ms, GFLOP, MB) to this file")
+    ap.add_argument("--detail", action="store_true", help="(--full) print the per-kernel-family table to stderr")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed jobs, write what the timed path returned in its last job "
                     "(the sampled latents, gathered over the ranks) as DIR/<name>.npy, float32, at most 64 MB in all (beyond that a fixed, "
                     "seeded sample of utterances); the inputs are seeded, so two builds can be compared output for output")
@@ -101,7 +107,10 @@ def parse():
     ap.add_argument("--cpu-pin", default="", help=argparse.SUPPRESS)                  # internal: "lo-hi" core range of one all-core worker
     ap.add_argument("--cpu-batch", type=int, default=2, help=argparse.SUPPRESS)       # internal: batch of one all-core worker
     ap.add_argument("--cpu-weights", default="", help=argparse.SUPPRESS)              # internal: flat fp32 weight file the workers map (written once by the parent)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if (a.ops or a.detail) and not a.full:          # the per-kernel family table is a --full leg: refuse rather than write nothing
+        ap.error("--ops and --detail need --full")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------
@@ -197,17 +206,16 @@ def cpu_worker(seconds: float, threads: int, T: int, Lp: int, B: int = 2, weight
     print(json.dumps({"samples": n, "seconds": time.perf_counter() - t0}), flush=True)
 
 
-def cpu_grid(cores_eff: int, full: bool):
+def cpu_grid(cores_eff: int):
     """(processes, threads, batch) legs of the baseline grid.  Many small processes is what a throughput-minded host would run (r5 review):
-    with E usable cores the default legs are E/8 x 8, E/4 x 4 and E/2 x 2 threads at batch 2 (= 32x8, 64x4, 128x2 on an unthrottled 256-CPU
-    host; 2x8, 4x4, 8x2 under this pool's 16-CPU quota); --full adds E x 1 at batch 1 and E/16 x 16 at batch 4."""
+    with E usable cores the legs are E/8 x 8, E/4 x 4 and E/2 x 2 threads at batch 2 (= 32x8, 64x4, 128x2 on an unthrottled 256-CPU
+    host; 2x8, 4x4, 8x2 under a 16-CPU quota), E x 1 at batch 1 and E/16 x 16 at batch 4."""
     legs = [(max(1, cores_eff // t), t, 2) for t in (8, 4, 2) if t <= cores_eff]
-    if full:
-        legs += [(cores_eff, 1, 1)] + ([(cores_eff // 16, 16, 4)] if cores_eff >= 32 else [])
+    legs += [(cores_eff, 1, 1)] + ([(cores_eff // 16, 16, 4)] if cores_eff >= 32 else [])
     return [g for g in dict.fromkeys(legs) if g[0] >= 1]
 
 
-def cpu_baseline(T: int, Lp: int, B: int, budget_s: float, sampler=None, W=None, full=False):
+def cpu_baseline(T: int, Lp: int, B: int, budget_s: float, sampler=None, W=None):
     """(1) one process at the bench batch (its output is also the parity reference, timed as the `single_process` leg); (2) the grid of
     cpu_grid(): P processes x T threads, every worker pinned to its own disjoint cores, weights mapped from one shared file, started
     together after their warm-up, samples/s summed, the best leg (or the single process, if faster) is `value`; (3) `sampler` = (solver,
@@ -236,7 +244,7 @@ def cpu_baseline(T: int, Lp: int, B: int, budget_s: float, sampler=None, W=None,
         single = {"sample_steps_per_s": B / dt, "processes": 1, "threads_per_process": th, "batch_per_process": B, "seconds": dt}
         # ---- the grid
         sweep, agg = [], None
-        grid = cpu_grid(eff, full)
+        grid = cpu_grid(eff)
         secs = max(2.5, budget_s / max(len(grid), 1))
         avail = sorted(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else list(range(visible))
         for nproc, tha, bw in grid:
@@ -456,7 +464,7 @@ def compact_line(d: dict) -> dict:
         if k in d:
             o[k] = rnd(d[k], 4)
     o["device"] = d["device"]
-    o["detail"] = "bench_detail.json (every block unabridged; --full adds fp32 / bf16 / configs 2 and 5 / strong scaling)"
+    o["detail"] = "bench_detail.json (every block unabridged; --full adds the roofline, parity, CPU baseline, fp32 / bf16 / configs 2 and 5 / strong scaling)"
     return o
 
 
@@ -682,11 +690,13 @@ def main():
     wall = statistics.median(walls)
     finite = bool(torch.isfinite(x).all().item())
     x_timed = x.clone()
-    # the timed (captured-graph) loop must return exactly what the same loop launched eagerly returns
-    loop_check = None
-    attn_fb = None if dry else eng.attn_fallbacks(reset=True, stream=stream)          # workgroups that paid an attention kernel twice, all jobs so far
-    gn_alone = None if dry else eng.gn_coop_alone(reset=True, stream=stream)         # cooperative GroupNorm prologue: workgroups that waited in vain for a sibling, all jobs so far
-    if use_graph and not dry:
+    # (--full) the timed (captured-graph) loop must return exactly what the same loop launched eagerly returns
+    loop_check = attn_fb = gn_alone = None
+    checks = a.full and not dry
+    if checks:
+        attn_fb = eng.attn_fallbacks(reset=True, stream=stream)          # workgroups that paid an attention kernel twice, all jobs so far
+        gn_alone = eng.gn_coop_alone(reset=True, stream=stream)          # cooperative GroupNorm prologue: workgroups that waited in vain for a sibling, all jobs so far
+    if use_graph and checks:
         with torch.cuda.stream(stream):
             x.copy_(io["noise"])
             eng.set_condition(io["content"], io["prompt"], io["mask"], stream=stream)
@@ -728,15 +738,15 @@ def main():
     if rank == 0:
         step_ms = wall * 1e3 / K
         fam = roof = None
-        if not dry:
+        if checks:
             fam = family_table(eng, stream, a.ops)
             roof = roofline_block(fam, a.precision, step_ms, gflop_sample, B, (B, T, Lp))
 
-        # ---- CPU baseline (oracle on the host cores) + parity of the timed precision at the bench shape
+        # ---- (--full) CPU baseline (oracle on the host cores) + parity of the timed precision at the bench shape
         cpu = parity = None
-        if world == 1 and not a.skip_cpu and not dry:
+        if checks and world == 1 and not a.skip_cpu:
             try:
-                cpu, ref, samp = cpu_baseline(T, Lp, B, a.cpu_budget, sampler=(solver, K, 2), W=W, full=a.full)
+                cpu, ref, samp = cpu_baseline(T, Lp, B, a.cpu_budget, sampler=(solver, K, 2), W=W)
             except Exception as ex:                      # the baseline leg must never take the GPU number down
                 cpu = {"value": None, "unit": f"denoiser-steps/s (batch {B})", "cores": _host_cores(), "kind": "port", "sample": f"failed: {ex!r}"}
         if ref is not None:
@@ -782,7 +792,7 @@ def main():
         if a.detail and roof:
             for k, v in roof["families"].items():
                 print(f"  {k:14s} {v}", file=sys.stderr)
-        # ---- THE line: compact (< 4 KB), printed as soon as the headline, its roofline, parity and CPU baseline exist -- before any long leg
+        # ---- THE line: compact (< 4 KB), printed as soon as the headline (and with --full its roofline, parity and CPU baseline) exists -- before any long leg
         cl = compact_line(out)
         line = json.dumps(cl)
         for k in ("detail", "jobs_ms", "device", "per_rank_ms_per_step"):      # (never let the size guard take the line down: shed optional keys instead)

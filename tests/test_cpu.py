@@ -645,6 +645,16 @@ def test_bench_dump_outputs_budget(tmp_path):
     assert np.array_equal(np.load(tmp_path / "c" / "small.npy"), small)
 
 
+@pytest.mark.parametrize("flag", [["--ops", "ops.tsv"], ["--detail"]])
+def test_bench_family_table_options_need_full(flag, tmp_path):
+    """The per-kernel family table is a --full leg: a plain run asked for its per-launch file or its stderr table refuses before it
+    starts, instead of running and writing nothing."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-dist", "1", "--steps", "3", "--warmup", "1", "--reps", "2",
+                        "--batch", "2", "--seconds", "1", "--detail-json", ""] + flag, capture_output=True, text=True, timeout=300, cwd=tmp_path)
+    assert r.returncode == 2 and "need --full" in r.stderr and r.stdout == ""
+    assert not (tmp_path / "ops.tsv").exists()
+
+
 def test_repeat_expand_matches_reference_golden():
     """ns2vc_amd.audio.repeat_expand_2d (index map + one gather) against outputs of the reference's own utils.repeat_expand_2d
     (utils.py:482-496): bit-identical, including non-integer ratios, target shorter than source, and batched input."""

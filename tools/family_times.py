@@ -2,7 +2,7 @@
 """rocprofv3 kernel-trace view of the bench loop per kernel family: profiles/<TAG>_family_times.json, which bench.py stamps
 into roofline.rocprof (the in-loop figure it reports itself comes from HIP events; this is the profiler's).
 usage: family_times.py TAG kernel_stats.csv bench_line.json OUTDIR
-  kernel_stats.csv = `rocprofv3 --kernel-trace --stats` of `python bench.py --skip-cpu --skip-fp32 --skip-others --skip-strong ...`,
+  kernel_stats.csv = `rocprofv3 --kernel-trace --stats` of `python bench.py --full --skip-cpu --skip-fp32 --skip-others --skip-strong ...`,
   bench_line.json  = the JSON line that run printed (launches per step and the shape come from it)."""
 import csv, json, os, re, subprocess, sys
 
@@ -53,7 +53,7 @@ for r in csv.DictReader(open(f_stats)):
 # r4's last builds have no norm family left to count by
 n_fwd = calls.get("attention", 0) / max(per_step.get("attention", 1), 1)
 out = {"source": "rocprofv3 --kernel-trace --stats -- " + " ".join(["python bench.py"] + [f"--{k.replace('_', '-')} {v}" for k, v in (("steps", bench["steps"]), ("warmup", bench["warmup"]))])
-                 + " --skip-cpu --reps 3",
+                 + " --full --skip-cpu --skip-fp32 --skip-others --skip-strong --reps 3",
        "precision": bench["dtype"], "shape": [bench["config"]["global_batch"], bench["config"]["frames"], bench["config"]["prompt_frames"]],
        "commit": commit(), "forward_equivalents_in_trace": n_fwd, "step_ms": bench["ms_per_step"],
        "families": {f: {"calls": calls[f], "ms_per_step": tot[f] / 1e6 / max(n_fwd, 1e-9)} for f in tot}}

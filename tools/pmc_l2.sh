@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --skip-cpu --steps 4 --warmup 4 --reps 1 --detail-json= ${PMC_BENCH_ARGS}"
+CMD="python $R/bench.py --full --skip-cpu --skip-fp32 --skip-others --skip-strong --steps 4 --warmup 4 --reps 1 --detail-json= ${PMC_BENCH_ARGS}"
 i=0
 FILES=""
 for G in "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum" \

@@ -90,7 +90,7 @@ for k, c in sorted(per.items()):
     f["n"] += n
 families = {k: {"launches_counted": int(v["n"]), "l2_hit_rate": round(v["hit"] / (v["hit"] + v["miss"]), 4) if v["hit"] + v["miss"] > 0 else None,
                 "l2_req_per_launch": round(v["req"] / v["n"]) if v["n"] else None} for k, v in fam.items()}
-out = {"source": "rocprofv3 --pmc <4 TCC / TCP counters per pass> --kernel-trace -- python bench.py --skip-cpu --steps 4 --warmup 4 --reps 1 (tools/pmc_l2.sh); "
+out = {"source": "rocprofv3 --pmc <4 TCC / TCP counters per pass> --kernel-trace -- python bench.py --full --skip-cpu --skip-fp32 --skip-others --skip-strong --steps 4 --warmup 4 --reps 1 (tools/pmc_l2.sh); "
                  "hit rate = TCC_HIT_sum / (TCC_HIT_sum + TCC_MISS_sum) (MI355X_MICROARCH.md, L2 section); EA = the L2's memory-side interface "
                  "(Infinity Cache + HBM behind it)", "workload": "10 s x batch 32, fp16, unipc", "precision": "fp16", "shape": [32, 938, 469],
        "commit": commit(), "families": families, "kernels": kern}

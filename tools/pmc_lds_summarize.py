@@ -9,8 +9,8 @@ for r in csv.DictReader(open(src)):
     acc[k][r["Counter_Name"]] += float(r["Counter_Value"])
     if r["Counter_Name"] == "SQ_BUSY_CYCLES":
         launches[k] += 1
-out = {"source": "rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_BUSY_CYCLES --kernel-trace -- python bench.py --skip-cpu "
-                 "--skip-fp32 --steps 4 --warmup 4 --reps 1 (own pass)", "commit": os.environ.get("NS2VC_COMMIT"), "kernels": {}}
+out = {"source": "rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_BUSY_CYCLES --kernel-trace -- python bench.py --full --skip-cpu "
+                 "--skip-fp32 --skip-others --skip-strong --steps 4 --warmup 4 --reps 1 (own pass)", "commit": os.environ.get("NS2VC_COMMIT"), "kernels": {}}
 for k, v in sorted(acc.items(), key=lambda kv: -kv[1].get("SQ_BUSY_CYCLES", 0)):
     a, c = v.get("SQ_ACTIVE_INST_LDS", 0.0), v.get("SQ_LDS_BANK_CONFLICT", 0.0)
     if not k.startswith(("gemm", "conv3ts", "attn", "ffn", "geglu", "rowchain", "gn_apply", "time_embed", "solver")):

@@ -13,7 +13,7 @@ for r in csv.DictReader(open(src)):
     names.add(r["Counter_Name"])
     if r["Counter_Name"] == "SQ_WAVE_CYCLES":
         launches[k] += 1
-out = {"source": "rocprofv3 --pmc " + " ".join(sorted(names)) + " --kernel-trace -- python bench.py --skip-cpu --skip-fp32 --skip-others --skip-strong --steps 4 --warmup 4 --reps 1 (own pass)",
+out = {"source": "rocprofv3 --pmc " + " ".join(sorted(names)) + " --kernel-trace -- python bench.py --full --skip-cpu --skip-fp32 --skip-others --skip-strong --steps 4 --warmup 4 --reps 1 (own pass)",
        "commit": os.environ.get("NS2VC_COMMIT"), "kernels": {}}
 for k, v in sorted(acc.items(), key=lambda kv: -kv[1].get("SQ_WAVE_CYCLES", 0)):
     if not k.startswith(("gemm", "conv3ts", "attn", "ffn", "geglu", "rowchain")):
