@@ -17,7 +17,17 @@
  *   - API tensors use the reference's layouts: latent/content (B, C, T) "NCT"
  *     fp32 contiguous, prompt (B, Lp, 256) fp32 contiguous, mask (B, Lp) uint8
  *     (1 = keep), timesteps (B) fp32 (fractional values are legal,
- *     sampler/dpm_solver.py:278).
+ *     sampler/dpm_solver.py:278);
+ *   - a kernel-level call (ns2vc_k_*) reads and writes only the LOGICAL elements of the tensors it is given: rows x width at
+ *     the given pitch, from the given pointer.  Bytes between the rows (columns [width, pitch), or in front of a tensor that
+ *     is a column slice of wider rows) and bytes in front of / behind a tensor are never written and never influence a
+ *     result, whatever they hold (NaN, Inf, another tensor's fp32 bits): rows a tile rounds up to are clamped, bounded by the
+ *     buffer descriptor or discarded before they reach a reduction.  `res` may alias `out_f32` element for element (same
+ *     pointer, same pitch).  Buffers a call is documented to write (a0 under gnp_x, gnp_raw, stats, rowstats, gnp_sync, the
+ *     solver state) are outputs in this sense: their logical region only.  tests/test_kernel_bounds_gpu.py pins this;
+ *   - operand-typed source tensors (a0 / a1 / a2, q / k / v, yn, a_op): the caller passes pointers on a 16-byte boundary (a
+ *     precondition: the launchers do not check source pointers), and row pitches that are multiples of 16 bytes -- a pitch that
+ *     is not is refused by the launcher (non-zero return, nothing launched).
  */
 #ifndef NS2VC_HIP_H
 #define NS2VC_HIP_H

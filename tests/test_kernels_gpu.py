@@ -16,7 +16,8 @@ import zlib
 import numpy as np
 import pytest
 
-from util import bf16_round, f16_round, gather_rows, gelu_erf, rel_l2, silu
+from util import (GEGLU_FLIPS, TOL_ATTN_FP8, TOL_FFN, TOL_ROWCHAIN_GN_Y, TOL_ROWCHAIN_Y, TOL_STATS, bf16_round, eps16, f16_round, gather_rows, gelu_erf, rel_l2, silu,
+                  tol_attention, tol_ffn_xattn, tol_gnp_rows, tol_groupnorm, tol_layernorm_apply, tol_ln_linear, tol_pair_rows)
 
 pytestmark = pytest.mark.gpu
 
@@ -71,11 +72,6 @@ class OpBuf:
 def rnd(a, prec):
     a = np.asarray(a, dtype=np.float32)
     return bf16_round(a) if prec == 1 else (f16_round(a) if prec == 2 else a)
-
-
-def eps16(prec):
-    """unit roundoff of the operand type (round to nearest): 2^-9 bf16, 2^-12 fp16"""
-    return {0: 2.0 ** -25, 1: 2.0 ** -9, 2: 2.0 ** -12}[prec]
 
 
 def _pack_tiled(W, ctot, c2, prec):
@@ -307,7 +303,7 @@ def test_conv_tapshare_kernel(tile, prec, diag):
         e_s = np.abs(st[..., 0] / 2 ** 28 - ref_s).max() / np.abs(ref_s).max()
         e_q = np.abs(st[..., 1] / 2 ** 16 - ref_q).max() / np.abs(ref_q).max()
         diag(f"conv3ts + 1x1 segment tile={tile} prec={prec} {(B, T, c0, c2, N)}: {e:.3e}  statistics {e_s:.1e} / {e_q:.1e}")
-        assert e < TOL[prec] and e_s < 1e-5 and e_q < 1e-5
+        assert e < TOL[prec] and e_s < TOL_STATS and e_q < TOL_STATS
         lib.ns2vc_dev_free(d_w)
 
 
@@ -404,7 +400,7 @@ def test_gemm_groupnorm_prologue(tile, prec, diag):
              f"rows vs fp64 {e_op:.2e}  result vs fp64 {e_out:.2e}  rows==two-launch {same_op}  result==two-launch {same_out}")
         assert np.isfinite(ops[1]).all() and np.isfinite(outs[1]).all()          # every row the tiles read was produced
         assert same_op and same_out
-        assert e_op < (1e-6 if prec == 0 else eps16(prec)) and e_out < TOL[prec]
+        assert e_op < tol_gnp_rows(prec)[0] and e_out < TOL[prec]
 
 
 @pytest.mark.parametrize("prec", PRECS, ids=PREC_IDS)
@@ -481,7 +477,7 @@ def test_gemm_groupnorm_prologue_of_a_concat(tile, prec, diag):
              f"{e_raw:.2e}  rows, raw rows and result == two-launch path (redundant, cooperative x2): {same}")
         assert np.isfinite(ops[1]).all() and np.isfinite(raws[1]).all() and np.isfinite(outs[1]).all()
         assert same
-        assert e_op < (1e-6 if prec == 0 else eps16(prec)) and e_raw < (1e-7 if prec == 0 else eps16(prec))
+        assert e_op < tol_gnp_rows(prec)[0] and e_raw < tol_gnp_rows(prec)[1]
 
 
 IN_LOOP_CASES = [  # B, T, c0, c1, N, temb, silu, raw copy, fused 1x1 segment channels
@@ -590,7 +586,7 @@ def test_conv_groupnorm_in_loop(tile, prec, diag):
         diag(f"conv + in-loop GroupNorm tile={tile} prec={prec} B={B} T={T} C={c0}+{c1} N={N} temb={temb_on} silu={silu} raw={raw_on} c2={c2}: result == two-launch path "
              f"{same_out}  raw copy == {same_raw}  operand tensor untouched {untouched}  rows vs fp64 {e_op:.2e}  result vs fp64 {e_out:.2e}")
         assert np.isfinite(outs[1]).all() and same_out and same_raw and untouched
-        assert e_op < (1e-6 if prec == 0 else eps16(prec)) and e_out < TOL[prec]
+        assert e_op < tol_gnp_rows(prec)[0] and e_out < TOL[prec]
 
 
 
@@ -663,7 +659,7 @@ def test_conv_on_hi_lo_operand_pairs(tile, prec, diag):
         diag(f"conv on hi + lo operand pairs tile={tile} prec={prec} B={B} T={T} C={Cc} N={N} temb={temb_on} silu={silu}: hi plane == plain rows {same_hi}; hi + lo vs fp64 rows {e_pair:.2e}; "
              f"result vs the fp64 conv of unrounded rows and weights: plain {e0:.2e}, pair {e1:.2e}")
         assert same_hi and np.isfinite(outs[1]).all()
-        assert e_pair < (2e-5 if prec == 1 else 1e-6) and e1 < 0.02 * e0
+        assert e_pair < tol_pair_rows(prec) and e1 < 0.02 * e0
 
 
 @pytest.mark.parametrize("algo", [2, 0], ids=["prologue", "inloop"])
@@ -812,7 +808,7 @@ def test_gemm_layernorm_by_linearity(tile, prec, diag):
         e_s = np.abs(st[..., 0] - ys.sum(2)).max() / np.abs(ys.sum(2)).max()
         e_q = np.abs(st[..., 1] - (ys ** 2).sum(2)).max() / (ys ** 2).sum(2).max()
         diag(f"ln-linear producer tile={tile} prec={prec}: slice sums {e_s:.2e} slice sumsq {e_q:.2e}")
-        assert e_s < 1e-5 and e_q < 1e-5
+        assert e_s < TOL_STATS and e_q < TOL_STATS
         # ---- consumers
         mu = y.mean(1, keepdims=True)
         yn = (y - mu) / np.sqrt(y.var(1, keepdims=True) + 1e-5)
@@ -848,7 +844,7 @@ def test_gemm_layernorm_by_linearity(tile, prec, diag):
             e = rel_l2(out, ref)
             diag(f"ln-linear consumer tile={tile} prec={prec} geglu={geglu}: rel_l2 {e:.3e}")
             # fp32: exact up to rounding; 16-bit: the raw operand copy is rounded BEFORE normalisation (eps of |y|, not of |y - mean|)
-            assert e < (2e-5 if prec == 0 else 8 * eps16(prec))
+            assert e < tol_ln_linear(prec)
             lib.ns2vc_dev_free(d_w2); lib.ns2vc_dev_free(ws)
     finally:
         lib.ns2vc_debug_set_gemm_tile(0, 0, 0)
@@ -1075,7 +1071,7 @@ def test_geglu_token_stationary(M, ldo_extra, prec, diag):
         err = np.abs(out - ref)
         bad = np.argwhere(~(err <= 2e-2 + 2e-2 * np.abs(ref)))
         diag(f"  FAIL: flips {flips:.4f}; {len(bad)} bad of {out.size}; rows {sorted(set(bad[:, 0].tolist()))[:16]} cols {sorted(set(bad[:, 1].tolist()))[:24]}")
-    assert np.isfinite(out).all() and e < eps16(prec) and flips < 0.03
+    assert np.isfinite(out).all() and e < eps16(prec) and flips < GEGLU_FLIPS
     assert np.isnan(h[:, 4 * d:]).all()
     assert (0.2 if M > 1 else 0.0) < ratio < 12.0      # (max over rows of |mean| / std: a single row can have any)
     # the same launch twice: bitwise equal (no accumulation order depends on timing)
@@ -1180,9 +1176,9 @@ def test_ffn_fused(dim, B, T, prestage, prec, diag):
         err = np.abs(out - ref)
         bad = np.argwhere(~(err <= 1e-2 + 1e-2 * np.abs(ref)))
         diag(f"  FAIL: {len(bad)} bad of {out.size}; rows {sorted(set(bad[:, 0].tolist()))[:16]} cols {sorted(set(bad[:, 1].tolist()))[:16]}")
-    assert np.isfinite(out).all() and e < 2e-4
+    assert np.isfinite(out).all() and e < TOL_FFN
     assert np.array_equal(op, rnd(out, prec))
-    assert e_s < 1e-5 and e_q < 1e-5
+    assert e_s < TOL_STATS and e_q < TOL_STATS
     assert 0.5 < ratio < 12.0
     lib.ns2vc_dev_free(stream)
 
@@ -1287,8 +1283,8 @@ def test_ffn_fused_with_cross_attention(dim, B, T, Lk, masked, prec, diag):
     e_s = np.abs(gs[..., 0] / 2 ** 28 - blk.sum(axis=(1, 3))).max() / np.abs(blk.sum(axis=(1, 3))).max()
     diag(f"ffn + in-kernel cross-attention dim={d} B={B} T={T} Lk={Lk} mask={masked} prec={prec}: vs fp64 {e:.3e} (two-launch path {e2:.3e}; fused vs two-launch {e12:.3e})  "
          f"nan={int(np.isnan(out).sum())}  stats sum {e_s:.2e}")
-    assert np.isfinite(out).all() and e < (4e-4 if prec == 2 else 3e-3) and e12 < (6e-4 if prec == 2 else 5e-3)
-    assert e_s < 1e-5
+    assert np.isfinite(out).all() and e < tol_ffn_xattn(prec) and e12 < (6e-4 if prec == 2 else 5e-3)
+    assert e_s < TOL_STATS
     lib.ns2vc_dev_free(stream)
 
 
@@ -1376,7 +1372,7 @@ def test_attention(case, prec, keys, diag):
     out = d_out.read((B, Lq, D))
     e = rel_l2(out, ref)
     diag(f"attn {name} prec={prec} rel_l2={e:.3e} nan={int(np.isnan(out).sum())}")
-    tol = 2e-5 if prec == 0 else 8 * eps16(prec)      # 16-bit: scaled Q, P and the output are rounded to the operand type
+    tol = tol_attention(prec)
     if not e < tol:
         err = np.abs(out - ref).reshape(B, Lq, H, hd)
         diag(f"  FAIL {name}: per-head max err {err.max(axis=(0, 1, 3)).round(4).tolist()} per-d max {err.max(axis=(0, 1, 2)).round(3).tolist()[:16]}")
@@ -1588,7 +1584,7 @@ def test_groupnorm(shape, prec, diag):
                                     d_t.ptr if with_t else None, temb.shape[1], off, silu_on, d_o.ptr, d_r.ptr, prec, None), "groupnorm")
         e1, e2 = rel_l2(d_o.read(), ref), rel_l2(d_r.read(), A)
         diag(f"groupnorm {shape} prec={prec} temb={with_t} silu={silu_on}: out {e1:.2e} raw {e2:.2e}")
-        assert e1 < (5e-6 if prec == 0 else 2 * eps16(prec)) and e2 < (1e-7 if prec == 0 else 2 * eps16(prec))
+        assert e1 < tol_groupnorm(prec)[0] and e2 < tol_groupnorm(prec)[1]
 
 
 @pytest.mark.parametrize("prec", PRECS, ids=PREC_IDS)
@@ -1608,7 +1604,7 @@ def test_layernorm_apply(shape, prec, diag):
     ref = (xd - xd.mean(-1, keepdims=True)) / np.sqrt(xd.var(-1, keepdims=True) + 1e-5)
     e = rel_l2(d_o.read(), ref)
     diag(f"layernorm_apply {shape} prec={prec} rel_l2={e:.3e}")
-    assert e < (2e-6 if prec == 0 else 2 * eps16(prec))
+    assert e < tol_layernorm_apply(prec)
 
 
 def test_layout_roundtrip(diag):
@@ -1700,7 +1696,7 @@ def test_rowchain_fused(dim, mult, M, res, nt, prec, diag):
         bad = np.argwhere(~(err <= 2e-2 + 2e-2 * np.abs(z)))
         diag(f"  FAIL: {len(bad)} bad of {zo.size}; rows {sorted(set(bad[:, 0].tolist()))[:16]} cols {sorted(set(bad[:, 1].tolist()))[:24]}")
     assert np.isfinite(zo).all() and np.isfinite(yo).all()
-    assert e_y < 1e-6                       # fp32 accumulation of exactly rounded operands
+    assert e_y < TOL_ROWCHAIN_Y             # fp32 accumulation of exactly rounded operands
     assert e_z < eps16(prec)                # one operand rounding of the result on top of a near-exact value
     want = (np.abs(y.mean(1)) / np.sqrt(y.var(1) + 1e-5)).max()
     assert abs(ratio - want) < 1e-3 * want
@@ -1786,7 +1782,7 @@ def _rowchain_groupnorm_prologue(dim, B, T, nt, Gn, prec, diag):
         # normalised rows agree except where a value sits on a rounding boundary of the operand type -- a ~1e-4 fraction of
         # elements, one operand ulp each; inside the engine both paths read the same int64 sums and are bit-identical,
         # tests/test_engine_gpu.py::test_rows_groupnorm_prologue_is_bit_identical)
-        assert np.isfinite(zo).all() and e_y < 2e-5 and e_z < eps16(prec)
+        assert np.isfinite(zo).all() and e_y < TOL_ROWCHAIN_GN_Y and e_z < eps16(prec)
         if mult == 1:                                  # W1 = I, b1 = 0: y IS the panel the prologue built
             assert (yo != a_gn).mean() < 2e-3 and np.abs(yo - a_gn).max() <= eps16(prec) * 4 * np.abs(a_gn).max()
 
@@ -1831,7 +1827,7 @@ def test_attention_fp8_pv(case, prec, diag):
         assert np.isfinite(out).all()
         errs[flag] = rel_l2(out, ref)
     diag(f"attention {name} prec={prec}: 16-bit PV {errs[0]:.3e}, fp8 PV {errs[1]:.3e}")
-    assert errs[1] < 4e-2 and errs[1] > 2 * errs[0]
+    assert errs[1] < TOL_ATTN_FP8 and errs[1] > 2 * errs[0]
     a32 = AttnArgs()
     a32.pv_fp8 = 1
     assert lib.ns2vc_k_attention(C.byref(a32), hd, 0, None) != 0          # no fp8 variant of the exact-fp32 kernel: loud

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from util import f16_round, fmt_local, local_errors, rel_l2
+from util import TOL_SOLVER, f16_round, fmt_local, local_errors, rel_l2
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,7 +105,7 @@ def test_k_solver_update_against_numpy(prec, hist2, diag):
     errs = {"xe": rel_l2(got["xe"], ne), "xbar": rel_l2(got["xbar"], nb), "d1": rel_l2(got["d1"], nd), "mprev": rel_l2(got["mprev"], m)}
     diag(f"k_solver_update {prec} hist2={hist2}: " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()))
     for k, v in errs.items():
-        assert v < 1e-6, k
+        assert v < TOL_SOLVER, k
     if hist2:
         assert np.array_equal(got["mprev2"], st["mprev"])       # m_{i-1} moves down the history
     else:

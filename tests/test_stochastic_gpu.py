@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from util import fmt_local, local_errors, rel_l2
+from util import NOISE_ULP, fmt_local, local_errors, rel_l2
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,7 +63,7 @@ def test_k_noise_equals_host_statement(step, diag):
     d = np.abs(dev[:, :, :100].astype(np.float64) - host)
     ulp = d / np.spacing(np.maximum(np.abs(host), 1.0).astype(np.float32))
     diag(f"k_noise step {step} vs noise.gauss: max |d| {d.max():.2e}, max {ulp.max():.1f} ulp of max(|z|, 1)")
-    assert ulp.max() <= 8
+    assert ulp.max() <= NOISE_ULP
 
 
 def test_k_noise_statistics(diag):

@@ -48,6 +48,51 @@ def f16_round(a: np.ndarray) -> np.ndarray:
         return np.asarray(a, dtype=np.float32).astype(np.float16).astype(np.float32)
 
 
+# ---- bounds shared by the kernel tests (tests/test_kernels_gpu.py, test_solvers_gpu.py, test_stochastic_gpu.py) and the guard-band tests
+# (tests/test_kernel_bounds_gpu.py): one definition, so the strided launches are held to exactly what the tight ones are
+def eps16(prec):
+    """unit roundoff of the operand type (round to nearest): 2^-9 bf16, 2^-12 fp16"""
+    return {0: 2.0 ** -25, 1: 2.0 ** -9, 2: 2.0 ** -12}[prec]
+
+
+TOL_STATS = 1e-5            # epilogue statistics (int64 fixed point / per-slice row sums) vs fp64 sums of the result, relative to the largest
+TOL_ATTN_FP8 = 4e-2         # pv_fp8 attention vs exact fp64 attention
+GEGLU_FLIPS = 0.03          # token-stationary GEGLU: fraction of results one operand ulp off the rounded reference
+TOL_ROWCHAIN_Y = 1e-6       # rowchain y: fp32 accumulation of exactly rounded operands
+TOL_ROWCHAIN_GN_Y = 2e-5    # ... with the GroupNorm prologue (rows from the int64 sums)
+TOL_FFN = 2e-4              # fused feed-forward vs fp64 with the kernel's rounding points
+NOISE_ULP = 8               # ns2vc_k_noise vs ns2vc_amd.noise.gauss, ulps of max(|z|, 1)
+TOL_SOLVER = 1e-6           # ns2vc_k_solver_update vs the fp64 recurrence
+
+
+def tol_attention(prec):    # 16-bit: scaled Q, P and the output are rounded to the operand type
+    return 2e-5 if prec == 0 else 8 * eps16(prec)
+
+
+def tol_ln_linear(prec):    # LayerNorm-by-linearity consumer (16-bit: the raw operand copy is rounded BEFORE normalisation)
+    return 2e-5 if prec == 0 else 8 * eps16(prec)
+
+
+def tol_groupnorm(prec):    # (normalised rows, raw copy)
+    return (5e-6 if prec == 0 else 2 * eps16(prec)), (1e-7 if prec == 0 else 2 * eps16(prec))
+
+
+def tol_gnp_rows(prec):     # GroupNorm-prologue rows of a GEMM: (normalised rows, raw copy)
+    return (1e-6 if prec == 0 else eps16(prec)), (1e-7 if prec == 0 else eps16(prec))
+
+
+def tol_pair_rows(prec):    # hi + lo operand pair vs the fp64 rows
+    return 2e-5 if prec == 1 else 1e-6
+
+
+def tol_layernorm_apply(prec):
+    return 2e-6 if prec == 0 else 2 * eps16(prec)
+
+
+def tol_ffn_xattn(prec):    # fused feed-forward with the in-kernel cross-attention vs fp64
+    return 4e-4 if prec == 2 else 3e-3
+
+
 def silu(x):
     return x / (1.0 + np.exp(-x))
 
