@@ -1,0 +1,341 @@
+// The part of the C ABI that takes no engine handle: device, stream, event and memcpy helpers, the ns2vc_pack_* weight packers, the
+// single-kernel launchers ns2vc_k_*, the ns2vc_debug_* hooks and the operand conversions (kernel tests and tools/ drive the kernels through these).
+#include "engine_internal.h"
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+
+using namespace ns2vc;
+
+hipError_t ns2vc::init_all_attributes() {
+  hipError_t e = init_gemm_attributes();
+  if (e == hipSuccess) e = init_convts_attributes();
+  if (e == hipSuccess) e = init_attn_attributes();
+  if (e == hipSuccess) e = init_ffn_attributes();
+  if (e == hipSuccess) e = init_geglu_attributes();
+  if (e == hipSuccess) e = init_rowchain_attributes();
+  return e;
+}
+// the attribute setup of one kernel family in front of its packer; `once`: skipped after the first success
+static int init_attributes(hipError_t (*init)(), bool* once = nullptr) {
+  if (once && *once) return 0;
+  const hipError_t e = init();
+  if (e != hipSuccess) return fail("kernel attribute setup failed: %s", hipGetErrorString(e));
+  if (once) *once = true;
+  return 0;
+}
+// a packed host image -> a device allocation of its own, handed to the caller (who frees it with ns2vc_dev_free)
+static int upload(const void* src, size_t bytes, void** out_dev) {
+  void* d = nullptr;
+  HIPCHK(hipMalloc(&d, std::max<size_t>(bytes, 1)));
+  HIPCHK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+  *out_dev = d;
+  return 0;
+}
+// the status of a kernel launch as the ABI reports it
+static int launched(hipError_t e, const char* what) { return e == hipSuccess ? 0 : fail("%s: %s", what, hipGetErrorString(e)); }
+static int upload_u16(const std::vector<unsigned short>& v, void** out_dev) { return upload(v.data(), v.size() * 2, out_dev); }
+
+// per device (the process may serve several): the result of misc.hip's placement probe, taken at the first engine of a device
+int ns2vc::xcd_round_robin_of_current_device() {
+  static std::mutex mu;
+  static std::map<int, int> seen;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return -1;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = seen.find(dev);
+  if (it != seen.end()) return it->second;
+  const int r = probe_xcd_round_robin();
+  seen[dev] = r;
+  return r;
+}
+
+extern "C" {
+
+int ns2vc_abi_version(void) { return NS2VC_ABI_VERSION; }
+const char* ns2vc_last_error(void) { return g_err.c_str(); }
+
+int ns2vc_device_count(int* out_count) {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess) { *out_count = 0; return fail("hipGetDeviceCount: %s", hipGetErrorString(e)); }
+  *out_count = n;
+  return 0;
+}
+int ns2vc_set_device(int device) { HIPCHK(hipSetDevice(device)); return 0; }
+int ns2vc_device_name(char* buf, int buflen) {
+  hipDeviceProp_t p;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipGetDeviceProperties(&p, dev));
+  snprintf(buf, buflen, "%s|%s|CUs=%d|clock_khz=%d|mem_gb=%.1f", p.name, p.gcnArchName, p.multiProcessorCount, p.clockRate,
+           (double)p.totalGlobalMem / 1e9);
+  return 0;
+}
+
+int ns2vc_device_xcd_round_robin(int* out) {
+  if (!out) return fail("null argument");
+  *out = xcd_round_robin_of_current_device();
+  return 0;
+}
+
+// ---- raw helpers ----------------------------------------------------------------------
+int ns2vc_dev_malloc(void** out, size_t bytes) { HIPCHK(hipMalloc(out, bytes ? bytes : 1)); return 0; }
+int ns2vc_dev_free(void* p) { HIPCHK(hipFree(p)); return 0; }
+int ns2vc_memcpy_h2d(void* dst, const void* src, size_t bytes) { HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return 0; }
+int ns2vc_memcpy_d2h(void* dst, const void* src, size_t bytes) { HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return 0; }
+int ns2vc_dev_sync(void) { HIPCHK(hipDeviceSynchronize()); return 0; }
+int ns2vc_stream_create(void** out) { hipStream_t s; HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); *out = s; return 0; }
+// NOTE: hipExtStreamCreateWithCUMask makes a DEFAULT (blocking) stream: it synchronises implicitly with the legacy null stream, so work
+// queued on the null stream serialises with it (keep PyTorch work on explicit streams when overlapping stages).  The mask is validated against the
+// device: at least one bit set, and no bit at or beyond the CU count.
+int ns2vc_stream_create_cu_mask(void** out, const uint32_t* mask_words, int n_words) {
+  if (!out || !mask_words || n_words <= 0) return fail("null argument");
+  int dev = 0, cus = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  if (n_words > (cus + 31) / 32) return fail("CU mask of %d words for a device with %d CUs (at most %d words)", n_words, cus, (cus + 31) / 32);
+  bool any = false;
+  for (int w = 0; w < n_words; ++w)
+    for (int b = 0; b < 32; ++b)
+      if (mask_words[w] >> b & 1u) {
+        if (w * 32 + b >= cus) return fail("CU mask bit %d set, the device has %d CUs", w * 32 + b, cus);
+        any = true;
+      }
+  if (!any) return fail("empty CU mask");
+  hipStream_t s;
+  HIPCHK(hipExtStreamCreateWithCUMask(&s, (uint32_t)n_words, mask_words));
+  *out = s;
+  return 0;
+}
+int ns2vc_stream_destroy(void* s) { HIPCHK(hipStreamDestroy((hipStream_t)s)); return 0; }
+int ns2vc_stream_sync(void* s) { HIPCHK(hipStreamSynchronize((hipStream_t)s)); return 0; }
+int ns2vc_event_create(void** out) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); *out = e; return 0; }
+int ns2vc_event_destroy(void* e) { HIPCHK(hipEventDestroy((hipEvent_t)e)); return 0; }
+int ns2vc_event_record(void* e, void* s) { HIPCHK(hipEventRecord((hipEvent_t)e, (hipStream_t)s)); return 0; }
+int ns2vc_event_elapsed_ms(void* a, void* b, float* ms) {
+  HIPCHK(hipEventSynchronize((hipEvent_t)b));
+  HIPCHK(hipEventElapsedTime(ms, (hipEvent_t)a, (hipEvent_t)b));
+  return 0;
+}
+
+// ---- kernel-level entry points -----------------------------------------------------------
+int ns2vc_pack_weight(const float* rows_host, int N, int K, int precision, void** out_dev) {
+  if (!rows_host || !out_dev || N <= 0 || K <= 0) return fail("bad argument");
+  static bool inited = false;
+  if (init_attributes(init_all_attributes, &inited)) return 1;
+  return ns2vc_to_operand(rows_host, (size_t)N * K, precision, out_dev);
+}
+int ns2vc_pack_conv3_tiled(const float* rows_host, int N, int ctot, int c2, int precision, void** out_dev) {
+  if (!rows_host || !out_dev || N <= 0) return fail("bad argument");
+  std::vector<unsigned char> img;
+  if (pack_conv3_tiled(rows_host, N, ctot, c2, precision, img) != hipSuccess) return fail("pack_conv3_tiled: ctot / c2 must be multiples of the chunk (64 elements; 32 for fp32)");
+  return upload(img.data(), img.size(), out_dev);
+}
+int ns2vc_weight_rowsum(const float* rows_host, int N, int K, int precision, float** out_dev) {
+  if (!rows_host || !out_dev || N <= 0 || K <= 0) return fail("bad argument");
+  const std::vector<float> ws = rounded_rowsum(rows_host, N, K, N, precision);
+  return upload(ws.data(), ws.size() * sizeof(float), (void**)out_dev);
+}
+int ns2vc_debug_set_attn_optimistic(int on) {
+  set_attn_optimistic(on);
+  return 0;
+}
+int ns2vc_debug_set_gemm_trace(void* dev_u64_blocks_x8) {
+  set_gemm_trace((unsigned long long*)dev_u64_blocks_x8);
+  set_ffn_trace((unsigned long long*)dev_u64_blocks_x8);
+  set_rc_trace((unsigned long long*)dev_u64_blocks_x8);
+  set_ts_trace((unsigned long long*)dev_u64_blocks_x8);     // (convts.hip and geglu.hip write 16 words per block)
+  set_gg_trace((unsigned long long*)dev_u64_blocks_x8);
+  return 0;
+}
+int ns2vc_debug_poison(unsigned pattern, int lds_bytes, void* stream) {
+  static unsigned* sink = nullptr;
+  if (lds_bytes < 4 || lds_bytes > 160 * 1024) return fail("poison: LDS bytes out of range");
+  if (!sink) HIPCHK(hipMalloc((void**)&sink, 64));
+  return launched(launch_poison(pattern, lds_bytes & ~3, sink, (hipStream_t)stream), "launch_poison");
+}
+int ns2vc_debug_placement(void* stream, int n_blocks, int spin, uint32_t* out_host) {
+  if (!out_host || n_blocks <= 0 || n_blocks > (1 << 20)) return fail("bad argument");
+  unsigned* d = nullptr;
+  HIPCHK(hipMalloc((void**)&d, (size_t)n_blocks * 2 * sizeof(unsigned)));
+  hipError_t e = launch_placement(d, n_blocks, spin, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemcpy(out_host, d, (size_t)n_blocks * 2 * sizeof(unsigned), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail("placement probe: %s", hipGetErrorString(e));
+  return 0;
+}
+int ns2vc_debug_set_gemm_tile(int bm, int bn, int stages) { set_forced_gemm_tile(bm, bn, stages); return 0; }
+int ns2vc_k_gemm(const ns2vc_gemm_args* a, int precision, void* stream) {
+  if (!a) return fail("null args");
+  hipError_t e = launch_gemm(*a, precision, (hipStream_t)stream);
+  if (e != hipSuccess) {
+    const int line = last_gemm_refusal_line();
+    if (line) return fail("launch_gemm: %s (refused by the argument check at gemm.hip:%d)", hipGetErrorString(e), line);
+    return fail("launch_gemm: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+int ns2vc_pack_ffn(const float* w1_packed_host, const float* w2f_host, int dim, int precision, void** out_stream_dev) {
+  if (!w1_packed_host || !w2f_host || !out_stream_dev) return fail("null argument");
+  static bool inited = false;
+  if (init_attributes(init_ffn_attributes, &inited)) return 1;
+  std::vector<unsigned short> st;
+  if (pack_ffn_stream(w1_packed_host, w2f_host, nullptr, dim, precision, st) != hipSuccess) return fail("ffn: dim must be 128 or 256 and the precision 16-bit");
+  return upload_u16(st, out_stream_dev);
+}
+int ns2vc_pack_ffn_pre(const float* w1_packed_host, const float* w2f_host, const float* w0_host, int dim, int precision, void** out_stream_dev) {
+  if (!w1_packed_host || !w2f_host || !w0_host || !out_stream_dev) return fail("null argument");
+  if (init_attributes(init_ffn_attributes)) return 1;
+  std::vector<unsigned short> st;
+  if (pack_ffn_stream(w1_packed_host, w2f_host, w0_host, dim, precision, st) != hipSuccess) return fail("ffn: dim must be 128 or 256 and the precision 16-bit");
+  return upload_u16(st, out_stream_dev);
+}
+int ns2vc_pack_rowchain(const float* w1_host, const float* w2_host, int dim, int n2, int precision, void** out_stream_dev) {
+  if (!w1_host || !w2_host || !out_stream_dev) return fail("null argument");
+  static bool inited = false;
+  if (init_attributes(init_rowchain_attributes, &inited)) return 1;
+  std::vector<unsigned short> st;
+  if (pack_rowchain_stream(w1_host, w2_host, dim, n2, precision, st) != hipSuccess)
+    return fail("rowchain: dim must be 128, 256 or 384, n2 = dim or 3 dim, and the precision 16-bit");
+  return upload_u16(st, out_stream_dev);
+}
+int ns2vc_pack_rowchain_sliced(const float* w1_host, const float* w2_host, int dim, int n2, int slices, int precision, void** out_stream_dev) {
+  if (!w1_host || !w2_host || !out_stream_dev) return fail("null argument");
+  static bool inited = false;
+  if (init_attributes(init_rowchain_attributes, &inited)) return 1;
+  std::vector<unsigned short> st;
+  if (pack_rowchain_stream(w1_host, w2_host, dim, n2, precision, st, slices) != hipSuccess)
+    return fail("rowchain (sliced): dim 384, n2 = dim or 3 dim, 2 slices, 16-bit precision");
+  return upload_u16(st, out_stream_dev);
+}
+int ns2vc_debug_set_attn_keys(int keys) {
+  if (keys != 0 && keys != 64 && keys != 128) return fail("attention K/V tile: 0 (heuristic), 64 or 128 keys");
+  set_forced_attn_keys(keys);
+  return 0;
+}
+int ns2vc_debug_set_rowchain_tokens(int nt) {
+  if (nt < 0 || nt > 2) return fail("rowchain tokens: 0 (heuristic), 1 (64-token blocks) or 2 (128-token blocks)");
+  set_forced_rowchain_tokens(nt);
+  return 0;
+}
+int ns2vc_k_rowchain(const ns2vc_rowchain_args* a, int precision, void* stream) {
+  if (!a) return fail("null args");
+  return launched(launch_rowchain(*a, precision, (hipStream_t)stream), "launch_rowchain");
+}
+size_t ns2vc_xattn_pack_bytes(int B, int Lk, int hd) { return xattn_pack_bytes(B, Lk, hd); }
+int ns2vc_k_xattn_pack(const void* k, int ldk, const void* v, int ldv, int B, int Lk, int hd, void* out, int precision, void* stream) {
+  hipError_t e = launch_xattn_pack(k, ldk, v, ldv, B, Lk, hd, out, precision, (hipStream_t)stream);
+  if (e != hipSuccess) return fail("xattn_pack: %s (16-bit precisions, head dim 16 | 32, 8 heads, 16-byte aligned k rows)", hipGetErrorString(e));
+  return 0;
+}
+int ns2vc_k_ffn(const ns2vc_ffn_args* a, int precision, void* stream) {
+  if (!a) return fail("null args");
+  return launched(launch_ffn(*a, precision, (hipStream_t)stream), "launch_ffn");
+}
+int ns2vc_pack_geglu(const float* w1_packed_host, const float* bias1_packed_host, int dim, int precision, void** out_stream_dev, float** out_consts_dev) {
+  if (!w1_packed_host || !out_stream_dev || !out_consts_dev) return fail("null argument");
+  if (init_attributes(init_geglu_attributes)) return 1;
+  std::vector<unsigned short> st;
+  std::vector<float> cs;
+  if (pack_geglu_stream(w1_packed_host, bias1_packed_host, dim, precision, st, cs) != hipSuccess) return fail("geglu: dim must be 384 and the precision 16-bit");
+  if (upload_u16(st, out_stream_dev)) return 1;
+  return upload(cs.data(), cs.size() * 4, (void**)out_consts_dev);
+}
+int ns2vc_debug_set_geglu_min_rows(int rows) { g_geglu_min_rows = rows < 0 ? 4608 : rows; return 0; }
+int ns2vc_pack_geglu_host(const float* w1_packed_host, const float* bias1_packed_host, int dim, int precision, uint16_t* stream_out, float* consts_out) {
+  if (!w1_packed_host || !stream_out || !consts_out) return fail("null argument");
+  std::vector<unsigned short> st;
+  std::vector<float> cs;
+  if (pack_geglu_stream(w1_packed_host, bias1_packed_host, dim, precision, st, cs) != hipSuccess) return fail("geglu: dim must be 384 and the precision 16-bit");
+  memcpy(stream_out, st.data(), st.size() * 2);
+  memcpy(consts_out, cs.data(), cs.size() * 4);
+  return 0;
+}
+int ns2vc_k_geglu(const ns2vc_geglu_args* a, int precision, void* stream) {
+  if (!a) return fail("null args");
+  return launched(launch_geglu(*a, precision, (hipStream_t)stream), "launch_geglu");
+}
+int ns2vc_k_attention(const ns2vc_attn_args* a, int head_dim, int precision, void* stream) {
+  if (!a) return fail("null args");
+  return launched(launch_attention(*a, head_dim, precision, (hipStream_t)stream), "launch_attention");
+}
+int ns2vc_k_groupnorm(const float* a0, int lda0, int c0, const float* a1, int lda1, int c1, int B, int T, int G, float eps,
+                      const float* gamma, const float* beta, const float* temb, int ldtemb, int temb_off, int silu, void* out_op,
+                      void* raw_op, int precision, void* stream) {
+  const int rows = 32, nchunk = (T + rows - 1) / rows;
+  double* part = nullptr;
+  HIPCHK(hipMalloc((void**)&part, (size_t)B * nchunk * G * 2 * sizeof(double)));
+  hipError_t e = launch_gn_partial(a0, lda0, c0, a1, lda1, c1, B, T, G, part, nchunk, rows, (hipStream_t)stream);
+  if (e == hipSuccess)
+    e = launch_gn_apply(a0, lda0, c0, a1, lda1, c1, B, T, G, eps, part, nchunk, nullptr, nullptr, gamma, beta, temb, ldtemb, temb_off, silu,
+                        out_op, raw_op, precision, (hipStream_t)stream);
+  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(part);
+  if (e != hipSuccess) return fail("groupnorm launch: %s", hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail("groupnorm sync: %s", hipGetErrorString(e2));
+  return 0;
+}
+int ns2vc_k_groupnorm_stats(const float* a0, int lda0, int c0, const long long* stats0, int B, int T, int G, float eps, const float* gamma,
+                            const float* beta, const float* temb, int ldtemb, int temb_off, int silu, void* out_op, int precision, void* stream) {
+  if (!stats0 || (c0 % G) || ((c0 / G) & 15)) return fail("groupnorm_stats: needs the int64 epilogue statistics and groups of whole 16-channel blocks");
+  return launched(launch_gn_apply(a0, lda0, c0, nullptr, 0, 0, B, T, G, eps, nullptr, 0, stats0, nullptr, gamma, beta, temb, ldtemb, temb_off, silu,
+                                 out_op, nullptr, precision, (hipStream_t)stream), "groupnorm_stats launch");
+}
+int ns2vc_k_groupnorm_stats2(const float* a0, int lda0, int c0, const long long* stats0, const float* a1, int lda1, int c1, const long long* stats1,
+                             int B, int T, int G, float eps, const float* gamma, const float* beta, const float* temb, int ldtemb, int temb_off,
+                             int silu, void* out_op, void* raw_op, int precision, void* stream) {
+  if (!stats0 || !a1 || !stats1 || (c0 & 15) || (c1 & 15) || ((c0 + c1) % G) || (((c0 + c1) / G) & 15))
+    return fail("groupnorm_stats2: needs both sources' int64 epilogue statistics, whole 16-channel blocks per source and per group");
+  return launched(launch_gn_apply(a0, lda0, c0, a1, lda1, c1, B, T, G, eps, nullptr, 0, stats0, stats1, gamma, beta, temb, ldtemb, temb_off, silu,
+                                 out_op, raw_op, precision, (hipStream_t)stream), "groupnorm_stats2 launch");
+}
+int ns2vc_k_layernorm_apply(const float* x, int ldx, int M, int C, float eps, void* out_op, int precision, void* stream) {
+  return launched(launch_ln_apply_op(x, ldx, M, C, eps, out_op, precision, (hipStream_t)stream), "ln_apply launch");
+}
+int ns2vc_to_operand(const float* host, size_t n, int precision, void** out_dev) {
+  if (!host || !out_dev) return fail("null argument");
+  if (precision == NS2VC_PREC_F32) return upload(host, n * 4, out_dev);
+  std::vector<uint16_t> q(n);
+  for (size_t i = 0; i < n; ++i) q[i] = f32_to_op16_bits(host[i], precision);
+  return upload(q.data(), n * 2, out_dev);
+}
+int ns2vc_round_to_operand(const float* host_in, size_t n, int precision, float* host_out) {
+  if (!host_in || !host_out) return fail("null argument");
+  if (precision != NS2VC_PREC_F32 && precision != NS2VC_PREC_BF16 && precision != NS2VC_PREC_F16) return fail("unknown precision %d", precision);
+  for (size_t i = 0; i < n; ++i)
+    host_out[i] = precision == NS2VC_PREC_F32 ? host_in[i] : op16_bits_to_f32(f32_to_op16_bits(host_in[i], precision), precision);
+  return 0;
+}
+int ns2vc_from_operand(const void* dev, size_t n, int precision, float* host) {
+  if (!dev || !host) return fail("null argument");
+  HIPCHK(hipDeviceSynchronize());
+  if (precision != NS2VC_PREC_F32) {
+    std::vector<uint16_t> q(n);
+    HIPCHK(hipMemcpy(q.data(), dev, n * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) host[i] = op16_bits_to_f32(q[i], precision);
+  } else {
+    HIPCHK(hipMemcpy(host, dev, n * 4, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+int ns2vc_k_nct_to_btc(const float* src, int C, int T, int B, float* dst, int ldd, int cpad, void* stream) {
+  return launched(launch_nct_to_btc(src, C, T, B, dst, nullptr, PREC_F32, ldd, cpad, (hipStream_t)stream), "nct_to_btc launch");
+}
+int ns2vc_k_btc_to_nct(const float* src, int lds, int C, int T, int B, float* dst, void* stream) {
+  return launched(launch_btc_to_nct(src, lds, C, T, B, dst, (hipStream_t)stream), "btc_to_nct launch");
+}
+int ns2vc_k_solver_update(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
+                          float* d1, float* mprev, float* mprev2, size_t n, int ld, void* stream) {
+  if (!coef_dev || !step_dev || !x0 || !xe || !xe_op || !xbar || !d1 || !mprev) return fail("null argument");
+  if (ld <= 0 || (ld & 3) || n % (size_t)ld) return fail("n (%zu) must be a multiple of ld (%d), ld a multiple of 4", n, ld);
+  return launched(launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n, (hipStream_t)stream,
+                                      precision != PREC_F32 ? ld : 0, SolverNoise(), mprev2), "solver_update launch");
+}
+int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream) {
+  return launched(launch_noise(reinterpret_cast<const unsigned long long*>(seeds_dev), B, C, T, ld, step, lens_dev, out, (hipStream_t)stream), "noise launch");
+}
+
+}  // extern "C"

@@ -308,6 +308,16 @@ void set_forced_attn_keys(int keys);            // test hook: 0 = heuristic, 64 
 hipError_t launch_ffn(const ::ns2vc_ffn_args& a, int prec, hipStream_t s);
 bool ffn_eligible(int dim, int T, int prec);
 hipError_t init_ffn_attributes();
+hipError_t pack_ffn_stream(const float* w1p, const float* w2f, const float* w0, int dim, int prec, std::vector<unsigned short>& out);
+void set_ffn_trace(unsigned long long* p);
+// token-stationary GEGLU projection (geglu.hip), 16-bit operand types, dim 384
+bool geglu_eligible(int dim, int T, int prec);
+hipError_t pack_geglu_stream(const float* w1p, const float* bias1p, int dim, int prec, std::vector<unsigned short>& stream, std::vector<float>& consts);
+hipError_t launch_geglu(const ::ns2vc_geglu_args& a, int prec, hipStream_t s);
+hipError_t init_geglu_attributes();
+void set_gg_trace(unsigned long long* p);
+void set_ts_trace(unsigned long long* p);       // convts.hip
+void set_attn_optimistic(int on);               // attn.hip
 
 // misc kernels (misc.hip).  "op" buffers are operand-typed (bf16 / fp16 / fp32 by `prec`)
 hipError_t launch_gn_partial(const float* a0, int lda0, int c0, const float* a1, int lda1, int c1,
@@ -329,6 +339,9 @@ hipError_t launch_time_embed(const float* t_ptr, int t_stride, const int* step_p
 hipError_t launch_rowchain(const ::ns2vc_rowchain_args& a, int prec, hipStream_t s);            // rowchain.hip
 bool rowchain_eligible(int dim, int n2, int T, int prec);
 hipError_t init_rowchain_attributes();
+hipError_t pack_rowchain_stream(const float* w1, const float* w2, int dim, int n2, int prec, std::vector<unsigned short>& out, int slices = 1);
+int rowchain_slice_blocks(int n2, int slices);
+void set_rc_trace(unsigned long long* p);
 void set_forced_rowchain_tokens(int nt);        // test hook: 0 = heuristic, 1 = 64-token blocks, 2 = 128-token blocks (dim 128 only)
 hipError_t launch_emb_from_table(const float* table, const int* step_ptr, const float* aug, float* emb, void* emb_act_op, int prec, int B,
                                  int edim, hipStream_t s);

@@ -6,7 +6,7 @@
 //     n   = LayerNorm(y)                                   (norm3, gamma/beta folded into W1 / b1 at pack time)
 //     h   = (n W1v^T + b1v) * gelu(n W1g^T + b1g)          (ff.net.0: GEGLU, hidden = 4 dim)
 //     out = Wpo (y + W2 h + b2) + bpo + x                  (ff.net.2, + residual, proj_out (1x1 conv), + block residual)
-//         = [Wpo W2 | Wpo] [h | y] + (Wpo b2 + bpo) + x    (folded at pack time: engine.cpp pack_all)
+//         = [Wpo W2 | Wpo] [h | y] + (Wpo b2 + bpo) + x    (folded at pack time: pack.cpp pack_all)
 //
 // As separate launches the GEGLU GEMM (K = dim: one or two K tiles, N = 8 dim) was the slowest GEMM of the step at every
 // level (30-44 us: prologue, two cold K tiles and an erf epilogue per workgroup, 15 workgroups per CU, and a 30 MB

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(512) void geglu_kernel(const GegluArgs a) {
 // ---------------------------------------------------------------------------
 bool geglu_eligible(int dim, int T, int prec) { return dim == 384 && T >= 1 && (prec == PREC_BF16 || prec == PREC_F16); }
 
-// w1p [8 dim][dim]: LayerNorm-folded ff.net.0 rows in the packed (32 value | 32 gate) order of the GEGLU GEMM (engine.cpp pack_all / ns2vc_pack_ffn); bias1p [8 dim].
+// w1p [8 dim][dim]: LayerNorm-folded ff.net.0 rows in the packed (32 value | 32 gate) order of the GEGLU GEMM (pack.cpp pack_all / ns2vc_pack_ffn); bias1p [8 dim].
 // Output: the tile stream ([quarter][unit block][K tile][128 rows][64 k], pre-swizzled) and the constants ([quarter][stream row] (rowsum of the ROUNDED row, bias))
 // in stream row order, i.e. with the rows of every 32-unit group permuted by gg_unit_of_row.
 hipError_t pack_geglu_stream(const float* w1p, const float* bias1p, int dim, int prec, std::vector<unsigned short>& stream, std::vector<float>& consts) {

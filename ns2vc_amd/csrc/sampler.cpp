@@ -1,0 +1,241 @@
+// The sampling loop: the solver table, the per-item noise seeds, one evaluation + solver update per step -- captured once as a hipGraph and
+// replayed -- and the hand-off of the solver state between two engines.
+#include "engine_internal.h"
+
+#include <cstring>
+
+using namespace ns2vc;
+
+// Does a step fold its solver update into conv_out?  r6: when conv_out is the plan's last launch and runs on the tap-sharing kernel, the update happens in its epilogue
+// (same arithmetic, element for element: common.h solver_upd) -- x0 is never written, the state tensors are read and written once instead of twice
+bool ns2vc::solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
+  if (!h->fuse_solver || h->debug || h->conv_out_idx < 0 || h->conv_out_idx != (int)h->fwd_ops.size() - 1) return false;
+  // (masked plan: the update must see x0 with its padded rows zeroed -- conv_out's epilogue has not zeroed them -- so it stays a launch of its own)
+  if (h->lens.masked) return false;
+  if (h->conv_out_prec != h->prec) return false;      // (exact_io: conv_out runs in fp32 there, the operand copy of the state is 16-bit)
+  if (h->stochastic) return false;                     // (the epilogue has no noise term: a stochastic table runs the stand-alone update)
+  if (h->hist2.on) return false;                       // (nor an m_{i-2}: history-2 tables too)
+  g = h->conv_out_g;
+  g.out_f32 = nullptr;
+  g.sol_coef = h->coef_dev; g.sol_step = h->step_dev; g.sol_ncoef = NS2VC_NCOEF;
+  g.sol_xe = h->xe; g.sol_xe_op = h->xe_op; g.sol_xbar = h->xbar; g.sol_d1 = h->d1; g.sol_mprev = h->mprev; g.sol_ld = h->CP; g.sol_op_pair = h->prec != PREC_F32;
+  return gemm_uses_convts(g, h->conv_out_prec);
+}
+
+extern "C" {
+
+int ns2vc_sampler_load(ns2vc_unet* h, int steps, const float* coef_host) {
+  const int kMaxSteps = 1024;   // fixed capacity: the table pointer is baked into the captured graph
+  if (!h || !coef_host || steps <= 0) return fail("bad sampler table");
+  if (steps > kMaxSteps) return fail("at most %d solver steps are supported", kMaxSteps);
+  if (!h->coef_dev) HIPCHK(hipMalloc((void**)&h->coef_dev, (size_t)kMaxSteps * NS2VC_NCOEF * sizeof(float)));
+  HIPCHK(hipDeviceSynchronize());   // a previous loop may still be reading the table
+  HIPCHK(hipMemcpy(h->coef_dev, coef_host, (size_t)steps * NS2VC_NCOEF * sizeof(float), hipMemcpyHostToDevice));
+  {
+    unsigned long long hsh = 1469598103934665603ull;
+    const unsigned char* pb = reinterpret_cast<const unsigned char*>(coef_host);
+    for (size_t i = 0; i < (size_t)steps * NS2VC_NCOEF * sizeof(float); ++i) { hsh ^= pb[i]; hsh *= 1099511628211ull; }
+    h->coef_hash = hsh;
+  }
+  h->steps = steps;
+  h->temb_table_valid = false;
+  h->next_step = -1;
+  bool stochastic = false;
+  for (int i = 0; i < steps; ++i) stochastic |= coef_host[(size_t)i * NS2VC_NCOEF + 9] != 0.f;
+  bool hist2 = false;
+  for (int i = 0; i < steps; ++i) hist2 |= coef_host[(size_t)i * NS2VC_NCOEF + 10] != 0.f || coef_host[(size_t)i * NS2VC_NCOEF + 11] != 0.f;
+  if (stochastic && hist2) { h->steps = 0; return fail("a solver table with both a noise column and history 2 (columns 10-11) is not supported"); }
+  // (the update's noise arguments and its history-2 form are baked into the captured step graph)
+  if (stochastic != h->stochastic || hist2 != h->hist2.on) drop_step_graph(h);
+  h->stochastic = stochastic;
+  h->hist2.on = hist2;
+  return 0;
+}
+
+// the m_{i-2} buffer of history-2 tables for the prepared shape; a new one invalidates the captured step graph (its update reads the old pointer)
+static int ensure_mprev2(ns2vc_unet* h) {
+  const size_t n = (size_t)h->B * h->T * h->CP;
+  if (h->hist2.mprev2 && h->hist2.n >= n) return 0;
+  drop_step_graph(h);
+  if (h->hist2.mprev2) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->hist2.mprev2)); h->hist2.mprev2 = nullptr; h->hist2.n = 0; }
+  HIPCHK(hipMalloc((void**)&h->hist2.mprev2, n * sizeof(float)));
+  h->hist2.n = n;
+  return 0;
+}
+
+// a seeds buffer for at least n items; a new one invalidates the captured step graph (its update reads the old pointer)
+static int ensure_seeds(ns2vc_unet* h, int n) {
+  if (h->seeds.dev && h->seeds.cap >= n) return 0;
+  drop_step_graph(h);
+  if (h->seeds.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->seeds.dev)); h->seeds.dev = nullptr; h->seeds.cap = 0; }
+  const int cap = (n + 1) & ~1;            // 16-byte multiple (launch_copy16)
+  HIPCHK(hipMalloc((void**)&h->seeds.dev, (size_t)cap * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(h->seeds.dev, 0, (size_t)cap * sizeof(unsigned long long)));
+  h->seeds.cap = cap;
+  return 0;
+}
+
+int ns2vc_sampler_set_seeds(ns2vc_unet* h, const uint64_t* seeds_b, void* stream) {
+  if (check_ready(h, true)) return 1;
+  if (!seeds_b) return fail("null seeds");
+  hipStream_t s = (hipStream_t)stream;
+  const int B = h->B;
+  if (ensure_seeds(h, B)) return 1;
+  Staged& st = h->seeds.stage;
+  const size_t nb = (size_t)B * sizeof(uint64_t);
+  if (st.reserve(nb)) return 1;
+  memcpy(st.buf, seeds_b, nb);
+  HIPCHK(hipMemcpyAsync(h->seeds.dev, st.buf, nb, hipMemcpyHostToDevice, s));
+  if (st.record(s)) return 1;
+  h->seeds.set = true;
+  return 0;
+}
+
+// one evaluation + solver update
+static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
+  GemmArgs g;
+  const bool fold = solver_in_conv_out(h, g);
+  const size_t last = fold ? (size_t)h->conv_out_idx : h->fwd_ops.size();
+  size_t first = 0;
+  // r6: under capture the timestep-embedding branch becomes a parallel branch of the graph (fork after the statistics clear, which advances the step counter
+  // the branch reads; join in front of the first launch that reads the scale / shift rows).  Eager loops keep one stream: same launches, same results.
+  if (capturing && temb_forks(h, last)) {
+    if (!h->tfork.side_stream) HIPCHK(hipStreamCreateWithFlags(&h->tfork.side_stream, hipStreamNonBlocking));
+    if (!h->tfork.ev_fork) HIPCHK(hipEventCreateWithFlags(&h->tfork.ev_fork, hipEventDisableTiming));
+    if (!h->tfork.ev_join) HIPCHK(hipEventCreateWithFlags(&h->tfork.ev_join, hipEventDisableTiming));
+    if (run_ops(h->fwd_ops, s, 0, (size_t)h->tfork.begin)) return 1;
+    HIPCHK(hipEventRecord(h->tfork.ev_fork, s));
+    HIPCHK(hipStreamWaitEvent(h->tfork.side_stream, h->tfork.ev_fork, 0));
+    if (run_ops(h->fwd_ops, h->tfork.side_stream, (size_t)h->tfork.begin, (size_t)h->tfork.end)) return 1;
+    HIPCHK(hipEventRecord(h->tfork.ev_join, h->tfork.side_stream));
+    if (run_ops(h->fwd_ops, s, (size_t)h->tfork.end, (size_t)h->tfork.join)) return 1;
+    HIPCHK(hipStreamWaitEvent(s, h->tfork.ev_join, 0));
+    first = (size_t)h->tfork.join;
+  }
+  if (run_ops(h->fwd_ops, s, first, last)) return 1;
+  if (fold) {
+    HIPCHK(launch_gemm(g, h->conv_out_prec, s));
+    return 0;
+  }
+  const size_t n = (size_t)h->B * h->T * h->CP;
+  SolverNoise nz;
+  if (h->stochastic) {       // noise on the item's valid frames and real channels only (masked plan: level-0 lengths = the first B entries)
+    nz.seeds = h->seeds.dev; nz.lens = h->lens.masked ? h->lens.dev : nullptr; nz.T = h->T; nz.ld = h->CP; nz.nc = h->cfg.latent_channels;
+  }
+  HIPCHK(launch_solver_update(h->coef_dev, h->step_dev, NS2VC_NCOEF, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s, h->pair_off(), nz,
+                              h->hist2.on ? h->hist2.mprev2 : nullptr));
+  return 0;
+}
+
+// The loop in three parts, so that a caller can hand the solver state to a second engine in mid-loop (mixed precision:
+// ns2vc_sampler_handoff): begin = state from x_T, steps = the next n evaluations + updates, end = layout change back.
+int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
+  if (check_ready(h, true)) return 1;
+  if (!x_T_bct) return fail("null tensor");
+  if (!h->coef_dev || h->steps <= 0) return fail("no solver table loaded (call ns2vc_sampler_load)");
+  if (h->stochastic && !h->seeds.set) return fail("the loaded solver table adds noise: set per-item seeds first (ns2vc_sampler_set_seeds)");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)h->B * h->T * h->CP;
+  if (load_state(h, x_T_bct, s)) return 1;  // (masked: x_T is zero past every item's end; the solver update keeps it so -- its noise term skips those rows)
+  HIPCHK(launch_copy16(h->xe, h->xbar, n * sizeof(float), s));
+  HIPCHK(launch_zero(h->d1, n * sizeof(float), s));
+  HIPCHK(launch_zero(h->mprev, n * sizeof(float), s));
+  if (h->hist2.on) {
+    if (ensure_mprev2(h)) return 1;
+    HIPCHK(launch_zero(h->hist2.mprev2, n * sizeof(float), s));
+  }
+  HIPCHK(launch_fill_i32(h->step_dev, -1, s));      // the first launch of every step advances it (gn_stats.clear)
+  h->next_step = 0;
+  return 0;
+}
+
+int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream) {
+  if (check_ready(h, true)) return 1;
+  if (!h->coef_dev || h->steps <= 0) return fail("no solver table loaded (call ns2vc_sampler_load)");
+  if (h->next_step < 0) return fail("no sampling loop in progress (call ns2vc_sampler_begin or ns2vc_sampler_handoff)");
+  if (h->hist2.on && !h->hist2.mprev2) return fail("history-2 table without its m_prev2 buffer (begin the loop after loading the table)");
+  if (n_steps < 0 || h->next_step + n_steps > h->steps) return fail("steps %d..%d outside the loaded table of %d", h->next_step, h->next_step + n_steps, h->steps);
+  hipStream_t s = (hipStream_t)stream;
+  const auto& c = h->cfg;
+  h->use_step_table = true;
+  if (!h->temb_table_valid) {      // new table or new weights: timestep MLP of every table row (column 0 = t), no prompt term
+    const int E = c.block_out_channels[0] * 4;
+    if (!h->temb_table) HIPCHK(hipMalloc((void**)&h->temb_table, (size_t)1024 * E * sizeof(float)));
+    HIPCHK(launch_time_embed(h->coef_dev, NS2VC_NCOEF, nullptr, 0, h->t_w1t, h->t_b1, h->t_w2t, h->t_b2, nullptr, h->temb_table, nullptr,
+                             h->prec, h->steps, c.block_out_channels[0], E, s));
+    h->temb_table_valid = true;
+  }
+  if (use_graph && !h->step_graph && n_steps > 0) {
+    if (!h->cap_stream) HIPCHK(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
+    hipGraph_t graph = nullptr;
+    HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+    const int rc = run_step(h, h->cap_stream, true);
+    hipError_t e = hipStreamEndCapture(h->cap_stream, &graph);
+    if (rc) { if (graph) (void)hipGraphDestroy(graph); return 1; }
+    if (e != hipSuccess) return fail("hipStreamEndCapture: %s", hipGetErrorString(e));
+    e = hipGraphInstantiate(&h->step_graph, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) { h->step_graph = nullptr; return fail("hipGraphInstantiate: %s", hipGetErrorString(e)); }
+  }
+  for (int i = 0; i < n_steps; ++i) {
+    if (use_graph) HIPCHK(hipGraphLaunch(h->step_graph, s));
+    else if (run_step(h, s)) return 1;
+  }
+  h->next_step += n_steps;
+  return 0;
+}
+
+// Solver state of `src` (x_e, x_bar, d1, m_prev, m_prev2 of history-2 tables, loop position) -> `dst`, which continues the SAME table from there: the
+// engines may differ in precision (the state is fp32 in every mode; dst's operand copy of x_e is rebuilt in its own type).
+// Both must be prepared for the same (B, T) and hold the same solver table and condition.
+int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
+  if (check_ready(dst, true) || check_ready(src, true)) return 1;
+  if (dst == src) return fail("handoff to the same engine");
+  if (dst->B != src->B || dst->T != src->T || dst->CP != src->CP) return fail("handoff between different shapes");
+  if (dst->device != src->device) return fail("handoff between engines on different devices");
+  if (src->next_step < 0) return fail("source engine has no sampling loop in progress");
+  if (!dst->coef_dev || dst->steps != src->steps) return fail("destination engine must hold the same solver table (%d vs %d steps)", dst->steps, src->steps);
+  if (dst->coef_hash != src->coef_hash) return fail("destination engine holds a DIFFERENT solver table with the same number of steps (solver / order / betas differ)");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)src->B * src->T * src->CP;
+  HIPCHK(launch_copy16(src->xe, dst->xe, n * sizeof(float), s));
+  HIPCHK(launch_copy16(src->xbar, dst->xbar, n * sizeof(float), s));
+  HIPCHK(launch_copy16(src->d1, dst->d1, n * sizeof(float), s));
+  HIPCHK(launch_copy16(src->mprev, dst->mprev, n * sizeof(float), s));
+  if (src->hist2.on) {          // (same table hash: dst->hist2.on too)
+    if (ensure_mprev2(dst)) return 1;
+    HIPCHK(launch_copy16(src->hist2.mprev2, dst->hist2.mprev2, n * sizeof(float), s));
+  }
+  HIPCHK(launch_cast_op(dst->xe, n, dst->xe_op, dst->prec, s, dst->pair_off()));
+  if (src->seeds.set) {      // the tail continues the same noise stream
+    if (ensure_seeds(dst, src->B)) return 1;
+    HIPCHK(launch_copy16(src->seeds.dev, dst->seeds.dev, (size_t)((src->B + 1) & ~1) * sizeof(unsigned long long), s));
+    dst->seeds.set = true;
+  }
+  HIPCHK(launch_fill_i32(dst->step_dev, src->next_step - 1, s));
+  dst->next_step = src->next_step;
+  src->next_step = -1;
+  return 0;
+}
+
+int ns2vc_sampler_peek(ns2vc_unet* h, float* x_out_bct, void* stream) {
+  if (check_ready(h, true)) return 1;
+  if (!x_out_bct) return fail("null tensor");
+  if (h->next_step < 0) return fail("no sampling loop in progress");
+  HIPCHK(launch_btc_to_nct(h->xe, h->CP, h->cfg.latent_channels, h->T, h->B, x_out_bct, (hipStream_t)stream));
+  return 0;
+}
+
+int ns2vc_sampler_end(ns2vc_unet* h, float* x_out_bct, void* stream) {
+  if (ns2vc_sampler_peek(h, x_out_bct, stream)) return 1;
+  h->next_step = -1;
+  return 0;
+}
+
+int ns2vc_sampler_run(ns2vc_unet* h, float* x_inout_bct, int use_graph, void* stream) {
+  if (ns2vc_sampler_begin(h, x_inout_bct, stream)) return 1;
+  if (ns2vc_sampler_steps(h, h->steps, use_graph, stream)) return 1;
+  return ns2vc_sampler_end(h, x_inout_bct, stream);
+}
+
+}  // extern "C"

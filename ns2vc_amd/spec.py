@@ -75,7 +75,7 @@ class UNetConfig:
 
 
 def engine_block_types(n_levels: int) -> Tuple[Tuple[str, ...], Tuple[str, ...]]:
-    """The (down, up) block types the HIP engine builds for ``n_levels`` levels (csrc/engine.cpp make_topology): cross-attention at every
+    """The (down, up) block types the HIP engine builds for ``n_levels`` levels (csrc/pack.cpp make_topology): cross-attention at every
     level but the deepest."""
     return (("CrossAttnDownBlock2D",) * (n_levels - 1) + ("DownBlock2D",),
             ("UpBlock2D",) + ("CrossAttnUpBlock2D",) * (n_levels - 1))

@@ -1140,7 +1140,7 @@ def test_rowchain_groupnorm_prologue_bounds(dim, B, T, nt, Gn, prec, diag):
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # layouts a launcher refuses: the ONLY cases of this file that are not run.  Each row: entry point, layout, the header sentence that forbids
-# it.  None of them is a layout engine.cpp's Planner passes (its lda* / ldo* are channel counts, multiples of 64 elements, and its workspace
+# it.  None of them is a layout plan.cpp's Planner passes (its lda* / ldo* are channel counts, multiples of 64 elements, and its workspace
 # slices are 256-byte aligned).  If a launcher starts accepting one, the test fails until the row is removed and the layout is run above.
 # ---------------------------------------------------------------------------------------------------------------------------------------
 EXPECTED_REFUSALS = [

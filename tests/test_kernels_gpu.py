@@ -1118,7 +1118,7 @@ def test_ffn_fused(dim, B, T, prestage, prec, diag):
     W1, b1 = rng.standard_normal((8 * d, d)) / np.sqrt(d), 0.3 * rng.standard_normal(8 * d)
     W2, b2 = rng.standard_normal((d, 4 * d)) / np.sqrt(4 * d), 0.3 * rng.standard_normal(d)
     Wpo, bpo = rng.standard_normal((d, d)) / np.sqrt(d), 0.3 * rng.standard_normal(d)
-    # ---- pack-time folds (engine.cpp pack_all), fp64
+    # ---- pack-time folds (pack.cpp pack_all), fp64
     W1f, b1f = W1 * gamma[None, :], b1 + W1 @ beta
     order = np.concatenate([np.concatenate([np.arange(32 * g, 32 * g + 32), 4 * d + np.arange(32 * g, 32 * g + 32)]) for g in range(4 * d // 32)])
     W1p, b1p = W1f[order].astype(np.float32), b1f[order].astype(np.float32)
