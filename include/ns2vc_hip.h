@@ -69,6 +69,9 @@ enum { NS2VC_PREC_F32 = 0,  /* fp32 operands, exact-fp32 MFMA (v_mfma_f32_32x32x
 
 /* ---- library ----------------------------------------------------------------------- */
 int ns2vc_abi_version(void);
+/* sizeof(ns2vc_gemm_args) as this library was built: the struct grows at its END within an ABI version (the last field is `lens`), so a binding that
+ * mirrors it compares sizes before it passes one */
+int ns2vc_sizeof_gemm_args(void);
 const char* ns2vc_last_error(void);
 int ns2vc_device_count(int* out_count);
 int ns2vc_set_device(int device);               /* one process per GPU: call with LOCAL_RANK */
@@ -100,6 +103,8 @@ int ns2vc_unet_num_missing_weights(ns2vc_unet* h, char* first_missing, int bufle
  *   "fold_ff"   1|0  ff.net.2 folded into proj_out at pack time (default 1) vs two launches
  *   "fuse_ffn"  1|0  GEGLU feed-forward + proj_out in ONE launch where eligible (16-bit precisions, dim <= 256; needs
  *                    ln_linear and fold_ff; default 1) vs the GEGLU GEMM + the folded GEMM
+ *   "masked_fuse" 1|0  (default 0) a plan built under per-item lengths keeps the fused launches whose kernels mask their own rows
+ *                    (ns2vc_gemm_args.lens) instead of the unfused launches described at ns2vc_unet_set_lengths; dense plans ignore it
  * The environment variables NS2VC_LN_LINEAR / NS2VC_FOLD_FF / NS2VC_FUSE_FFN set the defaults at ns2vc_unet_create.
  *   "temb_join_skip" n  (tests, not a plan option) record the fork_temb join at the (n+1)-th reader of the time scale /
  *                    shift rows instead of the first; the plan build then refuses the fork (ns2vc_unet_op_info which = 2) */
@@ -311,6 +316,17 @@ typedef struct ns2vc_gemm_args {  /* implicit GEMM: conv1d k3/k1 (stride 1, stri
    *                  prologue only (its own instantiation; other kernels refuse the flag).  Without gnp_x a pair is just a wider operand tensor: any kernel takes it.
    *   sol_op_pair = 1: sol_xe_op rows hold such a pair, [hi(sol_ld) | lo(sol_ld)], row stride 2 * sol_ld (what ns2vc_k_solver_update writes for the engine). */
   int32_t gnp_pair, sol_op_pair;
+  /* Per-item valid lengths (backward-compatible addition to ABI v7: the field is the LAST of the struct, NULL = everything above as it was).
+   * lens = DEVICE [B], 1 <= lens[b] <= Tout: the kernel keeps the row invariant of a length-masked batch itself.  An output row (b, t) with
+   * t >= lens[b] is stored as exact zeros in out_f32 and out_op (bias and residual not added, whatever the accumulator, the residual row or the
+   * operand rows behind it hold) and adds nothing to `stats`; with gnp_x the prologue takes mean / rstd over lens[b] * (channels per group)
+   * elements instead of Tin * ..., and writes the operand rows (a0, gnp_raw, both planes of a gnp_pair) past lens[b] as zeros.  The per-item
+   * period of the rows is Tout (= Tin wherever a prologue runs).  Served by the masked instantiations of the tap-sharing conv kernel (materialising
+   * prologue; algo 0 is run as algo 2) and of the 8-wave GEMM kernel without a prologue; every other combination is refused, never run unmasked:
+   * rowstats, ln_stats, sol_coef, gnp_x outside the tap-sharing kernel, N % 128 != 0 or a narrow GEGLU (N < 2048) outside it.
+   * The struct is 8 bytes longer than in earlier builds of ABI v7 and ns2vc_k_gemm reads all of it: a binding compiled against the earlier header
+   * MUST be rebuilt (or it passes 8 bytes of its own memory as `lens`); ns2vc_sizeof_gemm_args() is there to check. */
+  const int32_t* lens;
 } ns2vc_gemm_args;
 
 typedef struct ns2vc_attn_args {

@@ -57,6 +57,7 @@ class GemmArgs(C.Structure):
         ("sol_xe", C.c_void_p), ("sol_xe_op", C.c_void_p), ("sol_xbar", C.c_void_p), ("sol_d1", C.c_void_p), ("sol_mprev", C.c_void_p), ("sol_ld", C.c_int32),
         ("conv_bn", C.c_int32),
         ("gnp_pair", C.c_int32), ("sol_op_pair", C.c_int32),
+        ("lens", C.c_void_p),
     ]
 
 
@@ -123,6 +124,7 @@ _PP = C.POINTER(C.c_void_p)
 _I = C.c_int
 PROTOTYPES = {
     "ns2vc_abi_version": (_I, []),
+    "ns2vc_sizeof_gemm_args": (_I, []),
     "ns2vc_last_error": (C.c_char_p, []),
     "ns2vc_device_count": (_I, [C.POINTER(_I)]),
     "ns2vc_set_device": (_I, [_I]),
@@ -239,6 +241,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         fn.argtypes = args
     if lib.ns2vc_abi_version() != ABI_VERSION:
         raise Ns2vcError(f"ABI version mismatch: library reports {lib.ns2vc_abi_version()}, binding expects {ABI_VERSION}")
+    if lib.ns2vc_sizeof_gemm_args() != C.sizeof(GemmArgs):
+        raise Ns2vcError(f"ns2vc_gemm_args: library has {lib.ns2vc_sizeof_gemm_args()} bytes, binding {C.sizeof(GemmArgs)}")
     if path is None:
         _lib = lib
     return lib

@@ -119,8 +119,15 @@ template <int LO, int HI> struct TsWait {
 // normalise inside the K loop (gnpro.h GnInloop; chunk-granular loop only)
 // SOL: with the solver-update epilogue (GemmArgs.sol_*; its own instantiations: compiled into every kernel it cost the 128-column tiles 26 spilled registers and the
 // step 0.2 %, profiles/r06_ab_split_io.txt)
-template <typename TM, int BN, int NL, int GNP, bool KS = false, bool SOL = false>
+// MASKED: per-item valid lengths (GemmArgs.lens; option masked_fuse).  The epilogue stores the rows past an item's end as exact zeros (no bias, no residual) and
+// keeps them out of the GroupNorm statistics; the prologue divides by the item's own element count and writes zero operand rows there (gnpro.h).  Its own
+// instantiations, like SOL: the dense kernels keep their instructions (a run-time test in this epilogue gave every tile spills, r6 register audit)
+// (the flag rides in the GNP argument as + 4 -- GNP 4 | 5 | 7 = masked 0 | 1 | 3 -- so that the template's argument list stays <.., GNP, KS, SOL>)
+enum { TS_GN_NONE = 0, TS_GN_PRO = 1, TS_GN_INLOOP = 2, TS_GN_PAIR = 3, TS_MASKED = 4 };     // GNPF = one of the first four (| TS_MASKED)
+template <typename TM, int BN, int NL, int GNPF, bool KS = false, bool SOL = false>
 __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g) {
+  constexpr int GNP = GNPF & 3;
+  constexpr bool MASKED = (GNPF & TS_MASKED) != 0;
   op_mode_init<TM>();
   constexpr int EPC = MmaT<TM>::EPC;
   constexpr int BKE = 8 * EPC;                                   // channels per chunk
@@ -312,7 +319,7 @@ __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g
       // the real rows behind padded rows [q0 - 1, q0 + 127): f(q) = number of real rows with a padded index below q
       auto real_below = [&](int q) __attribute__((always_inline)) { const int b = q / P; return b * T + min(q - b * P, T); };
       const int rlo = real_below(max(q0 - 1, 0)), rhi = real_below(min(q0 + TS_BM - 1, MP));
-      GnPrologue<TM, NS2VC_TS_GNP_XB, GNP == 3> gpro;
+      GnPrologue<TM, NS2VC_TS_GNP_XB, GNP == 3, MASKED> gpro;
       gpro.begin(g, rlo, rhi, tm, tid, 64 * NW, coop ? tn : 0, coop ? nb_n : 1);
       gpro.finish(g, tid, aring);                                // (its table lives in the activation ring: nothing has been issued into it yet)
     }
@@ -546,6 +553,8 @@ __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g
   constexpr int QSPAN = KS ? 32 : WM;
   const int b0 = min(qw0 / P, g.B - 1);                          // its batch item; T >= 66 > QSPAN: the rows touch b0 and at most b0 + 1
   float gs0 = 0.f, gq0 = 0.f, gs1 = 0.f, gq1 = 0.f;
+  int len0 = T, len1 = T;                                        // MASKED: valid frames of items b0 and b0 + 1
+  if constexpr (MASKED) { len0 = g.lens[b0]; len1 = g.lens[min(b0 + 1, g.B - 1)]; }
 #pragma unroll
   for (int mt = 0; mt < ROUNDS; ++mt) {
     lds_barrier();                                               // rings (or the previous slab) are free
@@ -569,7 +578,7 @@ __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g
     }
     lds_barrier();
     int mrow[NIT];
-    bool okr[NIT], first[NIT];
+    bool okr[NIT], first[NIT], live[NIT];                        // live: the row takes part in the result (MASKED: t < the item's length; else = okr)
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {
       const int rl = kg * 16 + k * RPI + rsub;                   // row inside the slab
@@ -579,6 +588,7 @@ __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g
       okr[k] = rt < TS_BMO && q < MP && t < T;
       mrow[k] = okr[k] ? q - b : 0;
       first[k] = b == b0;
+      live[k] = MASKED ? okr[k] && t < (first[k] ? len0 : len1) : okr[k];
     }
     float4 rr[NIT];
     if (g.res) {                                                 // residual rows first (res may alias out_f32 element-for-element)
@@ -599,7 +609,7 @@ __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g
         a.x += a1.x; a.y += a1.y; a.z += a1.z; a.w += a1.w;
       }
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (okr[k]) {
+      if (live[k]) {
         v.x = a.x + bv.x + rr[k].x; v.y = a.y + bv.y + rr[k].y; v.z = a.z + bv.z + rr[k].z; v.w = a.w + bv.w + rr[k].w;
         const float ps = (v.x + v.y) + (v.z + v.w), pq = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
         if (first[k]) { gs0 += ps; gq0 += pq; } else { gs1 += ps; gq1 += pq; }
@@ -741,7 +751,19 @@ template <typename TM, int BN, int NL, bool KS> static hipError_t launch_ts_cfg(
   // GroupNorm in front: inside the loop (GnInloop: eight non-consumer waves = four DMA + four producer waves, chunk-granular loop, plain consumer layout) unless
   // the caller asks for the materialising prologue (algo == 2)
   constexpr bool HAS_INLOOP = NS2VC_TS_CHUNK && NL == 8 && !KS;
-  if (g.sol_coef) {                                               // the solver-update epilogue: its own instantiations (one 128-column tile, eight loaders)
+  if (g.lens) {                                                   // per-item valid lengths: the masked instantiations (eight loaders, plain consumer layout, materialising prologue)
+    constexpr bool HAS_MASKED = NL == 8 && !KS;
+    if constexpr (HAS_MASKED) {
+      if (g.sol_coef) return hipErrorInvalidValue;
+      if (g.gnp_x && g.gnp_pair) {
+        if constexpr (!std::is_same<TM, float>::value) hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, TS_GN_PAIR | TS_MASKED, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
+        else return hipErrorInvalidValue;
+      }
+      else if (g.gnp_x) hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, TS_GN_PRO | TS_MASKED, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
+      else hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, TS_GN_NONE | TS_MASKED, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
+    } else return hipErrorInvalidValue;
+  }
+  else if (g.sol_coef) {                                               // the solver-update epilogue: its own instantiations (one 128-column tile, eight loaders)
     constexpr bool HAS_SOL = BN == 128 && NL == 8 && !KS;
     if constexpr (HAS_SOL) {
       if (g.gnp_x && g.gnp_pair) {
@@ -777,6 +799,7 @@ hipError_t launch_convts(const GemmArgs& g, int prec, int bn, int nl, int ks, hi
   if (!nl) nl = NS2VC_TS_NL_DEFAULT;
   if (ks < 0) ks = NS2VC_TS_KS_DEFAULT;
   if (g.sol_coef) { bn = 128; nl = 8; ks = 0; }                   // (the one configuration the solver epilogue is instantiated for)
+  if (g.lens) { nl = 8; ks = 0; }                                 // (... and the masked epilogue / prologue: either column tile)
   if (g.N % bn) return hipErrorInvalidValue;
   switch (prec) {
     case PREC_BF16: return launch_ts_typed<bf16_t>(g, bn, nl, ks, s);
@@ -805,6 +828,14 @@ template <typename TM> static hipError_t ts_init_typed() {
     if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, 3, false, true>, ts_lds_bytes(128));
     if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, 3>, ts_lds_bytes(64));
     if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, 3>, ts_lds_bytes(128));
+  }
+  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, TS_GN_NONE | TS_MASKED>, ts_lds_bytes(64));
+  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, TS_GN_PRO | TS_MASKED>, ts_lds_bytes(64));
+  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, TS_GN_NONE | TS_MASKED>, ts_lds_bytes(128));
+  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, TS_GN_PRO | TS_MASKED>, ts_lds_bytes(128));
+  if constexpr (!std::is_same<TM, float>::value) {
+    if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, TS_GN_PAIR | TS_MASKED>, ts_lds_bytes(64));
+    if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, TS_GN_PAIR | TS_MASKED>, ts_lds_bytes(128));
   }
   if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 4, 0, true>, ts_lds_bytes(64));
   if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 4, 1, true>, ts_lds_bytes(64));

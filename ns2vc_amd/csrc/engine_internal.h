@@ -222,6 +222,12 @@ struct ns2vc_unet {
   unsigned long long coef_hash = 0;       // FNV-1a of the loaded solver table (handoff compares)
   std::vector<ns2vc::Tap> taps;
   bool has_mask = false;
+  // Option masked_fuse (off): a plan built under per-item lengths keeps the dense plan's fused launches wherever the kernel has a masked form
+  // (GemmArgs.lens: the tap-sharing conv kernel with its GroupNorm prologue, the 8-wave GEMM kernel's epilogue) -- those launches keep the
+  // rows past an item's end zero and out of the epilogue statistics themselves, so their gn_partial / mask_rows launches go away.  What
+  // has no masked form yet keeps today's unfused launches: the transformer's token-local kernels (row chains, fused feed-forward / GEGLU,
+  // LayerNorm by linearity), the attention's result rows, GEMMs on the 4-wave kernel, the nearest upsampling.  Dense plans ignore it.
+  bool masked_fuse = false;
   // Per-item valid lengths (ns2vc_unet_set_lengths).  `masked`: the plan was built for them -- GroupNorm statistics by their own pass over
   // rows whose padding is zero (no epilogue sums, so no fused GroupNorm prologue, row chain or LayerNorm by linearity), every activation's
   // rows past an item's end zeroed after the launch that writes them, the self-attention keys there masked by an additive bias row, the

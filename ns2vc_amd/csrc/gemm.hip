@@ -435,7 +435,9 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const GemmArgs g, const int 
 // partial tile in LDS (re-using the operand ring), then each of the eight waves adds the pair for 16 rows and moves
 // whole rows out (16-B fp32 / 8-B bf16 stores, coalesced); bias, GEGLU, LayerNorm fix-up, residual, statistics.
 // ---------------------------------------------------------------------------
-template <typename TM, int BM, bool LNC>
+// MASKED: per-item valid lengths (GemmArgs.lens): a result row (b, t) with t >= lens[b] is stored as exact zeros (no bias, no residual, whatever the
+// accumulator holds) and stays out of the GroupNorm statistics.  Its own instantiations: the dense epilogue keeps its instructions.
+template <typename TM, int BM, bool LNC, bool MASKED = false>
 __device__ __forceinline__ void gemm4_epilogue(const GemmArgs& g, f32x16_t (&acc)[BM / 64][2], char* smem, int m0, int n0, int tid,
                                                unsigned long long* tr, const LnRaw& lnraw) {
   constexpr int WM = BM / 2, WN = 64, MT = WM / 32, NT = 2;
@@ -491,6 +493,12 @@ __device__ __forceinline__ void gemm4_epilogue(const GemmArgs& g, f32x16_t (&acc
     lds_barrier();
     if (mt == 0) NS2VC_STAMP(5);
     const int mrow0 = mw0 + mt * 32 + kg * 16;      // first of my 16 rows
+    auto live_row = [&](int m) __attribute__((always_inline)) {       // MASKED: is row m inside its item's valid frames?
+      if constexpr (MASKED) {
+        const int mc = min(m, g.M - 1), b = mc / g.Tout;
+        return m < g.M && mc - b * g.Tout < g.lens[b];
+      } else return m < g.M;
+    };
     if (g.geglu) {
 #pragma unroll
       for (int it = 0; it < 2; ++it) {
@@ -514,6 +522,7 @@ __device__ __forceinline__ void gemm4_epilogue(const GemmArgs& g, f32x16_t (&acc
             const float4 rr = *reinterpret_cast<const float4*>(g.res + (size_t)m * g.ldres + ocol);
             v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
           }
+          if constexpr (MASKED) { if (!live_row(m)) v = make_float4(0.f, 0.f, 0.f, 0.f); }
           if (of) out_f4(of + (size_t)m * g.ldo_f32 + ocol, v.x, v.y, v.z, v.w);
           if (oo) out_op4<TM>(oo + (size_t)m * g.ldo_op + ocol, v.x, v.y, v.z, v.w);
         }
@@ -548,7 +557,7 @@ __device__ __forceinline__ void gemm4_epilogue(const GemmArgs& g, f32x16_t (&acc
         }
         float ps = 0.f, pq = 0.f;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (m < g.M) {
+        if (live_row(m)) {
           v.x = a.x + bv.x + rr[k].x; v.y = a.y + bv.y + rr[k].y; v.z = a.z + bv.z + rr[k].z; v.w = a.w + bv.w + rr[k].w;
           ps = (v.x + v.y) + (v.z + v.w); pq = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
           if (m < mB) { gs0 += ps; gq0 += pq; } else { gs1 += ps; gq1 += pq; }
@@ -649,7 +658,7 @@ template <int SPEC> struct G4Waves {
 };
 // GNP: the instantiation that carries the GroupNorm prologue (its own kernels: the prologue's registers -- +20 at its peak -- would
 // otherwise cost the 64-row loader / consumer tiles of EVERY GEMM their second workgroup per CU)
-template <typename TM, int BM, int BN, int STAGES, bool LNC, int SPEC = 0, bool GNP = false>
+template <typename TM, int BM, int BN, int STAGES, bool LNC, int SPEC = 0, bool GNP = false, bool MASKED = false>
 __global__ __launch_bounds__(64 * G4Waves<SPEC>::NW) void gemm4_kernel(const GemmArgs g NS2VC_G4_FLAGS_PARAM) {
   op_mode_init<TM>();
   constexpr int EPC = MmaT<TM>::EPC;
@@ -954,7 +963,7 @@ __global__ __launch_bounds__(64 * G4Waves<SPEC>::NW) void gemm4_kernel(const Gem
   }
 
   if (SPEC != 0 && ewave < 0) return;             // loaders beyond the epilogue's eight waves
-  gemm4_epilogue<TM, BM, LNC>(g, acc, smem, m0, n0, tid - EOFF * 64, tr, lnraw);
+  gemm4_epilogue<TM, BM, LNC, MASKED>(g, acc, smem, m0, n0, tid - EOFF * 64, tr, lnraw);
 }
 
 // ---------------------------------------------------------------------------
@@ -989,11 +998,13 @@ static hipError_t launch_cfg4(const GemmArgs& g, hipStream_t s) {
   int nb = (g.N / BN) * ((g.M + BM - 1) / BM);
   if (g.gnp_x && g.gnp_sync && g.N / BN > 1) nb = 8 * (((g.M + BM - 1) / BM + 7) / 8) * (g.N / BN);   // cooperative prologue: row blocks per XCD, padded
 #if NS2VC_GEMM_ABLATE
+  if (g.lens) return hipErrorInvalidValue;                    // (the ablation build has no masked instantiations: refused, never run unmasked)
   if (g.gnp_x) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC, true>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g, g_gemm_flags);
   else if (g.ln_stats) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, true, SPEC>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g, g_gemm_flags);
   else hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g, g_gemm_flags);
 #else
-  if (g.gnp_x) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC, true>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g);   // (never with a LayerNorm consumer epilogue: launch_gemm checks)
+  if (g.lens) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC, false, true>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g);   // (no prologue, no LayerNorm consumer: launch_gemm checks)
+  else if (g.gnp_x) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC, true>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g);   // (never with a LayerNorm consumer epilogue: launch_gemm checks)
   else if (g.ln_stats) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, true, SPEC>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g);
   else hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g);
 #endif
@@ -1015,8 +1026,9 @@ void set_forced_gemm_tile(int bm, int bn, int stages) {
 // Tile choice.  `st` 2..4 = gemm2_kernel with that ring depth; 12 / 13 = gemm4_kernel (8 waves, K split) with ring 2 / 3.
 // The compiled set is exactly what this function can return:
 //   gemm4: {128, 64} x 128, ring {2, 3};   gemm2 (4 waves): 64x128 ring 2 (narrow GEGLU), 64x64 ring {2, 3, 4} (N not a multiple of 128).
+// `dry`: nothing is launched -- hipSuccess when the tile choice lands on a kernel that has a masked epilogue (gemm_masks_rows)
 template <typename TM>
-static hipError_t launch_typed(const GemmArgs& g, hipStream_t s) {
+static hipError_t launch_typed(const GemmArgs& g, hipStream_t s, bool dry = false) {
   const int bke = 128 / (int)sizeof(TM);
   const int nk = g.K / bke;
   int bm, bn, st;
@@ -1050,6 +1062,8 @@ static hipError_t launch_typed(const GemmArgs& g, hipStream_t s) {
     }
   }
   if (g.gnp_x && !((st >= 12 && st <= 13) || (st >= 22 && st <= 44))) return gemm_invalid(__LINE__);   // the prologue lives in gemm4_kernel
+  if (g.lens && !((st >= 12 && st <= 13) || (st >= 22 && st <= 44))) return gemm_invalid(__LINE__);    // ... and so does the masked epilogue
+  if (dry) return hipSuccess;
   if (st >= 22 && st <= 44) {   // loader / consumer specialised kernels: st = 10 * (1 + SPEC) + ring depth
     if (bn != 128) return gemm_invalid(__LINE__);
 #define NS2VC_CASE4S(BM_, ST_, SP_) if (bm == BM_ && st == 10 * (1 + SP_) + ST_) return launch_cfg4<TM, BM_, 128, ST_, SP_>(g, s)
@@ -1087,6 +1101,8 @@ hipError_t launch_gemm(const GemmArgs& g_, int prec, hipStream_t s) {
   if (g.ln_stats && (!g.ln_wsum || g.ln_dim <= 0 || (g.ln_dim & 127) || g.ln_dim > 512)) return gemm_invalid(__LINE__);
   if (g.rowstats && (g.N & 127)) return gemm_invalid(__LINE__);
   if ((g.out_f32 && (g.ldo_f32 & 3)) || (g.out_op && (g.ldo_op & 3)) || (g.res && (g.ldres & 3))) return gemm_invalid(__LINE__);   // 16-B row segments
+  // per-item valid lengths: rows of period Tout; no LayerNorm by linearity (its row statistics and health read-out have no masked form), no solver epilogue
+  if (g.lens && (g.rowstats || g.ln_stats || g.sol_coef || g.Tout < 1 || g.M != g.B * g.Tout)) return gemm_invalid(__LINE__);
   if (g.gnp_x) {     // GroupNorm-apply prologue: one or two (concatenated) sources, same-length rows, whole 16-channel blocks per group, <= 3 batch items per tile + halo
     // (gnp_pair: a0 holds the hi + lo planes of c0 / 2 normalised channels; the hi plane may be read once more through a1 = a0)
     const int cn = g.gnp_pair ? g.c0 >> 1 : g.c0;
@@ -1120,12 +1136,33 @@ hipError_t launch_gemm(const GemmArgs& g_, int prec, hipStream_t s) {
   }
   if (g.sol_coef) return gemm_invalid(__LINE__);             // the solver epilogue exists in the tap-sharing kernel only
   if (g.gnp_pair) return gemm_invalid(__LINE__);             // ... and so does the prologue that writes hi + lo operand pairs
+  if (g.lens && g.gnp_x) return gemm_invalid(__LINE__);      // ... and the masked GroupNorm prologue
   switch (prec) {
     case PREC_BF16: return launch_typed<bf16_t>(g, s);
     case PREC_F16: return launch_typed<f16_t>(g, s);
     case PREC_F32: return launch_typed<float>(g, s);
     default: return gemm_invalid(__LINE__);
   }
+}
+
+// would launch_gemm run this launch on a kernel that keeps the rows past an item's end zero by itself, were GemmArgs.lens set?  (the tap-sharing conv kernel,
+// the 8-wave kernel without a prologue: the planner asks per launch, and leaves every other launch its mask_rows launch and its separate statistics)
+bool gemm_masks_rows(const GemmArgs& g_, int prec) {
+  GemmArgs g = g_;
+  if (g.rowstats || g.ln_stats || g.sol_coef || g.N % 64 != 0 || g.M <= 0 || g.Tout < 1 || g.M != g.B * g.Tout) return false;
+  if (gemm_uses_convts(g, prec)) return true;
+  if (g.gnp_x || g.gnp_pair) return false;
+  static const int dummy = 0;
+  g.lens = &dummy;                                            // (never read: a dry run of the tile choice)
+  hipError_t e;
+  switch (prec) {
+    case PREC_BF16: e = launch_typed<bf16_t>(g, nullptr, true); break;
+    case PREC_F16: e = launch_typed<f16_t>(g, nullptr, true); break;
+    case PREC_F32: e = launch_typed<float>(g, nullptr, true); break;
+    default: return false;
+  }
+  g_gemm_fail_line = 0;
+  return e == hipSuccess;
 }
 
 // would launch_gemm hand this launch to the tap-sharing conv kernel right now?  (the engine asks before it folds the solver update into conv_out)
@@ -1150,6 +1187,7 @@ template <typename K> static hipError_t set_lds(K kern, size_t bytes) {
     hipError_t e = set_lds(gemm4_kernel<TM, BM, 128, ST, false>, gemm4_lds_bytes(BM, 128, ST));                 \
     if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, true>, gemm4_lds_bytes(BM, 128, ST));        \
     if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, 0, true>, gemm4_lds_bytes(BM, 128, ST)); \
+    if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, 0, false, true>, gemm4_lds_bytes(BM, 128, ST)); \
     if (e != hipSuccess) return e;                                                                              \
   } while (0)
 #define NS2VC_SET4S(TM, BM, ST, SP)                                                                             \
@@ -1157,6 +1195,7 @@ template <typename K> static hipError_t set_lds(K kern, size_t bytes) {
     hipError_t e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, SP>, gemm4_lds_bytes(BM, 128, ST));             \
     if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, true, SP>, gemm4_lds_bytes(BM, 128, ST));    \
     if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, SP, true>, gemm4_lds_bytes(BM, 128, ST)); \
+    if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, SP, false, true>, gemm4_lds_bytes(BM, 128, ST)); \
     if (e != hipSuccess) return e;                                                                              \
   } while (0)
 template <typename TM> static hipError_t init_typed() {

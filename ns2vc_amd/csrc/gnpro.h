@@ -28,7 +28,9 @@ namespace ns2vc {
 // back: hoisting `begin` above the kernel's row-offset set-up was measured and lost, see NS2VC_GNP_SPLIT.)
 // PAIR: the rows are written as a hi + lo operand pair (GemmArgs.gnp_pair; its own instantiation -- as a run-time test in the row loop it cost EVERY
 // prologue launch 1.5 - 1.8 %, through seven more spilled registers)
-template <typename TM, int XB_, bool PAIR = false> struct GnPrologue {
+// MASKED: per-item valid lengths (GemmArgs.lens; its own instantiation for the same reason): mean / rstd over lens[b] * Cg elements, and the rows
+// past an item's end written as zeros -- GN(0) != 0, and a conv's halo must read there what an unpadded run's zero padding holds
+template <typename TM, int XB_, bool PAIR = false, bool MASKED = false> struct GnPrologue {
 #ifndef NS2VC_GNP_XB
 #define NS2VC_GNP_XB 6
 #endif
@@ -38,6 +40,7 @@ template <typename TM, int XB_, bool PAIR = false> struct GnPrologue {
   static constexpr int XB = XB_;                                            // rows in flight per thread (1: no gain in the loop, 6: -1 %); more only where the tile is alone on its CU anyway
   static constexpr int OFF_BSUM = 256, OFF_OK = 3584;                       // table area (the ring stage nobody has been issued into yet): (mean, rstd) pairs | block sums | flag
   int rlo, rhi, olo, ohi, lim, rln, b_lo, nbi, rl, c, cq, gg, Cg, nshare_, cur;
+  int vend;                                                                 // MASKED: first row past the valid rows of item `cur`
   unsigned long long* cnt_;
   bool active;
   float4 ga, be, t1, t2, xb[XB];                                            // t1 / t2: the time (scale | shift) quad of item `cur`
@@ -59,6 +62,7 @@ template <typename TM, int XB_, bool PAIR = false> struct GnPrologue {
   }
   __device__ __forceinline__ void load_temb(const GemmArgs& g, int bi) {
     t1 = t2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (MASKED) vend = (b_lo + bi) * g.Tin + g.lens[b_lo + bi];
     if (g.gnp_temb) {
       const int C = PAIR ? g.c0 >> 1 : g.c0;
       const float* tp = g.gnp_temb + (size_t)(b_lo + bi) * g.gnp_ldtemb + cq;
@@ -163,6 +167,9 @@ template <typename TM, int XB_, bool PAIR = false> struct GnPrologue {
           }
           float y0 = w[k].x * a[0] + b[0], y1 = w[k].y * a[1] + b[1], y2 = w[k].z * a[2] + b[2], y3 = w[k].w * a[3] + b[3];
           if (g.gnp_silu) { y0 = silu_f(y0); y1 = silu_f(y1); y2 = silu_f(y2); y3 = silu_f(y3); }
+          if constexpr (MASKED) {
+            if (r >= vend) { y0 = y1 = y2 = y3 = 0.f; w[k] = make_float4(0.f, 0.f, 0.f, 0.f); }     // (selects: whatever the padded source row holds stays out)
+          }
 #if NS2VC_GNP_WT
           out_op4<TM>(dst + (size_t)r * g.lda0 + c, y0, y1, y2, y3);
           if (PAIR) out_op4<TM>(dst + (size_t)r * g.lda0 + (g.c0 >> 1) + c, op_rest<TM>(y0), op_rest<TM>(y1), op_rest<TM>(y2), op_rest<TM>(y3));   // the lo plane of a hi + lo pair
@@ -187,8 +194,9 @@ template <typename TM, int XB_, bool PAIR = false> struct GnPrologue {
       const int nb = Cg >> 4;
       double ds = 0.0, dq = 0.0;
       for (int j = 0; j < nb; ++j) { const double2 e = bsum[bi * nblk + gq * nb + j]; ds += e.x; dq += e.y; }
-      const float inv_nf = 1.0f / ((float)T * (float)Cg);
-      const double inv_n = (double)inv_nf * (2.0 - (double)inv_nf * ((double)T * (double)Cg));
+      const int nv = MASKED ? g.lens[b_lo + bi] : T;                        // rows the statistics were taken over
+      const float inv_nf = 1.0f / ((float)nv * (float)Cg);
+      const double inv_n = (double)inv_nf * (2.0 - (double)inv_nf * ((double)nv * (double)Cg));
       const double mean = ds * inv_n;
       double var = dq * inv_n - mean * mean;
       if (var < 0.0) var = 0.0;

@@ -41,6 +41,9 @@ struct Planner {
   int gn_rows = 64;
   // per-item valid lengths (h->lens.masked): level lengths of the plan, and the zeroing of padded rows after every launch that writes a frame tensor
   bool masked = false;
+  // option masked_fuse: the launches whose kernel masks its own rows (gemm_masks_rows) get the length table instead of a mask_rows launch, keep their epilogue
+  // statistics, and a k = 3 conv on the tap-sharing kernel keeps its GroupNorm prologue
+  bool fused = false;
   std::vector<int> Ts;
   int level_of(int Tl) const {
     for (size_t l = 0; l < Ts.size(); ++l) if (Ts[l] == Tl) return (int)l;
@@ -72,7 +75,8 @@ struct Planner {
   std::map<const void*, long long*> stats_of;
   long long* new_stats(const float* tensor, int Tl, int C) {
     // (masked: the epilogue would also sum the padded rows it has not zeroed yet -- the statistics come from gn_partial over the masked rows)
-    if (Tl < 64 || (C & 15) || masked) { stats_of.erase(tensor); return nullptr; }
+    // (masked_fuse: the producer's masked epilogue leaves the padded rows out; Planner::gemm takes the slab back where the producer has no such epilogue)
+    if (Tl < 64 || (C & 15) || (masked && !fused)) { stats_of.erase(tensor); return nullptr; }
     const size_t n = (size_t)B * (C / 16) * 2;
     if (stats_used + n > stats_cap) { stats_of.erase(tensor); return nullptr; }
     long long* p = stats_pool ? stats_pool + stats_used : reinterpret_cast<long long*>(sizeof(long long) * (stats_used + 1));  // sizing pass: non-null token
@@ -142,6 +146,12 @@ struct Planner {
     // (a GroupNorm prologue reads the fp32 rows and writes + re-reads the operand rows it builds)
     const double pro = g.gnp_x ? in_rows * cgn * (4.0 + osz * (g.gnp_raw ? 2.0 : 1.0)) : 0.0;
     if (g.taps == 3 && g.tmode == TMODE_SAME && !g.conv_bn) g.conv_bn = convts_bn_for(g, h->bn128_min);     // the column tile is a PLAN decision (this engine's device)
+    // masked_fuse: the kernel zeroes the rows past an item's end itself where it can; elsewhere the mask_rows launches below and no epilogue statistics
+    const bool self_mask = fused && ops == &h->fwd_ops && g.Tout > 1 && level_of(g.Tout) >= 0 && gemm_masks_rows(g, pr);
+    if (self_mask) {
+      g.lens = lens_of(g.Tout);
+      if (g.gnp_x && g.algo == 0) g.algo = 2;                    // (the masked prologue is the materialising one)
+    } else if (masked && g.stats) { stats_of.erase(g.out_f32); g.stats = nullptr; }
     if (g.gnp_temb) temb_reader();
     add(g.gnp_x ? name + "[+norm]" : name, [=](hipStream_t s) { return launch_gemm(g, pr, s); }, 1, flops, bytes + pro);
     if (!sizing && g.gnp_x && g.gnp_sync) {
@@ -149,7 +159,7 @@ struct Planner {
       const size_t nbytes = (((size_t)g.B * g.Tin + 63) / 64) * 8;
       ops->back().rearm = [=](hipStream_t s) { return launch_zero(words, (nbytes + 15) & ~(size_t)15, s); };
     }
-    if (g.Tout > 1) {
+    if (g.Tout > 1 && !self_mask) {
       const int nc = g.geglu ? g.N / 2 : g.N;
       mask(name, g.out_f32, g.ldo_f32, nc, 4, g.Tout);
       mask(name, g.out_op, g.ldo_op, nc, operand_bytes(pr), g.Tout);
@@ -193,8 +203,18 @@ struct Planner {
     const long long* st0 = find_stats(a0);
     const long long* st1 = a1 ? find_stats(a1) : nullptr;
     const bool epi = st0 && (!a1 || st1) && (((c0 + c1) / Gq) % 16 == 0) && (c0 % 16 == 0);
+    // masked: a prologue only under masked_fuse and only in front of a conv the tap-sharing kernel takes (the one kernel with a masked prologue)
+    bool pro_ok = !masked;
+    if (masked && fused && consumer_taps == 3 && consumer_n > 0) {
+      GemmArgs t;
+      memset(&t, 0, sizeof(t));
+      t.taps = 3; t.tmode = TMODE_SAME; t.B = Bq; t.Tin = t.Tout = Tl; t.M = Bq * Tl; t.N = consumer_n;
+      t.c0 = pair ? 2 * (c0 + c1) : c0 + c1; t.c1 = pair ? c0 + c1 : 0;
+      t.algo = h->conv_ts ? 2 : 1;
+      pro_ok = gemm_uses_convts(t, prec);
+    }
     // (pair: the prologue that writes hi + lo pairs exists in the tap-sharing conv kernel only)
-    if (epi && h->fuse_gn_gemm && consumer_n > 0 && (consumer_n % 128) == 0 && (h->fuse_gn_cat || (!a1 && !raw)) && Tl >= 66 && c0 + c1 <= 1024 &&
+    if (epi && pro_ok && h->fuse_gn_gemm && consumer_n > 0 && (consumer_n % 128) == 0 && (h->fuse_gn_cat || (!a1 && !raw)) && Tl >= 66 && c0 + c1 <= 1024 &&
         (!pair || (h->conv_ts && consumer_taps == 3 && ((c0 + c1) % 64) == 0)) &&
         ((c0 + c1) % Gq) == 0 && Gq <= 8 && (lda0 & 3) == 0 && (!a1 || ((lda1 & 3) == 0 && (c1 & 15) == 0))) {
       GnPro p;
@@ -499,6 +519,7 @@ int build_plan(ns2vc_unet* h, bool sizing) {
     h->lens.selfbias = sizing ? nullptr : reinterpret_cast<float*>(static_cast<char*>(h->arena) + h->lens.off + lb);
   }
   P.masked = h->lens.masked;
+  P.fused = h->lens.masked && h->masked_fuse;
   P.Ts = Ts;
   // ---- shared scratch
   P.gn_rows = 32;

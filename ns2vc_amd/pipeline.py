@@ -86,14 +86,19 @@ class Denoiser:
 
     def __init__(self, state: Dict[str, object], cfg: UNetConfig = UNetConfig(), precision: str = DEFAULT_PRECISION,
                  betas: Optional[np.ndarray] = None, ln_guard: Optional[float] = -1.0, tail_fp32: Optional[int] = None,
-                 precision_check: Optional[float] = -1.0, attn_fallback_limit: Optional[float] = 0.10):
+                 precision_check: Optional[float] = -1.0, attn_fallback_limit: Optional[float] = 0.10, masked_fuse: bool = False):
         self.cfg = cfg
+        # engine option ``masked_fuse``: under ``lengths=`` the plan keeps its fused launches where the kernels mask their own rows; passed to
+        # the fp32 engine of the tail / self-check as well
+        self.masked_fuse = bool(masked_fuse)
         self.attn_fallback_limit = attn_fallback_limit if precision not in ("fp32", "f32") else None
         self.attn_fallback_rate_seen: Optional[float] = None
         self._attn_checked = False
         self.precision = {"f32": "fp32", "f16": "fp16"}.get(precision, precision)
         self.engine = Engine(cfg, precision=precision)
         self.engine.load_state_dict(state)
+        if self.masked_fuse:
+            self.engine.set_option("masked_fuse", True)
         self._state = state
         self.betas = linear_betas() if betas is None else np.asarray(betas, dtype=np.float32)
         # ddim / ddpm index the model's own float32 buffers, which the reference derives from the float64 betas
@@ -175,6 +180,12 @@ class Denoiser:
         """A plan option of the engine (``Engine.set_option``; e.g. ``gn_coop`` off for a pipeline that runs the denoiser on a CU partition).
         The plan and the sampler table are rebuilt by the next ``sample``."""
         self.engine.set_option(name, value)
+        if name == "masked_fuse":
+            self.masked_fuse = bool(value)
+            if self.tail_engine is not None:
+                self.tail_engine.set_option(name, value)
+                self._tail_shape = None
+                self._tail_table_key = None
         self._shape = None
         self._table_key = None
 
@@ -194,6 +205,8 @@ class Denoiser:
             self.tail_engine.load_state_dict(self._state)
             if self._ln_switched:
                 self.tail_engine.set_option("ln_linear", False)
+            if self.masked_fuse:
+                self.tail_engine.set_option("masked_fuse", True)
             self._tail_shape = None
             self._tail_table_key = None
         if self._tail_shape != self._shape:

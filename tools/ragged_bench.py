@@ -2,6 +2,8 @@
   (a) dense     -- one B = 32 batch, every segment 938 frames (the benchmark's best case);
   (b) ragged    -- one B = 32 batch padded to 938 with per-item lengths (ns2vc_unet_set_lengths);
   (c) per-shape -- equal-shape grouping without padding, which for 32 distinct lengths is 32 batch-1 loops.
+--masked-fuse adds (b') -- leg (b) with the engine option masked_fuse on -- in the same process, `--alternate` times in turn with (a) and (b), the order rotating;
+--skip-per-shape leaves (c) out.
 Each figure is the median of `--reps` timed sampling loops (hipGraph replays, condition set outside the timing) after a warm-up loop.
 Usage: python tools/ragged_bench.py [--reps 5] [--out FILE]"""
 import argparse
@@ -22,6 +24,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--masked-fuse", action="store_true", help="also run leg (b) with the option masked_fuse on")
+    ap.add_argument("--alternate", type=int, default=3, help="repetitions of (a), (b), (b') in turn (with --masked-fuse)")
+    ap.add_argument("--skip-per-shape", action="store_true")
     a = ap.parse_args()
     B, T, Lp = 32, 938, 469
     lens = [int(v) for v in np.linspace(470, 938, B).round()]
@@ -31,8 +36,13 @@ def main():
     xT = torch.from_numpy(hash_normal("rb.x", (B, 100, T))).to(dev)
     e = Engine(precision="fp16")
     e.load_state_dict(procedural_state_dict(seed=0))
+    fused_now = False                            # the engine's masked_fuse option as last set
 
-    def loop_ms(bsz, tl, lengths=None, sl=slice(None)):
+    def loop_ms(bsz, tl, lengths=None, sl=slice(None), fuse=False):
+        nonlocal fused_now
+        if fused_now != fuse:
+            e.set_option("masked_fuse", fuse)        # (drops the plan: prepared again below)
+            fused_now = fuse
         if e.shape != (bsz, tl, Lp):
             e.prepare(bsz, tl, Lp)
             e.load_sampler("unipc", a.steps)
@@ -54,12 +64,27 @@ def main():
 
     dense = loop_ms(B, T)
     ragged = loop_ms(B, T, lens)
-    per = sum(loop_ms(1, L, None, slice(i, i + 1)) for i, L in enumerate(lens))
+    alt = []
+    if a.masked_fuse:
+        legs = {"a": lambda: loop_ms(B, T), "b": lambda: loop_ms(B, T, lens), "b_fused": lambda: loop_ms(B, T, lens, fuse=True)}
+        order = ["a", "b", "b_fused"]
+        for i in range(a.alternate):             # the order rotates, so that a drift of the clocks does not favour one leg
+            rot = order[i % 3:] + order[:i % 3]
+            rep = {k: round(legs[k](), 3) for k in rot}
+            rep["order"] = rot
+            alt.append(rep)
+        loop_ms(B, T)                            # (option off again for leg (c))
+    per = 0.0 if a.skip_per_shape else sum(loop_ms(1, L, None, slice(i, i + 1)) for i, L in enumerate(lens))
     e.close()
     r = {"segments": B, "lengths": [min(lens), max(lens)], "solver": f"unipc-{a.steps}", "precision": "fp16",
          "a_dense_ms": round(dense, 3), "b_ragged_ms": round(ragged, 3), "c_per_shape_ms": round(per, 3),
          "b_over_a": round(ragged / dense, 3), "c_over_b": round(per / ragged, 2),
          "ms_per_step": {"a": round(dense / a.steps, 3), "b": round(ragged / a.steps, 3), "c": round(per / a.steps, 3)}}
+    if alt:
+        med = {k: float(np.median([x[k] for x in alt])) for k in ("a", "b", "b_fused")}
+        r["alternating_ms"] = alt
+        r["fused"] = {"b_fused_ms": round(med["b_fused"], 3), "b_fused_over_a": round(med["b_fused"] / med["a"], 3), "b_fused_over_b": round(med["b_fused"] / med["b"], 3),
+                      "ms_per_step": {k: round(v / a.steps, 3) for k, v in med.items()}}
     line = json.dumps(r)
     print(line)
     if a.out:
