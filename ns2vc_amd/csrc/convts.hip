@@ -26,14 +26,15 @@
 //     single-tap chunks (tau = 1: the centre rows) behind the main ones;
 //   * the GroupNorm-apply prologue (gnpro.h) builds exactly the real rows the panel will read; its cooperative form shares them
 //     between the N / BN column tiles of a row block;
-//   * epilogue as gemm4's (LDS-staged transpose, whole-row stores, bias, fp32 residual, fp32 + operand stores, int64 fixed-point
-//     GroupNorm statistics), with the padded -> real row map applied per stored row.
+//   * epilogue as gemm4's, from the same building blocks (epilogue.h: LDS-staged transpose, whole-row stores, bias, fp32 residual, fp32 + operand
+//     stores, int64 fixed-point GroupNorm statistics), with the padded -> real row map applied per stored row.
 //
 // The summation order over K differs from gemm4_kernel's (chunk-major instead of tap-major), so results agree with it to fp32
 // rounding, not bitwise; within this kernel everything is deterministic.
 #include "common.h"
 #include "mma.h"
 #include "gnpro.h"
+#include "epilogue.h"
 #include <type_traits>
 #include <vector>
 #include <cstring>
@@ -532,8 +533,8 @@ __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g
   TS_STAMP(2);
 
   if (ewave < 0) return;                                         // loaders beyond the epilogue's eight waves (s_barrier counts live waves only)
-  // ---- epilogue: per 32-row slab the four consumer waves stage their 32 x 64 tile in LDS (re-using the rings), then each of the
-  // eight waves moves 16 whole rows out (16-B fp32 / 8-B 16-bit stores, coalesced); bias, residual, statistics; padded -> real rows
+  // ---- epilogue (epilogue.h): per 32-row slab the four consumer waves stage their 32 x 64 tile in LDS (re-using the rings), then each of the
+  // eight waves moves 16 whole rows out; bias, residual, statistics; padded -> real rows
   const int kg = ewave >> 2, wq = ewave & 3;                     // row half inside a slab; slab slot (KS: 32-row slab of the tile, else wave tile)
   // The eight epilogue waves each own rows kg*16 .. +15 of one staged 32 x 64 slab `wq`.  Plain layout: slab wq = consumer wq's current 32-row
   // block (MT rounds); K-split layout: all four 32-row slabs of the tile are staged at once, each by the two consumers (K halves) of its
@@ -541,81 +542,49 @@ __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g
   const int em = KS ? 0 : wq / WGN, en = KS ? 0 : wq % WGN;
   constexpr int EP = 64 + 4, SLAB = 32 * EP;
   float* const etw = reinterpret_cast<float*>(smem);             // staging: [K half][4 slabs] (KS) / [4 slabs]
-  float* of = g.out_f32;
-  TM* oo = reinterpret_cast<TM*>(g.out_op);
-  constexpr int LPR = 16, RPI = 4, NIT = 4;
-  const int rsub = lane / LPR, cq = lane % LPR;
-  const int ncol = n0 + en * 64 + cq * 4;
-  float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (g.bias) bv = *reinterpret_cast<const float4*>(g.bias + ncol);
+  constexpr int LPR = 16, NIT = 4;
+  LinearCols<LPR, false> lc(lane, n0 + en * 64);
+  lc.load(g);
+  const int ncol = lc.ncol;
   constexpr int ROUNDS = KS ? 1 : MT;
   const int qw0 = q0 + (KS ? wq * 32 : em * WM);                 // first padded row of what this wave's statistics cover
   constexpr int QSPAN = KS ? 32 : WM;
   const int b0 = min(qw0 / P, g.B - 1);                          // its batch item; T >= 66 > QSPAN: the rows touch b0 and at most b0 + 1
-  float gs0 = 0.f, gq0 = 0.f, gs1 = 0.f, gq1 = 0.f;
+  GnStats gn;
   int len0 = T, len1 = T;                                        // MASKED: valid frames of items b0 and b0 + 1
   if constexpr (MASKED) { len0 = g.lens[b0]; len1 = g.lens[min(b0 + 1, g.B - 1)]; }
+  const float* const er = etw + wq * SLAB + kg * 16 * EP;        // my 16 rows
+  auto ld = [&](int row, int col) __attribute__((always_inline)) {
+    float4 a = *reinterpret_cast<const float4*>(er + row * EP + col);
+    if constexpr (KS) {                                          // K half 0 + K half 1, always in this order
+      const float4 a1 = *reinterpret_cast<const float4*>(er + 4 * SLAB + row * EP + col);
+      a.x += a1.x; a.y += a1.y; a.z += a1.z; a.w += a1.w;
+    }
+    return a;
+  };
 #pragma unroll
   for (int mt = 0; mt < ROUNDS; ++mt) {
     lds_barrier();                                               // rings (or the previous slab) are free
     if (kg == 1) {                                               // (the consumer waves)
       if constexpr (KS) {
 #pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          float* const e = etw + (kh * 4 + wm * 2 + i) * SLAB;
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) e[(8 * (r >> 2) + 4 * hi + (r & 3)) * EP + j * 32 + l31] = acc[i][j][r];
-        }
+        for (int i = 0; i < MT; ++i) epi_stage<NT, EP>(etw + (kh * 4 + wm * 2 + i) * SLAB, acc[i], lane);
       } else {
-        float* const e = etw + wq * SLAB;
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) e[(8 * (r >> 2) + 4 * hi + (r & 3)) * EP + j * 32 + l31] = acc[mt][j][r];
+        epi_stage<NT, EP>(etw + wq * SLAB, acc[mt], lane);
       }
     }
     lds_barrier();
-    int mrow[NIT];
-    bool okr[NIT], first[NIT], live[NIT];                        // live: the row takes part in the result (MASKED: t < the item's length; else = okr)
-#pragma unroll
-    for (int k = 0; k < NIT; ++k) {
-      const int rl = kg * 16 + k * RPI + rsub;                   // row inside the slab
+    auto rowof = [&](int row) __attribute__((always_inline)) {
+      const int rl = kg * 16 + row;                              // row inside the slab
       const int rt = KS ? wq * 32 + rl : em * WM + mt * 32 + rl; // row inside the tile
       const int q = q0 + rt;
       const int b = q / P, t = q - b * P;
-      okr[k] = rt < TS_BMO && q < MP && t < T;
-      mrow[k] = okr[k] ? q - b : 0;
-      first[k] = b == b0;
-      live[k] = MASKED ? okr[k] && t < (first[k] ? len0 : len1) : okr[k];
-    }
-    float4 rr[NIT];
-    if (g.res) {                                                 // residual rows first (res may alias out_f32 element-for-element)
-#pragma unroll
-      for (int k = 0; k < NIT; ++k) rr[k] = *reinterpret_cast<const float4*>(g.res + (size_t)mrow[k] * g.ldres + ncol);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NIT; ++k) rr[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float4 vv[NIT];
-    const float* const er = etw + wq * SLAB;
-#pragma unroll
-    for (int k = 0; k < NIT; ++k) {
-      const int row = kg * 16 + k * RPI + rsub;
-      float4 a = *reinterpret_cast<const float4*>(er + row * EP + cq * 4);
-      if constexpr (KS) {                                        // K half 0 + K half 1, always in this order
-        const float4 a1 = *reinterpret_cast<const float4*>(er + 4 * SLAB + row * EP + cq * 4);
-        a.x += a1.x; a.y += a1.y; a.z += a1.z; a.w += a1.w;
-      }
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (live[k]) {
-        v.x = a.x + bv.x + rr[k].x; v.y = a.y + bv.y + rr[k].y; v.z = a.z + bv.z + rr[k].z; v.w = a.w + bv.w + rr[k].w;
-        const float ps = (v.x + v.y) + (v.z + v.w), pq = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-        if (first[k]) { gs0 += ps; gq0 += pq; } else { gs1 += ps; gq1 += pq; }
-      }
-      vv[k] = v;
-    }
+      const bool okr = rt < TS_BMO && q < MP && t < T, first = b == b0;
+      const int mrow = okr ? q - b : 0;
+      return EpiRow{mrow, mrow, okr, MASKED ? okr && t < (first ? len0 : len1) : okr, first};
+    };
+    LinearRows<NIT> e;
+    epi_linear_values<LPR, NIT, false, false>(g, lane, lc, LnRow{}, gn, e, ld, rowof);
     if constexpr (SOL) {
      if (g.sol_coef) {
       // r6 (tested option, engine switch fuse_solver): the sampling loop's solver update on the tile this workgroup holds (conv_out: every latent row exactly
@@ -626,22 +595,23 @@ __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g
       float4 sxe[NIT], sxb[NIT], sd1[NIT], smp[NIT];
 #pragma unroll
       for (int k = 0; k < NIT; ++k) {
-        const size_t o = (size_t)mrow[k] * g.sol_ld + ncol;
+        const size_t o = (size_t)rowof(epi_slab_row<LPR>(lane, k)).m * g.sol_ld + ncol;
         sxe[k] = *reinterpret_cast<const float4*>(g.sol_xe + o); sxb[k] = *reinterpret_cast<const float4*>(g.sol_xbar + o);
         sd1[k] = *reinterpret_cast<const float4*>(g.sol_d1 + o); smp[k] = *reinterpret_cast<const float4*>(g.sol_mprev + o);
       }
 #pragma unroll
       for (int k = 0; k < NIT; ++k) {
-        if (okr[k]) {
-          const size_t o = (size_t)mrow[k] * g.sol_ld + ncol;
+        const EpiRow rw = rowof(epi_slab_row<LPR>(lane, k));
+        if (rw.stored) {
+          const size_t o = (size_t)rw.m * g.sol_ld + ncol;
           float4 oxe, oxb, od1, om;
-          solver_upd(sk, vv[k].x, sxe[k].x, sxb[k].x, sd1[k].x, smp[k].x, oxe.x, oxb.x, od1.x, om.x);
-          solver_upd(sk, vv[k].y, sxe[k].y, sxb[k].y, sd1[k].y, smp[k].y, oxe.y, oxb.y, od1.y, om.y);
-          solver_upd(sk, vv[k].z, sxe[k].z, sxb[k].z, sd1[k].z, smp[k].z, oxe.z, oxb.z, od1.z, om.z);
-          solver_upd(sk, vv[k].w, sxe[k].w, sxb[k].w, sd1[k].w, smp[k].w, oxe.w, oxb.w, od1.w, om.w);
+          solver_upd(sk, e.v[k].x, sxe[k].x, sxb[k].x, sd1[k].x, smp[k].x, oxe.x, oxb.x, od1.x, om.x);
+          solver_upd(sk, e.v[k].y, sxe[k].y, sxb[k].y, sd1[k].y, smp[k].y, oxe.y, oxb.y, od1.y, om.y);
+          solver_upd(sk, e.v[k].z, sxe[k].z, sxb[k].z, sd1[k].z, smp[k].z, oxe.z, oxb.z, od1.z, om.z);
+          solver_upd(sk, e.v[k].w, sxe[k].w, sxb[k].w, sd1[k].w, smp[k].w, oxe.w, oxb.w, od1.w, om.w);
           out_f4(g.sol_xe + o, oxe.x, oxe.y, oxe.z, oxe.w);
           if (g.sol_op_pair) {                             // hi + lo operand pair, rows of 2 * sol_ld columns
-            TM* const q = reinterpret_cast<TM*>(g.sol_xe_op) + o + (size_t)mrow[k] * g.sol_ld;
+            TM* const q = reinterpret_cast<TM*>(g.sol_xe_op) + o + (size_t)rw.m * g.sol_ld;
             out_op4<TM>(q, oxe.x, oxe.y, oxe.z, oxe.w);
             out_op4<TM>(q + g.sol_ld, op_rest<TM>(oxe.x), op_rest<TM>(oxe.y), op_rest<TM>(oxe.z), op_rest<TM>(oxe.w));
           } else {
@@ -654,33 +624,9 @@ __global__ __launch_bounds__(64 * (NL + 4)) void conv3ts_kernel(const GemmArgs g
       }
      }
     }
-#pragma unroll
-    for (int k = 0; k < NIT; ++k) {
-      if (okr[k]) {
-        if (of) out_f4(of + (size_t)mrow[k] * g.ldo_f32 + ncol, vv[k].x, vv[k].y, vv[k].z, vv[k].w);
-        if (oo) out_op4<TM>(oo + (size_t)mrow[k] * g.ldo_op + ncol, vv[k].x, vv[k].y, vv[k].z, vv[k].w);
-      }
-    }
+    epi_linear_store<TM, LPR, NIT, false>(g, lane, ncol, e, rowof);
   }
-  if (g.stats) {
-    // fixed shuffle tree over the lanes that share a 16-channel block (4 column quads x the row lanes), then ONE int64 fixed-point
-    // atomic per (batch item, block, moment): order-independent => deterministic
-    double d0 = gs0, d1 = gq0, d2 = gs1, d3 = gq1;
-#pragma unroll
-    for (int o = 1; o <= 2; o <<= 1) { d0 += __shfl_xor(d0, o); d1 += __shfl_xor(d1, o); d2 += __shfl_xor(d2, o); d3 += __shfl_xor(d3, o); }
-#pragma unroll
-    for (int o = LPR; o < 64; o <<= 1) { d0 += __shfl_xor(d0, o); d1 += __shfl_xor(d1, o); d2 += __shfl_xor(d2, o); d3 += __shfl_xor(d3, o); }
-    if (rsub == 0 && (cq & 3) == 0 && qw0 < MP) {
-      const int blk = ncol >> 4, nblk = g.N >> 4;
-      unsigned long long* st = reinterpret_cast<unsigned long long*>(g.stats) + ((size_t)b0 * nblk + blk) * 2;
-      atomicAdd(st, (unsigned long long)llrint(d0 * GN_SUM_SCALE));
-      atomicAdd(st + 1, (unsigned long long)llrint(d1 * GN_SQ_SCALE));
-      if (b0 + 1 < g.B && (b0 + 1) * P < qw0 + QSPAN) {
-        atomicAdd(st + 2 * nblk, (unsigned long long)llrint(d2 * GN_SUM_SCALE));
-        atomicAdd(st + 2 * nblk + 1, (unsigned long long)llrint(d3 * GN_SQ_SCALE));
-      }
-    }
-  }
+  gn.template commit<LPR>(g, lane, b0, ncol, qw0 < MP, b0 + 1 < g.B && (b0 + 1) * P < qw0 + QSPAN);
 #if NS2VC_GEMM_TRACE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (only so that the last stamp includes the store drain)
   if (tr && wave == EOFF && lane == 0) tr[3] = TS_NOW();

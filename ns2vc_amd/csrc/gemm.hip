@@ -35,6 +35,7 @@
 // attention), GroupNorm / LayerNorm partial statistics of the result.
 #include "common.h"
 #include "mma.h"
+#include "epilogue.h"
 
 namespace ns2vc {
 
@@ -55,59 +56,15 @@ __device__ unsigned long long* g_gemm_trace = nullptr;
 constexpr int TROW = 128;   // bytes of K per tile row (64 bf16 / 32 f32)
 
 // ---------------------------------------------------------------------------
-// LayerNorm by linearity.  LayerNorm(x) W^T = rstd * (x W^T - mean * rowsum(W)), so a GEMM whose input is a LayerNorm
-// reads the RAW x (the operand copy its producer writes anyway) and fixes the result up in the epilogue; the
-// producer's epilogue leaves (sum, sum of squares) per row and 64-column slice as plain fp32 stores (one writer per
-// slot: deterministic, nothing to zero).  No normalisation pass over HBM.
+// epilogues: the building blocks are epilogue.h's; here, where each kernel stages its partial tiles and its row map m = m0 + ..
 // ---------------------------------------------------------------------------
-// consumer, part 1 (top of the kernel, so the cold-load latency hides under the K loop): this lane's row pairs, raw
-struct LnRaw { float4 v[4]; };                      // up to 8 slices of 64 channels = ln_dim 512
-__device__ __forceinline__ void ln_row_load(const GemmArgs& g, int m, bool valid, LnRaw& r) {
-  const int n4 = g.ln_stats ? (g.ln_dim >> 7) : 0;  // float4 = two (sum, sumsq) pairs = 128 channels
-  const float4* p = reinterpret_cast<const float4*>(g.ln_stats + (size_t)min(m, g.M - 1) * (g.ln_dim >> 6) * 2);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) r.v[i] = (valid && i < n4) ? p[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-// consumer, part 2 (epilogue): mean / rstd of the row
-__device__ __forceinline__ void ln_row_finish(const GemmArgs& g, const LnRaw& r, float& mean_f, float& rstd_f, int n0) {
-  float s = 0.f, q = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { s += r.v[i].x + r.v[i].z; q += r.v[i].y + r.v[i].w; }
-  const float inv = 1.0f / (float)max(g.ln_dim, 1);
-  const float mean = s * inv;
-  double var = (double)q * (double)inv - (double)mean * (double)mean;     // the one cancellation-prone step
-  if (var < 0.0) var = 0.0;
-  mean_f = mean;
-  rstd_f = 1.0f / sqrtf((float)var + g.ln_eps);
-  // health of the linearity trick: the 16-bit modes round the raw row BEFORE centring, so the error on a row grows with
-  // |mean| / std.  The first column workgroup of every row panel reports the largest ratio it sees (a plain read first:
-  // the atomic is issued only by a wave that raises the maximum, i.e. a handful of times per forward).
-  if (g.ln_health && n0 == 0) {
-    float ratio = fabsf(mean) * rstd_f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ratio = fmaxf(ratio, __shfl_xor(ratio, o));
-    if ((threadIdx.x & 63) == 0 && ratio > __uint_as_float(__hip_atomic_load(g.ln_health, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
-      atomicMax(g.ln_health, __float_as_uint(ratio));
-  }
-}
-// sum over the 16 lanes (one DPP row) that hold one 64-column slice of a result row; no LDS traffic, all 16 get the total
-__device__ __forceinline__ float sum16_dpp(float x) {
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x124, 0xf, 0xf, false));   // row_ror:4
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, false));   // row_ror:8
-  return x;
-}
-// producer (64-column wave tiles only): (sum, sumsq) of this row's 64-column slice -> rowstats[m][ncol/64]
-// (plain store: every slot has exactly one writer)
-__device__ __forceinline__ void ln_row_store(const GemmArgs& g, int m, int ncol, int cq, float ps, float pq) {
-  ps = sum16_dpp(ps); pq = sum16_dpp(pq);
-  if (cq == 0 && m < g.M) *reinterpret_cast<float2*>(g.rowstats + ((size_t)m * (g.N >> 6) + (ncol >> 6)) * 2) = make_float2(ps, pq);
+// rows [mw0, mw0 + WM) of a wave tile belong to batch item b0 or b0 + 1 (Tout >= WM); mB = first row of item b0 + 1
+__device__ __forceinline__ void gemm_item_split(const GemmArgs& g, int mw0, int& b0, int& mB) {
+  b0 = g.stats ? min(mw0, g.M - 1) / g.Tout : 0;                // (division only when the statistics are wanted)
+  mB = g.stats ? (b0 + 1) * g.Tout : 0x7fffffff;
 }
 
-// ---------------------------------------------------------------------------
-// shared epilogue (bias, GEGLU, residual, fp32 / operand stores, GroupNorm statistics)
-// ---------------------------------------------------------------------------
+// gemm2_kernel: every wave transposes its whole tile through its own slice of the ring
 template <typename TM, int BM, int BN, bool LNC>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16_t (&acc)[BM / 64][BN / 64], char* smem, int m0, int n0, int tid,
                                               unsigned long long* tr, const LnRaw& lnraw) {
@@ -115,127 +72,41 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16_t (&acc)
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int l31 = lane & 31, hi = lane >> 5;
-  // ---- epilogue.  C layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5), i.e. a lane
-  // owns ONE column: direct stores would be 4-byte (fp32) / 2-byte (bf16) scalars.  Instead every wave transposes
-  // its tile through its own slice of the (now idle) LDS ring and then moves whole rows: 16-B loads of bias /
-  // residual, 16-B fp32 and 8-B bf16 stores, fully coalesced.
-  constexpr int EP = WN + 4;                       // LDS pitch in floats (16-B aligned rows)
+  constexpr int EP = WN + 4;                       // LDS pitch in floats
   NS2VC_STAMP(4);
   __syncthreads();                                 // every wave is done reading the last K tile
   float* et = reinterpret_cast<float*>(smem) + wave * (WM * EP);
 #pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) et[(i * 32 + 8 * (r >> 2) + 4 * hi + (r & 3)) * EP + j * 32 + l31] = acc[i][j][r];
+  for (int i = 0; i < MT; ++i) epi_stage<NT, EP>(et + i * 32 * EP, acc[i], lane);
   __syncthreads();
   NS2VC_STAMP(5);
-  float* of = g.out_f32;
-  TM* oo = reinterpret_cast<TM*>(g.out_op);
-  const int mw0 = m0 + wm * WM;
+  const int mw0 = m0 + wm * WM, col0 = n0 + wn * WN;
+  int b0, mB;
+  gemm_item_split(g, mw0, b0, mB);
   // LayerNorm-by-linearity consumer: lane l holds mean / rstd of row mw0 + l (l < WM; the pairs were loaded at the top
   // of the kernel so the latency hid under the K loop), fetched per row by shuffle
-  constexpr bool lnc = LNC;           // compile-time: GEMMs that are not LayerNorm consumers carry none of this
-  float lmean = 0.f, lrstd = 1.f;
-  if constexpr (lnc) ln_row_finish(g, lnraw, lmean, lrstd, n0);
+  LnRow ln;
+  if constexpr (LNC) ln_row_finish(g, lnraw, ln.mean, ln.rstd, n0);
+  auto ld = [&](int row, int col) __attribute__((always_inline)) { return *reinterpret_cast<const float4*>(et + row * EP + col); };
+  auto rowof = [&](int row) __attribute__((always_inline)) {
+    const int m = mw0 + row;
+    return EpiRow{m, min(m, g.M - 1), m < g.M, m < g.M, m < mB};
+  };
   if (g.geglu) {
     if constexpr (NT == 2) {
-      constexpr int LPR = 8, RPI = 8, NIT = WM / RPI;          // 32 output columns per row = 8 lanes x 4
-      const int rsub = lane >> 3, cq = lane & 7;
-      const int pcol = n0 + wn * WN + cq * 4;                  // packed column of the value quad; gate quad = +32
-      const int ocol = ((n0 + wn * WN) >> 1) + cq * 4;
-      float4 bv = make_float4(0.f, 0.f, 0.f, 0.f), bg = bv, wsv = bv, wsg = bv;
-      if (g.bias) { bv = *reinterpret_cast<const float4*>(g.bias + pcol); bg = *reinterpret_cast<const float4*>(g.bias + pcol + 32); }
-      if constexpr (lnc) { wsv = *reinterpret_cast<const float4*>(g.ln_wsum + pcol); wsg = *reinterpret_cast<const float4*>(g.ln_wsum + pcol + 32); }
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int row = it * RPI + rsub, m = mw0 + row;
-        float4 a = *reinterpret_cast<const float4*>(et + row * EP + cq * 4);
-        float4 t = *reinterpret_cast<const float4*>(et + row * EP + 32 + cq * 4);
-        if constexpr (lnc) {
-          const float mu = __shfl(lmean, row), rs = __shfl(lrstd, row);
-          a.x = rs * (a.x - mu * wsv.x); a.y = rs * (a.y - mu * wsv.y); a.z = rs * (a.z - mu * wsv.z); a.w = rs * (a.w - mu * wsv.w);
-          t.x = rs * (t.x - mu * wsg.x); t.y = rs * (t.y - mu * wsg.y); t.z = rs * (t.z - mu * wsg.z); t.w = rs * (t.w - mu * wsg.w);
-        }
-        if (m < g.M) {
-          float4 v;
-          v.x = (a.x + bv.x) * gelu_erf_f(t.x + bg.x); v.y = (a.y + bv.y) * gelu_erf_f(t.y + bg.y);
-          v.z = (a.z + bv.z) * gelu_erf_f(t.z + bg.z); v.w = (a.w + bv.w) * gelu_erf_f(t.w + bg.w);
-          if (g.res) {
-            const float4 rr = *reinterpret_cast<const float4*>(g.res + (size_t)m * g.ldres + ocol);
-            v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-          }
-          if (of) out_f4(of + (size_t)m * g.ldo_f32 + ocol, v.x, v.y, v.z, v.w);
-          if (oo) out_op4<TM>(oo + (size_t)m * g.ldo_op + ocol, v.x, v.y, v.z, v.w);
-        }
-      }
-      (void)LPR;
+      GegluCols<LNC> gc(lane, col0);
+      gc.load(g);
+      epi_geglu_rows<TM, WM / 8, LNC>(g, lane, gc, ln, ld, rowof);
     }
   } else {
-    constexpr int LPR = WN / 4, RPI = 64 / LPR, NIT = WM / RPI;
-    const int rsub = lane / LPR, cq = lane % LPR;
-    const int ncol = n0 + wn * WN + cq * 4;
-    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f), ws = bv;
-    if (g.bias) bv = *reinterpret_cast<const float4*>(g.bias + ncol);
-    if constexpr (lnc) ws = *reinterpret_cast<const float4*>(g.ln_wsum + ncol);
-    // optional GroupNorm statistics of the result: this wave's rows belong to batch b0 or b0+1 (Tout >= WM)
-    const int b0 = g.stats ? min(mw0, g.M - 1) / g.Tout : 0;     // (division only when the statistics are wanted)
-    const int mB = g.stats ? (b0 + 1) * g.Tout : 0x7fffffff;    // first row of the next batch item
-    float gs0 = 0.f, gq0 = 0.f, gs1 = 0.f, gq1 = 0.f;
-    constexpr int RB = NIT < 8 ? NIT : 8;                      // residual rows fetched per batch (before any store:
-#pragma unroll                                                 //  res may alias out_f32 element-for-element)
-    for (int it0 = 0; it0 < NIT; it0 += RB) {
-      float4 rr[RB];
-#pragma unroll
-      for (int k = 0; k < RB; ++k) {
-        const int m = mw0 + (it0 + k) * RPI + rsub;
-        rr[k] = (g.res && m < g.M) ? *reinterpret_cast<const float4*>(g.res + (size_t)m * g.ldres + ncol) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int k = 0; k < RB; ++k) {
-        const int row = (it0 + k) * RPI + rsub, m = mw0 + row;
-        float4 a = *reinterpret_cast<const float4*>(et + row * EP + cq * 4);
-        if constexpr (lnc) {
-          const float mu = __shfl(lmean, row), rs = __shfl(lrstd, row);
-          a.x = rs * (a.x - mu * ws.x); a.y = rs * (a.y - mu * ws.y); a.z = rs * (a.z - mu * ws.z); a.w = rs * (a.w - mu * ws.w);
-        }
-        float ps = 0.f, pq = 0.f;
-        if (m < g.M) {
-          float4 v;
-          v.x = a.x + bv.x + rr[k].x; v.y = a.y + bv.y + rr[k].y; v.z = a.z + bv.z + rr[k].z; v.w = a.w + bv.w + rr[k].w;
-          if (of) out_f4(of + (size_t)m * g.ldo_f32 + ncol, v.x, v.y, v.z, v.w);
-          if (oo) out_op4<TM>(oo + (size_t)m * g.ldo_op + ncol, v.x, v.y, v.z, v.w);
-          ps = (v.x + v.y) + (v.z + v.w); pq = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-          if (m < mB) { gs0 += ps; gq0 += pq; } else { gs1 += ps; gq1 += pq; }
-        }
-        if constexpr (LPR == 16) { if (g.rowstats) ln_row_store(g, m, ncol, cq, ps, pq); }
-      }
-    }
-    if (g.stats) {
-      // fixed shuffle tree over the lanes that share a 16-channel block (4 column quads x all row lanes),
-      // then ONE int64 fixed-point atomic per (batch item, block, moment): order-independent => deterministic
-      double d0 = gs0, d1 = gq0, d2 = gs1, d3 = gq1;
-#pragma unroll
-      for (int o = 1; o <= 2; o <<= 1) {                       // the 4 column quads of a 16-channel block
-        d0 += __shfl_xor(d0, o); d1 += __shfl_xor(d1, o); d2 += __shfl_xor(d2, o); d3 += __shfl_xor(d3, o);
-      }
-#pragma unroll
-      for (int o = LPR; o < 64; o <<= 1) {                     // the row lanes
-        d0 += __shfl_xor(d0, o); d1 += __shfl_xor(d1, o); d2 += __shfl_xor(d2, o); d3 += __shfl_xor(d3, o);
-      }
-      if (rsub == 0 && (cq & 3) == 0 && mw0 < g.M) {
-        const int blk = ncol >> 4, nblk = g.N >> 4;
-        unsigned long long* st = reinterpret_cast<unsigned long long*>(g.stats) + ((size_t)b0 * nblk + blk) * 2;
-        atomicAdd(st, (unsigned long long)llrint(d0 * GN_SUM_SCALE));
-        atomicAdd(st + 1, (unsigned long long)llrint(d1 * GN_SQ_SCALE));
-        if (mB < g.M && mB < mw0 + WM) {
-          atomicAdd(st + 2 * nblk, (unsigned long long)llrint(d2 * GN_SUM_SCALE));
-          atomicAdd(st + 2 * nblk + 1, (unsigned long long)llrint(d3 * GN_SQ_SCALE));
-        }
-      }
-    }
+    constexpr int LPR = WN / 4, NIT = WM / (64 / LPR);
+    LinearCols<LPR, LNC> lc(lane, col0);
+    lc.load(g);
+    GnStats gn;
+    LinearRows<NIT> e;
+    epi_linear_values<LPR, NIT, LNC, LPR == 16>(g, lane, lc, ln, gn, e, ld, rowof);
+    epi_linear_store<TM, LPR, NIT, LPR == 16>(g, lane, lc.ncol, e, rowof);
+    gn.template commit<LPR>(g, lane, b0, lc.ncol, mw0 < g.M, mB < g.M && mB < mw0 + WM);
   }
 #if NS2VC_GEMM_TRACE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (only so that the last stamp includes the store drain)
@@ -433,10 +304,9 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const GemmArgs g, const int 
 // ---------------------------------------------------------------------------
 // epilogue of the 8-wave K-split kernel (gemm4_kernel): per 32-row slab, both K halves stage their
 // partial tile in LDS (re-using the operand ring), then each of the eight waves adds the pair for 16 rows and moves
-// whole rows out (16-B fp32 / 8-B bf16 stores, coalesced); bias, GEGLU, LayerNorm fix-up, residual, statistics.
+// whole rows out; bias, GEGLU, LayerNorm fix-up, residual, statistics (epilogue.h).
 // ---------------------------------------------------------------------------
-// MASKED: per-item valid lengths (GemmArgs.lens): a result row (b, t) with t >= lens[b] is stored as exact zeros (no bias, no residual, whatever the
-// accumulator holds) and stays out of the GroupNorm statistics.  Its own instantiations: the dense epilogue keeps its instructions.
+// MASKED: per-item valid lengths (GemmArgs.lens; EpiRow.live).  Its own instantiations: the dense epilogue keeps its instructions.
 template <typename TM, int BM, bool LNC, bool MASKED = false>
 __device__ __forceinline__ void gemm4_epilogue(const GemmArgs& g, f32x16_t (&acc)[BM / 64][2], char* smem, int m0, int n0, int tid,
                                                unsigned long long* tr, const LnRaw& lnraw) {
@@ -445,159 +315,51 @@ __device__ __forceinline__ void gemm4_epilogue(const GemmArgs& g, f32x16_t (&acc
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kg = wave >> 2, wq = wave & 3;
   const int wm = wq >> 1, wn = wq & 1;
-  const int l31 = lane & 31, hi = lane >> 5;
-  (void)NT;
   NS2VC_STAMP(4);
-  // ---- epilogue: per 32-row slab, both K halves stage their partial tile, then each of the eight waves adds the
-  // pair for 16 rows and moves whole rows out (16-B fp32 / 8-B bf16 stores, coalesced)
   constexpr int EP = WN + 4;                        // staging pitch in floats
   constexpr int SLAB = 32 * EP;                     // floats per staged 32 x 64 slab
   float* const et_mine = reinterpret_cast<float*>(smem) + wave * SLAB;
   const float* const et_a = reinterpret_cast<const float*>(smem) + wq * SLAB + kg * 16 * EP;        // K half 0, my 16 rows
   const float* const et_b = et_a + 4 * SLAB;                                                          // K half 1
-  float* of = g.out_f32;
-  TM* oo = reinterpret_cast<TM*>(g.out_op);
-  const int mw0 = m0 + wm * WM;                     // first row of the wave tile (both K halves)
-  const int b0 = g.stats ? min(mw0, g.M - 1) / g.Tout : 0;       // (division only when the statistics are wanted)
-  const int mB = g.stats ? (b0 + 1) * g.Tout : 0x7fffffff;
-  float gs0 = 0.f, gq0 = 0.f, gs1 = 0.f, gq1 = 0.f;
-  constexpr int LPR = WN / 4, RPI = 64 / LPR, NIT = 16 / RPI;    // 16 lanes per row, 4 rows per pass, 4 passes
-  const int rsub = lane / LPR, cq = lane % LPR;
-  const int ncol = n0 + wn * WN + cq * 4;
-  float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (g.bias && !g.geglu) bv = *reinterpret_cast<const float4*>(g.bias + ncol);
-  // GEGLU: 32 output columns per row = 8 lanes x 4, 8 rows per pass
-  const int grsub = lane >> 3, gcq = lane & 7;
-  const int pcol = n0 + wn * WN + gcq * 4;          // packed column of the value quad; gate quad = +32
-  const int ocol = ((n0 + wn * WN) >> 1) + gcq * 4;
-  float4 gbv = make_float4(0.f, 0.f, 0.f, 0.f), gbg = gbv;
-  if (g.bias && g.geglu) { gbv = *reinterpret_cast<const float4*>(g.bias + pcol); gbg = *reinterpret_cast<const float4*>(g.bias + pcol + 32); }
+  const int mw0 = m0 + wm * WM, col0 = n0 + wn * WN;              // first row / column of the wave tile (both K halves)
+  int b0, mB;
+  gemm_item_split(g, mw0, b0, mB);
+  GnStats gn;
+  constexpr int LPR = WN / 4, NIT = 16 / (64 / LPR);             // 16 lanes per row, 4 rows per pass, 4 passes
   // LayerNorm-by-linearity consumer: lane l < 16*MT holds mean / rstd of the l-th row this wave will emit (loaded before the K loop)
-  constexpr bool lnc = LNC;
-  float lmean = 0.f, lrstd = 1.f;
-  float4 ws = make_float4(0.f, 0.f, 0.f, 0.f), wsv = ws, wsg = ws;
-  if constexpr (lnc) {
-    ln_row_finish(g, lnraw, lmean, lrstd, n0);
-    if (g.geglu) { wsv = *reinterpret_cast<const float4*>(g.ln_wsum + pcol); wsg = *reinterpret_cast<const float4*>(g.ln_wsum + pcol + 32); }
-    else ws = *reinterpret_cast<const float4*>(g.ln_wsum + ncol);
-  }
+  LnRow ln;
+  if constexpr (LNC) ln_row_finish(g, lnraw, ln.mean, ln.rstd, n0);
+  LinearCols<LPR, LNC> lc(lane, col0);
+  GegluCols<LNC> gc(lane, col0);
+  if (g.geglu) gc.load(g); else lc.load(g);
+  auto ld = [&](int row, int col) __attribute__((always_inline)) {          // K half 0 + K half 1, always in this order
+    const float4 a0 = *reinterpret_cast<const float4*>(et_a + row * EP + col);
+    const float4 a1 = *reinterpret_cast<const float4*>(et_b + row * EP + col);
+    return make_float4(a0.x + a1.x, a0.y + a1.y, a0.z + a1.z, a0.w + a1.w);
+  };
 
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
-    lds_barrier();                                  // ring (or the previous slab) is free.  (LDS-only barriers: the stores of
-                                                    //  the previous slab are in flight and nobody here waits for them)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) et_mine[(8 * (r >> 2) + 4 * hi + (r & 3)) * EP + j * 32 + l31] = acc[mt][j][r];
+    lds_barrier();                                  // ring (or the previous slab) is free
+    epi_stage<NT, EP>(et_mine, acc[mt], lane);
     lds_barrier();
     if (mt == 0) NS2VC_STAMP(5);
     const int mrow0 = mw0 + mt * 32 + kg * 16;      // first of my 16 rows
-    auto live_row = [&](int m) __attribute__((always_inline)) {       // MASKED: is row m inside its item's valid frames?
-      if constexpr (MASKED) {
-        const int mc = min(m, g.M - 1), b = mc / g.Tout;
-        return m < g.M && mc - b * g.Tout < g.lens[b];
-      } else return m < g.M;
+    auto rowof = [&](int row) __attribute__((always_inline)) {
+      const int m = mrow0 + row, mc = min(m, g.M - 1);
+      bool live = m < g.M;
+      if constexpr (MASKED) { const int b = mc / g.Tout; live = live && mc - b * g.Tout < g.lens[b]; }
+      return EpiRow{m, mc, m < g.M, live, m < mB};
     };
     if (g.geglu) {
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int row = it * 8 + grsub, m = mrow0 + row;
-        const float4 a0 = *reinterpret_cast<const float4*>(et_a + row * EP + gcq * 4);
-        const float4 a1 = *reinterpret_cast<const float4*>(et_b + row * EP + gcq * 4);
-        const float4 t0 = *reinterpret_cast<const float4*>(et_a + row * EP + 32 + gcq * 4);
-        const float4 t1 = *reinterpret_cast<const float4*>(et_b + row * EP + 32 + gcq * 4);
-        float4 a = make_float4(a0.x + a1.x, a0.y + a1.y, a0.z + a1.z, a0.w + a1.w);
-        float4 t = make_float4(t0.x + t1.x, t0.y + t1.y, t0.z + t1.z, t0.w + t1.w);
-        if constexpr (lnc) {
-          const float mu = __shfl(lmean, mt * 16 + row), rs = __shfl(lrstd, mt * 16 + row);
-          a.x = rs * (a.x - mu * wsv.x); a.y = rs * (a.y - mu * wsv.y); a.z = rs * (a.z - mu * wsv.z); a.w = rs * (a.w - mu * wsv.w);
-          t.x = rs * (t.x - mu * wsg.x); t.y = rs * (t.y - mu * wsg.y); t.z = rs * (t.z - mu * wsg.z); t.w = rs * (t.w - mu * wsg.w);
-        }
-        if (m < g.M) {
-          float4 v;
-          v.x = (a.x + gbv.x) * gelu_erf_f(t.x + gbg.x); v.y = (a.y + gbv.y) * gelu_erf_f(t.y + gbg.y);
-          v.z = (a.z + gbv.z) * gelu_erf_f(t.z + gbg.z); v.w = (a.w + gbv.w) * gelu_erf_f(t.w + gbg.w);
-          if (g.res) {
-            const float4 rr = *reinterpret_cast<const float4*>(g.res + (size_t)m * g.ldres + ocol);
-            v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-          }
-          if constexpr (MASKED) { if (!live_row(m)) v = make_float4(0.f, 0.f, 0.f, 0.f); }
-          if (of) out_f4(of + (size_t)m * g.ldo_f32 + ocol, v.x, v.y, v.z, v.w);
-          if (oo) out_op4<TM>(oo + (size_t)m * g.ldo_op + ocol, v.x, v.y, v.z, v.w);
-        }
-      }
+      epi_geglu_rows<TM, 2, LNC>(g, lane, gc, LnRow{ln.mean, ln.rstd, mt * 16}, ld, rowof);
     } else {
-      float4 rr[NIT];                               // residual rows first (res may alias out_f32 element-for-element)
-      if (g.res) {                                  // (uniform branch, rows past M read row M-1 and are never stored: straight-line
-#pragma unroll                                      //  loads -- per-lane conditional loads were compiled with a wait after each)
-        for (int k = 0; k < NIT; ++k) {
-          const int m = min(mrow0 + k * RPI + rsub, g.M - 1);
-          rr[k] = *reinterpret_cast<const float4*>(g.res + (size_t)m * g.ldres + ncol);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < NIT; ++k) rr[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      // Two passes: FIRST every value of the slab is computed into its own registers (this consumes all residual rows and
-      // LDS reads), THEN all stores are issued back to back.  Interleaved, the compiler had to wait for stores to complete
-      // (s_waitcnt vmcnt) before it could reuse a store's data registers for the next row pass, and with loads and stores
-      // both pending it can only wait with vmcnt(0): every pass sat through the write latency of the previous one.
-      float4 vv[NIT];
-      float2 rs2[NIT];
-#pragma unroll
-      for (int k = 0; k < NIT; ++k) {
-        const int row = k * RPI + rsub, m = mrow0 + row;
-        const float4 a0 = *reinterpret_cast<const float4*>(et_a + row * EP + cq * 4);
-        const float4 a1 = *reinterpret_cast<const float4*>(et_b + row * EP + cq * 4);
-        float4 a = make_float4(a0.x + a1.x, a0.y + a1.y, a0.z + a1.z, a0.w + a1.w);
-        if constexpr (lnc) {
-          const float mu = __shfl(lmean, mt * 16 + row), rs = __shfl(lrstd, mt * 16 + row);
-          a.x = rs * (a.x - mu * ws.x); a.y = rs * (a.y - mu * ws.y); a.z = rs * (a.z - mu * ws.z); a.w = rs * (a.w - mu * ws.w);
-        }
-        float ps = 0.f, pq = 0.f;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (live_row(m)) {
-          v.x = a.x + bv.x + rr[k].x; v.y = a.y + bv.y + rr[k].y; v.z = a.z + bv.z + rr[k].z; v.w = a.w + bv.w + rr[k].w;
-          ps = (v.x + v.y) + (v.z + v.w); pq = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-          if (m < mB) { gs0 += ps; gq0 += pq; } else { gs1 += ps; gq1 += pq; }
-        }
-        vv[k] = v;
-        rs2[k] = make_float2(0.f, 0.f);
-        if (g.rowstats) rs2[k] = make_float2(sum16_dpp(ps), sum16_dpp(pq));
-      }
-#pragma unroll
-      for (int k = 0; k < NIT; ++k) {
-        const int m = mrow0 + k * RPI + rsub;
-        if (m < g.M) {
-          if (of) out_f4(of + (size_t)m * g.ldo_f32 + ncol, vv[k].x, vv[k].y, vv[k].z, vv[k].w);
-          if (oo) out_op4<TM>(oo + (size_t)m * g.ldo_op + ncol, vv[k].x, vv[k].y, vv[k].z, vv[k].w);
-          if (g.rowstats && cq == 0) *reinterpret_cast<float2*>(g.rowstats + ((size_t)m * (g.N >> 6) + (ncol >> 6)) * 2) = rs2[k];
-        }
-      }
+      LinearRows<NIT> e;
+      epi_linear_values<LPR, NIT, LNC, true>(g, lane, lc, LnRow{ln.mean, ln.rstd, mt * 16}, gn, e, ld, rowof);
+      epi_linear_store<TM, LPR, NIT, true>(g, lane, lc.ncol, e, rowof);
     }
   }
-  if (g.stats) {
-    double d0 = gs0, d1 = gq0, d2 = gs1, d3 = gq1;
-#pragma unroll
-    for (int o = 1; o <= 2; o <<= 1) {
-      d0 += __shfl_xor(d0, o); d1 += __shfl_xor(d1, o); d2 += __shfl_xor(d2, o); d3 += __shfl_xor(d3, o);
-    }
-#pragma unroll
-    for (int o = LPR; o < 64; o <<= 1) {
-      d0 += __shfl_xor(d0, o); d1 += __shfl_xor(d1, o); d2 += __shfl_xor(d2, o); d3 += __shfl_xor(d3, o);
-    }
-    if (rsub == 0 && (cq & 3) == 0 && mw0 < g.M) {
-      const int blk = ncol >> 4, nblk = g.N >> 4;
-      unsigned long long* st = reinterpret_cast<unsigned long long*>(g.stats) + ((size_t)b0 * nblk + blk) * 2;
-      atomicAdd(st, (unsigned long long)llrint(d0 * GN_SUM_SCALE));
-      atomicAdd(st + 1, (unsigned long long)llrint(d1 * GN_SQ_SCALE));
-      if (mB < g.M && mB < mw0 + WM) {
-        atomicAdd(st + 2 * nblk, (unsigned long long)llrint(d2 * GN_SUM_SCALE));
-        atomicAdd(st + 2 * nblk + 1, (unsigned long long)llrint(d3 * GN_SQ_SCALE));
-      }
-    }
-  }
+  gn.template commit<LPR>(g, lane, b0, lc.ncol, mw0 < g.M, mB < g.M && mB < mw0 + WM);
 #if NS2VC_GEMM_TRACE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (only so that the last stamp includes the store drain)
 #endif
