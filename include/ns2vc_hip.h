@@ -243,7 +243,7 @@ typedef struct ns2vc_gemm_args {  /* implicit GEMM: conv1d k3/k1 (stride 1, stri
   void* out_op; int32_t ldo_op;   /* operand-typed copy of the result (feeds the next GEMM / attention), or NULL */
   /* optional GroupNorm statistics of the result, accumulated by the epilogue: int64 fixed point
    * [B][N/16][2] = (sum * 2^28, sum of squares * 2^16) per batch item and 16-channel block; must be zeroed
-   * by the caller; needs Tout >= 32, geglu == 0 */
+   * by the caller; needs Tout >= 64 (a wave's rows then touch at most two batch items), geglu == 0, N % 16 == 0: refused otherwise */
   long long* stats;
   /* optional second K segment (a fused 1x1 conv on another operand tensor, e.g. the resnet shortcut):
    * K = taps*(c0+c1) + c2, out += A2[m, :] * W[:, taps*(c0+c1):]; same row mapping, centre tap */

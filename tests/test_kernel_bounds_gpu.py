@@ -1148,6 +1148,23 @@ EXPECTED_REFUSALS = [
      "Conventions: operand-typed source tensors ... row pitches that are multiples of 16 bytes -- a pitch that is not is refused"),
     ("ns2vc_k_gemm", "gnp_sync with a0 16 bytes past a 128-byte line",
      "ns2vc_gemm_args.gnp_sync: Needs a0 128-byte aligned and whole 128-byte lines per row"),
+    # per-item valid lengths where no masked kernel form exists: refused, never run unmasked
+    ("ns2vc_k_gemm", "lens with a forced 4-wave tile: (64, 128, 2)",
+     "ns2vc_gemm_args.lens: Served by the masked instantiations of the tap-sharing conv kernel ... and of the 8-wave GEMM kernel ...; every other combination is refused"),
+    ("ns2vc_k_gemm", "lens with N = 192 on a linear launch: the 64-column tiles of the 4-wave kernel",
+     "ns2vc_gemm_args.lens: N % 128 != 0 ... outside it"),
+    ("ns2vc_k_gemm", "lens with GEGLU N = 1024 under the heuristic: the 4-wave kernel",
+     "ns2vc_gemm_args.lens: a narrow GEGLU (N < 2048) outside it"),
+    ("ns2vc_k_gemm", "lens with ln_stats: a LayerNorm-by-linearity consumer",
+     "ns2vc_gemm_args.lens: rowstats, ln_stats"),
+    ("ns2vc_k_gemm", "lens with sol_coef: the solver epilogue",
+     "ns2vc_gemm_args.lens: sol_coef"),
+    ("ns2vc_k_gemm", "lens with gnp_x and algo = 1: the prologue on the 8-wave kernel",
+     "ns2vc_gemm_args.lens: gnp_x outside the tap-sharing kernel"),
+    ("ns2vc_k_gemm", "lens with M != B * Tout: M one row short",
+     "ns2vc_gemm_args.lens: The per-item period of the rows is Tout"),
+    ("ns2vc_k_gemm", "stats with Tout = 63: below the smallest period the statistics take",
+     "ns2vc_gemm_args.stats: needs Tout >= 64"),
     ("ns2vc_k_geglu", "ldo = 4 dim - 8: an output pitch narrower than the hidden width",
      "ns2vc_geglu_args: out_op [M][ldo] (>= 4 dim columns)"),
     ("ns2vc_k_attention", "pv_fp8 with fp32 operands",
@@ -1166,7 +1183,72 @@ def test_expected_refusals(row, diag):
     ctx = Ctx("nan")
     prec, kind = 2, "f16"
     diag(f"bounds refusal {entry} / {layout}: call")
-    if entry == "ns2vc_k_gemm":
+    if entry == "ns2vc_k_gemm" and (layout.startswith("lens") or layout.startswith("stats")):
+        # an otherwise ordinary launch on owned buffers (outputs prefilled with NaN); only what the row names is wrong
+        what = layout.split(":")[0]
+        B, T, Cc, N, taps = 2, (63 if "Tout = 63" in what else 70), 128, 128, 1
+        geglu = "GEGLU" in what
+        if "N = 192" in what:
+            N = 192
+        if geglu:
+            N = 1024
+        if "gnp_x" in what or "sol_coef" in what:
+            taps = 3                                     # (sol_coef: k = 3, T >= 66, N = 128 -- the tap-sharing kernel's own solver epilogue, were lens not set)
+        M, K, Nout = B * T, taps * Cc, (N // 2 if geglu else N)
+        rng = np.random.default_rng(3)
+        d_w = _pack(rnd(rng.standard_normal((N, K)) / np.sqrt(K), prec), prec)
+        g = GemmArgs()
+        x = rng.standard_normal((M, Cc)).astype(np.float32)
+        d_a = ctx.t("a0", M, Cc, kind, data=rnd(x, prec))
+        g.a0, g.c0, g.lda0 = d_a.ptr, Cc, d_a.ld
+        g.B, g.Tin, g.Tout, g.M, g.taps, g.tmode = B, T, T, (M - 1 if "M != B" in what else M), taps, 0
+        g.w, g.K, g.N, g.geglu = d_w.value, K, N, int(geglu)
+        d_o = ctx.t("out_f32", M, Nout, "f32", pad=8)
+        d_op = ctx.t("out_op", M, Nout, kind, pad=8)
+        g.out_f32, g.ldo_f32, g.out_op, g.ldo_op = d_o.ptr, d_o.ld, d_op.ptr, d_op.ld
+        if what.startswith("lens"):
+            g.lens = ctx.t("lens", 1, B, "i32", data=np.array([[T, T // 2]], np.int32)).ptr
+        else:
+            g.stats = ctx.t("stats", B, N // 16 * 2, "i64", data=np.zeros((B, N // 16 * 2), np.int64)).ptr
+        if "ln_stats" in what:
+            g.ln_stats = ctx.t("ln_stats", M, 4, "f32", data=np.ones((M, 4))).ptr
+            g.ln_wsum, g.ln_eps, g.ln_dim = ctx.vec("ln_wsum", np.zeros(N, np.float32)).ptr, 1e-5, Cc
+        if "sol_coef" in what:
+            g.sol_coef, g.sol_ncoef = ctx.t("sol_coef", 2, 12, "f32", data=np.ones((2, 12))).ptr, 12
+            g.sol_step = ctx.t("sol_step", 1, 4, "i32", data=np.zeros((1, 4), np.int32)).ptr
+            state = [ctx.t(n_, M, N, "f32", data=np.ones((M, N))) for n_ in ("sol_xe", "sol_xbar", "sol_d1", "sol_mprev")]
+            g.sol_xe, g.sol_xbar, g.sol_d1, g.sol_mprev, g.sol_ld = state[0].ptr, state[1].ptr, state[2].ptr, state[3].ptr, N
+            g.sol_xe_op = ctx.t("sol_xe_op", M, N, kind, data=np.ones((M, N))).ptr
+        if "gnp_x" in what:
+            g.gnp_x, g.gnp_ldx = ctx.t("gnp_x", M, Cc, "f32", data=x).ptr, Cc
+            g.gnp_stats = ctx.t("gnp_stats", B, Cc // 16 * 2, "i64", data=_gn_stats(x, B, T, Cc).reshape(B, -1)).ptr
+            g.gnp_gamma, g.gnp_beta = ctx.vec("g", np.ones(Cc, np.float32)).ptr, ctx.vec("b", np.zeros(Cc, np.float32)).ptr
+            g.gnp_eps, g.gnp_G, g.algo = 1e-5, 8, 1
+        tile = (64, 128, 2) if "4-wave tile" in what else (0, 0, 0)
+        _check(lib.ns2vc_debug_set_gemm_tile(*tile), "set tile")
+        try:
+            rc = lib.ns2vc_k_gemm(C.byref(g), prec, None)
+            msg = lib.ns2vc_last_error()
+            untouched = all(np.array_equal(g_._download(), g_.image) for g_ in ctx.bufs)
+            # the control: what the row names is the ONLY thing wrong -- the same launch without `lens` (a `stats` row: without `stats`) runs
+            if "M != B" in what:
+                g.M = M
+            elif what.startswith("lens"):
+                g.lens = None
+            else:
+                g.stats = None
+            rc_twin = lib.ns2vc_k_gemm(C.byref(g), prec, None)
+            msg_twin = lib.ns2vc_last_error() if rc_twin else b""
+            _check(lib.ns2vc_dev_sync(), "sync")
+        finally:
+            lib.ns2vc_debug_set_gemm_tile(0, 0, 0)
+        lib.ns2vc_dev_free(d_w)
+        diag(f"bounds refusal {entry} / {layout}: rc {rc} ({msg.decode() if msg else ''}) buffers untouched {untouched}; without it rc {rc_twin} ({msg_twin.decode()})")
+        ctx.free()
+        assert rc != 0 and untouched and b"refused by the argument check" in msg, (rc, msg)
+        assert rc_twin == 0, msg_twin
+        return
+    elif entry == "ns2vc_k_gemm":
         B, T, Cc, N = 2, 70, 128, 256
         M = B * T
         W = np.zeros((N, Cc), np.float32)
