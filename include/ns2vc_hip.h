@@ -72,6 +72,7 @@ int ns2vc_abi_version(void);
 /* sizeof(ns2vc_gemm_args) as this library was built: the struct grows at its END within an ABI version (the last field is `lens`), so a binding that
  * mirrors it compares sizes before it passes one */
 int ns2vc_sizeof_gemm_args(void);
+int ns2vc_sizeof_attn_args(void);                /* the same for the attention arguments, whose last fields are `q_lens, k_lens` */
 const char* ns2vc_last_error(void);
 int ns2vc_device_count(int* out_count);
 int ns2vc_set_device(int device);               /* one process per GPU: call with LOCAL_RANK */
@@ -105,6 +106,9 @@ int ns2vc_unet_num_missing_weights(ns2vc_unet* h, char* first_missing, int bufle
  *                    ln_linear and fold_ff; default 1) vs the GEGLU GEMM + the folded GEMM
  *   "masked_fuse" 1|0  (default 0) a plan built under per-item lengths keeps the fused launches whose kernels mask their own rows
  *                    (ns2vc_gemm_args.lens) instead of the unfused launches described at ns2vc_unet_set_lengths; dense plans ignore it
+ *   "masked_attn" 1|0  (default 0) a plan built under per-item lengths gives the attention launches the level's length table (ns2vc_attn_args.q_lens /
+ *                    k_lens) instead of the self-attention key-bias row and the mask_rows launch behind each of them; independent of masked_fuse;
+ *                    dense plans ignore it
  * The environment variables NS2VC_LN_LINEAR / NS2VC_FOLD_FF / NS2VC_FUSE_FFN set the defaults at ns2vc_unet_create.
  *   "temb_join_skip" n  (tests, not a plan option) record the fork_temb join at the (n+1)-th reader of the time scale /
  *                    shift rows instead of the first; the plan build then refuses the fork (ns2vc_unet_op_info which = 2) */
@@ -339,6 +343,22 @@ typedef struct ns2vc_attn_args {
   int32_t pv_fp8;                 /* 16-bit precisions only: 1 = the PV product on the fp8 MFMA (V and the probabilities rounded to OCP e4m3) */
   int32_t exact_only;             /* 1 = skip the optimistic pass (no per-tile maximum) and take the exact pass directly */
   unsigned* fallbacks;            /* device counter or NULL: += 1 per workgroup whose optimistic pass had to be repeated exactly */
+  /* Per-item query and key counts (backward-compatible addition to ABI v7: the two fields are the LAST of the struct, both NULL = everything above as
+   * it was; either may be NULL on its own).  The row stride between items stays Lq / Lk.
+   *   k_lens = DEVICE [B], 1 <= k_lens[b] <= Lk: item b attends to its keys [0, k_lens[b]) only, exactly as the launch does for that item alone at
+   *            Lk = k_lens[b] (the same tiles in the same order: its rows are bit-identical to that launch's).  Key and value rows at or past
+   *            k_lens[b] are never read; `bias`, when also given, applies to the keys below k_lens[b].
+   *   q_lens = DEVICE [B], 1 <= q_lens[b] <= Lq: the rows of `out` at or past q_lens[b] are stored as exact zeros, whatever q holds there (those q
+   *            rows are never read).  A 128-query tile wholly past q_lens[b] stores its zeros and returns: no K / V tile staged, no MFMA.  Padded
+   *            rows take no part in the optimistic pass's repeat decision and never raise `fallbacks`.
+   * Served by the masked instantiations of the attention kernel: every operand type, head width and key tile, optimistic and exact pass.  With
+   * pv_fp8 the call is refused (hipErrorInvalidValue), never run unmasked.  The kernel clamps a count to its range before it uses it, so a bad table
+   * cannot send a fetch or a store outside the tensors; ns2vc_k_attention also reads the tables back (it waits for `stream`) and refuses a
+   * count outside its range before anything is launched.
+   * The struct is 16 bytes longer than in earlier builds of ABI v7 and ns2vc_k_attention reads all of it: a binding compiled against the earlier
+   * header MUST be rebuilt; ns2vc_sizeof_attn_args() is there to check. */
+  const int32_t* q_lens;
+  const int32_t* k_lens;
 } ns2vc_attn_args;
 
 /* Fused feed-forward + proj_out of one transformer block (attention.py:178-203 GEGLU feed-forward, transformer_1d.py:287-295),

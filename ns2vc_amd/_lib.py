@@ -115,6 +115,7 @@ class AttnArgs(C.Structure):
         ("bias", C.c_void_p), ("scale", C.c_float),
         ("out", C.c_void_p), ("ldo", C.c_int32),
         ("pv_fp8", C.c_int32), ("exact_only", C.c_int32), ("fallbacks", C.c_void_p),
+        ("q_lens", C.c_void_p), ("k_lens", C.c_void_p),
     ]
 
 
@@ -125,6 +126,7 @@ _I = C.c_int
 PROTOTYPES = {
     "ns2vc_abi_version": (_I, []),
     "ns2vc_sizeof_gemm_args": (_I, []),
+    "ns2vc_sizeof_attn_args": (_I, []),
     "ns2vc_last_error": (C.c_char_p, []),
     "ns2vc_device_count": (_I, [C.POINTER(_I)]),
     "ns2vc_set_device": (_I, [_I]),
@@ -243,6 +245,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         raise Ns2vcError(f"ABI version mismatch: library reports {lib.ns2vc_abi_version()}, binding expects {ABI_VERSION}")
     if lib.ns2vc_sizeof_gemm_args() != C.sizeof(GemmArgs):
         raise Ns2vcError(f"ns2vc_gemm_args: library has {lib.ns2vc_sizeof_gemm_args()} bytes, binding {C.sizeof(GemmArgs)}")
+    if lib.ns2vc_sizeof_attn_args() != C.sizeof(AttnArgs):
+        raise Ns2vcError(f"ns2vc_attn_args: library has {lib.ns2vc_sizeof_attn_args()} bytes, binding {C.sizeof(AttnArgs)}")
     if path is None:
         _lib = lib
     return lib

@@ -55,6 +55,7 @@ extern "C" {
 
 int ns2vc_abi_version(void) { return NS2VC_ABI_VERSION; }
 int ns2vc_sizeof_gemm_args(void) { return (int)sizeof(ns2vc_gemm_args); }
+int ns2vc_sizeof_attn_args(void) { return (int)sizeof(ns2vc_attn_args); }
 const char* ns2vc_last_error(void) { return g_err.c_str(); }
 
 int ns2vc_device_count(int* out_count) {
@@ -261,6 +262,20 @@ int ns2vc_k_geglu(const ns2vc_geglu_args* a, int precision, void* stream) {
 }
 int ns2vc_k_attention(const ns2vc_attn_args* a, int head_dim, int precision, void* stream) {
   if (!a) return fail("null args");
+  // per-item counts: this entry (tests, tools) reads the tables back and refuses a count outside its range; the engine's tables are checked on the
+  // host by ns2vc_unet_set_lengths, and the kernel clamps what it reads either way
+  if (a->q_lens || a->k_lens) {
+    if (a->B <= 0) return fail("attention: B=%d", a->B);
+    std::vector<int32_t> host((size_t)a->B);
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    const struct { const int32_t* dev; int max; const char* name; } tabs[2] = {{a->q_lens, a->Lq, "q_lens"}, {a->k_lens, a->Lk, "k_lens"}};
+    for (const auto& t : tabs) {
+      if (!t.dev) continue;
+      HIPCHK(hipMemcpy(host.data(), t.dev, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      for (int b = 0; b < a->B; ++b)
+        if (host[b] < 1 || host[b] > t.max) return fail("attention: %s[%d]=%d outside 1..%d", t.name, b, host[b], t.max);
+    }
+  }
   return launched(launch_attention(*a, head_dim, precision, (hipStream_t)stream), "launch_attention");
 }
 int ns2vc_k_groupnorm(const float* a0, int lda0, int c0, const float* a1, int lda1, int c1, int B, int T, int G, float eps,

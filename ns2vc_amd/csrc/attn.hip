@@ -141,7 +141,12 @@ template <bool B> struct OptTag { static constexpr bool value = B; };
 __device__ int g_attn_exact_only = 0;
 // slot of key (0..63) inside a 64-slot V^T row of the fp8 path
 __device__ __forceinline__ int vpos8(int key) { return ((key & 4) << 3) | ((key & 32) >> 1) | ((key & 24) >> 1) | (key & 3); }
-template <typename TM, int HD, int KEYS, bool P8>
+// MASKED: per-item query and key counts (AttnArgs.q_lens / k_lens; option masked_attn).  Its own instantiations: the dense ones keep their instructions.
+// The item's key count Lkb stands wherever the dense kernel uses Lk -- the clamp of the row fetch, the tail keys' -inf, the tile count and the C-operand
+// condition -- so item b walks exactly the tiles the dense kernel walks for it alone at Lk = Lkb (the row stride between items stays Lk).  The item's query
+// count Lqb does the same for Lq (rows past it are fetched from the last valid row, enter as zeros and never decide a repeat of the optimistic pass), except
+// that those rows exist in `out`: they are stored as exact zeros, and a query tile wholly past Lqb stores them before it touches K, V or the LDS.
+template <typename TM, int HD, int KEYS, bool P8, bool MASKED = false>
 __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
   op_mode_init<TM>();
   static_assert(!P8 || (sizeof(TM) == 2 && KEYS == 64), "the fp8 PV path: 16-bit operand types, one 64-key tile per f8f6f4 MFMA");
@@ -181,6 +186,19 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
     qb = rem - h * nqb;
   }
   const int q = qb * 128 + wave * 32 + l31;
+  int Lqb = a.Lq, Lkb = a.Lk;             // this item's query / key counts (workgroup-uniform; clamped to the tensor: a bad table cannot send a fetch outside it)
+  if constexpr (MASKED) {
+    if (a.q_lens) Lqb = min(max(a.q_lens[b], 0), a.Lq);
+    if (a.k_lens) Lkb = min(max(a.k_lens[b], 1), a.Lk);
+    if (qb * 128 >= Lqb) {                // nothing but padded queries: their zeros, and no K / V tile, no MFMA
+      if (q < a.Lq) {
+        char* zp = reinterpret_cast<char*>(a.out) + ((size_t)(b * a.Lq + q) * a.ldo + h * HD) * SZ;
+#pragma unroll
+        for (int pc = hi; pc < PPR; pc += 2) *reinterpret_cast<u32x4_t*>(zp + pc * 16) = u32x4_t{0, 0, 0, 0};
+      }
+      return;
+    }
+  }
   const float LOG2E = 1.4426950408889634f;
   const float sc2 = a.scale * LOG2E;      // scores are kept in log2 units
 
@@ -197,7 +215,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
   // ---- Q fragments (B operand of S^T = K Q^T), pre-multiplied by scale*log2e: lane (q, hi) holds d = s*2*EPC + hi*EPC .. +EPC
   u32x4_t qf[NS];
   {
-    const TM* qp = reinterpret_cast<const TM*>(a.q) + ((size_t)(b * a.Lq + min(q, a.Lq - 1)) * a.ldq + h * HD);
+    const TM* qp = reinterpret_cast<const TM*>(a.q) + ((size_t)(b * a.Lq + min(q, Lqb - 1)) * a.ldq + h * HD);
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
       const u32x4_t raw = *reinterpret_cast<const u32x4_t*>(qp + s * 2 * EPC + hi * EPC);
@@ -208,7 +226,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
         auto sc = [&](uint32_t w) __attribute__((always_inline)) { return Op16<TM>::pack(Op16<TM>::lo(w) * sc2, Op16<TM>::hi(w) * sc2); };
         qf[s] = u32x4_t{sc(raw.x), sc(raw.y), sc(raw.z), sc(raw.w)};
       }
-      if (q >= a.Lq) qf[s] = u32x4_t{0, 0, 0, 0};
+      if (q >= Lqb) qf[s] = u32x4_t{0, 0, 0, 0};
     }
   }
   float m_ref = 0.f;                       // softmax reference of this lane's query (operand-representable)
@@ -241,17 +259,17 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
       if (u < NPIECE) {
         {  // K: row-major pieces, coalesced along d
           const int key = u / PPR, pc = u - key * PPR;
-          const int kk = min(key0 + key, a.Lk - 1);
+          const int kk = min(key0 + key, Lkb - 1);
           kraw[i] = *reinterpret_cast<const u32x4_t*>(kbase + (size_t)kk * a.ldk + pc * EPC);
         }
         {  // V: key-fastest pieces (the transposed LDS write is then conflict-free)
           const int key = u % KEYS, pc = u / KEYS;
-          const int kk = min(key0 + key, a.Lk - 1);
+          const int kk = min(key0 + key, Lkb - 1);
           vraw[i] = *reinterpret_cast<const u32x4_t*>(vbase + (size_t)kk * a.ldv + pc * EPC);
         }
       }
     }
-    if (tid < KEYS && bias) braw = bias[min(key0 + tid, a.Lk - 1)];
+    if (tid < KEYS && bias) braw = bias[min(key0 + tid, Lkb - 1)];
   };
   auto store_tile = [&](int stage, int key0s) __attribute__((always_inline)) {
     char* Ks = smem + stage * STAGE;
@@ -281,13 +299,13 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
       }
     }
     if (tid < KEYS) {                                 // K aux element 1 = bias(key) in log2 units; -inf for the keys past Lk
-      const float bl = (key0s + tid < a.Lk) ? (bias ? braw * LOG2E : 0.f) : -INFINITY;
+      const float bl = (key0s + tid < Lkb) ? (bias ? braw * LOG2E : 0.f) : -INFINITY;
       *reinterpret_cast<TM*>(Ks + tid * KROWB + HD * SZ + SZ) = op_from_float<TM>(bl);
     }
   };
 
   f32x16_t o[DT];
-  const int ntile = (a.Lk + KEYS - 1) / KEYS;
+  const int ntile = (Lkb + KEYS - 1) / KEYS;
   // OPT (r3, 16-bit operand types without the fp8 PV): the per-tile maximum (16 v_max3 + a lane exchange + a vote per tile, ~15 %
   // of the loop's VALU work, which is what bounds this kernel) only guards the 16-bit range of the probabilities.  The optimistic
   // pass takes the reference from the FIRST tile alone (its maximum + OPT_MARGIN: later scores may exceed the first tile's by
@@ -326,7 +344,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
 
     // ---- S'^T[key][q] = sum_d K[key][d] * (Q[q][d]*scale*log2e) + 1*(-m_ref[q]) + bias[key]*1   (two 32-key sub-tiles)
     f32x16_t s[NSUB];
-    if (CINIT && !bias && (t + 1 < ntile || a.Lk % KEYS == 0)) {       // (wave-uniform) the reference through the C operand, no aux slab
+    if (CINIT && !bias && (t + 1 < ntile || Lkb % KEYS == 0)) {       // (wave-uniform) the reference through the C operand, no aux slab
 #pragma unroll
       for (int k2 = 0; k2 < NSUB; ++k2) {
         const char* kr = Ks + (k2 * 32 + l31) * KROWB + hi * 16;
@@ -431,7 +449,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
     // reached the fp16 range (the converts SATURATE under MODE.FP16_OVFL, so an overflow would not show up as inf), and it is
     // positive unless every probability flushed to zero -- otherwise the exact pass decides
     const float lq = o[LB][LR];
-    const int bad = (hi == 0 && q < a.Lq && !(lq > 0.f && lq < 16384.f)) ? 1 : 0;
+    const int bad = (hi == 0 && q < Lqb && !(lq > 0.f && lq < 16384.f)) ? 1 : 0;
     const bool wave_bad = __any(bad) != 0;
     if (__syncthreads_or(bad)) {
       if (a.fallbacks && threadIdx.x == 0) atomicAdd(a.fallbacks, 1u);      // (this workgroup stages its tiles twice: counted, ns2vc_unet_attn_fallbacks)
@@ -447,6 +465,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
   const float l_tot = __uint_as_float(lsw[0]);
   const float inv = 1.0f / l_tot;
   TM* op = reinterpret_cast<TM*>(a.out) + ((size_t)(b * a.Lq + min(q, a.Lq - 1)) * a.ldo + h * HD);
+  const bool padded = MASKED && q >= Lqb;      // a row past the item's end (both lane halves agree): exact zeros, whatever its accumulators hold
   if constexpr (SZ == 2) {
     // 16-bit results: the two lane halves of a query trade 4-element groups so that every lane stores 8 consecutive d (16 B) -- half the store
     // instructions of the 8-byte form, and the output of a workgroup is nothing but row-per-lane pieces whose issue sets its tail (r5: without
@@ -463,7 +482,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
 #if defined(NS2VC_ATTN_ABLATE_STORE)      // diagnostic build (wrong results, timing only): no output stores
           asm volatile("" :: "v"(x0[0]), "v"(x1[0]), "v"(x0[1]), "v"(x1[1]));
 #else
-          if (q < a.Lq) *reinterpret_cast<u32x4_t*>(op + d * 32 + 8 * (2 * gp + hi)) = u32x4_t{x0[0], x1[0], x0[1], x1[1]};
+          if (q < a.Lq) *reinterpret_cast<u32x4_t*>(op + d * 32 + 8 * (2 * gp + hi)) = padded ? u32x4_t{0, 0, 0, 0} : u32x4_t{x0[0], x1[0], x0[1], x1[1]};
 #endif
         }
       }
@@ -473,7 +492,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         const int d0 = d * 32 + 8 * gq + 4 * hi;
-        if (d0 < HD) store_op4<TM>(op + d0, o[d][4 * gq] * inv, o[d][4 * gq + 1] * inv, o[d][4 * gq + 2] * inv, o[d][4 * gq + 3] * inv);
+        if (d0 < HD) store_op4<TM>(op + d0, padded ? 0.f : o[d][4 * gq] * inv, padded ? 0.f : o[d][4 * gq + 1] * inv, padded ? 0.f : o[d][4 * gq + 2] * inv,
+                                   padded ? 0.f : o[d][4 * gq + 3] * inv);
       }
   }
 }
@@ -496,10 +516,12 @@ void set_attn_optimistic(int on) { const int v = on ? 0 : 1; (void)hipMemcpyToSy
 template <typename TM, int HD, int KEYS> static hipError_t launch_hdk(const AttnArgs& a, hipStream_t s) {
   dim3 grid(((a.Lq + 127) / 128) * a.H * a.B);
   const size_t lds = attn_lds<TM, HD, KEYS>();          // (the fp8 variant needs less: its V^T rows are half as long)
-  hipLaunchKernelGGL((attn_kernel<TM, HD, KEYS, false>), grid, dim3(256), lds, s, a);
+  if (a.q_lens || a.k_lens) hipLaunchKernelGGL((attn_kernel<TM, HD, KEYS, false, true>), grid, dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((attn_kernel<TM, HD, KEYS, false>), grid, dim3(256), lds, s, a);
   return hipGetLastError();
 }
 template <typename TM, int HD> static hipError_t launch_hd(const AttnArgs& a, hipStream_t s) {
+  if (a.pv_fp8 && (a.q_lens || a.k_lens)) return hipErrorInvalidValue;      // (the fp8 PV form has no masked instantiation: refused, never run unmasked)
   if constexpr (sizeof(TM) == 2) {
     if (a.pv_fp8) {
       dim3 grid(((a.Lq + 127) / 128) * a.H * a.B);
@@ -527,9 +549,15 @@ template <typename TM> static hipError_t launch_tm(const AttnArgs& a, int hd, hi
 template <typename TM, int HD> static hipError_t set_attr() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<TM, HD, 64, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)attn_lds<TM, HD, 64>());
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<TM, HD, 64, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)attn_lds<TM, HD, 64>());
   if constexpr (attn_has128<TM, HD>()) {
     if (e == hipSuccess)
       e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<TM, HD, 128, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)attn_lds<TM, HD, 128>());
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<TM, HD, 128, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)attn_lds<TM, HD, 128>());
   }
   if constexpr (sizeof(TM) == 2) {
@@ -553,9 +581,18 @@ hipError_t init_attn_attributes() {
   return e;
 }
 
+// would launch_attention run this launch on a masked instantiation, were AttnArgs.q_lens / k_lens set?  (every operand type, head width and key tile;
+// not the fp8 PV form)  The planner asks per launch: an attention refused here keeps its key-bias row and its mask_rows launch.
+bool attention_masks_rows(const AttnArgs& a, int head_dim, int prec) {
+  if (a.pv_fp8) return false;
+  if (head_dim != 16 && head_dim != 32 && head_dim != 48 && head_dim != 64) return false;
+  return prec == PREC_BF16 || prec == PREC_F16 || prec == PREC_F32;
+}
+
 hipError_t launch_attention(const AttnArgs& a, int head_dim, int prec, hipStream_t s) {
   const int al = prec == PREC_F32 ? 3 : 7;       // rows must start 16-B aligned
   if (!a.q || !a.k || !a.v || !a.out) return hipErrorInvalidValue;
+  if ((a.q_lens || a.k_lens) && !attention_masks_rows(a, head_dim, prec)) return hipErrorInvalidValue;     // refused, never run unmasked
   if (a.Lq <= 0 || a.Lk <= 0 || (a.ldq & al) || (a.ldk & al) || (a.ldv & al) || (a.ldo & al)) return hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(a.out) & 15) return hipErrorInvalidValue;      // (results leave in 16-byte pieces)
   switch (prec) {

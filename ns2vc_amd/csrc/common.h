@@ -291,6 +291,7 @@ bool gemm_masks_rows(const GemmArgs& g, int prec);                        // ...
 bool gemm_uses_convts(const GemmArgs& g, int prec);                        // would launch_gemm run this launch on the tap-sharing conv kernel (convts.hip)?
 int last_gemm_refusal_line();                                               // gemm.hip line of the argument check that refused the last launch on this thread (0: none), cleared by the call
 hipError_t launch_attention(const AttnArgs& a, int head_dim, int prec, hipStream_t s);
+bool attention_masks_rows(const AttnArgs& a, int head_dim, int prec);      // ... on a masked instantiation (AttnArgs.q_lens / k_lens), were they set?
 hipError_t init_gemm_attributes();
 // tap-sharing k = 3 conv kernel (convts.hip)
 bool convts_eligible(const GemmArgs& g, int prec);

@@ -228,6 +228,11 @@ struct ns2vc_unet {
   // has no masked form yet keeps today's unfused launches: the transformer's token-local kernels (row chains, fused feed-forward / GEGLU,
   // LayerNorm by linearity), the attention's result rows, GEMMs on the 4-wave kernel, the nearest upsampling.  Dense plans ignore it.
   bool masked_fuse = false;
+  // Option masked_attn (off): under per-item lengths the attention launches get the level's length table (AttnArgs.q_lens, and k_lens for the
+  // self-attention) instead of the key-bias row and the mask_rows launch behind them: the keys, key tiles and query tiles past an item's end are
+  // skipped, not computed and thrown away.  Asked per launch (attention_masks_rows): the fp8 PV form keeps the bias row and its sweeper.
+  // Independent of masked_fuse; dense plans ignore it.
+  bool masked_attn = false;
   // Per-item valid lengths (ns2vc_unet_set_lengths).  `masked`: the plan was built for them -- GroupNorm statistics by their own pass over
   // rows whose padding is zero (no epilogue sums, so no fused GroupNorm prologue, row chain or LayerNorm by linearity), every activation's
   // rows past an item's end zeroed after the launch that writes them, the self-attention keys there masked by an additive bias row, the

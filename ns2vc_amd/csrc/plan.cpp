@@ -277,8 +277,10 @@ struct Planner {
     gemm(r.prefix + ".conv2", g2);
   }
 
+  // `self`: Lk is a frame count like Lq (attn1); its keys past an item's end are masked by the level's key-bias row, or -- option masked_attn --
+  // left out by the kernel itself (AttnArgs.k_lens), which then also stores the result rows past the end as zeros (q_lens): no mask_rows launch
   void attention(const std::string& name, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int Lq, int Lk,
-                 const float* bias, int hd, void* out, int ldo) {
+                 const float* bias, int hd, void* out, int ldo, bool self = false) {
     AttnArgs a;
     memset(&a, 0, sizeof(a));
     a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
@@ -289,9 +291,14 @@ struct Planner {
     a.exact_only = h->attn_optimistic ? 0 : 1;
     a.fallbacks = h->attn_fallbacks;
     const int pr = prec;
+    const bool self_mask = masked && h->masked_attn && ops == &h->fwd_ops && level_of(Lq) >= 0 && attention_masks_rows(a, hd, pr);
+    if (self_mask) {
+      a.q_lens = lens_of(Lq);
+      if (self) a.k_lens = lens_of(Lk);
+    } else if (self) a.bias = selfbias_of(Lk);
     add(name, [=](hipStream_t s) { return launch_attention(a, hd, pr, s); }, 2, 4.0 * B * a.H * (double)Lq * Lk * hd,
         (double)opsz * B * a.H * hd * (2.0 * Lq + 2.0 * Lk));
-    mask(name, out, ldo, a.H * hd, opsz, Lq);
+    if (!self_mask) mask(name, out, ldo, a.H * hd, opsz, Lq);
   }
 
   // r6: does this block run its prompt cross-attention inside the fused feed-forward kernel?  (the plan of the pre-stage form, 8 heads of 16 / 32 channels)
@@ -355,7 +362,7 @@ struct Planner {
       consume(g, r1, a.qkv);
       gemm(t + ".attn1.qkv", g);
     }
-    attention(t + ".attn1.sdpa", qkv, 3 * d, op_off(qkv, d), 3 * d, op_off(qkv, 2 * d), 3 * d, Tl, Tl, selfbias_of(Tl), hd, ao, d);
+    attention(t + ".attn1.sdpa", qkv, 3 * d, op_off(qkv, d), 3 * d, op_off(qkv, 2 * d), 3 * d, Tl, Tl, nullptr, hd, ao, d, true);
     float* r2 = lin ? rs2 : nullptr;
     if (rows_ok) {
       rowchain(t + ".rows[attn1.to_out+attn2.to_q]", ao, nullptr, a.chain_mid, a.o1.bias, a.chain_mid_consts, y, qb, d);

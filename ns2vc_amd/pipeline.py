@@ -86,11 +86,15 @@ class Denoiser:
 
     def __init__(self, state: Dict[str, object], cfg: UNetConfig = UNetConfig(), precision: str = DEFAULT_PRECISION,
                  betas: Optional[np.ndarray] = None, ln_guard: Optional[float] = -1.0, tail_fp32: Optional[int] = None,
-                 precision_check: Optional[float] = -1.0, attn_fallback_limit: Optional[float] = 0.10, masked_fuse: bool = False):
+                 precision_check: Optional[float] = -1.0, attn_fallback_limit: Optional[float] = 0.10, masked_fuse: bool = False,
+                 masked_attn: bool = False):
         self.cfg = cfg
         # engine option ``masked_fuse``: under ``lengths=`` the plan keeps its fused launches where the kernels mask their own rows; passed to
         # the fp32 engine of the tail / self-check as well
         self.masked_fuse = bool(masked_fuse)
+        # engine option ``masked_attn``: under ``lengths=`` the attention launches skip the keys and query tiles past an item's end themselves
+        # (no key-bias row, no sweeper launch behind them); independent of ``masked_fuse``, passed on the same way
+        self.masked_attn = bool(masked_attn)
         self.attn_fallback_limit = attn_fallback_limit if precision not in ("fp32", "f32") else None
         self.attn_fallback_rate_seen: Optional[float] = None
         self._attn_checked = False
@@ -99,6 +103,8 @@ class Denoiser:
         self.engine.load_state_dict(state)
         if self.masked_fuse:
             self.engine.set_option("masked_fuse", True)
+        if self.masked_attn:
+            self.engine.set_option("masked_attn", True)
         self._state = state
         self.betas = linear_betas() if betas is None else np.asarray(betas, dtype=np.float32)
         # ddim / ddpm index the model's own float32 buffers, which the reference derives from the float64 betas
@@ -180,8 +186,8 @@ class Denoiser:
         """A plan option of the engine (``Engine.set_option``; e.g. ``gn_coop`` off for a pipeline that runs the denoiser on a CU partition).
         The plan and the sampler table are rebuilt by the next ``sample``."""
         self.engine.set_option(name, value)
-        if name == "masked_fuse":
-            self.masked_fuse = bool(value)
+        if name in ("masked_fuse", "masked_attn"):
+            setattr(self, name, bool(value))
             if self.tail_engine is not None:
                 self.tail_engine.set_option(name, value)
                 self._tail_shape = None
@@ -207,6 +213,8 @@ class Denoiser:
                 self.tail_engine.set_option("ln_linear", False)
             if self.masked_fuse:
                 self.tail_engine.set_option("masked_fuse", True)
+            if self.masked_attn:
+                self.tail_engine.set_option("masked_attn", True)
             self._tail_shape = None
             self._tail_table_key = None
         if self._tail_shape != self._shape:

@@ -3,6 +3,7 @@
   (b) ragged    -- one B = 32 batch padded to 938 with per-item lengths (ns2vc_unet_set_lengths);
   (c) per-shape -- equal-shape grouping without padding, which for 32 distinct lengths is 32 batch-1 loops.
 --masked-fuse adds (b') -- leg (b) with the engine option masked_fuse on -- in the same process, `--alternate` times in turn with (a) and (b), the order rotating;
+--masked-attn (with --masked-fuse) adds (b'') -- leg (b') with the engine option masked_attn on as well -- to that rotation;
 --skip-per-shape leaves (c) out.
 Each figure is the median of `--reps` timed sampling loops (hipGraph replays, condition set outside the timing) after a warm-up loop.
 Usage: python tools/ragged_bench.py [--reps 5] [--out FILE]"""
@@ -25,6 +26,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--masked-fuse", action="store_true", help="also run leg (b) with the option masked_fuse on")
+    ap.add_argument("--masked-attn", action="store_true", help="with --masked-fuse: also run leg (b') with the option masked_attn on")
     ap.add_argument("--alternate", type=int, default=3, help="repetitions of (a), (b), (b') in turn (with --masked-fuse)")
     ap.add_argument("--skip-per-shape", action="store_true")
     a = ap.parse_args()
@@ -36,13 +38,16 @@ def main():
     xT = torch.from_numpy(hash_normal("rb.x", (B, 100, T))).to(dev)
     e = Engine(precision="fp16")
     e.load_state_dict(procedural_state_dict(seed=0))
-    fused_now = False                            # the engine's masked_fuse option as last set
+    fused_now = attn_now = False                 # the engine's masked_fuse / masked_attn options as last set
 
-    def loop_ms(bsz, tl, lengths=None, sl=slice(None), fuse=False):
-        nonlocal fused_now
+    def loop_ms(bsz, tl, lengths=None, sl=slice(None), fuse=False, attn=False):
+        nonlocal fused_now, attn_now
         if fused_now != fuse:
             e.set_option("masked_fuse", fuse)        # (drops the plan: prepared again below)
             fused_now = fuse
+        if attn_now != attn:
+            e.set_option("masked_attn", attn)
+            attn_now = attn
         if e.shape != (bsz, tl, Lp):
             e.prepare(bsz, tl, Lp)
             e.load_sampler("unipc", a.steps)
@@ -68,8 +73,12 @@ def main():
     if a.masked_fuse:
         legs = {"a": lambda: loop_ms(B, T), "b": lambda: loop_ms(B, T, lens), "b_fused": lambda: loop_ms(B, T, lens, fuse=True)}
         order = ["a", "b", "b_fused"]
+        if a.masked_attn:
+            legs["b_fused_attn"] = lambda: loop_ms(B, T, lens, fuse=True, attn=True)
+            order.append("b_fused_attn")
         for i in range(a.alternate):             # the order rotates, so that a drift of the clocks does not favour one leg
-            rot = order[i % 3:] + order[:i % 3]
+            k0 = i % len(order)
+            rot = order[k0:] + order[:k0]
             rep = {k: round(legs[k](), 3) for k in rot}
             rep["order"] = rot
             alt.append(rep)
@@ -81,10 +90,13 @@ def main():
          "b_over_a": round(ragged / dense, 3), "c_over_b": round(per / ragged, 2),
          "ms_per_step": {"a": round(dense / a.steps, 3), "b": round(ragged / a.steps, 3), "c": round(per / a.steps, 3)}}
     if alt:
-        med = {k: float(np.median([x[k] for x in alt])) for k in ("a", "b", "b_fused")}
+        med = {k: float(np.median([x[k] for x in alt])) for k in alt[0] if k != "order"}
         r["alternating_ms"] = alt
         r["fused"] = {"b_fused_ms": round(med["b_fused"], 3), "b_fused_over_a": round(med["b_fused"] / med["a"], 3), "b_fused_over_b": round(med["b_fused"] / med["b"], 3),
                       "ms_per_step": {k: round(v / a.steps, 3) for k, v in med.items()}}
+        if "b_fused_attn" in med:
+            r["fused"].update({"b_fused_attn_ms": round(med["b_fused_attn"], 3), "b_fused_attn_over_a": round(med["b_fused_attn"] / med["a"], 3),
+                               "b_fused_attn_over_b_fused": round(med["b_fused_attn"] / med["b_fused"], 3)})
     line = json.dumps(r)
     print(line)
     if a.out:
