@@ -73,6 +73,7 @@ int ns2vc_abi_version(void);
  * mirrors it compares sizes before it passes one */
 int ns2vc_sizeof_gemm_args(void);
 int ns2vc_sizeof_attn_args(void);                /* the same for the attention arguments, whose last fields are `q_lens, k_lens` */
+int ns2vc_sizeof_rowchain_args(void);            /* ... and for the row-chain arguments, whose last field is `lens` */
 const char* ns2vc_last_error(void);
 int ns2vc_device_count(int* out_count);
 int ns2vc_set_device(int device);               /* one process per GPU: call with LOCAL_RANK */
@@ -109,6 +110,10 @@ int ns2vc_unet_num_missing_weights(ns2vc_unet* h, char* first_missing, int bufle
  *   "masked_attn" 1|0  (default 0) a plan built under per-item lengths gives the attention launches the level's length table (ns2vc_attn_args.q_lens /
  *                    k_lens) instead of the self-attention key-bias row and the mask_rows launch behind each of them; independent of masked_fuse;
  *                    dense plans ignore it
+ *   "masked_rows" 1|0  (default 0) a plan built under per-item lengths keeps the two row-chain launches of a transformer block (ns2vc_k_rowchain)
+ *                    and gives them the level's length table (ns2vc_rowchain_args.lens) instead of the GroupNorm apply, proj_in, norm1, attn1.qkv,
+ *                    attn1.to_out, norm2, attn2.to_q launches and their mask_rows sweeps; independent of masked_fuse and masked_attn; dense plans
+ *                    ignore it
  * The environment variables NS2VC_LN_LINEAR / NS2VC_FOLD_FF / NS2VC_FUSE_FFN set the defaults at ns2vc_unet_create.
  *   "temb_join_skip" n  (tests, not a plan option) record the fork_temb join at the (n+1)-th reader of the time scale /
  *                    shift rows instead of the first; the plan build then refuses the fork (ns2vc_unet_op_info which = 2) */
@@ -450,6 +455,18 @@ typedef struct ns2vc_rowchain_args {
   /* r4: N-sliced stage 2 (dim 384): `slices` = 2 -> two workgroups per token block, each repeats stage 1 and computes one slice of the stage-2
    * rows (5 + 4 of the 9 row blocks of q|k|v, 2 + 1 of the 3 of to_q); wstream / consts2 from ns2vc_pack_rowchain_sliced.  0 / 1 = one workgroup. */
   int32_t slices;
+  /* Per-item frame counts (backward-compatible addition to ABI v7: the LAST field of the struct, NULL = everything above as it was).
+   *   lens = DEVICE [M / T], one count per batch item; `T` = rows per item is then required with or without the GroupNorm prologue (T >= 1 and
+   *          M % T == 0; T >= 64 with the prologue, as before).  Row m is frame t = m - b T of item b = m / T and takes part iff t < lens[b]; a
+   *          count is clamped to 0 .. T before it is used.
+   * A row at or past its item's end: out1_f32 and out2_op are stored as exact zeros (no bias, no residual, no LayerNorm fix-up), whatever a_op / gn_x
+   * hold there; its `res` row is not read; it takes no part in ln_health.  Every other row is bit-identical to the launch on its item alone at
+   * M = lens[b]; with the GroupNorm prologue gn_stats hold the sums over the item's valid rows only (as ns2vc_gemm_args.lens leaves them) and the
+   * divisor is lens[b] * dim / G.  Served by the masked instantiations of the kernel: both operand types, every dim and n2, 128-token blocks and
+   * two slices included.  A call that sets `lens` with T < 1, M % T != 0 or a prologue at T < 64 is refused (hipErrorInvalidValue), never run unmasked.
+   * The struct is 8 bytes longer than in earlier builds of ABI v7 and ns2vc_k_rowchain reads all of it: a binding compiled against the earlier
+   * header MUST be rebuilt; ns2vc_sizeof_rowchain_args() is there to check. */
+  const int32_t* lens;
 } ns2vc_rowchain_args;
 /* w1 [dim][dim], w2 [n2][dim]: fp32 host, row-major.  Returns the device tile stream the kernel consumes. */
 int ns2vc_pack_rowchain(const float* w1_host, const float* w2_host, int dim, int n2, int precision, void** out_stream_dev);

@@ -104,6 +104,7 @@ class RowchainArgs(C.Structure):
         ("gn_stats", C.c_void_p), ("gn_gamma", C.c_void_p), ("gn_beta", C.c_void_p),
         ("gn_eps", C.c_float), ("T", C.c_int32), ("G", C.c_int32),
         ("slices", C.c_int32),
+        ("lens", C.c_void_p),
     ]
 
 
@@ -127,6 +128,7 @@ PROTOTYPES = {
     "ns2vc_abi_version": (_I, []),
     "ns2vc_sizeof_gemm_args": (_I, []),
     "ns2vc_sizeof_attn_args": (_I, []),
+    "ns2vc_sizeof_rowchain_args": (_I, []),
     "ns2vc_last_error": (C.c_char_p, []),
     "ns2vc_device_count": (_I, [C.POINTER(_I)]),
     "ns2vc_set_device": (_I, [_I]),
@@ -247,6 +249,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         raise Ns2vcError(f"ns2vc_gemm_args: library has {lib.ns2vc_sizeof_gemm_args()} bytes, binding {C.sizeof(GemmArgs)}")
     if lib.ns2vc_sizeof_attn_args() != C.sizeof(AttnArgs):
         raise Ns2vcError(f"ns2vc_attn_args: library has {lib.ns2vc_sizeof_attn_args()} bytes, binding {C.sizeof(AttnArgs)}")
+    if lib.ns2vc_sizeof_rowchain_args() != C.sizeof(RowchainArgs):
+        raise Ns2vcError(f"ns2vc_rowchain_args: library has {lib.ns2vc_sizeof_rowchain_args()} bytes, binding {C.sizeof(RowchainArgs)}")
     if path is None:
         _lib = lib
     return lib

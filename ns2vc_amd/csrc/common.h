@@ -340,6 +340,7 @@ hipError_t launch_time_embed(const float* t_ptr, int t_stride, const int* step_p
                              const float* aug, float* emb, void* emb_act_op, int prec, int B, int tdim, int edim, hipStream_t s);
 hipError_t launch_rowchain(const ::ns2vc_rowchain_args& a, int prec, hipStream_t s);            // rowchain.hip
 bool rowchain_eligible(int dim, int n2, int T, int prec);
+bool rowchain_masks_rows(const ::ns2vc_rowchain_args& a, int prec);                            // ... on a masked instantiation (ns2vc_rowchain_args.lens), were it set?
 hipError_t init_rowchain_attributes();
 hipError_t pack_rowchain_stream(const float* w1, const float* w2, int dim, int n2, int prec, std::vector<unsigned short>& out, int slices = 1);
 int rowchain_slice_blocks(int n2, int slices);

@@ -233,6 +233,13 @@ struct ns2vc_unet {
   // skipped, not computed and thrown away.  Asked per launch (attention_masks_rows): the fp8 PV form keeps the bias row and its sweeper.
   // Independent of masked_fuse; dense plans ignore it.
   bool masked_attn = false;
+  // Option masked_rows (off): under per-item lengths a transformer block keeps its two row-chain launches (rowchain.hip), which get the level's
+  // length table (ns2vc_rowchain_args.lens): a lane of that kernel owns one token, so the rows past an item's end are zero rows by a per-lane
+  // predicate and the LayerNorm statistics that forbid LayerNorm by linearity under lengths never leave the kernel.  Replaces the GroupNorm apply
+  // (with masked_fuse, where the producer's statistics survive), proj_in, norm1, attn1.qkv, attn1.to_out, norm2, attn2.to_q and their mask_rows
+  // launches; norm3 and everything behind it stay as they are.  Asked per launch (rowchain_masks_rows).  Independent of masked_fuse and
+  // masked_attn; dense plans ignore it.
+  bool masked_rows = false;
   // Per-item valid lengths (ns2vc_unet_set_lengths).  `masked`: the plan was built for them -- GroupNorm statistics by their own pass over
   // rows whose padding is zero (no epilogue sums, so no fused GroupNorm prologue, row chain or LayerNorm by linearity), every activation's
   // rows past an item's end zeroed after the launch that writes them, the self-attention keys there masked by an additive bias row, the

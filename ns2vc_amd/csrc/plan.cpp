@@ -322,7 +322,11 @@ struct Planner {
     // `yn` and per-row statistics; the consumer GEMM reads yn and normalises in its epilogue -- no ln_apply pass
     // (masked: the row statistics of LayerNorm by linearity come from epilogues that see the padded rows before they are zeroed, and its health
     //  guard would count them: the explicit normalisation pass over the zeroed rows instead -- LayerNorm of a zero row is zero)
-    const bool lin = h->ln_linear && (d % 128 == 0) && d <= 512 && !masked;
+    const bool lin_dense = h->ln_linear && (d % 128 == 0) && d <= 512;
+    const bool lin = lin_dense && !masked;
+    // option masked_rows: the row chains keep their LayerNorm sums inside the kernel (neither rs1 nor rs2 exists for them) and a lane owns one token,
+    // so under lengths they run on their masked instantiations with the level's length table -- everything else of `lin` stays off
+    const bool lens_rows = masked && h->masked_rows && ops == &h->fwd_ops && level_of(Tl) >= 0;
     auto consume = [&](GemmArgs& gg, float* rs, const PackedW& w) {
       if (rs) { gg.ln_stats = rs; gg.ln_wsum = w.wsum; gg.ln_eps = 1e-5f; gg.ln_dim = d; gg.ln_health = h->ln_health; }
     };
@@ -341,10 +345,24 @@ struct Planner {
       // r4: two N-slices per token block where that still is one round of workgroups (dim 384 at the bench batch: 118 blocks on 256 CUs);
       // only for the chain without a residual (the second chain reads and rewrites y in place: two slices would race on it)
       if (!res && stream == a.chain_in && a.chain_in_s2 && h->slice_rows && 2 * ((M + 63) / 64) <= h->cus + 8) { c.wstream = a.chain_in_s2; c.slices = 2; }   // (one round of workgroups on this device's CUs)
+      if (lens_rows) { c.lens = lens_of(Tl); c.T = Tl; }            // (the kernel zeroes the rows past an item's end itself: no mask() behind it)
       add(c.slices == 2 ? nm + "[2 slices]" : nm, [=](hipStream_t s) { return launch_rowchain(c, pr, s); }, 1, 2.0 * M * (double)d * (d + n2),
           (double)M * (d * ((gn_st ? 4.0 : opsz) + 4.0 + (res ? 4.0 : 0.0)) + n2 * opsz) + (double)(d + n2) * d * opsz);
     };
-    const bool rows_ok = lin && h->fuse_rows && a.chain_in && a.chain_mid && rowchain_eligible(d, d, Tl, pr);
+    // (masked: asked per launch, rowchain_masks_rows, for the shapes of both chains with and without the GroupNorm prologue)
+    auto chains_mask_rows = [&]() {
+      ns2vc_rowchain_args c;
+      memset(&c, 0, sizeof(c));
+      c.M = M; c.dim = d; c.T = Tl;
+      c.n2 = 3 * d;
+      const bool in_ok = rowchain_masks_rows(c, pr);
+      c.n2 = d;
+      return in_ok && rowchain_masks_rows(c, pr);
+    };
+    const bool rows_ok = (masked ? lin_dense && lens_rows && chains_mask_rows() : lin) && h->fuse_rows && a.chain_in && a.chain_mid &&
+                         rowchain_eligible(d, d, Tl, pr);
+    // (masked: the producer's statistics survive under lengths only where its masked epilogue left the padded rows out -- masked_fuse; new_stats /
+    //  Planner::gemm drop the slab everywhere else, and the chain then reads xn from the masked gn_apply)
     const long long* xst = (rows_ok && h->fuse_rows_gn && Tl >= 64 && (d % G) == 0 && ((d / G) % 16) == 0) ? find_stats(x) : nullptr;
     GnPro pn;
     if (!xst) pn = groupnorm(a.prefix + ".norm", x, d, d, nullptr, 0, 0, Tl, 1e-6f, a.ng, a.nb, nullptr, 0, 0, 0, xn, nullptr, rows_ok ? 0 : a.proj_in.N);

@@ -65,7 +65,9 @@ template <int D, int R2, int NT> struct RowchainGeom {
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
-template <typename TM, int D, int R2, int NT>
+// MASKED: per-item frame counts (RowchainArgs.lens; option masked_rows).  Its own instantiations: the dense ones keep their instructions.  A lane owns
+// one token, so the mask is a per-lane predicate of the prologue and the two epilogues; the K loops and their counted waits do not know about it.
+template <typename TM, int D, int R2, int NT, bool MASKED = false>
 __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
   op_mode_init<TM>();
   using G = RowchainGeom<D, R2, NT>;
@@ -75,6 +77,11 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
   char* const panel = smem + RING * RC_PAIR;
   const float* const consts = reinterpret_cast<const float*>(panel + G::PANEL);
   float2* const stats = reinterpret_cast<float2*>(panel + G::PANEL + G::CONSTS);
+  // MASKED: one word per token of the block behind everything else (the masked launch asks for TOK * 4 bytes more): 1 = the token lies inside M and
+  // in front of its item's end.  Written once in the prologue and read by the stage-2 store loop, so that no register carries the predicate
+  // across the stage-2 K loop (the 128-token form at n2 = 3 dim sits at 256 VGPRs already, and a spill beside the counted waits is not an option);
+  // up to the stage-1 epilogue the lane keeps it in `live`.
+  int* const liveflag = reinterpret_cast<int*>(smem + G::LDS);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -93,6 +100,19 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
   const int m0 = blk * TOK;
   if (m0 >= a.M) return;                            // (padding of the sliced grid to whole groups of 8; uniform over the workgroup)
   const int tok0 = 32 * NT * tw + l31;              // this lane's tokens inside the block: tok0 + 32 u (both lane halves)
+  // MASKED: token row m is frame t = m - b T of item b = m / T and takes part iff t < lens[b].  The counts are fetched here, in front of every DMA
+  // piece: whatever the compiler waits for where they are first used (the residual rows below) is older than the weight pairs or at worst makes a
+  // counted wait of step_begin longer, never shorter.  A count is clamped to 0 .. T before it is used, and it only ever selects zeros.
+  int tlen[NT], tfr[NT];
+  if constexpr (MASKED) {
+    const int nitem = a.M / a.T;
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+      const int m = min(m0 + tok0 + 32 * u, a.M - 1), b = min(m / a.T, nitem - 1);
+      tfr[u] = m - b * a.T;
+      tlen[u] = a.lens[b];
+    }
+  }
 
   const i32x4_t rW = make_rsrc(reinterpret_cast<const char*>(a.wstream) + (size_t)sl * NP * RC_PAIR, (unsigned long long)NP * RC_PAIR);
   const unsigned lane16 = (unsigned)(lane * 16);
@@ -141,6 +161,14 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
   // residual rows of this lane's tokens: independent of everything else, so their latency hides under the first tiles
   // (res may alias out1 element for element: the same lane reads here and writes in the stage-1 epilogue)
   float4 rr[NT][NB1][4];
+  bool live[NT];                                    // MASKED: this lane's token u lies inside M and in front of its item's end
+  if constexpr (MASKED) {
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+      live[u] = m0 + tok0 + 32 * u < a.M && tfr[u] < min(max(tlen[u], 0), a.T);
+      liveflag[tok0 + 32 * u] = live[u] ? 1 : 0;   // (all eight lanes that own the token write the same word; read in the stage-2 epilogue, many barriers later)
+    }
+  }
 #pragma unroll
   for (int u = 0; u < NT; ++u)
 #pragma unroll
@@ -148,7 +176,7 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int m = m0 + tok0 + 32 * u;
-        rr[u][rb][g] = (a.res && m < a.M) ? *reinterpret_cast<const float4*>(a.res + (size_t)m * a.ldres + 128 * rb + 32 * cg + 8 * g + 4 * hi)
+        rr[u][rb][g] = (a.res && (MASKED ? live[u] : m < a.M)) ? *reinterpret_cast<const float4*>(a.res + (size_t)m * a.ldres + 128 * rb + 32 * cg + 8 * g + 4 * hi)
                                           : make_float4(0.f, 0.f, 0.f, 0.f);
       }
 
@@ -174,8 +202,16 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
       const long long* st = a.gn_stats + ((size_t)(b_lo + bi) * nblk + (size_t)g * nb) * 2;
       double ds = 0.0, dq = 0.0;
       for (int j = 0; j < nb; ++j) { ds += (double)st[2 * j] * (1.0 / GN_SUM_SCALE); dq += (double)st[2 * j + 1] * (1.0 / GN_SQ_SCALE); }
-      const float inv_nf = 1.0f / ((float)a.T * (float)Cg);
-      const double inv_n = (double)inv_nf * (2.0 - (double)inv_nf * ((double)a.T * (double)Cg));
+      // MASKED: the producer's masked epilogue summed the item's valid rows only, so the divisor is the item's own frame count -- the
+      // statistics are what a launch at T = lens[b] computes.  (The count sits behind the 32 (mean, rstd) pairs for the row predicate below.)
+      int Tb = a.T;
+      if constexpr (MASKED) {
+        const int L = min(max(a.lens[min(b_lo + bi, a.M / a.T - 1)], 0), a.T);
+        if (g == 0) reinterpret_cast<int*>(gtab + 32)[bi] = L;
+        Tb = max(L, 1);
+      }
+      const float inv_nf = 1.0f / ((float)Tb * (float)Cg);
+      const double inv_n = (double)inv_nf * (2.0 - (double)inv_nf * ((double)Tb * (double)Cg));
       const double mean = ds * inv_n;
       double var = dq * inv_n - mean * mean;
       if (var < 0.0) var = 0.0;
@@ -194,6 +230,8 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
 #pragma unroll
       for (int k = 1; k < 4; ++k) bi += (m >= (b_lo + k) * a.T) ? 1 : 0;
       mrs[ps] = gtab[min(bi, 3) * 8 + g];
+      // MASKED: a row at or past its item's end is flagged by a negative rstd (a real one is positive): no register of its own
+      if constexpr (MASKED) if (m - (b_lo + min(bi, 3)) * a.T >= reinterpret_cast<const int*>(gtab + 32)[min(bi, 3)]) mrs[ps].y = -1.f;
     }
     // gfx950 hazard guard (profiles/r04_gn_prologue_rootcause.txt): every (mean, rstd) pair has landed before the first packed
     // fp32 product is formed from them (the compiler's counted lgkmcnt(N) waits in front of v_pk_* with op_sel is the pattern
@@ -209,6 +247,7 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
       float y0 = xv[ps].x * s0 + (be.x - mr.x * s0), y1 = xv[ps].y * s1 + (be.y - mr.x * s1);
       float y2 = xv[ps].z * s2 + (be.z - mr.x * s2), y3 = xv[ps].w * s3 + (be.w - mr.x * s3);
       if (m >= a.M) { y0 = 0.f; y1 = 0.f; y2 = 0.f; y3 = 0.f; }
+      if constexpr (MASKED) if (mr.y < 0.f) { y0 = 0.f; y1 = 0.f; y2 = 0.f; y3 = 0.f; }     // GN(0) != 0: a padded row enters the panel as zeros
       char* dst = panel + (c >> 6) * PTILE + row * 128 + ((((c & 63) >> 3) ^ ((row >> 1) & 7)) * 16) + (c & 4) * 2;
       if (act && row < TOK) *reinterpret_cast<uint2*>(dst) = make_uint2(Op16<TM>::pack(y0, y1), Op16<TM>::pack(y2, y3));
     }
@@ -294,7 +333,7 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
 #pragma unroll
   for (int u = 0; u < NT; ++u) {
     const int tok = tok0 + 32 * u, mtok = m0 + tok;
-    const bool tok_ok = mtok < a.M;
+    const bool tok_ok = MASKED ? live[u] : mtok < a.M;      // (MASKED: a token past its item's end is a zero row: no bias, no residual, no sums)
     float ps = 0.f, pq = 0.f;
 #pragma unroll
     for (int rb = 0; rb < NB1; ++rb) {
@@ -358,7 +397,7 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
       double var = (double)q * (double)inv - (double)mean[u] * (double)mean[u];
       if (var < 0.0) var = 0.0;
       rstd[u] = 1.0f / sqrtf((float)var + a.ln_eps);
-      if (m0 + tok < a.M) ratio = fmaxf(ratio, fabsf(mean[u]) * rstd[u]);
+      if (MASKED ? live[u] : m0 + tok < a.M) ratio = fmaxf(ratio, fabsf(mean[u]) * rstd[u]);
     }
     if (a.ln_health && cg == 0 && sl == 0) {          // same health report as the LayerNorm-consumer GEMMs (gemm.hip ln_row_finish)
 #pragma unroll
@@ -445,7 +484,9 @@ __global__ __launch_bounds__(512) void rowchain_kernel(const RowchainArgs a) {
       const int id = i * 512 + tid;
       const int row = id / CPR, col = id - row * CPR;
       const int mt = m0 + row, n = 128 * (rb0 + sl * R2) + 8 * col;
-      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(smem + (size_t)row * PB + col * 16);
+      u32x4_t v = *reinterpret_cast<const u32x4_t*>(smem + (size_t)row * PB + col * 16);
+      // (MASKED: the fix-up of a zero row gives bias2 -- rstd = 1 / sqrt(eps) there; a token past its item's end is stored as exact zeros)
+      if constexpr (MASKED) if (liveflag[row] == 0) v = u32x4_t{0u, 0u, 0u, 0u};
 #if NS2VC_RC_ABLATE & 1     // diagnostic build (wrong results, timing only): no stage-2 stores
       asm volatile("" :: "v"(v));
 #else
@@ -503,26 +544,35 @@ bool rowchain_eligible(int dim, int n2, int T, int prec) {
   return (dim == 128 || dim == 256 || dim == 384) && (n2 == dim || n2 == 3 * dim) && T >= 1 && (prec == PREC_BF16 || prec == PREC_F16);
 }
 
-template <typename TM, int D, int R2, int NT> static hipError_t launch_rc(const RowchainArgs& a, hipStream_t s) {
-  const size_t lds = RowchainGeom<D, R2, NT>::LDS;
+template <typename TM, int D, int R2, int NT, bool MASKED> static hipError_t launch_rc(const RowchainArgs& a, hipStream_t s) {
   constexpr int TOK = RowchainGeom<D, R2, NT>::TOK;
+  const size_t lds = RowchainGeom<D, R2, NT>::LDS + (MASKED ? TOK * 4 : 0);      // (+ the per-token flags of the masked form)
+  static_assert(RowchainGeom<D, R2, NT>::LDS + TOK * 4 <= 160 * 1024, "LDS budget of the masked form");
   const int nblk = (a.M + TOK - 1) / TOK, S = a.slices > 1 ? a.slices : 1;
-  hipLaunchKernelGGL((rowchain_kernel<TM, D, R2, NT>), dim3(S > 1 ? ((nblk + 7) / 8) * 8 * S : nblk), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((rowchain_kernel<TM, D, R2, NT, MASKED>), dim3(S > 1 ? ((nblk + 7) / 8) * 8 * S : nblk), dim3(512), lds, s, a);
   return hipGetLastError();
 }
 // 64-token workgroups by default.  At dim 128 a workgroup's weights are small and M is large: when 64-token blocks would not
 // fit the chip in one round (one workgroup per CU: the LDS ring), 128-token blocks halve the grid and the weight traffic
 static int g_force_nt = 0;   // test / tuning hook (ns2vc_debug_set_rowchain_tokens): 1 / 2 forces the block size (2 only exists for dim 128)
 void set_forced_rowchain_tokens(int nt) { g_force_nt = nt; }
-template <typename TM> static hipError_t launch_rc_tm(const RowchainArgs& a, hipStream_t s) {
+template <typename TM, bool MK> static hipError_t launch_rc_tm(const RowchainArgs& a, hipStream_t s) {
   if (a.dim == 128) {
     const bool big = g_force_nt ? g_force_nt == 2 : (a.M + 63) / 64 > 256;
-    if (big) return a.n2 == 128 ? launch_rc<TM, 128, 1, 2>(a, s) : launch_rc<TM, 128, 3, 2>(a, s);
-    return a.n2 == 128 ? launch_rc<TM, 128, 1, 1>(a, s) : launch_rc<TM, 128, 3, 1>(a, s);
+    if (big) return a.n2 == 128 ? launch_rc<TM, 128, 1, 2, MK>(a, s) : launch_rc<TM, 128, 3, 2, MK>(a, s);
+    return a.n2 == 128 ? launch_rc<TM, 128, 1, 1, MK>(a, s) : launch_rc<TM, 128, 3, 1, MK>(a, s);
   }
-  if (a.dim == 384 && a.slices == 2) return a.n2 == 384 ? launch_rc<TM, 384, 2, 1>(a, s) : launch_rc<TM, 384, 5, 1>(a, s);
-  if (a.dim == 384) return a.n2 == 384 ? launch_rc<TM, 384, 3, 1>(a, s) : launch_rc<TM, 384, 9, 1>(a, s);
-  return a.n2 == 256 ? launch_rc<TM, 256, 2, 1>(a, s) : launch_rc<TM, 256, 6, 1>(a, s);
+  if (a.dim == 384 && a.slices == 2) return a.n2 == 384 ? launch_rc<TM, 384, 2, 1, MK>(a, s) : launch_rc<TM, 384, 5, 1, MK>(a, s);
+  if (a.dim == 384) return a.n2 == 384 ? launch_rc<TM, 384, 3, 1, MK>(a, s) : launch_rc<TM, 384, 9, 1, MK>(a, s);
+  return a.n2 == 256 ? launch_rc<TM, 256, 2, 1, MK>(a, s) : launch_rc<TM, 256, 6, 1, MK>(a, s);
+}
+
+// Would launch_rowchain run these arguments on a masked instantiation (RowchainArgs.lens), were it set?  Every instantiation launch_rc_tm selects has
+// a masked twin with its twin's resources (tests/test_masked_rows_cpu.py), so the list of refused shapes is empty; what is left are the conditions
+// on T: the frame of a row is derived from it with or without a GroupNorm prologue.
+bool rowchain_masks_rows(const RowchainArgs& a, int prec) {
+  if (!rowchain_eligible(a.dim, a.n2, 64, prec) || a.M <= 0 || a.T < 1 || (a.M % a.T)) return false;
+  return !a.gn_x || a.T >= 64;
 }
 
 hipError_t launch_rowchain(const RowchainArgs& a, int prec, hipStream_t s) {
@@ -535,20 +585,26 @@ hipError_t launch_rowchain(const RowchainArgs& a, int prec, hipStream_t s) {
   } else if (a.lda & 7) return hipErrorInvalidValue;
   if ( (a.res && (a.ldres & 3)) || (a.out1_f32 && (a.ldo1 & 3)) || (a.ldo2 & 7)) return hipErrorInvalidValue;
   if ((unsigned long long)a.M * a.lda * 2ull > 0xFFF00000ull) return hipErrorInvalidValue;
-  return prec == PREC_BF16 ? launch_rc_tm<bf16_t>(a, s) : launch_rc_tm<f16_t>(a, s);
+  if (a.lens) {
+    if (!rowchain_masks_rows(a, prec)) return hipErrorInvalidValue;      // refused, never run unmasked
+    return prec == PREC_BF16 ? launch_rc_tm<bf16_t, true>(a, s) : launch_rc_tm<f16_t, true>(a, s);
+  }
+  return prec == PREC_BF16 ? launch_rc_tm<bf16_t, false>(a, s) : launch_rc_tm<f16_t, false>(a, s);
 }
 
 hipError_t init_rowchain_attributes() {
   hipError_t e;
-#define NS2VC_RC_ATTR(TM, DD_, RR_, NT_)                                                                                            \
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(rowchain_kernel<TM, DD_, RR_, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                               (int)RowchainGeom<DD_, RR_, NT_>::LDS)) != hipSuccess) return e
+#define NS2VC_RC_ATTR1(TM, DD_, RR_, NT_, MK_)                                                                                      \
+  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(rowchain_kernel<TM, DD_, RR_, NT_, MK_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                               (int)RowchainGeom<DD_, RR_, NT_>::LDS + ((MK_) ? RowchainGeom<DD_, RR_, NT_>::TOK * 4 : 0))) != hipSuccess) return e
+#define NS2VC_RC_ATTR(TM, DD_, RR_, NT_) NS2VC_RC_ATTR1(TM, DD_, RR_, NT_, false); NS2VC_RC_ATTR1(TM, DD_, RR_, NT_, true)
   NS2VC_RC_ATTR(bf16_t, 128, 1, 1); NS2VC_RC_ATTR(bf16_t, 128, 3, 1); NS2VC_RC_ATTR(bf16_t, 256, 2, 1); NS2VC_RC_ATTR(bf16_t, 256, 6, 1);
   NS2VC_RC_ATTR(f16_t, 128, 1, 1); NS2VC_RC_ATTR(f16_t, 128, 3, 1); NS2VC_RC_ATTR(f16_t, 256, 2, 1); NS2VC_RC_ATTR(f16_t, 256, 6, 1);
   NS2VC_RC_ATTR(bf16_t, 128, 1, 2); NS2VC_RC_ATTR(bf16_t, 128, 3, 2); NS2VC_RC_ATTR(f16_t, 128, 1, 2); NS2VC_RC_ATTR(f16_t, 128, 3, 2);
   NS2VC_RC_ATTR(bf16_t, 384, 3, 1); NS2VC_RC_ATTR(bf16_t, 384, 9, 1); NS2VC_RC_ATTR(f16_t, 384, 3, 1); NS2VC_RC_ATTR(f16_t, 384, 9, 1);
   NS2VC_RC_ATTR(bf16_t, 384, 2, 1); NS2VC_RC_ATTR(bf16_t, 384, 5, 1); NS2VC_RC_ATTR(f16_t, 384, 2, 1); NS2VC_RC_ATTR(f16_t, 384, 5, 1);
 #undef NS2VC_RC_ATTR
+#undef NS2VC_RC_ATTR1
   return hipSuccess;
 }
 

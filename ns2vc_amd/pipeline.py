@@ -87,7 +87,7 @@ class Denoiser:
     def __init__(self, state: Dict[str, object], cfg: UNetConfig = UNetConfig(), precision: str = DEFAULT_PRECISION,
                  betas: Optional[np.ndarray] = None, ln_guard: Optional[float] = -1.0, tail_fp32: Optional[int] = None,
                  precision_check: Optional[float] = -1.0, attn_fallback_limit: Optional[float] = 0.10, masked_fuse: bool = False,
-                 masked_attn: bool = False):
+                 masked_attn: bool = False, masked_rows: bool = False):
         self.cfg = cfg
         # engine option ``masked_fuse``: under ``lengths=`` the plan keeps its fused launches where the kernels mask their own rows; passed to
         # the fp32 engine of the tail / self-check as well
@@ -95,6 +95,9 @@ class Denoiser:
         # engine option ``masked_attn``: under ``lengths=`` the attention launches skip the keys and query tiles past an item's end themselves
         # (no key-bias row, no sweeper launch behind them); independent of ``masked_fuse``, passed on the same way
         self.masked_attn = bool(masked_attn)
+        # engine option ``masked_rows``: under ``lengths=`` the transformer blocks keep their two row-chain launches, which zero the rows past an
+        # item's end themselves; independent of the two above, passed on the same way (the fp32 engine has no row chains and ignores it)
+        self.masked_rows = bool(masked_rows)
         self.attn_fallback_limit = attn_fallback_limit if precision not in ("fp32", "f32") else None
         self.attn_fallback_rate_seen: Optional[float] = None
         self._attn_checked = False
@@ -105,6 +108,8 @@ class Denoiser:
             self.engine.set_option("masked_fuse", True)
         if self.masked_attn:
             self.engine.set_option("masked_attn", True)
+        if self.masked_rows:
+            self.engine.set_option("masked_rows", True)
         self._state = state
         self.betas = linear_betas() if betas is None else np.asarray(betas, dtype=np.float32)
         # ddim / ddpm index the model's own float32 buffers, which the reference derives from the float64 betas
@@ -186,7 +191,7 @@ class Denoiser:
         """A plan option of the engine (``Engine.set_option``; e.g. ``gn_coop`` off for a pipeline that runs the denoiser on a CU partition).
         The plan and the sampler table are rebuilt by the next ``sample``."""
         self.engine.set_option(name, value)
-        if name in ("masked_fuse", "masked_attn"):
+        if name in ("masked_fuse", "masked_attn", "masked_rows"):
             setattr(self, name, bool(value))
             if self.tail_engine is not None:
                 self.tail_engine.set_option(name, value)
@@ -215,6 +220,8 @@ class Denoiser:
                 self.tail_engine.set_option("masked_fuse", True)
             if self.masked_attn:
                 self.tail_engine.set_option("masked_attn", True)
+            if self.masked_rows:
+                self.tail_engine.set_option("masked_rows", True)
             self._tail_shape = None
             self._tail_table_key = None
         if self._tail_shape != self._shape:
