@@ -74,6 +74,7 @@ int ns2vc_abi_version(void);
 int ns2vc_sizeof_gemm_args(void);
 int ns2vc_sizeof_attn_args(void);                /* the same for the attention arguments, whose last fields are `q_lens, k_lens` */
 int ns2vc_sizeof_rowchain_args(void);            /* ... and for the row-chain arguments, whose last field is `lens` */
+int ns2vc_sizeof_ffn_args(void);                 /* ... and for the fused feed-forward arguments, whose last field is `lens` */
 const char* ns2vc_last_error(void);
 int ns2vc_device_count(int* out_count);
 int ns2vc_set_device(int device);               /* one process per GPU: call with LOCAL_RANK */
@@ -114,6 +115,10 @@ int ns2vc_unet_num_missing_weights(ns2vc_unet* h, char* first_missing, int bufle
  *                    and gives them the level's length table (ns2vc_rowchain_args.lens) instead of the GroupNorm apply, proj_in, norm1, attn1.qkv,
  *                    attn1.to_out, norm2, attn2.to_q launches and their mask_rows sweeps; independent of masked_fuse and masked_attn; dense plans
  *                    ignore it
+ *   "masked_ffn" 1|0  (default 0) a plan built under per-item lengths keeps the pre-stage launch of the fused feed-forward of a dim-128 / 256
+ *                    transformer block (ns2vc_k_ffn with pre_a) and gives it the level's length table (ns2vc_ffn_args.lens) instead of the
+ *                    attn2.to_out, norm3, ff.geglu, ff.out+proj_out launches and their mask_rows sweeps; independent of masked_fuse, masked_attn
+ *                    and masked_rows; dense plans and the fp32 engine ignore it
  * The environment variables NS2VC_LN_LINEAR / NS2VC_FOLD_FF / NS2VC_FUSE_FFN set the defaults at ns2vc_unet_create.
  *   "temb_join_skip" n  (tests, not a plan option) record the fork_temb join at the (n+1)-th reader of the time scale /
  *                    shift rows instead of the first; the plan build then refuses the fork (ns2vc_unet_op_info which = 2) */
@@ -396,6 +401,18 @@ typedef struct ns2vc_ffn_args {
    * att_scale = 1/sqrt(dim/8).  Token blocks are then cut per batch item (ceil(T / 64) workgroups per item). */
   const void* att_q; int32_t att_ldq;
   const void* att_kv; const float* att_bias; float att_scale; int32_t att_Lk;
+  /* Per-item frame counts (backward-compatible addition to ABI v7: the LAST field of the struct, NULL = everything above as it was).
+   *   lens = DEVICE [B], 1 <= lens[b] <= T, one count per batch item.  Row m is frame t = m - b T of item b = m / T and takes part iff t < lens[b];
+   *          a count is clamped to 0 .. T before it is used.
+   * A row at or past its item's end: out_f32 and out_op are stored as exact zeros (no bias2, no residual), whatever yn / pre_a hold there; its
+   * `res`, `pre_res` and `ln_stats` rows are not read; it takes no part in ln_health and adds nothing to `stats`, which hold the sums over every
+   * item's valid rows only.  Every other row is bit-identical to the launch on its item alone at T = M = lens[b].  A 64-row block without a valid
+   * row stores its zeros and returns: no weight is streamed for it.  Served by the masked instantiations of the kernel: both operand types, dim 128
+   * and 256, the plain and the pre-stage form.  A call that sets `lens` together with att_q (the in-kernel cross-attention has no masked form) or
+   * with M != B T is refused (hipErrorInvalidValue), never run unmasked.
+   * The struct is 8 bytes longer than in earlier builds of ABI v7 and ns2vc_k_ffn reads all of it: a binding compiled against the earlier header
+   * MUST be rebuilt; ns2vc_sizeof_ffn_args() is there to check. */
+  const int32_t* lens;
 } ns2vc_ffn_args;
 /* w1_packed [8*dim][dim]: LayerNorm-folded ff.net.0 rows in the packed (32 value | 32 gate) order; w2f [dim][5*dim] =
  * [Wpo W2 | Wpo]; both fp32 host, row-major.  Returns the device tile stream the kernel consumes. */

@@ -77,6 +77,7 @@ class FfnArgs(C.Structure):
         ("pre_res", C.c_void_p), ("pre_ldres", C.c_int32),
         ("att_q", C.c_void_p), ("att_ldq", C.c_int32),
         ("att_kv", C.c_void_p), ("att_bias", C.c_void_p), ("att_scale", C.c_float), ("att_Lk", C.c_int32),
+        ("lens", C.c_void_p),
     ]
 
 
@@ -129,6 +130,7 @@ PROTOTYPES = {
     "ns2vc_sizeof_gemm_args": (_I, []),
     "ns2vc_sizeof_attn_args": (_I, []),
     "ns2vc_sizeof_rowchain_args": (_I, []),
+    "ns2vc_sizeof_ffn_args": (_I, []),
     "ns2vc_last_error": (C.c_char_p, []),
     "ns2vc_device_count": (_I, [C.POINTER(_I)]),
     "ns2vc_set_device": (_I, [_I]),
@@ -251,6 +253,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         raise Ns2vcError(f"ns2vc_attn_args: library has {lib.ns2vc_sizeof_attn_args()} bytes, binding {C.sizeof(AttnArgs)}")
     if lib.ns2vc_sizeof_rowchain_args() != C.sizeof(RowchainArgs):
         raise Ns2vcError(f"ns2vc_rowchain_args: library has {lib.ns2vc_sizeof_rowchain_args()} bytes, binding {C.sizeof(RowchainArgs)}")
+    if lib.ns2vc_sizeof_ffn_args() != C.sizeof(FfnArgs):
+        raise Ns2vcError(f"ns2vc_ffn_args: library has {lib.ns2vc_sizeof_ffn_args()} bytes, binding {C.sizeof(FfnArgs)}")
     if path is None:
         _lib = lib
     return lib

@@ -309,6 +309,7 @@ void set_forced_attn_keys(int keys);            // test hook: 0 = heuristic, 64 
 // fused feed-forward + proj_out (ffn.hip), 16-bit operand types only
 hipError_t launch_ffn(const ::ns2vc_ffn_args& a, int prec, hipStream_t s);
 bool ffn_eligible(int dim, int T, int prec);
+bool ffn_masks_rows(const ::ns2vc_ffn_args& a, int prec);                                      // ... on a masked instantiation (ns2vc_ffn_args.lens), were it set?
 hipError_t init_ffn_attributes();
 hipError_t pack_ffn_stream(const float* w1p, const float* w2f, const float* w0, int dim, int prec, std::vector<unsigned short>& out);
 void set_ffn_trace(unsigned long long* p);

@@ -240,6 +240,13 @@ struct ns2vc_unet {
   // launches; norm3 and everything behind it stay as they are.  Asked per launch (rowchain_masks_rows).  Independent of masked_fuse and
   // masked_attn; dense plans ignore it.
   bool masked_rows = false;
+  // Option masked_ffn (off): under per-item lengths a transformer block of dim 128 / 256 keeps the pre-stage launch of the fused feed-forward
+  // (ffn.hip), which gets the level's length table (ns2vc_ffn_args.lens).  In that form the kernel computes the LayerNorm sums of norm3 itself, so it
+  // needs no LayerNorm-by-linearity producer, and a lane owns one token: a row past an item's end is a zero row by a per-lane predicate, stored as
+  // exact zeros, left out of the GroupNorm statistics of the result.  Replaces attn2.to_out, norm3, ff.geglu, ff.out+proj_out and their mask_rows
+  // launches; the plain form (whose ln_stats would need a masked producer), dim 384 / 512 and levels under 64 frames stay as they are.  Asked per
+  // launch (ffn_masks_rows).  Independent of masked_fuse, masked_attn and masked_rows; dense plans and the fp32 engine ignore it.
+  bool masked_ffn = false;
   // Per-item valid lengths (ns2vc_unet_set_lengths).  `masked`: the plan was built for them -- GroupNorm statistics by their own pass over
   // rows whose padding is zero (no epilogue sums, so no fused GroupNorm prologue, row chain or LayerNorm by linearity), every activation's
   // rows past an item's end zeroed after the launch that writes them, the self-attention keys there masked by an additive bias row, the

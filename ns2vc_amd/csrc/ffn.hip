@@ -100,10 +100,16 @@ template <int D, bool PRE = false> struct FfnGeom {
 
 // ATT (with PRE): the prompt cross-attention of attn2 computed here too (r6, FfnArgs.att_*): the panel the pre-stage multiplies is PRODUCED by the eight
 // waves -- one per head -- instead of being fetched from an attention launch's output.
-template <typename TM, int D, bool PRE, bool ATT = false>
+//
+// MASKED: per-item frame counts (FfnArgs.lens; option masked_ffn).  Its own instantiations: the dense ones keep their instructions.  A lane owns one
+// token and nothing but the GroupNorm statistics of the result crosses tokens, so a token at or past its item's end is treated exactly as a token at or
+// past `mlim` is -- a zero panel row, no residual, no statistics row, no part in ln_health or in `stats` -- and, being inside M, its result rows are
+// stored as exact zeros.  The pair loop and its counted waits do not know about it.
+template <typename TM, int D, bool PRE, bool ATT = false, bool MASKED = false>
 __global__ __launch_bounds__(512) void ffn_kernel(const FfnArgs a) {
   op_mode_init<TM>();
   static_assert(!ATT || PRE, "the in-kernel cross-attention feeds the pre-stage");
+  static_assert(!(ATT && MASKED), "the in-kernel cross-attention has no masked form");
   using G = FfnGeom<D, PRE>;
   constexpr int KT = G::KT, NB = G::NB, NSS = G::NSS, NB128 = G::NB128, NP = G::PAIRS, EP = G::EP, RING = G::RING;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -124,6 +130,38 @@ __global__ __launch_bounds__(512) void ffn_kernel(const FfnArgs a) {
   const int m0 = ATT ? ab * a.T + ((int)blockIdx.x - ab * nbi) * 64 : (int)blockIdx.x * 64;
   const int mlim = ATT ? (ab + 1) * a.T : a.M;      // first row that is not this block's any more
   const int mtok = m0 + 32 * tw + l31;              // this lane's token (both lane halves)
+  // MASKED: token row m is frame t = m - b T of item b = m / T and takes part iff t < lens[b].  T >= 64, so the 64 tokens of a block belong to at
+  // most two items: their two counts are fetched HERE -- two loads with workgroup-uniform addresses, in front of the L2 warm-up and of the first LDS-DMA
+  // -- and consumed here: the block's valid rows are [.., end0) and [start1, end1), three scalars, and the predicates of the three token mappings
+  // the kernel uses (panel DMA row, this lane's MFMA token, this lane's epilogue token) are formed from them before anything is in flight.  No
+  // memory operation of the mask exists past this point, so the counted waits of step_begin see what they see in the dense kernel.  A count is
+  // clamped to 0 .. T before it is used, and it only ever selects zeros.
+  bool live_p = false, live_t = false, live_e = false;      // (MASKED only) panel row m0 + 8 wave + lane / 8; mtok; the epilogue's em
+  if constexpr (MASKED) {
+    const int nitem = a.M / a.T, ib = min(m0 / a.T, nitem - 1);          // (m0 < M: the grid is ceil(M / 64) blocks)
+    const int l0 = a.lens[ib], l1 = a.lens[min(ib + 1, nitem - 1)];
+    const int end0 = ib * a.T + min(max(l0, 0), a.T), start1 = (ib + 1) * a.T;
+    const int end1 = ib + 1 < nitem ? start1 + min(max(l1, 0), a.T) : start1;
+    auto live = [&](int m) __attribute__((always_inline)) { return m < end0 || (m >= start1 && m < end1); };
+    const int em = m0 + (tid >> 3);                  // (= m0 + 32 eth + etok of the final epilogue)
+    live_p = live(m0 + 8 * wave + (lane >> 3));
+    live_t = live(mtok);
+    live_e = live(em);
+    if (!(m0 < end0 || (start1 < m0 + 64 && start1 < end1))) {
+      // every token of the block is absent (padded or past M): its rows inside M are stored as zeros and the workgroup is done -- no warm-up slice,
+      // no DMA, no barrier; nothing is in flight but these stores, and nothing is added to `stats`.  (Uniform over the workgroup: scalars only.)
+      if (em < a.M) {
+        const int equad = tid & 7;
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+          const int n = 32 * nb + 4 * equad;
+          if (a.out_f32) out_f4(a.out_f32 + (size_t)em * a.ldo_f32 + n, 0.f, 0.f, 0.f, 0.f);
+          if (a.out_op) out_op4<TM>(reinterpret_cast<TM*>(a.out_op) + (size_t)em * a.ldo_op + n, 0.f, 0.f, 0.f, 0.f);
+        }
+      }
+      return;
+    }
+  }
   unsigned long long* const tr = (NS2VC_GEMM_TRACE && g_ffn_trace) ? g_ffn_trace + (size_t)blockIdx.x * 8 : nullptr;
   unsigned long long t_ff1 = 0, t_gg = 0, t_ff2 = 0, t_mark = 0;
   (void)t_ff1; (void)t_gg; (void)t_ff2;             // (only read in the trace build)
@@ -287,7 +325,7 @@ __global__ __launch_bounds__(512) void ffn_kernel(const FfnArgs a) {
     const int prow = 8 * wave + (lane >> 3), pchunk = lane & 7;           // one 1-KB piece per wave = 8 rows x 128 B
     const int m = m0 + prow;
     const int ldp = PRE ? a.pre_lda : a.ldy;          // PRE: the panel starts as the attention output rows (pre-stage A operand)
-    const unsigned voff = m < mlim ? (unsigned)m * (unsigned)ldp * 2u + (unsigned)((pchunk ^ ((prow >> 1) & 7)) * 16) : DMA_OOB;
+    const unsigned voff = (MASKED ? live_p : m < mlim) ? (unsigned)m * (unsigned)ldp * 2u + (unsigned)((pchunk ^ ((prow >> 1) & 7)) * 16) : DMA_OOB;
     const i32x4_t rY = make_rsrc(PRE ? a.pre_a : a.yn, (unsigned long long)a.M * ldp * 2ull);
     if constexpr (!ATT) {
 #pragma unroll
@@ -301,7 +339,32 @@ __global__ __launch_bounds__(512) void ffn_kernel(const FfnArgs a) {
   // pre-stage bias / residual rows of this lane's token: issued BEFORE the weight pairs so that the counted waits on the
   // pairs (loads complete in issue order) do not have to sit through them
   float4 b0[NB128][4], rr0[NB128][4];
-  if constexpr (PRE) {
+  if constexpr (PRE && MASKED) {
+    // (one predicate for the whole row: the residual loads of a present token leave back to back, those of an absent one do not exist)
+#pragma unroll
+    for (int rb = 0; rb < NB128; ++rb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        b0[rb][g] = *reinterpret_cast<const float4*>(a.pre_bias + 128 * rb + 32 * hw + 8 * g + 4 * hi);
+        rr0[rb][g] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    if (live_t) {
+#pragma unroll
+      for (int rb = 0; rb < NB128; ++rb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) rr0[rb][g] = *reinterpret_cast<const float4*>(a.pre_res + (size_t)mtok * a.pre_ldres + 128 * rb + 32 * hw + 8 * g + 4 * hi);
+    }
+    // consumed HERE, while no weight pair exists yet: the wait the compiler places for these registers then covers the panel, the constants and the
+    // warm-up slice only (the dense kernel waits for the same between its predicated loads).  Left to the first step's pinning, its `s_waitcnt
+    // vmcnt(0)` landed behind the first barrier, over the prefetched pairs
+#pragma unroll
+    for (int rb = 0; rb < NB128; ++rb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        asm volatile("" : "+v"(b0[rb][g].x), "+v"(b0[rb][g].y), "+v"(b0[rb][g].z), "+v"(b0[rb][g].w));
+        asm volatile("" : "+v"(rr0[rb][g].x), "+v"(rr0[rb][g].y), "+v"(rr0[rb][g].z), "+v"(rr0[rb][g].w));
+      }
+  } else if constexpr (PRE) {
 #pragma unroll
     for (int rb = 0; rb < NB128; ++rb)
 #pragma unroll
@@ -335,7 +398,7 @@ __global__ __launch_bounds__(512) void ffn_kernel(const FfnArgs a) {
     if (var < 0.0) var = 0.0;
     rstd = 1.0f / sqrtf((float)var + a.ln_eps);
     if (a.ln_health && hw == 0) {          // same health report as the LayerNorm-consumer GEMMs (gemm.hip ln_row_finish)
-      float ratio = mtok < mlim ? fabsf(mean) * rstd : 0.f;
+      float ratio = (MASKED ? live_t : mtok < mlim) ? fabsf(mean) * rstd : 0.f;
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) ratio = fmaxf(ratio, __shfl_xor(ratio, o));
       if (lane == 0 && ratio > __uint_as_float(__hip_atomic_load(a.ln_health, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
@@ -345,8 +408,21 @@ __global__ __launch_bounds__(512) void ffn_kernel(const FfnArgs a) {
   if constexpr (!PRE) {
     const float4* sp = reinterpret_cast<const float4*>(a.ln_stats + (size_t)min(mtok, a.M - 1) * (D / 64) * 2);
     float s = 0.f, q = 0.f;
+    if constexpr (MASKED) {
+      // (the statistics row of an absent token is not read: zero sums, mean 0 and a finite rstd for its zero panel row)
+      float4 v[D / 128];
 #pragma unroll
-    for (int i = 0; i < D / 128; ++i) { const float4 v = sp[i]; s += v.x + v.z; q += v.y + v.w; }
+      for (int i = 0; i < D / 128; ++i) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (live_t) {
+#pragma unroll
+        for (int i = 0; i < D / 128; ++i) v[i] = sp[i];
+      }
+#pragma unroll
+      for (int i = 0; i < D / 128; ++i) { s += v[i].x + v[i].z; q += v[i].y + v[i].w; }
+    } else {
+#pragma unroll
+      for (int i = 0; i < D / 128; ++i) { const float4 v = sp[i]; s += v.x + v.z; q += v.y + v.w; }
+    }
     ln_finish(s, q);
   }
 
@@ -427,7 +503,7 @@ __global__ __launch_bounds__(512) void ffn_kernel(const FfnArgs a) {
         v.y = acc0[rb][4 * g + 1] + b0[rb][g].y + rr0[rb][g].y;
         v.z = acc0[rb][4 * g + 2] + b0[rb][g].z + rr0[rb][g].z;
         v.w = acc0[rb][4 * g + 3] + b0[rb][g].w + rr0[rb][g].w;
-        if (mtok >= mlim) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (MASKED ? !live_t : mtok >= mlim) v = make_float4(0.f, 0.f, 0.f, 0.f);
         ps += (v.x + v.y) + (v.z + v.w);
         pq += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
         const int n = 128 * rb + 32 * hw + 8 * g + 4 * hi;
@@ -553,7 +629,7 @@ __global__ __launch_bounds__(512) void ffn_kernel(const FfnArgs a) {
   constexpr int EBLK = 2 * 4 * 32 * EP;                   // floats per staged 32-channel block
   const int L = tid, eth = L >> 8, etok = (L >> 3) & 31, equad = L & 7;
   const int em = m0 + 32 * eth + etok;
-  const bool eok = em < mlim;
+  const bool eok = MASKED ? live_e : em < mlim;
   float4 rr[NB];                                          // residual rows + bias: every load in flight before the first store
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
@@ -590,6 +666,10 @@ __global__ __launch_bounds__(512) void ffn_kernel(const FfnArgs a) {
         if (a.out_f32) out_f4(a.out_f32 + (size_t)em * a.ldo_f32 + n, v.x, v.y, v.z, v.w);
         if (oo) out_op4<TM>(oo + (size_t)em * a.ldo_op + n, v.x, v.y, v.z, v.w);
         ps = (v.x + v.y) + (v.z + v.w); pq = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+      } else if (MASKED && em < a.M) {
+        // a token past its item's end: exact zeros in both outputs, whatever the accumulators hold (no bias2, no residual), nothing for `stats`
+        if (a.out_f32) out_f4(a.out_f32 + (size_t)em * a.ldo_f32 + n, 0.f, 0.f, 0.f, 0.f);
+        if (oo) out_op4<TM>(oo + (size_t)em * a.ldo_op + n, 0.f, 0.f, 0.f, 0.f);
       }
       if (a.stats) P[nb * 512 + L] = make_float2(ps, pq);
     }
@@ -671,7 +751,11 @@ hipError_t pack_ffn_stream(const float* w1p, const float* w2f, const float* w0, 
 bool ffn_eligible(int dim, int T, int prec) { return (dim == 128 || dim == 256) && T >= 64 && (prec == PREC_BF16 || prec == PREC_F16); }
 
 template <typename TM, int D> static hipError_t launch_ffn_t(const FfnArgs& a, hipStream_t s) {
-  if (a.att_q) {
+  if (a.lens) {       // the masked twins (launch_ffn has asked ffn_masks_rows: never with att_q)
+    const size_t lds = a.pre_a ? FfnGeom<D, true>::LDS : FfnGeom<D, false>::LDS;
+    if (a.pre_a) hipLaunchKernelGGL((ffn_kernel<TM, D, true, false, true>), dim3((a.M + 63) / 64), dim3(512), lds, s, a);
+    else hipLaunchKernelGGL((ffn_kernel<TM, D, false, false, true>), dim3((a.M + 63) / 64), dim3(512), lds, s, a);
+  } else if (a.att_q) {
     const size_t lds = FfnGeom<D, true>::LDS;
     hipLaunchKernelGGL((ffn_kernel<TM, D, true, true>), dim3(a.B * ((a.T + 63) / 64)), dim3(512), lds, s, a);
   } else if (a.pre_a) {
@@ -684,8 +768,18 @@ template <typename TM, int D> static hipError_t launch_ffn_t(const FfnArgs& a, h
   return hipGetLastError();
 }
 
+// Would launch_ffn run these arguments on a masked instantiation (FfnArgs.lens), were it set?  Both operand types, dim 128 and 256, the plain and the
+// pre-stage form have a masked twin with their twin's resources (tests/test_masked_ffn_cpu.py); the in-kernel cross-attention has none.  The frame of
+// a row is derived from T: M = B T, and T >= 64 (a 64-token block then touches at most two items), which ffn_eligible asks of every launch.
+bool ffn_masks_rows(const FfnArgs& a, int prec) {
+  return ffn_eligible(a.dim, a.T, prec) && a.B >= 1 && a.M == a.B * a.T && !a.att_q;
+}
+
 hipError_t launch_ffn(const FfnArgs& a, int prec, hipStream_t s) {
   if (!ffn_eligible(a.dim, a.T, prec) || a.M <= 0 || a.M != a.B * a.T) return hipErrorInvalidValue;
+  if (a.lens) {
+    if (!ffn_masks_rows(a, prec)) return hipErrorInvalidValue;          // refused, never run unmasked
+  }
   if (!a.wstream || !a.consts || !a.bias2 || !a.res || (!a.out_f32 && !a.out_op)) return hipErrorInvalidValue;
   if (a.att_q) {      // in-kernel cross-attention: with the pre-stage's weights, bias and residual; 8 heads of dim / 8 channels, 16-byte aligned fragments
     if (!a.pre_bias || !a.pre_res || (a.pre_ldres & 3) || !a.att_kv || a.att_Lk < 1 || (a.att_ldq & 7) ||
@@ -752,6 +846,12 @@ hipError_t init_ffn_attributes() {
   NS2VC_FFN_ATTR(bf16_t, 128, false); NS2VC_FFN_ATTR(bf16_t, 256, false); NS2VC_FFN_ATTR(f16_t, 128, false); NS2VC_FFN_ATTR(f16_t, 256, false);
   NS2VC_FFN_ATTR(bf16_t, 128, true); NS2VC_FFN_ATTR(bf16_t, 256, true); NS2VC_FFN_ATTR(f16_t, 128, true); NS2VC_FFN_ATTR(f16_t, 256, true);
 #undef NS2VC_FFN_ATTR
+#define NS2VC_FFN_ATTRM(TM, D_, PRE_)                                                                                                       \
+  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ffn_kernel<TM, D_, PRE_, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                               (int)FfnGeom<D_, PRE_>::LDS)) != hipSuccess) return e
+  NS2VC_FFN_ATTRM(bf16_t, 128, false); NS2VC_FFN_ATTRM(bf16_t, 256, false); NS2VC_FFN_ATTRM(f16_t, 128, false); NS2VC_FFN_ATTRM(f16_t, 256, false);
+  NS2VC_FFN_ATTRM(bf16_t, 128, true); NS2VC_FFN_ATTRM(bf16_t, 256, true); NS2VC_FFN_ATTRM(f16_t, 128, true); NS2VC_FFN_ATTRM(f16_t, 256, true);
+#undef NS2VC_FFN_ATTRM
 #define NS2VC_FFN_ATTR2(TM, D_)                                                                                                      \
   if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ffn_kernel<TM, D_, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                (int)FfnGeom<D_, true>::LDS)) != hipSuccess) return e

@@ -406,7 +406,19 @@ struct Planner {
     // normalised rows, so there the raw copy goes to qb (the cross-attention query buffer, free by now).
     const bool fold = h->fold_ff;
     void* yraw = r3 ? yn : (fold ? qb : nullptr);
-    const bool ffn_ok = fold && r3 && h->fuse_ffn && a.ffn_stream && ffn_eligible(d, Tl, pr);
+    // option masked_ffn: in its pre-stage form the fused feed-forward computes the LayerNorm sums of norm3 itself (no r3) and a lane owns one token, so
+    // under lengths it runs on its masked instantiations with the level's length table; the plain form, which reads r3, is not planned under lengths
+    auto ffn_masks = [&]() {
+      ns2vc_ffn_args f;
+      memset(&f, 0, sizeof(f));
+      f.B = B; f.T = Tl; f.M = M; f.dim = d;
+      return ffn_masks_rows(f, pr);
+    };
+    // (every condition of the kept launch in one place, as lens_rows / rows_ok above: the option, the forward plan, a level with a length row, the
+    //  dense conditions of the pre-stage form and a masked kernel for the launch)
+    const bool lens_ffn = masked && h->masked_ffn && ops == &h->fwd_ops && level_of(Tl) >= 0 && lin_dense && fold && h->fuse_ffn && a.ffn_stream &&
+                          h->fuse_ffn_pre && a.ffn_pre_stream && ffn_eligible(d, Tl, pr) && ffn_masks();
+    const bool ffn_ok = lens_ffn || (fold && r3 && h->fuse_ffn && a.ffn_stream && ffn_eligible(d, Tl, pr));
     // attn2.to_out + residual as the pre-stage of the fused feed-forward kernel: y after the cross-attention is never stored
     const bool ffn_pre = ffn_ok && h->fuse_ffn_pre && a.ffn_pre_stream;
     if (!ffn_pre) {
@@ -435,6 +447,7 @@ struct Planner {
       f.out_f32 = out; f.ldo_f32 = d; f.out_op = out_op; f.ldo_op = d;
       f.stats = new_stats(out, Tl, d);
       f.B = B; f.T = Tl; f.M = M; f.dim = d; f.ln_health = h->ln_health;
+      if (lens_ffn) f.lens = lens_of(Tl);           // (the kernel zeroes the rows past an item's end itself: no mask() behind it)
       const double fl = 2.0 * M * (double)d * ((ffn_pre ? 14.0 : 13.0) * d) + (xatt ? 4.0 * B * h->cfg.heads * (double)Tl * Lp * hd : 0.0);
       add(a.prefix + (xatt ? ".ffn[attn2.sdpa+to_out+geglu+ff.out+proj_out]" : ffn_pre ? ".ffn[attn2.to_out+geglu+ff.out+proj_out]" : ".ffn[geglu+ff.out+proj_out]"),
           [=](hipStream_t s) { return launch_ffn(f, pr, s); }, 1, fl,
