@@ -75,6 +75,7 @@ int ns2vc_sizeof_gemm_args(void);
 int ns2vc_sizeof_attn_args(void);                /* the same for the attention arguments, whose last fields are `q_lens, k_lens` */
 int ns2vc_sizeof_rowchain_args(void);            /* ... and for the row-chain arguments, whose last field is `lens` */
 int ns2vc_sizeof_ffn_args(void);                 /* ... and for the fused feed-forward arguments, whose last field is `lens` */
+int ns2vc_sizeof_geglu_args(void);               /* ... and for the token-stationary GEGLU arguments, whose last fields are `T, lens` */
 const char* ns2vc_last_error(void);
 int ns2vc_device_count(int* out_count);
 int ns2vc_set_device(int device);               /* one process per GPU: call with LOCAL_RANK */
@@ -119,6 +120,11 @@ int ns2vc_unet_num_missing_weights(ns2vc_unet* h, char* first_missing, int bufle
  *                    transformer block (ns2vc_k_ffn with pre_a) and gives it the level's length table (ns2vc_ffn_args.lens) instead of the
  *                    attn2.to_out, norm3, ff.geglu, ff.out+proj_out launches and their mask_rows sweeps; independent of masked_fuse, masked_attn
  *                    and masked_rows; dense plans and the fp32 engine ignore it
+ *   "masked_geglu" 1|0 (default 0) a plan built under per-item lengths keeps the token-stationary GEGLU launch of a dim-384 transformer block
+ *                    (ns2vc_k_geglu) on a level of at least the dense crossover's rows and gives it the level's length table
+ *                    (ns2vc_geglu_args.T, lens) with ln_stats = NULL -- the kernel takes the LayerNorm sums from the operand rows it holds --
+ *                    instead of the norm3 launch and the plain GEGLU GEMM with its mask_rows sweep; attn2.to_out and ff.out+proj_out stay as
+ *                    they are; independent of the four options above; dense plans and the fp32 engine ignore it
  * The environment variables NS2VC_LN_LINEAR / NS2VC_FOLD_FF / NS2VC_FUSE_FFN set the defaults at ns2vc_unet_create.
  *   "temb_join_skip" n  (tests, not a plan option) record the fork_temb join at the (n+1)-th reader of the time scale /
  *                    shift rows instead of the first; the plan build then refuses the fork (ns2vc_unet_op_info which = 2) */
@@ -440,6 +446,24 @@ typedef struct ns2vc_geglu_args {
   void* out_op; int32_t ldo;
   int32_t M, dim;
   unsigned* ln_health;                      /* optional, as in ns2vc_gemm_args */
+  /* Per-item frame counts (backward-compatible addition to ABI v7: the two fields are the LAST of the struct, a zero-filled tail = everything above
+   * as it was).
+   *   T    = frames per item, any value >= 1 with M % T == 0 (read only when `lens` is set);
+   *   lens = DEVICE [B], B = M / T entries, one count per batch item.  Row m is frame t = m - b T of item b = m / T and takes part iff t < lens[b];
+   *          a count is clamped to 0 .. T before it is used.
+   * A row at or past its item's end: its `yn` and `ln_stats` rows are not read, it takes no part in ln_health, and its out_op row (the 4 dim
+   * columns) is stored as exact zeros.  Rows at or past M stay unwritten.  A 128-row block without a valid row stores its zeros and returns: no
+   * weight is streamed for it.
+   * Statistics under `lens`: with ln_stats given they are used exactly as without lengths -- every valid row is bit-identical to the launch without
+   * `lens` on its item alone at M = lens[b].  With ln_stats == NULL (allowed only together with `lens`) the kernel takes (sum, sum of squares) from
+   * the token's ROUNDED operand row `yn`, which it holds in registers: no row-statistics producer is needed.  The two modes agree to about 0.1
+   * operand ulp in relative L2 and are equally close to the exact LayerNorm of the unrounded row, but they are not bit-comparable with each other.
+   * Served by the masked instantiations of the kernel (both operand types).  A call that sets `lens` with T < 1 or M % T != 0, or that leaves
+   * ln_stats NULL without `lens`, is refused (hipErrorInvalidValue), never run unmasked.
+   * The struct is 16 bytes longer than in earlier builds of ABI v7 and ns2vc_k_geglu reads all of it: a binding compiled against the earlier header
+   * MUST be rebuilt; ns2vc_sizeof_geglu_args() is there to check. */
+  int32_t T;
+  const int32_t* lens;
 } ns2vc_geglu_args;
 /* w1_packed [8*dim][dim], bias1_packed [8*dim] (or NULL): LayerNorm-folded ff.net.0 rows / bias in the packed (32 value | 32 gate) order,
  * fp32 host.  Returns the device tile stream and the device constants ((rowsum of the rounded row, bias) per stream row). */

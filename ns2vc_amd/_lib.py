@@ -89,6 +89,7 @@ class GegluArgs(C.Structure):
         ("out_op", C.c_void_p), ("ldo", C.c_int32),
         ("M", C.c_int32), ("dim", C.c_int32),
         ("ln_health", C.c_void_p),
+        ("T", C.c_int32), ("lens", C.c_void_p),
     ]
 
 
@@ -131,6 +132,7 @@ PROTOTYPES = {
     "ns2vc_sizeof_attn_args": (_I, []),
     "ns2vc_sizeof_rowchain_args": (_I, []),
     "ns2vc_sizeof_ffn_args": (_I, []),
+    "ns2vc_sizeof_geglu_args": (_I, []),
     "ns2vc_last_error": (C.c_char_p, []),
     "ns2vc_device_count": (_I, [C.POINTER(_I)]),
     "ns2vc_set_device": (_I, [_I]),
@@ -255,6 +257,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         raise Ns2vcError(f"ns2vc_rowchain_args: library has {lib.ns2vc_sizeof_rowchain_args()} bytes, binding {C.sizeof(RowchainArgs)}")
     if lib.ns2vc_sizeof_ffn_args() != C.sizeof(FfnArgs):
         raise Ns2vcError(f"ns2vc_ffn_args: library has {lib.ns2vc_sizeof_ffn_args()} bytes, binding {C.sizeof(FfnArgs)}")
+    if lib.ns2vc_sizeof_geglu_args() != C.sizeof(GegluArgs):
+        raise Ns2vcError(f"ns2vc_geglu_args: library has {lib.ns2vc_sizeof_geglu_args()} bytes, binding {C.sizeof(GegluArgs)}")
     if path is None:
         _lib = lib
     return lib

@@ -58,6 +58,7 @@ int ns2vc_sizeof_gemm_args(void) { return (int)sizeof(ns2vc_gemm_args); }
 int ns2vc_sizeof_attn_args(void) { return (int)sizeof(ns2vc_attn_args); }
 int ns2vc_sizeof_rowchain_args(void) { return (int)sizeof(ns2vc_rowchain_args); }
 int ns2vc_sizeof_ffn_args(void) { return (int)sizeof(ns2vc_ffn_args); }
+int ns2vc_sizeof_geglu_args(void) { return (int)sizeof(ns2vc_geglu_args); }
 const char* ns2vc_last_error(void) { return g_err.c_str(); }
 
 int ns2vc_device_count(int* out_count) {

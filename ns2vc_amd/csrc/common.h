@@ -317,6 +317,7 @@ void set_ffn_trace(unsigned long long* p);
 bool geglu_eligible(int dim, int T, int prec);
 hipError_t pack_geglu_stream(const float* w1p, const float* bias1p, int dim, int prec, std::vector<unsigned short>& stream, std::vector<float>& consts);
 hipError_t launch_geglu(const ::ns2vc_geglu_args& a, int prec, hipStream_t s);
+bool geglu_masks_rows(const ::ns2vc_geglu_args& a, int prec);                                  // ... on a masked instantiation (ns2vc_geglu_args.lens, T), were it set?
 hipError_t init_geglu_attributes();
 void set_gg_trace(unsigned long long* p);
 void set_ts_trace(unsigned long long* p);       // convts.hip

@@ -247,6 +247,13 @@ struct ns2vc_unet {
   // launches; the plain form (whose ln_stats would need a masked producer), dim 384 / 512 and levels under 64 frames stay as they are.  Asked per
   // launch (ffn_masks_rows).  Independent of masked_fuse, masked_attn and masked_rows; dense plans and the fp32 engine ignore it.
   bool masked_ffn = false;
+  // Option masked_geglu (off): under per-item lengths a dim-384 transformer block on a level of at least g_geglu_min_rows rows keeps the
+  // token-stationary GEGLU launch (geglu.hip), which gets the level's length table (ns2vc_geglu_args.T, lens) and no ln_stats: its masked
+  // instantiation takes the LayerNorm sums of norm3 from the operand rows it holds in registers, so it needs no LayerNorm-by-linearity producer, and
+  // stores the rows past an item's end as exact zeros.  Replaces norm3 and the plain GEGLU GEMM with its mask_rows launch; attn2.to_out (raw operand
+  // copy to qb) and ff.out+proj_out stay as they are.  Asked per launch (geglu_masks_rows).  Independent of the four options above; dense plans and
+  // the fp32 engine ignore it.
+  bool masked_geglu = false;
   // Per-item valid lengths (ns2vc_unet_set_lengths).  `masked`: the plan was built for them -- GroupNorm statistics by their own pass over
   // rows whose padding is zero (no epilogue sums, so no fused GroupNorm prologue, row chain or LayerNorm by linearity), every activation's
   // rows past an item's end zeroed after the launch that writes them, the self-attention keys there masked by an additive bias row, the

@@ -81,7 +81,13 @@ template <int N> __device__ __forceinline__ void gg_wait_tiles(int t) {
   else { if (t >= N) wait_vmcnt<2 * N>(); else gg_wait_tiles<N - 1>(t); }
 }
 
-template <typename TM, int D>
+// MASKED: per-item frame counts (GegluArgs.lens, T; option masked_geglu).  Its own instantiations: the dense ones keep their instructions.  Row m is
+// frame t = m - b T of item b = m / T and takes part iff m < M and t < clamp(lens[b], 0, T).  T is any value >= 1, so a 128-token block may touch many
+// items: the predicate is per token, kept as two 64-bit lane masks in SGPRs (tokens 0 .. 63 and 64 .. 127 of the block) that every wave forms for
+// itself.  A token that does not take part is treated as a token past M is -- a zero panel row, no statistics row, no part in ln_health -- and, being
+// inside M, its results are stored as exact zeros.  With ln_stats == NULL (this form only) the LayerNorm sums are taken from the token's rounded
+// operand row, which the lane and its partner (lane ^ 32) hold in registers anyway.  The K loop is the dense one, wait for wait and barrier for barrier.
+template <typename TM, int D, bool MASKED = false>
 __global__ __launch_bounds__(512) void geglu_kernel(const GegluArgs a) {
   op_mode_init<TM>();
   using G = GegluGeom<D>;
@@ -115,6 +121,37 @@ __global__ __launch_bounds__(512) void geglu_kernel(const GegluArgs a) {
   const int m0 = tb * GG_TOK;
   const int mtok = m0 + 32 * tq + l31;              // this lane's token (both lane halves)
 
+  // MASKED: the block's predicate.  Lane l of EVERY wave evaluates tokens l and 64 + l of the block -- two gathers from `lens`, issued and consumed
+  // here, in front of every DMA and every barrier -- and a ballot turns the 64 answers into a mask that is the same in all eight waves: its inputs
+  // (a.M, a.T, m0 and the table, which nothing writes while the kernel runs) and the lane -> token mapping do not depend on the wave.  A count is
+  // clamped before it is used and only ever selects zeros; the gather index is clamped into the table.
+  unsigned long long live_lo = 0ull, live_hi = 0ull;
+  bool live_t = true;                               // this lane's own token mtok takes part
+  if constexpr (MASKED) {
+    const int nitem = a.M / a.T;
+    bool lv[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int m = m0 + 64 * j + lane, mc = min(m, a.M - 1), b = min(mc / a.T, nitem - 1);
+      lv[j] = m < a.M && mc - b * a.T < min(max(a.lens[b], 0), a.T);
+    }
+    live_lo = __ballot(lv[0]);
+    live_hi = __ballot(lv[1]);
+    // A block without a valid row: zeros for this quarter's columns of its rows inside M, and out -- no DMA issued, no barrier met.  The exit is
+    // workgroup-uniform by construction: both masks are the same 128 bits in every wave (above), so all eight waves take the same side of this
+    // branch, and it stands in front of the first barrier of the kernel.
+    if ((live_lo | live_hi) == 0ull) {
+      constexpr int CH = UB * 64 * 2 / 16;          // 16-byte chunks of a row's quarter
+      for (int i = tid; i < GG_TOK * CH; i += 512) {
+        const int r = i / CH, c = i - r * CH;
+        if (m0 + r < a.M)
+          *reinterpret_cast<u32x4_t*>(reinterpret_cast<char*>(a.out_op) + ((size_t)(m0 + r) * a.ldo + (size_t)(q * UB * 64)) * 2 + c * 16) = u32x4_t{0u, 0u, 0u, 0u};
+      }
+      return;
+    }
+    live_t = (((tq & 2) ? live_hi : live_lo) >> (32 * (tq & 1) + l31)) & 1ull;
+  }
+
   const i32x4_t rW = make_rsrc(a.wstream, (unsigned long long)GG_SPLIT * NP * GG_TILE);
   const unsigned lane16 = (unsigned)(lane * 16);
   const unsigned wq0 = (unsigned)(q * NP) * GG_TILE;        // this quarter's tiles inside the stream
@@ -144,7 +181,9 @@ __global__ __launch_bounds__(512) void geglu_kernel(const GegluArgs a) {
     for (int hp2 = 0; hp2 < 2; ++hp2) {               // two passes of 64 rows (8 waves x 8 rows)
       const int prow = 64 * hp2 + 8 * wave + (lane >> 3), pchunk = lane & 7;
       const int m = m0 + prow;
-      const unsigned voff = m < a.M ? (unsigned)m * (unsigned)a.ldy * 2u + (unsigned)((pchunk ^ ((prow >> 1) & 7)) * 16) : DMA_OOB;
+      // (MASKED: bit 8 wave + lane / 8 of the pass's mask; a row that does not take part is not read -- it arrives as zeros, like a row past M)
+      const bool pok = MASKED ? (((hp2 ? live_hi : live_lo) >> (8 * wave + (lane >> 3))) & 1ull) != 0ull : m < a.M;
+      const unsigned voff = pok ? (unsigned)m * (unsigned)a.ldy * 2u + (unsigned)((pchunk ^ ((prow >> 1) & 7)) * 16) : DMA_OOB;
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) blds16(rY, voff, (unsigned)(kt * 128), lds0 + PANEL0 + kt * (GG_TOK * 128) + (64 * hp2 + 8 * wave) * 128);
     }
@@ -161,23 +200,37 @@ __global__ __launch_bounds__(512) void geglu_kernel(const GegluArgs a) {
   // ---- LayerNorm statistics of this lane's token (ordinary loads: the compiler waits for them -- and, not seeing the DMA above, for everything
   // issued so far: that is the wait for the panel)
   float mean = 0.f, rstd = 1.f;
-  {
-    const float4* sp = reinterpret_cast<const float4*>(a.ln_stats + (size_t)min(mtok, a.M - 1) * (D / 64) * 2);
-    float s = 0.f, qq = 0.f;
-#pragma unroll
-    for (int i = 0; i < D / 128; ++i) { const float4 v = sp[i]; s += v.x + v.z; qq += v.y + v.w; }
+  // (sum, sum of squares) of the row -> mean, rstd and the health report
+  auto ln_finish = [&](float s, float qq) __attribute__((always_inline)) {
     const float inv = 1.0f / (float)D;
     mean = s * inv;
     double var = (double)qq * (double)inv - (double)mean * (double)mean;
     if (var < 0.0) var = 0.0;
     rstd = 1.0f / sqrtf((float)var + a.ln_eps);
     if (a.ln_health && hg == 0 && q == 0) {          // same health report as the LayerNorm-consumer GEMMs (gemm.hip ln_row_finish)
-      float ratio = mtok < a.M ? fabsf(mean) * rstd : 0.f;
+      float ratio = (MASKED ? live_t : mtok < a.M) ? fabsf(mean) * rstd : 0.f;
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) ratio = fmaxf(ratio, __shfl_xor(ratio, o));
       if (lane == 0 && ratio > __uint_as_float(__hip_atomic_load(a.ln_health, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
         atomicMax(a.ln_health, __float_as_uint(ratio));
     }
+  };
+  // (MASKED with ln_stats == NULL: the sums come from the token's own fragments, below, once the panel has landed)
+  if (!MASKED || a.ln_stats) {
+    float s = 0.f, qq = 0.f;
+    if constexpr (MASKED) {
+      // (the statistics row of a token that does not take part is not read: zero sums, mean 0 and a finite rstd for its zero panel row)
+      if (live_t) {
+        const float4* sp = reinterpret_cast<const float4*>(a.ln_stats + (size_t)mtok * (D / 64) * 2);
+#pragma unroll
+        for (int i = 0; i < D / 128; ++i) { const float4 v = sp[i]; s += v.x + v.z; qq += v.y + v.w; }
+      }
+    } else {
+      const float4* sp = reinterpret_cast<const float4*>(a.ln_stats + (size_t)min(mtok, a.M - 1) * (D / 64) * 2);
+#pragma unroll
+      for (int i = 0; i < D / 128; ++i) { const float4 v = sp[i]; s += v.x + v.z; qq += v.y + v.w; }
+    }
+    ln_finish(s, qq);
   }
   asm volatile("" : "+v"(mean), "+v"(rstd));
   wait_vmcnt<0>();
@@ -214,6 +267,29 @@ __global__ __launch_bounds__(512) void geglu_kernel(const GegluArgs a) {
     __builtin_amdgcn_s_barrier();                   // everyone has its tokens: the panel's slots join the ring
 #pragma unroll
     for (int p0 = NT0; p0 < RING; ++p0) issue_tile(p0, p0);
+  }
+  if constexpr (MASKED) {
+    // ln_stats == NULL: (sum, sum of squares) of the token's ROUNDED operand row, from the fragments.  This lane holds the 16-byte chunks 2 ks + hi of
+    // every K tile -- one half of the row -- and lane ^ 32 the other: fp32 accumulation in the fixed order (kt, ks, element), one exchange, and the
+    // two halves added (a + b = b + a bit for bit: both lanes get the same sums).  No load of its own; the health report's atomic only adds to what
+    // the first counted wait of the loop sees outstanding, which makes that wait longer, never shorter.
+    if (!a.ln_stats) {
+      float s = 0.f, qq = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float x0 = Op16<TM>::lo(tk[kt][ks][e]), x1 = Op16<TM>::hi(tk[kt][ks][e]);
+            s += x0; qq = fmaf(x0, x0, qq);
+            s += x1; qq = fmaf(x1, x1, qq);
+          }
+      s += __shfl_xor(s, 32);
+      qq += __shfl_xor(qq, 32);
+      ln_finish(s, qq);
+      asm volatile("" : "+v"(mean), "+v"(rstd));
+    }
   }
 #if NS2VC_GG_PRIO
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // static priority for the second-dispatched half (the arbitration loser on every step otherwise)
@@ -260,6 +336,9 @@ __global__ __launch_bounds__(512) void geglu_kernel(const GegluArgs a) {
     }
     hp[2 * j] = Op16<TM>::pack(hh[0], hh[1]);
     hp[2 * j + 1] = Op16<TM>::pack(hh[2], hh[3]);
+    // (MASKED: a token that does not take part is stored as exact zeros -- a select, whatever the accumulators hold; the staged block and the stores
+    //  then carry the zeros with no predicate of their own)
+    if constexpr (MASKED) if (!live_t) { hp[2 * j] = 0u; hp[2 * j + 1] = 0u; }
   };
   // Result stores.  A lane holds 16 units of ONE token: stored from the registers, every instruction is 64 scattered 16-byte pieces in 32 rows, and the
   // store path -- not the MFMAs, not the weight stream -- set the kernel's time (with everything else removed from the loop it still ran 25 of its
@@ -462,23 +541,34 @@ hipError_t pack_geglu_stream(const float* w1p, const float* bias1p, int dim, int
   return hipSuccess;
 }
 
-template <typename TM> static hipError_t launch_geglu_t(const GegluArgs& a, hipStream_t s) {
+template <typename TM, bool MASKED> static hipError_t launch_geglu_t(const GegluArgs& a, hipStream_t s) {
   const int ntb = (a.M + GG_TOK - 1) / GG_TOK;
-  hipLaunchKernelGGL((geglu_kernel<TM, 384>), dim3(ntb * GG_SPLIT), dim3(512), GegluGeom<384>::LDS, s, a);
+  hipLaunchKernelGGL((geglu_kernel<TM, 384, MASKED>), dim3(ntb * GG_SPLIT), dim3(512), GegluGeom<384>::LDS, s, a);
   return hipGetLastError();
+}
+
+// Would launch_geglu run these arguments on a masked instantiation (GegluArgs.lens), were it set?  Both instantiations have a masked twin; what is left
+// are the conditions on T, from which the frame of a row is derived.
+bool geglu_masks_rows(const GegluArgs& a, int prec) {
+  return geglu_eligible(a.dim, 1, prec) && a.M > 0 && a.T >= 1 && (a.M % a.T) == 0;
 }
 
 hipError_t launch_geglu(const GegluArgs& a, int prec, hipStream_t s) {
   if (!geglu_eligible(a.dim, 1, prec) || a.M <= 0) return hipErrorInvalidValue;
-  if (!a.yn || !a.ln_stats || !a.wstream || !a.consts || !a.out_op) return hipErrorInvalidValue;
+  if (!a.yn || !a.wstream || !a.consts || !a.out_op) return hipErrorInvalidValue;
+  if (!a.lens && !a.ln_stats) return hipErrorInvalidValue;                  // (the dense kernel has no statistics of its own)
+  if (a.lens && !geglu_masks_rows(a, prec)) return hipErrorInvalidValue;    // refused, never run unmasked
   if (a.ldy < a.dim || a.ldo < 4 * a.dim || (a.ldy & 7) || (a.ldo & 7) || (unsigned long long)a.M * a.ldy * 2ull > 0xFFF00000ull || (unsigned long long)a.M * a.ldo * 2ull > 0x7FF00000ull) return hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(a.out_op) & 15) != 0) return hipErrorInvalidValue;
-  return prec == PREC_BF16 ? launch_geglu_t<bf16_t>(a, s) : launch_geglu_t<f16_t>(a, s);
+  if (a.lens) return prec == PREC_BF16 ? launch_geglu_t<bf16_t, true>(a, s) : launch_geglu_t<f16_t, true>(a, s);
+  return prec == PREC_BF16 ? launch_geglu_t<bf16_t, false>(a, s) : launch_geglu_t<f16_t, false>(a, s);
 }
 
 hipError_t init_geglu_attributes() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<bf16_t, 384>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<f16_t, 384>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<bf16_t, 384, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<f16_t, 384, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<bf16_t, 384, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<f16_t, 384, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
   return e;
 }
 

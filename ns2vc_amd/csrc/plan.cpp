@@ -455,14 +455,27 @@ struct Planner {
               (xatt ? (double)opsz * B * d * 2.0 * Lp : 0.0));
       return;
     }
-    if (!r3) layernorm(t + ".norm3");
+    // option masked_geglu: under lengths the token-stationary kernel takes the LayerNorm sums of norm3 from the raw operand rows it holds (qb, which
+    // attn2.to_out has just written and ff.out+proj_out reads again) and masks its own rows -- no norm3 pass, no r3, no mask() behind it.  (Every
+    // condition of the kept launch in one place: the option, the forward plan, a level with a length row, the dense conditions of the launch
+    // with its crossover and a masked kernel for it; the fused feed-forward above did not apply.)
+    auto geglu_masks = [&]() {
+      ns2vc_geglu_args f;
+      memset(&f, 0, sizeof(f));
+      f.M = M; f.dim = d; f.T = Tl;
+      return geglu_masks_rows(f, pr);
+    };
+    const bool lens_geglu = masked && h->masked_geglu && ops == &h->fwd_ops && level_of(Tl) >= 0 && lin_dense && fold && h->fuse_geglu &&
+                            a.geglu_stream && geglu_eligible(d, Tl, pr) && M >= g_geglu_min_rows && geglu_masks();
+    if (!r3 && !lens_geglu) layernorm(t + ".norm3");
     // (a workgroup of that kernel sweeps a quarter of the hidden units for its 128 tokens -- 36 dependent tile steps: worth it once the token blocks
     //  fill the chip; below ~144 workgroups the GEMM's 24 column tiles per row block finish sooner.  r5 batch sweep: batch 1-4 +0.1 ms/step without this; crossover between 3760 and 5640 rows)
-    if (r3 && h->fuse_geglu && a.geglu_stream && geglu_eligible(d, Tl, pr) && M >= g_geglu_min_rows) {
+    if (lens_geglu || (r3 && h->fuse_geglu && a.geglu_stream && geglu_eligible(d, Tl, pr) && M >= g_geglu_min_rows)) {
       // the token rows stay in LDS, only weights stream (csrc/geglu.hip): half the L2 -> LDS bytes of the GEMM below
       ns2vc_geglu_args f;
       memset(&f, 0, sizeof(f));
       f.yn = yn; f.ldy = d; f.ln_stats = r3; f.ln_eps = 1e-5f;
+      if (lens_geglu) { f.yn = qb; f.ln_stats = nullptr; f.T = Tl; f.lens = lens_of(Tl); }
       f.wstream = a.geglu_stream; f.consts = a.geglu_consts;
       f.out_op = ffh; f.ldo = 4 * d; f.M = M; f.dim = d; f.ln_health = h->ln_health;
       add(t + ".ff.geglu[token-stationary]", [=](hipStream_t s) { return launch_geglu(f, pr, s); }, 1, 2.0 * M * (double)d * 8.0 * d,

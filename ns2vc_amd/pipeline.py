@@ -87,7 +87,7 @@ class Denoiser:
     def __init__(self, state: Dict[str, object], cfg: UNetConfig = UNetConfig(), precision: str = DEFAULT_PRECISION,
                  betas: Optional[np.ndarray] = None, ln_guard: Optional[float] = -1.0, tail_fp32: Optional[int] = None,
                  precision_check: Optional[float] = -1.0, attn_fallback_limit: Optional[float] = 0.10, masked_fuse: bool = False,
-                 masked_attn: bool = False, masked_rows: bool = False, masked_ffn: bool = False):
+                 masked_attn: bool = False, masked_rows: bool = False, masked_ffn: bool = False, masked_geglu: bool = False):
         self.cfg = cfg
         # engine option ``masked_fuse``: under ``lengths=`` the plan keeps its fused launches where the kernels mask their own rows; passed to
         # the fp32 engine of the tail / self-check as well
@@ -101,6 +101,9 @@ class Denoiser:
         # engine option ``masked_ffn``: under ``lengths=`` the dim-128 / 256 transformer blocks keep the pre-stage launch of the fused feed-forward,
         # which zeroes the rows past an item's end itself; independent of the three above, passed on the same way (the fp32 engine ignores it)
         self.masked_ffn = bool(masked_ffn)
+        # engine option ``masked_geglu``: under ``lengths=`` the dim-384 transformer blocks keep the token-stationary GEGLU launch, which takes the
+        # LayerNorm sums from its own operand rows and zeroes the rows past an item's end itself; independent of the four above, passed on the same way
+        self.masked_geglu = bool(masked_geglu)
         self.attn_fallback_limit = attn_fallback_limit if precision not in ("fp32", "f32") else None
         self.attn_fallback_rate_seen: Optional[float] = None
         self._attn_checked = False
@@ -115,6 +118,8 @@ class Denoiser:
             self.engine.set_option("masked_rows", True)
         if self.masked_ffn:
             self.engine.set_option("masked_ffn", True)
+        if self.masked_geglu:
+            self.engine.set_option("masked_geglu", True)
         self._state = state
         self.betas = linear_betas() if betas is None else np.asarray(betas, dtype=np.float32)
         # ddim / ddpm index the model's own float32 buffers, which the reference derives from the float64 betas
@@ -196,7 +201,7 @@ class Denoiser:
         """A plan option of the engine (``Engine.set_option``; e.g. ``gn_coop`` off for a pipeline that runs the denoiser on a CU partition).
         The plan and the sampler table are rebuilt by the next ``sample``."""
         self.engine.set_option(name, value)
-        if name in ("masked_fuse", "masked_attn", "masked_rows", "masked_ffn"):
+        if name in ("masked_fuse", "masked_attn", "masked_rows", "masked_ffn") or name == "masked_geglu":
             setattr(self, name, bool(value))
             if self.tail_engine is not None:
                 self.tail_engine.set_option(name, value)
@@ -229,6 +234,8 @@ class Denoiser:
                 self.tail_engine.set_option("masked_rows", True)
             if self.masked_ffn:
                 self.tail_engine.set_option("masked_ffn", True)
+            if self.masked_geglu:
+                self.tail_engine.set_option("masked_geglu", True)
             self._tail_shape = None
             self._tail_table_key = None
         if self._tail_shape != self._shape:

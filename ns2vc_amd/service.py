@@ -64,7 +64,7 @@ class GroupedConverter:
     def __init__(self, pre_model: PreModel, denoiser: Denoiser, decode_fn: Optional[Callable] = None, max_batch: int = 32,
                  solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, ragged: bool = False, eta: float = 0.0,
                  masked_fuse: Optional[bool] = None, masked_attn: Optional[bool] = None,
-                 masked_rows: Optional[bool] = None, masked_ffn: Optional[bool] = None, **options):
+                 masked_rows: Optional[bool] = None, masked_ffn: Optional[bool] = None, masked_geglu: Optional[bool] = None, **options):
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
         if masked_fuse is not None and bool(masked_fuse) != denoiser.masked_fuse:     # the denoiser's engine option of that name (ragged batches only)
             denoiser.set_option("masked_fuse", bool(masked_fuse))
@@ -74,6 +74,8 @@ class GroupedConverter:
             denoiser.set_option("masked_rows", bool(masked_rows))
         if masked_ffn is not None and bool(masked_ffn) != denoiser.masked_ffn:
             denoiser.set_option("masked_ffn", bool(masked_ffn))
+        if masked_geglu is not None and bool(masked_geglu) != denoiser.masked_geglu:
+            denoiser.set_option("masked_geglu", bool(masked_geglu))
         self.max_batch, self.seed, self.ragged = max_batch, seed, ragged
         if solver == "ddpm" and steps == 30:      # (the constructor's default step count is the continuous solvers'; ddpm runs every timestep)
             steps = None

@@ -6,6 +6,7 @@
 --masked-attn (with --masked-fuse) adds (b'') -- leg (b') with the engine option masked_attn on as well -- to that rotation;
 --masked-rows (with --masked-fuse --masked-attn) adds (b3) -- leg (b'') with the engine option masked_rows on as well -- to that rotation;
 --masked-ffn (with --masked-fuse --masked-attn --masked-rows) adds (b4) -- leg (b3) with the engine option masked_ffn on as well -- to that rotation;
+--masked-geglu (with --masked-fuse --masked-attn --masked-rows --masked-ffn) adds (b5) -- leg (b4) with the engine option masked_geglu on as well -- to that rotation;
 --skip-per-shape leaves (c) out.
 Each figure is the median of `--reps` timed sampling loops (hipGraph replays, condition set outside the timing) after a warm-up loop.
 Usage: python tools/ragged_bench.py [--reps 5] [--out FILE]"""
@@ -31,6 +32,7 @@ def main():
     ap.add_argument("--masked-attn", action="store_true", help="with --masked-fuse: also run leg (b') with the option masked_attn on")
     ap.add_argument("--masked-rows", action="store_true", help="with --masked-fuse --masked-attn: also run leg (b'') with the option masked_rows on")
     ap.add_argument("--masked-ffn", action="store_true", help="with --masked-fuse --masked-attn --masked-rows: also run leg (b3) with the option masked_ffn on")
+    ap.add_argument("--masked-geglu", action="store_true", help="with --masked-fuse --masked-attn --masked-rows --masked-ffn: also run leg (b4) with the option masked_geglu on")
     ap.add_argument("--alternate", type=int, default=3, help="repetitions of (a), (b), (b') in turn (with --masked-fuse)")
     ap.add_argument("--skip-per-shape", action="store_true")
     a = ap.parse_args()
@@ -42,10 +44,10 @@ def main():
     xT = torch.from_numpy(hash_normal("rb.x", (B, 100, T))).to(dev)
     e = Engine(precision="fp16")
     e.load_state_dict(procedural_state_dict(seed=0))
-    fused_now = attn_now = rows_now = ffn_now = False      # the engine's masked_fuse / masked_attn / masked_rows / masked_ffn options as last set
+    fused_now = attn_now = rows_now = ffn_now = geglu_now = False      # the engine's masked_fuse / masked_attn / masked_rows / masked_ffn / masked_geglu options as last set
 
-    def loop_ms(bsz, tl, lengths=None, sl=slice(None), fuse=False, attn=False, rows=False, ffn=False):
-        nonlocal fused_now, attn_now, rows_now, ffn_now
+    def loop_ms(bsz, tl, lengths=None, sl=slice(None), fuse=False, attn=False, rows=False, ffn=False, geglu=False):
+        nonlocal fused_now, attn_now, rows_now, ffn_now, geglu_now
         if fused_now != fuse:
             e.set_option("masked_fuse", fuse)        # (drops the plan: prepared again below)
             fused_now = fuse
@@ -58,6 +60,9 @@ def main():
         if ffn_now != ffn:
             e.set_option("masked_ffn", ffn)
             ffn_now = ffn
+        if geglu_now != geglu:
+            e.set_option("masked_geglu", geglu)
+            geglu_now = geglu
         if e.shape != (bsz, tl, Lp):
             e.prepare(bsz, tl, Lp)
             e.load_sampler("unipc", a.steps)
@@ -92,6 +97,9 @@ def main():
                 if a.masked_ffn:
                     legs["b_fused_attn_rows_ffn"] = lambda: loop_ms(B, T, lens, fuse=True, attn=True, rows=True, ffn=True)
                     order.append("b_fused_attn_rows_ffn")
+                    if a.masked_geglu:
+                        legs["b_fused_attn_rows_ffn_geglu"] = lambda: loop_ms(B, T, lens, fuse=True, attn=True, rows=True, ffn=True, geglu=True)
+                        order.append("b_fused_attn_rows_ffn_geglu")
         for i in range(a.alternate):             # the order rotates, so that a drift of the clocks does not favour one leg
             k0 = i % len(order)
             rot = order[k0:] + order[:k0]
@@ -121,6 +129,10 @@ def main():
             r["fused"].update({"b_fused_attn_rows_ffn_ms": round(med["b_fused_attn_rows_ffn"], 3),
                                "b_fused_attn_rows_ffn_over_a": round(med["b_fused_attn_rows_ffn"] / med["a"], 3),
                                "b_fused_attn_rows_ffn_over_b_fused_attn_rows": round(med["b_fused_attn_rows_ffn"] / med["b_fused_attn_rows"], 3)})
+        if "b_fused_attn_rows_ffn_geglu" in med:
+            r["fused"].update({"b_fused_attn_rows_ffn_geglu_ms": round(med["b_fused_attn_rows_ffn_geglu"], 3),
+                               "b_fused_attn_rows_ffn_geglu_over_a": round(med["b_fused_attn_rows_ffn_geglu"] / med["a"], 3),
+                               "b_fused_attn_rows_ffn_geglu_over_b_fused_attn_rows_ffn": round(med["b_fused_attn_rows_ffn_geglu"] / med["b_fused_attn_rows_ffn"], 3)})
     line = json.dumps(r)
     print(line)
     if a.out:
