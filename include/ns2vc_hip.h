@@ -111,7 +111,10 @@ int ns2vc_unet_num_missing_weights(ns2vc_unet* h, char* first_missing, int bufle
  *                    (ns2vc_gemm_args.lens) instead of the unfused launches described at ns2vc_unet_set_lengths; dense plans ignore it
  *   "masked_attn" 1|0  (default 0) a plan built under per-item lengths gives the attention launches the level's length table (ns2vc_attn_args.q_lens /
  *                    k_lens) instead of the self-attention key-bias row and the mask_rows launch behind each of them; independent of masked_fuse;
- *                    dense plans ignore it
+ *                    dense plans ignore it.  A plan built under per-item PROMPT lengths (ns2vc_unet_set_prompt_lengths) gives the attn2 launches
+ *                    the prompt table as k_lens instead of the bias row (which they keep only where a mask was given): the key tiles past an
+ *                    item's prompt are skipped; q_lens as above under latent lengths.  The fp8 PV form and fuse_xattn's in-kernel
+ *                    cross-attention keep the bias row
  *   "masked_rows" 1|0  (default 0) a plan built under per-item lengths keeps the two row-chain launches of a transformer block (ns2vc_k_rowchain)
  *                    and gives them the level's length table (ns2vc_rowchain_args.lens) instead of the GroupNorm apply, proj_in, norm1, attn1.qkv,
  *                    attn1.to_out, norm2, attn2.to_q launches and their mask_rows sweeps; independent of masked_fuse and masked_attn; dense plans
@@ -168,6 +171,20 @@ int ns2vc_unet_set_mask(ns2vc_unet* h, const uint8_t* mask_bl, void* stream);
  * materialised.  Later calls with other lengths only copy the (levels x B) table and the key-mask rows on `stream` (from pinned staging: lengths_b may be reused
  * on return, and the host waits for nothing but the previous call's copy; a repeat of the current lengths copies nothing): a captured graph stays valid. */
 int ns2vc_unet_set_lengths(ns2vc_unet* h, const int32_t* lengths_b, void* stream);
+/* Per-item prompt lengths (backward-compatible addition to ABI v7): plens_b = HOST array [B] with 1 <= P_b <= Lp, or NULL = dense (every item Lp prompt
+ * frames).  Item b of the batch then gives what the engine gives for that item alone with a prompt of P_b frames and no mask (to the precision's
+ * rounding), and nothing a prompt row at or past P_b holds (NaN and Inf included) reaches any result.  An out-of-range value returns an error and changes
+ * nothing; ns2vc_unet_prepare resets to dense.  Call it BEFORE set_condition / set_prompt for the batch: the engine's prompt copy is zeroed past P_b
+ * there, add_embedding's class token is the mean over the item's P_b frames and its attention pooling takes the keys [0, P_b + 1) -- the summation
+ * order and bounds of a launch at Lp = P_b, so the item's add_embedding row has that launch's bits wherever the pooling's q|k|v GEMM runs on the same
+ * tile -- and attn2 of every block drops the keys at or past P_b: by an additive bias row (the value the mask conversion writes for a dropped key),
+ * or, with option masked_attn, by ns2vc_attn_args.k_lens.  The device table lives behind everything the dense plan carves (and behind the tables of
+ * ns2vc_unet_set_lengths): the dense layout does not move.  The first non-NULL call after dense rebuilds the (cheap) plan and drops a captured step
+ * graph, as ns2vc_unet_set_mask does when a bias appears.  Later calls for the same shape are one copy of the table on `stream` (from pinned staging:
+ * plens_b may be reused on return) plus the bias-row launch: a captured graph stays valid; a repeat of the current lengths copies nothing.  With a
+ * mask_bl also given the mask applies to the keys below P_b; the pooling ignores the mask, as it does without lengths (the reference's semantics of
+ * encoder_attention_mask: unmasked pooling).  Independent of ns2vc_unet_set_lengths: both may be set. */
+int ns2vc_unet_set_prompt_lengths(ns2vc_unet* h, const int32_t* plens_b, void* stream);
 
 /* One denoiser evaluation = Diffusion_Encoder.forward (model.py:403-415) ->
  * UNet1DConditionModel.forward (unet_1d_condition.py:743-1037) for the condition set above.
@@ -211,6 +228,11 @@ int ns2vc_unet_attn_fallbacks(ns2vc_unet* h, unsigned long long* count, int rese
  * sibling since the plan was built (or the last reset) and built all their rows themselves: a performance counter -- the results do
  * not depend on it.  Synchronises `stream`. */
 int ns2vc_unet_gn_coop_alone(ns2vc_unet* h, unsigned long long* count, int reset, void* stream);
+/* Backward-compatible addition to ABI v7.  Step graphs this engine has captured and instantiated since it was created: a captured loop that finds its
+ * graph still valid replays it and leaves the count alone (new lengths, prompt lengths, seeds or a new condition for the same shape); whatever drops
+ * the graph (prepare, an option, the first lengths / prompt lengths / mask after none, another kind of solver table) makes the next captured loop
+ * count one more.  No device work, no wait. */
+int ns2vc_unet_graph_captures(ns2vc_unet* h, unsigned long long* count);
 
 /* ---- introspection for tests / profiling -------------------------------------------- */
 int ns2vc_unet_set_debug(ns2vc_unet* h, int enable);  /* keep a copy of every block output; drops the plan: call before prepare() */

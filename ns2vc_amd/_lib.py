@@ -150,6 +150,7 @@ PROTOTYPES = {
     "ns2vc_unet_set_prompt": (_I, [_P, _P, _P, _P]),
     "ns2vc_unet_set_mask": (_I, [_P, _P, _P]),
     "ns2vc_unet_set_lengths": (_I, [_P, _P, _P]),
+    "ns2vc_unet_set_prompt_lengths": (_I, [_P, _P, _P]),
     "ns2vc_unet_forward": (_I, [_P, _P, _P, _P, _P]),
     "ns2vc_sampler_load": (_I, [_P, _I, C.POINTER(C.c_float)]),
     "ns2vc_sampler_run": (_I, [_P, _P, _I, _P]),
@@ -161,6 +162,7 @@ PROTOTYPES = {
     "ns2vc_sampler_set_seeds": (_I, [_P, _P, _P]),
     "ns2vc_unet_attn_fallbacks": (_I, [_P, C.POINTER(C.c_ulonglong), _I, _P]),
     "ns2vc_unet_gn_coop_alone": (_I, [_P, C.POINTER(C.c_ulonglong), _I, _P]),
+    "ns2vc_unet_graph_captures": (_I, [_P, C.POINTER(C.c_ulonglong)]),
     "ns2vc_unet_set_debug": (_I, [_P, _I]),
     "ns2vc_unet_set_option": (_I, [_P, C.c_char_p, _I]),
     "ns2vc_unet_ln_ratio": (_I, [_P, C.POINTER(C.c_float), _P]),

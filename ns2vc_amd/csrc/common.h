@@ -359,10 +359,13 @@ hipError_t launch_nct_to_btc(const float* src, int C, int T, int B, float* dst_f
                              int ldd_op = 0, int split = 0);   // split > 0 (16-bit): dst_op rows of ldd_op columns hold a hi + lo pair, lo at column split + c
 hipError_t launch_btc_to_nct(const float* src, int lds, int C, int T, int B, float* dst, hipStream_t s);
 hipError_t launch_mask_bias(const uint8_t* mask, int n, float* bias, hipStream_t s);
+// the bias row under per-item prompt lengths (plens = DEVICE [B]): -10000 for the keys at or past plens[b], the mask's value below (mask may be NULL)
+hipError_t launch_prompt_bias(const uint8_t* mask, const int* plens, int B, int Lp, float* bias, hipStream_t s);
 hipError_t launch_ln_apply(const float* x, int M, int C, float eps, const float* gamma, const float* beta,
                            float* out, int L, int Lout_stride_rows, hipStream_t s);
-hipError_t launch_pool_cls(float* seq, int B, int L, int C, const float* pos, hipStream_t s);
-hipError_t launch_pool_attn(const float* qkv, int B, int L1, int C, int heads, float* pooled, hipStream_t s);
+// plens (DEVICE [B] or NULL): per-item prompt lengths -- the kernels' own forms, which pool over frames [0, plens[b]) of item b only
+hipError_t launch_pool_cls(float* seq, int B, int L, int C, const float* pos, hipStream_t s, const int* plens = nullptr);
+hipError_t launch_pool_attn(const float* qkv, int B, int L1, int C, int heads, float* pooled, hipStream_t s, const int* plens = nullptr);
 hipError_t launch_pool_proj(const float* pooled, int B, int C, const float* wt, const float* b, int E,
                             const float* gamma, const float* beta, float eps, float* out, hipStream_t s);
 // noise (optional): column 9 of the table row; where it is nonzero, state element (b, t, c) of rows of `ld` columns gains noise * z with

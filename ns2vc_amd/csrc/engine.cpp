@@ -261,6 +261,8 @@ int ns2vc_unet_prepare(ns2vc_unet* h, int B, int T, int Lp) {
   h->lens.masked = false;         // a new shape starts dense (ns2vc_unet_set_lengths)
   h->lens.applied.clear();
   h->seeds.set = false;      // ... and without noise seeds (ns2vc_sampler_set_seeds)
+  h->plens.on = false;       // ... and with whole prompts (ns2vc_unet_set_prompt_lengths)
+  h->plens.applied.clear();
   if (build_plan(h, true)) return 1;
   HIPCHK(hipMalloc(&h->arena, h->arena_bytes));
   HIPCHK(hipMemset(h->arena, 0, h->arena_bytes));
@@ -301,10 +303,10 @@ int ns2vc_unet_set_mask(ns2vc_unet* h, const uint8_t* mask_bl, void* stream) {
     drop_step_graph(h);
     if (build_plan(h, false)) return 1;
   }
-  if (want_mask) {
-    HIPCHK(hipMemcpyAsync(h->mask_dev, mask_bl, (size_t)h->B * h->Lp, hipMemcpyDeviceToDevice, s));
-    HIPCHK(launch_mask_bias(h->mask_dev, h->B * h->Lp, h->maskbias, s));
-  }
+  if (want_mask) HIPCHK(hipMemcpyAsync(h->mask_dev, mask_bl, (size_t)h->B * h->Lp, hipMemcpyDeviceToDevice, s));
+  // per-item prompt lengths: the row also drops the keys past an item's frames, with or without a mask
+  if (h->plens.on) HIPCHK(launch_prompt_bias(want_mask ? h->mask_dev : nullptr, h->plens.dev, h->B, h->Lp, h->maskbias, s));
+  else if (want_mask) HIPCHK(launch_mask_bias(h->mask_dev, h->B * h->Lp, h->maskbias, s));
   return 0;
 }
 
@@ -373,6 +375,38 @@ int ns2vc_unet_set_lengths(ns2vc_unet* h, const int32_t* lengths_b, void* stream
   return 0;
 }
 
+int ns2vc_unet_set_prompt_lengths(ns2vc_unet* h, const int32_t* plens_b, void* stream) {
+  if (check_ready(h, true)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (!plens_b) {
+    if (!h->plens.on) return 0;
+    h->plens.on = false;
+    h->plens.applied.clear();
+    if (rebuild_plan(h)) return 1;
+    if (h->has_mask) HIPCHK(launch_mask_bias(h->mask_dev, h->B * h->Lp, h->maskbias, s));     // (the row of the mask alone again)
+    return 0;
+  }
+  const int B = h->B;
+  for (int b = 0; b < B; ++b)
+    if (plens_b[b] < 1 || plens_b[b] > h->Lp) return fail("prompt_lengths[%d] = %d outside [1, Lp = %d]", b, (int)plens_b[b], h->Lp);
+  if (h->plens.on && h->plens.applied.size() == (size_t)B && std::equal(plens_b, plens_b + B, h->plens.applied.begin())) return 0;   // (the table already holds them)
+  if (!h->plens.on) {
+    // the condition plan and the cross-attention launches bake in whether the table is read: rebuild the (cheap) plan, as set_mask does when a
+    // bias appears; the arena's layout does not depend on it
+    h->plens.on = true;
+    if (rebuild_plan(h)) { h->plens.on = false; (void)rebuild_plan(h); return 1; }
+  }
+  const size_t lb = (size_t)B * sizeof(int32_t);
+  Staged& stage = h->plens.stage;
+  if (stage.reserve(lb)) return 1;
+  memcpy(stage.buf, plens_b, lb);
+  HIPCHK(hipMemcpyAsync(h->plens.dev, stage.buf, lb, hipMemcpyHostToDevice, s));
+  if (stage.record(s)) return 1;
+  HIPCHK(launch_prompt_bias(h->has_mask ? h->mask_dev : nullptr, h->plens.dev, B, h->Lp, h->maskbias, s));
+  h->plens.applied.assign(plens_b, plens_b + B);
+  return 0;
+}
+
 int ns2vc_unet_forward(ns2vc_unet* h, const float* x_bct, const float* t_b, float* out_bct, void* stream) {
   if (check_ready(h, true)) return 1;
   if (!x_bct || !t_b || !out_bct) return fail("null tensor");
@@ -404,6 +438,12 @@ int ns2vc_unet_attn_fallbacks(ns2vc_unet* h, unsigned long long* count, int rese
 int ns2vc_unet_gn_coop_alone(ns2vc_unet* h, unsigned long long* count, int reset, void* stream) {
   if (!h) return fail("null argument");
   return read_counter(h->ln_health ? h->ln_health + 48 : nullptr, count, reset, (hipStream_t)stream);
+}
+
+int ns2vc_unet_graph_captures(ns2vc_unet* h, unsigned long long* count) {
+  if (!h || !count) return fail("null argument");
+  *count = h->graph_captures;
+  return 0;
 }
 
 int ns2vc_unet_num_taps(ns2vc_unet* h) { return h ? (int)h->taps.size() : 0; }

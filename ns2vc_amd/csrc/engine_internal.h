@@ -231,7 +231,8 @@ struct ns2vc_unet {
   // Option masked_attn (off): under per-item lengths the attention launches get the level's length table (AttnArgs.q_lens, and k_lens for the
   // self-attention) instead of the key-bias row and the mask_rows launch behind them: the keys, key tiles and query tiles past an item's end are
   // skipped, not computed and thrown away.  Asked per launch (attention_masks_rows): the fp8 PV form keeps the bias row and its sweeper.
-  // Independent of masked_fuse; dense plans ignore it.
+  // Independent of masked_fuse; dense plans ignore it.  Under per-item PROMPT lengths (plens below) it also hands attn2 the prompt table as k_lens
+  // instead of the bias row.
   bool masked_attn = false;
   // Option masked_rows (off): under per-item lengths a transformer block keeps its two row-chain launches (rowchain.hip), which get the level's
   // length table (ns2vc_rowchain_args.lens): a lane of that kernel owns one token, so the rows past an item's end are zero rows by a per-lane
@@ -267,6 +268,16 @@ struct ns2vc_unet {
     std::vector<int32_t> applied;          // the lengths the tables hold (a repeat of them copies nothing)
     ns2vc::Staged stage;                   // pinned staging of both tables for the asynchronous copies
   } lens;
+  // Per-item prompt lengths (ns2vc_unet_set_prompt_lengths).  `on`: the plan was built for them -- the prompt copy zeroed past an item's frames on
+  // entry, both attention poolings of add_embedding over the item's own frames, and attn2 of every block reading either the table (k_lens, option
+  // masked_attn) or the bias row h->maskbias, which then also drops the keys past an item's frames.  The table sits behind the length tables above,
+  // at a place that does not depend on the plan: new lengths for the same shape are a copy and the bias-row launch, a captured graph stays valid.
+  struct PromptLengths {
+    bool on = false;
+    int* dev = nullptr;                    // [B] prompt frames per item
+    std::vector<int32_t> applied;          // the lengths the table holds (a repeat of them copies nothing)
+    ns2vc::Staged stage;
+  } plens;
   // Per-item noise seeds of the stochastic samplers (ns2vc_sampler_set_seeds): a buffer of its own (the captured step graph reads it, so new
   // seeds are a copy into it), pinned staging as for the lengths.
   struct Seeds {
@@ -309,6 +320,7 @@ struct ns2vc_unet {
 
   hipStream_t cap_stream = nullptr;
   hipGraphExec_t step_graph = nullptr;
+  unsigned long long graph_captures = 0;      // step graphs instantiated over the engine's life (ns2vc_unet_graph_captures)
 
   // 16-bit engines keep the solver state's operand copy as a hi + lo pair, rows [hi(CP) | lo(CP)] (common.h op_rest): its row width and where lo starts
   int pair_width() const { return prec != ns2vc::PREC_F32 ? 2 * CP : CP; }

@@ -301,29 +301,39 @@ __global__ __launch_bounds__(256) void ln_apply_kernel(const float* __restrict__
 }
 
 // class token = mean_t(LN(prompt)) + positional_embedding  (embeddings.py:524).  grid (B, C/64): 64 channels x 4 time slices
-// per block, the slices meet in LDS in a fixed order (was: one block per batch item walking all L rows serially, 109 us)
-__global__ __launch_bounds__(256) void pool_cls_kernel(float* __restrict__ seq, int L, int C, const float* __restrict__ pos) {
+// per block, the slices meet in LDS in a fixed order (was: one block per batch item walking all L rows serially, 109 us).
+// P = frames summed (and the divisor), L = frames per item of `seq` (the row stride): P == L in the dense form
+__device__ __forceinline__ void pool_cls_body(float* __restrict__ seq, int L, int P, int C, const float* __restrict__ pos) {
   __shared__ float part[4][64];
   const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), sl = threadIdx.x >> 6;
   float s = 0.f;
   if (c < C) {
     const float* p = seq + ((size_t)b * (L + 1) + 1) * C + c;
-    for (int t = sl; t < L; t += 4) s += p[(size_t)t * C];
+    for (int t = sl; t < P; t += 4) s += p[(size_t)t * C];
   }
   part[sl][threadIdx.x & 63] = s;
   __syncthreads();
   if (sl == 0 && c < C) {
     const int i = threadIdx.x & 63;
-    seq[(size_t)b * (L + 1) * C + c] = ((part[0][i] + part[1][i]) + (part[2][i] + part[3][i])) / (float)L + pos[c];
+    seq[(size_t)b * (L + 1) * C + c] = ((part[0][i] + part[1][i]) + (part[2][i] + part[3][i])) / (float)P + pos[c];
   }
+}
+__global__ __launch_bounds__(256) void pool_cls_kernel(float* __restrict__ seq, int L, int C, const float* __restrict__ pos) {
+  pool_cls_body(seq, L, L, C, pos);
+}
+// per-item prompt lengths (ns2vc_unet_set_prompt_lengths): item b sums its frames t < plens[b] in the same slice order and divides by plens[b] --
+// what the dense form does for that item alone at L = plens[b]; the rows past them are never read
+__global__ __launch_bounds__(256) void pool_cls_lens_kernel(float* __restrict__ seq, int L, int C, const float* __restrict__ pos,
+                                                            const int* __restrict__ plens) {
+  pool_cls_body(seq, L, min(max(plens[blockIdx.x], 1), L), C, pos);
 }
 
 // AttentionPooling (embeddings.py:499-546): one query (the class token) per
 // (batch, head); keys/values = [cls ; LN(prompt)].  qkv rows hold (q|k|v), each
 // C wide.  One wave per head (grid (B, heads/4): was one block per batch item looping over 16 heads per wave, 188 us),
 // lanes stride over keys.  dph = C/heads <= 8.
-__global__ __launch_bounds__(256) void pool_attn_kernel(const float* __restrict__ qkv, int L1, int C, int heads,
-                                                        float* __restrict__ pooled) {
+// L1 = rows per item of `qkv` (the row stride, and the stride of the waves' score rows), n = keys taken: n == L1 in the dense form
+__device__ __forceinline__ void pool_attn_body(const float* __restrict__ qkv, int L1, int n, int C, int heads, float* __restrict__ pooled) {
   extern __shared__ float s_sc[];           // 4 waves x L1 scores
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int dph = C / heads;
@@ -337,7 +347,7 @@ __global__ __launch_bounds__(256) void pool_attn_kernel(const float* __restrict_
 #pragma unroll
     for (int c = 0; c < 8; ++c) qv[c] = (c < dph) ? base[h * dph + c] : 0.f;      // row 0 = class token
     float mx = -INFINITY;
-    for (int j = lane; j < L1; j += 64) {
+    for (int j = lane; j < n; j += 64) {
       const float* kp = base + (size_t)j * 3 * C + C + h * dph;
       float s = 0.f;
 #pragma unroll
@@ -349,7 +359,7 @@ __global__ __launch_bounds__(256) void pool_attn_kernel(const float* __restrict_
     mx = wave_max(mx);
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float den = 0.f;
-    for (int j = lane; j < L1; j += 64) {
+    for (int j = lane; j < n; j += 64) {
       const float w = __expf(sc[j] - mx);
       den += w;
       const float* vp = base + (size_t)j * 3 * C + 2 * C + h * dph;
@@ -363,6 +373,16 @@ __global__ __launch_bounds__(256) void pool_attn_kernel(const float* __restrict_
       if (lane == 0 && c < dph) pooled[(size_t)b * C + h * dph + c] = a / den;
     }
   }
+}
+__global__ __launch_bounds__(256) void pool_attn_kernel(const float* __restrict__ qkv, int L1, int C, int heads,
+                                                        float* __restrict__ pooled) {
+  pool_attn_body(qkv, L1, L1, C, heads, pooled);
+}
+// per-item prompt lengths: item b's keys are [0, plens[b] + 1) -- the class token and its own frames, in the order of the dense form at
+// L1 = plens[b] + 1; the rows past them are never read
+__global__ __launch_bounds__(256) void pool_attn_lens_kernel(const float* __restrict__ qkv, int L1, int C, int heads, float* __restrict__ pooled,
+                                                             const int* __restrict__ plens) {
+  pool_attn_body(qkv, L1, min(max(plens[blockIdx.x], 1), L1 - 1) + 1, C, heads, pooled);
 }
 
 // proj (Linear C->E) + LayerNorm(E)  (embeddings.py:431-433) -> aug_emb [B][E]
@@ -528,6 +548,15 @@ __global__ void mask_bias_kernel(const uint8_t* __restrict__ mask, int n, float*
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) bias[i] = (1.0f - (mask[i] ? 1.0f : 0.0f)) * -10000.0f;
 }
+// the same row under per-item prompt lengths: the keys at or past plens[b] get the value a dropped key gets above, the keys below it the
+// mask's value (mask == NULL: 0)
+__global__ void prompt_bias_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ plens, int B, int Lp, float* __restrict__ bias) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * Lp) return;
+  const int b = i / Lp, j = i - b * Lp;
+  const bool keep = j < plens[b] && (!mask || mask[i]);
+  bias[i] = (1.0f - (keep ? 1.0f : 0.0f)) * -10000.0f;
+}
 
 // ---------------------------------------------------------------------------
 // Fused solver update (ns2vc_amd/schedule.py documents the recurrence and cites
@@ -687,13 +716,16 @@ hipError_t launch_ln_apply(const float* x, int M, int C, float eps, const float*
   hipLaunchKernelGGL(ln_apply_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, M, C, eps, gamma, beta, out, L);
   return hipGetLastError();
 }
-hipError_t launch_pool_cls(float* seq, int B, int L, int C, const float* pos, hipStream_t s) {
-  hipLaunchKernelGGL(pool_cls_kernel, dim3(B, (C + 63) / 64), dim3(256), 0, s, seq, L, C, pos);
+hipError_t launch_pool_cls(float* seq, int B, int L, int C, const float* pos, hipStream_t s, const int* plens) {
+  if (plens) hipLaunchKernelGGL(pool_cls_lens_kernel, dim3(B, (C + 63) / 64), dim3(256), 0, s, seq, L, C, pos, plens);
+  else hipLaunchKernelGGL(pool_cls_kernel, dim3(B, (C + 63) / 64), dim3(256), 0, s, seq, L, C, pos);
   return hipGetLastError();
 }
-hipError_t launch_pool_attn(const float* qkv, int B, int L1, int C, int heads, float* pooled, hipStream_t s) {
-  if (C % heads || C / heads > 8) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pool_attn_kernel, dim3(B, (heads + 3) / 4), dim3(256), 4 * (size_t)L1 * sizeof(float), s, qkv, L1, C, heads, pooled);
+hipError_t launch_pool_attn(const float* qkv, int B, int L1, int C, int heads, float* pooled, hipStream_t s, const int* plens) {
+  if (C % heads || C / heads > 8 || (plens && L1 < 2)) return hipErrorInvalidValue;
+  const size_t lds = 4 * (size_t)L1 * sizeof(float);
+  if (plens) hipLaunchKernelGGL(pool_attn_lens_kernel, dim3(B, (heads + 3) / 4), dim3(256), lds, s, qkv, L1, C, heads, pooled, plens);
+  else hipLaunchKernelGGL(pool_attn_kernel, dim3(B, (heads + 3) / 4), dim3(256), lds, s, qkv, L1, C, heads, pooled);
   return hipGetLastError();
 }
 hipError_t launch_pool_proj(const float* pooled, int B, int C, const float* wt, const float* b, int E, const float* gamma,
@@ -762,6 +794,11 @@ hipError_t launch_btc_to_nct(const float* src, int lds_, int C, int T, int B, fl
 }
 hipError_t launch_mask_bias(const uint8_t* mask, int n, float* bias, hipStream_t s) {
   hipLaunchKernelGGL(mask_bias_kernel, dim3((n + 255) / 256), dim3(256), 0, s, mask, n, bias);
+  return hipGetLastError();
+}
+hipError_t launch_prompt_bias(const uint8_t* mask, const int* plens, int B, int Lp, float* bias, hipStream_t s) {
+  if (!plens || !bias || B <= 0 || Lp <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(prompt_bias_kernel, dim3((B * Lp + 255) / 256), dim3(256), 0, s, mask, plens, B, Lp, bias);
   return hipGetLastError();
 }
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0, float* xe, void* xe_op, int prec,

@@ -279,8 +279,12 @@ struct Planner {
 
   // `self`: Lk is a frame count like Lq (attn1); its keys past an item's end are masked by the level's key-bias row, or -- option masked_attn --
   // left out by the kernel itself (AttnArgs.k_lens), which then also stores the result rows past the end as zeros (q_lens): no mask_rows launch
+  // `cross_lens`: the per-item prompt lengths (attn2 under ns2vc_unet_set_prompt_lengths; `bias` is then the row that also drops the keys past an
+  // item's frames).  With masked_attn the kernel takes the table as k_lens -- the key tiles past an item's frames are skipped -- and the bias only
+  // where a mask was given; otherwise (option off, the fp8 PV form) the launch reads the bias row.  (With a mask the launch keeps the COMBINED row
+  // beside k_lens: its tail repeats what k_lens already drops, but its entries below P_b are the mask's holes, which k_lens cannot express.)
   void attention(const std::string& name, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int Lq, int Lk,
-                 const float* bias, int hd, void* out, int ldo, bool self = false) {
+                 const float* bias, int hd, void* out, int ldo, bool self = false, const int* cross_lens = nullptr) {
     AttnArgs a;
     memset(&a, 0, sizeof(a));
     a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
@@ -296,6 +300,10 @@ struct Planner {
       a.q_lens = lens_of(Lq);
       if (self) a.k_lens = lens_of(Lk);
     } else if (self) a.bias = selfbias_of(Lk);
+    if (cross_lens && (self_mask || (h->masked_attn && ops == &h->fwd_ops && attention_masks_rows(a, hd, pr)))) {
+      a.k_lens = cross_lens;
+      if (!h->has_mask) a.bias = nullptr;
+    }
     add(name, [=](hipStream_t s) { return launch_attention(a, hd, pr, s); }, 2, 4.0 * B * a.H * (double)Lq * Lk * hd,
         (double)opsz * B * a.H * hd * (2.0 * Lq + 2.0 * Lk));
     if (!self_mask) mask(name, out, ldo, a.H * hd, opsz, Lq);
@@ -399,7 +407,7 @@ struct Planner {
     const bool xatt = xattn_fused(a, Tl) && xattn_vt.count(a.prefix);
     if (!xatt)
       attention(t + ".attn2.sdpa", qb, d, op_off(h->kv, a.kv_off), nkv, op_off(h->kv, a.kv_off + d), nkv, Tl, Lp,
-                h->has_mask ? h->maskbias : nullptr, hd, ao, d);
+                (h->has_mask || h->plens.on) ? h->maskbias : nullptr, hd, ao, d, false, h->plens.on ? h->plens.dev : nullptr);
     float* r3 = lin ? rs3 : nullptr;
     // With the feed-forward output folded into proj_out, proj_out reads the RAW operand copy of y next to the GEGLU
     // output.  LayerNorm by linearity writes that copy anyway (yn); the explicit-LayerNorm plan overwrites yn with the
@@ -441,7 +449,7 @@ struct Planner {
       if (xatt) {         // (implies ffn_pre) the cross-attention's output never exists: the kernel builds its token panel from q, the hoisted k rows and V^T
         f.pre_a = nullptr;
         f.att_q = qb; f.att_ldq = d; f.att_kv = xattn_vt[a.prefix];
-        f.att_bias = h->has_mask ? h->maskbias : nullptr; f.att_scale = 1.0f / std::sqrt((float)hd); f.att_Lk = Lp;
+        f.att_bias = (h->has_mask || h->plens.on) ? h->maskbias : nullptr; f.att_scale = 1.0f / std::sqrt((float)hd); f.att_Lk = Lp;
       }
       f.res = x; f.ldres = d;
       f.out_f32 = out; f.ldo_f32 = d; f.out_op = out_op; f.ldo_op = d;
@@ -568,7 +576,11 @@ int build_plan(ns2vc_unet* h, bool sizing) {
     lens_bytes = lb + ((nb * sizeof(float) + 255) & ~(size_t)255);
     h->lens.dev = sizing ? nullptr : reinterpret_cast<int*>(static_cast<char*>(h->arena) + h->lens.off);
     h->lens.selfbias = sizing ? nullptr : reinterpret_cast<float*>(static_cast<char*>(h->arena) + h->lens.off + lb);
+    // ... and the per-item prompt lengths [B] behind both (ns2vc_unet_set_prompt_lengths)
+    h->plens.dev = sizing ? nullptr : reinterpret_cast<int*>(static_cast<char*>(h->arena) + h->lens.off + lens_bytes);
+    lens_bytes += ((size_t)B * sizeof(int) + 255) & ~(size_t)255;
   }
+  const int* plens = h->plens.on ? h->plens.dev : nullptr;
   P.masked = h->lens.masked;
   P.fused = h->lens.masked && h->masked_fuse;
   P.Ts = Ts;
@@ -606,6 +618,9 @@ int build_plan(ns2vc_unet* h, bool sizing) {
     if (!sizing) h->cond_split = h->cond_ops.size();
     // all cross-attention k|v projections in one GEMM: prompt [B*Lp][cross] x [n_kv][cross]^T -> operand tensor
     const size_t np = (size_t)B * Lp * cross;
+    // per-item prompt lengths: the prompt copy's rows past an item's frames -> 0, so that every row-wise launch below sees finite rows whatever the
+    // caller's padding holds
+    if (plens) P.add("cond.prompt.mask", [=](hipStream_t s) { return launch_mask_rows(prompt, (size_t)cross * 4, (size_t)cross * 4, B, Lp, plens, s); }, 4);
     P.add("cond.prompt.cast", [=](hipStream_t s) { return launch_cast_op(prompt, np, prompt_op, prec, s); });
     g = P.base(prompt_op, cross, cross, Lp, Lp, h->kv_all, nullptr, h->kv, h->kv_all.N);
     P.gemm("cond.cross_kv", g);
@@ -625,14 +640,14 @@ int build_plan(ns2vc_unet* h, bool sizing) {
     const int ph_ = c.pool_heads;
     const size_t ns = (size_t)B * (Lp + 1) * cross;
     P.add("cond.pool.ln1", [=](hipStream_t s) { return launch_ln_apply(prompt, B * Lp, cross, 1e-5f, n1g, n1b, seq, Lp, 0, s); });
-    P.add("cond.pool.cls", [=](hipStream_t s) { return launch_pool_cls(seq, B, Lp, cross, pos, s); });
+    P.add("cond.pool.cls", [=](hipStream_t s) { return launch_pool_cls(seq, B, Lp, cross, pos, s, plens); });
     P.add("cond.pool.cast", [=](hipStream_t s) { return launch_cast_op(seq, ns, seq_op, prec, s); });
     g = P.base(seq_op, cross, cross, Lp + 1, Lp + 1, h->pool_qkv, pq, nullptr, h->pool_qkv.N);
     P.gemm("cond.pool.qkv", g);
     const int ldq = h->pool_qkv.N;
     if (ldq != 3 * cross) return fail("pool qkv width %d must equal 3*cross=%d (cross must be a multiple of 128)", ldq, 3 * cross);
     if ((ns & 3) || (np & 3)) return fail("internal: cast sizes must be multiples of 4");
-    P.add("cond.pool.attn", [=](hipStream_t s) { return launch_pool_attn(pq, B, Lp + 1, cross, ph_, pooled, s); });
+    P.add("cond.pool.attn", [=](hipStream_t s) { return launch_pool_attn(pq, B, Lp + 1, cross, ph_, pooled, s, plens); });
     P.add("cond.pool.proj", [=](hipStream_t s) { return launch_pool_proj(pooled, B, cross, projT, projb, E, n2g, n2b, 1e-5f, aug, s); });
     P.tap("aug", aug, B, E);
   }

@@ -176,6 +176,7 @@ int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream)
     e = hipGraphInstantiate(&h->step_graph, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) { h->step_graph = nullptr; return fail("hipGraphInstantiate: %s", hipGetErrorString(e)); }
+    ++h->graph_captures;
   }
   for (int i = 0; i < n_steps; ++i) {
     if (use_graph) HIPCHK(hipGraphLaunch(h->step_graph, s));

@@ -200,6 +200,7 @@ class Engine:
         self.h = h
         self.shape: Optional[Tuple[int, int, int]] = None
         self.lengths: Optional[np.ndarray] = None      # per-item valid frames (set_lengths), None = dense
+        self.prompt_lengths: Optional[np.ndarray] = None   # per-item prompt frames (set_prompt_lengths), None = every item Lp
         self.table: Optional[SolverTable] = None
         self._weights_ready = False
         self._debug = False
@@ -276,6 +277,7 @@ class Engine:
         check(self.lib.ns2vc_unet_prepare(self.h, B, T, Lp), "ns2vc_unet_prepare")
         self.shape = (B, T, Lp)
         self.lengths = None
+        self.prompt_lengths = None
 
     def workspace_bytes(self) -> int:
         n = C.c_size_t()
@@ -318,6 +320,22 @@ class Engine:
             raise ValueError(f"lengths has {a.shape[0]} entries, the prepared batch {self.shape[0]}")
         check(self.lib.ns2vc_unet_set_lengths(self.h, a.ctypes.data, _stream_ptr(stream)), "set_lengths")
         self.lengths = a.copy()
+
+    def set_prompt_lengths(self, prompt_lengths=None, stream=None) -> None:
+        """Per-item prompt frames of the prepared (B, Lp) batch: a sequence / array / tensor of B ints in [1, Lp], or None = every item Lp.
+        Item b then gives what it gives alone with a prompt of prompt_lengths[b] frames and no mask; whatever the prompt rows past them hold
+        reaches no result.  Call before set_condition / set_prompt; prepare() resets it."""
+        if prompt_lengths is None:
+            check(self.lib.ns2vc_unet_set_prompt_lengths(self.h, None, _stream_ptr(stream)), "set_prompt_lengths")
+            self.prompt_lengths = None
+            return
+        if hasattr(prompt_lengths, "detach"):
+            prompt_lengths = prompt_lengths.detach().cpu().numpy()
+        a = np.ascontiguousarray(np.asarray(prompt_lengths).reshape(-1), dtype=np.int32)
+        if self.shape is None or a.shape[0] != self.shape[0]:
+            raise ValueError(f"prompt_lengths has {a.shape[0]} entries, the prepared batch {None if self.shape is None else self.shape[0]}")
+        check(self.lib.ns2vc_unet_set_prompt_lengths(self.h, a.ctypes.data, _stream_ptr(stream)), "set_prompt_lengths")
+        self.prompt_lengths = a.copy()
 
     def set_seeds(self, seeds, stream=None) -> None:
         """(B,) 64-bit seeds of the per-item noise streams of a stochastic table (ns2vc_amd.noise), for the prepared batch;
@@ -394,6 +412,12 @@ class Engine:
         the last reset (a performance counter: the values are the same either way).  Waits for ``stream``."""
         n = C.c_ulonglong()
         check(self.lib.ns2vc_unet_gn_coop_alone(self.h, C.byref(n), int(reset), _stream_ptr(stream)), "gn_coop_alone")
+        return int(n.value)
+
+    def graph_captures(self) -> int:
+        """step graphs captured since the engine was created: a loop that replays a still-valid graph leaves the count alone"""
+        n = C.c_ulonglong()
+        check(self.lib.ns2vc_unet_graph_captures(self.h, C.byref(n)), "graph_captures")
         return int(n.value)
 
     # -- profiling --------------------------------------------------------------------

@@ -146,16 +146,24 @@ class PreModel(nn.Module):
 
     @torch.no_grad()
     def infer(self, c_padded: torch.Tensor, refer_padded: torch.Tensor, lengths: torch.Tensor, refer_lengths: torch.Tensor,
-              autocast: Optional[torch.dtype] = None, exact_lengths: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+              autocast: Optional[torch.dtype] = None, exact_lengths: bool = False,
+              exact_prompt_lengths: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """c_padded (B, 256, T) ContentVec features, refer_padded (B, 100, Lp) reference mel, lengths / refer_lengths (B,).
         Returns content (B, 256, T), prompt (B, Lp, 256), prompt_mask (B, Lp) bool -- what ``Denoiser.sample`` takes.
         ``autocast`` = torch.float16 / torch.bfloat16 runs the GEMMs, convolutions and attention of the two encoders with
         16-bit operands (``torch.autocast``; LayerNorm and the outputs stay fp32) -- the reference's own inference runs fp32.
         ``exact_lengths``: the content of item b is what segment b gives ALONE (its conv feed-forward reads zeros past its end); the default
-        keeps the reference's batched arithmetic, where padding reaches a segment's last frames.  Prompts are not affected (one Lp per batch)."""
+        keeps the reference's batched arithmetic, where padding reaches a segment's last frames.  Prompts are not affected by it.
+        ``exact_prompt_lengths``: the same for the reference clips of a batch padded to one Lp -- the prompt encoder's conv feed-forward reads zeros
+        past a clip's end and ``ref_enc`` pools over the clip's own frames, so prompt b (rows [0, refer_lengths[b]); zeros beyond) and the
+        speaker vector that enters content b are what clip b gives alone.  The default keeps the reference's arithmetic (one Lp per batch)."""
         with torch.autocast(c_padded.device.type, dtype=autocast, enabled=autocast is not None):
-            g = self.ref_enc(refer_padded.transpose(1, 2)).unsqueeze(-1)               # (B, 100, 1)
-            prompt = self.prompt_encoder(refer_padded, refer_lengths)
+            if exact_prompt_lengths:
+                g = self.ref_enc(refer_padded.transpose(1, 2), refer_lengths).unsqueeze(-1)
+                prompt = self.prompt_encoder(refer_padded, refer_lengths, None, True)
+            else:
+                g = self.ref_enc(refer_padded.transpose(1, 2)).unsqueeze(-1)               # (B, 100, 1)
+                prompt = self.prompt_encoder(refer_padded, refer_lengths)
             content = self.phoneme_encoder(c_padded, lengths, g, exact_lengths).transpose(1, 2)
         mask = torch.arange(refer_padded.shape[2], device=refer_padded.device)[None, :] < refer_lengths[:, None]
         return content.float().contiguous(), prompt.float().contiguous(), mask

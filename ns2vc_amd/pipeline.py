@@ -276,7 +276,7 @@ class Denoiser:
         self.serving_fp32 = False
         self._attn_checked = False
 
-    def _self_check(self, points, c32, p32, mask, stream, keep_fp32: bool, lengths=None) -> None:
+    def _self_check(self, points, c32, p32, mask, stream, keep_fp32: bool, lengths=None, prompt_lengths=None) -> None:
         """once per set of weights: the same evaluations on the 16-bit and on the fp32 engine (class docstring, ``precision_check``);
         ``points`` = [(x, t)] with x (B,100,T) fp32 and t (B,) fp32.  With ``lengths`` both engines return exact zeros past every item's
         end, so the per-utterance figures cover its valid frames only."""
@@ -285,8 +285,8 @@ class Denoiser:
             return
         self._precision_checked = True
         e32 = self._fp32_engine()
-        self._condition(self.engine, c32, p32, mask, stream, lengths)
-        self._condition(e32, c32, p32, mask, stream, lengths)
+        self._condition(self.engine, c32, p32, mask, stream, lengths, prompt_lengths)
+        self._condition(e32, c32, p32, mask, stream, lengths, prompt_lengths)
         self.precision_errors = []
         err, worst = 0.0, 0.0
         for x, t in points:
@@ -315,9 +315,11 @@ class Denoiser:
             self._tail_table_key = None
 
     @staticmethod
-    def _condition(eng, c32, p32, mask, stream, lengths) -> None:
-        """per-item valid frames (None = dense) first -- the content's padded frames are zeroed by set_condition -- then the condition"""
+    def _condition(eng, c32, p32, mask, stream, lengths, prompt_lengths=None) -> None:
+        """per-item valid frames and prompt frames (None = dense) first -- the padded content and prompt frames are zeroed by set_condition --
+        then the condition"""
         eng.set_lengths(lengths, stream=stream)
+        eng.set_prompt_lengths(prompt_lengths, stream=stream)
         eng.set_condition(c32, p32, mask, stream=stream)
 
     def _trajectory_points(self, x_T, use_graph, stream):
@@ -340,10 +342,12 @@ class Denoiser:
         self.engine.sample_end(scratch, stream=stream)
         return pts
 
-    def denoise(self, x, t, content, prompt, prompt_mask=None, lengths=None):
+    def denoise(self, x, t, content, prompt, prompt_mask=None, lengths=None, prompt_lengths=None):
         """One evaluation: x (B,100,T), t (B,), content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool -> x0_pred.
         ``lengths`` (B,) ints in [1, T] or None: item b is a segment of lengths[b] frames padded to T (``Engine.set_lengths``); its
-        result on those frames is what it gives alone, and 0 beyond."""
+        result on those frames is what it gives alone, and 0 beyond.
+        ``prompt_lengths`` (B,) ints in [1, Lp] or None: item b's prompt is its first prompt_lengths[b] rows (``Engine.set_prompt_lengths``); its
+        result is what it gives alone with that prompt and no mask, whatever the rows past them hold."""
         import torch
         B, _, T = x.shape
         self._guard_before()
@@ -351,9 +355,9 @@ class Denoiser:
         s = torch.cuda.current_stream(x.device)
         mask = None if prompt_mask is None else prompt_mask.to(torch.uint8).contiguous()
         c32, p32, x32, t32 = content.float().contiguous(), prompt.float().contiguous(), x.float().contiguous(), t.float().contiguous()
-        self._self_check([(x32, t32)], c32, p32, mask, s, keep_fp32=bool(self.tail_fp32), lengths=lengths)
+        self._self_check([(x32, t32)], c32, p32, mask, s, keep_fp32=bool(self.tail_fp32), lengths=lengths, prompt_lengths=prompt_lengths)
         eng = self._fp32_engine() if self.serving_fp32 else self.engine
-        self._condition(eng, c32, p32, mask, s, lengths)
+        self._condition(eng, c32, p32, mask, s, lengths, prompt_lengths)
         out = torch.empty_like(x, dtype=torch.float32)
         first_attn = not self.serving_fp32 and not self._attn_checked and self.attn_fallback_limit is not None
         if first_attn:
@@ -361,7 +365,7 @@ class Denoiser:
         eng.forward(x32, t32, out, stream=s)
         if self.serving_fp32:
             return out
-        redone = self._guard_after(s, lambda: self.denoise(x, t, content, prompt, prompt_mask, lengths))
+        redone = self._guard_after(s, lambda: self.denoise(x, t, content, prompt, prompt_mask, lengths, prompt_lengths))
         if first_attn and redone is None:
             self._attn_check(1, s)                            # (after the guard's read-out: a switch drops the plan)
         return out if redone is None else redone
@@ -388,7 +392,7 @@ class Denoiser:
 
     def sample(self, content, prompt, prompt_mask=None, noise=None, solver: str = "unipc", steps: Optional[int] = None, order: int = 2,
                use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None,
-               **options):
+               prompt_lengths=None, **options):
         """content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool; ``noise`` (B,100,T) = x_T (drawn with
         torch.randn like model.py:635 if None).  Returns the sampled latent (B,100,T) fp32.
         ``solver``: ``unipc`` | ``dpmsolver++`` (``order`` 1 | 2 | 3, multistep) or the reference's discrete samplers ``ddim`` (``eta`` =
@@ -396,6 +400,7 @@ class Denoiser:
         ``seeds`` (B,) ints: the per-item noise streams of ddpm / ddim with eta > 0 (ns2vc_amd.noise; item b's noise depends on
         seeds[b] alone), drawn from ``generator`` after x_T if None, so ``generator=`` reproduces a run.
         ``lengths`` (B,) ints in [1, T] or None: per-item valid frames of a padded batch (see ``denoise``); x_T is zeroed past them.
+        ``prompt_lengths`` (B,) ints in [1, Lp] or None: per-item prompt frames of a batch whose prompts are padded to one Lp (see ``denoise``).
         ``tail_fp32`` overrides the instance's setting for this call (see the class docstring).
         ``options`` (keyword-only): the reference's ``UniPC.sample`` / ``DPM_Solver.sample`` keywords that ``schedule.build_table`` serves
         -- ``skip_type``, ``lower_order_final``, ``denoise_to_zero`` (one more evaluation), ``variant`` (UniPC), ``solver_type``
@@ -424,29 +429,31 @@ class Denoiser:
         mask = None if prompt_mask is None else prompt_mask.to(device=dev, dtype=torch.uint8).contiguous()
         c32, p32 = content.float().contiguous(), prompt.float().contiguous()
         if self.precision_check is not None and not self._precision_checked:
-            self._condition(self.engine, c32, p32, mask, s, lengths)
-            self._self_check(self._trajectory_points(x, use_graph, s), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths)
+            self._condition(self.engine, c32, p32, mask, s, lengths, prompt_lengths)
+            self._self_check(self._trajectory_points(x, use_graph, s), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths,
+                             prompt_lengths=prompt_lengths)
         tail = self._tail(solver, steps, order, n_tail, eta, **options)
         if tail is not None and stochastic:
             tail.set_seeds(seeds, stream=s)
         if self.serving_fp32:            # a failed precision check: the whole loop on the fp32 engine
-            self._condition(tail, c32, p32, mask, s, lengths)
+            self._condition(tail, c32, p32, mask, s, lengths, prompt_lengths)
             tail.sample(x, use_graph=use_graph, stream=s)
             return x
-        self._condition(self.engine, c32, p32, mask, s, lengths)
+        self._condition(self.engine, c32, p32, mask, s, lengths, prompt_lengths)
         if tail is not None:
-            self._condition(tail, c32, p32, mask, s, lengths)
+            self._condition(tail, c32, p32, mask, s, lengths, prompt_lengths)
         first_attn = not self._attn_checked and self.attn_fallback_limit is not None
         if first_attn:
             self.engine.attn_fallbacks(reset=True, stream=s)      # count this loop alone (the self-check's evaluations are behind us)
         self.engine.sample(x, use_graph=use_graph, stream=s, tail=tail, tail_steps=n_tail if tail is not None else 0)
         redone = self._guard_after(s, lambda: self.sample(content, prompt, prompt_mask, noise, solver, steps, order, use_graph,
-                                                          tail_fp32=tail_fp32, lengths=lengths, eta=eta, seeds=seeds, **options))
+                                                          tail_fp32=tail_fp32, lengths=lengths, eta=eta, seeds=seeds, prompt_lengths=prompt_lengths,
+                                                          **options))
         if first_attn and redone is None:
             self._attn_check(nfe - (n_tail if tail is not None else 0), s)      # (after the guard's read-out: a switch drops the plan)
         return x if redone is None else redone
 
-    def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, seeds=None, **kw):
+    def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, seeds=None, prompt_lengths=None, **kw):
         """Data-parallel: every rank receives the GLOBAL batch description, runs its contiguous slice and the
         finished latents are all-gathered (RCCL).  The noise (and ``seeds``, for ddpm / ddim with eta > 0: drawn for the global
         batch from ``generator`` if None) is drawn for the global batch and sliced, so an utterance's
@@ -466,7 +473,8 @@ class Denoiser:
             if seeds is None and kw.get("solver") in DISCRETE_SOLVERS:
                 seeds = draw_seeds(n, kw.get("generator"))
             sd = None if seeds is None else seeds[lo:hi]
-            local = self.sample(content[lo:hi], prompt[lo:hi], pm, noise[lo:hi], lengths=ln, seeds=sd, **kw)
+            pl = None if prompt_lengths is None else prompt_lengths[lo:hi]
+            local = self.sample(content[lo:hi], prompt[lo:hi], pm, noise[lo:hi], lengths=ln, seeds=sd, prompt_lengths=pl, **kw)
         return _dist.gather_latents(local, n)
 
 
@@ -478,7 +486,7 @@ class OverlappedPipeline:
         pre(k+1)   |   denoise(k)   |   post(k-1)
 
     ``pre_fn(item)`` runs on the front-end stream and returns a dict with torch CUDA tensors ``content`` (B,256,T),
-    ``prompt`` (B,Lp,256) and optionally ``prompt_mask`` (B,Lp) bool and ``noise`` (B,100,T); ``post_fn(latent, item)``
+    ``prompt`` (B,Lp,256) and optionally ``prompt_mask`` (B,Lp) bool, ``noise`` (B,100,T), ``lengths`` and ``prompt_lengths``; ``post_fn(latent, item)``
     runs on the back-end stream with the sampled latent (B,100,T) fp32.  Ordering is by events only -- the host never
     blocks until the end of ``run`` -- and the denoiser still replays one captured hipGraph per step on its own stream.
     """
@@ -550,7 +558,7 @@ class OverlappedPipeline:
                         if v.device != self.device:          # front end on another device: peer copy, ordered behind its event on the denoiser's stream
                             cond[k_] = v.to(self.device, non_blocking=True)
                 latent = self.denoiser.sample(cond["content"], cond["prompt"], cond.get("prompt_mask"), cond.get("noise"), lengths=cond.get("lengths"),
-                                              seeds=cond.get("seeds"), **self.kw)
+                                              seeds=cond.get("seeds"), prompt_lengths=cond.get("prompt_lengths"), **self.kw)
                 ev_den = torch.cuda.Event()
                 ev_den.record(self.s_den)
             with torch.cuda.device(self.post_device), torch.cuda.stream(self.s_post):

@@ -9,13 +9,20 @@ The reference's ``Svc.infer`` (``inference/infer_tool.py:189-206``) converts ONE
   embeddings (``ref_enc`` ``model.py:362`` and the UNet's ``add_embedding``, which take no mask) -- so padding either
   side changes a segment's result (measured: 0.2-0.5 relative on the latent for a prompt padded 40 -> 64).  Grouping
   EQUAL shapes keeps every segment's result what the reference's batch-1 call gives, to within the precision's rounding
-  noise.  A conversion job normally shares ONE reference clip over all its segments (``infer.py:92-122``: the segment loop sits inside the loop over reference clips), so Lp rarely
+  noise (``ragged_prompts`` below lifts this for the prompt side).  A conversion job normally shares ONE reference clip over all its segments (``infer.py:92-122``: the segment loop sits inside the loop over reference clips), so Lp rarely
   splits a group.
 * ``ragged=True``: segments are grouped by prompt length only, sorted longest first and packed into batches of at most
   ``max_batch``, each padded to its longest segment.  The denoiser runs the batch with per-item lengths
   (``Denoiser.sample(lengths=...)``, ``ns2vc_unet_set_lengths``): every GroupNorm statistic, self-attention softmax and
   convolution halo sees an item's own frames only, so a segment's result is what it gives alone, to the precision's rounding.
   Each segment's x_T is drawn as in the default mode, at its own length, then zero-padded.
+* ``ragged_prompts=True``: the prompt length no longer splits a group.  The reference clips of a batch are zero-padded to the batch's
+  longest, the front end runs with ``exact_prompt_lengths=True`` (the prompt encoder's conv halo and ``ref_enc``'s pooling see a clip's own
+  frames only) and the denoiser with per-item prompt lengths (``Denoiser.sample(prompt_lengths=...)``, ``ns2vc_unet_set_prompt_lengths``):
+  cross-attention AND the attention pooling of ``add_embedding`` take an item's own prompt frames, so a segment's result is what it gives
+  alone with its own clip, to the precision's rounding -- the padding that costs 0.2-0.5 relative above reaches nothing.  Grouping is then by
+  T only in the default mode, and one list of all segments, longest first, in ``ragged`` mode: a job with many reference clips still fills
+  its batches.
 * ``solver="ddim"`` (with ``eta``) / ``"ddpm"``: the reference's discrete samplers.  Their per-step noise comes from the segment's own
   seed (``noise.derive_seed(seed, index)``), so a segment's result does not depend on its group in either mode.
 * each group runs ``PreModel.infer`` -> ``Denoiser.sample`` -> ``decode_fn`` through ``OverlappedPipeline``: the
@@ -60,11 +67,13 @@ def segment_from_audio(content_encoder, wav16k: torch.Tensor, samples_at_target_
 
 class GroupedConverter:
     ragged = False      # the default mode (exact-shape groups), also for an instance that only plans (built without __init__)
+    ragged_prompts = False
 
     def __init__(self, pre_model: PreModel, denoiser: Denoiser, decode_fn: Optional[Callable] = None, max_batch: int = 32,
                  solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, ragged: bool = False, eta: float = 0.0,
                  masked_fuse: Optional[bool] = None, masked_attn: Optional[bool] = None,
-                 masked_rows: Optional[bool] = None, masked_ffn: Optional[bool] = None, masked_geglu: Optional[bool] = None, **options):
+                 masked_rows: Optional[bool] = None, masked_ffn: Optional[bool] = None, masked_geglu: Optional[bool] = None,
+                 ragged_prompts: bool = False, **options):
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
         if masked_fuse is not None and bool(masked_fuse) != denoiser.masked_fuse:     # the denoiser's engine option of that name (ragged batches only)
             denoiser.set_option("masked_fuse", bool(masked_fuse))
@@ -77,6 +86,7 @@ class GroupedConverter:
         if masked_geglu is not None and bool(masked_geglu) != denoiser.masked_geglu:
             denoiser.set_option("masked_geglu", bool(masked_geglu))
         self.max_batch, self.seed, self.ragged = max_batch, seed, ragged
+        self.ragged_prompts = bool(ragged_prompts)
         if solver == "ddpm" and steps == 30:      # (the constructor's default step count is the continuous solvers'; ddpm runs every timestep)
             steps = None
         table_options(options)           # the keyword-only sampler options of Denoiser.sample (skip_type, denoise_to_zero, ...)
@@ -88,11 +98,12 @@ class GroupedConverter:
 
     def plan(self, segments: Sequence[Segment]) -> List[List[int]]:
         """indices of `segments` grouped by (latent length, prompt length), groups of at most ``max_batch``, longest first;
-        ``ragged``: grouped by prompt length only, each group's segments longest first (stable), cut into batches of at most ``max_batch``"""
+        ``ragged``: grouped by prompt length only, each group's segments longest first (stable), cut into batches of at most ``max_batch``;
+        ``ragged_prompts``: the prompt length splits nothing -- by latent length only, or (``ragged``) all segments longest first"""
         if self.ragged:
             by_lp: Dict[int, List[int]] = defaultdict(list)
             for i, s in enumerate(segments):
-                by_lp[int(s.refer.shape[-1])].append(i)
+                by_lp[0 if self.ragged_prompts else int(s.refer.shape[-1])].append(i)
             groups = []
             for lp in sorted(by_lp, reverse=True):
                 idx = sorted(by_lp[lp], key=lambda i: -int(segments[i].content.shape[-1]))
@@ -100,7 +111,7 @@ class GroupedConverter:
             return groups
         by_len: Dict[tuple, List[int]] = defaultdict(list)
         for i, s in enumerate(segments):
-            by_len[(int(s.content.shape[-1]), int(s.refer.shape[-1]))].append(i)
+            by_len[(int(s.content.shape[-1]), 0 if self.ragged_prompts else int(s.refer.shape[-1]))].append(i)
         groups = []
         for key in sorted(by_len, reverse=True):
             idx = by_len[key]
@@ -112,15 +123,28 @@ class GroupedConverter:
         dev = next(self.pre.parameters()).device
         groups = self.plan(segments)
 
+        def padded_refer(idx):
+            """ragged_prompts: the group's reference clips zero-padded to its longest, and their own lengths"""
+            plens = [int(segments[i].refer.shape[-1]) for i in idx]
+            refer = torch.zeros((len(idx), segments[idx[0]].refer.shape[0], max(plens)), dtype=torch.float32, device=dev)
+            for b, i in enumerate(idx):
+                refer[b, :, :plens[b]] = segments[i].refer.to(dev, torch.float32)
+            return refer, plens
+
         def pre_fn(idx):
             if self.ragged:
                 return ragged_pre(idx)
             T, Lp = int(segments[idx[0]].content.shape[-1]), int(segments[idx[0]].refer.shape[-1])
             c = torch.stack([segments[i].content.to(dev, torch.float32) for i in idx])
+            noise = torch.stack([torch.randn((self.den.cfg.latent_channels, T), generator=torch.Generator().manual_seed(self.seed + i)) for i in idx]).to(dev)
+            if self.ragged_prompts:
+                refer, plens = padded_refer(idx)
+                content, prompt, _ = self.pre.infer(c, refer, torch.full((len(idx),), T, device=dev), torch.tensor(plens, device=dev),
+                                                    exact_prompt_lengths=True)
+                return {"content": content, "prompt": prompt, "prompt_mask": None, "noise": noise, "seeds": self._seeds(idx), "prompt_lengths": plens}
             refer = torch.stack([segments[i].refer.to(dev, torch.float32) for i in idx])
             content, prompt, mask = self.pre.infer(c, refer, torch.full((len(idx),), T, device=dev), torch.full((len(idx),), Lp, device=dev))
             # x_T per SEGMENT (seeded by its position in the input), so a segment's result does not depend on its group
-            noise = torch.stack([torch.randn((self.den.cfg.latent_channels, T), generator=torch.Generator().manual_seed(self.seed + i)) for i in idx]).to(dev)
             return {"content": content, "prompt": prompt, "prompt_mask": mask, "noise": noise, "seeds": self._seeds(idx)}
 
         def ragged_pre(idx):
@@ -132,6 +156,12 @@ class GroupedConverter:
                 c[b, :, :lens[b]] = segments[i].content.to(dev, torch.float32)
                 # x_T per SEGMENT at its own length (as in the default mode), zero-padded: its result does not depend on its batch
                 noise[b, :, :lens[b]] = torch.randn((self.den.cfg.latent_channels, lens[b]), generator=torch.Generator().manual_seed(self.seed + i))
+            if self.ragged_prompts:
+                refer, plens = padded_refer(idx)
+                content, prompt, _ = self.pre.infer(c, refer, torch.tensor(lens, device=dev), torch.tensor(plens, device=dev), exact_lengths=True,
+                                                    exact_prompt_lengths=True)
+                return {"content": content, "prompt": prompt, "prompt_mask": None, "noise": noise.to(dev), "lengths": lens, "seeds": self._seeds(idx),
+                        "prompt_lengths": plens}
             refer = torch.stack([segments[i].refer.to(dev, torch.float32) for i in idx])
             content, prompt, mask = self.pre.infer(c, refer, torch.tensor(lens, device=dev), torch.full((len(idx),), Lp, device=dev),
                                                    exact_lengths=True)

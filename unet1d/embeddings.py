@@ -21,16 +21,27 @@ class AttentionPooling(nn.Module):
         self.num_heads = num_heads
         self.dim_per_head = embed_dim // num_heads
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, lengths: torch.Tensor = None) -> torch.Tensor:
+        """``lengths`` (B,) or None: item b pools over its first lengths[b] frames only (its class token is their mean, the frames
+        past them are no keys) -- what it gives alone at L = lengths[b].  None: the reference's arithmetic over all L frames."""
         B, L, W = x.shape
         H, d = self.num_heads, self.dim_per_head
-        cls = x.mean(dim=1, keepdim=True) + self.positional_embedding.to(x.dtype)
+        if lengths is None:
+            cls = x.mean(dim=1, keepdim=True) + self.positional_embedding.to(x.dtype)
+        else:
+            keep = torch.arange(L, device=x.device)[None, :] < lengths.to(x.device)[:, None]                  # (B, L)
+            x = torch.where(keep[:, :, None], x, torch.zeros((), dtype=x.dtype, device=x.device))             # (NaN-safe: padded frames never enter a sum)
+            cls = x.sum(dim=1, keepdim=True) / lengths.to(x.device, x.dtype)[:, None, None] + self.positional_embedding.to(x.dtype)
         seq = torch.cat([cls, x], dim=1)
         q = self.q_proj(cls).view(B, 1, H, d).transpose(1, 2)
         k = self.k_proj(seq).view(B, L + 1, H, d).transpose(1, 2)
         v = self.v_proj(seq).view(B, L + 1, H, d).transpose(1, 2)
         # softmax(q k^T / sqrt(d)) v with the single class-token query
-        w = torch.softmax((q @ k.transpose(-1, -2)).float() / d ** 0.5, dim=-1).to(v.dtype)
+        sc = (q @ k.transpose(-1, -2)).float() / d ** 0.5
+        if lengths is not None:
+            key_keep = torch.cat([torch.ones((B, 1), dtype=torch.bool, device=x.device), keep], dim=1)       # the class token, then the item's own frames
+            sc = sc.masked_fill(~key_keep[:, None, None, :], float("-inf"))
+        w = torch.softmax(sc, dim=-1).to(v.dtype)
         return (w @ v).transpose(1, 2).reshape(B, W)
 
 
@@ -42,5 +53,7 @@ class TextTimeEmbedding(nn.Module):
         self.proj = nn.Linear(encoder_dim, time_embed_dim)
         self.norm2 = nn.LayerNorm(time_embed_dim)
 
-    def forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
-        return self.norm2(self.proj(self.pool(self.norm1(hidden_states))))
+    def forward(self, hidden_states: torch.Tensor, lengths: torch.Tensor = None) -> torch.Tensor:
+        if lengths is None:
+            return self.norm2(self.proj(self.pool(self.norm1(hidden_states))))
+        return self.norm2(self.proj(self.pool(self.norm1(hidden_states), lengths)))
