@@ -556,6 +556,7 @@ int ns2vc_debug_poison(unsigned pattern, int lds_bytes, void* stream); /* test t
 /* ABI v6 (diagnostic): where the 256-thread blocks of an n_blocks launch on `stream` ran: out_host[2 i] = XCC id (HW_REG_XCC_ID),
  * out_host[2 i + 1] = HW_REG_HW_ID of block i; `spin` > 0 keeps blocks resident for a while so the grid spreads over the CUs the stream may use. */
 int ns2vc_debug_placement(void* stream, int n_blocks, int spin, uint32_t* out_host);
+int ns2vc_debug_kernel_table(int family, int* rows, int* unready); /* tests: the instantiation table of one kernel template (0 gemm2, 1 gemm4, 2 conv3ts, 3 attn, 4 ffn, 5 geglu, 6 rowchain). *rows = its row count (no device needed).  With unready != NULL the family's attribute setup runs, and *unready = the rows whose function reports less dynamic LDS than the row needs, or that need more than 160 KB */
 int ns2vc_debug_set_gemm_tile(int bm, int bn, int stages); /* force the GEMM tile: stages 2..4 = 4-wave kernel ring depth, 12|13 = 8-wave K-split kernel ring 2|3; 0,0,0 = heuristic; (-1,0,0) = heuristic without the loader/consumer tiles, (-2,0,0) = with them again; ABI v6: (128, 64|128, 54|58) = the tap-sharing conv kernel with 4|8 loader waves (k = 3 launches only), (-3,0,0) = never that kernel, (-4,0,nl) = heuristic with it again, nl loader waves (0 = default) */
 int ns2vc_k_attention(const ns2vc_attn_args* a, int head_dim, int precision, void* stream);
 /* GroupNorm (+ optional resnet time scale/shift, + optional SiLU) of a (possibly concatenated) fp32 tensor,

@@ -1,6 +1,7 @@
 // The part of the C ABI that takes no engine handle: device, stream, event and memcpy helpers, the ns2vc_pack_* weight packers, the
 // single-kernel launchers ns2vc_k_*, the ns2vc_debug_* hooks and the operand conversions (kernel tests and tools/ drive the kernels through these).
 #include "engine_internal.h"
+#include "kernel_table.h"
 
 #include <algorithm>
 #include <cstring>
@@ -173,6 +174,25 @@ int ns2vc_debug_placement(void* stream, int n_blocks, int spin, uint32_t* out_ho
   return 0;
 }
 int ns2vc_debug_set_gemm_tile(int bm, int bn, int stages) { set_forced_gemm_tile(bm, bn, stages); return 0; }
+int ns2vc_debug_kernel_table(int family, int* rows, int* unready) {
+  static const struct { const KernelTable& (*table)(); hipError_t (*init)(); } fam[] = {
+      {gemm2_kernel_table, init_gemm_attributes}, {gemm4_kernel_table, init_gemm_attributes}, {conv3ts_kernel_table, init_convts_attributes},
+      {attn_kernel_table, init_attn_attributes},  {ffn_kernel_table, init_ffn_attributes},    {geglu_kernel_table, init_geglu_attributes},
+      {rowchain_kernel_table, init_rowchain_attributes}};
+  constexpr int NF = (int)(sizeof(fam) / sizeof(fam[0]));
+  if (family < 0 || family >= NF || !rows) return fail("kernel table: family 0 .. %d, rows not NULL", NF - 1);
+  const KernelTable& t = fam[family].table();
+  *rows = t.n;
+  if (!unready) return 0;
+  if (init_attributes(fam[family].init)) return 1;
+  *unready = 0;
+  for (int i = 0; i < t.n; ++i) {
+    hipFuncAttributes fa;
+    HIPCHK(hipFuncGetAttributes(&fa, t.rows[i].fn));
+    if (fa.maxDynamicSharedSizeBytes < (int)t.rows[i].lds || t.rows[i].lds > 160 * 1024) ++*unready;
+  }
+  return 0;
+}
 int ns2vc_k_gemm(const ns2vc_gemm_args* a, int precision, void* stream) {
   if (!a) return fail("null args");
   hipError_t e = launch_gemm(*a, precision, (hipStream_t)stream);

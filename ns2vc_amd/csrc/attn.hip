@@ -19,6 +19,7 @@
 // q/k/v/out are operand-typed tensors (bf16, or fp32 in parity mode): no conversions while staging.
 #include "common.h"
 #include "mma.h"
+#include "kernel_table.h"
 #include <cstdlib>
 
 namespace ns2vc {
@@ -504,103 +505,55 @@ template <typename TM, int HD, int KEYS> static constexpr size_t attn_lds() {
   return 2 * (size_t)(KEYS * (HD * SZ + 48) + HDX * (KEYS * SZ + 16));
 }
 
+// The compiled set, one row per instantiation: every operand type and head width with 64-key tiles, dense and masked; for the 16-bit
+// types the fp8 PV form (dense only) and, at hd 16 / 32, the 128-key tiles.
 // 64-key tiles everywhere.  128-key tiles (half the per-tile bookkeeping, barriers and waits; round-1 review item) exist for
 // the narrow heads of the 16-bit precisions (hd 16 / 32) behind the tuning hook, and LOSE: same-box 3.93 (64) vs 3.98 ms/step
 // (128), attention 0.68 vs 0.73 ms -- 64 more score registers and twice the LDS per workgroup cost more occupancy than the
 // bookkeeping saves in a VALU-bound loop.
-template <typename TM, int HD> static constexpr bool attn_has128() { return sizeof(TM) == 2 && HD <= 32; }
+// (the fp8 variant needs less than attn_lds: its V^T rows are half as long)
+#define NS2VC_ATTN_ROW(TM, PREC, HD, KEYS, FP8, MK) \
+  {kernel_key(PREC, HD, KEYS, FP8, MK), reinterpret_cast<const void*>(attn_kernel<TM, HD, KEYS, FP8, MK>), (uint32_t)attn_lds<TM, HD, KEYS>(), 256}
+#define NS2VC_ATTN_ROW2(TM, PREC, HD, KEYS) NS2VC_ATTN_ROW(TM, PREC, HD, KEYS, false, false), NS2VC_ATTN_ROW(TM, PREC, HD, KEYS, false, true)
+#define NS2VC_ATTN_ROWS16(TM, PREC)                                                                                            \
+  NS2VC_ATTN_ROW2(TM, PREC, 16, 64), NS2VC_ATTN_ROW2(TM, PREC, 16, 128), NS2VC_ATTN_ROW(TM, PREC, 16, 64, true, false),         \
+  NS2VC_ATTN_ROW2(TM, PREC, 32, 64), NS2VC_ATTN_ROW2(TM, PREC, 32, 128), NS2VC_ATTN_ROW(TM, PREC, 32, 64, true, false),         \
+  NS2VC_ATTN_ROW2(TM, PREC, 48, 64), NS2VC_ATTN_ROW(TM, PREC, 48, 64, true, false),                                             \
+  NS2VC_ATTN_ROW2(TM, PREC, 64, 64), NS2VC_ATTN_ROW(TM, PREC, 64, 64, true, false)
+static const KernelRow attn_rows[] = {
+  NS2VC_ATTN_ROW2(float, PREC_F32, 16, 64), NS2VC_ATTN_ROW2(float, PREC_F32, 32, 64), NS2VC_ATTN_ROW2(float, PREC_F32, 48, 64), NS2VC_ATTN_ROW2(float, PREC_F32, 64, 64),
+  NS2VC_ATTN_ROWS16(bf16_t, PREC_BF16),
+  NS2VC_ATTN_ROWS16(f16_t, PREC_F16),
+};
+#undef NS2VC_ATTN_ROWS16
+#undef NS2VC_ATTN_ROW2
+#undef NS2VC_ATTN_ROW
+static const KernelTable k_attn_table(attn_rows);      // (static: host data, no copy in the code object)
+const KernelTable& attn_kernel_table() { return k_attn_table; }
+
 static int g_force_keys = 0;   // test / tuning hook (ns2vc_debug_set_attn_keys): 128 selects the 128-key kernels
 void set_forced_attn_keys(int keys) { g_force_keys = keys; }
 void set_attn_optimistic(int on) { const int v = on ? 0 : 1; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_exact_only), &v, sizeof(v)); }
 
-template <typename TM, int HD, int KEYS> static hipError_t launch_hdk(const AttnArgs& a, hipStream_t s) {
-  dim3 grid(((a.Lq + 127) / 128) * a.H * a.B);
-  const size_t lds = attn_lds<TM, HD, KEYS>();          // (the fp8 variant needs less: its V^T rows are half as long)
-  if (a.q_lens || a.k_lens) hipLaunchKernelGGL((attn_kernel<TM, HD, KEYS, false, true>), grid, dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((attn_kernel<TM, HD, KEYS, false>), grid, dim3(256), lds, s, a);
-  return hipGetLastError();
-}
-template <typename TM, int HD> static hipError_t launch_hd(const AttnArgs& a, hipStream_t s) {
-  if (a.pv_fp8 && (a.q_lens || a.k_lens)) return hipErrorInvalidValue;      // (the fp8 PV form has no masked instantiation: refused, never run unmasked)
-  if constexpr (sizeof(TM) == 2) {
-    if (a.pv_fp8) {
-      dim3 grid(((a.Lq + 127) / 128) * a.H * a.B);
-      const size_t lds = attn_lds<TM, HD, 64>();
-      hipLaunchKernelGGL((attn_kernel<TM, HD, 64, true>), grid, dim3(256), lds, s, a);
-      return hipGetLastError();
-    }
-  } else if (a.pv_fp8) return hipErrorInvalidValue;
-  if constexpr (attn_has128<TM, HD>()) {
-    if (g_force_keys == 128) return launch_hdk<TM, HD, 128>(a, s);
-  }
-  return launch_hdk<TM, HD, 64>(a, s);
-}
-
-template <typename TM> static hipError_t launch_tm(const AttnArgs& a, int hd, hipStream_t s) {
-  switch (hd) {
-    case 16: return launch_hd<TM, 16>(a, s);
-    case 32: return launch_hd<TM, 32>(a, s);
-    case 48: return launch_hd<TM, 48>(a, s);
-    case 64: return launch_hd<TM, 64>(a, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-template <typename TM, int HD> static hipError_t set_attr() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<TM, HD, 64, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)attn_lds<TM, HD, 64>());
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<TM, HD, 64, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)attn_lds<TM, HD, 64>());
-  if constexpr (attn_has128<TM, HD>()) {
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<TM, HD, 128, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)attn_lds<TM, HD, 128>());
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<TM, HD, 128, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)attn_lds<TM, HD, 128>());
-  }
-  if constexpr (sizeof(TM) == 2) {
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<TM, HD, 64, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)attn_lds<TM, HD, 64>());
-  }
-  return e;
-}
-template <typename TM> static hipError_t set_attr_tm() {
-  hipError_t e;
-  if ((e = set_attr<TM, 16>()) != hipSuccess) return e;
-  if ((e = set_attr<TM, 32>()) != hipSuccess) return e;
-  if ((e = set_attr<TM, 48>()) != hipSuccess) return e;
-  return set_attr<TM, 64>();
-}
-hipError_t init_attn_attributes() {
-  hipError_t e = set_attr_tm<float>();
-  if (e == hipSuccess) e = set_attr_tm<bf16_t>();
-  if (e == hipSuccess) e = set_attr_tm<f16_t>();
-  return e;
-}
+hipError_t init_attn_attributes() { return set_lds_all(k_attn_table); }
 
 // would launch_attention run this launch on a masked instantiation, were AttnArgs.q_lens / k_lens set?  (every operand type, head width and key tile;
-// not the fp8 PV form)  The planner asks per launch: an attention refused here keeps its key-bias row and its mask_rows launch.
+// not the fp8 PV form: the table says)  The planner asks per launch: an attention refused here keeps its key-bias row and its mask_rows launch.
 bool attention_masks_rows(const AttnArgs& a, int head_dim, int prec) {
-  if (a.pv_fp8) return false;
-  if (head_dim != 16 && head_dim != 32 && head_dim != 48 && head_dim != 64) return false;
-  return prec == PREC_BF16 || prec == PREC_F16 || prec == PREC_F32;
+  return find(k_attn_table, kernel_key(prec, head_dim, 64, a.pv_fp8 != 0, true)) != nullptr;
 }
 
 hipError_t launch_attention(const AttnArgs& a, int head_dim, int prec, hipStream_t s) {
   const int al = prec == PREC_F32 ? 3 : 7;       // rows must start 16-B aligned
   if (!a.q || !a.k || !a.v || !a.out) return hipErrorInvalidValue;
-  if ((a.q_lens || a.k_lens) && !attention_masks_rows(a, head_dim, prec)) return hipErrorInvalidValue;     // refused, never run unmasked
+  const bool masked = a.q_lens || a.k_lens, fp8 = a.pv_fp8 != 0;
+  if (masked && !attention_masks_rows(a, head_dim, prec)) return hipErrorInvalidValue;     // refused, never run unmasked
   if (a.Lq <= 0 || a.Lk <= 0 || (a.ldq & al) || (a.ldk & al) || (a.ldv & al) || (a.ldo & al)) return hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(a.out) & 15) return hipErrorInvalidValue;      // (results leave in 16-byte pieces)
-  switch (prec) {
-    case PREC_BF16: return launch_tm<bf16_t>(a, head_dim, s);
-    case PREC_F16: return launch_tm<f16_t>(a, head_dim, s);
-    case PREC_F32: return launch_tm<float>(a, head_dim, s);
-    default: return hipErrorInvalidValue;
-  }
+  const int keys = !fp8 && g_force_keys == 128 && find(k_attn_table, kernel_key(prec, head_dim, 128, false, masked)) ? 128 : 64;
+  const KernelRow* row = find(k_attn_table, kernel_key(prec, head_dim, keys, fp8, masked));      // (no row: fp8 PV at fp32, or masked)
+  if (!row) return hipErrorInvalidValue;
+  return launch(*row, dim3(((a.Lq + 127) / 128) * a.H * a.B), s, a);      // (const AttnArgs)
 }
 
 }  // namespace ns2vc

@@ -35,6 +35,7 @@
 #include "mma.h"
 #include "gnpro.h"
 #include "epilogue.h"
+#include "kernel_table.h"
 #include <type_traits>
 #include <vector>
 #include <cstring>
@@ -690,54 +691,48 @@ int convts_bn_for(const GemmArgs& g, int bn128_min) {
 int convts_default_bn(const GemmArgs& g) { return (g.conv_bn == 64 || (g.conv_bn == 128 && g.N % 128 == 0)) ? g.conv_bn : convts_bn_for(g, g_bn128_min); }
 int convts_row_blocks(const GemmArgs& g) { return (int)(((long long)g.B * (g.Tin + 1) + TS_BMO - 1) / TS_BMO); }
 
-template <typename TM, int BN, int NL, bool KS> static hipError_t launch_ts_cfg(const GemmArgs& g, hipStream_t s) {
-  const int nbm = convts_row_blocks(g), nbn = g.N / BN;
-  int nb = nbm * nbn;
-  if (g.gnp_x && g.gnp_sync && nbn > 1) nb = 8 * ((nbm + 7) / 8) * nbn;      // cooperative prologue: row blocks per XCD, padded
-  // GroupNorm in front: inside the loop (GnInloop: eight non-consumer waves = four DMA + four producer waves, chunk-granular loop, plain consumer layout) unless
-  // the caller asks for the materialising prologue (algo == 2)
-  constexpr bool HAS_INLOOP = NS2VC_TS_CHUNK && NL == 8 && !KS;
-  if (g.lens) {                                                   // per-item valid lengths: the masked instantiations (eight loaders, plain consumer layout, materialising prologue)
-    constexpr bool HAS_MASKED = NL == 8 && !KS;
-    if constexpr (HAS_MASKED) {
-      if (g.sol_coef) return hipErrorInvalidValue;
-      if (g.gnp_x && g.gnp_pair) {
-        if constexpr (!std::is_same<TM, float>::value) hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, TS_GN_PAIR | TS_MASKED, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
-        else return hipErrorInvalidValue;
-      }
-      else if (g.gnp_x) hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, TS_GN_PRO | TS_MASKED, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
-      else hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, TS_GN_NONE | TS_MASKED, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
-    } else return hipErrorInvalidValue;
-  }
-  else if (g.sol_coef) {                                               // the solver-update epilogue: its own instantiations (one 128-column tile, eight loaders)
-    constexpr bool HAS_SOL = BN == 128 && NL == 8 && !KS;
-    if constexpr (HAS_SOL) {
-      if (g.gnp_x && g.gnp_pair) {
-        if constexpr (!std::is_same<TM, float>::value) hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, 3, KS, true>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
-        else return hipErrorInvalidValue;
-      }
-      else if (g.gnp_x) hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, 1, KS, true>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);     // (always the materialising prologue)
-      else hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, 0, KS, true>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
-    } else return hipErrorInvalidValue;
-  }
-  else if (g.gnp_x && g.gnp_pair) {                                    // a hi + lo operand pair is something the materialising prologue writes (its own instantiation)
-    if constexpr (!std::is_same<TM, float>::value && NL == 8 && !KS) hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, 3, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
-    else return hipErrorInvalidValue;
-  }
-  else if (g.gnp_x && HAS_INLOOP && g.algo != 2) {
-    if constexpr (HAS_INLOOP) hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, 2, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
-  }
-  else if (g.gnp_x) hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, 1, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
-  else hipLaunchKernelGGL((conv3ts_kernel<TM, BN, NL, 0, KS>), dim3(nb), dim3(64 * (NL + 4)), ts_lds_bytes(BN), s, g);
-  return hipGetLastError();
-}
-template <typename TM> static hipError_t launch_ts_typed(const GemmArgs& g, int bn, int nl, int ks, hipStream_t s) {
-  if (bn == 64 && nl == 4) return ks ? launch_ts_cfg<TM, 64, 4, true>(g, s) : launch_ts_cfg<TM, 64, 4, false>(g, s);
-  if (bn == 64 && nl == 8) return ks ? launch_ts_cfg<TM, 64, 8, true>(g, s) : launch_ts_cfg<TM, 64, 8, false>(g, s);
-  if (bn == 128 && nl == 4) return launch_ts_cfg<TM, 128, 4, false>(g, s);
-  if (bn == 128 && nl == 8) return launch_ts_cfg<TM, 128, 8, false>(g, s);
-  return hipErrorInvalidValue;
-}
+// The compiled set, one row per instantiation.  Per operand type: both column tiles x 4 | 8 loader waves, without GroupNorm and with the materialising
+// prologue; the K-split consumer layout of the 64-column tile for the same; at eight loaders and the plain layout also the in-loop GroupNorm (chunk-granular
+// builds), the solver-update epilogue (128 columns), the hi + lo pair prologue (16-bit types) and the masked form of every GNPF but the in-loop one.
+// The rows stand in the order in which the code object has always laid these kernels out (row order is layout order): a row added at the end leaves
+// every other kernel where it is.  P16 wraps the rows of the hi + lo pair prologue (16-bit operand types only), NS2VC_TS_IF_CHUNK those of the in-loop GroupNorm.
+#define NS2VC_TS_ROW(TM, PREC, BN, NL, GNPF, KS, SOL) \
+  {kernel_key(PREC, BN, NL, GNPF, KS, SOL), reinterpret_cast<const void*>(conv3ts_kernel<TM, BN, NL, GNPF, KS, SOL>), (uint32_t)ts_lds_bytes(BN), 64 * (NL + 4)},
+#define NS2VC_TS_YES(row) row
+#define NS2VC_TS_NO(row)
+#if NS2VC_TS_CHUNK
+#define NS2VC_TS_IF_CHUNK NS2VC_TS_YES
+#else
+#define NS2VC_TS_IF_CHUNK NS2VC_TS_NO
+#endif
+#define NS2VC_TS_ROWS(TM, PREC, P16)                                                                                                   \
+  NS2VC_TS_ROW(TM, PREC, 64, 4, TS_GN_PRO, true, false) NS2VC_TS_ROW(TM, PREC, 64, 4, TS_GN_NONE, true, false)                          \
+  NS2VC_TS_ROW(TM, PREC, 64, 4, TS_GN_PRO, false, false) NS2VC_TS_ROW(TM, PREC, 64, 4, TS_GN_NONE, false, false)                        \
+  NS2VC_TS_ROW(TM, PREC, 64, 8, TS_GN_PRO, true, false) NS2VC_TS_ROW(TM, PREC, 64, 8, TS_GN_NONE, true, false)                          \
+  P16(NS2VC_TS_ROW(TM, PREC, 64, 8, TS_GN_PAIR | TS_MASKED, false, false))                                                             \
+  NS2VC_TS_ROW(TM, PREC, 64, 8, TS_GN_PRO | TS_MASKED, false, false) NS2VC_TS_ROW(TM, PREC, 64, 8, TS_GN_NONE | TS_MASKED, false, false) \
+  P16(NS2VC_TS_ROW(TM, PREC, 64, 8, TS_GN_PAIR, false, false)) NS2VC_TS_IF_CHUNK(NS2VC_TS_ROW(TM, PREC, 64, 8, TS_GN_INLOOP, false, false))         \
+  NS2VC_TS_ROW(TM, PREC, 64, 8, TS_GN_PRO, false, false) NS2VC_TS_ROW(TM, PREC, 64, 8, TS_GN_NONE, false, false)                        \
+  NS2VC_TS_ROW(TM, PREC, 128, 4, TS_GN_PRO, false, false) NS2VC_TS_ROW(TM, PREC, 128, 4, TS_GN_NONE, false, false)                      \
+  P16(NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_PAIR | TS_MASKED, false, false))                                                            \
+  NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_PRO | TS_MASKED, false, false) NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_NONE | TS_MASKED, false, false) \
+  P16(NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_PAIR, false, true))                                                                         \
+  NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_PRO, false, true) NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_NONE, false, true)                        \
+  P16(NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_PAIR, false, false)) NS2VC_TS_IF_CHUNK(NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_INLOOP, false, false))       \
+  NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_PRO, false, false) NS2VC_TS_ROW(TM, PREC, 128, 8, TS_GN_NONE, false, false)
+static const KernelRow ts_rows[] = {
+  NS2VC_TS_ROWS(bf16_t, PREC_BF16, NS2VC_TS_YES)
+  NS2VC_TS_ROWS(f16_t, PREC_F16, NS2VC_TS_YES)
+  NS2VC_TS_ROWS(float, PREC_F32, NS2VC_TS_NO)
+};
+#undef NS2VC_TS_ROWS
+#undef NS2VC_TS_IF_CHUNK
+#undef NS2VC_TS_NO
+#undef NS2VC_TS_YES
+#undef NS2VC_TS_ROW
+static const KernelTable k_conv3ts_table(ts_rows);      // (static: host data, no copy in the code object)
+const KernelTable& conv3ts_kernel_table() { return k_conv3ts_table; }
+
 // bn 64 | 128 (0: heuristic), nl 4 | 8 loader waves (0: default), ks: the K-split consumer layout of the 64-column tile (-1: default)
 hipError_t launch_convts(const GemmArgs& g, int prec, int bn, int nl, int ks, hipStream_t s) {
   if (!convts_eligible(g, prec)) return hipErrorInvalidValue;
@@ -747,54 +742,21 @@ hipError_t launch_convts(const GemmArgs& g, int prec, int bn, int nl, int ks, hi
   if (g.sol_coef) { bn = 128; nl = 8; ks = 0; }                   // (the one configuration the solver epilogue is instantiated for)
   if (g.lens) { nl = 8; ks = 0; }                                 // (... and the masked epilogue / prologue: either column tile)
   if (g.N % bn) return hipErrorInvalidValue;
-  switch (prec) {
-    case PREC_BF16: return launch_ts_typed<bf16_t>(g, bn, nl, ks, s);
-    case PREC_F16: return launch_ts_typed<f16_t>(g, bn, nl, ks, s);
-    case PREC_F32: return launch_ts_typed<float>(g, bn, nl, ks, s);
-    default: return hipErrorInvalidValue;
-  }
+  // GroupNorm in front: inside the loop (GnInloop: eight non-consumer waves = four DMA + four producer waves, chunk-granular loop, plain consumer layout) where
+  // that instantiation exists, unless the caller asks for the materialising prologue (algo == 2); a hi + lo operand pair is something the materialising
+  // prologue writes.  Per-item valid lengths reach the masked rows only, the solver-update epilogue its own: a key with no row is refused.
+  const bool kspl = bn == 64 && ks, sol = g.sol_coef != nullptr;
+  int gnpf = g.gnp_x ? (g.gnp_pair ? TS_GN_PAIR : TS_GN_PRO) : TS_GN_NONE;
+  if (g.lens) gnpf |= TS_MASKED;
+  else if (gnpf == TS_GN_PRO && !sol && g.algo != 2 && find(k_conv3ts_table, kernel_key(prec, bn, nl, TS_GN_INLOOP, kspl, false))) gnpf = TS_GN_INLOOP;
+  const KernelRow* row = find(k_conv3ts_table, kernel_key(prec, bn, nl, gnpf, kspl, sol));
+  if (!row) return hipErrorInvalidValue;
+  const int nbm = convts_row_blocks(g), nbn = g.N / bn;
+  int nb = nbm * nbn;
+  if (g.gnp_x && g.gnp_sync && nbn > 1) nb = 8 * ((nbm + 7) / 8) * nbn;      // cooperative prologue: row blocks per XCD, padded
+  return launch(*row, dim3(nb), s, g);      // (const GemmArgs)
 }
 
-template <typename K> static hipError_t ts_set_lds(K kern, size_t bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-template <typename TM> static hipError_t ts_init_typed() {
-  hipError_t e = hipSuccess;
-#define NS2VC_TS_SET(BN_, NL_)                                                                      \
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, BN_, NL_, 0>, ts_lds_bytes(BN_));     \
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, BN_, NL_, 1>, ts_lds_bytes(BN_))
-  NS2VC_TS_SET(64, 4); NS2VC_TS_SET(128, 4); NS2VC_TS_SET(64, 8); NS2VC_TS_SET(128, 8);
-#if NS2VC_TS_CHUNK
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, 2>, ts_lds_bytes(64));
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, 2>, ts_lds_bytes(128));
-#endif
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, 0, false, true>, ts_lds_bytes(128));
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, 1, false, true>, ts_lds_bytes(128));
-  if constexpr (!std::is_same<TM, float>::value) {
-    if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, 3, false, true>, ts_lds_bytes(128));
-    if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, 3>, ts_lds_bytes(64));
-    if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, 3>, ts_lds_bytes(128));
-  }
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, TS_GN_NONE | TS_MASKED>, ts_lds_bytes(64));
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, TS_GN_PRO | TS_MASKED>, ts_lds_bytes(64));
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, TS_GN_NONE | TS_MASKED>, ts_lds_bytes(128));
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, TS_GN_PRO | TS_MASKED>, ts_lds_bytes(128));
-  if constexpr (!std::is_same<TM, float>::value) {
-    if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, TS_GN_PAIR | TS_MASKED>, ts_lds_bytes(64));
-    if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 128, 8, TS_GN_PAIR | TS_MASKED>, ts_lds_bytes(128));
-  }
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 4, 0, true>, ts_lds_bytes(64));
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 4, 1, true>, ts_lds_bytes(64));
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, 0, true>, ts_lds_bytes(64));
-  if (e == hipSuccess) e = ts_set_lds(conv3ts_kernel<TM, 64, 8, 1, true>, ts_lds_bytes(64));
-#undef NS2VC_TS_SET
-  return e;
-}
-hipError_t init_convts_attributes() {
-  hipError_t e = ts_init_typed<float>();
-  if (e == hipSuccess) e = ts_init_typed<bf16_t>();
-  if (e == hipSuccess) e = ts_init_typed<f16_t>();
-  return e;
-}
+hipError_t init_convts_attributes() { return set_lds_all(k_conv3ts_table); }
 
 }  // namespace ns2vc

@@ -26,6 +26,7 @@
 #include "common.h"
 #include <type_traits>
 #include "mma.h"
+#include "kernel_table.h"
 #include <vector>
 
 namespace ns2vc {
@@ -750,50 +751,6 @@ hipError_t pack_ffn_stream(const float* w1p, const float* w2f, const float* w0, 
 
 bool ffn_eligible(int dim, int T, int prec) { return (dim == 128 || dim == 256) && T >= 64 && (prec == PREC_BF16 || prec == PREC_F16); }
 
-template <typename TM, int D> static hipError_t launch_ffn_t(const FfnArgs& a, hipStream_t s) {
-  if (a.lens) {       // the masked twins (launch_ffn has asked ffn_masks_rows: never with att_q)
-    const size_t lds = a.pre_a ? FfnGeom<D, true>::LDS : FfnGeom<D, false>::LDS;
-    if (a.pre_a) hipLaunchKernelGGL((ffn_kernel<TM, D, true, false, true>), dim3((a.M + 63) / 64), dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((ffn_kernel<TM, D, false, false, true>), dim3((a.M + 63) / 64), dim3(512), lds, s, a);
-  } else if (a.att_q) {
-    const size_t lds = FfnGeom<D, true>::LDS;
-    hipLaunchKernelGGL((ffn_kernel<TM, D, true, true>), dim3(a.B * ((a.T + 63) / 64)), dim3(512), lds, s, a);
-  } else if (a.pre_a) {
-    const size_t lds = FfnGeom<D, true>::LDS;
-    hipLaunchKernelGGL((ffn_kernel<TM, D, true>), dim3((a.M + 63) / 64), dim3(512), lds, s, a);
-  } else {
-    const size_t lds = FfnGeom<D, false>::LDS;
-    hipLaunchKernelGGL((ffn_kernel<TM, D, false>), dim3((a.M + 63) / 64), dim3(512), lds, s, a);
-  }
-  return hipGetLastError();
-}
-
-// Would launch_ffn run these arguments on a masked instantiation (FfnArgs.lens), were it set?  Both operand types, dim 128 and 256, the plain and the
-// pre-stage form have a masked twin with their twin's resources (tests/test_masked_ffn_cpu.py); the in-kernel cross-attention has none.  The frame of
-// a row is derived from T: M = B T, and T >= 64 (a 64-token block then touches at most two items), which ffn_eligible asks of every launch.
-bool ffn_masks_rows(const FfnArgs& a, int prec) {
-  return ffn_eligible(a.dim, a.T, prec) && a.B >= 1 && a.M == a.B * a.T && !a.att_q;
-}
-
-hipError_t launch_ffn(const FfnArgs& a, int prec, hipStream_t s) {
-  if (!ffn_eligible(a.dim, a.T, prec) || a.M <= 0 || a.M != a.B * a.T) return hipErrorInvalidValue;
-  if (a.lens) {
-    if (!ffn_masks_rows(a, prec)) return hipErrorInvalidValue;          // refused, never run unmasked
-  }
-  if (!a.wstream || !a.consts || !a.bias2 || !a.res || (!a.out_f32 && !a.out_op)) return hipErrorInvalidValue;
-  if (a.att_q) {      // in-kernel cross-attention: with the pre-stage's weights, bias and residual; 8 heads of dim / 8 channels, 16-byte aligned fragments
-    if (!a.pre_bias || !a.pre_res || (a.pre_ldres & 3) || !a.att_kv || a.att_Lk < 1 || (a.att_ldq & 7) ||
-        ((reinterpret_cast<uintptr_t>(a.att_q) | reinterpret_cast<uintptr_t>(a.att_kv)) & 15) || !(a.att_scale > 0.f))
-      return hipErrorInvalidValue;
-  } else if (a.pre_a ? (!a.pre_bias || !a.pre_res || (a.pre_lda & 7) || (a.pre_ldres & 3) || (unsigned long long)a.M * a.pre_lda * 2ull > 0xFFF00000ull)
-              : (!a.yn || !a.ln_stats))
-    return hipErrorInvalidValue;
-  if ((!a.pre_a && !a.att_q && (a.ldy & 7)) || (a.ldres & 3) || (a.out_f32 && (a.ldo_f32 & 3)) || (a.out_op && (a.ldo_op & 3))) return hipErrorInvalidValue;
-  if (!a.pre_a && !a.att_q && (unsigned long long)a.M * a.ldy * 2ull > 0xFFF00000ull) return hipErrorInvalidValue;
-  if (prec == PREC_BF16) return a.dim == 128 ? launch_ffn_t<bf16_t, 128>(a, s) : launch_ffn_t<bf16_t, 256>(a, s);
-  return a.dim == 128 ? launch_ffn_t<f16_t, 128>(a, s) : launch_ffn_t<f16_t, 256>(a, s);
-}
-
 // ---------------------------------------------------------------------------
 // k | v fragment image for the in-kernel cross-attention (FfnArgs.att_kv; once per utterance, beside the hoisted k | v projection)
 // ---------------------------------------------------------------------------
@@ -838,26 +795,55 @@ hipError_t launch_xattn_pack(const void* k, int ldk, const void* v, int ldv, int
   return hipGetLastError();
 }
 
-hipError_t init_ffn_attributes() {
-  hipError_t e;
-#define NS2VC_FFN_ATTR(TM, D_, PRE_)                                                                                          \
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ffn_kernel<TM, D_, PRE_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                               (int)FfnGeom<D_, PRE_>::LDS)) != hipSuccess) return e
-  NS2VC_FFN_ATTR(bf16_t, 128, false); NS2VC_FFN_ATTR(bf16_t, 256, false); NS2VC_FFN_ATTR(f16_t, 128, false); NS2VC_FFN_ATTR(f16_t, 256, false);
-  NS2VC_FFN_ATTR(bf16_t, 128, true); NS2VC_FFN_ATTR(bf16_t, 256, true); NS2VC_FFN_ATTR(f16_t, 128, true); NS2VC_FFN_ATTR(f16_t, 256, true);
-#undef NS2VC_FFN_ATTR
-#define NS2VC_FFN_ATTRM(TM, D_, PRE_)                                                                                                       \
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ffn_kernel<TM, D_, PRE_, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                               (int)FfnGeom<D_, PRE_>::LDS)) != hipSuccess) return e
-  NS2VC_FFN_ATTRM(bf16_t, 128, false); NS2VC_FFN_ATTRM(bf16_t, 256, false); NS2VC_FFN_ATTRM(f16_t, 128, false); NS2VC_FFN_ATTRM(f16_t, 256, false);
-  NS2VC_FFN_ATTRM(bf16_t, 128, true); NS2VC_FFN_ATTRM(bf16_t, 256, true); NS2VC_FFN_ATTRM(f16_t, 128, true); NS2VC_FFN_ATTRM(f16_t, 256, true);
-#undef NS2VC_FFN_ATTRM
-#define NS2VC_FFN_ATTR2(TM, D_)                                                                                                      \
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ffn_kernel<TM, D_, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                               (int)FfnGeom<D_, true>::LDS)) != hipSuccess) return e
-  NS2VC_FFN_ATTR2(bf16_t, 128); NS2VC_FFN_ATTR2(bf16_t, 256); NS2VC_FFN_ATTR2(f16_t, 128); NS2VC_FFN_ATTR2(f16_t, 256);
-#undef NS2VC_FFN_ATTR2
-  return hipSuccess;
+// ---------------------------------------------------------------------------
+// the launcher (behind the pack kernel: the code object keeps its kernels in the order of their first use)
+// ---------------------------------------------------------------------------
+// The compiled set, one row per instantiation: dim 128 | 256 in both 16-bit operand types, each plain and with the pre-stage, these four with a
+// masked twin, and the pre-stage form with the in-kernel cross-attention (no masked twin)
+static uint64_t ffn_key(const FfnArgs& a, int prec, bool masked) { return kernel_key(prec, a.dim, a.pre_a || a.att_q, a.att_q != nullptr, masked); }
+#define NS2VC_FFN_ROW(TM, PREC, D, PRE, ATT, MK) \
+  {kernel_key(PREC, D, PRE, ATT, MK), reinterpret_cast<const void*>(ffn_kernel<TM, D, PRE, ATT, MK>), (uint32_t)FfnGeom<D, PRE>::LDS, 512}
+#define NS2VC_FFN_ROWS(PRE, ATT, MK)                                                              \
+  NS2VC_FFN_ROW(bf16_t, PREC_BF16, 128, PRE, ATT, MK), NS2VC_FFN_ROW(bf16_t, PREC_BF16, 256, PRE, ATT, MK), \
+  NS2VC_FFN_ROW(f16_t, PREC_F16, 128, PRE, ATT, MK), NS2VC_FFN_ROW(f16_t, PREC_F16, 256, PRE, ATT, MK)
+static const KernelRow ffn_rows[] = {
+  NS2VC_FFN_ROWS(false, false, false), NS2VC_FFN_ROWS(true, false, false),
+  NS2VC_FFN_ROWS(false, false, true), NS2VC_FFN_ROWS(true, false, true),
+  NS2VC_FFN_ROWS(true, true, false),
+};
+#undef NS2VC_FFN_ROWS
+#undef NS2VC_FFN_ROW
+static const KernelTable k_ffn_table(ffn_rows);      // (static: host data, no copy in the code object)
+const KernelTable& ffn_kernel_table() { return k_ffn_table; }
+
+// Would launch_ffn run these arguments on a masked instantiation (FfnArgs.lens), were it set?  Both operand types, dim 128 and 256, the plain and the
+// pre-stage form have a masked twin with their twin's resources (tests/test_masked_ffn_cpu.py); the in-kernel cross-attention has none: the table
+// says which.  The frame of a row is derived from T: M = B T, and T >= 64 (a 64-token block then touches at most two items), which ffn_eligible asks
+// of every launch.
+bool ffn_masks_rows(const FfnArgs& a, int prec) {
+  return ffn_eligible(a.dim, a.T, prec) && a.B >= 1 && a.M == a.B * a.T && find(k_ffn_table, ffn_key(a, prec, true));
 }
+
+hipError_t launch_ffn(const FfnArgs& a, int prec, hipStream_t s) {
+  if (!ffn_eligible(a.dim, a.T, prec) || a.M <= 0 || a.M != a.B * a.T) return hipErrorInvalidValue;
+  if (a.lens) {
+    if (!ffn_masks_rows(a, prec)) return hipErrorInvalidValue;          // refused, never run unmasked
+  }
+  if (!a.wstream || !a.consts || !a.bias2 || !a.res || (!a.out_f32 && !a.out_op)) return hipErrorInvalidValue;
+  if (a.att_q) {      // in-kernel cross-attention: with the pre-stage's weights, bias and residual; 8 heads of dim / 8 channels, 16-byte aligned fragments
+    if (!a.pre_bias || !a.pre_res || (a.pre_ldres & 3) || !a.att_kv || a.att_Lk < 1 || (a.att_ldq & 7) ||
+        ((reinterpret_cast<uintptr_t>(a.att_q) | reinterpret_cast<uintptr_t>(a.att_kv)) & 15) || !(a.att_scale > 0.f))
+      return hipErrorInvalidValue;
+  } else if (a.pre_a ? (!a.pre_bias || !a.pre_res || (a.pre_lda & 7) || (a.pre_ldres & 3) || (unsigned long long)a.M * a.pre_lda * 2ull > 0xFFF00000ull)
+              : (!a.yn || !a.ln_stats))
+    return hipErrorInvalidValue;
+  if ((!a.pre_a && !a.att_q && (a.ldy & 7)) || (a.ldres & 3) || (a.out_f32 && (a.ldo_f32 & 3)) || (a.out_op && (a.ldo_op & 3))) return hipErrorInvalidValue;
+  if (!a.pre_a && !a.att_q && (unsigned long long)a.M * a.ldy * 2ull > 0xFFF00000ull) return hipErrorInvalidValue;
+  const KernelRow* row = find(k_ffn_table, ffn_key(a, prec, a.lens != nullptr));
+  if (!row) return hipErrorInvalidValue;
+  return launch(*row, dim3(a.att_q ? a.B * ((a.T + 63) / 64) : (a.M + 63) / 64), s, a);      // (const FfnArgs)
+}
+
+hipError_t init_ffn_attributes() { return set_lds_all(k_ffn_table); }
 
 }  // namespace ns2vc

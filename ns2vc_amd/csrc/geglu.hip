@@ -17,6 +17,7 @@
 // 16 CONSECUTIVE hidden units: two 16-byte stores, no LDS staging, no epilogue.  512 threads = 8 waves = 4 token quarters x 2 unit groups of a tile.
 #include "common.h"
 #include "mma.h"
+#include "kernel_table.h"
 #include <type_traits>
 #include <vector>
 
@@ -541,11 +542,15 @@ hipError_t pack_geglu_stream(const float* w1p, const float* bias1p, int dim, int
   return hipSuccess;
 }
 
-template <typename TM, bool MASKED> static hipError_t launch_geglu_t(const GegluArgs& a, hipStream_t s) {
-  const int ntb = (a.M + GG_TOK - 1) / GG_TOK;
-  hipLaunchKernelGGL((geglu_kernel<TM, 384, MASKED>), dim3(ntb * GG_SPLIT), dim3(512), GegluGeom<384>::LDS, s, a);
-  return hipGetLastError();
-}
+// The compiled set, one row per instantiation: dim 384, both 16-bit operand types, each with its masked twin
+#define NS2VC_GG_ROW(TM, PREC, D, MK) {kernel_key(PREC, D, MK), reinterpret_cast<const void*>(geglu_kernel<TM, D, MK>), (uint32_t)GegluGeom<D>::LDS, 512}
+static const KernelRow gg_rows[] = {
+  NS2VC_GG_ROW(bf16_t, PREC_BF16, 384, false), NS2VC_GG_ROW(f16_t, PREC_F16, 384, false),
+  NS2VC_GG_ROW(bf16_t, PREC_BF16, 384, true), NS2VC_GG_ROW(f16_t, PREC_F16, 384, true),
+};
+#undef NS2VC_GG_ROW
+static const KernelTable k_geglu_table(gg_rows);      // (static: host data, no copy in the code object)
+const KernelTable& geglu_kernel_table() { return k_geglu_table; }
 
 // Would launch_geglu run these arguments on a masked instantiation (GegluArgs.lens), were it set?  Both instantiations have a masked twin; what is left
 // are the conditions on T, from which the frame of a row is derived.
@@ -560,16 +565,11 @@ hipError_t launch_geglu(const GegluArgs& a, int prec, hipStream_t s) {
   if (a.lens && !geglu_masks_rows(a, prec)) return hipErrorInvalidValue;    // refused, never run unmasked
   if (a.ldy < a.dim || a.ldo < 4 * a.dim || (a.ldy & 7) || (a.ldo & 7) || (unsigned long long)a.M * a.ldy * 2ull > 0xFFF00000ull || (unsigned long long)a.M * a.ldo * 2ull > 0x7FF00000ull) return hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(a.out_op) & 15) != 0) return hipErrorInvalidValue;
-  if (a.lens) return prec == PREC_BF16 ? launch_geglu_t<bf16_t, true>(a, s) : launch_geglu_t<f16_t, true>(a, s);
-  return prec == PREC_BF16 ? launch_geglu_t<bf16_t, false>(a, s) : launch_geglu_t<f16_t, false>(a, s);
+  const KernelRow* row = find(k_geglu_table, kernel_key(prec, a.dim, a.lens != nullptr));      // (lens: a masked key finds masked rows only)
+  if (!row) return hipErrorInvalidValue;
+  return launch(*row, dim3((a.M + GG_TOK - 1) / GG_TOK * GG_SPLIT), s, a);      // (const GegluArgs)
 }
 
-hipError_t init_geglu_attributes() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<bf16_t, 384, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<f16_t, 384, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<bf16_t, 384, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(geglu_kernel<f16_t, 384, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GegluGeom<384>::LDS);
-  return e;
-}
+hipError_t init_geglu_attributes() { return set_lds_all(k_geglu_table); }
 
 }  // namespace ns2vc

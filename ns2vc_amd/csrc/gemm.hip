@@ -36,6 +36,7 @@
 #include "common.h"
 #include "mma.h"
 #include "epilogue.h"
+#include "kernel_table.h"
 
 namespace ns2vc {
 
@@ -739,14 +740,6 @@ static constexpr size_t gemm_lds_bytes(int bm, int bn, int stages) {
 }
 
 static int g_gemm_flags = 0;
-template <typename TM, int BM, int BN, int STAGES>
-static hipError_t launch_cfg(const GemmArgs& g, hipStream_t s) {
-  const int nb = (g.N / BN) * ((g.M + BM - 1) / BM);
-  const size_t lds = gemm_lds_bytes(BM, BN, STAGES);
-  if (g.ln_stats) hipLaunchKernelGGL((gemm2_kernel<TM, BM, BN, STAGES, true>), dim3(nb), dim3(256), lds, s, g, g_gemm_flags);
-  else hipLaunchKernelGGL((gemm2_kernel<TM, BM, BN, STAGES, false>), dim3(nb), dim3(256), lds, s, g, g_gemm_flags);
-  return hipGetLastError();
-}
 
 void set_gemm_trace(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_trace), &p, sizeof(p)); }
 
@@ -755,23 +748,45 @@ static constexpr size_t gemm4_lds_bytes(int bm, int bn, int stages) {
   const size_t epi = (size_t)8 * 32 * (bn / 2 + 4) * 4;
   return ring > epi ? ring : epi;
 }
-template <typename TM, int BM, int BN, int STAGES, int SPEC = 0>
-static hipError_t launch_cfg4(const GemmArgs& g, hipStream_t s) {
-  int nb = (g.N / BN) * ((g.M + BM - 1) / BM);
-  if (g.gnp_x && g.gnp_sync && g.N / BN > 1) nb = 8 * (((g.M + BM - 1) / BM + 7) / 8) * (g.N / BN);   // cooperative prologue: row blocks per XCD, padded
+
+// The compiled set, one row per instantiation; `form`: which of a tile's variants (for gemm2 the plain and the LayerNorm consumer epilogue only).
+enum { GEMM_PLAIN = 0, GEMM_LNC = 1, GEMM_GNP = 2, GEMM_MASKED = 3 };
+//   gemm4: {128, 64} x 128, 8 waves with K split (SPEC 0) at ring {2, 3}, 4 loader + 4 consumer waves (SPEC 1) at ring 3; each plain, with the LayerNorm
+//   consumer epilogue, with the GroupNorm prologue and with the masked epilogue (which the ablation build does not have)
+//   Measured and not kept for SPEC (profiles/r03_gemm_spec.txt): 8 + 8 and 8 + 4 waves (no faster at one workgroup per CU, slower at two: 1024 / 768
+//   threads), ring 2 (+11 % in the captured step) and ring 4 (one workgroup per CU)
+#define NS2VC_G4_ROW(TM, PREC, BM, ST, SPEC, FORM)                                                                                \
+  {kernel_key(PREC, BM, 128, ST, SPEC, FORM),                                                                                    \
+   reinterpret_cast<const void*>(gemm4_kernel<TM, BM, 128, ST, FORM == GEMM_LNC, SPEC, FORM == GEMM_GNP, FORM == GEMM_MASKED>), \
+   (uint32_t)gemm4_lds_bytes(BM, 128, ST), 64 * G4Waves<SPEC>::NW},
 #if NS2VC_GEMM_ABLATE
-  if (g.lens) return hipErrorInvalidValue;                    // (the ablation build has no masked instantiations: refused, never run unmasked)
-  if (g.gnp_x) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC, true>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g, g_gemm_flags);
-  else if (g.ln_stats) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, true, SPEC>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g, g_gemm_flags);
-  else hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g, g_gemm_flags);
+#define NS2VC_G4_MASKED(TM, PREC, BM, ST, SPEC)
 #else
-  if (g.lens) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC, false, true>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g);   // (no prologue, no LayerNorm consumer: launch_gemm checks)
-  else if (g.gnp_x) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC, true>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g);   // (never with a LayerNorm consumer epilogue: launch_gemm checks)
-  else if (g.ln_stats) hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, true, SPEC>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g);
-  else hipLaunchKernelGGL((gemm4_kernel<TM, BM, BN, STAGES, false, SPEC>), dim3(nb), dim3(64 * G4Waves<SPEC>::NW), gemm4_lds_bytes(BM, BN, STAGES), s, g);
+#define NS2VC_G4_MASKED(TM, PREC, BM, ST, SPEC) NS2VC_G4_ROW(TM, PREC, BM, ST, SPEC, GEMM_MASKED)
 #endif
-  return hipGetLastError();
-}
+#define NS2VC_G4_ROW4(TM, PREC, BM, ST, SPEC) \
+  NS2VC_G4_MASKED(TM, PREC, BM, ST, SPEC) NS2VC_G4_ROW(TM, PREC, BM, ST, SPEC, GEMM_GNP) NS2VC_G4_ROW(TM, PREC, BM, ST, SPEC, GEMM_LNC) NS2VC_G4_ROW(TM, PREC, BM, ST, SPEC, GEMM_PLAIN)
+#define NS2VC_G4_ROWS(TM, PREC)                                             \
+  NS2VC_G4_ROW4(TM, PREC, 128, 3, 1) NS2VC_G4_ROW4(TM, PREC, 64, 3, 1)       \
+  NS2VC_G4_ROW4(TM, PREC, 128, 2, 0) NS2VC_G4_ROW4(TM, PREC, 128, 3, 0) NS2VC_G4_ROW4(TM, PREC, 64, 2, 0) NS2VC_G4_ROW4(TM, PREC, 64, 3, 0)
+static const KernelRow gemm4_rows[] = {NS2VC_G4_ROWS(bf16_t, PREC_BF16) NS2VC_G4_ROWS(f16_t, PREC_F16) NS2VC_G4_ROWS(float, PREC_F32)};
+#undef NS2VC_G4_ROWS
+#undef NS2VC_G4_ROW4
+#undef NS2VC_G4_MASKED
+#undef NS2VC_G4_ROW
+static const KernelTable k_gemm4_table(gemm4_rows);      // (static: host data, no copy in the code object)
+const KernelTable& gemm4_kernel_table() { return k_gemm4_table; }
+//   gemm2 (4 waves): 64x128 ring 2 (narrow GEGLU), 64x64 ring {2, 3, 4} (N not a multiple of 128)
+#define NS2VC_G2_ROW(TM, PREC, BM, BN, ST, LNC) \
+  {kernel_key(PREC, BM, BN, ST, LNC ? GEMM_LNC : GEMM_PLAIN), reinterpret_cast<const void*>(gemm2_kernel<TM, BM, BN, ST, LNC>), (uint32_t)gemm_lds_bytes(BM, BN, ST), 256},
+#define NS2VC_G2_ROW2(TM, PREC, BM, BN, ST) NS2VC_G2_ROW(TM, PREC, BM, BN, ST, true) NS2VC_G2_ROW(TM, PREC, BM, BN, ST, false)
+#define NS2VC_G2_ROWS(TM, PREC) NS2VC_G2_ROW2(TM, PREC, 64, 128, 2) NS2VC_G2_ROW2(TM, PREC, 64, 64, 2) NS2VC_G2_ROW2(TM, PREC, 64, 64, 3) NS2VC_G2_ROW2(TM, PREC, 64, 64, 4)
+static const KernelRow gemm2_rows[] = {NS2VC_G2_ROWS(bf16_t, PREC_BF16) NS2VC_G2_ROWS(f16_t, PREC_F16) NS2VC_G2_ROWS(float, PREC_F32)};
+#undef NS2VC_G2_ROWS
+#undef NS2VC_G2_ROW2
+#undef NS2VC_G2_ROW
+static const KernelTable k_gemm2_table(gemm2_rows);      // (static: host data, no copy in the code object)
+const KernelTable& gemm2_kernel_table() { return k_gemm2_table; }
 
 // which of the argument checks below refused a launch (the engine and ns2vc_k_gemm append it to their error text)
 static thread_local int g_gemm_fail_line = 0;
@@ -785,13 +800,12 @@ void set_forced_gemm_tile(int bm, int bn, int stages) {
   if (bm == -1 || bm == -2) { g_spec = bm == -2 ? 1 : 0; return; }
   if (bm == -3 || bm == -4) { g_ts = bm == -4 ? 1 : 0; g_ts_nl = (bm == -4 && (stages == 4 || stages == 8)) ? stages : 0; g_ts_ks = bm == -4 ? (bn == 1 ? 1 : bn == 2 ? 0 : -1) : -1; return; } g_force_bm = bm; g_force_bn = bn; g_force_st = stages & 255; g_gemm_flags = stages >> 8; }
 
-// Tile choice.  `st` 2..4 = gemm2_kernel with that ring depth; 12 / 13 = gemm4_kernel (8 waves, K split) with ring 2 / 3.
-// The compiled set is exactly what this function can return:
-//   gemm4: {128, 64} x 128, ring {2, 3};   gemm2 (4 waves): 64x128 ring 2 (narrow GEGLU), 64x64 ring {2, 3, 4} (N not a multiple of 128).
-// `dry`: nothing is launched -- hipSuccess when the tile choice lands on a kernel that has a masked epilogue (gemm_masks_rows)
-template <typename TM>
-static hipError_t launch_typed(const GemmArgs& g, hipStream_t s, bool dry = false) {
-  const int bke = 128 / (int)sizeof(TM);
+// Tile choice.  `st` 2..4 = gemm2_kernel with that ring depth; 12 / 13 = gemm4_kernel (8 waves, K split) with ring 2 / 3; 22..44 = gemm4_kernel with
+// loader / consumer waves: st = 10 * (1 + SPEC) + ring depth.  What is compiled are the rows of k_gemm2_table and k_gemm4_table: a choice (or a forced tile)
+// with no row is refused.  `masked`: the row that keeps the rows past an item's end zero (GemmArgs.lens, or gemm_masks_rows asking whether there is one).
+struct GemmChoice { const KernelRow* row; int bm, bn; bool g4; };
+static hipError_t choose_gemm(const GemmArgs& g, int prec, bool masked, GemmChoice* out) {
+  const int bke = prec == PREC_F32 ? 32 : 64;
   const int nk = g.K / bke;
   int bm, bn, st;
   const bool n128 = (g.N % 128) == 0;
@@ -823,30 +837,27 @@ static hipError_t launch_typed(const GemmArgs& g, hipStream_t s, bool dry = fals
       bm = 64; bn = 64; st = nk >= 32 ? 4 : (nk >= 20 ? 3 : 2);
     }
   }
-  if (g.gnp_x && !((st >= 12 && st <= 13) || (st >= 22 && st <= 44))) return gemm_invalid(__LINE__);   // the prologue lives in gemm4_kernel
-  if (g.lens && !((st >= 12 && st <= 13) || (st >= 22 && st <= 44))) return gemm_invalid(__LINE__);    // ... and so does the masked epilogue
-  if (dry) return hipSuccess;
-  if (st >= 22 && st <= 44) {   // loader / consumer specialised kernels: st = 10 * (1 + SPEC) + ring depth
-    if (bn != 128) return gemm_invalid(__LINE__);
-#define NS2VC_CASE4S(BM_, ST_, SP_) if (bm == BM_ && st == 10 * (1 + SP_) + ST_) return launch_cfg4<TM, BM_, 128, ST_, SP_>(g, s)
-    // compiled: 4 + 4 waves, ring 3.  Measured and not kept (profiles/r03_gemm_spec.txt): 8 + 8 and 8 + 4 waves (no faster at one
-    // workgroup per CU, slower at two: 1024 / 768 threads), ring 2 (+11 % in the captured step) and ring 4 (one workgroup per CU)
-    NS2VC_CASE4S(128, 3, 1); NS2VC_CASE4S(64, 3, 1);
-#undef NS2VC_CASE4S
-    return gemm_invalid(__LINE__);
-  }
-  if (st == 12 || st == 13) {   // 8-wave K-split kernel, ring depth st - 10
-    if (bn != 128) return gemm_invalid(__LINE__);
-#define NS2VC_CASE4(BM_, ST_) if (bm == BM_ && st == 10 + ST_) return launch_cfg4<TM, BM_, 128, ST_>(g, s)
-    NS2VC_CASE4(128, 2); NS2VC_CASE4(128, 3); NS2VC_CASE4(64, 2); NS2VC_CASE4(64, 3);
-#undef NS2VC_CASE4
-    return gemm_invalid(__LINE__);
-  }
-#define NS2VC_CASE(BM_, BN_, ST_) if (bm == BM_ && bn == BN_ && st == ST_) return launch_cfg<TM, BM_, BN_, ST_>(g, s)
-  NS2VC_CASE(64, 128, 2);
-  NS2VC_CASE(64, 64, 2); NS2VC_CASE(64, 64, 3); NS2VC_CASE(64, 64, 4);
-#undef NS2VC_CASE
-  return gemm_invalid(__LINE__);
+  // the form: the prologue and the masked epilogue live in gemm4_kernel (no prologue with a LayerNorm consumer epilogue, no prologue or LayerNorm
+  // consumer under lens: launch_gemm checks)
+  const int form = masked ? GEMM_MASKED : g.gnp_x ? GEMM_GNP : g.ln_stats ? GEMM_LNC : GEMM_PLAIN;
+  const bool spec = st >= 22 && st <= 44, g4 = spec || st == 12 || st == 13;
+  const KernelRow* row = g4 ? find(k_gemm4_table, kernel_key(prec, bm, bn, st % 10, spec ? st / 10 - 1 : 0, form)) : find(k_gemm2_table, kernel_key(prec, bm, bn, st, form));
+  if (!row) return gemm_invalid(__LINE__);
+  *out = GemmChoice{row, bm, bn, g4};
+  return hipSuccess;
+}
+static hipError_t launch_chosen(const GemmArgs& g, int prec, hipStream_t s) {
+  GemmChoice c;
+  const hipError_t e = choose_gemm(g, prec, g.lens != nullptr, &c);
+  if (e != hipSuccess) return e;
+  int nb = (g.N / c.bn) * ((g.M + c.bm - 1) / c.bm);
+  if (c.g4 && g.gnp_x && g.gnp_sync && g.N / c.bn > 1) nb = 8 * (((g.M + c.bm - 1) / c.bm + 7) / 8) * (g.N / c.bn);   // cooperative prologue: row blocks per XCD, padded
+  // parameter lists: gemm2_kernel(const GemmArgs, const int flags) always; gemm4_kernel(const GemmArgs), and (const GemmArgs, const int flags)
+  // in the ablation build only (NS2VC_G4_FLAGS_PARAM)
+#if !NS2VC_GEMM_ABLATE
+  if (c.g4) return launch(*c.row, dim3(nb), s, g);
+#endif
+  return launch(*c.row, dim3(nb), s, g, g_gemm_flags);
 }
 
 hipError_t launch_gemm(const GemmArgs& g_, int prec, hipStream_t s) {
@@ -899,12 +910,7 @@ hipError_t launch_gemm(const GemmArgs& g_, int prec, hipStream_t s) {
   if (g.sol_coef) return gemm_invalid(__LINE__);             // the solver epilogue exists in the tap-sharing kernel only
   if (g.gnp_pair) return gemm_invalid(__LINE__);             // ... and so does the prologue that writes hi + lo operand pairs
   if (g.lens && g.gnp_x) return gemm_invalid(__LINE__);      // ... and the masked GroupNorm prologue
-  switch (prec) {
-    case PREC_BF16: return launch_typed<bf16_t>(g, s);
-    case PREC_F16: return launch_typed<f16_t>(g, s);
-    case PREC_F32: return launch_typed<float>(g, s);
-    default: return gemm_invalid(__LINE__);
-  }
+  return launch_chosen(g, prec, s);
 }
 
 // would launch_gemm run this launch on a kernel that keeps the rows past an item's end zero by itself, were GemmArgs.lens set?  (the tap-sharing conv kernel,
@@ -914,17 +920,10 @@ bool gemm_masks_rows(const GemmArgs& g_, int prec) {
   if (g.rowstats || g.ln_stats || g.sol_coef || g.N % 64 != 0 || g.M <= 0 || g.Tout < 1 || g.M != g.B * g.Tout) return false;
   if (gemm_uses_convts(g, prec)) return true;
   if (g.gnp_x || g.gnp_pair) return false;
-  static const int dummy = 0;
-  g.lens = &dummy;                                            // (never read: a dry run of the tile choice)
-  hipError_t e;
-  switch (prec) {
-    case PREC_BF16: e = launch_typed<bf16_t>(g, nullptr, true); break;
-    case PREC_F16: e = launch_typed<f16_t>(g, nullptr, true); break;
-    case PREC_F32: e = launch_typed<float>(g, nullptr, true); break;
-    default: return false;
-  }
+  GemmChoice c;
+  const bool has = choose_gemm(g, prec, true, &c) == hipSuccess;       // (nothing is launched: is there a masked row behind the tile choice?)
   g_gemm_fail_line = 0;
-  return e == hipSuccess;
+  return has;
 }
 
 // would launch_gemm hand this launch to the tap-sharing conv kernel right now?  (the engine asks before it folds the solver update into conv_out)
@@ -934,44 +933,9 @@ bool gemm_uses_convts(const GemmArgs& g, int prec) {
   return g.algo != 1 && (forced_ts || (g_ts && !g_force_bm)) && convts_eligible(g, prec);
 }
 
-template <typename K> static hipError_t set_lds(K kern, size_t bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-#define NS2VC_SET(TM, BM, BN, ST)                                                                              \
-  do {                                                                                                          \
-    hipError_t e = set_lds(gemm2_kernel<TM, BM, BN, ST, false>, gemm_lds_bytes(BM, BN, ST));                    \
-    if (e == hipSuccess) e = set_lds(gemm2_kernel<TM, BM, BN, ST, true>, gemm_lds_bytes(BM, BN, ST));           \
-    if (e != hipSuccess) return e;                                                                              \
-  } while (0)
-#define NS2VC_SET4(TM, BM, ST)                                                                                  \
-  do {                                                                                                          \
-    hipError_t e = set_lds(gemm4_kernel<TM, BM, 128, ST, false>, gemm4_lds_bytes(BM, 128, ST));                 \
-    if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, true>, gemm4_lds_bytes(BM, 128, ST));        \
-    if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, 0, true>, gemm4_lds_bytes(BM, 128, ST)); \
-    if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, 0, false, true>, gemm4_lds_bytes(BM, 128, ST)); \
-    if (e != hipSuccess) return e;                                                                              \
-  } while (0)
-#define NS2VC_SET4S(TM, BM, ST, SP)                                                                             \
-  do {                                                                                                          \
-    hipError_t e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, SP>, gemm4_lds_bytes(BM, 128, ST));             \
-    if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, true, SP>, gemm4_lds_bytes(BM, 128, ST));    \
-    if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, SP, true>, gemm4_lds_bytes(BM, 128, ST)); \
-    if (e == hipSuccess) e = set_lds(gemm4_kernel<TM, BM, 128, ST, false, SP, false, true>, gemm4_lds_bytes(BM, 128, ST)); \
-    if (e != hipSuccess) return e;                                                                              \
-  } while (0)
-template <typename TM> static hipError_t init_typed() {
-  NS2VC_SET4(TM, 128, 2); NS2VC_SET4(TM, 128, 3); NS2VC_SET4(TM, 64, 2); NS2VC_SET4(TM, 64, 3);
-  NS2VC_SET4S(TM, 128, 3, 1); NS2VC_SET4S(TM, 64, 3, 1);
-  NS2VC_SET(TM, 64, 128, 2);
-  NS2VC_SET(TM, 64, 64, 2); NS2VC_SET(TM, 64, 64, 3); NS2VC_SET(TM, 64, 64, 4);
-  return hipSuccess;
-}
 hipError_t init_gemm_attributes() {
-  hipError_t e = init_typed<float>();
-  if (e == hipSuccess) e = init_typed<bf16_t>();
-  if (e == hipSuccess) e = init_typed<f16_t>();
-  return e;
+  const hipError_t e = set_lds_all(k_gemm2_table);
+  return e != hipSuccess ? e : set_lds_all(k_gemm4_table);
 }
 
 }  // namespace ns2vc

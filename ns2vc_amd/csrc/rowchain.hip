@@ -19,7 +19,9 @@
 // of EVERY 128-row weight tile for its 32 tokens.
 #include "common.h"
 #include "mma.h"
+#include "kernel_table.h"
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 namespace ns2vc {
@@ -544,30 +546,43 @@ bool rowchain_eligible(int dim, int n2, int T, int prec) {
   return (dim == 128 || dim == 256 || dim == 384) && (n2 == dim || n2 == 3 * dim) && T >= 1 && (prec == PREC_BF16 || prec == PREC_F16);
 }
 
-template <typename TM, int D, int R2, int NT, bool MASKED> static hipError_t launch_rc(const RowchainArgs& a, hipStream_t s) {
-  constexpr int TOK = RowchainGeom<D, R2, NT>::TOK;
-  const size_t lds = RowchainGeom<D, R2, NT>::LDS + (MASKED ? TOK * 4 : 0);      // (+ the per-token flags of the masked form)
-  static_assert(RowchainGeom<D, R2, NT>::LDS + TOK * 4 <= 160 * 1024, "LDS budget of the masked form");
-  const int nblk = (a.M + TOK - 1) / TOK, S = a.slices > 1 ? a.slices : 1;
-  hipLaunchKernelGGL((rowchain_kernel<TM, D, R2, NT, MASKED>), dim3(S > 1 ? ((nblk + 7) / 8) * 8 * S : nblk), dim3(512), lds, s, a);
-  return hipGetLastError();
+// The compiled set, one row per instantiation: 64-token workgroups at every dim (R2 stage-2 row blocks: n2 / 128, or the 2 | 5 of a slice of the two-slice
+// launch at dim 384), 128-token workgroups at dim 128; every row has a masked twin (+ its per-token flags in LDS)
+template <typename TM> constexpr int rc_prec() { return std::is_same<TM, bf16_t>::value ? PREC_BF16 : PREC_F16; }
+template <int D, int R2, int NT, bool MASKED> constexpr uint32_t rc_lds() {      // (+ the per-token flags of the masked form)
+  static_assert(RowchainGeom<D, R2, NT>::LDS + RowchainGeom<D, R2, NT>::TOK * 4 <= 160 * 1024, "LDS budget of the masked form");
+  return RowchainGeom<D, R2, NT>::LDS + (MASKED ? RowchainGeom<D, R2, NT>::TOK * 4 : 0);
 }
+#define NS2VC_RC_ROW1(TM, D, R2, NT, MK)                                                                \
+  {kernel_key(rc_prec<TM>(), D, R2, NT, MK), reinterpret_cast<const void*>(rowchain_kernel<TM, D, R2, NT, MK>), \
+   rc_lds<D, R2, NT, MK>(), 512}
+#define NS2VC_RC_ROW(TM, D, R2, NT) NS2VC_RC_ROW1(TM, D, R2, NT, false), NS2VC_RC_ROW1(TM, D, R2, NT, true)
+static const KernelRow rc_rows[] = {
+  NS2VC_RC_ROW(bf16_t, 128, 1, 1), NS2VC_RC_ROW(bf16_t, 128, 3, 1), NS2VC_RC_ROW(bf16_t, 256, 2, 1), NS2VC_RC_ROW(bf16_t, 256, 6, 1),
+  NS2VC_RC_ROW(f16_t, 128, 1, 1),  NS2VC_RC_ROW(f16_t, 128, 3, 1),  NS2VC_RC_ROW(f16_t, 256, 2, 1),  NS2VC_RC_ROW(f16_t, 256, 6, 1),
+  NS2VC_RC_ROW(bf16_t, 128, 1, 2), NS2VC_RC_ROW(bf16_t, 128, 3, 2), NS2VC_RC_ROW(f16_t, 128, 1, 2),  NS2VC_RC_ROW(f16_t, 128, 3, 2),
+  NS2VC_RC_ROW(bf16_t, 384, 3, 1), NS2VC_RC_ROW(bf16_t, 384, 9, 1), NS2VC_RC_ROW(f16_t, 384, 3, 1),  NS2VC_RC_ROW(f16_t, 384, 9, 1),
+  NS2VC_RC_ROW(bf16_t, 384, 2, 1), NS2VC_RC_ROW(bf16_t, 384, 5, 1), NS2VC_RC_ROW(f16_t, 384, 2, 1),  NS2VC_RC_ROW(f16_t, 384, 5, 1),
+};
+#undef NS2VC_RC_ROW
+#undef NS2VC_RC_ROW1
+static const KernelTable k_rowchain_table(rc_rows);      // (static: host data, no copy in the code object)
+const KernelTable& rowchain_kernel_table() { return k_rowchain_table; }
+
 // 64-token workgroups by default.  At dim 128 a workgroup's weights are small and M is large: when 64-token blocks would not
 // fit the chip in one round (one workgroup per CU: the LDS ring), 128-token blocks halve the grid and the weight traffic
 static int g_force_nt = 0;   // test / tuning hook (ns2vc_debug_set_rowchain_tokens): 1 / 2 forces the block size (2 only exists for dim 128)
 void set_forced_rowchain_tokens(int nt) { g_force_nt = nt; }
-template <typename TM, bool MK> static hipError_t launch_rc_tm(const RowchainArgs& a, hipStream_t s) {
-  if (a.dim == 128) {
-    const bool big = g_force_nt ? g_force_nt == 2 : (a.M + 63) / 64 > 256;
-    if (big) return a.n2 == 128 ? launch_rc<TM, 128, 1, 2, MK>(a, s) : launch_rc<TM, 128, 3, 2, MK>(a, s);
-    return a.n2 == 128 ? launch_rc<TM, 128, 1, 1, MK>(a, s) : launch_rc<TM, 128, 3, 1, MK>(a, s);
-  }
-  if (a.dim == 384 && a.slices == 2) return a.n2 == 384 ? launch_rc<TM, 384, 2, 1, MK>(a, s) : launch_rc<TM, 384, 5, 1, MK>(a, s);
-  if (a.dim == 384) return a.n2 == 384 ? launch_rc<TM, 384, 3, 1, MK>(a, s) : launch_rc<TM, 384, 9, 1, MK>(a, s);
-  return a.n2 == 256 ? launch_rc<TM, 256, 2, 1, MK>(a, s) : launch_rc<TM, 256, 6, 1, MK>(a, s);
+static hipError_t launch_rc(const RowchainArgs& a, int prec, bool masked, hipStream_t s) {
+  const int S = a.slices > 1 ? a.slices : 1;
+  const int nt = a.dim == 128 && (g_force_nt ? g_force_nt == 2 : (a.M + 63) / 64 > 256) ? 2 : 1;
+  const KernelRow* row = find(k_rowchain_table, kernel_key(prec, a.dim, rowchain_slice_blocks(a.n2, S), nt, masked));
+  if (!row) return hipErrorInvalidValue;
+  const int nblk = (a.M + 64 * nt - 1) / (64 * nt);
+  return launch(*row, dim3(S > 1 ? ((nblk + 7) / 8) * 8 * S : nblk), s, a);      // (const RowchainArgs)
 }
 
-// Would launch_rowchain run these arguments on a masked instantiation (RowchainArgs.lens), were it set?  Every instantiation launch_rc_tm selects has
+// Would launch_rowchain run these arguments on a masked instantiation (RowchainArgs.lens), were it set?  Every dense row of the table has
 // a masked twin with its twin's resources (tests/test_masked_rows_cpu.py), so the list of refused shapes is empty; what is left are the conditions
 // on T: the frame of a row is derived from it with or without a GroupNorm prologue.
 bool rowchain_masks_rows(const RowchainArgs& a, int prec) {
@@ -585,27 +600,10 @@ hipError_t launch_rowchain(const RowchainArgs& a, int prec, hipStream_t s) {
   } else if (a.lda & 7) return hipErrorInvalidValue;
   if ( (a.res && (a.ldres & 3)) || (a.out1_f32 && (a.ldo1 & 3)) || (a.ldo2 & 7)) return hipErrorInvalidValue;
   if ((unsigned long long)a.M * a.lda * 2ull > 0xFFF00000ull) return hipErrorInvalidValue;
-  if (a.lens) {
-    if (!rowchain_masks_rows(a, prec)) return hipErrorInvalidValue;      // refused, never run unmasked
-    return prec == PREC_BF16 ? launch_rc_tm<bf16_t, true>(a, s) : launch_rc_tm<f16_t, true>(a, s);
-  }
-  return prec == PREC_BF16 ? launch_rc_tm<bf16_t, false>(a, s) : launch_rc_tm<f16_t, false>(a, s);
+  if (a.lens) { if (!rowchain_masks_rows(a, prec)) return hipErrorInvalidValue; }      // refused, never run unmasked: a masked key finds masked rows only
+  return launch_rc(a, prec, a.lens != nullptr, s);
 }
 
-hipError_t init_rowchain_attributes() {
-  hipError_t e;
-#define NS2VC_RC_ATTR1(TM, DD_, RR_, NT_, MK_)                                                                                      \
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(rowchain_kernel<TM, DD_, RR_, NT_, MK_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                               (int)RowchainGeom<DD_, RR_, NT_>::LDS + ((MK_) ? RowchainGeom<DD_, RR_, NT_>::TOK * 4 : 0))) != hipSuccess) return e
-#define NS2VC_RC_ATTR(TM, DD_, RR_, NT_) NS2VC_RC_ATTR1(TM, DD_, RR_, NT_, false); NS2VC_RC_ATTR1(TM, DD_, RR_, NT_, true)
-  NS2VC_RC_ATTR(bf16_t, 128, 1, 1); NS2VC_RC_ATTR(bf16_t, 128, 3, 1); NS2VC_RC_ATTR(bf16_t, 256, 2, 1); NS2VC_RC_ATTR(bf16_t, 256, 6, 1);
-  NS2VC_RC_ATTR(f16_t, 128, 1, 1); NS2VC_RC_ATTR(f16_t, 128, 3, 1); NS2VC_RC_ATTR(f16_t, 256, 2, 1); NS2VC_RC_ATTR(f16_t, 256, 6, 1);
-  NS2VC_RC_ATTR(bf16_t, 128, 1, 2); NS2VC_RC_ATTR(bf16_t, 128, 3, 2); NS2VC_RC_ATTR(f16_t, 128, 1, 2); NS2VC_RC_ATTR(f16_t, 128, 3, 2);
-  NS2VC_RC_ATTR(bf16_t, 384, 3, 1); NS2VC_RC_ATTR(bf16_t, 384, 9, 1); NS2VC_RC_ATTR(f16_t, 384, 3, 1); NS2VC_RC_ATTR(f16_t, 384, 9, 1);
-  NS2VC_RC_ATTR(bf16_t, 384, 2, 1); NS2VC_RC_ATTR(bf16_t, 384, 5, 1); NS2VC_RC_ATTR(f16_t, 384, 2, 1); NS2VC_RC_ATTR(f16_t, 384, 5, 1);
-#undef NS2VC_RC_ATTR
-#undef NS2VC_RC_ATTR1
-  return hipSuccess;
-}
+hipError_t init_rowchain_attributes() { return set_lds_all(k_rowchain_table); }
 
 }  // namespace ns2vc
