@@ -218,6 +218,19 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream);   /* 
  * `stream` from pinned staging (a captured step graph stays valid; seeds_b may be reused on return).  ns2vc_unet_prepare clears them, and
  * ns2vc_sampler_begin refuses a stochastic table without them.  Stochastic tables never run the update in conv_out's epilogue (fuse_solver). */
 int ns2vc_sampler_set_seeds(ns2vc_unet* h, const uint64_t* seeds_b, void* stream);
+/* Classifier-free guidance (backward-compatible addition to ABI v7; replaces model_wrapper's guidance_type="classifier-free", condition,
+ * unconditional_condition, guidance_scale: sampler/uni_pc.py:155-233, sampler/dpm_solver.py:170-333).  The engine is prepared for B = 2n items and
+ * given the condition cat([unconditional, conditional]) -- rows [0, n) unconditional, [n, 2n) conditional, as the reference batches them
+ * (uni_pc.py:222-229) -- and, where it runs per-item lengths, `lengths` and `prompt_lengths` of 2n entries; the two halves MUST hold the same
+ * latent lengths (ns2vc_sampler_begin refuses otherwise).  scale_host = HOST array [n] of finite per-item scales, copied on `stream` from pinned
+ * staging as the seeds are: later calls with new values replay the captured step graph.  scale_host = NULL turns guidance off.  A change of
+ * on / off drops the step graph, clears the seeds and ends a loop in progress; ns2vc_unet_prepare turns guidance off.
+ * With guidance on, ns2vc_sampler_begin / _run / _peek / _end take and give n items, ns2vc_sampler_set_seeds takes n seeds (both halves get the
+ * same noise) and every step combines x0_g = x0_u + scale[b] * (x0_c - x0_u) in front of the unchanged update (the reference combines in noise
+ * space; eps is affine in x0 with the same x, alpha, sigma in both halves, so it is the same point).  scale[b] == 1 takes x0_c itself: such an
+ * item follows its unguided trajectory.  The update never runs in conv_out's epilogue (fuse_solver is ignored).  ns2vc_sampler_handoff carries
+ * the guidance of `src` (on / off, n, the scales) over to `dst`. */
+int ns2vc_sampler_set_guidance(ns2vc_unet* h, const float* scale_host, int n, void* stream);
 /* x_e of a loop in progress (the point the next evaluation is taken at) without ending the loop: what a precision self-check
  * evaluates two engines on (ns2vc_amd.pipeline.Denoiser) */
 int ns2vc_sampler_peek(ns2vc_unet* h, float* x_out_bct, void* stream);
@@ -588,6 +601,16 @@ int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int st
  * there and leaves m_{i-1}.  No noise term (stochastic tables run only inside the loop). */
 int ns2vc_k_solver_update(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
                           float* d1, float* mprev, float* mprev2, size_t n, int ld, void* stream);
+/* The guided form of that launch (backward-compatible addition to ABI v7; the combination of sampler/uni_pc.py:225-229 and
+ * sampler/dpm_solver.py:327-331 in x0 space, see ns2vc_sampler_set_guidance): a batch of 2n items of T rows of ld columns, rows [0, n*T)
+ * unconditional and [n*T, 2n*T) conditional.  n_half = n * T * ld, the elements of ONE half; x0, xe and xe_op cover both halves, xbar, d1,
+ * mprev and mprev2 the first only.  Element e of the first half: x0_g = scale_dev[b] == 1 ? x0[e + n_half] : x0[e] + scale_dev[b] * (x0[e + n_half] - x0[e])
+ * with b = (e / ld) / T, then the update of ns2vc_k_solver_update; the new xe and its operand copy go to both halves (pair row r + n*T).
+ * seeds_dev (DEVICE [n], optional): the noise term of stochastic rows as the loop adds it, on channels c < nc and frames t < lens_dev[b]
+ * (DEVICE [n] or NULL = all T); not with mprev2.  Refused, never run unguided: T <= 0, n_half not a multiple of T * ld, ld not a multiple of 4. */
+int ns2vc_k_solver_update_guided(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
+                                 float* d1, float* mprev, float* mprev2, size_t n_half, int ld, const float* scale_dev, int T, const uint64_t* seeds_dev,
+                                 const int32_t* lens_dev, int nc, void* stream);
 
 #ifdef __cplusplus
 }

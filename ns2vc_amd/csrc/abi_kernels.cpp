@@ -373,6 +373,18 @@ int ns2vc_k_solver_update(const float* coef_dev, const int32_t* step_dev, const 
   return launched(launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n, (hipStream_t)stream,
                                       precision != PREC_F32 ? ld : 0, SolverNoise(), mprev2), "solver_update launch");
 }
+int ns2vc_k_solver_update_guided(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
+                                 float* d1, float* mprev, float* mprev2, size_t n_half, int ld, const float* scale_dev, int T, const uint64_t* seeds_dev,
+                                 const int32_t* lens_dev, int nc, void* stream) {
+  if (!coef_dev || !step_dev || !x0 || !xe || !xe_op || !xbar || !d1 || !mprev || !scale_dev) return fail("null argument");
+  if (ld <= 0) return fail("ld (%d) must be positive", ld);
+  SolverGuide gd;
+  gd.scale = scale_dev; gd.T = T; gd.ld = ld;
+  SolverNoise nz;
+  if (seeds_dev) { nz.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev); nz.lens = lens_dev; nz.T = T; nz.ld = ld; nz.nc = nc; }
+  return launched(launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n_half, (hipStream_t)stream,
+                                      precision != PREC_F32 ? ld : 0, nz, mprev2, gd), "guided solver_update launch");
+}
 int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream) {
   return launched(launch_noise(reinterpret_cast<const unsigned long long*>(seeds_dev), B, C, T, ld, step, lens_dev, out, (hipStream_t)stream), "noise launch");
 }

@@ -251,6 +251,12 @@ __device__ __forceinline__ void solver_upd2(const SolverCoef& k, float d2c, floa
   oxb = nb; od1 = nd; oxe = nb - k.pc * nd - pe * dm2; om = m;
 }
 
+// Classifier-free guidance (sampler/uni_pc.py:225-229, sampler/dpm_solver.py:327-331 combine in noise space; eps is affine in x0 with the same
+// x, alpha, sigma in both halves, so this is the same point): x0_g = x0_u + s * (x0_c - x0_u).  s == 1 SELECTS x0_c -- such an item follows its
+// unguided trajectory from the conditional values with no rounding added (and takes nothing from x0_u, NaN included).
+// ns2vc_amd.schedule.guided_x0 is the host statement.
+__device__ __forceinline__ float guided_x0(float x0u, float x0c, float s) { return s == 1.0f ? x0c : x0u + s * (x0c - x0u); }
+
 // Device noise of the stochastic samplers (DDPM, DDIM with eta > 0; ns2vc_amd/noise.py is the host statement of the stream):
 // Philox4x32-10 (Salmon et al., SC 2011) keyed by the item's 64-bit seed, counter (t, c / 4, step, 0) -> the four normals of
 // channels 4q..4q+3 at frame t by two Box-Muller pairs.  Precise logf / sincosf (not the __ intrinsics): the host agrees to ulps.
@@ -371,11 +377,15 @@ hipError_t launch_pool_proj(const float* pooled, int B, int C, const float* wt, 
 // noise (optional): column 9 of the table row; where it is nonzero, state element (b, t, c) of rows of `ld` columns gains noise * z with
 // z = philox_gauss4(seeds[b], t, c / 4, step), for c < nc and t < lens[b] (lens NULL: every t < T) -- the other elements get nothing
 struct SolverNoise { const unsigned long long* seeds = nullptr; const int* lens = nullptr; int T = 0, ld = 0, nc = 0; };
+// guidance (optional): scale = DEVICE [n] per-item scales of a guided engine of 2n items of T rows of ld columns.  n then counts the elements of
+// ONE half: x0, xe and xe_op cover both halves (unconditional rows first), xbar / d1 / mprev / mprev2 the first
+struct SolverGuide { const float* scale = nullptr; int T = 0, ld = 0; };
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0,
                                 float* xe, void* xe_op, int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s,
                                 int split = 0,                  // split > 0 (16-bit): xe_op rows are [hi(split) | lo(split)] of state rows of `split` columns
                                 const SolverNoise& noise = SolverNoise(),
-                                float* mprev2 = nullptr);       // non-NULL: the history-2 update (order-3 tables; m_{i-2} in, m_{i-1} out); no noise with it
+                                float* mprev2 = nullptr,        // non-NULL: the history-2 update (order-3 tables; m_{i-2} in, m_{i-1} out); no noise with it
+                                const SolverGuide& guide = SolverGuide());
 // the normals a stochastic update adds at table row `step` (ns2vc_k_noise): out rows [B*T][ld] fp32, zeros where no noise goes
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s);
 hipError_t launch_fill_i32(int* p, int v, hipStream_t s);

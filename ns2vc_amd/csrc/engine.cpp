@@ -28,12 +28,13 @@ int ns2vc::check_ready(ns2vc_unet* h, bool need_plan) {
 
 // x [B][C][T] -> the solver state, channels-last: the fp32 rows and their operand copy (16-bit: the hi + lo pair);
 // masked plans: the rows past every item's end of both -> 0
-int ns2vc::load_state(ns2vc_unet* h, const float* x_bct, hipStream_t s) {
-  HIPCHK(launch_nct_to_btc(x_bct, h->cfg.latent_channels, h->T, h->B, h->xe, h->xe_op, h->prec, h->CP, h->CP, s, h->pair_width(), h->pair_off()));
+int ns2vc::load_state(ns2vc_unet* h, const float* x_bct, hipStream_t s, int items) {
+  const int B = items > 0 ? items : h->B;
+  HIPCHK(launch_nct_to_btc(x_bct, h->cfg.latent_channels, h->T, B, h->xe, h->xe_op, h->prec, h->CP, h->CP, s, h->pair_width(), h->pair_off()));
   if (!h->lens.masked) return 0;
   const size_t ob = (size_t)h->pair_width() * operand_bytes(h->prec);
-  HIPCHK(launch_mask_rows(h->xe, (size_t)h->CP * 4, (size_t)h->CP * 4, h->B, h->T, h->lens.dev, s));
-  HIPCHK(launch_mask_rows(h->xe_op, ob, ob, h->B, h->T, h->lens.dev, s));
+  HIPCHK(launch_mask_rows(h->xe, (size_t)h->CP * 4, (size_t)h->CP * 4, B, h->T, h->lens.dev, s));
+  HIPCHK(launch_mask_rows(h->xe_op, ob, ob, B, h->T, h->lens.dev, s));
   return 0;
 }
 
@@ -261,6 +262,8 @@ int ns2vc_unet_prepare(ns2vc_unet* h, int B, int T, int Lp) {
   h->lens.masked = false;         // a new shape starts dense (ns2vc_unet_set_lengths)
   h->lens.applied.clear();
   h->seeds.set = false;      // ... and without noise seeds (ns2vc_sampler_set_seeds)
+  h->guide.on = false;       // ... and unguided (ns2vc_sampler_set_guidance)
+  h->guide.n = 0;
   h->plens.on = false;       // ... and with whole prompts (ns2vc_unet_set_prompt_lengths)
   h->plens.applied.clear();
   if (build_plan(h, true)) return 1;

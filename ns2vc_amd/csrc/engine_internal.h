@@ -287,6 +287,17 @@ struct ns2vc_unet {
     ns2vc::Staged stage;
   } seeds;
   bool stochastic = false;                 // the loaded table has a nonzero noise column
+  // Classifier-free guidance (ns2vc_sampler_set_guidance): the engine is prepared for B = 2n items, rows [0, n*T) the unconditional half and
+  // [n*T, 2n*T) the conditional one; the loop's entry points take and give n items and the update combines the halves by the per-item scales.
+  // The scales live in a buffer of their own as the seeds do (new values are a copy, the captured step graph stays valid).
+  struct Guidance {
+    bool on = false;
+    int n = 0;
+    float* dev = nullptr;
+    int cap = 0;
+    ns2vc::Staged stage;
+  } guide;
+  int loop_items() const { return guide.on ? guide.n : B; }      // items the sampling loop's entry points take and give
   // History 2 (order-3 tables: a nonzero column 10 or 11, detected by ns2vc_sampler_load): the update also keeps m_{i-2}, in a buffer
   // of its own outside the plan arena, allocated on the first loop that needs it -- the dense plan's layout and launches do not change.
   struct History2 {
@@ -328,6 +339,7 @@ struct ns2vc_unet {
 
   ~ns2vc_unet() {      // (the pinned staging of the lengths and the seeds releases itself after this: ns2vc::Staged)
     if (seeds.dev) (void)hipFree(seeds.dev);
+    if (guide.dev) (void)hipFree(guide.dev);
     if (hist2.mprev2) (void)hipFree(hist2.mprev2);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
@@ -360,7 +372,7 @@ void drop_step_graph(ns2vc_unet* h);
 void drop_plan(ns2vc_unet* h);
 // engine.cpp
 int check_ready(ns2vc_unet* h, bool need_plan);
-int load_state(ns2vc_unet* h, const float* x_bct, hipStream_t s);
+int load_state(ns2vc_unet* h, const float* x_bct, hipStream_t s, int items = 0);   // items: the first `items` of the batch (0 = all B)
 // sampler.cpp
 bool solver_in_conv_out(ns2vc_unet* h, GemmArgs& g);
 // abi_kernels.cpp

@@ -564,13 +564,17 @@ __global__ void prompt_bias_kernel(const uint8_t* __restrict__ mask, const int* 
 // the device-resident coefficient table, so the same captured graph serves
 // every step.  H2 (compile time): the history-2 form of order-3 tables, which also reads m_{i-2} from mprev2 and
 // writes m_{i-1} there; H2 = false is the order <= 2 update, arithmetic unchanged (mprev2 unused).
+// GD (compile time): classifier-free guidance on an engine of 2n items, rows [0, n*T) unconditional and [n*T, 2n*T) conditional.  n4 counts
+// the quads of ONE half; quad i combines x0[i] and x0[i + half] by item b's scale (common.h guided_x0), runs the same update on the first
+// half's state and writes xe / xe_op to both halves, so the next evaluation is an ordinary 2n-item forward.  xbar, d1, mprev, mprev2 live in
+// the first half only.  GD = false: the instructions of the kernel without the flag (gd unused).
 // ---------------------------------------------------------------------------
-template <typename TM, bool H2>
+template <typename TM, bool H2, bool GD>
 __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
                                                             const float* __restrict__ x0, float* __restrict__ xe, TM* __restrict__ xe_op,
                                                             float* __restrict__ xbar, float* __restrict__ d1,
                                                             float* __restrict__ mprev, size_t n4, int split, SolverNoise nz,
-                                                            float* __restrict__ mprev2) {
+                                                            float* __restrict__ mprev2, SolverGuide gd) {
   op_mode_init<TM>();
   const int step = *step_ptr;
   const SolverCoef k = solver_coef(coef + (size_t)step * ncoef);
@@ -579,7 +583,12 @@ __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restr
   const float knz = (!H2 && nz.seeds) ? coef[(size_t)step * ncoef + 9] : 0.f;
   const float d2c = H2 ? coef[(size_t)step * ncoef + 10] : 0.f, pe = H2 ? coef[(size_t)step * ncoef + 11] : 0.f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
+    float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
+    if constexpr (GD) {      // (ld % 4 == 0: a quad lies in one row, so in one item)
+      const float4 vxc = reinterpret_cast<const float4*>(x0)[i + n4];
+      const float sc = gd.scale[((4 * i) / (size_t)gd.ld) / (size_t)gd.T];
+      vx0 = make_float4(guided_x0(vx0.x, vxc.x, sc), guided_x0(vx0.y, vxc.y, sc), guided_x0(vx0.z, vxc.z, sc), guided_x0(vx0.w, vxc.w, sc));
+    }
     const float4 vxe = reinterpret_cast<const float4*>(xe)[i];
     const float4 vxb = reinterpret_cast<const float4*>(xbar)[i];
     const float4 vd1 = reinterpret_cast<const float4*>(d1)[i];
@@ -618,6 +627,18 @@ __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restr
       out_op4<TM>(q + split, op_rest<TM>(oxe.x), op_rest<TM>(oxe.y), op_rest<TM>(oxe.z), op_rest<TM>(oxe.w));
     } else {
       out_op4<TM>(xe_op + 4 * i, oxe.x, oxe.y, oxe.z, oxe.w);
+    }
+    if constexpr (GD) {                                     // the conditional half evaluates at the same point: its xe and operand copy (pair row r + n*T)
+      const size_t j = i + n4;
+      out_f4(xe + 4 * j, oxe.x, oxe.y, oxe.z, oxe.w);
+      if (split) {
+        const size_t r = (4 * j) / (size_t)split;
+        TM* const q = xe_op + 4 * j + r * (size_t)split;
+        out_op4<TM>(q, oxe.x, oxe.y, oxe.z, oxe.w);
+        out_op4<TM>(q + split, op_rest<TM>(oxe.x), op_rest<TM>(oxe.y), op_rest<TM>(oxe.z), op_rest<TM>(oxe.w));
+      } else {
+        out_op4<TM>(xe_op + 4 * j, oxe.x, oxe.y, oxe.z, oxe.w);
+      }
     }
     out_f4(xbar + 4 * i, oxb.x, oxb.y, oxb.z, oxb.w);
     out_f4(d1 + 4 * i, od1.x, od1.y, od1.z, od1.w);
@@ -802,19 +823,26 @@ hipError_t launch_prompt_bias(const uint8_t* mask, const int* plens, int B, int 
   return hipGetLastError();
 }
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0, float* xe, void* xe_op, int prec,
-                                float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise, float* mprev2) {
+                                float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise, float* mprev2,
+                                const SolverGuide& guide) {
   if ((n & 3) || (split && (prec == PREC_F32 || (split & 3) || n % (size_t)split))) return hipErrorInvalidValue;
   if (noise.seeds && (noise.ld <= 0 || (noise.ld & 3) || noise.T <= 0 || noise.nc > noise.ld || n % ((size_t)noise.ld * noise.T))) return hipErrorInvalidValue;
   if (mprev2 && (noise.seeds || ncoef < 12)) return hipErrorInvalidValue;
+  // guided (n = the elements of ONE half): whole items of T rows of ld columns per half, refused rather than run unguided
+  if (guide.scale && (guide.T <= 0 || guide.ld <= 0 || (guide.ld & 3) || n == 0 || n % ((size_t)guide.T * guide.ld) || (split && split != guide.ld) ||
+                      (noise.seeds && (noise.T != guide.T || noise.ld != guide.ld))))
+    return hipErrorInvalidValue;
   const size_t n4 = n >> 2;
   const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  if (mprev2) {
-    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_kernel<TMX, true>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op,
-                                           xbar, d1, mprev, n4, split, noise, mprev2));
+#define NS2VC_SOLVER_LAUNCH(H2, GD)                                                                                                                \
+  NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_kernel<TMX, H2, GD>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op, \
+                                         xbar, d1, mprev, n4, split, noise, mprev2, guide))
+  if (guide.scale) {
+    if (mprev2) { NS2VC_SOLVER_LAUNCH(true, true); } else { NS2VC_SOLVER_LAUNCH(false, true); }
   } else {
-    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_kernel<TMX, false>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op,
-                                           xbar, d1, mprev, n4, split, noise, mprev2));
+    if (mprev2) { NS2VC_SOLVER_LAUNCH(true, false); } else { NS2VC_SOLVER_LAUNCH(false, false); }
   }
+#undef NS2VC_SOLVER_LAUNCH
   return hipGetLastError();
 }
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s) {

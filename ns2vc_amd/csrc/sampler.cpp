@@ -2,6 +2,7 @@
 // replayed -- and the hand-off of the solver state between two engines.
 #include "engine_internal.h"
 
+#include <cmath>
 #include <cstring>
 
 using namespace ns2vc;
@@ -9,6 +10,7 @@ using namespace ns2vc;
 // Does a step fold its solver update into conv_out?  r6: when conv_out is the plan's last launch and runs on the tap-sharing kernel, the update happens in its epilogue
 // (same arithmetic, element for element: common.h solver_upd) -- x0 is never written, the state tensors are read and written once instead of twice
 bool ns2vc::solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
+  if (h->guide.on) return false;                       // (the epilogue has no guided form: fuse_solver is ignored under guidance)
   if (!h->fuse_solver || h->debug || h->conv_out_idx < 0 || h->conv_out_idx != (int)h->fwd_ops.size() - 1) return false;
   // (masked plan: the update must see x0 with its padded rows zeroed -- conv_out's epilogue has not zeroed them -- so it stays a launch of its own)
   if (h->lens.masked) return false;
@@ -79,7 +81,7 @@ int ns2vc_sampler_set_seeds(ns2vc_unet* h, const uint64_t* seeds_b, void* stream
   if (check_ready(h, true)) return 1;
   if (!seeds_b) return fail("null seeds");
   hipStream_t s = (hipStream_t)stream;
-  const int B = h->B;
+  const int B = h->loop_items();      // (guided: n seeds, both halves get the same noise)
   if (ensure_seeds(h, B)) return 1;
   Staged& st = h->seeds.stage;
   const size_t nb = (size_t)B * sizeof(uint64_t);
@@ -89,6 +91,45 @@ int ns2vc_sampler_set_seeds(ns2vc_unet* h, const uint64_t* seeds_b, void* stream
   if (st.record(s)) return 1;
   h->seeds.set = true;
   return 0;
+}
+
+// a scale buffer for at least n items; a new one invalidates the captured step graph (its update reads the old pointer)
+static int ensure_scales(ns2vc_unet* h, int n) {
+  if (h->guide.dev && h->guide.cap >= n) return 0;
+  drop_step_graph(h);
+  if (h->guide.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->guide.dev)); h->guide.dev = nullptr; h->guide.cap = 0; }
+  const int cap = (n + 3) & ~3;            // 16-byte multiple (launch_copy16)
+  HIPCHK(hipMalloc((void**)&h->guide.dev, (size_t)cap * sizeof(float)));
+  HIPCHK(hipMemset(h->guide.dev, 0, (size_t)cap * sizeof(float)));
+  h->guide.cap = cap;
+  return 0;
+}
+static int guidance_onoff(ns2vc_unet* h, bool on, int n) {
+  if (on != h->guide.on) {
+    drop_step_graph(h);      // (the step graph bakes in which update runs)
+    h->seeds.set = false;    // (B seeds are not the n seeds of a guided loop, nor the other way round)
+    h->next_step = -1;       // (nor does a loop in progress survive the change)
+  }
+  h->guide.on = on;
+  h->guide.n = on ? n : 0;
+  return 0;
+}
+
+int ns2vc_sampler_set_guidance(ns2vc_unet* h, const float* scale_host, int n, void* stream) {
+  if (check_ready(h, true)) return 1;
+  if (!scale_host) return guidance_onoff(h, false, 0);
+  if (n <= 0 || h->B != 2 * n) return fail("guidance for n = %d items needs an engine prepared for B = 2n (B = %d)", n, h->B);
+  for (int b = 0; b < n; ++b)
+    if (!std::isfinite(scale_host[b])) return fail("guidance scale[%d] is not finite", b);
+  hipStream_t s = (hipStream_t)stream;
+  if (ensure_scales(h, n)) return 1;
+  Staged& st = h->guide.stage;
+  const size_t nb = (size_t)n * sizeof(float);
+  if (st.reserve(nb)) return 1;
+  memcpy(st.buf, scale_host, nb);
+  HIPCHK(hipMemcpyAsync(h->guide.dev, st.buf, nb, hipMemcpyHostToDevice, s));
+  if (st.record(s)) return 1;
+  return guidance_onoff(h, true, n);
 }
 
 // one evaluation + solver update
@@ -117,13 +158,15 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
     HIPCHK(launch_gemm(g, h->conv_out_prec, s));
     return 0;
   }
-  const size_t n = (size_t)h->B * h->T * h->CP;
+  const size_t n = (size_t)h->loop_items() * h->T * h->CP;      // (guided: the elements of one half)
+  SolverGuide gd;
+  if (h->guide.on) { gd.scale = h->guide.dev; gd.T = h->T; gd.ld = h->CP; }
   SolverNoise nz;
   if (h->stochastic) {       // noise on the item's valid frames and real channels only (masked plan: level-0 lengths = the first B entries)
     nz.seeds = h->seeds.dev; nz.lens = h->lens.masked ? h->lens.dev : nullptr; nz.T = h->T; nz.ld = h->CP; nz.nc = h->cfg.latent_channels;
   }
   HIPCHK(launch_solver_update(h->coef_dev, h->step_dev, NS2VC_NCOEF, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s, h->pair_off(), nz,
-                              h->hist2.on ? h->hist2.mprev2 : nullptr));
+                              h->hist2.on ? h->hist2.mprev2 : nullptr, gd));
   return 0;
 }
 
@@ -136,8 +179,23 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   if (h->stochastic && !h->seeds.set) return fail("the loaded solver table adds noise: set per-item seeds first (ns2vc_sampler_set_seeds)");
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)h->B * h->T * h->CP;
-  if (load_state(h, x_T_bct, s)) return 1;  // (masked: x_T is zero past every item's end; the solver update keeps it so -- its noise term skips those rows)
-  HIPCHK(launch_copy16(h->xe, h->xbar, n * sizeof(float), s));
+  if (h->guide.on) {      // n items of x_T into the unconditional half, the same point into the conditional half
+    const int gn = h->guide.n;
+    if (h->lens.masked)
+      for (int b = 0; b < gn; ++b)
+        if (h->lens.applied[b] != h->lens.applied[b + gn])
+          return fail("guided loop: lengths[%d] = %d and lengths[%d] = %d differ (the two halves hold the same latents)", b, (int)h->lens.applied[b], b + gn,
+                      (int)h->lens.applied[b + gn]);
+    const size_t nh = n / 2, ohb = nh / h->CP * h->pair_width() * operand_bytes(h->prec);
+    if (load_state(h, x_T_bct, s, gn)) return 1;
+    HIPCHK(launch_copy16(h->xe, h->xe + nh, nh * sizeof(float), s));
+    HIPCHK(launch_copy16(h->xe_op, static_cast<char*>(h->xe_op) + ohb, ohb, s));
+    HIPCHK(launch_copy16(h->xe, h->xbar, nh * sizeof(float), s));
+    HIPCHK(launch_zero(h->xbar + nh, nh * sizeof(float), s));      // (the histories live in the first half; the second stays zero)
+  } else {
+    if (load_state(h, x_T_bct, s)) return 1;  // (masked: x_T is zero past every item's end; the solver update keeps it so -- its noise term skips those rows)
+    HIPCHK(launch_copy16(h->xe, h->xbar, n * sizeof(float), s));
+  }
   HIPCHK(launch_zero(h->d1, n * sizeof(float), s));
   HIPCHK(launch_zero(h->mprev, n * sizeof(float), s));
   if (h->hist2.on) {
@@ -188,7 +246,8 @@ int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream)
 
 // Solver state of `src` (x_e, x_bar, d1, m_prev, m_prev2 of history-2 tables, loop position) -> `dst`, which continues the SAME table from there: the
 // engines may differ in precision (the state is fp32 in every mode; dst's operand copy of x_e is rebuilt in its own type).
-// Both must be prepared for the same (B, T) and hold the same solver table and condition.
+// Both must be prepared for the same (B, T) and hold the same solver table and condition.  The guidance of `src` (on / off, n, the scales)
+// becomes that of `dst`; a guided loop's histories live in the first halves, and x_e and its operand copy in both.
 int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   if (check_ready(dst, true) || check_ready(src, true)) return 1;
   if (dst == src) return fail("handoff to the same engine");
@@ -199,18 +258,25 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   if (dst->coef_hash != src->coef_hash) return fail("destination engine holds a DIFFERENT solver table with the same number of steps (solver / order / betas differ)");
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)src->B * src->T * src->CP;
+  const size_t nh = (size_t)src->loop_items() * src->T * src->CP;      // the histories' extent (guided: the first half)
+  if (src->guide.on) {
+    if (ensure_scales(dst, src->guide.n)) return 1;
+    HIPCHK(launch_copy16(src->guide.dev, dst->guide.dev, (size_t)((src->guide.n + 3) & ~3) * sizeof(float), s));
+  }
+  guidance_onoff(dst, src->guide.on, src->guide.n);
   HIPCHK(launch_copy16(src->xe, dst->xe, n * sizeof(float), s));
-  HIPCHK(launch_copy16(src->xbar, dst->xbar, n * sizeof(float), s));
-  HIPCHK(launch_copy16(src->d1, dst->d1, n * sizeof(float), s));
-  HIPCHK(launch_copy16(src->mprev, dst->mprev, n * sizeof(float), s));
+  HIPCHK(launch_copy16(src->xbar, dst->xbar, nh * sizeof(float), s));
+  HIPCHK(launch_copy16(src->d1, dst->d1, nh * sizeof(float), s));
+  HIPCHK(launch_copy16(src->mprev, dst->mprev, nh * sizeof(float), s));
   if (src->hist2.on) {          // (same table hash: dst->hist2.on too)
     if (ensure_mprev2(dst)) return 1;
-    HIPCHK(launch_copy16(src->hist2.mprev2, dst->hist2.mprev2, n * sizeof(float), s));
+    HIPCHK(launch_copy16(src->hist2.mprev2, dst->hist2.mprev2, nh * sizeof(float), s));
   }
   HIPCHK(launch_cast_op(dst->xe, n, dst->xe_op, dst->prec, s, dst->pair_off()));
   if (src->seeds.set) {      // the tail continues the same noise stream
-    if (ensure_seeds(dst, src->B)) return 1;
-    HIPCHK(launch_copy16(src->seeds.dev, dst->seeds.dev, (size_t)((src->B + 1) & ~1) * sizeof(unsigned long long), s));
+    const int ns = src->loop_items();
+    if (ensure_seeds(dst, ns)) return 1;
+    HIPCHK(launch_copy16(src->seeds.dev, dst->seeds.dev, (size_t)((ns + 1) & ~1) * sizeof(unsigned long long), s));
     dst->seeds.set = true;
   }
   HIPCHK(launch_fill_i32(dst->step_dev, src->next_step - 1, s));
@@ -223,7 +289,7 @@ int ns2vc_sampler_peek(ns2vc_unet* h, float* x_out_bct, void* stream) {
   if (check_ready(h, true)) return 1;
   if (!x_out_bct) return fail("null tensor");
   if (h->next_step < 0) return fail("no sampling loop in progress");
-  HIPCHK(launch_btc_to_nct(h->xe, h->CP, h->cfg.latent_channels, h->T, h->B, x_out_bct, (hipStream_t)stream));
+  HIPCHK(launch_btc_to_nct(h->xe, h->CP, h->cfg.latent_channels, h->T, h->loop_items(), x_out_bct, (hipStream_t)stream));      // (guided: the n items)
   return 0;
 }
 

@@ -201,6 +201,7 @@ class Engine:
         self.shape: Optional[Tuple[int, int, int]] = None
         self.lengths: Optional[np.ndarray] = None      # per-item valid frames (set_lengths), None = dense
         self.prompt_lengths: Optional[np.ndarray] = None   # per-item prompt frames (set_prompt_lengths), None = every item Lp
+        self.guidance: Optional[np.ndarray] = None      # per-item guidance scales (set_guidance), None = unguided
         self.table: Optional[SolverTable] = None
         self._weights_ready = False
         self._debug = False
@@ -278,6 +279,7 @@ class Engine:
         self.shape = (B, T, Lp)
         self.lengths = None
         self.prompt_lengths = None
+        self.guidance = None
 
     def workspace_bytes(self) -> int:
         n = C.c_size_t()
@@ -343,9 +345,32 @@ class Engine:
         if hasattr(seeds, "detach"):
             seeds = seeds.detach().cpu().numpy()
         a = np.ascontiguousarray(np.asarray(seeds).reshape(-1).astype(np.uint64))
-        if self.shape is None or a.shape[0] != self.shape[0]:
-            raise ValueError(f"seeds has {a.shape[0]} entries, the prepared batch {None if self.shape is None else self.shape[0]}")
+        items = None if self.shape is None else (self.shape[0] if self.guidance is None else self.guidance.shape[0])
+        if a.shape[0] != items:
+            raise ValueError(f"seeds has {a.shape[0]} entries, the prepared batch {items}")
         check(self.lib.ns2vc_sampler_set_seeds(self.h, a.ctypes.data, _stream_ptr(stream)), "set_seeds")
+
+    def set_guidance(self, scales=None, stream=None) -> None:
+        """Classifier-free guidance of the sampling loop: (n,) finite per-item scales for an engine prepared with B = 2n whose condition is
+        cat([unconditional, conditional]) (and whose ``lengths`` / ``prompt_lengths``, where set, have 2n entries, the latent lengths equal
+        in both halves); None = off.  The loop's entry points (``sample*``, ``set_seeds``) then take and give n items, and every step
+        combines ``x0_u + scale * (x0_c - x0_u)`` (``schedule.guided_x0``; scale 1 takes ``x0_c`` itself) in front of the solver update.
+        Asynchronous on ``stream``: new values replay the captured step graph; on / off recaptures and clears the seeds.  ``prepare``
+        turns it off."""
+        if scales is None:
+            check(self.lib.ns2vc_sampler_set_guidance(self.h, None, 0, _stream_ptr(stream)), "set_guidance")
+            self.guidance = None
+            return
+        if hasattr(scales, "detach"):
+            scales = scales.detach().cpu().numpy()
+        a = np.ascontiguousarray(np.asarray(scales).reshape(-1), dtype=np.float32)
+        if self.shape is None or 2 * a.shape[0] != self.shape[0]:
+            raise ValueError(f"guidance for {a.shape[0]} items needs an engine prepared with B = {2 * a.shape[0]}, "
+                             f"not {None if self.shape is None else self.shape[0]}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError("guidance scales must be finite")
+        check(self.lib.ns2vc_sampler_set_guidance(self.h, a.ctypes.data, int(a.shape[0]), _stream_ptr(stream)), "set_guidance")
+        self.guidance = a.copy()
 
     def forward(self, x, t, out, stream=None) -> None:
         """x (B,100,T), t (B,) fp32, out (B,100,T): one denoiser evaluation."""
@@ -383,6 +408,7 @@ class Engine:
         check(self.lib.ns2vc_sampler_begin(self.h, _ptr(x_inout), sp), "sampler_begin")
         check(self.lib.ns2vc_sampler_steps(self.h, n - k, int(use_graph), sp), "sampler_steps")
         check(self.lib.ns2vc_sampler_handoff(tail.h, self.h, sp), "sampler_handoff")
+        tail.guidance = None if self.guidance is None else self.guidance.copy()      # (the hand-off carries the guidance over)
         check(self.lib.ns2vc_sampler_steps(tail.h, k, int(use_graph), sp), "sampler_steps(tail)")
         check(self.lib.ns2vc_sampler_end(tail.h, _ptr(x_inout), sp), "sampler_end")
 

@@ -40,6 +40,15 @@ DEFAULT_TAIL_FP32_ORDER3 = {"dpmsolver++": 4, "unipc": 1}
 def default_tail_fp32(solver: str, order: int) -> int:
     """trailing fp32 evaluations of a 16-bit loop when the caller sets none"""
     return (DEFAULT_TAIL_FP32_ORDER3 if order == 3 and solver in DEFAULT_TAIL_FP32_ORDER3 else DEFAULT_TAIL_FP32).get(solver, 0)
+def guided_tail_extra(scales) -> int:
+    """fp32 evaluations a guided 16-bit loop adds to its default tail.  A guided x0 is (1 - s) x0_u + s x0_c of two evaluations whose 16-bit
+    rounding errors are independent, so it carries g = sqrt((1 - s)^2 + s^2) times the error of one (2.9 at s = 2.5, 9.2 at s = 7; <= 1 for
+    s in [0, 1]), and the last evaluations set the error of the sampled latent (class docstring of ``Denoiser``).  Every fp32 evaluation at
+    the end of a loop lowers that error about threefold or more (1.12e-3 -> 3.5e-4 -> 8.2e-5 for UniPC at s = 2.5), so
+    ceil(log3 g) of them offset the gain of the largest scale."""
+    s = np.asarray(scales, dtype=np.float64).reshape(-1)
+    g = float(np.sqrt((1.0 - s) ** 2 + s ** 2).max()) if s.size else 1.0
+    return 0 if g <= 1.0 else int(np.ceil(np.log(g) / np.log(3.0) - 1e-9))
 # LayerNorm-by-linearity guard thresholds on max |mean|/std (see Denoiser): 16-bit modes lose ~ratio * 2^-11 on a row,
 # fp32 loses ~ratio^2 * 2^-24 in the variance E[x^2] - mean^2
 LN_GUARD_DEFAULT = {"fp16": 8.0, "bf16": 8.0, "fp32": 32.0}
@@ -322,9 +331,9 @@ class Denoiser:
         eng.set_prompt_lengths(prompt_lengths, stream=stream)
         eng.set_condition(c32, p32, mask, stream=stream)
 
-    def _trajectory_points(self, x_T, use_graph, stream):
+    def _trajectory_points(self, x_T, use_graph, stream, rep: int = 1):
         """(x_e, t) at the first, middle and last evaluation of the loaded table, from a preliminary loop on the 16-bit engine
-        (its condition must be set)"""
+        (its condition must be set).  ``rep`` = 2 under guidance: the loop gives B items, the evaluations take the point in both halves."""
         import torch
         tm = np.asarray(self.engine.table.t_model, dtype=np.float32)
         n = len(tm)
@@ -337,19 +346,102 @@ class Denoiser:
             pos = i
             xe = torch.empty_like(x_T)
             self.engine.sample_peek(xe, stream=stream)
-            pts.append((xe, torch.full((B,), float(tm[i]), dtype=torch.float32, device=x_T.device)))
+            pts.append((xe if rep == 1 else xe.repeat(rep, 1, 1), torch.full((B * rep,), float(tm[i]), dtype=torch.float32, device=x_T.device)))
         scratch = torch.empty_like(x_T)
         self.engine.sample_end(scratch, stream=stream)
         return pts
 
-    def denoise(self, x, t, content, prompt, prompt_mask=None, lengths=None, prompt_lengths=None):
+    @staticmethod
+    def _guidance_scales(B: int, guidance_scale, unconditional_prompt) -> Optional[np.ndarray]:
+        """(B,) float32 scales of a guided call, or None where nothing guided runs: no unconditional prompt, or every scale 1
+        (the reference's short cut, sampler/uni_pc.py:222-223).  Raises for a wrong shape or a non-finite scale."""
+        g = guidance_scale.detach().cpu().numpy() if hasattr(guidance_scale, "detach") else np.asarray(guidance_scale)
+        if g.ndim > 1 or (g.ndim == 1 and g.shape[0] != B) or g.dtype.kind not in "fiu":
+            raise ValueError(f"guidance_scale must be a float or hold one scale per item ({B},), got shape {tuple(g.shape)}")
+        g = np.array(np.broadcast_to(g.astype(np.float32), (B,)))      # (a writable copy)
+        if not np.all(np.isfinite(g)):
+            raise ValueError("guidance_scale must be finite")
+        if unconditional_prompt is None or np.all(g == 1.0):
+            return None
+        return g
+
+    @staticmethod
+    def _check_guidance_args(B: int, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
+                             unconditional_content) -> Optional[np.ndarray]:
+        """the argument errors of the guidance keywords; returns ``_guidance_scales``"""
+        g = Denoiser._guidance_scales(B, guidance_scale, unconditional_prompt)
+        if unconditional_prompt is None:
+            if unconditional_prompt_mask is not None or unconditional_prompt_lengths is not None or unconditional_content is not None:
+                raise ValueError("unconditional_prompt_mask / _lengths / unconditional_content need an unconditional_prompt")
+            return g
+        if len(unconditional_prompt.shape) != 3 or unconditional_prompt.shape[0] not in (1, B):
+            raise ValueError(f"unconditional_prompt must be ({B} | 1, Lu, C), got {tuple(unconditional_prompt.shape)}")
+        if unconditional_prompt_mask is not None and (tuple(unconditional_prompt_mask.shape) not in
+                                                      ((1, unconditional_prompt.shape[1]), (B, unconditional_prompt.shape[1]))):
+            raise ValueError(f"unconditional_prompt_mask must be ({B} | 1, {unconditional_prompt.shape[1]}), got {tuple(unconditional_prompt_mask.shape)}")
+        if unconditional_prompt_lengths is not None:
+            ul = np.asarray(unconditional_prompt_lengths.detach().cpu() if hasattr(unconditional_prompt_lengths, "detach") else unconditional_prompt_lengths)
+            if ul.reshape(-1).shape[0] not in (1, B):
+                raise ValueError(f"unconditional_prompt_lengths must hold {B} (or 1) entries, got {ul.reshape(-1).shape[0]}")
+        if unconditional_content is not None and unconditional_content.shape[0] != B:
+            raise ValueError(f"unconditional_content must hold {B} items, got {unconditional_content.shape[0]}")
+        return g
+
+    @staticmethod
+    def _guided_condition(content, prompt, prompt_mask, lengths, prompt_lengths, unconditional_prompt, unconditional_prompt_mask,
+                          unconditional_prompt_lengths, unconditional_content):
+        """The condition of a guided call on the engine of 2B items: cat([unconditional, conditional]) as the reference batches it
+        (sampler/uni_pc.py:222-229) for content, prompt, mask, latent lengths and prompt lengths.  Prompts of different lengths are
+        zero-padded to the longer and every row gets its own frame count (``Engine.set_prompt_lengths``)."""
+        import torch
+        B, Lp, Lu = content.shape[0], prompt.shape[1], unconditional_prompt.shape[1]
+        dev = content.device
+        L = max(Lp, Lu)
+
+        def pad(p, n):      # (b, l, ...) -> (b, n, ...) with zeros behind
+            p = p.to(dev)
+            return p if p.shape[1] == n else torch.cat([p, p.new_zeros((p.shape[0], n - p.shape[1]) + tuple(p.shape[2:]))], dim=1)
+
+        def ints(v, n, fill):
+            if v is None:
+                return np.full((n,), fill, dtype=np.int32)
+            v = np.asarray(v.detach().cpu() if hasattr(v, "detach") else v).reshape(-1).astype(np.int32)
+            return np.ascontiguousarray(np.broadcast_to(v, (n,)))
+
+        up = unconditional_prompt.float().expand(B, -1, -1)
+        prompt2 = torch.cat([pad(up, L), pad(prompt.float(), L)], dim=0).contiguous()
+        uc = content if unconditional_content is None else unconditional_content.to(dev)
+        content2 = torch.cat([uc.float(), content.float()], dim=0).contiguous()
+        mask2 = None
+        if prompt_mask is not None or unconditional_prompt_mask is not None:
+            um = torch.ones((B, Lu), dtype=torch.bool, device=dev) if unconditional_prompt_mask is None else unconditional_prompt_mask.to(dev).bool().expand(B, -1)
+            cm = torch.ones((B, Lp), dtype=torch.bool, device=dev) if prompt_mask is None else prompt_mask.to(dev).bool()
+            mask2 = torch.cat([pad(um, L), pad(cm, L)], dim=0).contiguous()
+        plens2 = None
+        if Lu != Lp or prompt_lengths is not None or unconditional_prompt_lengths is not None:
+            plens2 = np.concatenate([ints(unconditional_prompt_lengths, B, Lu), ints(prompt_lengths, B, Lp)])
+        lens2 = None if lengths is None else np.concatenate([ints(lengths, B, 0)] * 2)
+        return content2, prompt2, mask2, lens2, plens2
+
+    def denoise(self, x, t, content, prompt, prompt_mask=None, lengths=None, prompt_lengths=None, guidance_scale=1.0, unconditional_prompt=None,
+                unconditional_prompt_mask=None, unconditional_prompt_lengths=None, unconditional_content=None):
         """One evaluation: x (B,100,T), t (B,), content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool -> x0_pred.
         ``lengths`` (B,) ints in [1, T] or None: item b is a segment of lengths[b] frames padded to T (``Engine.set_lengths``); its
         result on those frames is what it gives alone, and 0 beyond.
         ``prompt_lengths`` (B,) ints in [1, Lp] or None: item b's prompt is its first prompt_lengths[b] rows (``Engine.set_prompt_lengths``); its
-        result is what it gives alone with that prompt and no mask, whatever the rows past them hold."""
+        result is what it gives alone with that prompt and no mask, whatever the rows past them hold.
+        ``guidance_scale`` (float or (B,)) with ``unconditional_prompt`` (B | 1, Lu, 256): classifier-free guidance -- ONE evaluation of the batch
+        cat([unconditional, conditional]) of 2B items and ``schedule.guided_x0`` of its halves in torch (see ``sample`` for the keywords)."""
         import torch
         B, _, T = x.shape
+        scales = self._check_guidance_args(B, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
+                                           unconditional_content)
+        if scales is not None:
+            c2, p2, m2, l2, pl2 = self._guided_condition(content, prompt, prompt_mask, lengths, prompt_lengths, unconditional_prompt,
+                                                         unconditional_prompt_mask, unconditional_prompt_lengths, unconditional_content)
+            o = self.denoise(torch.cat([x, x], dim=0), torch.cat([t, t], dim=0), c2, p2, m2, l2, pl2)
+            sc = torch.from_numpy(scales).to(o.device).view(B, 1, 1)
+            return torch.where(sc == 1.0, o[B:], o[:B] + sc * (o[B:] - o[:B]))      # (the select of guided_x0)
         self._guard_before()
         self._prepare(B, T, prompt.shape[1])
         s = torch.cuda.current_stream(x.device)
@@ -370,8 +462,12 @@ class Denoiser:
             self._attn_check(1, s)                            # (after the guard's read-out: a switch drops the plan)
         return out if redone is None else redone
 
-    def _check_sampler_args(self, solver: str, steps: Optional[int], eta: float, B: int, seeds, order: int = 2, **options) -> int:
+    def _check_sampler_args(self, solver: str, steps: Optional[int], eta: float, B: int, seeds, order: int = 2, guidance_scale=1.0,
+                            unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None,
+                            unconditional_content=None, **options) -> int:
         """the argument errors of ``sample``, raised before anything runs; returns the step count"""
+        self._check_guidance_args(B, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
+                                  unconditional_content)
         if solver not in SOLVERS:
             raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
         table_options(options)                  # unknown option names
@@ -392,7 +488,8 @@ class Denoiser:
 
     def sample(self, content, prompt, prompt_mask=None, noise=None, solver: str = "unipc", steps: Optional[int] = None, order: int = 2,
                use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None,
-               prompt_lengths=None, **options):
+               prompt_lengths=None, guidance_scale=1.0, unconditional_prompt=None, unconditional_prompt_mask=None,
+               unconditional_prompt_lengths=None, unconditional_content=None, **options):
         """content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool; ``noise`` (B,100,T) = x_T (drawn with
         torch.randn like model.py:635 if None).  Returns the sampled latent (B,100,T) fp32.
         ``solver``: ``unipc`` | ``dpmsolver++`` (``order`` 1 | 2 | 3, multistep) or the reference's discrete samplers ``ddim`` (``eta`` =
@@ -402,20 +499,42 @@ class Denoiser:
         ``lengths`` (B,) ints in [1, T] or None: per-item valid frames of a padded batch (see ``denoise``); x_T is zeroed past them.
         ``prompt_lengths`` (B,) ints in [1, Lp] or None: per-item prompt frames of a batch whose prompts are padded to one Lp (see ``denoise``).
         ``tail_fp32`` overrides the instance's setting for this call (see the class docstring).
+        ``guidance_scale`` (float or (B,) per item) with ``unconditional_prompt`` (B | 1, Lu, 256): classifier-free guidance, the reference's
+        ``model_wrapper(guidance_type="classifier-free", condition, unconditional_condition, guidance_scale)`` (sampler/uni_pc.py:155-233)
+        inside the captured loop: the engine (and the fp32 tail) run 2B items, cat([unconditional, conditional]), and every solver update
+        combines ``x0_u + s * (x0_c - x0_u)`` (``schedule.guided_x0``) first.  ``unconditional_prompt_mask`` (B | 1, Lu),
+        ``unconditional_prompt_lengths`` and ``unconditional_content`` (default: ``content``) describe the unconditional half; Lu may differ
+        from Lp.  An item with scale 1 follows its unguided trajectory; with every scale 1, or no unconditional prompt, nothing guided runs
+        and the call is today's B-item loop (uni_pc.py:222-223).
         ``options`` (keyword-only): the reference's ``UniPC.sample`` / ``DPM_Solver.sample`` keywords that ``schedule.build_table`` serves
         -- ``skip_type``, ``lower_order_final``, ``denoise_to_zero`` (one more evaluation), ``variant`` (UniPC), ``solver_type``
         (DPM-Solver++), ``t_start``, ``t_end``, ``method`` ("multistep" only)."""
         import torch
         B, _, T = content.shape
         dev = content.device
-        steps = self._check_sampler_args(solver, steps, eta, B, seeds, order, **options)
+        steps = self._check_sampler_args(solver, steps, eta, B, seeds, order, guidance_scale, unconditional_prompt, unconditional_prompt_mask,
+                                         unconditional_prompt_lengths, unconditional_content, **options)
+        scales = self._guidance_scales(B, guidance_scale, unconditional_prompt)
+        guide_kw = dict(guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
+                        unconditional_prompt_lengths=unconditional_prompt_lengths, unconditional_content=unconditional_content)
+        rep = 1
+        if scales is not None:      # the engine's batch is cat([unconditional, conditional]); the loop still takes and gives B items
+            content_c, prompt_c, prompt_mask_c, lengths_c, prompt_lengths_c = content, prompt, prompt_mask, lengths, prompt_lengths
+            content, prompt, prompt_mask, lengths, prompt_lengths = self._guided_condition(
+                content, prompt, prompt_mask, lengths, prompt_lengths, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
+                unconditional_content)
+            rep = 2
         self._guard_before()
-        self._prepare(B, T, prompt.shape[1])
+        self._prepare(rep * B, T, prompt.shape[1])
+        if scales is not None or self.engine.guidance is not None:
+            self.engine.set_guidance(scales, stream=torch.cuda.current_stream(dev))
         self._table(solver, steps, order, eta, **options)
         nfe = self.engine.table.steps               # (steps + 1 with denoise_to_zero)
         n_tail = tail_fp32 if tail_fp32 is not None else self.tail_fp32
         if n_tail is None:
             n_tail = default_tail_fp32(solver, order) if self.precision != "fp32" else 0
+            if scales is not None and self.precision != "fp32":      # guidance multiplies the 16-bit rounding of the last evaluations
+                n_tail += guided_tail_extra(scales)
         n_tail = max(0, min(int(n_tail), nfe))
         if noise is None:
             noise = torch.randn((B, self.cfg.latent_channels, T), device=dev, generator=generator)
@@ -430,9 +549,11 @@ class Denoiser:
         c32, p32 = content.float().contiguous(), prompt.float().contiguous()
         if self.precision_check is not None and not self._precision_checked:
             self._condition(self.engine, c32, p32, mask, s, lengths, prompt_lengths)
-            self._self_check(self._trajectory_points(x, use_graph, s), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths,
+            self._self_check(self._trajectory_points(x, use_graph, s, rep), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths,
                              prompt_lengths=prompt_lengths)
         tail = self._tail(solver, steps, order, n_tail, eta, **options)
+        if tail is not None and (scales is not None or tail.guidance is not None):
+            tail.set_guidance(scales, stream=s)
         if tail is not None and stochastic:
             tail.set_seeds(seeds, stream=s)
         if self.serving_fp32:            # a failed precision check: the whole loop on the fp32 engine
@@ -446,14 +567,17 @@ class Denoiser:
         if first_attn:
             self.engine.attn_fallbacks(reset=True, stream=s)      # count this loop alone (the self-check's evaluations are behind us)
         self.engine.sample(x, use_graph=use_graph, stream=s, tail=tail, tail_steps=n_tail if tail is not None else 0)
+        if scales is not None:      # (a redo starts from the caller's B-item arguments)
+            content, prompt, prompt_mask, lengths, prompt_lengths = content_c, prompt_c, prompt_mask_c, lengths_c, prompt_lengths_c
         redone = self._guard_after(s, lambda: self.sample(content, prompt, prompt_mask, noise, solver, steps, order, use_graph,
                                                           tail_fp32=tail_fp32, lengths=lengths, eta=eta, seeds=seeds, prompt_lengths=prompt_lengths,
-                                                          **options))
+                                                          **guide_kw, **options))
         if first_attn and redone is None:
             self._attn_check(nfe - (n_tail if tail is not None else 0), s)      # (after the guard's read-out: a switch drops the plan)
         return x if redone is None else redone
 
-    def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, seeds=None, prompt_lengths=None, **kw):
+    def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, seeds=None, prompt_lengths=None, guidance_scale=1.0,
+                       unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None, unconditional_content=None, **kw):
         """Data-parallel: every rank receives the GLOBAL batch description, runs its contiguous slice and the
         finished latents are all-gathered (RCCL).  The noise (and ``seeds``, for ddpm / ddim with eta > 0: drawn for the global
         batch from ``generator`` if None) is drawn for the global batch and sliced, so an utterance's
@@ -474,7 +598,15 @@ class Denoiser:
                 seeds = draw_seeds(n, kw.get("generator"))
             sd = None if seeds is None else seeds[lo:hi]
             pl = None if prompt_lengths is None else prompt_lengths[lo:hi]
-            local = self.sample(content[lo:hi], prompt[lo:hi], pm, noise[lo:hi], lengths=ln, seeds=sd, prompt_lengths=pl, **kw)
+
+            def part(v):      # the per-item guidance arguments go with the batch; a scalar / one shared row goes to every rank whole
+                if isinstance(v, (list, tuple)):
+                    v = np.asarray(v)
+                return v if v is None or np.ndim(v) == 0 or v.shape[0] != n else v[lo:hi]
+            local = self.sample(content[lo:hi], prompt[lo:hi], pm, noise[lo:hi], lengths=ln, seeds=sd, prompt_lengths=pl,
+                                guidance_scale=part(guidance_scale), unconditional_prompt=part(unconditional_prompt),
+                                unconditional_prompt_mask=part(unconditional_prompt_mask),
+                                unconditional_prompt_lengths=part(unconditional_prompt_lengths), unconditional_content=part(unconditional_content), **kw)
         return _dist.gather_latents(local, n)
 
 
@@ -492,13 +624,16 @@ class OverlappedPipeline:
     """
 
     def __init__(self, denoiser: Denoiser, pre_fn, post_fn, solver: str = "unipc", steps: Optional[int] = 20, order: int = 2,
-                 use_graph: bool = True, pre_device=None, post_device=None, stage_cus=None, denoiser_cus=None, eta: float = 0.0, **options):
+                 use_graph: bool = True, pre_device=None, post_device=None, stage_cus=None, denoiser_cus=None, eta: float = 0.0,
+                 guidance_scale=1.0, unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None, **options):
         """``pre_device`` / ``post_device`` (r4): run the front / back end on ANOTHER ROCm device of the node.  On one GPU the three streams
         serialise (the denoiser's launches hold every CU: 7.8 % of the stages' kernel time overlaps, profiles/r03_overlap_trace.txt); a stage
         on its own device overlaps by construction and only its tensors cross xGMI -- content + prompt 35 MB per 32 x 10 s batch in, the
         latent 12 MB out, stream-ordered peer copies behind the stage's event.  ``pre_fn`` then runs with ``pre_device`` current and must
         return tensors on it; ``post_fn`` receives the latent on ``post_device``.  None = the denoiser's device (the one-GPU pipeline).
         NOT measured on two devices yet (no multi-GPU box this round).
+        ``guidance_scale`` / ``unconditional_prompt`` (1, Lu, 256) / ``unconditional_prompt_mask`` / ``unconditional_prompt_lengths``: classifier-free
+        guidance with one unconditional prompt for every item of every batch (``Denoiser.sample``), passed through.
         ``options``: the keyword-only sampler options of ``Denoiser.sample`` (``skip_type``, ``denoise_to_zero``, ...), passed through."""
         import torch
         if not torch.cuda.is_available():
@@ -506,6 +641,9 @@ class OverlappedPipeline:
         self.denoiser, self.pre_fn, self.post_fn = denoiser, pre_fn, post_fn
         table_options(options)
         self.kw = dict(solver=solver, steps=steps, order=order, use_graph=use_graph, eta=eta, **options)
+        if unconditional_prompt is not None:
+            self.kw.update(guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
+                           unconditional_prompt_lengths=unconditional_prompt_lengths)
         dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         self.pre_device = torch.device(pre_device) if pre_device is not None else dev

@@ -394,6 +394,21 @@ def _discrete_table(solver: str, steps: int, betas: Optional[np.ndarray], eta: f
     return SolverTable(solver, steps, coef.astype(np.float32), times_out, {"pairs": np.array(pairs, dtype=np.int64)})
 
 
+def guided_x0(x0_u: np.ndarray, x0_c: np.ndarray, scale) -> np.ndarray:
+    """Classifier-free guidance, the host statement of common.h ``guided_x0``: ``x0_u + s * (x0_c - x0_u)`` per item, ``scale`` a float or
+    (B,) against (B, ...) arrays.  The reference combines in noise space (sampler/uni_pc.py:225-229, sampler/dpm_solver.py:327-331); with the
+    x_start wrapper eps = (x - alpha x0) / sigma is affine in x0 with the same x, alpha, sigma in both halves, so this is the same point.
+    Where ``scale == 1`` the result IS ``x0_c`` by a select (not ``x0_u + 1 * (x0_c - x0_u)``): such an item takes nothing from ``x0_u``
+    -- no rounding, no NaN -- and follows its unguided trajectory (the reference's short cut, uni_pc.py:222-223, per item)."""
+    x0_u, x0_c = np.asarray(x0_u), np.asarray(x0_c)
+    s = np.asarray(scale, dtype=x0_c.dtype)
+    if s.ndim > 1 or (s.ndim == 1 and s.shape[0] != x0_c.shape[0]):
+        raise ValueError(f"scale must be a float or hold one scale per item ({x0_c.shape[0]},), got shape {s.shape}")
+    s = s.reshape(s.shape + (1,) * (x0_c.ndim - s.ndim)) if s.ndim else s
+    with np.errstate(invalid="ignore"):
+        return np.where(s == 1, x0_c, x0_u + s * (x0_c - x0_u)).astype(x0_c.dtype)
+
+
 def has_history2(table: SolverTable) -> bool:
     """the table needs m_prev2 (some row of order 3): what the engine's ns2vc_sampler_load detects from columns 10-11"""
     return bool((np.asarray(table.coef)[:, 10:12] != 0).any())

@@ -73,7 +73,9 @@ class GroupedConverter:
                  solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, ragged: bool = False, eta: float = 0.0,
                  masked_fuse: Optional[bool] = None, masked_attn: Optional[bool] = None,
                  masked_rows: Optional[bool] = None, masked_ffn: Optional[bool] = None, masked_geglu: Optional[bool] = None,
-                 ragged_prompts: bool = False, **options):
+                 ragged_prompts: bool = False, guidance_scale: float = 1.0, unconditional_prompt: Optional[torch.Tensor] = None, **options):
+        """``guidance_scale`` with ``unconditional_prompt`` (1, Lu, 256), one for every segment: classifier-free guidance
+        (``Denoiser.sample``).  The engine then runs two items per segment, so a batch holds at most ``max_batch // 2`` segments."""
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
         if masked_fuse is not None and bool(masked_fuse) != denoiser.masked_fuse:     # the denoiser's engine option of that name (ragged batches only)
             denoiser.set_option("masked_fuse", bool(masked_fuse))
@@ -85,12 +87,21 @@ class GroupedConverter:
             denoiser.set_option("masked_ffn", bool(masked_ffn))
         if masked_geglu is not None and bool(masked_geglu) != denoiser.masked_geglu:
             denoiser.set_option("masked_geglu", bool(masked_geglu))
+        self.guided = unconditional_prompt is not None and float(guidance_scale) != 1.0
+        if self.guided:
+            if not np.isfinite(float(guidance_scale)):
+                raise ValueError("guidance_scale must be finite")
+            if len(unconditional_prompt.shape) != 3 or unconditional_prompt.shape[0] != 1:
+                raise ValueError(f"unconditional_prompt must be (1, Lu, C), got {tuple(unconditional_prompt.shape)}")
+            max_batch = max(1, max_batch // 2)
         self.max_batch, self.seed, self.ragged = max_batch, seed, ragged
         self.ragged_prompts = bool(ragged_prompts)
         if solver == "ddpm" and steps == 30:      # (the constructor's default step count is the continuous solvers'; ddpm runs every timestep)
             steps = None
         table_options(options)           # the keyword-only sampler options of Denoiser.sample (skip_type, denoise_to_zero, ...)
         self.kw = dict(solver=solver, steps=steps, order=order, eta=eta, **options)
+        if self.guided:
+            self.kw.update(guidance_scale=float(guidance_scale), unconditional_prompt=unconditional_prompt)
 
     def _seeds(self, idx) -> np.ndarray:
         """per-SEGMENT noise seeds of the stochastic samplers, from the converter's seed and the segment's position in the input"""
