@@ -231,6 +231,19 @@ int ns2vc_sampler_set_seeds(ns2vc_unet* h, const uint64_t* seeds_b, void* stream
  * item follows its unguided trajectory.  The update never runs in conv_out's epilogue (fuse_solver is ignored).  ns2vc_sampler_handoff carries
  * the guidance of `src` (on / off, n, the scales) over to `dst`. */
 int ns2vc_sampler_set_guidance(ns2vc_unet* h, const float* scale_host, int n, void* stream);
+/* Correction of the predicted x0 inside the loop (backward-compatible addition to ABI v7; the constructor options correcting_x0_fn,
+ * thresholding_max_val, dynamic_thresholding_ratio of the reference's two continuous solvers: sampler/dpm_solver.py:338-425, :433-442,
+ * sampler/uni_pc.py:236-294).  mode 0 = off; 1 = "dynamic_thresholding": per item and step s_b = max(quantile_ratio(|m_b|), max_val), then
+ * m_b = clamp(m_b, -s_b, s_b) / s_b, with m the model value after the x_start round trip (the guided one under guidance) and the quantile
+ * torch.quantile's (linear interpolation in float32) over the item's own elements -- frames t < L_b, channels c < latent_channels; 2 = clamp(m,
+ * -max_val, max_val), the common callable.  The corrected m is what enters the update and the histories.  The quantile is an exact selection on the
+ * device (one launch per step in front of the update), so the loop still captures.  0 <= ratio <= 1, max_val finite and > 0.  A change of mode, or
+ * of a value the active mode passes to its launches (mode 1: ratio and max_val; mode 2: max_val), drops the captured step graph; a repeat of the
+ * same values, or a change of a value no launch takes (the ratio under mode 2, either while off), does not.
+ * ns2vc_sampler_begin / _steps refuse a correction together with a stochastic table (the reference's ddim_sample / p_sample_loop have none), the
+ * update never runs in conv_out's epilogue under a correction (fuse_solver is ignored), ns2vc_unet_prepare leaves the setting alone, and
+ * ns2vc_sampler_handoff carries that of `src` over to `dst`. */
+int ns2vc_sampler_set_x0_correction(ns2vc_unet* h, int mode, float ratio, float max_val);
 /* x_e of a loop in progress (the point the next evaluation is taken at) without ending the loop: what a precision self-check
  * evaluates two engines on (ns2vc_amd.pipeline.Denoiser) */
 int ns2vc_sampler_peek(ns2vc_unet* h, float* x_out_bct, void* stream);
@@ -611,6 +624,19 @@ int ns2vc_k_solver_update(const float* coef_dev, const int32_t* step_dev, const 
 int ns2vc_k_solver_update_guided(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
                                  float* d1, float* mprev, float* mprev2, size_t n_half, int ld, const float* scale_dev, int T, const uint64_t* seeds_dev,
                                  const int32_t* lens_dev, int nc, void* stream);
+/* The quantile launch of the dynamic thresholding (backward-compatible addition to ABI v7) on ready values: thr[b] = torch.quantile(|v_b|, p) in
+ * its float32 rule (ns2vc_amd.schedule.abs_quantile), v_b = rows t < lens_dev[b] (DEVICE [n_items] or NULL = all T; clamped to [0, T]) and
+ * columns c < nc of item b's T rows of ld columns of `values` (fp32, 16-byte aligned, ld % 4 == 0).  Exact: a radix select over the bit patterns,
+ * integer counts only.  thr = DEVICE [n_items]; an item without elements gives 0.  NaN / Inf among the values: unspecified result, nothing else. */
+int ns2vc_k_abs_quantile(const float* values, int n_items, int T, int ld, int nc, const int32_t* lens_dev, float p, float* thr, void* stream);
+/* One corrected solver update as the loop makes it (backward-compatible addition to ABI v7; see ns2vc_sampler_set_x0_correction): mode 1 = the
+ * quantile launch on m formed from x0, xe and row *step_dev (guided_x0 of the halves first when scale_dev is set), thr_dev[b] = that quantile
+ * (DEVICE [n_items], n_items = n / (T * ld)), then the update with m = clamp(m, -s_b, s_b) / s_b, s_b = max(thr_dev[b], max_val); mode 2 = the
+ * update with m = clamp(m, -max_val, max_val), thr_dev unused.  scale_dev = NULL: the arguments of ns2vc_k_solver_update, n = all elements;
+ * non-NULL: those of ns2vc_k_solver_update_guided, n = the elements of ONE half.  lens_dev / nc: the elements the quantile runs over.  No noise. */
+int ns2vc_k_solver_update_corrected(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
+                                    float* d1, float* mprev, float* mprev2, size_t n, int ld, int T, const float* scale_dev, const int32_t* lens_dev,
+                                    int nc, int mode, float ratio, float max_val, float* thr_dev, void* stream);
 
 #ifdef __cplusplus
 }

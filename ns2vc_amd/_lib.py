@@ -161,6 +161,7 @@ PROTOTYPES = {
     "ns2vc_sampler_peek": (_I, [_P, _P, _P]),
     "ns2vc_sampler_set_seeds": (_I, [_P, _P, _P]),
     "ns2vc_sampler_set_guidance": (_I, [_P, _P, _I, _P]),
+    "ns2vc_sampler_set_x0_correction": (_I, [_P, _I, C.c_float, C.c_float]),
     "ns2vc_unet_attn_fallbacks": (_I, [_P, C.POINTER(C.c_ulonglong), _I, _P]),
     "ns2vc_unet_gn_coop_alone": (_I, [_P, C.POINTER(C.c_ulonglong), _I, _P]),
     "ns2vc_unet_graph_captures": (_I, [_P, C.POINTER(C.c_ulonglong)]),
@@ -225,6 +226,8 @@ PROTOTYPES = {
     "ns2vc_k_noise": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ns2vc_k_solver_update": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _P]),
     "ns2vc_k_solver_update_guided": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _P, _I, _P, _P, _I, _P]),
+    "ns2vc_k_abs_quantile": (_I, [_P, _I, _I, _I, _I, _P, C.c_float, _P, _P]),
+    "ns2vc_k_solver_update_corrected": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

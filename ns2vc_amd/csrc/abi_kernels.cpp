@@ -385,6 +385,34 @@ int ns2vc_k_solver_update_guided(const float* coef_dev, const int32_t* step_dev,
   return launched(launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n_half, (hipStream_t)stream,
                                       precision != PREC_F32 ? ld : 0, nz, mprev2, gd), "guided solver_update launch");
 }
+int ns2vc_k_abs_quantile(const float* values, int n_items, int T, int ld, int nc, const int32_t* lens_dev, float p, float* thr, void* stream) {
+  if (!values || !thr) return fail("null argument");
+  QuantArgs q;
+  q.v = values; q.lens = lens_dev; q.T = T; q.ld = ld; q.nc = nc; q.p = p;
+  return launched(launch_abs_quantile(q, n_items, thr, (hipStream_t)stream), "abs_quantile launch");
+}
+int ns2vc_k_solver_update_corrected(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
+                                    float* d1, float* mprev, float* mprev2, size_t n, int ld, int T, const float* scale_dev, const int32_t* lens_dev,
+                                    int nc, int mode, float ratio, float max_val, float* thr_dev, void* stream) {
+  if (!coef_dev || !step_dev || !x0 || !xe || !xe_op || !xbar || !d1 || !mprev) return fail("null argument");
+  if (mode != 1 && mode != 2) return fail("corrected update: mode %d must be 1 (dynamic thresholding) or 2 (clamp)", mode);
+  if (mode == 1 && !thr_dev) return fail("dynamic thresholding needs thr_dev");
+  if (ld <= 0 || (ld & 3) || T <= 0 || n == 0 || n % ((size_t)T * ld)) return fail("n (%zu) must hold whole items of T (%d) rows of ld (%d) columns, ld a multiple of 4", n, T, ld);
+  if (!(ratio >= 0.f && ratio <= 1.f) || !(max_val > 0.f)) return fail("ratio %g must be in [0, 1] and max_val %g > 0", (double)ratio, (double)max_val);
+  SolverGuide gd;
+  if (scale_dev) { gd.scale = scale_dev; gd.T = T; gd.ld = ld; }
+  SolverCorrect cx;
+  cx.mode = mode; cx.max_val = max_val; cx.T = T; cx.ld = ld;
+  if (mode == 1) {
+    QuantArgs q;
+    q.v = x0; q.xe = xe; q.coef = coef_dev; q.step_ptr = step_dev; q.ncoef = NS2VC_NCOEF; q.scale = scale_dev; q.half = scale_dev ? n : 0;
+    q.lens = lens_dev; q.T = T; q.ld = ld; q.nc = nc; q.p = ratio;
+    if (launched(launch_abs_quantile(q, (int)(n / ((size_t)T * ld)), thr_dev, (hipStream_t)stream), "abs_quantile launch")) return 1;
+    cx.thr = thr_dev;
+  }
+  return launched(launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n, (hipStream_t)stream,
+                                      precision != PREC_F32 ? ld : 0, SolverNoise(), mprev2, gd, cx), "corrected solver_update launch");
+}
 int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream) {
   return launched(launch_noise(reinterpret_cast<const unsigned long long*>(seeds_dev), B, C, T, ld, step, lens_dev, out, (hipStream_t)stream), "noise launch");
 }

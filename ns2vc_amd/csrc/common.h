@@ -251,6 +251,38 @@ __device__ __forceinline__ void solver_upd2(const SolverCoef& k, float d2c, floa
   oxb = nb; od1 = nd; oxe = nb - k.pc * nd - pe * dm2; om = m;
 }
 
+// The reference's correction of the predicted x0 (correcting_x0_fn: sampler/dpm_solver.py:416-425, :433-442, sampler/uni_pc.py:268-294), applied to m
+// in front of everything that uses it.  TH (compile time): 1 = dynamic thresholding, clamp(m, -s, s) / s with s = max(the item's |m| quantile,
+// max_val); 2 = the static clamp(m, -s, s), s = max_val.  solver_m is the round trip of solver_upd on its own (the quantile kernel forms the same m);
+// the two corrected updates are solver_upd / solver_upd2 with m replaced.  ns2vc_amd.schedule.correct_x0 is the host statement.
+__device__ __forceinline__ float solver_m(const SolverCoef& k, float vx0, float vxe) {
+  const float eps = (vxe - k.alpha * vx0) / k.sigma;
+  return (vxe - k.sigma * eps) / k.alpha;
+}
+template <int TH> __device__ __forceinline__ float solver_correct(float m, float s) {
+  const float c = fminf(fmaxf(m, -s), s);
+  return TH == 1 ? c / s : c;
+}
+template <int TH>
+__device__ __forceinline__ void solver_upd_c(const SolverCoef& k, float s, float vx0, float vxe, float vxb, float vd1, float vmp, float& oxe, float& oxb, float& od1,
+                                             float& om) {
+  const float m = solver_correct<TH>(solver_m(k, vx0, vxe), s);
+  const float x = vxb - k.g0 * vd1 - k.g1 * (m - vmp);
+  const float nb = k.A * x - k.Bc * m;
+  const float nd = k.d1c * (vmp - m);
+  oxb = nb; od1 = nd; oxe = nb - k.pc * nd; om = m;
+}
+template <int TH>
+__device__ __forceinline__ void solver_upd2_c(const SolverCoef& k, float s, float d2c, float pe, float vx0, float vxe, float vxb, float vd1, float vmp, float vmp2,
+                                              float& oxe, float& oxb, float& od1, float& om) {
+  const float m = solver_correct<TH>(solver_m(k, vx0, vxe), s);
+  const float x = vxb - k.g0 * vd1 - k.g1 * (m - vmp);
+  const float nb = k.A * x - k.Bc * m;
+  const float dm2 = vmp2 - m;
+  const float nd = k.d1c * (vmp - m) + d2c * dm2;
+  oxb = nb; od1 = nd; oxe = nb - k.pc * nd - pe * dm2; om = m;
+}
+
 // Classifier-free guidance (sampler/uni_pc.py:225-229, sampler/dpm_solver.py:327-331 combine in noise space; eps is affine in x0 with the same
 // x, alpha, sigma in both halves, so this is the same point): x0_g = x0_u + s * (x0_c - x0_u).  s == 1 SELECTS x0_c -- such an item follows its
 // unguided trajectory from the conditional values with no rounding added (and takes nothing from x0_u, NaN included).
@@ -380,12 +412,24 @@ struct SolverNoise { const unsigned long long* seeds = nullptr; const int* lens 
 // guidance (optional): scale = DEVICE [n] per-item scales of a guided engine of 2n items of T rows of ld columns.  n then counts the elements of
 // ONE half: x0, xe and xe_op cover both halves (unconditional rows first), xbar / d1 / mprev / mprev2 the first
 struct SolverGuide { const float* scale = nullptr; int T = 0, ld = 0; };
+// x0 correction (optional; common.h solver_correct): mode 1 = dynamic thresholding by max(thr[b], max_val), thr = DEVICE [items] left by
+// launch_abs_quantile; mode 2 = clamp by max_val.  Items are T rows of ld columns (guided: those of one half).  Not together with noise
+struct SolverCorrect { int mode = 0; const float* thr = nullptr; float max_val = 1.0f; int T = 0, ld = 0; };
+// thr[b] = the p-quantile (torch.quantile's float32 rule) of |m| over rows t < lens[b] (NULL: T) and columns c < nc of item b's T rows of ld columns.
+// xe == NULL: `v` holds the values themselves.  Otherwise v = x0 and m is formed as the update forms it from row *step_ptr of the table; with
+// `scale` (DEVICE [items]) on guided_x0 of v and v + half (half = the elements of one half).  One workgroup per item, nothing shared between them
+struct QuantArgs {
+  const float* v = nullptr; const float* xe = nullptr; const float* coef = nullptr; const int* step_ptr = nullptr; int ncoef = 0;
+  const float* scale = nullptr; size_t half = 0; const int* lens = nullptr; int T = 0, ld = 0, nc = 0; float p = 0.995f;
+};
+hipError_t launch_abs_quantile(const QuantArgs& q, int n_items, float* thr, hipStream_t s);
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0,
                                 float* xe, void* xe_op, int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s,
                                 int split = 0,                  // split > 0 (16-bit): xe_op rows are [hi(split) | lo(split)] of state rows of `split` columns
                                 const SolverNoise& noise = SolverNoise(),
                                 float* mprev2 = nullptr,        // non-NULL: the history-2 update (order-3 tables; m_{i-2} in, m_{i-1} out); no noise with it
-                                const SolverGuide& guide = SolverGuide());
+                                const SolverGuide& guide = SolverGuide(),
+                                const SolverCorrect& correct = SolverCorrect());
 // the normals a stochastic update adds at table row `step` (ns2vc_k_noise): out rows [B*T][ld] fp32, zeros where no noise goes
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s);
 hipError_t launch_fill_i32(int* p, int v, hipStream_t s);

@@ -305,6 +305,15 @@ struct ns2vc_unet {
     float* mprev2 = nullptr;
     size_t n = 0;
   } hist2;
+  // Correction of the predicted x0 (ns2vc_sampler_set_x0_correction): mode 1 = dynamic thresholding, 2 = clamp.  The ratio and max_val are
+  // arguments of the step's launches, so a change of the mode or of a value the active mode passes drops the captured step graph.  The per-item thresholds of mode 1 live in a
+  // buffer of their own outside the plan arena (one float per batch item), allocated when the correction is switched on.
+  struct X0Correction {
+    int mode = 0;
+    float ratio = 0.995f, max_val = 1.0f;
+    float* thr = nullptr;
+    int cap = 0;
+  } x0c;
 
   // named persistent buffers
   float *xe = nullptr, *xbar = nullptr, *d1 = nullptr, *mprev = nullptr, *x0 = nullptr;
@@ -341,6 +350,7 @@ struct ns2vc_unet {
     if (seeds.dev) (void)hipFree(seeds.dev);
     if (guide.dev) (void)hipFree(guide.dev);
     if (hist2.mprev2) (void)hipFree(hist2.mprev2);
+    if (x0c.thr) (void)hipFree(x0c.thr);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     if (tfork.side_stream) (void)hipStreamDestroy(tfork.side_stream);

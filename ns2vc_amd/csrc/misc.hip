@@ -1,8 +1,9 @@
 // Memory-bound helper kernels of the NS2VC denoiser engine (gfx950): GroupNorm /
 // LayerNorm statistics, the timestep-embedding MLP, prompt attention pooling,
-// layout changes at the API boundary and the fused solver update.  All fp32,
+// layout changes at the API boundary, the fused solver update and the per-item |x0| quantile of its corrected form.  All fp32,
 // wave64, vectorised 16-B accesses on the channels-last activation layout.
 #include "common.h"
+#include <cmath>
 #include <vector>
 
 namespace ns2vc {
@@ -645,6 +646,193 @@ __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restr
     out_f4(mprev + 4 * i, om.x, om.y, om.z, om.w);
   }
 }
+// The corrected update (ns2vc_sampler_set_x0_correction): solver_update_kernel with m corrected in front of everything that uses it (common.h
+// solver_correct, solver_upd_c / solver_upd2_c) and no noise term -- the reference's discrete samplers have no correction, the launcher refuses the
+// pair.  TH (compile time): 1 = by item b's threshold max(cx.thr[b], cx.max_val), which abs_quantile_kernel left there in the launch before; 2 = by
+// cx.max_val alone.  Items are cx.T rows of cx.ld columns; under GD those of ONE half.  A kernel of its own, not a fourth parameter of
+// solver_update_kernel: that kernel's instantiations keep their names and their instructions (tools/kernel_code_diff.py).  Keep the two in step: mode 2 with a max_val
+// no value reaches must give the plain update's bits (tests/test_x0_correction_gpu.py pins that for every form).
+// the new x_e of quad i and its operand copy: fp32 rows, or for 16-bit types the hi + lo pair in rows of 2 * split columns, the lo plane `split` columns further
+template <typename TM>
+__device__ __forceinline__ void solver_store_xe(float* __restrict__ xe, TM* __restrict__ xe_op, size_t i, int split, const float4& oxe) {
+  out_f4(xe + 4 * i, oxe.x, oxe.y, oxe.z, oxe.w);
+  if (split) {
+    const size_t r = (4 * i) / (size_t)split;
+    TM* const q = xe_op + 4 * i + r * (size_t)split;
+    out_op4<TM>(q, oxe.x, oxe.y, oxe.z, oxe.w);
+    out_op4<TM>(q + split, op_rest<TM>(oxe.x), op_rest<TM>(oxe.y), op_rest<TM>(oxe.z), op_rest<TM>(oxe.w));
+  } else {
+    out_op4<TM>(xe_op + 4 * i, oxe.x, oxe.y, oxe.z, oxe.w);
+  }
+}
+template <typename TM, bool H2, bool GD, int TH>
+__global__ __launch_bounds__(256) void solver_update_th_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
+                                                               const float* __restrict__ x0, float* __restrict__ xe, TM* __restrict__ xe_op,
+                                                               float* __restrict__ xbar, float* __restrict__ d1,
+                                                               float* __restrict__ mprev, size_t n4, int split,
+                                                               float* __restrict__ mprev2, SolverGuide gd, SolverCorrect cx) {
+  static_assert(TH == 1 || TH == 2, "the uncorrected update is solver_update_kernel");
+  op_mode_init<TM>();
+  const int step = *step_ptr;
+  const SolverCoef k = solver_coef(coef + (size_t)step * ncoef);
+  const float d2c = H2 ? coef[(size_t)step * ncoef + 10] : 0.f, pe = H2 ? coef[(size_t)step * ncoef + 11] : 0.f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
+    if constexpr (GD) {      // (ld % 4 == 0: a quad lies in one row, so in one item)
+      const float4 vxc = reinterpret_cast<const float4*>(x0)[i + n4];
+      const float sc = gd.scale[((4 * i) / (size_t)gd.ld) / (size_t)gd.T];
+      vx0 = make_float4(guided_x0(vx0.x, vxc.x, sc), guided_x0(vx0.y, vxc.y, sc), guided_x0(vx0.z, vxc.z, sc), guided_x0(vx0.w, vxc.w, sc));
+    }
+    const float4 vxe = reinterpret_cast<const float4*>(xe)[i];
+    const float4 vxb = reinterpret_cast<const float4*>(xbar)[i];
+    const float4 vd1 = reinterpret_cast<const float4*>(d1)[i];
+    const float4 vmp = reinterpret_cast<const float4*>(mprev)[i];
+    float4 oxe, oxb, od1, om;
+    {                             // (ld % 4 == 0: a quad lies in one row, so in one item)
+      const float sb = TH == 1 ? fmaxf(cx.thr[((4 * i) / (size_t)cx.ld) / (size_t)cx.T], cx.max_val) : cx.max_val;
+      if constexpr (H2) {
+        const float4 vm2 = reinterpret_cast<const float4*>(mprev2)[i];
+        solver_upd2_c<TH>(k, sb, d2c, pe, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxe.x, oxb.x, od1.x, om.x);
+        solver_upd2_c<TH>(k, sb, d2c, pe, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxe.y, oxb.y, od1.y, om.y);
+        solver_upd2_c<TH>(k, sb, d2c, pe, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxe.z, oxb.z, od1.z, om.z);
+        solver_upd2_c<TH>(k, sb, d2c, pe, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxe.w, oxb.w, od1.w, om.w);
+        out_f4(mprev2 + 4 * i, vmp.x, vmp.y, vmp.z, vmp.w);
+      } else {
+        solver_upd_c<TH>(k, sb, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, oxe.x, oxb.x, od1.x, om.x);
+        solver_upd_c<TH>(k, sb, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
+        solver_upd_c<TH>(k, sb, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
+        solver_upd_c<TH>(k, sb, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
+      }
+    }
+    solver_store_xe<TM>(xe, xe_op, i, split, oxe);
+    if constexpr (GD) solver_store_xe<TM>(xe, xe_op, i + n4, split, oxe);      // the conditional half evaluates at the same point (pair row r + n*T)
+    out_f4(xbar + 4 * i, oxb.x, oxb.y, oxb.z, oxb.w);
+    out_f4(d1 + 4 * i, od1.x, od1.y, od1.z, od1.w);
+    out_f4(mprev + 4 * i, om.x, om.y, om.z, om.w);
+  }
+}
+// ---------------------------------------------------------------------------
+// Per-item quantile of |m| for the dynamic thresholding of the predicted x0 (sampler/dpm_solver.py:416-425, sampler/uni_pc.py:268-277:
+// torch.quantile(|x0|.reshape(B, -1), p, dim=1)).  EXACT: a radix select over the IEEE bit pattern of |m| (for non-negative floats the unsigned
+// order of the 31 low bits is the value order; a NaN sorts above every finite key), three digit passes of 11 + 10 + 10 bits, each a sweep of the
+// item that counts the keys matching the prefix chosen so far into a 32-bit LDS histogram, then a block scan that picks the bin holding rank lo.
+// The last pass leaves v_lo; v_hi == v_lo when at least two keys of that value remain at or above rank lo, else it is the next occupied bin
+// of the last histogram, else (none: the next key differs in a higher digit) the minimum of the keys above v_lo by one more sweep.  Only integer
+// counts and minima decide, so the result does not depend on scheduling.  thr[b] = torch's lerp of (v_lo, v_hi) at w = pos - lo,
+// pos = p * (n - 1) in float32 (ns2vc_amd.schedule.abs_quantile is the host statement).
+// One workgroup of 1024 threads per item and no communication between workgroups; every loop bound is a function of T, ld and the block size
+// (lens is clamped to [0, T]).  An item's elements are rows t < lens[b] (NULL: T) and columns c < nc of its T rows of ld columns.
+// SRC (compile time): 0 = the rows hold ready values; 1 = m is formed from x0, xe and the table row as the update forms it (solver_m); 2 = the same
+// on guided_x0 of the two halves of x0 (q.half elements apart).  An item without elements gives 0.
+// ---------------------------------------------------------------------------
+template <int SRC>
+__device__ __forceinline__ void quant_keys(const QuantArgs& q, const SolverCoef& k, float sc, size_t base, int quad, int ldq, unsigned key[4], int& nk) {
+  const int t = quad / ldq, c = (quad - t * ldq) * 4;
+  nk = min(4, q.nc - c);                       // (<= 0: a quad of padding columns)
+  if (nk <= 0) return;
+  const size_t e = base + (size_t)t * q.ld + c;
+  float4 v = *reinterpret_cast<const float4*>(q.v + e);
+  if constexpr (SRC != 0) {
+    if constexpr (SRC == 2) {
+      const float4 vc = *reinterpret_cast<const float4*>(q.v + q.half + e);
+      v = make_float4(guided_x0(v.x, vc.x, sc), guided_x0(v.y, vc.y, sc), guided_x0(v.z, vc.z, sc), guided_x0(v.w, vc.w, sc));
+    }
+    const float4 x = *reinterpret_cast<const float4*>(q.xe + e);
+    v = make_float4(solver_m(k, v.x, x.x), solver_m(k, v.y, x.y), solver_m(k, v.z, x.z), solver_m(k, v.w, x.w));
+  }
+  key[0] = __float_as_uint(v.x) & 0x7FFFFFFFu; key[1] = __float_as_uint(v.y) & 0x7FFFFFFFu;
+  key[2] = __float_as_uint(v.z) & 0x7FFFFFFFu; key[3] = __float_as_uint(v.w) & 0x7FFFFFFFu;
+}
+template <int SRC>
+__global__ __launch_bounds__(1024) void abs_quantile_kernel(QuantArgs q, float* __restrict__ thr) {
+  constexpr int NT = 1024, NBIN = 2048;
+  __shared__ unsigned s_hist[NBIN];
+  __shared__ unsigned s_wave[16];
+  __shared__ unsigned s_sel[4];                // chosen bin, keys below it, its count, minimum above
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+  const int len = q.lens ? min(max(q.lens[b], 0), q.T) : q.T;
+  const int ldq = q.ld >> 2, nquad = len * ldq;
+  const unsigned n = (unsigned)len * (unsigned)q.nc;
+  if (n == 0) {                                // (block-uniform)
+    if (tid == 0) thr[b] = 0.f;
+    return;
+  }
+  SolverCoef k{};
+  float sc = 1.f;
+  if constexpr (SRC != 0) k = solver_coef(q.coef + (size_t)(*q.step_ptr) * q.ncoef);
+  if constexpr (SRC == 2) sc = q.scale[b];
+  const size_t base = (size_t)b * q.T * q.ld;
+  const float pos = q.p * (float)(n - 1);
+  const unsigned lo = min((unsigned)floorf(pos), n - 1), hi = min((unsigned)ceilf(pos), n - 1);
+  const float w = pos - (float)lo;
+  unsigned prefix = 0, pmask = 0, rank = lo, eq = 0;
+#pragma unroll 1
+  for (int pass = 0; pass < 3; ++pass) {
+    const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0);
+    const unsigned dmask = pass == 0 ? 0x7FFu : 0x3FFu;
+    for (int i = tid; i < NBIN; i += NT) s_hist[i] = 0;      // (the last reads of the pass before lie in front of its second barrier)
+    if (pass == 0 && tid < 4) s_sel[tid] = tid == 3 ? 0xFFFFFFFFu : 0u;
+    __syncthreads();
+    for (int quad = tid; quad < nquad; quad += NT) {
+      unsigned key[4]; int nk;
+      quant_keys<SRC>(q, k, sc, base, quad, ldq, key, nk);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nk && (key[j] & pmask) == prefix) atomicAdd(&s_hist[(key[j] >> shift) & dmask], 1u);
+    }
+    __syncthreads();
+    // block scan of the bins (two per thread, in bin order); the thread whose bins hold rank `rank` records the choice
+    const unsigned h0 = s_hist[2 * tid], h1 = s_hist[2 * tid + 1];
+    unsigned incl = h0 + h1;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(incl, o); if (lane >= o) incl += u; }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    unsigned before = 0;
+    for (int v = 0; v < wave; ++v) before += s_wave[v];
+    const unsigned excl = before + incl - (h0 + h1);
+    if (rank >= excl && rank < excl + h0) { s_sel[0] = 2 * tid; s_sel[1] = excl; s_sel[2] = h0; }
+    else if (rank >= excl + h0 && rank < excl + h0 + h1) { s_sel[0] = 2 * tid + 1; s_sel[1] = excl + h0; s_sel[2] = h1; }
+    __syncthreads();
+    const unsigned d = s_sel[0];
+    prefix |= d << shift;
+    pmask |= dmask << shift;
+    rank -= s_sel[1];
+    eq = s_sel[2];
+  }
+  // v_lo = prefix; `eq` keys hold that value and `rank` of them lie below rank lo
+  unsigned vhi = prefix;
+  if (hi != lo && rank + 2 > eq) {             // (block-uniform) the key of rank lo + 1 is the smallest one above v_lo
+    const unsigned d = prefix & 0x3FFu;
+    const unsigned c0 = 2 * tid, c1 = 2 * tid + 1;
+    unsigned cand = 0xFFFFFFFFu;
+    if (c1 < 1024u && c1 > d && s_hist[c1]) cand = c1;
+    if (c0 < 1024u && c0 > d && s_hist[c0]) cand = c0;
+    if (cand != 0xFFFFFFFFu) atomicMin(&s_sel[3], (prefix & ~0x3FFu) | cand);
+    __syncthreads();
+    const unsigned next_bin = s_sel[3];
+    __syncthreads();                           // (every thread has read it before anyone lowers it again)
+    if (next_bin == 0xFFFFFFFFu) {             // (block-uniform) no occupied bin above: sweep for the minimum of the keys above v_lo
+      unsigned mn = 0xFFFFFFFFu;
+      for (int quad = tid; quad < nquad; quad += NT) {
+        unsigned key[4]; int nk;
+        quant_keys<SRC>(q, k, sc, base, quad, ldq, key, nk);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < nk && key[j] > prefix) mn = min(mn, key[j]);
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) mn = min(mn, (unsigned)__shfl_xor(mn, o));
+      if (lane == 0 && mn != 0xFFFFFFFFu) atomicMin(&s_sel[3], mn);
+      __syncthreads();
+    }
+    vhi = s_sel[3] == 0xFFFFFFFFu ? prefix : s_sel[3];
+  }
+  if (tid == 0) {
+    const float a = __uint_as_float(prefix), e = __uint_as_float(vhi), dlt = e - a;
+    thr[b] = w < 0.5f ? fmaf(w, dlt, a) : fmaf(-dlt, 1.0f - w, e);     // torch's lerp
+  }
+}
 // the normals of ns2vc_k_noise: one thread per (row, channel quad), the same philox_gauss4 the update adds
 __global__ __launch_bounds__(256) void noise_kernel(const unsigned long long* __restrict__ seeds, int B, int nc, int T, int ld, int step,
                                                     const int* __restrict__ lens, float* __restrict__ out) {
@@ -824,7 +1012,7 @@ hipError_t launch_prompt_bias(const uint8_t* mask, const int* plens, int B, int 
 }
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0, float* xe, void* xe_op, int prec,
                                 float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise, float* mprev2,
-                                const SolverGuide& guide) {
+                                const SolverGuide& guide, const SolverCorrect& cx) {
   if ((n & 3) || (split && (prec == PREC_F32 || (split & 3) || n % (size_t)split))) return hipErrorInvalidValue;
   if (noise.seeds && (noise.ld <= 0 || (noise.ld & 3) || noise.T <= 0 || noise.nc > noise.ld || n % ((size_t)noise.ld * noise.T))) return hipErrorInvalidValue;
   if (mprev2 && (noise.seeds || ncoef < 12)) return hipErrorInvalidValue;
@@ -832,8 +1020,27 @@ hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoe
   if (guide.scale && (guide.T <= 0 || guide.ld <= 0 || (guide.ld & 3) || n == 0 || n % ((size_t)guide.T * guide.ld) || (split && split != guide.ld) ||
                       (noise.seeds && (noise.T != guide.T || noise.ld != guide.ld))))
     return hipErrorInvalidValue;
+  // corrected: whole items of T rows of ld columns, a threshold table with mode 1, no noise term -- refused rather than run uncorrected
+  if (cx.mode && (cx.mode < 0 || cx.mode > 2 || noise.seeds || cx.T <= 0 || cx.ld <= 0 || (cx.ld & 3) || n == 0 || n % ((size_t)cx.T * cx.ld) ||
+                  (cx.mode == 1 && !cx.thr) || !(cx.max_val > 0.f) || !std::isfinite(cx.max_val) || (guide.scale && (guide.T != cx.T || guide.ld != cx.ld))))
+    return hipErrorInvalidValue;
   const size_t n4 = n >> 2;
   const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+  if (cx.mode) {
+#define NS2VC_SOLVER_TH_LAUNCH(H2, GD, TH)                                                                                                             \
+  NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_th_kernel<TMX, H2, GD, TH>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op, \
+                                         xbar, d1, mprev, n4, split, mprev2, guide, cx))
+#define NS2VC_SOLVER_TH_FORM(TH)                                                                                       \
+  if (guide.scale) {                                                                                                   \
+    if (mprev2) { NS2VC_SOLVER_TH_LAUNCH(true, true, TH); } else { NS2VC_SOLVER_TH_LAUNCH(false, true, TH); }         \
+  } else {                                                                                                             \
+    if (mprev2) { NS2VC_SOLVER_TH_LAUNCH(true, false, TH); } else { NS2VC_SOLVER_TH_LAUNCH(false, false, TH); }       \
+  }
+    if (cx.mode == 1) { NS2VC_SOLVER_TH_FORM(1) } else { NS2VC_SOLVER_TH_FORM(2) }
+#undef NS2VC_SOLVER_TH_FORM
+#undef NS2VC_SOLVER_TH_LAUNCH
+    return hipGetLastError();
+  }
 #define NS2VC_SOLVER_LAUNCH(H2, GD)                                                                                                                \
   NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_kernel<TMX, H2, GD>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op, \
                                          xbar, d1, mprev, n4, split, noise, mprev2, guide))
@@ -843,6 +1050,18 @@ hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoe
     if (mprev2) { NS2VC_SOLVER_LAUNCH(true, false); } else { NS2VC_SOLVER_LAUNCH(false, false); }
   }
 #undef NS2VC_SOLVER_LAUNCH
+  return hipGetLastError();
+}
+hipError_t launch_abs_quantile(const QuantArgs& q, int n_items, float* thr, hipStream_t s) {
+  if (!q.v || !thr || n_items <= 0 || q.T <= 0 || q.ld <= 0 || (q.ld & 3) || q.nc <= 0 || q.nc > q.ld || !(q.p >= 0.f && q.p <= 1.f) ||
+      ((uintptr_t)q.v & 15) || (size_t)q.T * (size_t)q.ld > 0x7FFFFFFFull)
+    return hipErrorInvalidValue;
+  const bool formed = q.xe != nullptr;
+  if (formed && (!q.coef || !q.step_ptr || q.ncoef < 9 || ((uintptr_t)q.xe & 15))) return hipErrorInvalidValue;
+  if (q.scale && (!formed || q.half == 0 || (q.half & 3))) return hipErrorInvalidValue;
+  if (q.scale) hipLaunchKernelGGL(abs_quantile_kernel<2>, dim3(n_items), dim3(1024), 0, s, q, thr);
+  else if (formed) hipLaunchKernelGGL(abs_quantile_kernel<1>, dim3(n_items), dim3(1024), 0, s, q, thr);
+  else hipLaunchKernelGGL(abs_quantile_kernel<0>, dim3(n_items), dim3(1024), 0, s, q, thr);
   return hipGetLastError();
 }
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s) {

@@ -11,6 +11,7 @@ using namespace ns2vc;
 // (same arithmetic, element for element: common.h solver_upd) -- x0 is never written, the state tensors are read and written once instead of twice
 bool ns2vc::solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
   if (h->guide.on) return false;                       // (the epilogue has no guided form: fuse_solver is ignored under guidance)
+  if (h->x0c.mode) return false;                       // (nor a corrected one: the threshold needs the whole x0 first)
   if (!h->fuse_solver || h->debug || h->conv_out_idx < 0 || h->conv_out_idx != (int)h->fwd_ops.size() - 1) return false;
   // (masked plan: the update must see x0 with its padded rows zeroed -- conv_out's epilogue has not zeroed them -- so it stays a launch of its own)
   if (h->lens.masked) return false;
@@ -132,6 +133,35 @@ int ns2vc_sampler_set_guidance(ns2vc_unet* h, const float* scale_host, int n, vo
   return guidance_onoff(h, true, n);
 }
 
+// the threshold buffer of the dynamic thresholding for at least n items; a new one invalidates the captured step graph (its launches hold the pointer)
+static int ensure_thr(ns2vc_unet* h, int n) {
+  if (h->x0c.thr && h->x0c.cap >= n) return 0;
+  drop_step_graph(h);
+  if (h->x0c.thr) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->x0c.thr)); h->x0c.thr = nullptr; h->x0c.cap = 0; }
+  const int cap = (n + 3) & ~3;
+  HIPCHK(hipMalloc((void**)&h->x0c.thr, (size_t)cap * sizeof(float)));
+  HIPCHK(hipMemset(h->x0c.thr, 0, (size_t)cap * sizeof(float)));
+  h->x0c.cap = cap;
+  return 0;
+}
+static int x0_correction_set(ns2vc_unet* h, int mode, float ratio, float max_val) {
+  // the step graph bakes in what the active mode passes to its launches: mode 1 the ratio (quantile launch) and max_val (update), mode 2 max_val alone,
+  // mode 0 nothing -- a change of a value no launch takes recaptures nothing
+  const bool same = mode == h->x0c.mode && (mode == 0 || (max_val == h->x0c.max_val && (mode == 2 || ratio == h->x0c.ratio)));
+  if (!same) drop_step_graph(h);
+  h->x0c.mode = mode; h->x0c.ratio = ratio; h->x0c.max_val = max_val;
+  if (mode == 1 && h->B > 0 && ensure_thr(h, h->B)) return 1;
+  return 0;
+}
+
+int ns2vc_sampler_set_x0_correction(ns2vc_unet* h, int mode, float ratio, float max_val) {
+  if (check_ready(h, false)) return 1;
+  if (mode < 0 || mode > 2) return fail("x0 correction mode %d: 0 (off), 1 (dynamic thresholding) or 2 (clamp)", mode);
+  if (!(ratio >= 0.f && ratio <= 1.f)) return fail("dynamic thresholding ratio %g outside [0, 1]", (double)ratio);
+  if (!(std::isfinite(max_val) && max_val > 0.f)) return fail("thresholding max_val %g must be finite and > 0", (double)max_val);
+  return x0_correction_set(h, mode, ratio, max_val);
+}
+
 // one evaluation + solver update
 static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
   GemmArgs g;
@@ -165,8 +195,19 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
   if (h->stochastic) {       // noise on the item's valid frames and real channels only (masked plan: level-0 lengths = the first B entries)
     nz.seeds = h->seeds.dev; nz.lens = h->lens.masked ? h->lens.dev : nullptr; nz.T = h->T; nz.ld = h->CP; nz.nc = h->cfg.latent_channels;
   }
+  SolverCorrect cx;
+  if (h->x0c.mode) {         // (not with a stochastic table: ns2vc_sampler_begin refuses the pair)
+    cx.mode = h->x0c.mode; cx.max_val = h->x0c.max_val; cx.T = h->T; cx.ld = h->CP;
+    if (h->x0c.mode == 1) {  // the item's |m| quantile over its valid frames and real channels, from the update's own operands
+      QuantArgs q;
+      q.v = h->x0; q.xe = h->xe; q.coef = h->coef_dev; q.step_ptr = h->step_dev; q.ncoef = NS2VC_NCOEF; q.scale = gd.scale; q.half = gd.scale ? n : 0;
+      q.lens = h->lens.masked ? h->lens.dev : nullptr; q.T = h->T; q.ld = h->CP; q.nc = h->cfg.latent_channels; q.p = h->x0c.ratio;
+      HIPCHK(launch_abs_quantile(q, h->loop_items(), h->x0c.thr, s));
+      cx.thr = h->x0c.thr;
+    }
+  }
   HIPCHK(launch_solver_update(h->coef_dev, h->step_dev, NS2VC_NCOEF, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s, h->pair_off(), nz,
-                              h->hist2.on ? h->hist2.mprev2 : nullptr, gd));
+                              h->hist2.on ? h->hist2.mprev2 : nullptr, gd, cx));
   return 0;
 }
 
@@ -177,6 +218,10 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   if (!x_T_bct) return fail("null tensor");
   if (!h->coef_dev || h->steps <= 0) return fail("no solver table loaded (call ns2vc_sampler_load)");
   if (h->stochastic && !h->seeds.set) return fail("the loaded solver table adds noise: set per-item seeds first (ns2vc_sampler_set_seeds)");
+  if (h->stochastic && h->x0c.mode)
+    return fail("the x0 correction (mode %d) does not apply to a stochastic table (ddpm, ddim with eta > 0): the reference's discrete samplers have none; "
+                "turn it off (ns2vc_sampler_set_x0_correction) or load a noise-free table", h->x0c.mode);
+  if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)h->B * h->T * h->CP;
   if (h->guide.on) {      // n items of x_T into the unconditional half, the same point into the conditional half
@@ -212,6 +257,8 @@ int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream)
   if (!h->coef_dev || h->steps <= 0) return fail("no solver table loaded (call ns2vc_sampler_load)");
   if (h->next_step < 0) return fail("no sampling loop in progress (call ns2vc_sampler_begin or ns2vc_sampler_handoff)");
   if (h->hist2.on && !h->hist2.mprev2) return fail("history-2 table without its m_prev2 buffer (begin the loop after loading the table)");
+  if (h->stochastic && h->x0c.mode) return fail("the x0 correction does not apply to a stochastic table");
+  if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
   if (n_steps < 0 || h->next_step + n_steps > h->steps) return fail("steps %d..%d outside the loaded table of %d", h->next_step, h->next_step + n_steps, h->steps);
   hipStream_t s = (hipStream_t)stream;
   const auto& c = h->cfg;
@@ -247,7 +294,7 @@ int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream)
 // Solver state of `src` (x_e, x_bar, d1, m_prev, m_prev2 of history-2 tables, loop position) -> `dst`, which continues the SAME table from there: the
 // engines may differ in precision (the state is fp32 in every mode; dst's operand copy of x_e is rebuilt in its own type).
 // Both must be prepared for the same (B, T) and hold the same solver table and condition.  The guidance of `src` (on / off, n, the scales)
-// becomes that of `dst`; a guided loop's histories live in the first halves, and x_e and its operand copy in both.
+// and its x0 correction (mode, ratio, max_val) become those of `dst`; a guided loop's histories live in the first halves, and x_e and its operand copy in both.
 int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   if (check_ready(dst, true) || check_ready(src, true)) return 1;
   if (dst == src) return fail("handoff to the same engine");
@@ -264,6 +311,7 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
     HIPCHK(launch_copy16(src->guide.dev, dst->guide.dev, (size_t)((src->guide.n + 3) & ~3) * sizeof(float), s));
   }
   guidance_onoff(dst, src->guide.on, src->guide.n);
+  if (x0_correction_set(dst, src->x0c.mode, src->x0c.ratio, src->x0c.max_val)) return 1;      // (the tail corrects as the head does)
   HIPCHK(launch_copy16(src->xe, dst->xe, n * sizeof(float), s));
   HIPCHK(launch_copy16(src->xbar, dst->xbar, nh * sizeof(float), s));
   HIPCHK(launch_copy16(src->d1, dst->d1, nh * sizeof(float), s));

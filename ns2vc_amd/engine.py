@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Ns2vcError, PREC_BF16, PREC_F16, PREC_F32, check
-from .schedule import NCOEF, SolverTable, build_table
+from .schedule import NCOEF, SolverTable, build_table, check_x0_correction
 from .spec import UNetConfig, engine_block_types, engine_supports, param_spec
 
 # operand precision of the MFMAs (include/ns2vc_hip.h): fp16 is the default 16-bit mode -- same speed and bytes as bf16,
@@ -202,6 +202,7 @@ class Engine:
         self.lengths: Optional[np.ndarray] = None      # per-item valid frames (set_lengths), None = dense
         self.prompt_lengths: Optional[np.ndarray] = None   # per-item prompt frames (set_prompt_lengths), None = every item Lp
         self.guidance: Optional[np.ndarray] = None      # per-item guidance scales (set_guidance), None = unguided
+        self.x0_correction = None                       # (mode 1 | 2, ratio, max_val) of set_x0_correction, None = off
         self.table: Optional[SolverTable] = None
         self._weights_ready = False
         self._debug = False
@@ -372,6 +373,15 @@ class Engine:
         check(self.lib.ns2vc_sampler_set_guidance(self.h, a.ctypes.data, int(a.shape[0]), _stream_ptr(stream)), "set_guidance")
         self.guidance = a.copy()
 
+    def set_x0_correction(self, mode=None, ratio: float = 0.995, max_val: float = 1.0) -> None:
+        """Correction of the predicted x0 inside the sampling loop, the reference solvers' ``correcting_x0_fn`` (``schedule.correct_x0``):
+        ``mode`` None (off) | "dynamic_thresholding" (per item and step s = max(quantile_ratio(|m|), max_val), m = clamp(m, -s, s) / s, the
+        quantile over the item's own frames and channels) | "clamp" (m = clamp(m, -max_val, max_val)).  ``mode`` may also be the engine's number 0 | 1 | 2.  A change of the
+        mode, or of a value the active mode passes to its launches (clamp: max_val; dynamic thresholding: both), recaptures the step graph; ``prepare`` leaves the setting alone; a hand-off gives it to the tail.  Not with ddim / ddpm tables."""
+        m = check_x0_correction(mode, ratio, max_val)
+        check(self.lib.ns2vc_sampler_set_x0_correction(self.h, m, float(ratio), float(max_val)), "set_x0_correction")
+        self.x0_correction = None if m == 0 else (m, float(np.float32(ratio)), float(np.float32(max_val)))
+
     def forward(self, x, t, out, stream=None) -> None:
         """x (B,100,T), t (B,) fp32, out (B,100,T): one denoiser evaluation."""
         check(self.lib.ns2vc_unet_forward(self.h, _ptr(x), _ptr(t), _ptr(out), _stream_ptr(stream)), "forward")
@@ -409,6 +419,7 @@ class Engine:
         check(self.lib.ns2vc_sampler_steps(self.h, n - k, int(use_graph), sp), "sampler_steps")
         check(self.lib.ns2vc_sampler_handoff(tail.h, self.h, sp), "sampler_handoff")
         tail.guidance = None if self.guidance is None else self.guidance.copy()      # (the hand-off carries the guidance over)
+        tail.x0_correction = self.x0_correction                                        # (... and the x0 correction)
         check(self.lib.ns2vc_sampler_steps(tail.h, k, int(use_graph), sp), "sampler_steps(tail)")
         check(self.lib.ns2vc_sampler_end(tail.h, _ptr(x_inout), sp), "sampler_end")
 

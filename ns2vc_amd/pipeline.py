@@ -15,7 +15,7 @@ import numpy as np
 from . import dist as _dist
 from .engine import DEFAULT_PRECISION, Engine
 from .noise import draw_seeds
-from .schedule import DISCRETE_SOLVERS, SOLVERS, linear_betas, table_options
+from .schedule import DISCRETE_SOLVERS, SOLVERS, check_x0_correction, linear_betas, table_options
 from .spec import UNetConfig, attention_workgroups_per_forward
 
 
@@ -49,6 +49,31 @@ def guided_tail_extra(scales) -> int:
     s = np.asarray(scales, dtype=np.float64).reshape(-1)
     g = float(np.sqrt((1.0 - s) ** 2 + s ** 2).max()) if s.size else 1.0
     return 0 if g <= 1.0 else int(np.ceil(np.log(g) / np.log(3.0) - 1e-9))
+# relative L2 of ONE evaluation of a 16-bit engine against the exact result at the bench shape (README "parity"; bf16: the upper end of the
+# 6.4e-3 .. 7.0e-3 that tests/test_engine_gpu.py measures), and the bar a sampled latent is held to
+EVALUATION_ERROR = {"fp16": 7.2e-4, "bf16": 7.0e-3}
+PARITY_BAR = 1e-3
+
+
+def corrected_tail_min(precision: str, scales=None) -> int:
+    """fewest trailing fp32 evaluations of a 16-bit loop that runs an x0 correction (``correcting_x0_fn``).  A corrected model value is
+    clamp(m, -s, s) / s with s an order statistic of the same evaluation's |m|, so the 16-bit rounding of an evaluation reaches it twice:
+    d(m / s) = dm / s - m ds / s^2, the element's own error and the threshold's, which moves every element of the item the same way and is not
+    averaged down over the item.  Each is bounded by one evaluation's relative error e1 (``EVALUATION_ERROR``), so a corrected last evaluation
+    carries up to g e1 with g = 2 (times sqrt((1 - s)^2 + s^2) of the largest guidance scale, as ``guided_tail_extra``), and every fp32
+    evaluation at the end of a loop lowers the latent's error about threefold (same docstring).  ceil(log3(g e1 / bar)) of them bring it under the
+    bar: 1 for fp16 (2 x 7.2e-4 = 1.44e-3), 3 for bf16 (1.4e-2).  It is a floor under the default tail (+ ``guided_tail_extra``), not an
+    addition: a default tail that already runs as many evaluations in fp32 needs no more."""
+    e1 = EVALUATION_ERROR.get(precision)
+    if e1 is None:
+        return 0
+    g = 2.0
+    if scales is not None:
+        s = np.asarray(scales, dtype=np.float64).reshape(-1)
+        g *= max(1.0, float(np.sqrt((1.0 - s) ** 2 + s ** 2).max())) if s.size else 1.0
+    return max(0, int(np.ceil(np.log(g * e1 / PARITY_BAR) / np.log(3.0) - 1e-9)))
+
+
 # LayerNorm-by-linearity guard thresholds on max |mean|/std (see Denoiser): 16-bit modes lose ~ratio * 2^-11 on a row,
 # fp32 loses ~ratio^2 * 2^-24 in the variance E[x^2] - mean^2
 LN_GUARD_DEFAULT = {"fp16": 8.0, "bf16": 8.0, "fp32": 32.0}
@@ -218,6 +243,14 @@ class Denoiser:
                 self._tail_table_key = None
         self._shape = None
         self._table_key = None
+
+    @staticmethod
+    def _x0_correction(eng, corr) -> None:
+        """``corr`` = (correcting_x0_fn, ratio, max_val) or None on ``eng``; nothing reaches an engine that is off and stays off"""
+        if corr is not None:
+            eng.set_x0_correction(*corr)
+        elif getattr(eng, "x0_correction", None) is not None:
+            eng.set_x0_correction(None)
 
     def _betas_for(self, solver: str) -> np.ndarray:
         return self.betas64 if solver in DISCRETE_SOLVERS else self.betas
@@ -464,12 +497,15 @@ class Denoiser:
 
     def _check_sampler_args(self, solver: str, steps: Optional[int], eta: float, B: int, seeds, order: int = 2, guidance_scale=1.0,
                             unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None,
-                            unconditional_content=None, **options) -> int:
+                            unconditional_content=None, correcting_x0_fn=None, thresholding_max_val=1.0, dynamic_thresholding_ratio=0.995,
+                            **options) -> int:
         """the argument errors of ``sample``, raised before anything runs; returns the step count"""
         self._check_guidance_args(B, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
                                   unconditional_content)
         if solver not in SOLVERS:
             raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True) and solver in DISCRETE_SOLVERS:
+            raise ValueError(f"correcting_x0_fn applies to unipc / dpmsolver++ only (the reference's {solver} sampler has no correction)")
         table_options(options)                  # unknown option names
         if eta != 0.0 and solver != "ddim":
             raise ValueError(f"eta is DDIM's noise scale (ddim_sampling_eta); solver {solver!r} takes none")
@@ -489,7 +525,8 @@ class Denoiser:
     def sample(self, content, prompt, prompt_mask=None, noise=None, solver: str = "unipc", steps: Optional[int] = None, order: int = 2,
                use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None,
                prompt_lengths=None, guidance_scale=1.0, unconditional_prompt=None, unconditional_prompt_mask=None,
-               unconditional_prompt_lengths=None, unconditional_content=None, **options):
+               unconditional_prompt_lengths=None, unconditional_content=None, correcting_x0_fn=None, thresholding_max_val: float = 1.0,
+               dynamic_thresholding_ratio: float = 0.995, **options):
         """content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool; ``noise`` (B,100,T) = x_T (drawn with
         torch.randn like model.py:635 if None).  Returns the sampled latent (B,100,T) fp32.
         ``solver``: ``unipc`` | ``dpmsolver++`` (``order`` 1 | 2 | 3, multistep) or the reference's discrete samplers ``ddim`` (``eta`` =
@@ -506,6 +543,13 @@ class Denoiser:
         ``unconditional_prompt_lengths`` and ``unconditional_content`` (default: ``content``) describe the unconditional half; Lu may differ
         from Lp.  An item with scale 1 follows its unguided trajectory; with every scale 1, or no unconditional prompt, nothing guided runs
         and the call is today's B-item loop (uni_pc.py:222-223).
+        ``correcting_x0_fn`` None | "dynamic_thresholding" | "clamp" with ``thresholding_max_val`` and ``dynamic_thresholding_ratio``: the
+        constructor options of the reference's ``UniPC`` / ``DPM_Solver`` (uni_pc.py:236-294, dpm_solver.py:338-442) inside the captured loop,
+        on the 16-bit engine and the fp32 tail alike (``Engine.set_x0_correction``, ``schedule.correct_x0``): every step corrects the (guided)
+        predicted x0 in front of the update -- per item s = max(quantile_ratio(|x0|), max_val) over the item's own frames, clamp(x0, -s, s) / s;
+        "clamp" is clamp(x0, -max_val, max_val), the common callable.  unipc / dpmsolver++ only; a callable, or anything else but these names,
+        is refused (ValueError).  A 16-bit loop under a correction runs at least ``corrected_tail_min(precision, scales)`` trailing
+        evaluations on the fp32 engine unless ``tail_fp32`` says otherwise (1 for fp16, 3 for bf16).
         ``options`` (keyword-only): the reference's ``UniPC.sample`` / ``DPM_Solver.sample`` keywords that ``schedule.build_table`` serves
         -- ``skip_type``, ``lower_order_final``, ``denoise_to_zero`` (one more evaluation), ``variant`` (UniPC), ``solver_type``
         (DPM-Solver++), ``t_start``, ``t_end``, ``method`` ("multistep" only)."""
@@ -513,10 +557,13 @@ class Denoiser:
         B, _, T = content.shape
         dev = content.device
         steps = self._check_sampler_args(solver, steps, eta, B, seeds, order, guidance_scale, unconditional_prompt, unconditional_prompt_mask,
-                                         unconditional_prompt_lengths, unconditional_content, **options)
+                                         unconditional_prompt_lengths, unconditional_content, correcting_x0_fn, thresholding_max_val,
+                                         dynamic_thresholding_ratio, **options)
         scales = self._guidance_scales(B, guidance_scale, unconditional_prompt)
         guide_kw = dict(guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
-                        unconditional_prompt_lengths=unconditional_prompt_lengths, unconditional_content=unconditional_content)
+                        unconditional_prompt_lengths=unconditional_prompt_lengths, unconditional_content=unconditional_content,
+                        correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio)
+        corr = (correcting_x0_fn, float(dynamic_thresholding_ratio), float(thresholding_max_val)) if correcting_x0_fn is not None else None
         rep = 1
         if scales is not None:      # the engine's batch is cat([unconditional, conditional]); the loop still takes and gives B items
             content_c, prompt_c, prompt_mask_c, lengths_c, prompt_lengths_c = content, prompt, prompt_mask, lengths, prompt_lengths
@@ -528,6 +575,7 @@ class Denoiser:
         self._prepare(rep * B, T, prompt.shape[1])
         if scales is not None or self.engine.guidance is not None:
             self.engine.set_guidance(scales, stream=torch.cuda.current_stream(dev))
+        self._x0_correction(self.engine, corr)
         self._table(solver, steps, order, eta, **options)
         nfe = self.engine.table.steps               # (steps + 1 with denoise_to_zero)
         n_tail = tail_fp32 if tail_fp32 is not None else self.tail_fp32
@@ -535,6 +583,8 @@ class Denoiser:
             n_tail = default_tail_fp32(solver, order) if self.precision != "fp32" else 0
             if scales is not None and self.precision != "fp32":      # guidance multiplies the 16-bit rounding of the last evaluations
                 n_tail += guided_tail_extra(scales)
+            if corr is not None and self.precision != "fp32":        # ... and a correction lets it in twice (corrected_tail_min)
+                n_tail = max(n_tail, corrected_tail_min(self.precision, scales))
         n_tail = max(0, min(int(n_tail), nfe))
         if noise is None:
             noise = torch.randn((B, self.cfg.latent_channels, T), device=dev, generator=generator)
@@ -554,6 +604,8 @@ class Denoiser:
         tail = self._tail(solver, steps, order, n_tail, eta, **options)
         if tail is not None and (scales is not None or tail.guidance is not None):
             tail.set_guidance(scales, stream=s)
+        if tail is not None:
+            self._x0_correction(tail, corr)
         if tail is not None and stochastic:
             tail.set_seeds(seeds, stream=s)
         if self.serving_fp32:            # a failed precision check: the whole loop on the fp32 engine
@@ -625,7 +677,8 @@ class OverlappedPipeline:
 
     def __init__(self, denoiser: Denoiser, pre_fn, post_fn, solver: str = "unipc", steps: Optional[int] = 20, order: int = 2,
                  use_graph: bool = True, pre_device=None, post_device=None, stage_cus=None, denoiser_cus=None, eta: float = 0.0,
-                 guidance_scale=1.0, unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None, **options):
+                 guidance_scale=1.0, unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None,
+                 correcting_x0_fn=None, thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995, **options):
         """``pre_device`` / ``post_device`` (r4): run the front / back end on ANOTHER ROCm device of the node.  On one GPU the three streams
         serialise (the denoiser's launches hold every CU: 7.8 % of the stages' kernel time overlaps, profiles/r03_overlap_trace.txt); a stage
         on its own device overlaps by construction and only its tensors cross xGMI -- content + prompt 35 MB per 32 x 10 s batch in, the
@@ -634,6 +687,7 @@ class OverlappedPipeline:
         NOT measured on two devices yet (no multi-GPU box this round).
         ``guidance_scale`` / ``unconditional_prompt`` (1, Lu, 256) / ``unconditional_prompt_mask`` / ``unconditional_prompt_lengths``: classifier-free
         guidance with one unconditional prompt for every item of every batch (``Denoiser.sample``), passed through.
+        ``correcting_x0_fn`` / ``thresholding_max_val`` / ``dynamic_thresholding_ratio``: the x0 correction of ``Denoiser.sample``, passed through.
         ``options``: the keyword-only sampler options of ``Denoiser.sample`` (``skip_type``, ``denoise_to_zero``, ...), passed through."""
         import torch
         if not torch.cuda.is_available():
@@ -641,6 +695,10 @@ class OverlappedPipeline:
         self.denoiser, self.pre_fn, self.post_fn = denoiser, pre_fn, post_fn
         table_options(options)
         self.kw = dict(solver=solver, steps=steps, order=order, use_graph=use_graph, eta=eta, **options)
+        if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True):
+            if solver in DISCRETE_SOLVERS:
+                raise ValueError(f"correcting_x0_fn applies to unipc / dpmsolver++ only, not {solver!r}")
+            self.kw.update(correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio)
         if unconditional_prompt is not None:
             self.kw.update(guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
                            unconditional_prompt_lengths=unconditional_prompt_lengths)

@@ -409,16 +409,90 @@ def guided_x0(x0_u: np.ndarray, x0_c: np.ndarray, scale) -> np.ndarray:
         return np.where(s == 1, x0_c, x0_u + s * (x0_c - x0_u)).astype(x0_c.dtype)
 
 
+X0_CORRECTIONS = {None: 0, "dynamic_thresholding": 1, "clamp": 2}      # Denoiser.sample(correcting_x0_fn=) -> the engine's mode
+
+
+def abs_quantile(a: np.ndarray, p: float) -> np.float32:
+    """``torch.quantile(|a|.reshape(-1), p)`` of a float32 array, bit for bit: linear interpolation between the ascending order statistics
+    evaluated in float32 -- pos = f32(p) * f32(n - 1), lo = floor(pos), hi = ceil(pos), w = pos - lo -- and torch's own lerp, a fused
+    multiply-add from the nearer end: v_lo + w (v_hi - v_lo) where w < 0.5, v_hi - (v_hi - v_lo)(1 - w) otherwise.  The engine's radix
+    select (misc.hip abs_quantile_kernel) finds the same v_lo, v_hi and evaluates the same expression."""
+    f = np.float32
+    v = np.sort(np.abs(np.asarray(a, dtype=f)).reshape(-1))
+    n = v.shape[0]
+    if n == 0:
+        raise ValueError("abs_quantile of an empty array")
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"p must be in [0, 1], got {p}")
+    pos = f(p) * f(n - 1)
+    lo, hi = int(np.floor(pos)), int(np.ceil(pos))
+    w = f(pos - f(lo))
+    d = np.float64(f(v[hi] - v[lo]))      # (the product of two float32 is exact in float64: one rounding, as the fused form)
+    if w < f(0.5):
+        return f(np.float64(w) * d + np.float64(v[lo]))
+    return f(np.float64(v[hi]) - d * np.float64(f(f(1) - w)))
+
+
+def check_x0_correction(mode, ratio: float = 0.995, max_val: float = 1.0, names_only: bool = False) -> int:
+    """the argument errors of the x0 correction (ValueError); ``mode`` None | "dynamic_thresholding" | "clamp" -> 0 | 1 | 2.  The engine's own
+    numbers 0 | 1 | 2 are accepted too (``Engine.set_x0_correction``, ``correct_x0``) unless ``names_only``: the public keyword
+    ``correcting_x0_fn`` of ``Denoiser.sample`` and the classes around it takes the names alone."""
+    if callable(mode):
+        raise ValueError("correcting_x0_fn: a callable cannot run inside the captured loop; pass 'dynamic_thresholding', 'clamp' or None")
+    if not names_only and isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and int(mode) in (0, 1, 2):
+        m = int(mode)
+    elif mode is None or isinstance(mode, str) and mode in X0_CORRECTIONS:
+        m = X0_CORRECTIONS[mode]
+    else:
+        raise ValueError(f"correcting_x0_fn must be None, 'dynamic_thresholding' or 'clamp', got {mode!r}")
+    try:
+        r, v = float(ratio), float(max_val)
+    except (TypeError, ValueError):
+        raise ValueError(f"dynamic_thresholding_ratio and thresholding_max_val must be numbers, got {ratio!r}, {max_val!r}") from None
+    if not 0.0 <= r <= 1.0:      # (NaN fails both comparisons)
+        raise ValueError(f"dynamic_thresholding_ratio must be in [0, 1], got {ratio!r}")
+    if not (np.isfinite(v) and v > 0.0):
+        raise ValueError(f"thresholding_max_val must be finite and > 0, got {max_val!r}")
+    return m
+
+
+def correct_x0(m: np.ndarray, mode, ratio: float = 0.995, max_val: float = 1.0, lengths=None) -> np.ndarray:
+    """The reference's correction of the predicted x0 (sampler/dpm_solver.py:416-425, :433-442, sampler/uni_pc.py:268-294), float32, on
+    ``m`` (B, C, T) -- the model value after the x_start round trip.  ``dynamic_thresholding``: per item s = max(abs_quantile(m_b, ratio),
+    max_val), clamp(m_b, -s, s) / s, the quantile over the item's own frames t < lengths[b] (all T without lengths: what the reference
+    computes for the item alone at T = lengths[b]).  ``clamp``: clamp(m, -max_val, max_val).  The frames past an item's end pass through
+    the same clamp (zeros stay zeros)."""
+    mode = check_x0_correction(mode, ratio, max_val)
+    f = np.float32
+    m = np.asarray(m, dtype=f)
+    if mode == 0:
+        return m
+    if mode == 2:
+        return np.clip(m, f(-max_val), f(max_val))
+    out = np.empty_like(m)
+    for b in range(m.shape[0]):
+        L = m.shape[-1] if lengths is None else int(lengths[b])
+        s = max(abs_quantile(m[b, ..., :L], ratio), f(max_val))
+        out[b] = np.clip(m[b], -s, s) / s
+    return out
+
+
+_correct_x0 = correct_x0      # (run_table_numpy has a keyword of that name)
+
+
 def has_history2(table: SolverTable) -> bool:
     """the table needs m_prev2 (some row of order 3): what the engine's ns2vc_sampler_load detects from columns 10-11"""
     return bool((np.asarray(table.coef)[:, 10:12] != 0).any())
 
 
 def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarray], x_T: np.ndarray,
-                    trace: Optional[List[np.ndarray]] = None, noise_fn: Optional[Callable[[int], np.ndarray]] = None) -> np.ndarray:
+                    trace: Optional[List[np.ndarray]] = None, noise_fn: Optional[Callable[[int], np.ndarray]] = None,
+                    correct_x0: Optional[Dict[str, object]] = None) -> np.ndarray:
     """Host executor of the unified recurrence (float32), used by CPU tests to pin
     the tables against the oracle samplers.  ``x0_fn(x, t_model[B]) -> x0``.  ``noise_fn(i)`` -> the standard normals of
-    step i, shaped like x_T (ns2vc_amd.noise.gauss), for tables with a nonzero noise column."""
+    step i, shaped like x_T (ns2vc_amd.noise.gauss), for tables with a nonzero noise column.
+    ``correct_x0``: None (off) or the keywords of ``schedule.correct_x0`` -- ``dict(mode=, ratio=, max_val=, lengths=)`` -- applied to m
+    in front of everything that uses it (the reference's ``data_prediction_fn``); not together with a noise column."""
     f = np.float32
     xbar = x_T.astype(f).copy()
     xe = xbar.copy()
@@ -427,11 +501,16 @@ def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray]
     m_prev2 = np.zeros_like(xbar)
     hist2 = has_history2(table)
     B = x_T.shape[0]
+    if correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)) \
+            and (np.asarray(table.coef)[:, 9] != 0).any():
+        raise ValueError(f"the x0 correction does not apply to a stochastic {table.solver} table (the reference's discrete samplers have none)")
     for i in range(table.steps):
         t_model, alpha, sigma, g0, g1, A, Bc, d1c, pc = (f(v) for v in table.coef[i, :9])
         x0 = x0_fn(xe, np.full((B,), t_model, dtype=f)).astype(f)
         eps = (xe - alpha * x0) / sigma
         m = (xe - sigma * eps) / alpha
+        if correct_x0 is not None:
+            m = _correct_x0(m, **correct_x0)
         x = xbar - g0 * d1 - g1 * (m - m_prev)
         xbar = A * x - Bc * m
         if table.coef[i, 9] != 0:

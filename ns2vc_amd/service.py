@@ -44,7 +44,7 @@ import numpy as np
 from .frontend import PreModel
 from .noise import derive_seed
 from .pipeline import Denoiser, OverlappedPipeline
-from .schedule import table_options
+from .schedule import DISCRETE_SOLVERS, check_x0_correction, table_options
 
 
 @dataclass
@@ -73,8 +73,10 @@ class GroupedConverter:
                  solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, ragged: bool = False, eta: float = 0.0,
                  masked_fuse: Optional[bool] = None, masked_attn: Optional[bool] = None,
                  masked_rows: Optional[bool] = None, masked_ffn: Optional[bool] = None, masked_geglu: Optional[bool] = None,
-                 ragged_prompts: bool = False, guidance_scale: float = 1.0, unconditional_prompt: Optional[torch.Tensor] = None, **options):
-        """``guidance_scale`` with ``unconditional_prompt`` (1, Lu, 256), one for every segment: classifier-free guidance
+                 ragged_prompts: bool = False, guidance_scale: float = 1.0, unconditional_prompt: Optional[torch.Tensor] = None,
+                 correcting_x0_fn=None, thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995, **options):
+        """``correcting_x0_fn`` / ``thresholding_max_val`` / ``dynamic_thresholding_ratio``: the x0 correction of ``Denoiser.sample``, passed through.
+        ``guidance_scale`` with ``unconditional_prompt`` (1, Lu, 256), one for every segment: classifier-free guidance
         (``Denoiser.sample``).  The engine then runs two items per segment, so a batch holds at most ``max_batch // 2`` segments."""
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
         if masked_fuse is not None and bool(masked_fuse) != denoiser.masked_fuse:     # the denoiser's engine option of that name (ragged batches only)
@@ -102,6 +104,10 @@ class GroupedConverter:
         self.kw = dict(solver=solver, steps=steps, order=order, eta=eta, **options)
         if self.guided:
             self.kw.update(guidance_scale=float(guidance_scale), unconditional_prompt=unconditional_prompt)
+        if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True):
+            if solver in DISCRETE_SOLVERS:
+                raise ValueError(f"correcting_x0_fn applies to unipc / dpmsolver++ only, not {solver!r}")
+            self.kw.update(correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio)
 
     def _seeds(self, idx) -> np.ndarray:
         """per-SEGMENT noise seeds of the stochastic samplers, from the converter's seed and the segment's position in the input"""
