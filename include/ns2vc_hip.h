@@ -195,6 +195,20 @@ int ns2vc_unet_forward(ns2vc_unet* h, const float* x_bct, const float* t_b, floa
  * UniPC.sample sampler/uni_pc.py:606-658 incl. the x_start wrapper :271-292/:170-191).
  * `coef` = host array [steps][NS2VC_NCOEF] built by ns2vc_amd.schedule.build_table. */
 int ns2vc_sampler_load(ns2vc_unet* h, int steps, const float* coef_host);
+/* Per-item schedules (backward-compatible addition to ABI v7): every item of one batch runs its own solver / steps / order inside ONE loop --
+ * what took one DPM_Solver.sample / UniPC.sample call (sampler/dpm_solver.py:1171-1213, sampler/uni_pc.py:606-658) per group of requests that
+ * agree on every sampler setting.  table_rows = HOST [n_tables] row counts of the distinct tables, coef_host = their rows back to back
+ * ([sum(table_rows)][NS2VC_NCOEF], at most 1024 rows together: the device table's fixed capacity); item b of the n_items loop items (the
+ * prepared B; n under guidance -- set the guidance first) walks table item_table[b] beginning at loop step item_start[b] >= 0.  The loop runs
+ * S = max_b(item_start[b] + rows_b) steps; at loop step r item b is ACTIVE when 0 <= r - item_start[b] < rows_b and uses that row of its table;
+ * otherwise it is HELD: its evaluation runs at the clamped row's timestep, its result is ignored and no bit of its solver state changes.  Every
+ * item ends on what ns2vc_sampler_load with its table alone gives it, bit for bit; a stochastic item's Philox row word is its local row.  The
+ * records go to the device on `stream` from pinned staging: new schedules of the same form replay the captured step graph; switching the form on
+ * (this call) or off (ns2vc_sampler_load), and a change of the batch's union of "some item has history 2" / "some item adds noise", recapture.
+ * ns2vc_sampler_begin needs seeds when some item adds noise; the x0 correction stays per batch and is refused then; ns2vc_sampler_handoff needs
+ * the same tables and records on both engines.  ns2vc_amd.schedule.build_tables / run_tables_numpy are the host statement. */
+int ns2vc_sampler_load_items(ns2vc_unet* h, int n_tables, const int32_t* table_rows, const float* coef_host, int n_items, const int32_t* item_table,
+                             const int32_t* item_start, void* stream);
 /* x (B, latent_channels, T): x_T in, sample out.  use_graph != 0 replays one captured
  * hipGraph per step (no host sync inside the loop). */
 int ns2vc_sampler_run(ns2vc_unet* h, float* x_inout_bct, int use_graph, void* stream);
@@ -637,6 +651,16 @@ int ns2vc_k_abs_quantile(const float* values, int n_items, int T, int ld, int nc
 int ns2vc_k_solver_update_corrected(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
                                     float* d1, float* mprev, float* mprev2, size_t n, int ld, int T, const float* scale_dev, const int32_t* lens_dev,
                                     int nc, int mode, float ratio, float max_val, float* thr_dev, void* stream);
+/* One solver update under per-item schedules as the loop makes it (backward-compatible addition to ABI v7; see ns2vc_sampler_load_items):
+ * items_host = HOST [n_items][4] int32 records (row0, steps, start, flags: 1 = history 2, 2 = noise) into coef_dev of n_rows rows, checked
+ * here and copied to the device by the call, which also waits for `stream` (a test hook).  At loop step r = *step_dev item b is active when
+ * 0 <= r - start < steps and gets the update of ns2vc_k_solver_update (flags 1: its history-2 form; 2: with the noise term, Philox row word
+ * r - start) / _guided (scale_dev set: n = the elements of ONE half) / _corrected (mode 1 | 2) on row row0 + r - start; every other item keeps
+ * every bit of xe, xe_op, xbar, d1, mprev, mprev2 and thr_dev[b].  n = n_items * T * ld. */
+int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t* step_dev, const int32_t* items_host, int n_items, const float* x0, float* xe,
+                                void* xe_op, int precision, float* xbar, float* d1, float* mprev, float* mprev2, size_t n, int ld, int T,
+                                const float* scale_dev, const uint64_t* seeds_dev, const int32_t* lens_dev, int nc, int mode, float ratio, float max_val,
+                                float* thr_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -153,6 +153,7 @@ PROTOTYPES = {
     "ns2vc_unet_set_prompt_lengths": (_I, [_P, _P, _P]),
     "ns2vc_unet_forward": (_I, [_P, _P, _P, _P, _P]),
     "ns2vc_sampler_load": (_I, [_P, _I, C.POINTER(C.c_float)]),
+    "ns2vc_sampler_load_items": (_I, [_P, _I, _P, C.POINTER(C.c_float), _I, _P, _P, _P]),
     "ns2vc_sampler_run": (_I, [_P, _P, _I, _P]),
     "ns2vc_sampler_begin": (_I, [_P, _P, _P]),
     "ns2vc_sampler_steps": (_I, [_P, _I, _I, _P]),
@@ -228,6 +229,8 @@ PROTOTYPES = {
     "ns2vc_k_solver_update_guided": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _P, _I, _P, _P, _I, _P]),
     "ns2vc_k_abs_quantile": (_I, [_P, _I, _I, _I, _I, _P, C.c_float, _P, _P]),
     "ns2vc_k_solver_update_corrected": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P]),
+    "ns2vc_k_solver_update_items": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _I, _P, _P, _P, _I, _I, C.c_float, C.c_float,
+                                         _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -413,6 +413,57 @@ int ns2vc_k_solver_update_corrected(const float* coef_dev, const int32_t* step_d
   return launched(launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n, (hipStream_t)stream,
                                       precision != PREC_F32 ? ld : 0, SolverNoise(), mprev2, gd, cx), "corrected solver_update launch");
 }
+int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t* step_dev, const int32_t* items_host, int n_items, const float* x0, float* xe,
+                                void* xe_op, int precision, float* xbar, float* d1, float* mprev, float* mprev2, size_t n, int ld, int T,
+                                const float* scale_dev, const uint64_t* seeds_dev, const int32_t* lens_dev, int nc, int mode, float ratio, float max_val,
+                                float* thr_dev, void* stream) {
+  if (!coef_dev || !step_dev || !items_host || !x0 || !xe || !xe_op || !xbar || !d1 || !mprev) return fail("null argument");
+  if (mode < 0 || mode > 2) return fail("items update: mode %d must be 0 (off), 1 (dynamic thresholding) or 2 (clamp)", mode);
+  if (mode == 1 && !thr_dev) return fail("dynamic thresholding needs thr_dev");
+  if (ld <= 0 || (ld & 3) || T <= 0 || n_items <= 0 || n != (size_t)n_items * T * ld)
+    return fail("n (%zu) must hold the %d items of T (%d) rows of ld (%d) columns, ld a multiple of 4", n, n_items, T, ld);
+  if (mode && (!(ratio >= 0.f && ratio <= 1.f) || !(max_val > 0.f))) return fail("ratio %g must be in [0, 1] and max_val %g > 0", (double)ratio, (double)max_val);
+  static_assert(sizeof(SolverItem) == 4 * sizeof(int32_t), "records are four 32-bit words");
+  for (int b = 0; b < n_items; ++b) {      // the records name rows of the table and buffers the launch reads: checked here, the kernel trusts them
+    const int32_t* r = items_host + 4 * (size_t)b;
+    if (r[0] < 0 || r[1] <= 0 || r[2] < 0 || (long)r[0] + r[1] > n_rows) return fail("item %d: rows %d + %d outside the table of %d, or start %d < 0", b, r[0], r[1], n_rows, r[2]);
+    if ((r[3] & ~(SOLVER_ITEM_HIST2 | SOLVER_ITEM_NOISE)) || r[3] == (SOLVER_ITEM_HIST2 | SOLVER_ITEM_NOISE)) return fail("item %d: flags %d", b, r[3]);
+    if ((r[3] & SOLVER_ITEM_HIST2) && !mprev2) return fail("item %d runs history 2: mprev2 is needed", b);
+    if ((r[3] & SOLVER_ITEM_NOISE) && (!seeds_dev || mode)) return fail("item %d is stochastic: seeds_dev is needed and no correction applies", b);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  SolverItem* rec = nullptr;
+  HIPCHK(hipMalloc((void**)&rec, (size_t)n_items * sizeof(SolverItem)));
+  int rc = 1;
+  if (hipMemcpy(rec, items_host, (size_t)n_items * sizeof(SolverItem), hipMemcpyHostToDevice) == hipSuccess) {
+    SolverItems si;
+    si.rec = rec; si.T = T; si.ld = ld;
+    SolverGuide gd;
+    if (scale_dev) { gd.scale = scale_dev; gd.T = T; gd.ld = ld; }
+    SolverNoise nz;
+    if (seeds_dev) { nz.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev); nz.lens = lens_dev; nz.T = T; nz.ld = ld; nz.nc = nc; }
+    SolverCorrect cx;
+    rc = 0;
+    if (mode) {
+      cx.mode = mode; cx.max_val = max_val; cx.T = T; cx.ld = ld;
+      if (mode == 1) {
+        QuantArgs q;
+        q.v = x0; q.xe = xe; q.coef = coef_dev; q.step_ptr = step_dev; q.ncoef = NS2VC_NCOEF; q.scale = scale_dev; q.half = scale_dev ? n : 0;
+        q.lens = lens_dev; q.T = T; q.ld = ld; q.nc = nc; q.p = ratio;
+        rc = launched(launch_abs_quantile_items(q, rec, n_items, thr_dev, s), "abs_quantile_items launch");
+        cx.thr = thr_dev;
+      }
+    }
+    if (!rc)
+      rc = launched(launch_solver_update_items(coef_dev, step_dev, NS2VC_NCOEF, si, x0, xe, xe_op, precision, xbar, d1, mprev, n, s,
+                                               precision != PREC_F32 ? ld : 0, nz, mprev2, gd, cx), "items solver_update launch");
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("items solver_update: stream synchronize failed");
+  } else {
+    (void)fail("items solver_update: copy of the records failed");
+  }
+  (void)hipFree(rec);
+  return rc;
+}
 int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream) {
   return launched(launch_noise(reinterpret_cast<const unsigned long long*>(seeds_dev), B, C, T, ld, step, lens_dev, out, (hipStream_t)stream), "noise launch");
 }

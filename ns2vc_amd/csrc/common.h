@@ -318,6 +318,19 @@ __device__ __forceinline__ float4 philox_gauss4(unsigned long long seed, uint32_
   return z;
 }
 
+// Per-item solver schedules (ns2vc_sampler_load_items): loop item b walks rows [row0, row0 + steps) of the coefficient table, which holds the
+// rows of all distinct tables of the batch, beginning at loop step `start`.  At loop step r the item is ACTIVE when 0 <= r - start < steps and
+// uses row row0 + (r - start); otherwise it is HELD: its evaluation runs at the clamped row's timestep and nothing of its state is touched.
+// ns2vc_amd.schedule.run_tables_numpy is the host statement.
+struct SolverItem { int row0, steps, start, flags; };
+constexpr int SOLVER_ITEM_HIST2 = 1;      // the item's table has a nonzero column 10 or 11: solver_upd2 on all its rows, m_prev2 rolled
+constexpr int SOLVER_ITEM_NOISE = 2;      // ... a nonzero column 9: the noise term, Philox "table row" word = the item's local row
+__device__ __forceinline__ int solver_item_row(const SolverItem& it, int r, bool& active) {
+  const int j = r - it.start;
+  active = j >= 0 && j < it.steps;
+  return it.row0 + min(max(j, 0), it.steps - 1);
+}
+
 constexpr double GN_SUM_SCALE = 268435456.0;   // 2^28
 constexpr double GN_SQ_SCALE = 65536.0;        // 2^16
 
@@ -430,6 +443,16 @@ hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoe
                                 float* mprev2 = nullptr,        // non-NULL: the history-2 update (order-3 tables; m_{i-2} in, m_{i-1} out); no noise with it
                                 const SolverGuide& guide = SolverGuide(),
                                 const SolverCorrect& correct = SolverCorrect());
+// per-item schedules: rec = DEVICE [items] records (SolverItem above) of items of T rows of ld columns.  The update, the quantile and the time
+// embedding of a step then take every item's own table row; a held item is left alone (launch_solver_update_items, launch_abs_quantile_items: thr[b]
+// of a held item keeps its value) or evaluated at its clamped row (launch_emb_items_from_table: B engine rows read the n_items records B / n_items times)
+struct SolverItems { const SolverItem* rec = nullptr; int T = 0, ld = 0; };
+hipError_t launch_solver_update_items(const float* coef, const int* step_ptr, int ncoef, const SolverItems& items, const float* x0, float* xe, void* xe_op,
+                                      int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise,
+                                      float* mprev2, const SolverGuide& guide, const SolverCorrect& correct);
+hipError_t launch_abs_quantile_items(const QuantArgs& q, const SolverItem* items, int n_items, float* thr, hipStream_t s);
+hipError_t launch_emb_items_from_table(const float* table, const int* step_ptr, const SolverItem* items, int n_items, const float* aug, float* emb,
+                                       void* emb_act_op, int prec, int B, int edim, hipStream_t s);
 // the normals a stochastic update adds at table row `step` (ns2vc_k_noise): out rows [B*T][ld] fp32, zeros where no noise goes
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s);
 hipError_t launch_fill_i32(int* p, int v, hipStream_t s);

@@ -305,6 +305,17 @@ struct ns2vc_unet {
     float* mprev2 = nullptr;
     size_t n = 0;
   } hist2;
+  // Per-item schedules (ns2vc_sampler_load_items): every loop item walks a solver table of its own (common.h SolverItem).  coef_dev then holds the
+  // `rows` rows of the distinct tables, `steps` the loop's length S = max(start + steps), `stochastic` / `hist2.on` the UNION over the items (what
+  // begin allocates and requires).  The records live in a buffer of their own outside the plan arena, filled from pinned staging (new schedules of
+  // the same form are a copy: the captured step graph stays valid); on / off, and a change of either union flag, recapture.
+  struct ItemSchedules {
+    bool on = false;
+    int n = 0, rows = 0;                   // loop items the records cover; rows of coef_dev in use
+    ns2vc::SolverItem* dev = nullptr;
+    int cap = 0;
+    ns2vc::Staged stage;
+  } items;
   // Correction of the predicted x0 (ns2vc_sampler_set_x0_correction): mode 1 = dynamic thresholding, 2 = clamp.  The ratio and max_val are
   // arguments of the step's launches, so a change of the mode or of a value the active mode passes drops the captured step graph.  The per-item thresholds of mode 1 live in a
   // buffer of their own outside the plan arena (one float per batch item), allocated when the correction is switched on.
@@ -351,6 +362,7 @@ struct ns2vc_unet {
     if (guide.dev) (void)hipFree(guide.dev);
     if (hist2.mprev2) (void)hipFree(hist2.mprev2);
     if (x0c.thr) (void)hipFree(x0c.thr);
+    if (items.dev) (void)hipFree(items.dev);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     if (tfork.side_stream) (void)hipStreamDestroy(tfork.side_stream);

@@ -500,6 +500,26 @@ __global__ __launch_bounds__(256) void emb_from_table_kernel(const float* __rest
   emb[i] = y;
   store_op<TM>(emb_act + i, y / (1.0f + expf(-y)));
 }
+// Per-item schedules (ns2vc_sampler_load_items): the table holds the timestep MLP of the rows of ALL distinct solver tables and item b reads
+// the row of its own table at this loop step (common.h solver_item_row; a held item the clamped row -- its evaluation runs, its result is
+// ignored).  emb[b] = table[row(b, step)] + aug[b]: the same two fp32 additions in the same order.  The records cover nitems loop items; a
+// guided engine's 2 * nitems rows read them twice (both halves evaluate at the same timestep).
+template <typename TM>
+__global__ __launch_bounds__(256) void emb_items_from_table_kernel(const float* __restrict__ table, const int* __restrict__ step_ptr,
+                                                                   const SolverItem* __restrict__ items, int nitems,
+                                                                   const float* __restrict__ aug, float* __restrict__ emb,
+                                                                   TM* __restrict__ emb_act, int edim, int n) {
+  op_mode_init<TM>();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int b = i / edim, o = i - b * edim;
+  bool active;
+  const int row = solver_item_row(items[b % nitems], *step_ptr, active);
+  float y = table[(size_t)row * edim + o];
+  if (aug) y += aug[i];
+  emb[i] = y;
+  store_op<TM>(emb_act + i, y / (1.0f + expf(-y)));
+}
 
 // ---------------------------------------------------------------------------
 // API-boundary layout changes: reference tensors are NCT (B,C,T); the engine is
@@ -711,6 +731,115 @@ __global__ __launch_bounds__(256) void solver_update_th_kernel(const float* __re
     out_f4(mprev + 4 * i, om.x, om.y, om.z, om.w);
   }
 }
+// The update under per-item schedules (ns2vc_sampler_load_items): every loop item walks a solver table of its own.  Quad i belongs to item
+// b = (4 i / ld) / T (ld % 4 == 0: a quad lies in one row, so in one item -- the branches below are uniform per quad); its record (common.h
+// SolverItem) says where the item's rows sit in the coefficient table, how many there are, at which loop step it starts and which form it runs.
+// At loop step r = *step_ptr item b is ACTIVE when 0 <= r - start < steps and then uses row r - start of its table; otherwise it is HELD and
+// nothing of it is loaded or stored: xe, both planes of xe_op, xbar, d1, mprev and mprev2 keep their bits.  An active item runs what the
+// shared-table kernels run for its table, from the same inline functions: flag SOLVER_ITEM_HIST2 -> solver_upd2 and the roll of mprev2 (every row
+// of such an item, as solver_update_kernel<TM, true> does for such a table), else solver_upd; flag SOLVER_ITEM_NOISE -> the noise term of a row
+// with a nonzero column 9, its Philox "table row" word the item's LOCAL row, so the stream is what the item has alone.  TH (compile time): 0 = no
+// correction, 1 | 2 = solver_update_th_kernel's (no noise with it: the launcher refuses the pair).  GD as there: n4 counts the quads of one half,
+// the records cover the n loop items and both halves of xe / xe_op are written.  3 types x GD x TH = 18 instantiations; the item's form differs
+// between the items of one launch, so it is a run-time choice -- made by TWO sweeps over the quads, the first for the items without history 2,
+// the second (only with an mprev2 buffer) for those with it, each form's quad (solver_items_quad) a straight line from its loads to its stores.
+// One sweep that branched per quad and joined the two forms' results in front of common stores was one ulp off the shared-table kernels on x_e'
+// (seen on the device): the optimiser moves the last subtraction of the two forms into the block where they join, away from its products, and
+// the fused multiply-adds solver_update_kernel has are lost.  A kernel of its own for the reason solver_update_th_kernel is one.
+template <typename TM, bool GD, int TH, bool H2>
+__device__ __forceinline__ void solver_items_quad(const float* __restrict__ crow, int jrow, int b, size_t i, const float* __restrict__ x0,
+                                                  float* __restrict__ xe, TM* __restrict__ xe_op, float* __restrict__ xbar, float* __restrict__ d1,
+                                                  float* __restrict__ mprev, size_t n4, int split, const SolverNoise& nz, bool noisy,
+                                                  float* __restrict__ mprev2, const SolverGuide& gd, const SolverCorrect& cx, int T, int ld) {
+  const SolverCoef k = solver_coef(crow);
+  const float knz = (!H2 && TH == 0 && noisy) ? crow[9] : 0.f;      // 0 = no term at all, as in solver_update_kernel
+  const float d2c = H2 ? crow[10] : 0.f, pe = H2 ? crow[11] : 0.f;
+  float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
+  if constexpr (GD) {
+    const float4 vxc = reinterpret_cast<const float4*>(x0)[i + n4];
+    const float sc = gd.scale[b];
+    vx0 = make_float4(guided_x0(vx0.x, vxc.x, sc), guided_x0(vx0.y, vxc.y, sc), guided_x0(vx0.z, vxc.z, sc), guided_x0(vx0.w, vxc.w, sc));
+  }
+  const float4 vxe = reinterpret_cast<const float4*>(xe)[i];
+  const float4 vxb = reinterpret_cast<const float4*>(xbar)[i];
+  const float4 vd1 = reinterpret_cast<const float4*>(d1)[i];
+  const float4 vmp = reinterpret_cast<const float4*>(mprev)[i];
+  float4 oxe, oxb, od1, om;
+  if constexpr (TH != 0) {
+    const float sb = TH == 1 ? fmaxf(cx.thr[b], cx.max_val) : cx.max_val;
+    if constexpr (H2) {
+      const float4 vm2 = reinterpret_cast<const float4*>(mprev2)[i];
+      solver_upd2_c<TH>(k, sb, d2c, pe, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxe.x, oxb.x, od1.x, om.x);
+      solver_upd2_c<TH>(k, sb, d2c, pe, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxe.y, oxb.y, od1.y, om.y);
+      solver_upd2_c<TH>(k, sb, d2c, pe, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxe.z, oxb.z, od1.z, om.z);
+      solver_upd2_c<TH>(k, sb, d2c, pe, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxe.w, oxb.w, od1.w, om.w);
+      out_f4(mprev2 + 4 * i, vmp.x, vmp.y, vmp.z, vmp.w);
+    } else {
+      solver_upd_c<TH>(k, sb, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, oxe.x, oxb.x, od1.x, om.x);
+      solver_upd_c<TH>(k, sb, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
+      solver_upd_c<TH>(k, sb, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
+      solver_upd_c<TH>(k, sb, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
+    }
+  } else if constexpr (H2) {
+    const float4 vm2 = reinterpret_cast<const float4*>(mprev2)[i];
+    solver_upd2(k, d2c, pe, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxe.x, oxb.x, od1.x, om.x);
+    solver_upd2(k, d2c, pe, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxe.y, oxb.y, od1.y, om.y);
+    solver_upd2(k, d2c, pe, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxe.z, oxb.z, od1.z, om.z);
+    solver_upd2(k, d2c, pe, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxe.w, oxb.w, od1.w, om.w);
+    out_f4(mprev2 + 4 * i, vmp.x, vmp.y, vmp.z, vmp.w);
+  } else {
+    solver_upd(k, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, oxe.x, oxb.x, od1.x, om.x);
+    solver_upd(k, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
+    solver_upd(k, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
+    solver_upd(k, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
+  }
+  if (!H2 && TH == 0 && knz != 0.f) {      // xbar' += noise * z on the live elements, as in solver_update_kernel
+    const size_t e = 4 * i, r = e / (size_t)ld;
+    const int c = (int)(e - r * (size_t)ld), t = (int)(r - (size_t)b * T);
+    if (c < nz.nc && (!nz.lens || t < nz.lens[b])) {
+      const float4 z = philox_gauss4(nz.seeds[b], (uint32_t)t, (uint32_t)(c >> 2), (uint32_t)jrow);
+      oxb.x += knz * z.x;
+      if (c + 1 < nz.nc) oxb.y += knz * z.y;
+      if (c + 2 < nz.nc) oxb.z += knz * z.z;
+      if (c + 3 < nz.nc) oxb.w += knz * z.w;
+      oxe = make_float4(oxb.x - k.pc * od1.x, oxb.y - k.pc * od1.y, oxb.z - k.pc * od1.z, oxb.w - k.pc * od1.w);
+    }
+  }
+  solver_store_xe<TM>(xe, xe_op, i, split, oxe);
+  if constexpr (GD) solver_store_xe<TM>(xe, xe_op, i + n4, split, oxe);      // the conditional half evaluates at the same point (pair row r + n*T)
+  out_f4(xbar + 4 * i, oxb.x, oxb.y, oxb.z, oxb.w);
+  out_f4(d1 + 4 * i, od1.x, od1.y, od1.z, od1.w);
+  out_f4(mprev + 4 * i, om.x, om.y, om.z, om.w);
+}
+template <typename TM, bool GD, int TH>
+__global__ __launch_bounds__(256) void solver_update_items_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
+                                                                  SolverItems si, const float* __restrict__ x0, float* __restrict__ xe,
+                                                                  TM* __restrict__ xe_op, float* __restrict__ xbar, float* __restrict__ d1,
+                                                                  float* __restrict__ mprev, size_t n4, int split, SolverNoise nz,
+                                                                  float* __restrict__ mprev2, SolverGuide gd, SolverCorrect cx) {
+  static_assert(TH >= 0 && TH <= 2, "0 = uncorrected, 1 = dynamic thresholding, 2 = clamp");
+  op_mode_init<TM>();
+  const int step = *step_ptr;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const int b = (int)(((4 * i) / (size_t)si.ld) / (size_t)si.T);
+    const SolverItem it = si.rec[b];
+    bool active;
+    const int row = solver_item_row(it, step, active);
+    if (!active || (it.flags & SOLVER_ITEM_HIST2)) continue;      // held: nothing of this item is touched; history 2: the second sweep
+    solver_items_quad<TM, GD, TH, false>(coef + (size_t)row * ncoef, row - it.row0, b, i, x0, xe, xe_op, xbar, d1, mprev, n4, split, nz,
+                                         (it.flags & SOLVER_ITEM_NOISE) != 0, mprev2, gd, cx, si.T, si.ld);
+  }
+  if (!mprev2) return;                                            // (no item of the batch has history 2)
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const int b = (int)(((4 * i) / (size_t)si.ld) / (size_t)si.T);
+    const SolverItem it = si.rec[b];
+    bool active;
+    const int row = solver_item_row(it, step, active);
+    if (!active || !(it.flags & SOLVER_ITEM_HIST2)) continue;
+    solver_items_quad<TM, GD, TH, true>(coef + (size_t)row * ncoef, row - it.row0, b, i, x0, xe, xe_op, xbar, d1, mprev, n4, split, nz, false,
+                                        mprev2, gd, cx, si.T, si.ld);
+  }
+}
 // ---------------------------------------------------------------------------
 // Per-item quantile of |m| for the dynamic thresholding of the predicted x0 (sampler/dpm_solver.py:416-425, sampler/uni_pc.py:268-277:
 // torch.quantile(|x0|.reshape(B, -1), p, dim=1)).  EXACT: a radix select over the IEEE bit pattern of |m| (for non-negative floats the unsigned
@@ -760,6 +889,105 @@ __global__ __launch_bounds__(1024) void abs_quantile_kernel(QuantArgs q, float* 
   SolverCoef k{};
   float sc = 1.f;
   if constexpr (SRC != 0) k = solver_coef(q.coef + (size_t)(*q.step_ptr) * q.ncoef);
+  if constexpr (SRC == 2) sc = q.scale[b];
+  const size_t base = (size_t)b * q.T * q.ld;
+  const float pos = q.p * (float)(n - 1);
+  const unsigned lo = min((unsigned)floorf(pos), n - 1), hi = min((unsigned)ceilf(pos), n - 1);
+  const float w = pos - (float)lo;
+  unsigned prefix = 0, pmask = 0, rank = lo, eq = 0;
+#pragma unroll 1
+  for (int pass = 0; pass < 3; ++pass) {
+    const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0);
+    const unsigned dmask = pass == 0 ? 0x7FFu : 0x3FFu;
+    for (int i = tid; i < NBIN; i += NT) s_hist[i] = 0;      // (the last reads of the pass before lie in front of its second barrier)
+    if (pass == 0 && tid < 4) s_sel[tid] = tid == 3 ? 0xFFFFFFFFu : 0u;
+    __syncthreads();
+    for (int quad = tid; quad < nquad; quad += NT) {
+      unsigned key[4]; int nk;
+      quant_keys<SRC>(q, k, sc, base, quad, ldq, key, nk);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nk && (key[j] & pmask) == prefix) atomicAdd(&s_hist[(key[j] >> shift) & dmask], 1u);
+    }
+    __syncthreads();
+    // block scan of the bins (two per thread, in bin order); the thread whose bins hold rank `rank` records the choice
+    const unsigned h0 = s_hist[2 * tid], h1 = s_hist[2 * tid + 1];
+    unsigned incl = h0 + h1;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(incl, o); if (lane >= o) incl += u; }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    unsigned before = 0;
+    for (int v = 0; v < wave; ++v) before += s_wave[v];
+    const unsigned excl = before + incl - (h0 + h1);
+    if (rank >= excl && rank < excl + h0) { s_sel[0] = 2 * tid; s_sel[1] = excl; s_sel[2] = h0; }
+    else if (rank >= excl + h0 && rank < excl + h0 + h1) { s_sel[0] = 2 * tid + 1; s_sel[1] = excl + h0; s_sel[2] = h1; }
+    __syncthreads();
+    const unsigned d = s_sel[0];
+    prefix |= d << shift;
+    pmask |= dmask << shift;
+    rank -= s_sel[1];
+    eq = s_sel[2];
+  }
+  // v_lo = prefix; `eq` keys hold that value and `rank` of them lie below rank lo
+  unsigned vhi = prefix;
+  if (hi != lo && rank + 2 > eq) {             // (block-uniform) the key of rank lo + 1 is the smallest one above v_lo
+    const unsigned d = prefix & 0x3FFu;
+    const unsigned c0 = 2 * tid, c1 = 2 * tid + 1;
+    unsigned cand = 0xFFFFFFFFu;
+    if (c1 < 1024u && c1 > d && s_hist[c1]) cand = c1;
+    if (c0 < 1024u && c0 > d && s_hist[c0]) cand = c0;
+    if (cand != 0xFFFFFFFFu) atomicMin(&s_sel[3], (prefix & ~0x3FFu) | cand);
+    __syncthreads();
+    const unsigned next_bin = s_sel[3];
+    __syncthreads();                           // (every thread has read it before anyone lowers it again)
+    if (next_bin == 0xFFFFFFFFu) {             // (block-uniform) no occupied bin above: sweep for the minimum of the keys above v_lo
+      unsigned mn = 0xFFFFFFFFu;
+      for (int quad = tid; quad < nquad; quad += NT) {
+        unsigned key[4]; int nk;
+        quant_keys<SRC>(q, k, sc, base, quad, ldq, key, nk);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < nk && key[j] > prefix) mn = min(mn, key[j]);
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) mn = min(mn, (unsigned)__shfl_xor(mn, o));
+      if (lane == 0 && mn != 0xFFFFFFFFu) atomicMin(&s_sel[3], mn);
+      __syncthreads();
+    }
+    vhi = s_sel[3] == 0xFFFFFFFFu ? prefix : s_sel[3];
+  }
+  if (tid == 0) {
+    const float a = __uint_as_float(prefix), e = __uint_as_float(vhi), dlt = e - a;
+    thr[b] = w < 0.5f ? fmaf(w, dlt, a) : fmaf(-dlt, 1.0f - w, e);     // torch's lerp
+  }
+}
+// The same under per-item schedules (ns2vc_sampler_load_items; SRC 1 | 2: m is always formed there): item b's m comes from the row of its OWN
+// table at this loop step (common.h solver_item_row), and the workgroup of a held item returns at once and leaves thr[b] alone.  A kernel of its
+// own -- abs_quantile_kernel keeps its instructions (tools/kernel_code_diff.py) -- and otherwise its copy: keep the two in step.
+template <int SRC>
+__global__ __launch_bounds__(1024) void abs_quantile_items_kernel(QuantArgs q, float* __restrict__ thr, const SolverItem* __restrict__ items) {
+  static_assert(SRC == 1 || SRC == 2, "ready values have no table row");
+  constexpr int NT = 1024, NBIN = 2048;
+  __shared__ unsigned s_hist[NBIN];
+  __shared__ unsigned s_wave[16];
+  __shared__ unsigned s_sel[4];                // chosen bin, keys below it, its count, minimum above
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+  const int len = q.lens ? min(max(q.lens[b], 0), q.T) : q.T;
+  const int ldq = q.ld >> 2, nquad = len * ldq;
+  const unsigned n = (unsigned)len * (unsigned)q.nc;
+  SolverCoef k{};
+  float sc = 1.f;
+  {                                            // (block-uniform) a held item: nothing at all, thr[b] keeps its value
+    bool active;
+    const int row = solver_item_row(items[b], *q.step_ptr, active);
+    if (!active) return;
+    k = solver_coef(q.coef + (size_t)row * q.ncoef);
+  }
+  if (n == 0) {                                // (block-uniform)
+    if (tid == 0) thr[b] = 0.f;
+    return;
+  }
   if constexpr (SRC == 2) sc = q.scale[b];
   const size_t base = (size_t)b * q.T * q.ld;
   const float pos = q.p * (float)(n - 1);
@@ -1062,6 +1290,46 @@ hipError_t launch_abs_quantile(const QuantArgs& q, int n_items, float* thr, hipS
   if (q.scale) hipLaunchKernelGGL(abs_quantile_kernel<2>, dim3(n_items), dim3(1024), 0, s, q, thr);
   else if (formed) hipLaunchKernelGGL(abs_quantile_kernel<1>, dim3(n_items), dim3(1024), 0, s, q, thr);
   else hipLaunchKernelGGL(abs_quantile_kernel<0>, dim3(n_items), dim3(1024), 0, s, q, thr);
+  return hipGetLastError();
+}
+// the launches of a step under per-item schedules: whole items of si.T rows of si.ld columns, n = the elements of the n_items loop items (guided:
+// of one half), records for every one of them -- refused rather than run on the shared row
+hipError_t launch_solver_update_items(const float* coef, const int* step_ptr, int ncoef, const SolverItems& si, const float* x0, float* xe, void* xe_op,
+                                      int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise,
+                                      float* mprev2, const SolverGuide& guide, const SolverCorrect& cx) {
+  if (!si.rec || si.T <= 0 || si.ld <= 0 || (si.ld & 3) || n == 0 || n % ((size_t)si.T * si.ld) || ncoef < 12) return hipErrorInvalidValue;
+  if ((n & 3) || (split && (prec == PREC_F32 || split != si.ld))) return hipErrorInvalidValue;
+  if (noise.seeds && (noise.ld != si.ld || noise.T != si.T || noise.nc > noise.ld || cx.mode)) return hipErrorInvalidValue;
+  if (guide.scale && (guide.T != si.T || guide.ld != si.ld)) return hipErrorInvalidValue;
+  if (cx.mode && (cx.mode < 0 || cx.mode > 2 || cx.T != si.T || cx.ld != si.ld || (cx.mode == 1 && !cx.thr) || !(cx.max_val > 0.f) || !std::isfinite(cx.max_val)))
+    return hipErrorInvalidValue;
+  const size_t n4 = n >> 2;
+  const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+#define NS2VC_SOLVER_ITEMS_LAUNCH(GD, TH)                                                                                                        \
+  NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_items_kernel<TMX, GD, TH>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, si, x0, xe, \
+                                         (TMX*)xe_op, xbar, d1, mprev, n4, split, noise, mprev2, guide, cx))
+  if (guide.scale) {
+    if (cx.mode == 1) { NS2VC_SOLVER_ITEMS_LAUNCH(true, 1); } else if (cx.mode == 2) { NS2VC_SOLVER_ITEMS_LAUNCH(true, 2); } else { NS2VC_SOLVER_ITEMS_LAUNCH(true, 0); }
+  } else {
+    if (cx.mode == 1) { NS2VC_SOLVER_ITEMS_LAUNCH(false, 1); } else if (cx.mode == 2) { NS2VC_SOLVER_ITEMS_LAUNCH(false, 2); } else { NS2VC_SOLVER_ITEMS_LAUNCH(false, 0); }
+  }
+#undef NS2VC_SOLVER_ITEMS_LAUNCH
+  return hipGetLastError();
+}
+hipError_t launch_abs_quantile_items(const QuantArgs& q, const SolverItem* items, int n_items, float* thr, hipStream_t s) {
+  if (!items || !q.v || !q.xe || !q.coef || !q.step_ptr || q.ncoef < 9 || !thr || n_items <= 0 || q.T <= 0 || q.ld <= 0 || (q.ld & 3) || q.nc <= 0 || q.nc > q.ld ||
+      !(q.p >= 0.f && q.p <= 1.f) || (((uintptr_t)q.v | (uintptr_t)q.xe) & 15) || (size_t)q.T * (size_t)q.ld > 0x7FFFFFFFull || (q.scale && (q.half == 0 || (q.half & 3))))
+    return hipErrorInvalidValue;
+  if (q.scale) hipLaunchKernelGGL(abs_quantile_items_kernel<2>, dim3(n_items), dim3(1024), 0, s, q, thr, items);
+  else hipLaunchKernelGGL(abs_quantile_items_kernel<1>, dim3(n_items), dim3(1024), 0, s, q, thr, items);
+  return hipGetLastError();
+}
+hipError_t launch_emb_items_from_table(const float* table, const int* step_ptr, const SolverItem* items, int n_items, const float* aug, float* emb,
+                                       void* emb_act_op, int prec, int B, int edim, hipStream_t s) {
+  if (!items || n_items <= 0 || B % n_items) return hipErrorInvalidValue;
+  const int n = B * edim;
+  NS2VC_BY_PREC(prec, hipLaunchKernelGGL(emb_items_from_table_kernel<TMX>, dim3((n + 255) / 256), dim3(256), 0, s, table, step_ptr, items, n_items, aug,
+                                         emb, (TMX*)emb_act_op, edim, n));
   return hipGetLastError();
 }
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s) {

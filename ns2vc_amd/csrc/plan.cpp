@@ -674,6 +674,9 @@ int build_plan(ns2vc_unet* h, bool sizing) {
     if (!sizing) { h->tfork.begin = (int)h->fwd_ops.size(); h->tfork.join = h->tfork.first = -1; h->tfork.readers = 0; }
     P.add("time_embed", [=](hipStream_t s) {
       // sampling loop: the MLP of every step's timestep was evaluated once for the table (ns2vc_sampler_run), a step adds aug
+      // (per-item schedules: every item the row of its own table -- chosen at launch time like the table itself, the plan does not change)
+      if (hh->use_step_table && hh->items.on)
+        return launch_emb_items_from_table(hh->temb_table, hh->step_dev, hh->items.dev, hh->items.n, aug, emb, emb_act, eprec, B, E, s);
       if (hh->use_step_table) return launch_emb_from_table(hh->temb_table, hh->step_dev, aug, emb, emb_act, eprec, B, E, s);
       return launch_time_embed(tdev, 1, nullptr, 0, w1t, b1, w2t, b2, aug, emb, emb_act, eprec, B, tdim, E, s);
     });

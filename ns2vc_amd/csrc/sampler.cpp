@@ -18,6 +18,7 @@ bool ns2vc::solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
   if (h->conv_out_prec != h->prec) return false;      // (exact_io: conv_out runs in fp32 there, the operand copy of the state is 16-bit)
   if (h->stochastic) return false;                     // (the epilogue has no noise term: a stochastic table runs the stand-alone update)
   if (h->hist2.on) return false;                       // (nor an m_{i-2}: history-2 tables too)
+  if (h->items.on) return false;                       // (nor per-item rows: per-item schedules too)
   g = h->conv_out_g;
   g.out_f32 = nullptr;
   g.sol_coef = h->coef_dev; g.sol_step = h->step_dev; g.sol_ncoef = NS2VC_NCOEF;
@@ -49,9 +50,83 @@ int ns2vc_sampler_load(ns2vc_unet* h, int steps, const float* coef_host) {
   for (int i = 0; i < steps; ++i) hist2 |= coef_host[(size_t)i * NS2VC_NCOEF + 10] != 0.f || coef_host[(size_t)i * NS2VC_NCOEF + 11] != 0.f;
   if (stochastic && hist2) { h->steps = 0; return fail("a solver table with both a noise column and history 2 (columns 10-11) is not supported"); }
   // (the update's noise arguments and its history-2 form are baked into the captured step graph)
-  if (stochastic != h->stochastic || hist2 != h->hist2.on) drop_step_graph(h);
+  if (stochastic != h->stochastic || hist2 != h->hist2.on || h->items.on) drop_step_graph(h);      // (... and so is the per-item form, which a shared table switches off)
   h->stochastic = stochastic;
   h->hist2.on = hist2;
+  h->items.on = false;
+  return 0;
+}
+
+// Per-item schedules: the distinct tables' rows back to back in the coefficient table, one record per loop item.  The table pointer and the
+// records' pointer are baked into the captured step graph, their contents are not: new schedules of the same form replay it.
+int ns2vc_sampler_load_items(ns2vc_unet* h, int n_tables, const int32_t* table_rows, const float* coef_host, int n_items, const int32_t* item_table,
+                             const int32_t* item_start, void* stream) {
+  const int kMaxRows = 1024;    // fixed capacity of the coefficient table and of the timestep-embedding table (ns2vc_sampler_load's)
+  if (check_ready(h, true)) return 1;
+  if (!table_rows || !coef_host || !item_table || !item_start || n_tables <= 0 || n_items <= 0) return fail("bad per-item sampler tables");
+  if (n_items != h->loop_items())
+    return fail("per-item schedules for %d items, the loop takes %d (the prepared batch; n under guidance: set the guidance first)", n_items, h->loop_items());
+  std::vector<int> row0(n_tables), flags(n_tables, 0);
+  long rows = 0;
+  for (int k = 0; k < n_tables; ++k) {
+    if (table_rows[k] <= 0) return fail("table %d has %d rows", k, (int)table_rows[k]);
+    row0[k] = (int)rows;
+    rows += table_rows[k];
+    if (rows > kMaxRows) return fail("the distinct solver tables of the batch hold more than %d rows together (the table's fixed capacity)", kMaxRows);
+    for (int i = 0; i < table_rows[k]; ++i) {
+      const float* r = coef_host + (size_t)(row0[k] + i) * NS2VC_NCOEF;
+      if (r[9] != 0.f) flags[k] |= SOLVER_ITEM_NOISE;
+      if (r[10] != 0.f || r[11] != 0.f) flags[k] |= SOLVER_ITEM_HIST2;
+    }
+    if (flags[k] == (SOLVER_ITEM_NOISE | SOLVER_ITEM_HIST2))
+      return fail("table %d has both a noise column and history 2 (columns 10-11): not supported", k);
+  }
+  std::vector<SolverItem> rec(n_items);
+  int S = 0;
+  bool any_noise = false, any_h2 = false;
+  for (int b = 0; b < n_items; ++b) {
+    const int k = item_table[b];
+    if (k < 0 || k >= n_tables) return fail("item %d names table %d of %d", b, k, n_tables);
+    if (item_start[b] < 0 || item_start[b] > kMaxRows) return fail("item %d starts at loop step %d (0 .. %d)", b, (int)item_start[b], kMaxRows);
+    rec[b] = SolverItem{row0[k], (int)table_rows[k], (int)item_start[b], flags[k]};
+    S = std::max(S, rec[b].start + rec[b].steps);
+    any_noise |= (flags[k] & SOLVER_ITEM_NOISE) != 0;
+    any_h2 |= (flags[k] & SOLVER_ITEM_HIST2) != 0;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (!h->coef_dev) HIPCHK(hipMalloc((void**)&h->coef_dev, (size_t)kMaxRows * NS2VC_NCOEF * sizeof(float)));
+  if (!h->items.dev || h->items.cap < n_items) {      // a new records buffer invalidates the captured step graph (its launches hold the pointer)
+    drop_step_graph(h);
+    if (h->items.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->items.dev)); h->items.dev = nullptr; h->items.cap = 0; }
+    HIPCHK(hipMalloc((void**)&h->items.dev, (size_t)n_items * sizeof(SolverItem)));
+    h->items.cap = n_items;
+  }
+  HIPCHK(hipDeviceSynchronize());   // a previous loop may still be reading the table
+  HIPCHK(hipMemcpy(h->coef_dev, coef_host, (size_t)rows * NS2VC_NCOEF * sizeof(float), hipMemcpyHostToDevice));
+  Staged& st = h->items.stage;
+  const size_t nb = (size_t)n_items * sizeof(SolverItem);
+  if (st.reserve(nb)) return 1;
+  memcpy(st.buf, rec.data(), nb);
+  HIPCHK(hipMemcpyAsync(h->items.dev, st.buf, nb, hipMemcpyHostToDevice, s));
+  if (st.record(s)) return 1;
+  {      // the hand-off's table hash covers the rows and the records
+    unsigned long long hsh = 1469598103934665603ull;
+    const unsigned char* pb = reinterpret_cast<const unsigned char*>(coef_host);
+    for (size_t i = 0; i < (size_t)rows * NS2VC_NCOEF * sizeof(float); ++i) { hsh ^= pb[i]; hsh *= 1099511628211ull; }
+    pb = reinterpret_cast<const unsigned char*>(rec.data());
+    for (size_t i = 0; i < nb; ++i) { hsh ^= pb[i]; hsh *= 1099511628211ull; }
+    h->coef_hash = hsh;
+  }
+  // (which update runs, its noise arguments and its m_prev2 pointer are baked into the captured step graph)
+  if (!h->items.on || any_noise != h->stochastic || any_h2 != h->hist2.on) drop_step_graph(h);
+  h->items.on = true;
+  h->items.n = n_items;
+  h->items.rows = (int)rows;
+  h->steps = S;
+  h->stochastic = any_noise;
+  h->hist2.on = any_h2;
+  h->temb_table_valid = false;
+  h->next_step = -1;
   return 0;
 }
 
@@ -196,6 +271,24 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
     nz.seeds = h->seeds.dev; nz.lens = h->lens.masked ? h->lens.dev : nullptr; nz.T = h->T; nz.ld = h->CP; nz.nc = h->cfg.latent_channels;
   }
   SolverCorrect cx;
+  if (h->items.on) {         // per-item schedules: every item its own row, held items left alone (misc.hip solver_update_items_kernel)
+    if (h->items.n != h->loop_items()) return fail("per-item schedules for %d items, the loop has %d (load them again)", h->items.n, h->loop_items());
+    if (h->x0c.mode) {
+      cx.mode = h->x0c.mode; cx.max_val = h->x0c.max_val; cx.T = h->T; cx.ld = h->CP;
+      if (h->x0c.mode == 1) {
+        QuantArgs q;
+        q.v = h->x0; q.xe = h->xe; q.coef = h->coef_dev; q.step_ptr = h->step_dev; q.ncoef = NS2VC_NCOEF; q.scale = gd.scale; q.half = gd.scale ? n : 0;
+        q.lens = h->lens.masked ? h->lens.dev : nullptr; q.T = h->T; q.ld = h->CP; q.nc = h->cfg.latent_channels; q.p = h->x0c.ratio;
+        HIPCHK(launch_abs_quantile_items(q, h->items.dev, h->items.n, h->x0c.thr, s));
+        cx.thr = h->x0c.thr;
+      }
+    }
+    SolverItems si;
+    si.rec = h->items.dev; si.T = h->T; si.ld = h->CP;
+    HIPCHK(launch_solver_update_items(h->coef_dev, h->step_dev, NS2VC_NCOEF, si, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s,
+                                      h->pair_off(), nz, h->hist2.on ? h->hist2.mprev2 : nullptr, gd, cx));
+    return 0;
+  }
   if (h->x0c.mode) {         // (not with a stochastic table: ns2vc_sampler_begin refuses the pair)
     cx.mode = h->x0c.mode; cx.max_val = h->x0c.max_val; cx.T = h->T; cx.ld = h->CP;
     if (h->x0c.mode == 1) {  // the item's |m| quantile over its valid frames and real channels, from the update's own operands
@@ -217,6 +310,8 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   if (check_ready(h, true)) return 1;
   if (!x_T_bct) return fail("null tensor");
   if (!h->coef_dev || h->steps <= 0) return fail("no solver table loaded (call ns2vc_sampler_load)");
+  if (h->items.on && h->items.n != h->loop_items())
+    return fail("per-item schedules for %d items, the loop takes %d: load them again (ns2vc_sampler_load_items)", h->items.n, h->loop_items());
   if (h->stochastic && !h->seeds.set) return fail("the loaded solver table adds noise: set per-item seeds first (ns2vc_sampler_set_seeds)");
   if (h->stochastic && h->x0c.mode)
     return fail("the x0 correction (mode %d) does not apply to a stochastic table (ddpm, ddim with eta > 0): the reference's discrete samplers have none; "
@@ -267,7 +362,7 @@ int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream)
     const int E = c.block_out_channels[0] * 4;
     if (!h->temb_table) HIPCHK(hipMalloc((void**)&h->temb_table, (size_t)1024 * E * sizeof(float)));
     HIPCHK(launch_time_embed(h->coef_dev, NS2VC_NCOEF, nullptr, 0, h->t_w1t, h->t_b1, h->t_w2t, h->t_b2, nullptr, h->temb_table, nullptr,
-                             h->prec, h->steps, c.block_out_channels[0], E, s));
+                             h->prec, h->items.on ? h->items.rows : h->steps, c.block_out_channels[0], E, s));      // (per-item schedules: the rows of all distinct tables)
     h->temb_table_valid = true;
   }
   if (use_graph && !h->step_graph && n_steps > 0) {
@@ -302,6 +397,8 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   if (dst->device != src->device) return fail("handoff between engines on different devices");
   if (src->next_step < 0) return fail("source engine has no sampling loop in progress");
   if (!dst->coef_dev || dst->steps != src->steps) return fail("destination engine must hold the same solver table (%d vs %d steps)", dst->steps, src->steps);
+  if (dst->items.on != src->items.on || (src->items.on && dst->items.n != src->items.n))
+    return fail("destination engine must hold the same per-item schedules (ns2vc_sampler_load_items on both, or on neither)");
   if (dst->coef_hash != src->coef_hash) return fail("destination engine holds a DIFFERENT solver table with the same number of steps (solver / order / betas differ)");
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)src->B * src->T * src->CP;

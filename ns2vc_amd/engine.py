@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Ns2vcError, PREC_BF16, PREC_F16, PREC_F32, check
-from .schedule import NCOEF, SolverTable, build_table, check_x0_correction
+from .schedule import NCOEF, ItemTables, SolverTable, build_table, build_tables, check_x0_correction
 from .spec import UNetConfig, engine_block_types, engine_supports, param_spec
 
 # operand precision of the MFMAs (include/ns2vc_hip.h): fp16 is the default 16-bit mode -- same speed and bytes as bf16,
@@ -204,6 +204,7 @@ class Engine:
         self.guidance: Optional[np.ndarray] = None      # per-item guidance scales (set_guidance), None = unguided
         self.x0_correction = None                       # (mode 1 | 2, ratio, max_val) of set_x0_correction, None = off
         self.table: Optional[SolverTable] = None
+        self.tables: Optional[ItemTables] = None        # per-item schedules (load_samplers); None = the shared table
         self._weights_ready = False
         self._debug = False
 
@@ -397,7 +398,40 @@ class Engine:
         assert coef.shape == (table.steps, NCOEF)
         check(self.lib.ns2vc_sampler_load(self.h, table.steps, coef.ctypes.data_as(C.POINTER(C.c_float))), "sampler_load")
         self.table = table
+        self.tables = None
         return table
+
+    def load_samplers(self, specs, betas: Optional[np.ndarray] = None, discrete_betas: Optional[np.ndarray] = None, stream=None,
+                      starts=None) -> ItemTables:
+        """Per-item schedules: one dict per loop item (``schedule.schedule_key``: solver, steps, order, eta and the table options; the
+        prepared B items, n under guidance -- set the guidance first) -> ``build_tables`` -> the engine (``ns2vc_sampler_load_items``).
+        Every item walks its own table inside one captured loop of ``tables.steps`` = the longest table's evaluations, right-aligned
+        (``starts`` overrides), and ends on what ``load_sampler`` with its schedule alone gives it, bit for bit.  Equal schedules still take
+        this per-item form here (``Denoiser.sample`` routes them to ``load_sampler``).  ``sample(tail=, tail_steps=)`` works on engines
+        that hold the same schedules.  Stochastic items need ``set_seeds``."""
+        tabs = specs if isinstance(specs, ItemTables) else build_tables(specs, betas, discrete_betas, starts=starts)
+        coef, rows = tabs.coef, np.ascontiguousarray(tabs.rows, dtype=np.int32)
+        index, start = np.ascontiguousarray(tabs.index, dtype=np.int32), np.ascontiguousarray(tabs.start, dtype=np.int32)
+        assert coef.shape == (int(rows.sum()), NCOEF)
+        check(self.lib.ns2vc_sampler_load_items(self.h, int(rows.shape[0]), rows.ctypes.data, coef.ctypes.data_as(C.POINTER(C.c_float)),
+                                                int(index.shape[0]), index.ctypes.data, start.ctypes.data, _stream_ptr(stream)), "sampler_load_items")
+        self.tables = tabs
+        self.table = None
+        return tabs
+
+    def _same_schedule(self, other: "Engine") -> bool:
+        if (self.tables is None) != (other.tables is None):
+            return False
+        if self.tables is not None:
+            a, b = self.tables, other.tables
+            return np.array_equal(a.index, b.index) and np.array_equal(a.start, b.start) and np.array_equal(a.coef, b.coef)
+        return self.table is not None and other.table is not None and other.table.steps == self.table.steps and \
+            np.array_equal(np.asarray(self.table.coef, dtype=np.float32), np.asarray(other.table.coef, dtype=np.float32))
+
+    @property
+    def loop_steps(self) -> Optional[int]:
+        """evaluations of the loaded loop: the table's rows, or the longest item's under per-item schedules"""
+        return self.tables.steps if self.tables is not None else (None if self.table is None else self.table.steps)
 
     def sample(self, x_inout, use_graph: bool = True, stream=None, tail: Optional["Engine"] = None, tail_steps: int = 0) -> None:
         """x_inout (B,100,T): x_T in, sample out (in place).  NFE == steps of the loaded table.
@@ -410,10 +444,10 @@ class Engine:
         if tail is None or tail_steps <= 0:
             check(self.lib.ns2vc_sampler_run(self.h, _ptr(x_inout), int(use_graph), _stream_ptr(stream)), "sampler_run")
             return
-        if self.table is None or tail.table is None or tail.table.steps != self.table.steps or \
-                not np.array_equal(np.asarray(self.table.coef, dtype=np.float32), np.asarray(tail.table.coef, dtype=np.float32)):
-            raise Ns2vcError("mixed-precision sampling: both engines need the SAME solver table loaded (solver, steps, order, betas)")
-        n, k = self.table.steps, min(int(tail_steps), self.table.steps)
+        if not self._same_schedule(tail):
+            raise Ns2vcError("mixed-precision sampling: both engines need the SAME solver table loaded (solver, steps, order, betas; "
+                             "under per-item schedules the same schedules)")
+        n, k = self.loop_steps, min(int(tail_steps), self.loop_steps)
         sp = _stream_ptr(stream)
         check(self.lib.ns2vc_sampler_begin(self.h, _ptr(x_inout), sp), "sampler_begin")
         check(self.lib.ns2vc_sampler_steps(self.h, n - k, int(use_graph), sp), "sampler_steps")

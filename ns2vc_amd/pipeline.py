@@ -15,7 +15,7 @@ import numpy as np
 from . import dist as _dist
 from .engine import DEFAULT_PRECISION, Engine
 from .noise import draw_seeds
-from .schedule import DISCRETE_SOLVERS, SOLVERS, check_x0_correction, linear_betas, table_options
+from .schedule import DISCRETE_SOLVERS, SOLVERS, build_tables, check_x0_correction, linear_betas, schedule_key, table_options
 from .spec import UNetConfig, attention_workgroups_per_forward
 
 
@@ -261,6 +261,13 @@ class Denoiser:
             self.engine.load_sampler(solver, steps, self._betas_for(solver), order, eta, **options)
             self._table_key = key
 
+    def _tables(self, tabs, stream) -> None:
+        """per-item schedules -> the engine (its guidance must be set: the records cover the loop's items)"""
+        key = ("items", tabs.keys, tuple(int(v) for v in tabs.start))
+        if self._table_key != key:
+            self.engine.load_samplers(tabs, stream=stream)
+            self._table_key = key
+
     def _fp32_engine(self) -> Engine:
         """the exact-fp32 engine (tail of a 16-bit loop, precision self-check, fallback), prepared for the current shape"""
         if self.tail_engine is None:
@@ -295,6 +302,19 @@ class Denoiser:
         key = (solver, steps, order, eta, table_options(options))
         if self._tail_table_key != key:
             e.load_sampler(solver, steps, self._betas_for(solver), order, eta, **options)
+            self._tail_table_key = key
+        return e
+
+    def _tail_items(self, tabs, n_tail: int, scales, stream) -> Optional[Engine]:
+        """``_tail`` under per-item schedules: the guidance goes first, the records cover the loop's items"""
+        if (n_tail <= 0 and not self.serving_fp32) or self.precision == "fp32":
+            return None
+        e = self._fp32_engine()
+        if scales is not None or e.guidance is not None:
+            e.set_guidance(scales, stream=stream)
+        key = ("items", tabs.keys, tuple(int(v) for v in tabs.start), None if scales is None else len(scales))
+        if self._tail_table_key != key:
+            e.load_samplers(tabs, stream=stream)
             self._tail_table_key = key
         return e
 
@@ -368,8 +388,9 @@ class Denoiser:
         """(x_e, t) at the first, middle and last evaluation of the loaded table, from a preliminary loop on the 16-bit engine
         (its condition must be set).  ``rep`` = 2 under guidance: the loop gives B items, the evaluations take the point in both halves."""
         import torch
-        tm = np.asarray(self.engine.table.t_model, dtype=np.float32)
-        n = len(tm)
+        tabs = getattr(self.engine, "tables", None)      # per-item schedules: the points of the loop as run, t = every item's own model time there
+        tm = None if tabs is not None else np.asarray(self.engine.table.t_model, dtype=np.float32)
+        n = tabs.steps if tabs is not None else len(tm)
         idx = sorted({0, n // 2, n - 1})
         B = x_T.shape[0]
         pts, pos = [], 0
@@ -379,7 +400,9 @@ class Denoiser:
             pos = i
             xe = torch.empty_like(x_T)
             self.engine.sample_peek(xe, stream=stream)
-            pts.append((xe if rep == 1 else xe.repeat(rep, 1, 1), torch.full((B * rep,), float(tm[i]), dtype=torch.float32, device=x_T.device)))
+            t = torch.full((B * rep,), float(tm[i]), dtype=torch.float32, device=x_T.device) if tabs is None else \
+                torch.from_numpy(np.tile(tabs.t_model_at(i), rep)).to(x_T.device)
+            pts.append((xe if rep == 1 else xe.repeat(rep, 1, 1), t))
         scratch = torch.empty_like(x_T)
         self.engine.sample_end(scratch, stream=stream)
         return pts
@@ -522,11 +545,28 @@ class Denoiser:
             build_table(solver, int(steps), self._betas_for(solver), order, eta, **options)
         return int(steps)
 
+    def _check_schedules(self, schedules, B: int, solver: str, steps: int, order: int, eta: float, correcting_x0_fn, options):
+        """the argument errors of ``sample(schedules=)`` (ValueError, naming the item); returns the B schedule dicts with None filled in"""
+        if not isinstance(schedules, (list, tuple)) or len(schedules) != B:
+            raise ValueError(f"schedules must be a list of one schedule (dict or None) per item ({B}), got "
+                             f"{len(schedules) if isinstance(schedules, (list, tuple)) else type(schedules).__name__}")
+        own = dict(solver=solver, steps=steps, order=order, eta=eta, **options)
+        specs = []
+        for b, sp in enumerate(schedules):
+            sp = dict(own) if sp is None else sp
+            key = schedule_key(sp, b)
+            if correcting_x0_fn is not None and key[0] in DISCRETE_SOLVERS:
+                raise ValueError(f"schedules[{b}]: correcting_x0_fn applies to unipc / dpmsolver++ only (the reference's {key[0]} sampler has no correction)")
+            if key[0] == "ddpm" and key[1] != len(self.betas64):
+                raise ValueError(f"schedules[{b}]: ddpm runs every timestep of the schedule: steps must be {len(self.betas64)}, got {key[1]}")
+            specs.append(sp)
+        return specs
+
     def sample(self, content, prompt, prompt_mask=None, noise=None, solver: str = "unipc", steps: Optional[int] = None, order: int = 2,
                use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None,
                prompt_lengths=None, guidance_scale=1.0, unconditional_prompt=None, unconditional_prompt_mask=None,
                unconditional_prompt_lengths=None, unconditional_content=None, correcting_x0_fn=None, thresholding_max_val: float = 1.0,
-               dynamic_thresholding_ratio: float = 0.995, **options):
+               dynamic_thresholding_ratio: float = 0.995, schedules=None, **options):
         """content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool; ``noise`` (B,100,T) = x_T (drawn with
         torch.randn like model.py:635 if None).  Returns the sampled latent (B,100,T) fp32.
         ``solver``: ``unipc`` | ``dpmsolver++`` (``order`` 1 | 2 | 3, multistep) or the reference's discrete samplers ``ddim`` (``eta`` =
@@ -552,15 +592,30 @@ class Denoiser:
         evaluations on the fp32 engine unless ``tail_fp32`` says otherwise (1 for fp16, 3 for bf16).
         ``options`` (keyword-only): the reference's ``UniPC.sample`` / ``DPM_Solver.sample`` keywords that ``schedule.build_table`` serves
         -- ``skip_type``, ``lower_order_final``, ``denoise_to_zero`` (one more evaluation), ``variant`` (UniPC), ``solver_type``
-        (DPM-Solver++), ``t_start``, ``t_end``, ``method`` ("multistep" only)."""
+        (DPM-Solver++), ``t_start``, ``t_end``, ``method`` ("multistep" only).
+        ``schedules``: a list of B per-item schedules -- dicts with the keys ``solver``, ``steps``, ``order``, ``eta`` and the ``options``
+        above, or None = this call's own -- served by ONE captured loop of max(evaluations) steps (``Engine.load_samplers``,
+        ``schedule.run_tables_numpy``): the items are right-aligned, a shorter item is held (evaluated, not updated) until its turn, and every
+        item ends on what its schedule gives it in a call of its own.  B equal schedules take the shared-table path of that schedule.  The
+        default ``tail_fp32`` is the largest any item's schedule asks for; the x0 correction stays one setting per call."""
         import torch
         B, _, T = content.shape
         dev = content.device
         steps = self._check_sampler_args(solver, steps, eta, B, seeds, order, guidance_scale, unconditional_prompt, unconditional_prompt_mask,
                                          unconditional_prompt_lengths, unconditional_content, correcting_x0_fn, thresholding_max_val,
                                          dynamic_thresholding_ratio, **options)
+        tabs = None
+        if schedules is not None:
+            specs = self._check_schedules(schedules, B, solver, steps, order, eta, correcting_x0_fn, options)
+            keys = [schedule_key(sp, b) for b, sp in enumerate(specs)]
+            if all(k == keys[0] for k in keys):      # one schedule for everybody: today's shared-table loop, its kernels and its bits
+                return self.sample(content, prompt, prompt_mask, noise, keys[0][0], keys[0][1], keys[0][2], use_graph, generator, tail_fp32, lengths,
+                                   keys[0][3], seeds, prompt_lengths, guidance_scale, unconditional_prompt, unconditional_prompt_mask,
+                                   unconditional_prompt_lengths, unconditional_content, correcting_x0_fn, thresholding_max_val,
+                                   dynamic_thresholding_ratio, **dict(keys[0][4]))
+            tabs = build_tables(specs, self.betas, self.betas64)
         scales = self._guidance_scales(B, guidance_scale, unconditional_prompt)
-        guide_kw = dict(guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
+        guide_kw = dict(schedules=schedules, guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
                         unconditional_prompt_lengths=unconditional_prompt_lengths, unconditional_content=unconditional_content,
                         correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio)
         corr = (correcting_x0_fn, float(dynamic_thresholding_ratio), float(thresholding_max_val)) if correcting_x0_fn is not None else None
@@ -576,11 +631,16 @@ class Denoiser:
         if scales is not None or self.engine.guidance is not None:
             self.engine.set_guidance(scales, stream=torch.cuda.current_stream(dev))
         self._x0_correction(self.engine, corr)
-        self._table(solver, steps, order, eta, **options)
-        nfe = self.engine.table.steps               # (steps + 1 with denoise_to_zero)
+        if tabs is not None:
+            self._tables(tabs, torch.cuda.current_stream(dev))
+        else:
+            self._table(solver, steps, order, eta, **options)
+        nfe = self.engine.table.steps if tabs is None else tabs.steps      # (steps + 1 with denoise_to_zero; per-item schedules: the longest item's)
         n_tail = tail_fp32 if tail_fp32 is not None else self.tail_fp32
         if n_tail is None:
-            n_tail = default_tail_fp32(solver, order) if self.precision != "fp32" else 0
+            # (per-item schedules: the largest tail any item's own schedule asks for -- right-aligned, the last k loop steps are every item's last)
+            n_tail = max(default_tail_fp32(so, od) for so, od in ([(solver, order)] if tabs is None else [(k[0], k[2]) for k in tabs.keys])) \
+                if self.precision != "fp32" else 0
             if scales is not None and self.precision != "fp32":      # guidance multiplies the 16-bit rounding of the last evaluations
                 n_tail += guided_tail_extra(scales)
             if corr is not None and self.precision != "fp32":        # ... and a correction lets it in twice (corrected_tail_min)
@@ -590,7 +650,7 @@ class Denoiser:
             noise = torch.randn((B, self.cfg.latent_channels, T), device=dev, generator=generator)
         x = noise.to(device=dev, dtype=torch.float32).contiguous().clone()
         s = torch.cuda.current_stream(dev)
-        stochastic = bool((self.engine.table.coef[:, 9] != 0).any())
+        stochastic = bool((self.engine.table.coef[:, 9] != 0).any()) if tabs is None else bool((tabs.coef[:, 9] != 0).any())
         if stochastic:
             if seeds is None:
                 seeds = draw_seeds(B, generator)
@@ -601,8 +661,8 @@ class Denoiser:
             self._condition(self.engine, c32, p32, mask, s, lengths, prompt_lengths)
             self._self_check(self._trajectory_points(x, use_graph, s, rep), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths,
                              prompt_lengths=prompt_lengths)
-        tail = self._tail(solver, steps, order, n_tail, eta, **options)
-        if tail is not None and (scales is not None or tail.guidance is not None):
+        tail = self._tail(solver, steps, order, n_tail, eta, **options) if tabs is None else self._tail_items(tabs, n_tail, scales, s)
+        if tabs is None and tail is not None and (scales is not None or tail.guidance is not None):
             tail.set_guidance(scales, stream=s)
         if tail is not None:
             self._x0_correction(tail, corr)
@@ -650,6 +710,10 @@ class Denoiser:
                 seeds = draw_seeds(n, kw.get("generator"))
             sd = None if seeds is None else seeds[lo:hi]
             pl = None if prompt_lengths is None else prompt_lengths[lo:hi]
+            if kw.get("schedules") is not None:      # the per-item schedules go with the batch
+                if len(kw["schedules"]) != n:
+                    raise ValueError(f"schedules must be a list of one schedule (dict or None) per item ({n}), got {len(kw['schedules'])}")
+                kw = dict(kw, schedules=list(kw["schedules"][lo:hi]))
 
             def part(v):      # the per-item guidance arguments go with the batch; a scalar / one shared row goes to every rank whole
                 if isinstance(v, (list, tuple)):
@@ -670,7 +734,7 @@ class OverlappedPipeline:
         pre(k+1)   |   denoise(k)   |   post(k-1)
 
     ``pre_fn(item)`` runs on the front-end stream and returns a dict with torch CUDA tensors ``content`` (B,256,T),
-    ``prompt`` (B,Lp,256) and optionally ``prompt_mask`` (B,Lp) bool, ``noise`` (B,100,T), ``lengths`` and ``prompt_lengths``; ``post_fn(latent, item)``
+    ``prompt`` (B,Lp,256) and optionally ``prompt_mask`` (B,Lp) bool, ``noise`` (B,100,T), ``lengths``, ``prompt_lengths`` and ``schedules`` (``Denoiser.sample``); ``post_fn(latent, item)``
     runs on the back-end stream with the sampled latent (B,100,T) fp32.  Ordering is by events only -- the host never
     blocks until the end of ``run`` -- and the denoiser still replays one captured hipGraph per step on its own stream.
     """
@@ -754,7 +818,7 @@ class OverlappedPipeline:
                         if v.device != self.device:          # front end on another device: peer copy, ordered behind its event on the denoiser's stream
                             cond[k_] = v.to(self.device, non_blocking=True)
                 latent = self.denoiser.sample(cond["content"], cond["prompt"], cond.get("prompt_mask"), cond.get("noise"), lengths=cond.get("lengths"),
-                                              seeds=cond.get("seeds"), prompt_lengths=cond.get("prompt_lengths"), **self.kw)
+                                              seeds=cond.get("seeds"), prompt_lengths=cond.get("prompt_lengths"), schedules=cond.get("schedules"), **self.kw)
                 ev_den = torch.cuda.Event()
                 ev_den.record(self.s_den)
             with torch.cuda.device(self.post_device), torch.cuda.stream(self.s_post):

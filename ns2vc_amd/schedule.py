@@ -394,6 +394,174 @@ def _discrete_table(solver: str, steps: int, betas: Optional[np.ndarray], eta: f
     return SolverTable(solver, steps, coef.astype(np.float32), times_out, {"pairs": np.array(pairs, dtype=np.int64)})
 
 
+SCHEDULE_KEYS = ("solver", "steps", "order", "eta") + tuple(TABLE_OPTIONS)      # the keys of one item's schedule (a dict)
+
+
+def schedule_key(spec: Dict[str, object], item: Optional[int] = None) -> Tuple:
+    """One item's schedule -- ``dict(solver=, steps=, order=2, eta=0.0, **table options)`` -- checked and made hashable:
+    ``(solver, steps, order, eta, table_options)``.  Equal schedules have equal keys.  ``item`` names the item in the error."""
+    who = "schedule" if item is None else f"schedules[{item}]"
+    if not isinstance(spec, dict):
+        raise ValueError(f"{who} must be a dict with the keys {SCHEDULE_KEYS[:4]} and the table options, got {type(spec).__name__}")
+    bad = sorted(set(spec) - set(SCHEDULE_KEYS))
+    if bad:
+        raise ValueError(f"{who}: unknown key(s) {bad}; known: {list(SCHEDULE_KEYS)}")
+    if spec.get("solver") not in SOLVERS:
+        raise ValueError(f"{who}: solver must be one of {SOLVERS}, got {spec.get('solver')!r}")
+    if not isinstance(spec.get("steps"), (int, np.integer)) or isinstance(spec.get("steps"), bool) or int(spec["steps"]) <= 0:
+        raise ValueError(f"{who}: steps must be a positive int, got {spec.get('steps')!r}")
+    opts = {k: v for k, v in spec.items() if k in TABLE_OPTIONS}
+    if opts.get("method", "multistep") != "multistep":
+        raise ValueError(f"{who}: method must be 'multistep' (singlestep / adaptive solvers are not served by the captured loop), got {opts['method']!r}")
+    return (spec["solver"], int(spec["steps"]), int(spec.get("order", 2)), float(spec.get("eta", 0.0)), table_options(opts))
+
+
+@dataclass
+class ItemTables:
+    """The per-item schedules of one batch (``build_tables``): the DISTINCT tables, and per loop item which of them it walks and the loop
+    step it starts at.  The loop runs ``steps`` = max(start + rows) steps; ``row_at(r)`` / ``t_model_at(r)`` give every item's table row
+    (clamped for a held item) and model time at loop step r, ``active_at(r)`` who is updated there."""
+    tables: List[SolverTable]
+    index: np.ndarray         # (B,) int32: item b walks tables[index[b]]
+    start: np.ndarray         # (B,) int32
+    keys: Tuple = ()
+
+    @property
+    def rows(self) -> np.ndarray:
+        return np.array([t.steps for t in self.tables], dtype=np.int32)
+
+    @property
+    def item_rows(self) -> np.ndarray:
+        return self.rows[self.index]
+
+    @property
+    def steps(self) -> int:
+        return int((self.start + self.item_rows).max())
+
+    @property
+    def coef(self) -> np.ndarray:
+        """the rows of the distinct tables back to back, (sum(rows), NCOEF) float32: what the engine's device table holds"""
+        return np.ascontiguousarray(np.concatenate([np.asarray(t.coef, dtype=np.float32) for t in self.tables], axis=0))
+
+    def row_at(self, r: int) -> np.ndarray:
+        return np.clip(int(r) - self.start, 0, self.item_rows - 1).astype(np.int32)
+
+    def active_at(self, r: int) -> np.ndarray:
+        j = int(r) - self.start
+        return (j >= 0) & (j < self.item_rows)
+
+    def t_model_at(self, r: int) -> np.ndarray:
+        j = self.row_at(r)
+        return np.array([self.tables[k].coef[j[b], 0] for b, k in enumerate(self.index)], dtype=np.float32)
+
+    def table_of(self, b: int) -> SolverTable:
+        return self.tables[int(self.index[b])]
+
+    @property
+    def uniform(self) -> bool:
+        """every item walks the same table: the shared-table loop serves the batch"""
+        return len(self.tables) == 1
+
+
+def build_tables(specs, betas: Optional[np.ndarray] = None, discrete_betas: Optional[np.ndarray] = None, starts=None) -> ItemTables:
+    """One schedule per loop item (``schedule_key`` states the dict) -> ``ItemTables``.  Equal schedules share one table (and its rows in
+    the engine).  ``betas``: the continuous solvers' schedule as ``build_table`` takes it; ``discrete_betas``: ddim / ddpm's (the model's
+    float64 betas; default ``betas``).  Items are RIGHT-ALIGNED, start_b = S - rows_b with S the longest table: all finish together, so
+    the last k loop steps are every item's last min(k, rows_b) evaluations -- what a mixed-precision tail needs.  ``starts`` overrides that
+    (the engine takes any start >= 0)."""
+    specs = list(specs)
+    if not specs:
+        raise ValueError("build_tables needs at least one schedule")
+    keys = [schedule_key(s, b) for b, s in enumerate(specs)]
+    distinct: Dict[Tuple, int] = {}
+    tables: List[SolverTable] = []
+    index = np.zeros((len(keys),), dtype=np.int32)
+    for b, key in enumerate(keys):
+        if key not in distinct:
+            solver, steps, order, eta, opts = key
+            try:
+                tables.append(build_table(solver, steps, (discrete_betas if discrete_betas is not None else betas) if solver in DISCRETE_SOLVERS else betas,
+                                          order, eta, **dict(opts)))
+            except ValueError as e:
+                raise ValueError(f"schedules[{b}]: {e}") from None
+            distinct[key] = len(tables) - 1
+        index[b] = distinct[key]
+    rows = np.array([t.steps for t in tables], dtype=np.int32)[index]
+    if starts is None:
+        start = (rows.max() - rows).astype(np.int32)
+    else:
+        start = np.ascontiguousarray(np.asarray(starts).reshape(-1), dtype=np.int32)
+        if start.shape[0] != len(keys) or (start < 0).any():
+            raise ValueError(f"starts must hold one loop step >= 0 per item ({len(keys)})")
+    return ItemTables(tables, index, start, tuple(keys))
+
+
+def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarray], x_T: np.ndarray,
+                     trace: Optional[List[np.ndarray]] = None, noise_fn: Optional[Callable[[int, int], np.ndarray]] = None,
+                     guided_x0: Optional[np.ndarray] = None, correct_x0: Optional[Dict[str, object]] = None) -> np.ndarray:
+    """Host statement of the loop under per-item schedules (float32).  At loop step r item b has j = r - start_b: ACTIVE when
+    0 <= j < rows_b -- it then takes row j of its own table through the recurrence of ``run_table_numpy``, history 2 where ITS table has a
+    nonzero column 10 or 11 --, otherwise HELD: evaluated at the clamped row's model time, result ignored, state untouched.
+    ``x0_fn(x (B, ...), t_model (B,)) -> x0`` sees every item's own model time.  ``noise_fn(b, j)`` -> the standard normals of item b at
+    its LOCAL row j, shaped like x_T[b] (``noise.gauss(seed_b, j, ...)``: the stream the item has alone).  ``guided_x0``: (B,) scales --
+    ``x0_fn`` is then called on cat([x, x]) and cat([t, t]) (unconditional half first) and the halves are combined by
+    ``schedule.guided_x0``.  ``correct_x0``: the keywords of ``schedule.correct_x0`` for the whole batch (``lengths`` per item); refused when
+    an item is stochastic."""
+    f = np.float32
+    B = x_T.shape[0]
+    if tabs.index.shape[0] != B:
+        raise ValueError(f"{tabs.index.shape[0]} schedules for a batch of {B}")
+    xbar = x_T.astype(f).copy()
+    xe = xbar.copy()
+    d1 = np.zeros_like(xbar)
+    m_prev = np.zeros_like(xbar)
+    m_prev2 = np.zeros_like(xbar)
+    hist2 = [has_history2(tabs.table_of(b)) for b in range(B)]
+    noisy = [bool((np.asarray(tabs.table_of(b).coef)[:, 9] != 0).any()) for b in range(B)]
+    corr = None
+    if correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)):
+        if any(noisy):
+            raise ValueError(f"the x0 correction does not apply to a batch with a stochastic item (items {[b for b in range(B) if noisy[b]]})")
+        corr = dict(correct_x0)
+    lengths = None if corr is None else corr.pop("lengths", None)
+    for r in range(tabs.steps):
+        t = tabs.t_model_at(r)
+        if guided_x0 is None:
+            x0 = np.asarray(x0_fn(xe, t)).astype(f)
+        else:
+            both = np.asarray(x0_fn(np.concatenate([xe, xe], axis=0), np.concatenate([t, t]))).astype(f)
+            x0 = _guided_x0(both[:B], both[B:], np.asarray(guided_x0, dtype=f))
+        rows, act = tabs.row_at(r), tabs.active_at(r)
+        for b in range(B):
+            if not act[b]:
+                continue
+            sl = slice(b, b + 1)
+            c = tabs.table_of(b).coef[rows[b]]
+            _, alpha, sigma, g0, g1, A, Bc, d1c, pc = (f(v) for v in c[:9])
+            eps = (xe[sl] - alpha * x0[sl]) / sigma
+            m = (xe[sl] - sigma * eps) / alpha
+            if corr is not None:
+                m = _correct_x0(m, lengths=None if lengths is None else [lengths[b]], **corr)
+            x = xbar[sl] - g0 * d1[sl] - g1 * (m - m_prev[sl])
+            nb = A * x - Bc * m
+            if c[9] != 0:
+                if noise_fn is None:
+                    raise ValueError(f"row {rows[b]} of item {b}'s {tabs.table_of(b).solver} table adds noise: pass noise_fn")
+                nb = nb + f(c[9]) * np.asarray(noise_fn(b, int(rows[b])), dtype=f)[None]
+            if hist2[b]:
+                d2c, pe = f(c[10]), f(c[11])
+                nd = d1c * (m_prev[sl] - m) + d2c * (m_prev2[sl] - m)
+                ne = nb - pc * nd - pe * (m_prev2[sl] - m)
+                m_prev2[sl] = m_prev[sl]
+            else:
+                nd = d1c * (m_prev[sl] - m)
+                ne = nb - pc * nd
+            xbar[sl], d1[sl], xe[sl], m_prev[sl] = nb, nd, ne, m
+        if trace is not None:
+            trace.append(xe.copy())
+    return xe
+
+
 def guided_x0(x0_u: np.ndarray, x0_c: np.ndarray, scale) -> np.ndarray:
     """Classifier-free guidance, the host statement of common.h ``guided_x0``: ``x0_u + s * (x0_c - x0_u)`` per item, ``scale`` a float or
     (B,) against (B, ...) arrays.  The reference combines in noise space (sampler/uni_pc.py:225-229, sampler/dpm_solver.py:327-331); with the
@@ -409,6 +577,7 @@ def guided_x0(x0_u: np.ndarray, x0_c: np.ndarray, scale) -> np.ndarray:
         return np.where(s == 1, x0_c, x0_u + s * (x0_c - x0_u)).astype(x0_c.dtype)
 
 
+_guided_x0 = guided_x0      # (run_tables_numpy has a keyword of that name)
 X0_CORRECTIONS = {None: 0, "dynamic_thresholding": 1, "clamp": 2}      # Denoiser.sample(correcting_x0_fn=) -> the engine's mode
 
 

@@ -25,6 +25,7 @@ The reference's ``Svc.infer`` (``inference/infer_tool.py:189-206``) converts ONE
   its batches.
 * ``solver="ddim"`` (with ``eta``) / ``"ddpm"``: the reference's discrete samplers.  Their per-step noise comes from the segment's own
   seed (``noise.derive_seed(seed, index)``), so a segment's result does not depend on its group in either mode.
+* ``Segment.schedule``: a segment's own sampler schedule (``Denoiser.sample(schedules=)``); it never splits a group -- a group whose segments differ runs as one batch, one captured loop.
 * each group runs ``PreModel.infer`` -> ``Denoiser.sample`` -> ``decode_fn`` through ``OverlappedPipeline``: the
   PyTorch-ROCm front / back end of group k+1 / k-1 overlaps the HIP denoiser of group k on their own streams.
 
@@ -54,6 +55,10 @@ class Segment:
     content: torch.Tensor
     refer: torch.Tensor
     tag: object = None
+    # this segment's own sampler schedule -- dict(solver=, steps=, order=, eta=, table options), ``schedule.schedule_key`` -- or None = the
+    # converter's.  Grouping ignores it: a group with different schedules runs as ONE batch (``Denoiser.sample(schedules=)``), and a
+    # segment's result does not depend on its group
+    schedule: Optional[dict] = None
 
 
 def segment_from_audio(content_encoder, wav16k: torch.Tensor, samples_at_target_rate: int, refer_mel: torch.Tensor, hop: int = 256,
@@ -149,8 +154,13 @@ class GroupedConverter:
             return refer, plens
 
         def pre_fn(idx):
-            if self.ragged:
-                return ragged_pre(idx)
+            cond = ragged_pre(idx) if self.ragged else dense_pre(idx)
+            sch = [getattr(segments[i], "schedule", None) for i in idx]
+            if any(v is not None for v in sch):
+                cond["schedules"] = sch
+            return cond
+
+        def dense_pre(idx):
             T, Lp = int(segments[idx[0]].content.shape[-1]), int(segments[idx[0]].refer.shape[-1])
             c = torch.stack([segments[i].content.to(dev, torch.float32) for i in idx])
             noise = torch.stack([torch.randn((self.den.cfg.latent_channels, T), generator=torch.Generator().manual_seed(self.seed + i)) for i in idx]).to(dev)
