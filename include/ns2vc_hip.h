@@ -662,6 +662,60 @@ int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t
                                 const float* scale_dev, const uint64_t* seeds_dev, const int32_t* lens_dev, int nc, int mode, float ratio, float max_val,
                                 float* thr_dev, void* stream);
 
+/* ---- Slot loop: continuous batching (backward-compatible additions to ABI v7) --------------------------------------------------
+ * A loop over a prepared (B, T, Lp) engine whose loop items (B; n under guidance) are SLOTS that are filled, run and emptied independently while
+ * the captured step graph keeps replaying.  A request admitted into slot b with start = r runs rows 0 .. steps-1 of its own table at loop steps
+ * r .. r+steps-1 and ends on the bits it gets when the same engine shape runs it in the same slot from loop step 0 with the other slots idle;
+ * the other slots keep the bits they would have had without the admission.  Every call below is asynchronous on `stream` (host data travels
+ * through pinned staging; use ONE stream for a loop) and none ends the loop.  ns2vc_sampler_open is where buffers are allocated (records,
+ * slot lists for all B items, m_prev2, seeds, thresholds): it may wait for the device when one has to grow.  The calls of a running loop
+ * (_write_rows, _admit, _take, _rebase, ns2vc_unet_set_condition_items in slot mode) allocate nothing and never wait for the device; the
+ * host blocks only when it is eight calls ahead of the copies out of its staging ring.  Outside slot mode
+ * ns2vc_unet_set_condition_items allocates its slot list on first use and waits for `stream` when the list has to grow.
+ *
+ * ns2vc_sampler_open: puts the prepared engine into slot mode.  Every slot starts IDLE: record {row0 0, steps 1, start INT32_MAX, flags 0} --
+ * never active, evaluated at row 0 --, state (xe, its operand copy, xbar, d1, mprev, mprev2) zero, content and prompt rows zero with the
+ * hoisted tensors rebuilt from them, the 1024-row coefficient table zero (model time 0), its timestep-embedding table rebuilt: all finite.
+ * The step counter runs from 0.  What the captured step graph bakes in is fixed here: history2 != 0 = items with order-3 tables may come
+ * (m_prev2 is allocated), noise != 0 = stochastic items may come (the seeds buffer is allocated; not with the x0 correction); guidance and the
+ * x0 correction are the engine's settings at this moment.  Admissions within these forms never recapture (ns2vc_unet_graph_captures stays).
+ * Step counter rule: loop steps are 32-bit; a call that would pass 2^31 - 2 is refused.  ns2vc_sampler_rebase on a loop whose slots are all
+ * idle sets the counter back to 0 and does nothing else -- no recapture; table, condition and state stay (an idle record is active at no step).
+ * Opening again starts afresh (refused while slots are busy).  Refused with option fuse_solver.  ns2vc_sampler_handoff refuses a slot loop; ns2vc_sampler_load / _load_items refuse while slots are busy
+ * and otherwise leave slot mode; ns2vc_sampler_begin leaves it (and fails: a table must be loaded first); ns2vc_sampler_end ends it.
+ * In slot mode ns2vc_sampler_steps is not bounded by a table length (idle steps are legal) and ns2vc_sampler_peek gives all loop items.
+ * Legal in mid-loop, each a stream-ordered copy that replays the captured graph: ns2vc_unet_set_lengths and ns2vc_unet_set_prompt_lengths
+ * (while they stay ON: switching either on or off rebuilds the plan and recaptures), ns2vc_sampler_set_seeds, ns2vc_sampler_set_guidance
+ * (new scales; on / off ends the loop).  They take whole vectors: change the entries of idle slots only, or a running item changes course. */
+int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream);
+int ns2vc_sampler_rebase(ns2vc_unet* h, void* stream);
+/* rows [row0, row0 + nrows) of the 1024-row coefficient table <- coef_host [nrows][NS2VC_NCOEF] (finite), and the same rows of the
+ * timestep-embedding table (a row's embedding depends on that row alone: every other row keeps its bits).  Refused while a busy slot that has
+ * not finished walks any of the rows.  Which tables live where is the caller's business (ns2vc_amd.schedule.TablePool). */
+int ns2vc_sampler_write_rows(ns2vc_unet* h, int row0, int nrows, const float* coef_host, void* stream);
+/* n idle slots (HOST list, no repeats) take x_T_nct = DEVICE [n][C][T] and records = HOST [n][4] int32 {row0, steps, start, flags (1 = history 2,
+ * 2 = noise: must equal the form of the rows)} with start >= the current loop step.  ONE launch writes, for the listed slots only, exactly
+ * what ns2vc_sampler_begin leaves for those items (xe fp32 with pad channels and rows past lengths[slot] zero, the operand copy incl. the
+ * [hi | lo] pair of 16-bit engines, xbar = xe, d1 = mprev = mprev2 = 0; guided: xe and the operand copy also in slot + n, whose xbar rows are
+ * zero) and the slots' records; the slot list is read from device memory.  Set the slot's lengths, condition, seed and scale BEFORE it. */
+int ns2vc_sampler_admit(ns2vc_unet* h, int n, const int32_t* slots, const float* x_T_nct, const int32_t* records, void* stream);
+/* the slot-list form of ns2vc_sampler_peek: xe of n finished busy slots -> x_out_nct = DEVICE [n][C][T], one launch, which also makes the
+ * slots idle (their records; the state stays as it is, finite). */
+int ns2vc_sampler_take(ns2vc_unet* h, int n, const int32_t* slots, float* x_out_nct, void* stream);
+int ns2vc_sampler_slot_step(ns2vc_unet* h, int* loop_step); /* the loop step the next ns2vc_sampler_steps starts at; -1 = no slot loop */
+/* content_nct = DEVICE [n][content][T], prompt_nlc = DEVICE [n][Lp][cross], mask_nl = DEVICE [n][Lp] or NULL -> items slots[k] of the prepared
+ * B (a guided engine: both halves are the caller's business), as ns2vc_unet_set_content / _set_prompt write them for the whole batch (NCT ->
+ * channels-last, operand or hi + lo copy, rows past lengths[slot] zero), by ONE scatter launch; then the whole condition plan runs again: the
+ * other items' hoisted tensors keep their bits.  A mask needs a plan built with one (NULL then keeps every key).  Works in and out of slot mode. */
+int ns2vc_unet_set_condition_items(ns2vc_unet* h, int n, const int32_t* slots, const float* content_nct, const float* prompt_nlc, const uint8_t* mask_nl,
+                                   void* stream);
+/* test hooks of the two state kernels: slots_host = HOST [n] in [0, n_items); buffers as ns2vc_k_solver_update_items takes them (n_items items of
+ * T rows of ld columns; guided != 0: 2 * n_items items in xe / xe_op / xbar / d1 / mprev / mprev2); lens_dev = DEVICE [n_items] or NULL.  Both wait
+ * for `stream`.  No records are written. */
+int ns2vc_k_sampler_admit(const float* x_T, int C, int T, int n, const int32_t* slots_host, int n_items, float* xe, void* xe_op, int precision, float* xbar,
+                          float* d1, float* mprev, float* mprev2, int ld, const int32_t* lens_dev, int guided, void* stream);
+int ns2vc_k_sampler_take(const float* xe, int ld, int C, int T, int n, const int32_t* slots_host, int n_items, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

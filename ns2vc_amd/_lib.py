@@ -231,6 +231,15 @@ PROTOTYPES = {
     "ns2vc_k_solver_update_corrected": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P]),
     "ns2vc_k_solver_update_items": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _I, _P, _P, _P, _I, _I, C.c_float, C.c_float,
                                          _P, _P]),
+    "ns2vc_sampler_open": (_I, [_P, _I, _I, _P]),
+    "ns2vc_sampler_rebase": (_I, [_P, _P]),
+    "ns2vc_sampler_write_rows": (_I, [_P, _I, _I, C.POINTER(C.c_float), _P]),
+    "ns2vc_sampler_admit": (_I, [_P, _I, _P, _P, _P, _P]),
+    "ns2vc_sampler_take": (_I, [_P, _I, _P, _P, _P]),
+    "ns2vc_sampler_slot_step": (_I, [_P, C.POINTER(_I)]),
+    "ns2vc_unet_set_condition_items": (_I, [_P, _I, _P, _P, _P, _P, _P]),
+    "ns2vc_k_sampler_admit": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P]),
+    "ns2vc_k_sampler_take": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

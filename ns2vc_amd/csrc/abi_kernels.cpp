@@ -464,6 +464,47 @@ int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t
   (void)hipFree(rec);
   return rc;
 }
+// a host slot list, checked (entries in [0, n_items), none twice), on the device for one hook call
+static int upload_slots(const int32_t* slots_host, int n, int n_items, int** out_dev) {
+  if (!slots_host || n <= 0 || n_items <= 0 || n > n_items) return fail("a slot list needs 1 .. %d entries, got %d", n_items, n);
+  std::vector<char> seen((size_t)n_items, 0);
+  for (int k = 0; k < n; ++k) {
+    if (slots_host[k] < 0 || slots_host[k] >= n_items) return fail("slots[%d] = %d outside [0, %d)", k, (int)slots_host[k], n_items);
+    if (seen[slots_host[k]]) return fail("slot %d is listed twice", (int)slots_host[k]);
+    seen[slots_host[k]] = 1;
+  }
+  HIPCHK(hipMalloc((void**)out_dev, (size_t)n * sizeof(int)));
+  if (hipMemcpy(*out_dev, slots_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(*out_dev);
+    *out_dev = nullptr;
+    return fail("copy of the slot list failed");
+  }
+  return 0;
+}
+int ns2vc_k_sampler_admit(const float* x_T, int C, int T, int n, const int32_t* slots_host, int n_items, float* xe, void* xe_op, int precision, float* xbar,
+                          float* d1, float* mprev, float* mprev2, int ld, const int32_t* lens_dev, int guided, void* stream) {
+  if (!x_T || !xe || !xe_op || !xbar || !d1 || !mprev) return fail("null argument");
+  if (C <= 0 || ld <= 0 || (ld & 3) || C > ld || T <= 0) return fail("C (%d) must be in 1 .. ld (%d), ld a multiple of 4, T (%d) positive", C, ld, T);
+  int* sd = nullptr;
+  if (upload_slots(slots_host, n, n_items, &sd)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launched(launch_sampler_admit(x_T, C, T, n, sd, n_items, nullptr, nullptr, xe, xe_op, precision, xbar, d1, mprev, mprev2, ld,
+                                         precision != PREC_F32 ? ld : 0, lens_dev, guided ? n_items : 0, s), "sampler_admit launch");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("sampler_admit: stream synchronize failed");
+  (void)hipFree(sd);
+  return rc;
+}
+int ns2vc_k_sampler_take(const float* xe, int ld, int C, int T, int n, const int32_t* slots_host, int n_items, float* out, void* stream) {
+  if (!xe || !out) return fail("null argument");
+  if (C <= 0 || ld <= 0 || C > ld || T <= 0) return fail("C (%d) must be in 1 .. ld (%d), T (%d) positive", C, ld, T);
+  int* sd = nullptr;
+  if (upload_slots(slots_host, n, n_items, &sd)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launched(launch_sampler_take(xe, ld, C, T, n, sd, n_items, out, nullptr, s), "sampler_take launch");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("sampler_take: stream synchronize failed");
+  (void)hipFree(sd);
+  return rc;
+}
 int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream) {
   return launched(launch_noise(reinterpret_cast<const unsigned long long*>(seeds_dev), B, C, T, ld, step, lens_dev, out, (hipStream_t)stream), "noise launch");
 }

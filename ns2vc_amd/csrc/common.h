@@ -331,6 +331,11 @@ __device__ __forceinline__ int solver_item_row(const SolverItem& it, int r, bool
   return it.row0 + min(max(j, 0), it.steps - 1);
 }
 
+// the record of an IDLE slot of a slot loop (ns2vc_sampler_open): never active at any loop step r >= 0 (r - start < 0 without overflow), evaluated
+// at row 0 of the table
+constexpr int SOLVER_ITEM_NEVER = 0x7fffffff;
+__host__ __device__ __forceinline__ SolverItem solver_item_idle() { return SolverItem{0, 1, SOLVER_ITEM_NEVER, 0}; }
+
 constexpr double GN_SUM_SCALE = 268435456.0;   // 2^28
 constexpr double GN_SQ_SCALE = 65536.0;        // 2^16
 
@@ -453,6 +458,14 @@ hipError_t launch_solver_update_items(const float* coef, const int* step_ptr, in
 hipError_t launch_abs_quantile_items(const QuantArgs& q, const SolverItem* items, int n_items, float* thr, hipStream_t s);
 hipError_t launch_emb_items_from_table(const float* table, const int* step_ptr, const SolverItem* items, int n_items, const float* aug, float* emb,
                                        void* emb_act_op, int prec, int B, int edim, hipStream_t s);
+// slot loop (misc.hip, the last section): one launch per list of n slots read from device memory; nslots = the loop items an entry may name
+hipError_t launch_sampler_admit(const float* x_T, int C, int T, int n, const int* slots, int nslots, const SolverItem* rec_in, SolverItem* rec, float* xe,
+                                void* xe_op, int prec, float* xbar, float* d1, float* mprev, float* mprev2, int ld, int split, const int* lens, int half,
+                                hipStream_t s);
+hipError_t launch_sampler_take(const float* xe, int ld, int C, int T, int n, const int* slots, int nslots, float* dst, SolverItem* rec, hipStream_t s);
+hipError_t launch_condition_items(const float* content, int Cc, int T, const float* prompt, int Lp, int Cx, const uint8_t* mask, int n, const int* slots,
+                                  int nslots, void* content_op, int prec, int split, float* content_f32, const int* lens, float* prompt_dst,
+                                  uint8_t* mask_dst, hipStream_t s);
 // the normals a stochastic update adds at table row `step` (ns2vc_k_noise): out rows [B*T][ld] fp32, zeros where no noise goes
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s);
 hipError_t launch_fill_i32(int* p, int v, hipStream_t s);

@@ -327,6 +327,29 @@ int ns2vc_unet_set_condition(ns2vc_unet* h, const float* content_bct, const floa
   return ns2vc_unet_set_content(h, content_bct, stream);
 }
 
+// The condition of the listed items only (a slot loop's admissions): one scatter launch writes what set_content / set_prompt write for
+// those items, then the WHOLE condition plan runs again -- every launch of it works item by item, so the other items' hoisted tensors come out
+// with the bits they had.  A mask where the plan has none (or none where it has one, NULL = all keys kept) would rebuild the plan: refused.
+int ns2vc_unet_set_condition_items(ns2vc_unet* h, int n, const int32_t* slots, const float* content_nct, const float* prompt_nlc, const uint8_t* mask_nl,
+                                   void* stream) {
+  if (check_ready(h, true)) return 1;
+  if (!content_nct || !prompt_nlc) return fail("null condition tensor");
+  if (mask_nl && !h->has_mask)
+    return fail("the plan was built without a prompt mask: set one for the whole batch first (ns2vc_unet_set_mask) -- a per-item call does not rebuild the plan");
+  hipStream_t s = (hipStream_t)stream;
+  const auto& c = h->cfg;
+  const int* slots_dev = nullptr;
+  if (stage_slot_list(h, n, slots, h->B, nullptr, s, &slots_dev, nullptr)) return 1;
+  HIPCHK(launch_condition_items(content_nct, c.content_channels, h->T, prompt_nlc, h->Lp, c.cross_attention_dim, mask_nl, n, slots_dev, h->B, h->content_op,
+                                h->prec, h->prec != PREC_F32 ? c.content_channels : 0, h->content_f32, h->lens.masked ? h->lens.dev : nullptr, h->prompt,
+                                h->has_mask ? h->mask_dev : nullptr, s));
+  if (h->has_mask) {
+    if (h->plens.on) HIPCHK(launch_prompt_bias(h->mask_dev, h->plens.dev, h->B, h->Lp, h->maskbias, s));
+    else HIPCHK(launch_mask_bias(h->mask_dev, h->B * h->Lp, h->maskbias, s));
+  }
+  return run_ops(h->cond_ops, s);
+}
+
 // the plan for the current shape again, dense or masked (h->lens.masked), in the arena it already has: the persistent state (condition, solver
 // state, the length tables) sits at the same offsets in both, so nothing but the launch list and the captured step graph changes
 static int rebuild_plan(ns2vc_unet* h) {

@@ -316,6 +316,25 @@ struct ns2vc_unet {
     int cap = 0;
     ns2vc::Staged stage;
   } items;
+  // Slot loop (ns2vc_sampler_open): the per-item form with the loop items as SLOTS that are admitted and taken independently while the step
+  // counter keeps running.  `rec` / `busy` are the host's mirror of the device records (busy = admitted and not yet taken); the forms the
+  // captured step graph bakes in (hist2.on, stochastic) are fixed at open.  Slot lists and records travel through a ring of pinned staging
+  // buffers (a call waits only for the copy made `kRing` calls earlier) into `list_dev`, which the kernels read: [cap] slots, then [cap] records.
+  struct SlotLoop {
+    static constexpr int kRing = 8;
+    bool on = false;
+    std::vector<ns2vc::SolverItem> rec;
+    std::vector<char> busy;
+    std::vector<float> coef;                 // host mirror of the coefficient table (ns2vc_sampler_write_rows): admit derives an item's form from its rows
+    int* list_dev = nullptr;
+    int cap = 0;
+    ns2vc::Staged ring[kRing];
+    int ring_next = 0;
+    ns2vc::Staged coef_ring[kRing];
+    int coef_next = 0;
+    bool any_busy() const { for (char b : busy) if (b) return true; return false; }
+  } slots;
+  bool in_slot_loop() const { return slots.on && next_step >= 0; }
   // Correction of the predicted x0 (ns2vc_sampler_set_x0_correction): mode 1 = dynamic thresholding, 2 = clamp.  The ratio and max_val are
   // arguments of the step's launches, so a change of the mode or of a value the active mode passes drops the captured step graph.  The per-item thresholds of mode 1 live in a
   // buffer of their own outside the plan arena (one float per batch item), allocated when the correction is switched on.
@@ -363,6 +382,7 @@ struct ns2vc_unet {
     if (hist2.mprev2) (void)hipFree(hist2.mprev2);
     if (x0c.thr) (void)hipFree(x0c.thr);
     if (items.dev) (void)hipFree(items.dev);
+    if (slots.list_dev) (void)hipFree(slots.list_dev);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     if (tfork.side_stream) (void)hipStreamDestroy(tfork.side_stream);
@@ -397,6 +417,10 @@ int check_ready(ns2vc_unet* h, bool need_plan);
 int load_state(ns2vc_unet* h, const float* x_bct, hipStream_t s, int items = 0);   // items: the first `items` of the batch (0 = all B)
 // sampler.cpp
 bool solver_in_conv_out(ns2vc_unet* h, GemmArgs& g);
+// a host list of n slots in [0, nslots) (no repeats) -> the engine's device list, asynchronously on `s`; with `rec` their n records behind it.
+// *slots_dev / *rec_dev point into h->slots.list_dev.  Fails on a bad list.
+int stage_slot_list(ns2vc_unet* h, int n, const int32_t* slots, int nslots, const SolverItem* rec, hipStream_t s, const int** slots_dev,
+                    const SolverItem** rec_dev);
 // abi_kernels.cpp
 hipError_t init_all_attributes();
 int xcd_round_robin_of_current_device();

@@ -1450,4 +1450,148 @@ hipError_t launch_snapshot_u32(unsigned* src, unsigned* dst, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Slot loop (ns2vc_sampler_open): the B items of a running loop are filled, run and emptied independently.  Three kernels, each ONE
+// launch for a list of slots read from device memory (`slots` [n]; entry k of the caller's tensors goes to / comes from item slots[k]); an entry
+// outside [0, nslots) is skipped, never used as an index.  They sit behind everything else in this file: every earlier kernel keeps its code.
+// ---------------------------------------------------------------------------
+// x_T [n][C][T] -> the solver state of the listed slots, exactly what ns2vc_sampler_begin leaves for those items (nct_to_btc + mask_rows + copy16 +
+// zero): xe fp32 rows with the pad channels and the rows t >= lens[slot] zero, xe_op the same values in the operand type (16-bit: the [hi | lo] pair,
+// `split` columns apart), xbar = xe, d1 = mprev = mprev2 = 0, and the slot's record.  half > 0 (guided engine of 2 * half items): xe / xe_op also go
+// to item slot + half, whose xbar, d1, mprev, mprev2 rows are zero.  Nothing of any other item is touched.
+template <typename TM>
+__global__ __launch_bounds__(256) void sampler_admit_kernel(const float* __restrict__ src, int C, int T, const int* __restrict__ slots, int nslots,
+                                                            const SolverItem* __restrict__ rec_in, SolverItem* __restrict__ rec,
+                                                            float* __restrict__ xe, TM* __restrict__ xe_op, float* __restrict__ xbar,
+                                                            float* __restrict__ d1, float* __restrict__ mprev, float* __restrict__ mprev2, int ld,
+                                                            int split, const int* __restrict__ lens, int half) {
+  op_mode_init<TM>();
+  __shared__ float tile[32][33];
+  const int k = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int slot = slots[k];
+  if (slot < 0 || slot >= nslots) return;                    // (uniform per block: in front of the barrier)
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;    // 32 x 8
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    tile[i][tx] = (c < C && t < T) ? src[((size_t)k * C + c) * T + t] : 0.f;
+  }
+  __syncthreads();
+  const int L = lens ? lens[slot] : T;
+  const int ldo = split ? 2 * split : ld;
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (t >= T || c >= ld) continue;
+    const float v = t < L ? tile[tx][i] : 0.f;
+    const size_t r = (size_t)slot * T + t, e = r * ld + c;
+    xe[e] = v; xbar[e] = v; d1[e] = 0.f; mprev[e] = 0.f;
+    if (mprev2) mprev2[e] = 0.f;
+    TM* q = xe_op + r * ldo + c;
+    store_op<TM>(q, v);
+    if (split) store_op<TM>(q + split, op_rest<TM>(v));
+    if (half > 0) {
+      const size_t r2 = (size_t)(slot + half) * T + t, e2 = r2 * ld + c;
+      xe[e2] = v; xbar[e2] = 0.f; d1[e2] = 0.f; mprev[e2] = 0.f;
+      if (mprev2) mprev2[e2] = 0.f;
+      q = xe_op + r2 * ldo + c;
+      store_op<TM>(q, v);
+      if (split) store_op<TM>(q + split, op_rest<TM>(v));
+    }
+  }
+  if (rec && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) rec[slot] = rec_in[k];
+}
+// xe of the listed slots -> dst [n][C][T] (btc_to_nct_kernel's rows of those items), and the slots' records -> idle (common.h solver_item_idle)
+__global__ __launch_bounds__(256) void sampler_take_kernel(const float* __restrict__ src, int lds_, int C, int T, const int* __restrict__ slots,
+                                                           int nslots, float* __restrict__ dst, SolverItem* __restrict__ rec) {
+  __shared__ float tile[32][33];
+  const int k = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int slot = slots[k];
+  if (slot < 0 || slot >= nslots) return;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    tile[i][tx] = (t < T && c < C) ? src[((size_t)slot * T + t) * lds_ + c] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    if (c < C && t < T) dst[((size_t)k * C + c) * T + t] = tile[tx][i];
+  }
+  if (rec && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) rec[slot] = solver_item_idle();
+}
+// The condition of the listed slots: content [n][Cc][T] -> the slot's rows of the content operand copy (and of its fp32 copy, where the engine
+// keeps one) as ns2vc_unet_set_content writes them -- channels-last, 16-bit: the [hi | lo] pair, rows t >= lens[slot] zero --, and prompt
+// [n][Lp][Cx] (Cx % 4 == 0) -> the slot's rows of the fp32 prompt copy; mask_dst set: mask [n][Lp] (NULL: all ones) -> the slot's keep-mask row.
+// Blocks x < ceil(T / 32) transpose a content tile; the blocks behind them (y = 0 only) copy the prompt.
+template <typename TM>
+__global__ __launch_bounds__(256) void condition_items_kernel(const float* __restrict__ content, int Cc, int T, const float* __restrict__ prompt,
+                                                              int Lp, int Cx, const uint8_t* __restrict__ mask, const int* __restrict__ slots,
+                                                              int nslots, TM* __restrict__ content_op, int split, float* __restrict__ content_f32,
+                                                              const int* __restrict__ lens, float* __restrict__ prompt_dst,
+                                                              uint8_t* __restrict__ mask_dst) {
+  op_mode_init<TM>();
+  __shared__ float tile[32][33];
+  const int k = blockIdx.z;
+  const int slot = slots[k];
+  if (slot < 0 || slot >= nslots) return;
+  const int tb = (T + 31) / 32;
+  if ((int)blockIdx.x >= tb) {
+    if (blockIdx.y != 0) return;
+    const int pb = blockIdx.x - tb, npb = gridDim.x - tb;
+    const size_t n4 = (size_t)Lp * Cx / 4;
+    const float4* ps = reinterpret_cast<const float4*>(prompt + (size_t)k * Lp * Cx);
+    float4* pd = reinterpret_cast<float4*>(prompt_dst + (size_t)slot * Lp * Cx);
+    for (size_t i = (size_t)pb * 256 + threadIdx.x; i < n4; i += (size_t)npb * 256) pd[i] = ps[i];
+    if (mask_dst && pb == 0)
+      for (int j = threadIdx.x; j < Lp; j += 256) mask_dst[(size_t)slot * Lp + j] = mask ? mask[(size_t)k * Lp + j] : (uint8_t)1;
+    return;
+  }
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    tile[i][tx] = (c < Cc && t < T) ? content[((size_t)k * Cc + c) * T + t] : 0.f;
+  }
+  __syncthreads();
+  const int L = lens ? lens[slot] : T;
+  const int ldo = split ? 2 * split : Cc;
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (t >= T || c >= Cc) continue;
+    const float v = t < L ? tile[tx][i] : 0.f;
+    const size_t r = (size_t)slot * T + t;
+    if (content_f32) content_f32[r * Cc + c] = v;
+    TM* const q = content_op + r * ldo + c;
+    store_op<TM>(q, v);
+    if (split) store_op<TM>(q + split, op_rest<TM>(v));
+  }
+}
+hipError_t launch_sampler_admit(const float* x_T, int C, int T, int n, const int* slots, int nslots, const SolverItem* rec_in, SolverItem* rec, float* xe,
+                                void* xe_op, int prec, float* xbar, float* d1, float* mprev, float* mprev2, int ld, int split, const int* lens, int half,
+                                hipStream_t s) {
+  if (!x_T || !slots || !xe || !xe_op || !xbar || !d1 || !mprev || n <= 0 || nslots <= 0 || C <= 0 || C > ld || T <= 0 || ld <= 0 || half < 0 ||
+      (rec && !rec_in) || (split && (prec == PREC_F32 || split != ld)))
+    return hipErrorInvalidValue;
+  const dim3 grid((T + 31) / 32, (ld + 31) / 32, n);
+  NS2VC_BY_PREC(prec, hipLaunchKernelGGL(sampler_admit_kernel<TMX>, grid, dim3(256), 0, s, x_T, C, T, slots, nslots, rec_in, rec, xe, (TMX*)xe_op, xbar,
+                                         d1, mprev, mprev2, ld, split, lens, half));
+  return hipGetLastError();
+}
+hipError_t launch_sampler_take(const float* xe, int ld, int C, int T, int n, const int* slots, int nslots, float* dst, SolverItem* rec, hipStream_t s) {
+  if (!xe || !slots || !dst || n <= 0 || nslots <= 0 || C <= 0 || C > ld || T <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sampler_take_kernel, dim3((T + 31) / 32, (C + 31) / 32, n), dim3(256), 0, s, xe, ld, C, T, slots, nslots, dst, rec);
+  return hipGetLastError();
+}
+hipError_t launch_condition_items(const float* content, int Cc, int T, const float* prompt, int Lp, int Cx, const uint8_t* mask, int n, const int* slots,
+                                  int nslots, void* content_op, int prec, int split, float* content_f32, const int* lens, float* prompt_dst,
+                                  uint8_t* mask_dst, hipStream_t s) {
+  if (!content || !prompt || !slots || !content_op || !prompt_dst || n <= 0 || nslots <= 0 || Cc <= 0 || T <= 0 || Lp <= 0 || Cx <= 0 || (Cx & 3) ||
+      (((uintptr_t)prompt | (uintptr_t)prompt_dst) & 15) || (split && (prec == PREC_F32 || split != Cc)))
+    return hipErrorInvalidValue;
+  const int pblocks = (int)std::min<size_t>(8, std::max<size_t>(1, ((size_t)Lp * Cx / 4 + 255) / 256));
+  const dim3 grid((T + 31) / 32 + pblocks, (Cc + 31) / 32, n);
+  NS2VC_BY_PREC(prec, hipLaunchKernelGGL(condition_items_kernel<TMX>, grid, dim3(256), 0, s, content, Cc, T, prompt, Lp, Cx, mask, slots, nslots,
+                                         (TMX*)content_op, split, content_f32, lens, prompt_dst, mask_dst));
+  return hipGetLastError();
+}
+
 }  // namespace ns2vc

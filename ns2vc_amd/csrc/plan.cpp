@@ -847,6 +847,7 @@ void drop_plan(ns2vc_unet* h) {
   h->cond_ops.clear(); h->fwd_ops.clear(); h->taps.clear();
   h->arena_bytes = h->arena_used = 0;
   h->next_step = -1;           // the solver state lived in the arena
+  h->slots.on = false;         // (... and so did a slot loop's)
   h->ln_out.posted = false;
   h->attn_fallbacks = nullptr; // (the counters lived in the arena too)
   h->tfork.ok = false;

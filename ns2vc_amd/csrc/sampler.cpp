@@ -32,6 +32,9 @@ int ns2vc_sampler_load(ns2vc_unet* h, int steps, const float* coef_host) {
   const int kMaxSteps = 1024;   // fixed capacity: the table pointer is baked into the captured graph
   if (!h || !coef_host || steps <= 0) return fail("bad sampler table");
   if (steps > kMaxSteps) return fail("at most %d solver steps are supported", kMaxSteps);
+  if (h->in_slot_loop() && h->slots.any_busy())
+    return fail("a slot loop with busy slots is running (ns2vc_sampler_open): a shared table would end their items; take them first (ns2vc_sampler_take)");
+  h->slots.on = false;      // (a shared table leaves slot mode)
   if (!h->coef_dev) HIPCHK(hipMalloc((void**)&h->coef_dev, (size_t)kMaxSteps * NS2VC_NCOEF * sizeof(float)));
   HIPCHK(hipDeviceSynchronize());   // a previous loop may still be reading the table
   HIPCHK(hipMemcpy(h->coef_dev, coef_host, (size_t)steps * NS2VC_NCOEF * sizeof(float), hipMemcpyHostToDevice));
@@ -66,6 +69,9 @@ int ns2vc_sampler_load_items(ns2vc_unet* h, int n_tables, const int32_t* table_r
   if (!table_rows || !coef_host || !item_table || !item_start || n_tables <= 0 || n_items <= 0) return fail("bad per-item sampler tables");
   if (n_items != h->loop_items())
     return fail("per-item schedules for %d items, the loop takes %d (the prepared batch; n under guidance: set the guidance first)", n_items, h->loop_items());
+  if (h->in_slot_loop() && h->slots.any_busy())
+    return fail("a slot loop with busy slots is running (ns2vc_sampler_open): new schedules would end their items; take them first (ns2vc_sampler_take)");
+  h->slots.on = false;      // (closed per-item schedules leave slot mode)
   std::vector<int> row0(n_tables), flags(n_tables, 0);
   long rows = 0;
   for (int k = 0; k < n_tables; ++k) {
@@ -184,6 +190,7 @@ static int guidance_onoff(ns2vc_unet* h, bool on, int n) {
   if (on != h->guide.on) {
     drop_step_graph(h);      // (the step graph bakes in which update runs)
     h->seeds.set = false;    // (B seeds are not the n seeds of a guided loop, nor the other way round)
+    h->slots.on = false;     // (nor a slot loop: open it again)
     h->next_step = -1;       // (nor does a loop in progress survive the change)
   }
   h->guide.on = on;
@@ -309,6 +316,10 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
 int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   if (check_ready(h, true)) return 1;
   if (!x_T_bct) return fail("null tensor");
+  if (h->slots.on) {      // begin takes whole batches: it leaves slot mode, whose table rows and records belong to the slots' items
+    h->slots.on = false; h->steps = 0; h->next_step = -1;
+    return fail("the engine ran a slot loop (ns2vc_sampler_open), which this call has ended: load a table (ns2vc_sampler_load / _load_items) before ns2vc_sampler_begin");
+  }
   if (!h->coef_dev || h->steps <= 0) return fail("no solver table loaded (call ns2vc_sampler_load)");
   if (h->items.on && h->items.n != h->loop_items())
     return fail("per-item schedules for %d items, the loop takes %d: load them again (ns2vc_sampler_load_items)", h->items.n, h->loop_items());
@@ -349,12 +360,16 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
 
 int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream) {
   if (check_ready(h, true)) return 1;
-  if (!h->coef_dev || h->steps <= 0) return fail("no solver table loaded (call ns2vc_sampler_load)");
+  const bool slot_loop = h->in_slot_loop();      // (no table length bounds a slot loop: S follows the admissions, idle steps are legal)
+  if (!h->coef_dev || (h->steps <= 0 && !slot_loop)) return fail("no solver table loaded (call ns2vc_sampler_load)");
   if (h->next_step < 0) return fail("no sampling loop in progress (call ns2vc_sampler_begin or ns2vc_sampler_handoff)");
   if (h->hist2.on && !h->hist2.mprev2) return fail("history-2 table without its m_prev2 buffer (begin the loop after loading the table)");
   if (h->stochastic && h->x0c.mode) return fail("the x0 correction does not apply to a stochastic table");
   if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
-  if (n_steps < 0 || h->next_step + n_steps > h->steps) return fail("steps %d..%d outside the loaded table of %d", h->next_step, h->next_step + n_steps, h->steps);
+  if (slot_loop) {
+    if (n_steps < 0 || n_steps > SOLVER_ITEM_NEVER - 1 - h->next_step)
+      return fail("%d steps from loop step %d pass the end of the 32-bit step counter: drain the slots and call ns2vc_sampler_rebase", n_steps, h->next_step);
+  } else if (n_steps < 0 || h->next_step + n_steps > h->steps) return fail("steps %d..%d outside the loaded table of %d", h->next_step, h->next_step + n_steps, h->steps);
   hipStream_t s = (hipStream_t)stream;
   const auto& c = h->cfg;
   h->use_step_table = true;
@@ -396,6 +411,8 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   if (dst->B != src->B || dst->T != src->T || dst->CP != src->CP) return fail("handoff between different shapes");
   if (dst->device != src->device) return fail("handoff between engines on different devices");
   if (src->next_step < 0) return fail("source engine has no sampling loop in progress");
+  if (src->in_slot_loop() || dst->in_slot_loop())
+    return fail("a slot loop (ns2vc_sampler_open) cannot be handed off: its slots stand at different rows of different tables; run requests that need an fp32 tail on an fp32 engine");
   if (!dst->coef_dev || dst->steps != src->steps) return fail("destination engine must hold the same solver table (%d vs %d steps)", dst->steps, src->steps);
   if (dst->items.on != src->items.on || (src->items.on && dst->items.n != src->items.n))
     return fail("destination engine must hold the same per-item schedules (ns2vc_sampler_load_items on both, or on neither)");
@@ -441,6 +458,7 @@ int ns2vc_sampler_peek(ns2vc_unet* h, float* x_out_bct, void* stream) {
 int ns2vc_sampler_end(ns2vc_unet* h, float* x_out_bct, void* stream) {
   if (ns2vc_sampler_peek(h, x_out_bct, stream)) return 1;
   h->next_step = -1;
+  h->slots.on = false;
   return 0;
 }
 
@@ -448,6 +466,248 @@ int ns2vc_sampler_run(ns2vc_unet* h, float* x_inout_bct, int use_graph, void* st
   if (ns2vc_sampler_begin(h, x_inout_bct, stream)) return 1;
   if (ns2vc_sampler_steps(h, h->steps, use_graph, stream)) return 1;
   return ns2vc_sampler_end(h, x_inout_bct, stream);
+}
+
+}  // extern "C"
+
+// ---- slot loop ----------------------------------------------------------------------------------------------------------------
+static const int kSlotRows = 1024;      // the coefficient table's fixed capacity (ns2vc_sampler_load's)
+
+int ns2vc::stage_slot_list(ns2vc_unet* h, int n, const int32_t* slots, int nslots, const SolverItem* rec, hipStream_t s, const int** slots_dev,
+                           const SolverItem** rec_dev) {
+  if (!slots || n <= 0 || n > nslots) return fail("a slot list needs 1 .. %d entries, got %d", nslots, n);
+  std::vector<char> seen((size_t)nslots, 0);
+  for (int k = 0; k < n; ++k) {
+    if (slots[k] < 0 || slots[k] >= nslots) return fail("slots[%d] = %d outside [0, %d)", k, (int)slots[k], nslots);
+    if (seen[slots[k]]) return fail("slot %d is listed twice", (int)slots[k]);
+    seen[slots[k]] = 1;
+  }
+  auto& sl = h->slots;
+  if (!sl.list_dev || sl.cap < nslots) {      // (the kernels take the pointer as a launch argument: no captured graph holds it)
+    if (sl.list_dev) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(sl.list_dev)); sl.list_dev = nullptr; sl.cap = 0; }
+    HIPCHK(hipMalloc((void**)&sl.list_dev, (size_t)nslots * 5 * sizeof(int)));
+    sl.cap = nslots;
+  }
+  Staged& st = sl.ring[sl.ring_next];
+  sl.ring_next = (sl.ring_next + 1) % ns2vc_unet::SlotLoop::kRing;
+  const size_t lb = (size_t)n * sizeof(int), rb = rec ? (size_t)n * sizeof(SolverItem) : 0;
+  if (st.reserve(lb + rb)) return 1;
+  memcpy(st.buf, slots, lb);
+  if (rec) memcpy(static_cast<char*>(st.buf) + lb, rec, rb);
+  HIPCHK(hipMemcpyAsync(sl.list_dev, st.buf, lb, hipMemcpyHostToDevice, s));
+  SolverItem* rd = reinterpret_cast<SolverItem*>(sl.list_dev + sl.cap);
+  if (rec) HIPCHK(hipMemcpyAsync(rd, static_cast<char*>(st.buf) + lb, rb, hipMemcpyHostToDevice, s));
+  if (st.record(s)) return 1;
+  *slots_dev = sl.list_dev;
+  if (rec_dev) *rec_dev = rec ? rd : nullptr;
+  return 0;
+}
+
+static int need_slot_loop(ns2vc_unet* h) {
+  if (check_ready(h, true)) return 1;
+  if (!h->in_slot_loop()) return fail("no slot loop is open (call ns2vc_sampler_open)");
+  return 0;
+}
+
+extern "C" {
+
+int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
+  if (check_ready(h, true)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  auto& sl = h->slots;
+  const int n = h->loop_items();
+  const bool h2 = history2 != 0, nz = noise != 0;
+  if (h->fuse_solver) return fail("option fuse_solver folds the shared-table update into conv_out: a slot loop does not run with it (set it to 0 and prepare again)");
+  if (nz && h->x0c.mode)
+    return fail("a slot loop with stochastic items does not run with the x0 correction (mode %d): turn one of them off before ns2vc_sampler_open", h->x0c.mode);
+  if (h->guide.on && h->lens.masked)
+    for (int b = 0; b < n; ++b)
+      if (h->lens.applied[b] != h->lens.applied[b + n]) return fail("guided slot loop: lengths[%d] and lengths[%d] differ", b, b + n);
+  if (h->in_slot_loop() && sl.any_busy()) return fail("the slot loop is open and has busy slots: take them before opening again");
+  const size_t tb = (size_t)kSlotRows * NS2VC_NCOEF * sizeof(float);
+  if (!h->coef_dev) HIPCHK(hipMalloc((void**)&h->coef_dev, tb));
+  if (!h->items.dev || h->items.cap < n) {      // a new records buffer invalidates the captured step graph (its launches hold the pointer)
+    drop_step_graph(h);
+    if (h->items.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->items.dev)); h->items.dev = nullptr; h->items.cap = 0; }
+    HIPCHK(hipMalloc((void**)&h->items.dev, (size_t)n * sizeof(SolverItem)));
+    h->items.cap = n;
+  }
+  if (!sl.list_dev || sl.cap < h->B) {      // the slot lists of every later call fit (B covers both halves of a guided engine): no call in mid-loop grows it
+    if (sl.list_dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(sl.list_dev)); sl.list_dev = nullptr; sl.cap = 0; }
+    HIPCHK(hipMalloc((void**)&sl.list_dev, (size_t)h->B * 5 * sizeof(int)));
+    sl.cap = h->B;
+  }
+  if (h2 && ensure_mprev2(h)) return 1;
+  if (nz && ensure_seeds(h, n)) return 1;
+  if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
+  // (which update runs, its noise arguments and its m_prev2 pointer are baked into the captured step graph)
+  if (!h->items.on || nz != h->stochastic || h2 != h->hist2.on) drop_step_graph(h);
+  // every slot idle, on finite data: a zero table (model time 0 in every row), zero state, zero condition, hoisted tensors rebuilt from it
+  const size_t ne = (size_t)h->B * h->T * h->CP;
+  HIPCHK(launch_zero(h->coef_dev, tb, s));
+  HIPCHK(launch_zero(h->xe, ne * sizeof(float), s));
+  HIPCHK(launch_zero(h->xe_op, ne / h->CP * h->pair_width() * operand_bytes(h->prec), s));
+  HIPCHK(launch_zero(h->xbar, ne * sizeof(float), s));
+  HIPCHK(launch_zero(h->d1, ne * sizeof(float), s));
+  HIPCHK(launch_zero(h->mprev, ne * sizeof(float), s));
+  if (h2) HIPCHK(launch_zero(h->hist2.mprev2, ne * sizeof(float), s));
+  {
+    const auto& c = h->cfg;
+    const size_t rows = (size_t)h->B * h->T;
+    HIPCHK(launch_zero(h->content_op, rows * c.content_channels * (h->prec != PREC_F32 ? 2 : 1) * operand_bytes(h->prec), s));
+    if (h->content_f32) HIPCHK(launch_zero(h->content_f32, rows * c.content_channels * sizeof(float), s));
+    HIPCHK(launch_zero(h->prompt, (size_t)h->B * h->Lp * c.cross_attention_dim * sizeof(float), s));
+    if (run_ops(h->cond_ops, s)) return 1;
+    const int E = c.block_out_channels[0] * 4;
+    if (!h->temb_table) HIPCHK(hipMalloc((void**)&h->temb_table, (size_t)kSlotRows * E * sizeof(float)));
+    HIPCHK(launch_time_embed(h->coef_dev, NS2VC_NCOEF, nullptr, 0, h->t_w1t, h->t_b1, h->t_w2t, h->t_b2, nullptr, h->temb_table, nullptr, h->prec, kSlotRows,
+                             c.block_out_channels[0], E, s));
+    h->temb_table_valid = true;
+  }
+  sl.rec.assign((size_t)n, solver_item_idle());
+  sl.busy.assign((size_t)n, 0);
+  sl.coef.assign((size_t)kSlotRows * NS2VC_NCOEF, 0.f);
+  {
+    Staged& st = sl.ring[sl.ring_next];
+    sl.ring_next = (sl.ring_next + 1) % ns2vc_unet::SlotLoop::kRing;
+    const size_t nb = (size_t)n * sizeof(SolverItem);
+    if (st.reserve(nb)) return 1;
+    memcpy(st.buf, sl.rec.data(), nb);
+    HIPCHK(hipMemcpyAsync(h->items.dev, st.buf, nb, hipMemcpyHostToDevice, s));
+    if (st.record(s)) return 1;
+  }
+  if (nz) h->seeds.set = true;      // (the buffer holds finite seeds; ns2vc_sampler_set_seeds gives the slots theirs)
+  h->items.on = true;
+  h->items.n = n;
+  h->items.rows = kSlotRows;
+  h->stochastic = nz;
+  h->hist2.on = h2;
+  h->steps = 0;
+  h->coef_hash = 0;
+  HIPCHK(launch_fill_i32(h->step_dev, -1, s));      // the first launch of every step advances it (gn_stats.clear)
+  h->next_step = 0;
+  sl.on = true;
+  return 0;
+}
+
+// The 32-bit loop step must not bound a service's lifetime: with every slot idle (their records are "never active" at any step) the counter goes
+// back to 0 -- one one-thread launch, no recapture; the table, the condition and the slots' state stay.
+int ns2vc_sampler_rebase(ns2vc_unet* h, void* stream) {
+  if (need_slot_loop(h)) return 1;
+  if (h->slots.any_busy()) return fail("the loop step is rebased on a drained loop only: take the busy slots first");
+  HIPCHK(launch_fill_i32(h->step_dev, -1, (hipStream_t)stream));
+  h->next_step = 0;
+  h->steps = 0;
+  return 0;
+}
+
+int ns2vc_sampler_write_rows(ns2vc_unet* h, int row0, int nrows, const float* coef_host, void* stream) {
+  if (need_slot_loop(h)) return 1;
+  if (!coef_host || row0 < 0 || nrows <= 0 || row0 > kSlotRows - nrows) return fail("rows %d + %d outside the table of %d rows (its fixed capacity)", row0, nrows, kSlotRows);
+  auto& sl = h->slots;
+  for (size_t b = 0; b < sl.rec.size(); ++b) {      // a slot that has not finished reads its rows at every step still to come
+    const SolverItem& r = sl.rec[b];
+    if (sl.busy[b] && h->next_step < r.start + r.steps && r.row0 < row0 + nrows && row0 < r.row0 + r.steps)
+      return fail("rows %d .. %d are in use: slot %d walks rows %d .. %d until loop step %d (now %d)", row0, row0 + nrows - 1, (int)b, r.row0,
+                  r.row0 + r.steps - 1, r.start + r.steps, h->next_step);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t nb = (size_t)nrows * NS2VC_NCOEF * sizeof(float);
+  for (size_t i = 0; i < (size_t)nrows * NS2VC_NCOEF; ++i)
+    if (!std::isfinite(coef_host[i])) return fail("table value %zu of the rows is not finite", i);
+  Staged& st = sl.coef_ring[sl.coef_next];
+  sl.coef_next = (sl.coef_next + 1) % ns2vc_unet::SlotLoop::kRing;
+  if (st.reserve(nb)) return 1;
+  memcpy(st.buf, coef_host, nb);
+  memcpy(sl.coef.data() + (size_t)row0 * NS2VC_NCOEF, coef_host, nb);
+  float* dst = h->coef_dev + (size_t)row0 * NS2VC_NCOEF;
+  HIPCHK(hipMemcpyAsync(dst, st.buf, nb, hipMemcpyHostToDevice, s));
+  if (st.record(s)) return 1;
+  // the timestep MLP of these rows (column 0 = t): a row's embedding depends on that row alone, so the other rows keep their bits untouched
+  const auto& c = h->cfg;
+  const int E = c.block_out_channels[0] * 4;
+  if (h->temb_table_valid)
+    HIPCHK(launch_time_embed(dst, NS2VC_NCOEF, nullptr, 0, h->t_w1t, h->t_b1, h->t_w2t, h->t_b2, nullptr, h->temb_table + (size_t)row0 * E, nullptr, h->prec,
+                             nrows, c.block_out_channels[0], E, s));      // (not valid: ns2vc_sampler_steps rebuilds the whole table)
+  return 0;
+}
+
+int ns2vc_sampler_admit(ns2vc_unet* h, int n, const int32_t* slots, const float* x_T_nct, const int32_t* records, void* stream) {
+  if (need_slot_loop(h)) return 1;
+  if (!x_T_nct || !records) return fail("null argument");
+  auto& sl = h->slots;
+  const int ni = h->loop_items();
+  if (h->items.n != ni || (int)sl.rec.size() != ni) return fail("the slot loop was opened for %d items, the loop has %d: open it again", h->items.n, ni);
+  if (h->stochastic && !h->seeds.set) return fail("the slot loop takes stochastic items: set per-item seeds first (ns2vc_sampler_set_seeds)");
+  if (!slots || n <= 0 || n > ni) return fail("a slot list needs 1 .. %d entries, got %d", ni, n);
+  static_assert(sizeof(SolverItem) == 4 * sizeof(int32_t), "records are four 32-bit words");
+  std::vector<SolverItem> rec((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    const int32_t* r = records + 4 * (size_t)k;
+    const int b = slots[k];
+    if (b < 0 || b >= ni) return fail("slots[%d] = %d outside [0, %d)", k, b, ni);
+    if (sl.busy[b]) return fail("slot %d is busy (admitted at loop step %d for %d steps, not taken yet)", b, sl.rec[b].start, sl.rec[b].steps);
+    if (r[0] < 0 || r[1] <= 0 || r[0] > kSlotRows - r[1]) return fail("slot %d: rows %d + %d outside the table of %d rows", b, r[0], r[1], kSlotRows);
+    if (r[2] < h->next_step) return fail("slot %d: start %d lies in the past, the loop stands at step %d", b, r[2], h->next_step);
+    if (r[2] > SOLVER_ITEM_NEVER - 1 - r[1])
+      return fail("slot %d: loop steps %d + %d pass the end of the 32-bit step counter: drain the slots and call ns2vc_sampler_rebase", b, r[2], r[1]);
+    int flags = 0;
+    for (int i = 0; i < r[1]; ++i) {
+      const float* row = sl.coef.data() + (size_t)(r[0] + i) * NS2VC_NCOEF;
+      if (row[9] != 0.f) flags |= SOLVER_ITEM_NOISE;
+      if (row[10] != 0.f || row[11] != 0.f) flags |= SOLVER_ITEM_HIST2;
+      if (row[1] == 0.f) return fail("slot %d: row %d of the table was never written (ns2vc_sampler_write_rows)", b, r[0] + i);
+    }
+    if (flags != r[3]) return fail("slot %d: flags %d, its rows %d .. %d have the form %d (1 = history 2, 2 = noise)", b, r[3], r[0], r[0] + r[1] - 1, flags);
+    if (flags == (SOLVER_ITEM_NOISE | SOLVER_ITEM_HIST2)) return fail("slot %d: a table with both a noise column and history 2 is not supported", b);
+    if ((flags & SOLVER_ITEM_HIST2) && !h->hist2.on) return fail("slot %d runs history 2: the slot loop was opened without it (ns2vc_sampler_open history2 = 1)", b);
+    if ((flags & SOLVER_ITEM_NOISE) && !h->stochastic) return fail("slot %d is stochastic: the slot loop was opened without noise (ns2vc_sampler_open noise = 1)", b);
+    if (h->guide.on && h->lens.masked && h->lens.applied[b] != h->lens.applied[b + ni]) return fail("guided slot loop: lengths[%d] and lengths[%d] differ", b, b + ni);
+    rec[k] = SolverItem{r[0], r[1], r[2], r[3]};
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int* slots_dev = nullptr;
+  const SolverItem* rec_dev = nullptr;
+  if (stage_slot_list(h, n, slots, ni, rec.data(), s, &slots_dev, &rec_dev)) return 1;
+  HIPCHK(launch_sampler_admit(x_T_nct, h->cfg.latent_channels, h->T, n, slots_dev, ni, rec_dev, h->items.dev, h->xe, h->xe_op, h->prec, h->xbar, h->d1,
+                              h->mprev, h->hist2.on ? h->hist2.mprev2 : nullptr, h->CP, h->pair_off(), h->lens.masked ? h->lens.dev : nullptr,
+                              h->guide.on ? ni : 0, s));
+  for (int k = 0; k < n; ++k) {
+    sl.rec[slots[k]] = rec[k];
+    sl.busy[slots[k]] = 1;
+    h->steps = std::max(h->steps, rec[k].start + rec[k].steps);      // S follows the admissions
+  }
+  return 0;
+}
+
+int ns2vc_sampler_take(ns2vc_unet* h, int n, const int32_t* slots, float* x_out_nct, void* stream) {
+  if (need_slot_loop(h)) return 1;
+  if (!x_out_nct) return fail("null tensor");
+  auto& sl = h->slots;
+  const int ni = h->loop_items();
+  if (!slots || n <= 0 || n > ni) return fail("a slot list needs 1 .. %d entries, got %d", ni, n);
+  for (int k = 0; k < n; ++k) {
+    const int b = slots[k];
+    if (b < 0 || b >= ni) return fail("slots[%d] = %d outside [0, %d)", k, b, ni);
+    if (!sl.busy[b]) return fail("slot %d is idle: nothing to take", b);
+    if (h->next_step < sl.rec[b].start + sl.rec[b].steps)
+      return fail("slot %d has not finished: it runs until loop step %d, the loop stands at %d", b, sl.rec[b].start + sl.rec[b].steps, h->next_step);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int* slots_dev = nullptr;
+  if (stage_slot_list(h, n, slots, ni, nullptr, s, &slots_dev, nullptr)) return 1;
+  HIPCHK(launch_sampler_take(h->xe, h->CP, h->cfg.latent_channels, h->T, n, slots_dev, ni, x_out_nct, h->items.dev, s));
+  for (int k = 0; k < n; ++k) {
+    sl.rec[slots[k]] = solver_item_idle();
+    sl.busy[slots[k]] = 0;
+  }
+  return 0;
+}
+
+int ns2vc_sampler_slot_step(ns2vc_unet* h, int* loop_step) {
+  if (!h || !loop_step) return fail("null argument");
+  *loop_step = h->in_slot_loop() ? h->next_step : -1;
+  return 0;
 }
 
 }  // extern "C"

@@ -471,6 +471,59 @@ class Engine:
     def sample_end(self, x_out, stream=None) -> None:
         check(self.lib.ns2vc_sampler_end(self.h, _ptr(x_out), _stream_ptr(stream)), "sampler_end")
 
+    # -- slot loop: continuous batching (include/ns2vc_hip.h "Slot loop") ---------------------------------
+    @staticmethod
+    def _slot_list(slots) -> np.ndarray:
+        a = np.ascontiguousarray(np.asarray(slots).reshape(-1), dtype=np.int32)
+        if a.shape[0] == 0:
+            raise ValueError("an empty slot list")
+        return a
+
+    def open_slots(self, history2: bool = False, noise: bool = False, stream=None) -> None:
+        """Slot mode on the prepared shape: every loop item an idle slot on zero state and zero condition, the step counter running from 0.
+        ``history2`` / ``noise``: order-3 / stochastic items may be admitted (fixed here: the captured step graph bakes them in, as it does
+        the guidance and the x0 correction set at this moment).  Opening again starts afresh (refused while slots are busy)."""
+        check(self.lib.ns2vc_sampler_open(self.h, int(bool(history2)), int(bool(noise)), _stream_ptr(stream)), "sampler_open")
+        self.table = self.tables = None
+
+    def rebase_slots(self, stream=None) -> None:
+        """the loop step of a drained slot loop (every slot idle) back to 0: the 32-bit counter does not bound a service's lifetime"""
+        check(self.lib.ns2vc_sampler_rebase(self.h, _stream_ptr(stream)), "sampler_rebase")
+
+    def write_sampler_rows(self, row0: int, coef, stream=None) -> None:
+        """rows [row0, row0 + len(coef)) of the engine's 1024-row coefficient table (``schedule.TablePool`` decides where tables live)"""
+        a = np.ascontiguousarray(coef, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != NCOEF:
+            raise ValueError(f"table rows must be (rows, {NCOEF}), got {a.shape}")
+        check(self.lib.ns2vc_sampler_write_rows(self.h, int(row0), int(a.shape[0]), a.ctypes.data_as(C.POINTER(C.c_float)), _stream_ptr(stream)),
+              "sampler_write_rows")
+
+    def admit(self, slots, x_T, records, stream=None) -> None:
+        """idle ``slots`` take ``x_T`` (n, C, T) on the GPU and ``records`` (n, 4) int32 {row0, steps, start, flags}; one launch"""
+        s = self._slot_list(slots)
+        r = np.ascontiguousarray(np.asarray(records), dtype=np.int32)
+        if r.shape != (s.shape[0], 4):
+            raise ValueError(f"records must be ({s.shape[0]}, 4) {{row0, steps, start, flags}}, got {r.shape}")
+        check(self.lib.ns2vc_sampler_admit(self.h, int(s.shape[0]), s.ctypes.data, _ptr(x_T), r.ctypes.data, _stream_ptr(stream)), "sampler_admit")
+
+    def take(self, slots, out, stream=None) -> None:
+        """x_e of the finished ``slots`` -> ``out`` (n, C, T) on the GPU; the slots become idle; one launch"""
+        s = self._slot_list(slots)
+        check(self.lib.ns2vc_sampler_take(self.h, int(s.shape[0]), s.ctypes.data, _ptr(out), _stream_ptr(stream)), "sampler_take")
+
+    def slot_step(self) -> int:
+        """the loop step the next ``sample_steps`` of a slot loop starts at (-1: no slot loop)"""
+        n = C.c_int()
+        check(self.lib.ns2vc_sampler_slot_step(self.h, C.byref(n)), "sampler_slot_step")
+        return int(n.value)
+
+    def set_condition_items(self, slots, content, prompt, mask=None, stream=None) -> None:
+        """content (n, 256, T), prompt (n, Lp, 256), mask (n, Lp) or None on the GPU -> the items ``slots`` of the prepared batch; the other
+        items' hoisted tensors keep their bits.  Set the items' lengths / prompt lengths first."""
+        s = self._slot_list(slots)
+        check(self.lib.ns2vc_unet_set_condition_items(self.h, int(s.shape[0]), s.ctypes.data, _ptr(content), _ptr(prompt), _ptr(mask), _stream_ptr(stream)),
+              "set_condition_items")
+
     def attn_fallbacks(self, reset: bool = True, stream=None) -> int:
         """attention workgroups whose optimistic pass (no per-tile maximum) had to be repeated by the exact pass since the last
         reset: each paid its kernel twice (scores rising > ~18 log2 units above their first 64 keys).  Waits for ``stream``."""

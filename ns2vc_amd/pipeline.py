@@ -15,7 +15,8 @@ import numpy as np
 from . import dist as _dist
 from .engine import DEFAULT_PRECISION, Engine
 from .noise import draw_seeds
-from .schedule import DISCRETE_SOLVERS, SOLVERS, build_tables, check_x0_correction, linear_betas, schedule_key, table_options
+from .schedule import (DISCRETE_SOLVERS, ITEM_HIST2, ITEM_NOISE, SOLVERS, TablePool, build_table, build_tables, check_x0_correction, linear_betas,
+                       schedule_key, table_flags, table_options)
 from .spec import UNetConfig, attention_workgroups_per_forward
 
 
@@ -688,6 +689,18 @@ class Denoiser:
             self._attn_check(nfe - (n_tail if tail is not None else 0), s)      # (after the guard's read-out: a switch drops the plan)
         return x if redone is None else redone
 
+    def open_slots(self, B: int, T: int, Lp: int, order3: bool = False, stochastic: bool = False, unconditional_prompt=None,
+                   correcting_x0_fn=None, thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995,
+                   use_graph: bool = True, require_tail_free: bool = True) -> "SlotLoop":
+        """Continuous batching: a ``SlotLoop`` over an engine prepared for B slots of up to T frames and Lp prompt frames, whose slots are
+        filled (``admit``), run (``run``) and emptied (``take``) independently while one captured step graph keeps replaying.  Fixed here,
+        because the graph bakes them in: ``order3`` / ``stochastic`` (requests with order-3 / ddim-eta / ddpm schedules may come),
+        ``unconditional_prompt`` (1, Lu <= Lp, C) (a guided loop: the engine runs 2 B items, every request brings its own scale) and the
+        x0 correction.  ``require_tail_free`` False admits requests that ``sample`` would give trailing fp32 evaluations anyway (previews: their
+        latent carries the 16-bit rounding of its last evaluations).  See ``SlotLoop``."""
+        return SlotLoop(self, B, T, Lp, order3, stochastic, unconditional_prompt, correcting_x0_fn, thresholding_max_val,
+                        dynamic_thresholding_ratio, use_graph, require_tail_free)
+
     def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, seeds=None, prompt_lengths=None, guidance_scale=1.0,
                        unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None, unconditional_content=None, **kw):
         """Data-parallel: every rank receives the GLOBAL batch description, runs its contiguous slice and the
@@ -831,3 +844,277 @@ class OverlappedPipeline:
         self.s_post.synchronize()
         self.s_den.synchronize()
         return results
+
+
+def slot_tail_needed(precision: str, solver: str, order: int, scale: float = 1.0, corrected: bool = False) -> int:
+    """trailing fp32 evaluations ``Denoiser.sample`` would give a request with this schedule at this precision (``default_tail_fp32`` +
+    ``guided_tail_extra``, floored by ``corrected_tail_min``); a slot loop serves a request only when this is 0"""
+    if precision == "fp32":
+        return 0
+    n = default_tail_fp32(solver, order)
+    guided = float(scale) != 1.0
+    if guided:
+        n += guided_tail_extra([scale])
+    if corrected:
+        n = max(n, corrected_tail_min(precision, [scale] if guided else None))
+    return n
+
+
+class SlotLoop:
+    """A running loop of B slots (``Denoiser.open_slots``).  ``admit`` puts a request into an idle slot at the current loop
+    step, ``run`` steps the loop until the next busy slot finishes (or by ``n`` steps), ``take`` fetches finished slots' latents and frees
+    them, ``idle`` lists the free slots, ``close`` ends the loop (also with busy slots: the way out after an error).  A request ends on the bits it gets in the same slot of the same loop shape with every other slot
+    idle, whatever its neighbours do.  The loop always runs with per-item lengths and prompt lengths (an admission copies tables, never
+    rebuilds the plan) and replays ONE captured step graph.  Everything is enqueued on the current torch stream of the request's device;
+    nothing waits for the device.
+
+    A slot loop has no mixed-precision tail (the slots stand at different rows): a request whose schedule, guidance scale or correction
+    asks for trailing fp32 evaluations at the engine's precision is refused -- run the loop on a ``Denoiser(precision="fp32")``.  The
+    16-bit default, UniPC order 2 unguided and uncorrected, needs none.  The precision self-check runs once per set of weights on the first
+    admission into an all-idle loop, at the request's first evaluation point; the LayerNorm guard's read-outs are not taken inside a slot
+    loop (a plan switch would end it).  The 32-bit loop step is rebased to 0 by ``admit`` whenever the loop is drained and has passed 2^30."""
+
+    REBASE_AT = 1 << 30
+
+    def __init__(self, den: "Denoiser", B: int, T: int, Lp: int, order3: bool, stochastic: bool, unconditional_prompt, correcting_x0_fn,
+                 thresholding_max_val: float, dynamic_thresholding_ratio: float, use_graph: bool, require_tail_free: bool = True):
+        import torch
+        self.require_tail_free = bool(require_tail_free)
+        if min(int(B), int(T), int(Lp)) < 1:
+            raise ValueError("open_slots needs B, T, Lp >= 1")
+        self.den, self.B, self.T, self.Lp, self.use_graph = den, int(B), int(T), int(Lp), bool(use_graph)
+        self.order3, self.stochastic = bool(order3), bool(stochastic)
+        self.corr = None
+        if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True):
+            if self.stochastic:
+                raise ValueError("correcting_x0_fn applies to unipc / dpmsolver++ only: a slot loop that takes stochastic requests runs without it")
+            self.corr = (correcting_x0_fn, float(dynamic_thresholding_ratio), float(thresholding_max_val))
+        self.uncond = None
+        if unconditional_prompt is not None:
+            if len(unconditional_prompt.shape) != 3 or unconditional_prompt.shape[0] != 1 or unconditional_prompt.shape[1] > self.Lp:
+                raise ValueError(f"unconditional_prompt must be (1, Lu <= Lp = {self.Lp}, C), got {tuple(unconditional_prompt.shape)}")
+            self.uncond = unconditional_prompt
+        self.rep = 2 if self.uncond is not None else 1
+        self.pool = TablePool()
+        self._tables: Dict[tuple, object] = {}
+        self.items = [None] * self.B            # per slot: None (idle) or dict(key=, start=, steps=, length=)
+        self.step = 0
+        self.lengths = np.full((self.rep * self.B,), self.T, dtype=np.int32)
+        self.plens = np.full((self.rep * self.B,), self.Lp, dtype=np.int32)
+        self.seeds = np.zeros((self.B,), dtype=np.uint64)
+        self.scales = np.ones((self.B,), dtype=np.float32)
+        eng = den.engine
+        den._guard_before()
+        den._prepare(self.rep * self.B, self.T, self.Lp)
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        s = torch.cuda.current_stream(self.dev)
+        eng.set_lengths(self.lengths, stream=s)
+        eng.set_prompt_lengths(self.plens, stream=s)
+        if self.uncond is not None or eng.guidance is not None:
+            eng.set_guidance(self.scales if self.uncond is not None else None, stream=s)
+        den._x0_correction(eng, self.corr)
+        eng.open_slots(self.order3, self.stochastic, stream=s)
+        if self.stochastic:
+            eng.set_seeds(self.seeds, stream=s)
+        den._table_key = None                    # (the engine's table belongs to the pool now)
+
+    # -- bookkeeping -------------------------------------------------------------------------------------------------------
+    def idle(self):
+        return [b for b in range(self.B) if self.items[b] is None]
+
+    def finished(self):
+        return [b for b in range(self.B) if self.items[b] is not None and self.items[b]["start"] + self.items[b]["steps"] <= self.step]
+
+    def _table(self, key):
+        if key not in self._tables:
+            solver, steps, order, eta, opts = key
+            self._tables[key] = build_table(solver, steps, self.den._betas_for(solver), order, eta, **dict(opts))
+        return self._tables[key]
+
+    def check_request(self, schedule, guidance_scale: float = 1.0):
+        """the errors of a request that can be seen without its tensors (ValueError); returns (key, table, flags)"""
+        key = schedule_key(schedule)
+        solver, steps, order, eta, _ = key
+        if solver == "ddpm" and steps != len(self.den.betas64):
+            raise ValueError(f"ddpm runs every timestep of the schedule: steps must be {len(self.den.betas64)}, got {steps}")
+        if not np.isfinite(float(guidance_scale)):
+            raise ValueError("guidance_scale must be finite")
+        if float(guidance_scale) != 1.0 and self.uncond is None:
+            raise ValueError("a guided request needs a slot loop opened with unconditional_prompt=")
+        if self.corr is not None and solver in DISCRETE_SOLVERS:
+            raise ValueError(f"correcting_x0_fn applies to unipc / dpmsolver++ only, not {solver!r}")
+        n_tail = slot_tail_needed(self.den.precision, solver, order, guidance_scale, self.corr is not None)
+        if n_tail > 0 and self.require_tail_free:
+            raise ValueError(f"this request ({solver}, order {order}, guidance scale {float(guidance_scale):g}"
+                             f"{', corrected' if self.corr is not None else ''}) needs {n_tail} trailing fp32 evaluation(s) at precision "
+                             f"{self.den.precision!r}; a slot loop has no fp32 tail: open it on a Denoiser(precision=\"fp32\")")
+        table = self._table(key)
+        flags = table_flags(table)
+        if flags & ITEM_HIST2 and not self.order3:
+            raise ValueError("an order-3 request needs a slot loop opened with order3=True")
+        if flags & ITEM_NOISE and not self.stochastic:
+            raise ValueError(f"a stochastic request ({solver}) needs a slot loop opened with stochastic=True")
+        return key, table, flags
+
+    # -- the four calls ------------------------------------------------------------------------------------------------------
+    def admit(self, slot: int, content, prompt, noise, length: Optional[int] = None, prompt_length: Optional[int] = None, schedule=None,
+              seed: int = 0, guidance_scale: float = 1.0) -> None:
+        """one request into the idle ``slot`` at the current loop step: ``content`` (256, L), ``prompt`` (lp, 256), ``noise`` = x_T
+        (100, L) on the GPU, L <= T and lp <= Lp frames (``length`` / ``prompt_length`` default to them; shorter values use the first
+        frames), ``schedule`` = dict(solver=, steps=, order=, eta=, table options), ``seed`` of its noise stream (stochastic schedules),
+        ``guidance_scale`` (a guided loop)."""
+        self.admit_group([slot], [content], [prompt], [noise], None if length is None else [length],
+                         None if prompt_length is None else [prompt_length], [schedule], [seed], [guidance_scale])
+
+    def admit_group(self, slots, contents, prompts, noises, lengths=None, prompt_lengths=None, schedules=None, seeds=None, guidance_scales=None) -> None:
+        """``admit`` for several requests at once (lists of per-request tensors): one condition rebuild and one admit launch for all"""
+        import torch
+        n = len(slots)
+        if n == 0 or not (len(contents) == len(prompts) == len(noises) == n):
+            raise ValueError("admit_group needs one content, prompt and noise per slot")
+        slots = [int(b) for b in slots]
+        if len(set(slots)) != n or any(b < 0 or b >= self.B for b in slots):
+            raise ValueError(f"slots must be distinct and in [0, {self.B}), got {slots}")
+        busy = [b for b in slots if self.items[b] is not None]
+        if busy:
+            raise ValueError(f"slot(s) {busy} are busy: take them first")
+        schedules = [None] * n if schedules is None else list(schedules)
+        scales = [1.0] * n if guidance_scales is None else [float(g) for g in guidance_scales]
+        seeds = [0] * n if seeds is None else [int(v) for v in seeds]
+        cfg = self.den.cfg
+        reqs = []
+        for k in range(n):
+            if schedules[k] is None:
+                raise ValueError("a request needs its schedule: dict(solver=, steps=, ...)")
+            key, table, flags = self.check_request(schedules[k], scales[k])
+            c, p, x = contents[k], prompts[k], noises[k]
+            if c.dim() != 2 or c.shape[0] != cfg.content_channels or p.dim() != 2 or p.shape[1] != cfg.cross_attention_dim or \
+                    x.dim() != 2 or x.shape[0] != cfg.latent_channels:
+                raise ValueError(f"a request is content ({cfg.content_channels}, L), prompt (lp, {cfg.cross_attention_dim}), noise ({cfg.latent_channels}, L); "
+                                 f"got {tuple(c.shape)}, {tuple(p.shape)}, {tuple(x.shape)}")
+            L = int(c.shape[1]) if lengths is None else int(lengths[k])
+            lp = int(p.shape[0]) if prompt_lengths is None else int(prompt_lengths[k])
+            if not (1 <= L <= min(self.T, int(c.shape[1]), int(x.shape[1]))):
+                raise ValueError(f"length {L} outside [1, min(T = {self.T}, the content's {int(c.shape[1])} and the noise's {int(x.shape[1])} frames)]")
+            if not (1 <= lp <= min(self.Lp, int(p.shape[0]))):
+                raise ValueError(f"prompt_length {lp} outside [1, min(Lp = {self.Lp}, the prompt's {int(p.shape[0])} frames)]")
+            reqs.append((key, table, flags, L, lp))
+        dev = self.dev
+        s = torch.cuda.current_stream(dev)
+        eng = self.den.engine
+        if not any(it is not None for it in self.items) and self.step >= self.REBASE_AT:      # drained: rebase the 32-bit loop step
+            eng.rebase_slots(stream=s)
+            self.step = 0
+        c_all = torch.zeros((n, cfg.content_channels, self.T), dtype=torch.float32, device=dev)
+        p_all = torch.zeros((n, self.Lp, cfg.cross_attention_dim), dtype=torch.float32, device=dev)
+        x_all = torch.zeros((n, cfg.latent_channels, self.T), dtype=torch.float32, device=dev)
+        for k, (key, table, flags, L, lp) in enumerate(reqs):
+            c_all[k, :, :L] = contents[k][:, :L].to(dev, torch.float32)
+            p_all[k, :lp] = prompts[k][:lp].to(dev, torch.float32)
+            x_all[k, :, :L] = noises[k][:, :L].to(dev, torch.float32)
+        for k, b in enumerate(slots):
+            L, lp = reqs[k][3], reqs[k][4]
+            self.lengths[b], self.plens[b], self.seeds[b], self.scales[b] = L, lp, seeds[k], scales[k]
+            if self.rep == 2:      # (the unconditional half comes first)
+                self.lengths[b + self.B], self.plens[b], self.plens[b + self.B] = L, int(self.uncond.shape[1]), lp
+        if self.den.precision_check is not None and not self.den._precision_checked and not any(it is not None for it in self.items):
+            # the check's evaluations advance the engine's step counter and load the state of all items (zeros outside the admitted slots,
+            # as an idle slot has): rebase afterwards
+            self._self_check(slots, c_all, p_all, x_all, [r[1] for r in reqs], s)
+            eng.rebase_slots(stream=s)
+            self.step = 0
+        records = np.zeros((n, 4), dtype=np.int32)
+        acquired = []
+        try:
+            for k, (key, table, flags, L, lp) in enumerate(reqs):
+                row0, write = self.pool.acquire(key, table.coef)
+                acquired.append(key)
+                if write:
+                    eng.write_sampler_rows(row0, table.coef, stream=s)
+                records[k] = (row0, table.steps, self.step, flags)
+            eng.set_lengths(self.lengths, stream=s)
+            eng.set_prompt_lengths(self.plens, stream=s)
+            if self.stochastic:
+                eng.set_seeds(self.seeds, stream=s)
+            if self.rep == 2:
+                eng.set_guidance(self.scales, stream=s)
+                u = torch.zeros((n, self.Lp, cfg.cross_attention_dim), dtype=torch.float32, device=dev)
+                u[:, :self.uncond.shape[1]] = self.uncond.to(dev, torch.float32)
+                eng.set_condition_items(slots + [b + self.B for b in slots], torch.cat([c_all, c_all]), torch.cat([u, p_all]), None, stream=s)
+            else:
+                eng.set_condition_items(slots, c_all, p_all, None, stream=s)
+            eng.admit(slots, x_all, records, stream=s)
+        except Exception:          # nothing was admitted: the tables' users go back (the slots stay idle)
+            for key in acquired:
+                self.pool.release(key)
+            raise
+        for t in (c_all, p_all, x_all):
+            if t.is_cuda:
+                t.record_stream(s)
+        for k, b in enumerate(slots):
+            self.items[b] = dict(key=reqs[k][0], start=self.step, steps=reqs[k][1].steps, length=reqs[k][3])
+
+    def _self_check(self, slots, c_all, p_all, x_all, tables, s) -> None:
+        """the Denoiser's precision self-check on the first fill: the admitted requests' first evaluation point, the other slots idle"""
+        import torch
+        den, nb = self.den, self.rep * self.B
+        dev = c_all.device
+        cfg = den.cfg
+        c = torch.zeros((nb, cfg.content_channels, self.T), dtype=torch.float32, device=dev)
+        p = torch.zeros((nb, self.Lp, cfg.cross_attention_dim), dtype=torch.float32, device=dev)
+        x = torch.zeros((nb, cfg.latent_channels, self.T), dtype=torch.float32, device=dev)
+        t = torch.zeros((nb,), dtype=torch.float32, device=dev)
+        for k, b in enumerate(slots):
+            for h in range(self.rep):
+                c[b + h * self.B], x[b + h * self.B], t[b + h * self.B] = c_all[k], x_all[k], float(tables[k].coef[0, 0])
+            p[b + (self.rep - 1) * self.B] = p_all[k]
+            if self.rep == 2:
+                p[b, :self.uncond.shape[1]] = self.uncond[0].to(dev, torch.float32)
+        den._self_check([(x, t)], c, p, None, s, keep_fp32=False, lengths=self.lengths, prompt_lengths=self.plens)
+        if den.serving_fp32:
+            raise RuntimeError(f"the {den.precision} engine failed the precision self-check ({den.precision_error_seen:.2e}); a slot loop cannot "
+                               f"fall back per call: open it on a Denoiser(precision=\"fp32\")")
+
+    def run(self, n: Optional[int] = None):
+        """steps the loop until the next busy slot finishes -- not at all when one already has -- or by exactly ``n`` steps; returns the
+        finished slots (not yet taken)"""
+        import torch
+        if n is None:
+            ends = [it["start"] + it["steps"] for it in self.items if it is not None]
+            if not ends:
+                return []
+            n = max(0, min(ends) - self.step)
+        if n < 0:
+            raise ValueError("run(n) needs n >= 0")
+        if n > 0:
+            self.den.engine.sample_steps(int(n), use_graph=self.use_graph, stream=torch.cuda.current_stream(self.dev))
+            self.step += int(n)
+        return self.finished()
+
+    def close(self) -> None:
+        """ends the loop, whatever its slots hold (``ns2vc_sampler_end``: requests still running are dropped): the engine leaves slot mode
+        and takes ``sample`` / ``open_slots`` again.  Safe to call twice, and after an error in mid-loop."""
+        import torch
+        eng = self.den.engine
+        if eng.slot_step() >= 0:
+            scratch = torch.empty((self.B, self.den.cfg.latent_channels, self.T), dtype=torch.float32, device=self.dev)
+            eng.sample_end(scratch, stream=torch.cuda.current_stream(self.dev))
+        for b in range(self.B):
+            if self.items[b] is not None:
+                self.pool.release(self.items[b]["key"])
+                self.items[b] = None
+        self.den._table_key = None
+
+    def take(self, slots):
+        """latents (n, 100, T) of the finished ``slots`` (zeros past each request's length); the slots become idle"""
+        import torch
+        slots = [int(b) for b in slots]
+        bad = [b for b in slots if b < 0 or b >= self.B or self.items[b] is None or self.items[b]["start"] + self.items[b]["steps"] > self.step]
+        if bad:
+            raise ValueError(f"slot(s) {bad} hold no finished request")
+        out = torch.empty((len(slots), self.den.cfg.latent_channels, self.T), dtype=torch.float32, device=self.dev)
+        self.den.engine.take(slots, out, stream=torch.cuda.current_stream(self.dev))
+        for b in slots:
+            self.pool.release(self.items[b]["key"])
+            self.items[b] = None
+        return out

@@ -51,7 +51,7 @@ A row with noise == 0 adds nothing at all (not 0*z), so every noise-free table k
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -698,3 +698,188 @@ def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray]
         if trace is not None:
             trace.append(xe.copy())
     return xe
+
+
+# ---- slot loops: continuous batching ---------------------------------------------------------------------
+TABLE_ROWS = 1024         # rows of the engine's coefficient table (its fixed capacity)
+ITEM_HIST2, ITEM_NOISE = 1, 2      # record flags (common.h SOLVER_ITEM_*)
+
+
+def table_flags(table: SolverTable) -> int:
+    """the form an item with this table runs (the engine derives the same from the rows): 1 = history 2, 2 = noise"""
+    c = np.asarray(table.coef)
+    return (ITEM_HIST2 if (c[:, 10:12] != 0).any() else 0) | (ITEM_NOISE if (c[:, 9] != 0).any() else 0)
+
+
+def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarray], shape, trace: Optional[List[np.ndarray]] = None,
+                    noise_fn: Optional[Callable[[int, int, int], np.ndarray]] = None, correct_x0: Optional[Dict[str, object]] = None):
+    """Host statement of a slot loop (float32).  ``timeline[b]`` = the consecutive items of slot b, each ``(table, start, x_T)`` with
+    ``x_T`` shaped ``shape[1:]`` and ``start`` >= the previous item's start + rows; ``shape`` = (B, ...) of the loop's state.  At loop step r
+    the item of slot b with start <= r < start + rows is ACTIVE at its row r - start (``run_tables_numpy``'s update, history 2 where ITS
+    table has it); at r == start its state is loaded from x_T first (x_e = x_bar = x_T, d1 = m_prev = m_prev2 = 0: what an admission
+    writes).  A slot between items is HELD: evaluated -- at the clamped row of its last item, or at model time 0 while it has had none --,
+    never updated.  ``x0_fn(x (B, ...), t (B,))`` must treat the items independently, as the engine does.  ``noise_fn(b, k, j)`` -> the
+    normals of slot b's k-th item at its LOCAL row j.  Returns ``results[b][k]`` = x_e of that item after its last row: equal, bit for
+    bit, to the item run alone (``run_table_numpy``)."""
+    f = np.float32
+    B = int(shape[0])
+    if len(timeline) != B:
+        raise ValueError(f"{len(timeline)} slot timelines for {B} slots")
+    for b, items in enumerate(timeline):
+        end = 0
+        for k, (tab, start, x_T) in enumerate(items):
+            if int(start) < end:
+                raise ValueError(f"slot {b}: item {k} starts at loop step {start}, the slot is busy until {end}")
+            end = int(start) + tab.steps
+    corr = None
+    if correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)):
+        corr = dict(correct_x0)
+    lengths = None if corr is None else corr.pop("lengths", None)
+    xe = np.zeros(shape, f)
+    xbar, d1, m_prev, m_prev2 = (np.zeros(shape, f) for _ in range(4))
+    S = max([int(st) + tab.steps for items in timeline for tab, st, _ in items], default=0)
+    results = [[None] * len(items) for items in timeline]
+    cur = [-1] * B          # the item slot b holds (the last one admitted)
+    for r in range(S):
+        t = np.zeros((B,), f)
+        act = [None] * B
+        for b, items in enumerate(timeline):
+            if cur[b] + 1 < len(items) and int(items[cur[b] + 1][1]) == r:      # admission
+                cur[b] += 1
+                x_T = np.asarray(items[cur[b]][2], dtype=f)
+                xe[b], xbar[b] = x_T, x_T
+                d1[b], m_prev[b], m_prev2[b] = 0, 0, 0
+            if cur[b] >= 0:
+                tab, start, _ = items[cur[b]]
+                j = r - int(start)
+                t[b] = f(tab.coef[min(max(j, 0), tab.steps - 1), 0])
+                if 0 <= j < tab.steps:
+                    act[b] = (tab, j)
+        x0 = np.asarray(x0_fn(xe, t)).astype(f)
+        for b in range(B):
+            if act[b] is None:
+                continue
+            tab, j = act[b]
+            sl = slice(b, b + 1)
+            c = tab.coef[j]
+            _, alpha, sigma, g0, g1, A, Bc, d1c, pc = (f(v) for v in c[:9])
+            eps = (xe[sl] - alpha * x0[sl]) / sigma
+            m = (xe[sl] - sigma * eps) / alpha
+            if corr is not None:
+                m = _correct_x0(m, lengths=None if lengths is None else [lengths[b]], **corr)
+            x = xbar[sl] - g0 * d1[sl] - g1 * (m - m_prev[sl])
+            nb = A * x - Bc * m
+            if c[9] != 0:
+                if noise_fn is None:
+                    raise ValueError(f"row {j} of slot {b}'s {tab.solver} table adds noise: pass noise_fn")
+                nb = nb + f(c[9]) * np.asarray(noise_fn(b, cur[b], j), dtype=f)[None]
+            if has_history2(tab):
+                d2c, pe = f(c[10]), f(c[11])
+                nd = d1c * (m_prev[sl] - m) + d2c * (m_prev2[sl] - m)
+                ne = nb - pc * nd - pe * (m_prev2[sl] - m)
+                m_prev2[sl] = m_prev[sl]
+            else:
+                nd = d1c * (m_prev[sl] - m)
+                ne = nb - pc * nd
+            xbar[sl], d1[sl], xe[sl], m_prev[sl] = nb, nd, ne, m
+            if j == tab.steps - 1:
+                results[b][cur[b]] = xe[b].copy()
+        if trace is not None:
+            trace.append(xe.copy())
+    return results
+
+
+class TablePool:
+    """Which solver table lives in which rows of the engine's ``capacity``-row coefficient table during a slot loop.  Pure host
+    bookkeeping: ``acquire(key, coef)`` returns ``(row0, write)`` -- the table's first row and whether its rows must be written to the
+    engine (``Engine.write_sampler_rows``) -- and counts a user; ``release(key)`` drops one.  Tables are deduplicated by CONTENT (the
+    float32 bytes of the rows: two keys with equal rows share them).  A table nobody uses stays resident until room is needed; when an
+    acquisition does not fit, the unused tables are dropped and the free rows reused (first fit).  Live tables never move -- their
+    slots hold absolute rows --, so an acquisition that fits in no gap between them is refused with the capacity in the message."""
+
+    def __init__(self, capacity: int = TABLE_ROWS):
+        self.capacity = int(capacity)
+        self._by_content: Dict[bytes, list] = {}      # content -> [row0, rows, users]
+        self._content_of: Dict[object, bytes] = {}
+
+    def _gap(self, rows: int, entries) -> Optional[int]:
+        at = 0
+        for row0, n, _ in sorted(entries, key=lambda e: e[0]):
+            if row0 - at >= rows:
+                return at
+            at = row0 + n
+        return at if self.capacity - at >= rows else None
+
+    def rows_in_use(self) -> int:
+        return sum(e[1] for e in self._by_content.values() if e[2] > 0)
+
+    def resident(self) -> int:
+        return len(self._by_content)
+
+    def acquire(self, key, coef: np.ndarray):
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        if coef.ndim != 2 or coef.shape[1] != NCOEF or coef.shape[0] < 1:
+            raise ValueError(f"a table is (rows >= 1, {NCOEF}) float32, got {coef.shape}")
+        content = coef.tobytes()
+        e = self._by_content.get(content)
+        if e is not None:
+            e[2] += 1
+            self._content_of[key] = content
+            return e[0], False
+        rows = coef.shape[0]
+        row0 = self._gap(rows, self._by_content.values())
+        if row0 is None:          # repack: forget the tables no live slot uses
+            live = {c: v for c, v in self._by_content.items() if v[2] > 0}
+            row0 = self._gap(rows, live.values())
+            if row0 is None:
+                raise ValueError(f"a table of {rows} rows does not fit: {self.rows_in_use()} of the engine's {self.capacity} table rows are held by "
+                                 f"running requests (capacity {self.capacity})")
+            self._by_content = live
+            self._content_of = {k: c for k, c in self._content_of.items() if c in live}
+        self._by_content[content] = [row0, rows, 1]
+        self._content_of[key] = content
+        return row0, True
+
+    def release(self, key) -> None:
+        e = self._by_content.get(self._content_of.get(key, b""))
+        if e is None or e[2] <= 0:
+            raise ValueError(f"table {key!r} is not in use")
+        e[2] -= 1
+
+
+def plan_slots(steps: Sequence[int], n_slots: int, arrivals: Optional[Sequence[int]] = None):
+    """The scheduling of a slot loop as a pure function.  ``steps[i]`` = evaluations of request i (queue order), ``arrivals[i]`` = the loop
+    step from which it may start (default 0: all queued at once; non-decreasing).  Greedy and work-conserving: whenever a slot is free and
+    a request has arrived, the lowest free slot takes the next request of the queue at once.  Returns a list of events
+    ``(loop_step, take, admit)`` in loop order -- ``take`` = [(slot, request)] finished at that step, taken first; ``admit`` =
+    [(slot, request)] started at that step -- the loop steps ``run`` between two events being the difference of their loop steps, and the
+    loop's length as the last event's step.  No slot idles while a request that has arrived waits, so every request's start is the
+    earliest any schedule that keeps the queue order can give it, and the length is at most sum(steps) / n_slots + max(steps)."""
+    steps = [int(s) for s in steps]
+    if n_slots < 1 or any(s < 1 for s in steps):
+        raise ValueError("plan_slots needs n_slots >= 1 and steps >= 1")
+    arr = [0] * len(steps) if arrivals is None else [int(a) for a in arrivals]
+    if len(arr) != len(steps) or any(a < 0 for a in arr) or any(arr[i] > arr[i + 1] for i in range(len(arr) - 1)):
+        raise ValueError("arrivals must hold one non-decreasing loop step >= 0 per request")
+    free_at = [0] * n_slots           # loop step at which the slot's item finishes
+    holder = [None] * n_slots
+    events, nxt, r = [], 0, 0
+    while nxt < len(steps) or any(h is not None for h in holder):
+        take = [(b, holder[b]) for b in range(n_slots) if holder[b] is not None and free_at[b] <= r]
+        for b, _ in take:
+            holder[b] = None
+        admit = []
+        for b in range(n_slots):
+            if holder[b] is None and nxt < len(steps) and arr[nxt] <= r:
+                holder[b], free_at[b] = nxt, r + steps[nxt]
+                admit.append((b, nxt))
+                nxt += 1
+        if take or admit:
+            events.append((r, take, admit))
+        nexts = [free_at[b] for b in range(n_slots) if holder[b] is not None]
+        if nxt < len(steps) and any(h is None for h in holder):
+            nexts.append(arr[nxt])
+        if not nexts:
+            break
+        r = min(nexts)          # (> r: what finished by r was taken, what had arrived by r and found a slot was admitted)
+    return events

@@ -45,7 +45,7 @@ import numpy as np
 from .frontend import PreModel
 from .noise import derive_seed
 from .pipeline import Denoiser, OverlappedPipeline
-from .schedule import DISCRETE_SOLVERS, check_x0_correction, table_options
+from .schedule import DISCRETE_SOLVERS, ITEM_HIST2, ITEM_NOISE, build_table, check_x0_correction, plan_slots, schedule_key, table_flags, table_options
 
 
 @dataclass
@@ -205,4 +205,88 @@ class GroupedConverter:
         for idx, o in zip(groups, outs):
             for b, i in enumerate(idx):
                 result[i] = o[b]
+        return result
+
+
+class ContinuousConverter:
+    """Continuous batching: the segments are a QUEUE drained through ``slots`` slots of one running loop
+    (``Denoiser.open_slots``) instead of closed batches.  A slot that finishes is taken and gets the next segment of the queue at once, so
+    a 10-step preview does not wait for the 50-step render beside it and no slot-step is spent holding a finished item; which slot takes
+    which segment, how far the loop steps and when a slot is retired is decided by the pure function ``schedule.plan_slots``.  The engine
+    is prepared once for (``slots``, ``max_frames``, ``max_prompt``); every segment runs with its own length and prompt length.  The front
+    end runs per admitted group with exact lengths (``exact_lengths`` / ``exact_prompt_lengths``); x_T and the noise seed are per segment,
+    drawn as ``GroupedConverter`` draws them, so a segment's result does not depend on its slot or its neighbours.  ``Segment.schedule``
+    is honoured.  Options as ``GroupedConverter``'s; schedules that need an fp32 tail at the denoiser's precision are refused
+    (``SlotLoop``)."""
+
+    def __init__(self, pre_model: PreModel, denoiser: Denoiser, decode_fn: Optional[Callable] = None, slots: int = 32, max_frames: int = 938,
+                 max_prompt: int = 469, solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, eta: float = 0.0,
+                 guidance_scale: float = 1.0, unconditional_prompt: Optional[torch.Tensor] = None, correcting_x0_fn=None,
+                 thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995, use_graph: bool = True, **options):
+        self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
+        self.slots, self.max_frames, self.max_prompt, self.seed, self.use_graph = int(slots), int(max_frames), int(max_prompt), seed, use_graph
+        self.guided = unconditional_prompt is not None and float(guidance_scale) != 1.0
+        self.scale = float(guidance_scale) if self.guided else 1.0
+        self.uncond = unconditional_prompt if self.guided else None
+        if solver == "ddpm" and steps == 30:
+            steps = None
+        table_options(options)
+        if steps is None:
+            steps = {"ddim": 100, "ddpm": len(denoiser.betas64)}.get(solver, 20)
+        self.own = dict(solver=solver, steps=int(steps), order=order, eta=eta, **options)
+        self.corr = dict(correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio) \
+            if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True) else {}
+        self.last_plan = None          # (events of the last convert: tests, utilisation figures)
+
+    def convert(self, segments: Sequence[Segment]) -> List[torch.Tensor]:
+        """returns one tensor per segment, in input order: audio (samples,) with a ``decode_fn``, else the latent (100, T_i)"""
+        dev = next(self.pre.parameters()).device
+        specs = [s.schedule if getattr(s, "schedule", None) is not None else self.own for s in segments]
+        for i, s in enumerate(segments):
+            if int(s.content.shape[-1]) > self.max_frames or int(s.refer.shape[-1]) > self.max_prompt:
+                raise ValueError(f"segment {i} has {int(s.content.shape[-1])} frames and {int(s.refer.shape[-1])} prompt frames: the slots take "
+                                 f"{self.max_frames} and {self.max_prompt}")
+        built = {}                     # one table per distinct schedule, shared with the loop
+        for i, sp in enumerate(specs):
+            k = schedule_key(sp, i)
+            if k not in built:
+                built[k] = build_table(k[0], k[1], self.den._betas_for(k[0]), k[2], k[3], **dict(k[4]))
+        tables = [built[schedule_key(sp)] for sp in specs]
+        loop = self.den.open_slots(self.slots, self.max_frames, self.max_prompt, order3=any(table_flags(t) & ITEM_HIST2 for t in tables),
+                                   stochastic=any(table_flags(t) & ITEM_NOISE for t in tables), unconditional_prompt=self.uncond,
+                                   use_graph=self.use_graph, **self.corr)
+        loop._tables.update(built)
+        try:
+            for sp in specs:               # every refusal before anything runs
+                loop.check_request(sp, self.scale)
+            events = plan_slots([t.steps for t in tables], self.slots)
+            self.last_plan = events
+            result: List[Optional[torch.Tensor]] = [None] * len(segments)
+            nc = self.den.cfg.latent_channels
+            for r, take, admit in events:
+                if r > loop.step:
+                    loop.run(r - loop.step)
+                if take:
+                    lat = loop.take([b for b, _ in take])
+                    for k, (_, i) in enumerate(take):
+                        x = lat[k, :, :int(segments[i].content.shape[-1])]
+                        result[i] = x if self.decode is None else self.decode(x[None])[0]
+                if admit:
+                    idx = [i for _, i in admit]
+                    lens = [int(segments[i].content.shape[-1]) for i in idx]
+                    plens = [int(segments[i].refer.shape[-1]) for i in idx]
+                    c = torch.zeros((len(idx), segments[idx[0]].content.shape[0], max(lens)), dtype=torch.float32, device=dev)
+                    refer = torch.zeros((len(idx), segments[idx[0]].refer.shape[0], max(plens)), dtype=torch.float32, device=dev)
+                    for k, i in enumerate(idx):
+                        c[k, :, :lens[k]] = segments[i].content.to(dev, torch.float32)
+                        refer[k, :, :plens[k]] = segments[i].refer.to(dev, torch.float32)
+                    content, prompt, _ = self.pre.infer(c, refer, torch.tensor(lens, device=dev), torch.tensor(plens, device=dev), exact_lengths=True,
+                                                        exact_prompt_lengths=True)
+                    # x_T per SEGMENT at its own length, seeded by its position in the input (as GroupedConverter): its result does not depend on its slot
+                    noise = [torch.randn((nc, lens[k]), generator=torch.Generator().manual_seed(self.seed + i)).to(dev) for k, i in enumerate(idx)]
+                    loop.admit_group([b for b, _ in admit], [content[k] for k in range(len(idx))], [prompt[k] for k in range(len(idx))], noise, lens, plens,
+                                     [specs[i] for i in idx], [int(derive_seed(self.seed, i)) for i in idx], [self.scale] * len(idx))
+            torch.cuda.current_stream(dev).synchronize()
+        finally:                       # also after an error in mid-queue: no busy slot is left behind, the denoiser serves the next call
+            loop.close()
         return result
