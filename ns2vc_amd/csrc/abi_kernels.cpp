@@ -427,7 +427,7 @@ int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t
   for (int b = 0; b < n_items; ++b) {      // the records name rows of the table and buffers the launch reads: checked here, the kernel trusts them
     const int32_t* r = items_host + 4 * (size_t)b;
     if (r[0] < 0 || r[1] <= 0 || r[2] < 0 || (long)r[0] + r[1] > n_rows) return fail("item %d: rows %d + %d outside the table of %d, or start %d < 0", b, r[0], r[1], n_rows, r[2]);
-    if ((r[3] & ~(SOLVER_ITEM_HIST2 | SOLVER_ITEM_NOISE)) || r[3] == (SOLVER_ITEM_HIST2 | SOLVER_ITEM_NOISE)) return fail("item %d: flags %d", b, r[3]);
+    if ((r[3] & ~SOLVER_ITEM_BOTH) || r[3] == SOLVER_ITEM_BOTH) return fail("item %d: flags %d", b, r[3]);
     if ((r[3] & SOLVER_ITEM_HIST2) && !mprev2) return fail("item %d runs history 2: mprev2 is needed", b);
     if ((r[3] & SOLVER_ITEM_NOISE) && (!seeds_dev || mode)) return fail("item %d is stochastic: seeds_dev is needed and no correction applies", b);
   }

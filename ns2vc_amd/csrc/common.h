@@ -226,35 +226,17 @@ inline uint16_t f32_to_op16_bits(float v, int prec) { return prec == PREC_BF16 ?
 inline float op16_bits_to_f32(uint16_t b, int prec) { return prec == PREC_BF16 ? bf16_bits_to_f32(b) : f16_bits_to_f32(b); }
 // fixed-point scales of the epilogue GroupNorm statistics (order-independent int64 atomics => deterministic)
 // One element of the fused solver update (ns2vc_amd/schedule.py documents the recurrence; sampler/dpm_solver.py:433-442, 547-580, sampler/uni_pc.py:471-588):
-// the x0 -> eps -> x0 round trip of the reference's model wrapper, literally, then the unified multistep update.  ONE definition, used by
-// solver_update_kernel (misc.hip) and by the conv_out epilogue of conv3ts_kernel (convts.hip): the two forms give the same bits.
+// the x0 -> eps -> x0 round trip of the reference's model wrapper, literally (solver_m; the quantile kernel forms the same m), then the unified
+// multistep update.  ONE definition, solver_elem, used by the update kernels (misc.hip solver_quad) and, as solver_upd, by the conv_out epilogue of
+// conv3ts_kernel (convts.hip): all forms give the same bits.
+//   H2 (compile time): the second history term of order-3 rows (columns 10-11 of the table: d2c, pe; vmp2 = m_{i-2}).  Only tables with a nonzero
+//     column 10 or 11 run it; every other table keeps the arithmetic of H2 = false (d2c, pe, vmp2 unused).
+//   TH (compile time): the reference's correction of the predicted x0 (correcting_x0_fn: sampler/dpm_solver.py:416-425, :433-442,
+//     sampler/uni_pc.py:268-294), applied to m in front of everything that uses it.  0 = none (s unused); 1 = dynamic thresholding,
+//     clamp(m, -s, s) / s with s = max(the item's |m| quantile, max_val); 2 = the static clamp(m, -s, s), s = max_val.
+//     ns2vc_amd.schedule.correct_x0 is the host statement.
 struct SolverCoef { float alpha, sigma, g0, g1, A, Bc, d1c, pc; };
 __device__ __forceinline__ SolverCoef solver_coef(const float* __restrict__ c) { return SolverCoef{c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]}; }
-__device__ __forceinline__ void solver_upd(const SolverCoef& k, float vx0, float vxe, float vxb, float vd1, float vmp, float& oxe, float& oxb, float& od1, float& om) {
-  const float eps = (vxe - k.alpha * vx0) / k.sigma;
-  const float m = (vxe - k.sigma * eps) / k.alpha;
-  const float x = vxb - k.g0 * vd1 - k.g1 * (m - vmp);
-  const float nb = k.A * x - k.Bc * m;
-  const float nd = k.d1c * (vmp - m);
-  oxb = nb; od1 = nd; oxe = nb - k.pc * nd; om = m;
-}
-// The same element with the second history term of order-3 rows (columns 10-11 of the table: d2c, pe; vmp2 = m_{i-2}).  Only tables with
-// a nonzero column 10 or 11 run it (solver_update_kernel<TM, true>); every other table keeps solver_upd's arithmetic.
-__device__ __forceinline__ void solver_upd2(const SolverCoef& k, float d2c, float pe, float vx0, float vxe, float vxb, float vd1, float vmp, float vmp2,
-                                            float& oxe, float& oxb, float& od1, float& om) {
-  const float eps = (vxe - k.alpha * vx0) / k.sigma;
-  const float m = (vxe - k.sigma * eps) / k.alpha;
-  const float x = vxb - k.g0 * vd1 - k.g1 * (m - vmp);
-  const float nb = k.A * x - k.Bc * m;
-  const float dm2 = vmp2 - m;
-  const float nd = k.d1c * (vmp - m) + d2c * dm2;
-  oxb = nb; od1 = nd; oxe = nb - k.pc * nd - pe * dm2; om = m;
-}
-
-// The reference's correction of the predicted x0 (correcting_x0_fn: sampler/dpm_solver.py:416-425, :433-442, sampler/uni_pc.py:268-294), applied to m
-// in front of everything that uses it.  TH (compile time): 1 = dynamic thresholding, clamp(m, -s, s) / s with s = max(the item's |m| quantile,
-// max_val); 2 = the static clamp(m, -s, s), s = max_val.  solver_m is the round trip of solver_upd on its own (the quantile kernel forms the same m);
-// the two corrected updates are solver_upd / solver_upd2 with m replaced.  ns2vc_amd.schedule.correct_x0 is the host statement.
 __device__ __forceinline__ float solver_m(const SolverCoef& k, float vx0, float vxe) {
   const float eps = (vxe - k.alpha * vx0) / k.sigma;
   return (vxe - k.sigma * eps) / k.alpha;
@@ -263,24 +245,26 @@ template <int TH> __device__ __forceinline__ float solver_correct(float m, float
   const float c = fminf(fmaxf(m, -s), s);
   return TH == 1 ? c / s : c;
 }
-template <int TH>
-__device__ __forceinline__ void solver_upd_c(const SolverCoef& k, float s, float vx0, float vxe, float vxb, float vd1, float vmp, float& oxe, float& oxb, float& od1,
-                                             float& om) {
-  const float m = solver_correct<TH>(solver_m(k, vx0, vxe), s);
+// In two steps, because the stochastic samplers add their noise to xbar' in between (misc.hip solver_quad): solver_elem gives the new state
+// (xbar', d1', m), solver_xe the next evaluation point x_e' from it.  x_e' is formed ONCE, from the final state and next to its products: a second
+// statement of it inside a noise branch left the choice of fusing the multiply-adds to where the optimiser moved the subtraction.
+template <bool H2, int TH>
+__device__ __forceinline__ void solver_elem(const SolverCoef& k, float s, float d2c, float vx0, float vxe, float vxb, float vd1, float vmp, float vmp2,
+                                            float& oxb, float& od1, float& om) {
+  float m = solver_m(k, vx0, vxe);
+  if constexpr (TH != 0) m = solver_correct<TH>(m, s);
   const float x = vxb - k.g0 * vd1 - k.g1 * (m - vmp);
-  const float nb = k.A * x - k.Bc * m;
-  const float nd = k.d1c * (vmp - m);
-  oxb = nb; od1 = nd; oxe = nb - k.pc * nd; om = m;
+  oxb = k.A * x - k.Bc * m;
+  od1 = H2 ? k.d1c * (vmp - m) + d2c * (vmp2 - m) : k.d1c * (vmp - m);
+  om = m;
 }
-template <int TH>
-__device__ __forceinline__ void solver_upd2_c(const SolverCoef& k, float s, float d2c, float pe, float vx0, float vxe, float vxb, float vd1, float vmp, float vmp2,
-                                              float& oxe, float& oxb, float& od1, float& om) {
-  const float m = solver_correct<TH>(solver_m(k, vx0, vxe), s);
-  const float x = vxb - k.g0 * vd1 - k.g1 * (m - vmp);
-  const float nb = k.A * x - k.Bc * m;
-  const float dm2 = vmp2 - m;
-  const float nd = k.d1c * (vmp - m) + d2c * dm2;
-  oxb = nb; od1 = nd; oxe = nb - k.pc * nd - pe * dm2; om = m;
+template <bool H2>
+__device__ __forceinline__ float solver_xe(const SolverCoef& k, float pe, float oxb, float od1, float om, float vmp2) {
+  return H2 ? oxb - k.pc * od1 - pe * (vmp2 - om) : oxb - k.pc * od1;
+}
+__device__ __forceinline__ void solver_upd(const SolverCoef& k, float vx0, float vxe, float vxb, float vd1, float vmp, float& oxe, float& oxb, float& od1, float& om) {
+  solver_elem<false, 0>(k, 0.f, 0.f, vx0, vxe, vxb, vd1, vmp, 0.f, oxb, od1, om);
+  oxe = solver_xe<false>(k, 0.f, oxb, od1, om, 0.f);
 }
 
 // Classifier-free guidance (sampler/uni_pc.py:225-229, sampler/dpm_solver.py:327-331 combine in noise space; eps is affine in x0 with the same
@@ -323,7 +307,7 @@ __device__ __forceinline__ float4 philox_gauss4(unsigned long long seed, uint32_
 // uses row row0 + (r - start); otherwise it is HELD: its evaluation runs at the clamped row's timestep and nothing of its state is touched.
 // ns2vc_amd.schedule.run_tables_numpy is the host statement.
 struct SolverItem { int row0, steps, start, flags; };
-constexpr int SOLVER_ITEM_HIST2 = 1;      // the item's table has a nonzero column 10 or 11: solver_upd2 on all its rows, m_prev2 rolled
+constexpr int SOLVER_ITEM_HIST2 = 1;      // the item's table has a nonzero column 10 or 11: the history-2 element on all its rows, m_prev2 rolled
 constexpr int SOLVER_ITEM_NOISE = 2;      // ... a nonzero column 9: the noise term, Philox "table row" word = the item's local row
 __device__ __forceinline__ int solver_item_row(const SolverItem& it, int r, bool& active) {
   const int j = r - it.start;

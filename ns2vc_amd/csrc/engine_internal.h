@@ -32,6 +32,19 @@ inline int fail(const char* fmt, ...) {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// The form of a solver table, from its rows: SOLVER_ITEM_NOISE with a nonzero column 9, SOLVER_ITEM_HIST2 with a nonzero column 10 or 11.
+// No update runs both (SOLVER_ITEM_BOTH): every caller refuses such a table in its own words.
+constexpr int SOLVER_ITEM_BOTH = SOLVER_ITEM_NOISE | SOLVER_ITEM_HIST2;
+inline int solver_table_form(const float* rows, int n) {
+  int flags = 0;
+  for (int i = 0; i < n; ++i) {
+    const float* r = rows + (size_t)i * NS2VC_NCOEF;
+    if (r[9] != 0.f) flags |= SOLVER_ITEM_NOISE;
+    if (r[10] != 0.f || r[11] != 0.f) flags |= SOLVER_ITEM_HIST2;
+  }
+  return flags;
+}
+
 struct HostTensor {
   std::vector<float> data;
   std::vector<int64_t> shape;

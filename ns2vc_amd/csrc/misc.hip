@@ -4,6 +4,7 @@
 // wave64, vectorised 16-B accesses on the channels-last activation layout.
 #include "common.h"
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace ns2vc {
@@ -580,98 +581,35 @@ __global__ void prompt_bias_kernel(const uint8_t* __restrict__ mask, const int* 
 }
 
 // ---------------------------------------------------------------------------
-// Fused solver update (ns2vc_amd/schedule.py documents the recurrence and cites
-// sampler/dpm_solver.py + sampler/uni_pc.py).  Scalars come from row *step of
-// the device-resident coefficient table, so the same captured graph serves
-// every step.  H2 (compile time): the history-2 form of order-3 tables, which also reads m_{i-2} from mprev2 and
-// writes m_{i-1} there; H2 = false is the order <= 2 update, arithmetic unchanged (mprev2 unused).
-// GD (compile time): classifier-free guidance on an engine of 2n items, rows [0, n*T) unconditional and [n*T, 2n*T) conditional.  n4 counts
-// the quads of ONE half; quad i combines x0[i] and x0[i + half] by item b's scale (common.h guided_x0), runs the same update on the first
-// half's state and writes xe / xe_op to both halves, so the next evaluation is an ordinary 2n-item forward.  xbar, d1, mprev, mprev2 live in
-// the first half only.  GD = false: the instructions of the kernel without the flag (gd unused).
+// Fused solver update (ns2vc_amd/schedule.py documents the recurrence and cites sampler/dpm_solver.py + sampler/uni_pc.py).  Scalars come from a
+// row of the device-resident coefficient table chosen by *step_ptr, so the same captured graph serves every step.  The state is handled in quads
+// of four floats (ld % 4 == 0: a quad lies in one row, so in one item of T rows of ld columns), and ONE function, solver_quad, is the update of a
+// quad in every form: it loads the five state quads, guides x0, runs the element (common.h solver_elem), adds the noise and stores x_e', its operand
+// copy and the state.  The forms, all compile time:
+//   H2: the history-2 form of order-3 tables (a nonzero column 10 or 11), which also reads m_{i-2} from mprev2 and writes m_{i-1} there; H2 = false
+//       is the order <= 2 update (mprev2 unused).
+//   GD: classifier-free guidance on an engine of 2n items, rows [0, n*T) unconditional and [n*T, 2n*T) conditional.  n4 counts the quads of ONE
+//       half; quad i combines x0[i] and x0[i + n4] by its item's scale (common.h guided_x0), updates the first half's state and writes xe / xe_op
+//       to both halves, so the next evaluation is an ordinary 2n-item forward.  xbar, d1, mprev, mprev2 live in the first half only.
+//   TH: the x0 correction (ns2vc_sampler_set_x0_correction; common.h solver_correct).  0 = none; 1 = by the item's threshold max(cx.thr[b],
+//       cx.max_val), which the quantile kernel left there in the launch before; 2 = by cx.max_val alone.
+//   noise (run time, only with H2 = false and TH = 0 -- the launchers refuse the other pairs): a row with a nonzero column 9 adds knz * z to xbar'
+//       on the live elements, z = Philox normals keyed by the item's seed and (frame, channel quad, jrow).  knz == 0 is no term at all (adding 0 * z
+//       would turn -0 into +0), so every noise-free table keeps its bits.
+// Three kernels loop over the quads: solver_update_kernel (TH = 0) and solver_update_th_kernel (TH = 1 | 2) take the row `step` of a table all
+// items share; solver_update_items_kernel gives every item the row of its own table (per-item schedules, below).
+// Every form's quad is a straight line from its loads to its stores, and a kernel that runs two forms (the items kernel: H2 is a property of the
+// item) sweeps the quads once per form.  One sweep that branched per quad and joined the two forms' results in front of common stores was one ulp
+// off on x_e' (seen on the device): the optimiser moves the last subtraction of the two forms into the block where they join, away from its
+// products, and the fused multiply-adds of the straight-line form are lost.  For the same reason x_e' is formed once, behind the noise branch
+// (common.h solver_xe), not in the element and again in the branch.  tests/test_solver_bits_gpu.py holds every form to recorded bits.
 // ---------------------------------------------------------------------------
-template <typename TM, bool H2, bool GD>
-__global__ __launch_bounds__(256) void solver_update_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
-                                                            const float* __restrict__ x0, float* __restrict__ xe, TM* __restrict__ xe_op,
-                                                            float* __restrict__ xbar, float* __restrict__ d1,
-                                                            float* __restrict__ mprev, size_t n4, int split, SolverNoise nz,
-                                                            float* __restrict__ mprev2, SolverGuide gd) {
-  op_mode_init<TM>();
-  const int step = *step_ptr;
-  const SolverCoef k = solver_coef(coef + (size_t)step * ncoef);
-  // noise coefficient of this row (column 9): uniform per launch.  0 = no term at all (adding 0*z would turn -0 into +0), so
-  // every noise-free table keeps its bits.  (History-2 tables carry no noise: the launcher refuses the pair.)
-  const float knz = (!H2 && nz.seeds) ? coef[(size_t)step * ncoef + 9] : 0.f;
-  const float d2c = H2 ? coef[(size_t)step * ncoef + 10] : 0.f, pe = H2 ? coef[(size_t)step * ncoef + 11] : 0.f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
-    if constexpr (GD) {      // (ld % 4 == 0: a quad lies in one row, so in one item)
-      const float4 vxc = reinterpret_cast<const float4*>(x0)[i + n4];
-      const float sc = gd.scale[((4 * i) / (size_t)gd.ld) / (size_t)gd.T];
-      vx0 = make_float4(guided_x0(vx0.x, vxc.x, sc), guided_x0(vx0.y, vxc.y, sc), guided_x0(vx0.z, vxc.z, sc), guided_x0(vx0.w, vxc.w, sc));
-    }
-    const float4 vxe = reinterpret_cast<const float4*>(xe)[i];
-    const float4 vxb = reinterpret_cast<const float4*>(xbar)[i];
-    const float4 vd1 = reinterpret_cast<const float4*>(d1)[i];
-    const float4 vmp = reinterpret_cast<const float4*>(mprev)[i];
-    float4 oxe, oxb, od1, om;
-    if constexpr (H2) {
-      const float4 vm2 = reinterpret_cast<const float4*>(mprev2)[i];
-      solver_upd2(k, d2c, pe, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxe.x, oxb.x, od1.x, om.x);
-      solver_upd2(k, d2c, pe, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxe.y, oxb.y, od1.y, om.y);
-      solver_upd2(k, d2c, pe, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxe.z, oxb.z, od1.z, om.z);
-      solver_upd2(k, d2c, pe, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxe.w, oxb.w, od1.w, om.w);
-      out_f4(mprev2 + 4 * i, vmp.x, vmp.y, vmp.z, vmp.w);
-    } else {
-      solver_upd(k, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, oxe.x, oxb.x, od1.x, om.x);
-      solver_upd(k, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
-      solver_upd(k, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
-      solver_upd(k, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
-    }
-    if (!H2 && knz != 0.f) {      // xbar' += noise * z on the live elements (the state is zero elsewhere and stays so): ld % 4 == 0, one quad per thread
-      const size_t e = 4 * i, r = e / (size_t)nz.ld;
-      const int c = (int)(e - r * (size_t)nz.ld), b = (int)(r / (size_t)nz.T), t = (int)(r - (size_t)b * nz.T);
-      if (c < nz.nc && (!nz.lens || t < nz.lens[b])) {
-        const float4 z = philox_gauss4(nz.seeds[b], (uint32_t)t, (uint32_t)(c >> 2), (uint32_t)step);
-        oxb.x += knz * z.x;
-        if (c + 1 < nz.nc) oxb.y += knz * z.y;
-        if (c + 2 < nz.nc) oxb.z += knz * z.z;
-        if (c + 3 < nz.nc) oxb.w += knz * z.w;
-        oxe = make_float4(oxb.x - k.pc * od1.x, oxb.y - k.pc * od1.y, oxb.z - k.pc * od1.z, oxb.w - k.pc * od1.w);
-      }
-    }
-    out_f4(xe + 4 * i, oxe.x, oxe.y, oxe.z, oxe.w);
-    if (split) {                                            // hi + lo operand pair: rows of 2 * split columns, the lo plane `split` columns further
-      const size_t r = (4 * i) / (size_t)split;
-      TM* const q = xe_op + 4 * i + r * (size_t)split;
-      out_op4<TM>(q, oxe.x, oxe.y, oxe.z, oxe.w);
-      out_op4<TM>(q + split, op_rest<TM>(oxe.x), op_rest<TM>(oxe.y), op_rest<TM>(oxe.z), op_rest<TM>(oxe.w));
-    } else {
-      out_op4<TM>(xe_op + 4 * i, oxe.x, oxe.y, oxe.z, oxe.w);
-    }
-    if constexpr (GD) {                                     // the conditional half evaluates at the same point: its xe and operand copy (pair row r + n*T)
-      const size_t j = i + n4;
-      out_f4(xe + 4 * j, oxe.x, oxe.y, oxe.z, oxe.w);
-      if (split) {
-        const size_t r = (4 * j) / (size_t)split;
-        TM* const q = xe_op + 4 * j + r * (size_t)split;
-        out_op4<TM>(q, oxe.x, oxe.y, oxe.z, oxe.w);
-        out_op4<TM>(q + split, op_rest<TM>(oxe.x), op_rest<TM>(oxe.y), op_rest<TM>(oxe.z), op_rest<TM>(oxe.w));
-      } else {
-        out_op4<TM>(xe_op + 4 * j, oxe.x, oxe.y, oxe.z, oxe.w);
-      }
-    }
-    out_f4(xbar + 4 * i, oxb.x, oxb.y, oxb.z, oxb.w);
-    out_f4(d1 + 4 * i, od1.x, od1.y, od1.z, od1.w);
-    out_f4(mprev + 4 * i, om.x, om.y, om.z, om.w);
-  }
+// the scalars of one table row: the element's coefficients, the noise coefficient (0 without seeds), the history-2 pair
+struct SolverRow { SolverCoef k; float knz, d2c, pe; };
+template <bool H2>
+__device__ __forceinline__ SolverRow solver_row(const float* __restrict__ crow, bool noisy) {
+  return SolverRow{solver_coef(crow), (!H2 && noisy) ? crow[9] : 0.f, H2 ? crow[10] : 0.f, H2 ? crow[11] : 0.f};
 }
-// The corrected update (ns2vc_sampler_set_x0_correction): solver_update_kernel with m corrected in front of everything that uses it (common.h
-// solver_correct, solver_upd_c / solver_upd2_c) and no noise term -- the reference's discrete samplers have no correction, the launcher refuses the
-// pair.  TH (compile time): 1 = by item b's threshold max(cx.thr[b], cx.max_val), which abs_quantile_kernel left there in the launch before; 2 = by
-// cx.max_val alone.  Items are cx.T rows of cx.ld columns; under GD those of ONE half.  A kernel of its own, not a fourth parameter of
-// solver_update_kernel: that kernel's instantiations keep their names and their instructions (tools/kernel_code_diff.py).  Keep the two in step: mode 2 with a max_val
-// no value reaches must give the plain update's bits (tests/test_x0_correction_gpu.py pins that for every form).
 // the new x_e of quad i and its operand copy: fp32 rows, or for 16-bit types the hi + lo pair in rows of 2 * split columns, the lo plane `split` columns further
 template <typename TM>
 __device__ __forceinline__ void solver_store_xe(float* __restrict__ xe, TM* __restrict__ xe_op, size_t i, int split, const float4& oxe) {
@@ -685,6 +623,87 @@ __device__ __forceinline__ void solver_store_xe(float* __restrict__ xe, TM* __re
     out_op4<TM>(xe_op + 4 * i, oxe.x, oxe.y, oxe.z, oxe.w);
   }
 }
+// RECORDED BEHAVIOUR, kept bit for bit (tests/test_solver_bits_gpu.py): under per-item schedules (own_rows) the x_e' of a quad that TOOK noise is
+// the difference of xbar' and the ROUNDED product pc * d1' -- one rounding more than solver_xe's multiply-add, which every other quad and the
+// shared-table kernels have.  The kernel this body replaced came out that way by code motion; a change that may move bits should drop it.
+__device__ __forceinline__ float solver_xe_rounded(const SolverCoef& k, float oxb, float od1) {
+#pragma clang fp contract(off)
+  const float p = k.pc * od1;
+  return oxb - p;
+}
+// quad i with the scalars kr of its row; jrow = the Philox "table row" word; T, ld = the item shape (read only where an item index is needed)
+template <typename TM, bool H2, bool GD, int TH>
+__device__ __forceinline__ void solver_quad(const SolverRow& kr, int jrow, size_t i, const float* __restrict__ x0, float* __restrict__ xe,
+                                            TM* __restrict__ xe_op, float* __restrict__ xbar, float* __restrict__ d1, float* __restrict__ mprev,
+                                            float* __restrict__ mprev2, size_t n4, int split, const SolverNoise& nz, const SolverGuide& gd,
+                                            const SolverCorrect& cx, int T, int ld, bool own_rows) {
+  static_assert(TH >= 0 && TH <= 2, "0 = uncorrected, 1 = dynamic thresholding, 2 = clamp");
+  const SolverCoef& k = kr.k;
+  const auto item = [&] { return (int)(((4 * i) / (size_t)ld) / (size_t)T); };
+  float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
+  if constexpr (GD) {
+    const float4 vxc = reinterpret_cast<const float4*>(x0)[i + n4];
+    const float sc = gd.scale[item()];
+    vx0 = make_float4(guided_x0(vx0.x, vxc.x, sc), guided_x0(vx0.y, vxc.y, sc), guided_x0(vx0.z, vxc.z, sc), guided_x0(vx0.w, vxc.w, sc));
+  }
+  const float4 vxe = reinterpret_cast<const float4*>(xe)[i];
+  const float4 vxb = reinterpret_cast<const float4*>(xbar)[i];
+  const float4 vd1 = reinterpret_cast<const float4*>(d1)[i];
+  const float4 vmp = reinterpret_cast<const float4*>(mprev)[i];
+  float sb = 0.f;
+  if constexpr (TH != 0) sb = TH == 1 ? fmaxf(cx.thr[item()], cx.max_val) : cx.max_val;
+  float4 vm2 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (H2) vm2 = reinterpret_cast<const float4*>(mprev2)[i];
+  float4 oxb, od1, om;
+  solver_elem<H2, TH>(k, sb, kr.d2c, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxb.x, od1.x, om.x);
+  solver_elem<H2, TH>(k, sb, kr.d2c, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxb.y, od1.y, om.y);
+  solver_elem<H2, TH>(k, sb, kr.d2c, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxb.z, od1.z, om.z);
+  solver_elem<H2, TH>(k, sb, kr.d2c, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxb.w, od1.w, om.w);
+  if constexpr (H2) out_f4(mprev2 + 4 * i, vmp.x, vmp.y, vmp.z, vmp.w);
+  bool noised = false;
+  float4 oxe_rounded;
+  if constexpr (!H2 && TH == 0) {
+    if (kr.knz != 0.f) {      // xbar' += noise * z on the live elements (the state is zero elsewhere and stays so)
+      const size_t e = 4 * i, r = e / (size_t)ld;
+      const int c = (int)(e - r * (size_t)ld), b = (int)(r / (size_t)T), t = (int)(r - (size_t)b * T);
+      if (c < nz.nc && (!nz.lens || t < nz.lens[b])) {
+        const float4 z = philox_gauss4(nz.seeds[b], (uint32_t)t, (uint32_t)(c >> 2), (uint32_t)jrow);
+        oxb.x += kr.knz * z.x;
+        if (c + 1 < nz.nc) oxb.y += kr.knz * z.y;
+        if (c + 2 < nz.nc) oxb.z += kr.knz * z.z;
+        if (c + 3 < nz.nc) oxb.w += kr.knz * z.w;
+        if (own_rows) {
+          noised = true;
+          oxe_rounded = make_float4(solver_xe_rounded(k, oxb.x, od1.x), solver_xe_rounded(k, oxb.y, od1.y), solver_xe_rounded(k, oxb.z, od1.z),
+                                    solver_xe_rounded(k, oxb.w, od1.w));
+        }
+      }
+    }
+  }
+  float4 oxe = make_float4(solver_xe<H2>(k, kr.pe, oxb.x, od1.x, om.x, vm2.x), solver_xe<H2>(k, kr.pe, oxb.y, od1.y, om.y, vm2.y),
+                           solver_xe<H2>(k, kr.pe, oxb.z, od1.z, om.z, vm2.z), solver_xe<H2>(k, kr.pe, oxb.w, od1.w, om.w, vm2.w));
+  if (noised) oxe = oxe_rounded;
+  solver_store_xe<TM>(xe, xe_op, i, split, oxe);
+  if constexpr (GD) solver_store_xe<TM>(xe, xe_op, i + n4, split, oxe);      // the conditional half evaluates at the same point (pair row r + n*T)
+  out_f4(xbar + 4 * i, oxb.x, oxb.y, oxb.z, oxb.w);
+  out_f4(d1 + 4 * i, od1.x, od1.y, od1.z, od1.w);
+  out_f4(mprev + 4 * i, om.x, om.y, om.z, om.w);
+}
+template <typename TM, bool H2, bool GD>
+__global__ __launch_bounds__(256) void solver_update_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
+                                                            const float* __restrict__ x0, float* __restrict__ xe, TM* __restrict__ xe_op,
+                                                            float* __restrict__ xbar, float* __restrict__ d1,
+                                                            float* __restrict__ mprev, size_t n4, int split, SolverNoise nz,
+                                                            float* __restrict__ mprev2, SolverGuide gd) {
+  op_mode_init<TM>();
+  const int step = *step_ptr;
+  const SolverRow kr = solver_row<H2>(coef + (size_t)step * ncoef, nz.seeds != nullptr);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
+    solver_quad<TM, H2, GD, 0>(kr, step, i, x0, xe, xe_op, xbar, d1, mprev, mprev2, n4, split, nz, gd, SolverCorrect(), GD ? gd.T : nz.T,
+                               GD ? gd.ld : nz.ld, false);
+}
+// the corrected update: no noise term (the reference's discrete samplers have no correction, the launcher refuses the pair); items are cx.T rows
+// of cx.ld columns, under GD those of ONE half
 template <typename TM, bool H2, bool GD, int TH>
 __global__ __launch_bounds__(256) void solver_update_th_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
                                                                const float* __restrict__ x0, float* __restrict__ xe, TM* __restrict__ xe_op,
@@ -694,151 +713,38 @@ __global__ __launch_bounds__(256) void solver_update_th_kernel(const float* __re
   static_assert(TH == 1 || TH == 2, "the uncorrected update is solver_update_kernel");
   op_mode_init<TM>();
   const int step = *step_ptr;
-  const SolverCoef k = solver_coef(coef + (size_t)step * ncoef);
-  const float d2c = H2 ? coef[(size_t)step * ncoef + 10] : 0.f, pe = H2 ? coef[(size_t)step * ncoef + 11] : 0.f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
-    if constexpr (GD) {      // (ld % 4 == 0: a quad lies in one row, so in one item)
-      const float4 vxc = reinterpret_cast<const float4*>(x0)[i + n4];
-      const float sc = gd.scale[((4 * i) / (size_t)gd.ld) / (size_t)gd.T];
-      vx0 = make_float4(guided_x0(vx0.x, vxc.x, sc), guided_x0(vx0.y, vxc.y, sc), guided_x0(vx0.z, vxc.z, sc), guided_x0(vx0.w, vxc.w, sc));
-    }
-    const float4 vxe = reinterpret_cast<const float4*>(xe)[i];
-    const float4 vxb = reinterpret_cast<const float4*>(xbar)[i];
-    const float4 vd1 = reinterpret_cast<const float4*>(d1)[i];
-    const float4 vmp = reinterpret_cast<const float4*>(mprev)[i];
-    float4 oxe, oxb, od1, om;
-    {                             // (ld % 4 == 0: a quad lies in one row, so in one item)
-      const float sb = TH == 1 ? fmaxf(cx.thr[((4 * i) / (size_t)cx.ld) / (size_t)cx.T], cx.max_val) : cx.max_val;
-      if constexpr (H2) {
-        const float4 vm2 = reinterpret_cast<const float4*>(mprev2)[i];
-        solver_upd2_c<TH>(k, sb, d2c, pe, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxe.x, oxb.x, od1.x, om.x);
-        solver_upd2_c<TH>(k, sb, d2c, pe, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxe.y, oxb.y, od1.y, om.y);
-        solver_upd2_c<TH>(k, sb, d2c, pe, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxe.z, oxb.z, od1.z, om.z);
-        solver_upd2_c<TH>(k, sb, d2c, pe, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxe.w, oxb.w, od1.w, om.w);
-        out_f4(mprev2 + 4 * i, vmp.x, vmp.y, vmp.z, vmp.w);
-      } else {
-        solver_upd_c<TH>(k, sb, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, oxe.x, oxb.x, od1.x, om.x);
-        solver_upd_c<TH>(k, sb, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
-        solver_upd_c<TH>(k, sb, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
-        solver_upd_c<TH>(k, sb, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
-      }
-    }
-    solver_store_xe<TM>(xe, xe_op, i, split, oxe);
-    if constexpr (GD) solver_store_xe<TM>(xe, xe_op, i + n4, split, oxe);      // the conditional half evaluates at the same point (pair row r + n*T)
-    out_f4(xbar + 4 * i, oxb.x, oxb.y, oxb.z, oxb.w);
-    out_f4(d1 + 4 * i, od1.x, od1.y, od1.z, od1.w);
-    out_f4(mprev + 4 * i, om.x, om.y, om.z, om.w);
-  }
+  const SolverRow kr = solver_row<H2>(coef + (size_t)step * ncoef, false);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
+    solver_quad<TM, H2, GD, TH>(kr, step, i, x0, xe, xe_op, xbar, d1, mprev, mprev2, n4, split, SolverNoise(), gd, cx, cx.T, cx.ld, false);
 }
 // The update under per-item schedules (ns2vc_sampler_load_items): every loop item walks a solver table of its own.  Quad i belongs to item
-// b = (4 i / ld) / T (ld % 4 == 0: a quad lies in one row, so in one item -- the branches below are uniform per quad); its record (common.h
-// SolverItem) says where the item's rows sit in the coefficient table, how many there are, at which loop step it starts and which form it runs.
-// At loop step r = *step_ptr item b is ACTIVE when 0 <= r - start < steps and then uses row r - start of its table; otherwise it is HELD and
-// nothing of it is loaded or stored: xe, both planes of xe_op, xbar, d1, mprev and mprev2 keep their bits.  An active item runs what the
-// shared-table kernels run for its table, from the same inline functions: flag SOLVER_ITEM_HIST2 -> solver_upd2 and the roll of mprev2 (every row
-// of such an item, as solver_update_kernel<TM, true> does for such a table), else solver_upd; flag SOLVER_ITEM_NOISE -> the noise term of a row
-// with a nonzero column 9, its Philox "table row" word the item's LOCAL row, so the stream is what the item has alone.  TH (compile time): 0 = no
-// correction, 1 | 2 = solver_update_th_kernel's (no noise with it: the launcher refuses the pair).  GD as there: n4 counts the quads of one half,
-// the records cover the n loop items and both halves of xe / xe_op are written.  3 types x GD x TH = 18 instantiations; the item's form differs
-// between the items of one launch, so it is a run-time choice -- made by TWO sweeps over the quads, the first for the items without history 2,
-// the second (only with an mprev2 buffer) for those with it, each form's quad (solver_items_quad) a straight line from its loads to its stores.
-// One sweep that branched per quad and joined the two forms' results in front of common stores was one ulp off the shared-table kernels on x_e'
-// (seen on the device): the optimiser moves the last subtraction of the two forms into the block where they join, away from its products, and
-// the fused multiply-adds solver_update_kernel has are lost.  A kernel of its own for the reason solver_update_th_kernel is one.
-template <typename TM, bool GD, int TH, bool H2>
-__device__ __forceinline__ void solver_items_quad(const float* __restrict__ crow, int jrow, int b, size_t i, const float* __restrict__ x0,
-                                                  float* __restrict__ xe, TM* __restrict__ xe_op, float* __restrict__ xbar, float* __restrict__ d1,
-                                                  float* __restrict__ mprev, size_t n4, int split, const SolverNoise& nz, bool noisy,
-                                                  float* __restrict__ mprev2, const SolverGuide& gd, const SolverCorrect& cx, int T, int ld) {
-  const SolverCoef k = solver_coef(crow);
-  const float knz = (!H2 && TH == 0 && noisy) ? crow[9] : 0.f;      // 0 = no term at all, as in solver_update_kernel
-  const float d2c = H2 ? crow[10] : 0.f, pe = H2 ? crow[11] : 0.f;
-  float4 vx0 = reinterpret_cast<const float4*>(x0)[i];
-  if constexpr (GD) {
-    const float4 vxc = reinterpret_cast<const float4*>(x0)[i + n4];
-    const float sc = gd.scale[b];
-    vx0 = make_float4(guided_x0(vx0.x, vxc.x, sc), guided_x0(vx0.y, vxc.y, sc), guided_x0(vx0.z, vxc.z, sc), guided_x0(vx0.w, vxc.w, sc));
-  }
-  const float4 vxe = reinterpret_cast<const float4*>(xe)[i];
-  const float4 vxb = reinterpret_cast<const float4*>(xbar)[i];
-  const float4 vd1 = reinterpret_cast<const float4*>(d1)[i];
-  const float4 vmp = reinterpret_cast<const float4*>(mprev)[i];
-  float4 oxe, oxb, od1, om;
-  if constexpr (TH != 0) {
-    const float sb = TH == 1 ? fmaxf(cx.thr[b], cx.max_val) : cx.max_val;
-    if constexpr (H2) {
-      const float4 vm2 = reinterpret_cast<const float4*>(mprev2)[i];
-      solver_upd2_c<TH>(k, sb, d2c, pe, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxe.x, oxb.x, od1.x, om.x);
-      solver_upd2_c<TH>(k, sb, d2c, pe, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxe.y, oxb.y, od1.y, om.y);
-      solver_upd2_c<TH>(k, sb, d2c, pe, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxe.z, oxb.z, od1.z, om.z);
-      solver_upd2_c<TH>(k, sb, d2c, pe, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxe.w, oxb.w, od1.w, om.w);
-      out_f4(mprev2 + 4 * i, vmp.x, vmp.y, vmp.z, vmp.w);
-    } else {
-      solver_upd_c<TH>(k, sb, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, oxe.x, oxb.x, od1.x, om.x);
-      solver_upd_c<TH>(k, sb, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
-      solver_upd_c<TH>(k, sb, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
-      solver_upd_c<TH>(k, sb, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
-    }
-  } else if constexpr (H2) {
-    const float4 vm2 = reinterpret_cast<const float4*>(mprev2)[i];
-    solver_upd2(k, d2c, pe, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxe.x, oxb.x, od1.x, om.x);
-    solver_upd2(k, d2c, pe, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxe.y, oxb.y, od1.y, om.y);
-    solver_upd2(k, d2c, pe, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxe.z, oxb.z, od1.z, om.z);
-    solver_upd2(k, d2c, pe, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxe.w, oxb.w, od1.w, om.w);
-    out_f4(mprev2 + 4 * i, vmp.x, vmp.y, vmp.z, vmp.w);
-  } else {
-    solver_upd(k, vx0.x, vxe.x, vxb.x, vd1.x, vmp.x, oxe.x, oxb.x, od1.x, om.x);
-    solver_upd(k, vx0.y, vxe.y, vxb.y, vd1.y, vmp.y, oxe.y, oxb.y, od1.y, om.y);
-    solver_upd(k, vx0.z, vxe.z, vxb.z, vd1.z, vmp.z, oxe.z, oxb.z, od1.z, om.z);
-    solver_upd(k, vx0.w, vxe.w, vxb.w, vd1.w, vmp.w, oxe.w, oxb.w, od1.w, om.w);
-  }
-  if (!H2 && TH == 0 && knz != 0.f) {      // xbar' += noise * z on the live elements, as in solver_update_kernel
-    const size_t e = 4 * i, r = e / (size_t)ld;
-    const int c = (int)(e - r * (size_t)ld), t = (int)(r - (size_t)b * T);
-    if (c < nz.nc && (!nz.lens || t < nz.lens[b])) {
-      const float4 z = philox_gauss4(nz.seeds[b], (uint32_t)t, (uint32_t)(c >> 2), (uint32_t)jrow);
-      oxb.x += knz * z.x;
-      if (c + 1 < nz.nc) oxb.y += knz * z.y;
-      if (c + 2 < nz.nc) oxb.z += knz * z.z;
-      if (c + 3 < nz.nc) oxb.w += knz * z.w;
-      oxe = make_float4(oxb.x - k.pc * od1.x, oxb.y - k.pc * od1.y, oxb.z - k.pc * od1.z, oxb.w - k.pc * od1.w);
-    }
-  }
-  solver_store_xe<TM>(xe, xe_op, i, split, oxe);
-  if constexpr (GD) solver_store_xe<TM>(xe, xe_op, i + n4, split, oxe);      // the conditional half evaluates at the same point (pair row r + n*T)
-  out_f4(xbar + 4 * i, oxb.x, oxb.y, oxb.z, oxb.w);
-  out_f4(d1 + 4 * i, od1.x, od1.y, od1.z, od1.w);
-  out_f4(mprev + 4 * i, om.x, om.y, om.z, om.w);
-}
+// b = (4 i / ld) / T; its record (common.h SolverItem) says where the item's rows sit in the coefficient table, how many there are, at which loop
+// step it starts and which form it runs.  At loop step r = *step_ptr item b is ACTIVE when 0 <= r - start < steps and then uses row r - start of
+// its table; otherwise it is HELD and nothing of it is loaded or stored: xe, both planes of xe_op, xbar, d1, mprev and mprev2 keep their bits.
+// Flag SOLVER_ITEM_HIST2 -> H2 on every row of the item; flag SOLVER_ITEM_NOISE -> the noise term, its Philox "table row" word the item's LOCAL
+// row, so the stream is what the item has alone.  n4 counts the quads of one half, the records cover the n loop items.  Two sweeps: the items
+// without history 2, then (only with an mprev2 buffer) those with it.
 template <typename TM, bool GD, int TH>
 __global__ __launch_bounds__(256) void solver_update_items_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
                                                                   SolverItems si, const float* __restrict__ x0, float* __restrict__ xe,
                                                                   TM* __restrict__ xe_op, float* __restrict__ xbar, float* __restrict__ d1,
                                                                   float* __restrict__ mprev, size_t n4, int split, SolverNoise nz,
                                                                   float* __restrict__ mprev2, SolverGuide gd, SolverCorrect cx) {
-  static_assert(TH >= 0 && TH <= 2, "0 = uncorrected, 1 = dynamic thresholding, 2 = clamp");
   op_mode_init<TM>();
   const int step = *step_ptr;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const int b = (int)(((4 * i) / (size_t)si.ld) / (size_t)si.T);
-    const SolverItem it = si.rec[b];
-    bool active;
-    const int row = solver_item_row(it, step, active);
-    if (!active || (it.flags & SOLVER_ITEM_HIST2)) continue;      // held: nothing of this item is touched; history 2: the second sweep
-    solver_items_quad<TM, GD, TH, false>(coef + (size_t)row * ncoef, row - it.row0, b, i, x0, xe, xe_op, xbar, d1, mprev, n4, split, nz,
-                                         (it.flags & SOLVER_ITEM_NOISE) != 0, mprev2, gd, cx, si.T, si.ld);
-  }
-  if (!mprev2) return;                                            // (no item of the batch has history 2)
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const int b = (int)(((4 * i) / (size_t)si.ld) / (size_t)si.T);
-    const SolverItem it = si.rec[b];
-    bool active;
-    const int row = solver_item_row(it, step, active);
-    if (!active || !(it.flags & SOLVER_ITEM_HIST2)) continue;
-    solver_items_quad<TM, GD, TH, true>(coef + (size_t)row * ncoef, row - it.row0, b, i, x0, xe, xe_op, xbar, d1, mprev, n4, split, nz, false,
-                                        mprev2, gd, cx, si.T, si.ld);
-  }
+  const auto sweep = [&](auto h2) {
+    constexpr bool H2 = decltype(h2)::value;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+      const SolverItem it = si.rec[((4 * i) / (size_t)si.ld) / (size_t)si.T];
+      bool active;
+      const int row = solver_item_row(it, step, active);
+      if (!active || ((it.flags & SOLVER_ITEM_HIST2) != 0) != H2) continue;      // held: nothing of this item is touched; the other form: the other sweep
+      const SolverRow kr = solver_row<H2>(coef + (size_t)row * ncoef, TH == 0 && (it.flags & SOLVER_ITEM_NOISE) != 0);
+      solver_quad<TM, H2, GD, TH>(kr, row - it.row0, i, x0, xe, xe_op, xbar, d1, mprev, mprev2, n4, split, nz, gd, cx, si.T, si.ld, true);
+    }
+  };
+  sweep(std::false_type{});
+  if (mprev2) sweep(std::true_type{});                                            // (without the buffer no item of the batch has history 2)
 }
 // ---------------------------------------------------------------------------
 // Per-item quantile of |m| for the dynamic thresholding of the predicted x0 (sampler/dpm_solver.py:416-425, sampler/uni_pc.py:268-277:
@@ -872,24 +778,15 @@ __device__ __forceinline__ void quant_keys(const QuantArgs& q, const SolverCoef&
   key[0] = __float_as_uint(v.x) & 0x7FFFFFFFu; key[1] = __float_as_uint(v.y) & 0x7FFFFFFFu;
   key[2] = __float_as_uint(v.z) & 0x7FFFFFFFu; key[3] = __float_as_uint(v.w) & 0x7FFFFFFFu;
 }
+// the select over the nquad quads of item b (n > 0 live elements), m formed with the table row k and the guidance scale sc; writes thr[b]
 template <int SRC>
-__global__ __launch_bounds__(1024) void abs_quantile_kernel(QuantArgs q, float* __restrict__ thr) {
+__device__ __forceinline__ void quant_select(const QuantArgs& q, const SolverCoef& k, float sc, int b, int nquad, unsigned n, float* __restrict__ thr) {
   constexpr int NT = 1024, NBIN = 2048;
   __shared__ unsigned s_hist[NBIN];
   __shared__ unsigned s_wave[16];
   __shared__ unsigned s_sel[4];                // chosen bin, keys below it, its count, minimum above
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
-  const int len = q.lens ? min(max(q.lens[b], 0), q.T) : q.T;
-  const int ldq = q.ld >> 2, nquad = len * ldq;
-  const unsigned n = (unsigned)len * (unsigned)q.nc;
-  if (n == 0) {                                // (block-uniform)
-    if (tid == 0) thr[b] = 0.f;
-    return;
-  }
-  SolverCoef k{};
-  float sc = 1.f;
-  if constexpr (SRC != 0) k = solver_coef(q.coef + (size_t)(*q.step_ptr) * q.ncoef);
-  if constexpr (SRC == 2) sc = q.scale[b];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ldq = q.ld >> 2;
   const size_t base = (size_t)b * q.T * q.ld;
   const float pos = q.p * (float)(n - 1);
   const unsigned lo = min((unsigned)floorf(pos), n - 1), hi = min((unsigned)ceilf(pos), n - 1);
@@ -962,104 +859,32 @@ __global__ __launch_bounds__(1024) void abs_quantile_kernel(QuantArgs q, float* 
     thr[b] = w < 0.5f ? fmaf(w, dlt, a) : fmaf(-dlt, 1.0f - w, e);     // torch's lerp
   }
 }
+// what the two kernels do after they have the item's table row: an item without elements gives 0 (block-uniform), every other one the select
+template <int SRC>
+__device__ __forceinline__ void quant_item(const QuantArgs& q, const SolverCoef& k, int b, float* __restrict__ thr) {
+  const int len = q.lens ? min(max(q.lens[b], 0), q.T) : q.T;
+  const unsigned n = (unsigned)len * (unsigned)q.nc;
+  if (n == 0) {
+    if (threadIdx.x == 0) thr[b] = 0.f;
+    return;
+  }
+  quant_select<SRC>(q, k, SRC == 2 ? q.scale[b] : 1.f, b, len * (q.ld >> 2), n, thr);
+}
+template <int SRC>
+__global__ __launch_bounds__(1024) void abs_quantile_kernel(QuantArgs q, float* __restrict__ thr) {
+  SolverCoef k{};
+  if constexpr (SRC != 0) k = solver_coef(q.coef + (size_t)(*q.step_ptr) * q.ncoef);
+  quant_item<SRC>(q, k, blockIdx.x, thr);
+}
 // The same under per-item schedules (ns2vc_sampler_load_items; SRC 1 | 2: m is always formed there): item b's m comes from the row of its OWN
-// table at this loop step (common.h solver_item_row), and the workgroup of a held item returns at once and leaves thr[b] alone.  A kernel of its
-// own -- abs_quantile_kernel keeps its instructions (tools/kernel_code_diff.py) -- and otherwise its copy: keep the two in step.
+// table at this loop step (common.h solver_item_row), and the workgroup of a held item returns at once and leaves thr[b] alone.
 template <int SRC>
 __global__ __launch_bounds__(1024) void abs_quantile_items_kernel(QuantArgs q, float* __restrict__ thr, const SolverItem* __restrict__ items) {
   static_assert(SRC == 1 || SRC == 2, "ready values have no table row");
-  constexpr int NT = 1024, NBIN = 2048;
-  __shared__ unsigned s_hist[NBIN];
-  __shared__ unsigned s_wave[16];
-  __shared__ unsigned s_sel[4];                // chosen bin, keys below it, its count, minimum above
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
-  const int len = q.lens ? min(max(q.lens[b], 0), q.T) : q.T;
-  const int ldq = q.ld >> 2, nquad = len * ldq;
-  const unsigned n = (unsigned)len * (unsigned)q.nc;
-  SolverCoef k{};
-  float sc = 1.f;
-  {                                            // (block-uniform) a held item: nothing at all, thr[b] keeps its value
-    bool active;
-    const int row = solver_item_row(items[b], *q.step_ptr, active);
-    if (!active) return;
-    k = solver_coef(q.coef + (size_t)row * q.ncoef);
-  }
-  if (n == 0) {                                // (block-uniform)
-    if (tid == 0) thr[b] = 0.f;
-    return;
-  }
-  if constexpr (SRC == 2) sc = q.scale[b];
-  const size_t base = (size_t)b * q.T * q.ld;
-  const float pos = q.p * (float)(n - 1);
-  const unsigned lo = min((unsigned)floorf(pos), n - 1), hi = min((unsigned)ceilf(pos), n - 1);
-  const float w = pos - (float)lo;
-  unsigned prefix = 0, pmask = 0, rank = lo, eq = 0;
-#pragma unroll 1
-  for (int pass = 0; pass < 3; ++pass) {
-    const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0);
-    const unsigned dmask = pass == 0 ? 0x7FFu : 0x3FFu;
-    for (int i = tid; i < NBIN; i += NT) s_hist[i] = 0;      // (the last reads of the pass before lie in front of its second barrier)
-    if (pass == 0 && tid < 4) s_sel[tid] = tid == 3 ? 0xFFFFFFFFu : 0u;
-    __syncthreads();
-    for (int quad = tid; quad < nquad; quad += NT) {
-      unsigned key[4]; int nk;
-      quant_keys<SRC>(q, k, sc, base, quad, ldq, key, nk);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (j < nk && (key[j] & pmask) == prefix) atomicAdd(&s_hist[(key[j] >> shift) & dmask], 1u);
-    }
-    __syncthreads();
-    // block scan of the bins (two per thread, in bin order); the thread whose bins hold rank `rank` records the choice
-    const unsigned h0 = s_hist[2 * tid], h1 = s_hist[2 * tid + 1];
-    unsigned incl = h0 + h1;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(incl, o); if (lane >= o) incl += u; }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned before = 0;
-    for (int v = 0; v < wave; ++v) before += s_wave[v];
-    const unsigned excl = before + incl - (h0 + h1);
-    if (rank >= excl && rank < excl + h0) { s_sel[0] = 2 * tid; s_sel[1] = excl; s_sel[2] = h0; }
-    else if (rank >= excl + h0 && rank < excl + h0 + h1) { s_sel[0] = 2 * tid + 1; s_sel[1] = excl + h0; s_sel[2] = h1; }
-    __syncthreads();
-    const unsigned d = s_sel[0];
-    prefix |= d << shift;
-    pmask |= dmask << shift;
-    rank -= s_sel[1];
-    eq = s_sel[2];
-  }
-  // v_lo = prefix; `eq` keys hold that value and `rank` of them lie below rank lo
-  unsigned vhi = prefix;
-  if (hi != lo && rank + 2 > eq) {             // (block-uniform) the key of rank lo + 1 is the smallest one above v_lo
-    const unsigned d = prefix & 0x3FFu;
-    const unsigned c0 = 2 * tid, c1 = 2 * tid + 1;
-    unsigned cand = 0xFFFFFFFFu;
-    if (c1 < 1024u && c1 > d && s_hist[c1]) cand = c1;
-    if (c0 < 1024u && c0 > d && s_hist[c0]) cand = c0;
-    if (cand != 0xFFFFFFFFu) atomicMin(&s_sel[3], (prefix & ~0x3FFu) | cand);
-    __syncthreads();
-    const unsigned next_bin = s_sel[3];
-    __syncthreads();                           // (every thread has read it before anyone lowers it again)
-    if (next_bin == 0xFFFFFFFFu) {             // (block-uniform) no occupied bin above: sweep for the minimum of the keys above v_lo
-      unsigned mn = 0xFFFFFFFFu;
-      for (int quad = tid; quad < nquad; quad += NT) {
-        unsigned key[4]; int nk;
-        quant_keys<SRC>(q, k, sc, base, quad, ldq, key, nk);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (j < nk && key[j] > prefix) mn = min(mn, key[j]);
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) mn = min(mn, (unsigned)__shfl_xor(mn, o));
-      if (lane == 0 && mn != 0xFFFFFFFFu) atomicMin(&s_sel[3], mn);
-      __syncthreads();
-    }
-    vhi = s_sel[3] == 0xFFFFFFFFu ? prefix : s_sel[3];
-  }
-  if (tid == 0) {
-    const float a = __uint_as_float(prefix), e = __uint_as_float(vhi), dlt = e - a;
-    thr[b] = w < 0.5f ? fmaf(w, dlt, a) : fmaf(-dlt, 1.0f - w, e);     // torch's lerp
-  }
+  bool active;
+  const int row = solver_item_row(items[blockIdx.x], *q.step_ptr, active);
+  if (!active) return;                         // (block-uniform) a held item: nothing at all, thr[b] keeps its value
+  quant_item<SRC>(q, solver_coef(q.coef + (size_t)row * q.ncoef), blockIdx.x, thr);
 }
 // the normals of ns2vc_k_noise: one thread per (row, channel quad), the same philox_gauss4 the update adds
 __global__ __launch_bounds__(256) void noise_kernel(const unsigned long long* __restrict__ seeds, int B, int nc, int T, int ld, int step,
@@ -1238,6 +1063,13 @@ hipError_t launch_prompt_bias(const uint8_t* mask, const int* plens, int B, int 
   hipLaunchKernelGGL(prompt_bias_kernel, dim3((B * Lp + 255) / 256), dim3(256), 0, s, mask, plens, B, Lp, bias);
   return hipGetLastError();
 }
+// run-time flags -> template arguments of a launch: f gets std::true_type / std::false_type, or std::integral_constant<int, v> for v in LO .. HI
+// (the caller has checked the range), and names the kernel once with decltype(flag)::value; its hipError_t comes back
+template <typename F> static hipError_t with_flag(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <int LO, int HI, typename F> static hipError_t with_int(int v, F&& f) {
+  if constexpr (LO < HI) { if (v != LO) return with_int<LO + 1, HI>(v, f); }
+  return f(std::integral_constant<int, LO>{});
+}
 hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0, float* xe, void* xe_op, int prec,
                                 float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise, float* mprev2,
                                 const SolverGuide& guide, const SolverCorrect& cx) {
@@ -1254,31 +1086,18 @@ hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoe
     return hipErrorInvalidValue;
   const size_t n4 = n >> 2;
   const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  if (cx.mode) {
-#define NS2VC_SOLVER_TH_LAUNCH(H2, GD, TH)                                                                                                             \
-  NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_th_kernel<TMX, H2, GD, TH>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op, \
-                                         xbar, d1, mprev, n4, split, mprev2, guide, cx))
-#define NS2VC_SOLVER_TH_FORM(TH)                                                                                       \
-  if (guide.scale) {                                                                                                   \
-    if (mprev2) { NS2VC_SOLVER_TH_LAUNCH(true, true, TH); } else { NS2VC_SOLVER_TH_LAUNCH(false, true, TH); }         \
-  } else {                                                                                                             \
-    if (mprev2) { NS2VC_SOLVER_TH_LAUNCH(true, false, TH); } else { NS2VC_SOLVER_TH_LAUNCH(false, false, TH); }       \
-  }
-    if (cx.mode == 1) { NS2VC_SOLVER_TH_FORM(1) } else { NS2VC_SOLVER_TH_FORM(2) }
-#undef NS2VC_SOLVER_TH_FORM
-#undef NS2VC_SOLVER_TH_LAUNCH
+  return with_flag(mprev2 != nullptr, [&](auto h2) { return with_flag(guide.scale != nullptr, [&](auto gd) {
+    constexpr bool H2 = decltype(h2)::value, GD = decltype(gd)::value;
+    if (cx.mode)
+      return with_int<1, 2>(cx.mode, [&](auto th) {
+        NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_th_kernel<TMX, H2, GD, decltype(th)::value>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef,
+                                               x0, xe, (TMX*)xe_op, xbar, d1, mprev, n4, split, mprev2, guide, cx));
+        return hipGetLastError();
+      });
+    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_kernel<TMX, H2, GD>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op,
+                                           xbar, d1, mprev, n4, split, noise, mprev2, guide));
     return hipGetLastError();
-  }
-#define NS2VC_SOLVER_LAUNCH(H2, GD)                                                                                                                \
-  NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_kernel<TMX, H2, GD>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op, \
-                                         xbar, d1, mprev, n4, split, noise, mprev2, guide))
-  if (guide.scale) {
-    if (mprev2) { NS2VC_SOLVER_LAUNCH(true, true); } else { NS2VC_SOLVER_LAUNCH(false, true); }
-  } else {
-    if (mprev2) { NS2VC_SOLVER_LAUNCH(true, false); } else { NS2VC_SOLVER_LAUNCH(false, false); }
-  }
-#undef NS2VC_SOLVER_LAUNCH
-  return hipGetLastError();
+  }); });
 }
 hipError_t launch_abs_quantile(const QuantArgs& q, int n_items, float* thr, hipStream_t s) {
   if (!q.v || !thr || n_items <= 0 || q.T <= 0 || q.ld <= 0 || (q.ld & 3) || q.nc <= 0 || q.nc > q.ld || !(q.p >= 0.f && q.p <= 1.f) ||
@@ -1287,10 +1106,10 @@ hipError_t launch_abs_quantile(const QuantArgs& q, int n_items, float* thr, hipS
   const bool formed = q.xe != nullptr;
   if (formed && (!q.coef || !q.step_ptr || q.ncoef < 9 || ((uintptr_t)q.xe & 15))) return hipErrorInvalidValue;
   if (q.scale && (!formed || q.half == 0 || (q.half & 3))) return hipErrorInvalidValue;
-  if (q.scale) hipLaunchKernelGGL(abs_quantile_kernel<2>, dim3(n_items), dim3(1024), 0, s, q, thr);
-  else if (formed) hipLaunchKernelGGL(abs_quantile_kernel<1>, dim3(n_items), dim3(1024), 0, s, q, thr);
-  else hipLaunchKernelGGL(abs_quantile_kernel<0>, dim3(n_items), dim3(1024), 0, s, q, thr);
-  return hipGetLastError();
+  return with_int<0, 2>(q.scale ? 2 : (formed ? 1 : 0), [&](auto src) {
+    hipLaunchKernelGGL(abs_quantile_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr);
+    return hipGetLastError();
+  });
 }
 // the launches of a step under per-item schedules: whole items of si.T rows of si.ld columns, n = the elements of the n_items loop items (guided:
 // of one half), records for every one of them -- refused rather than run on the shared row
@@ -1305,24 +1124,20 @@ hipError_t launch_solver_update_items(const float* coef, const int* step_ptr, in
     return hipErrorInvalidValue;
   const size_t n4 = n >> 2;
   const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-#define NS2VC_SOLVER_ITEMS_LAUNCH(GD, TH)                                                                                                        \
-  NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_items_kernel<TMX, GD, TH>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, si, x0, xe, \
-                                         (TMX*)xe_op, xbar, d1, mprev, n4, split, noise, mprev2, guide, cx))
-  if (guide.scale) {
-    if (cx.mode == 1) { NS2VC_SOLVER_ITEMS_LAUNCH(true, 1); } else if (cx.mode == 2) { NS2VC_SOLVER_ITEMS_LAUNCH(true, 2); } else { NS2VC_SOLVER_ITEMS_LAUNCH(true, 0); }
-  } else {
-    if (cx.mode == 1) { NS2VC_SOLVER_ITEMS_LAUNCH(false, 1); } else if (cx.mode == 2) { NS2VC_SOLVER_ITEMS_LAUNCH(false, 2); } else { NS2VC_SOLVER_ITEMS_LAUNCH(false, 0); }
-  }
-#undef NS2VC_SOLVER_ITEMS_LAUNCH
-  return hipGetLastError();
+  return with_flag(guide.scale != nullptr, [&](auto gd) { return with_int<0, 2>(cx.mode, [&](auto th) {
+    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_items_kernel<TMX, decltype(gd)::value, decltype(th)::value>), dim3(blocks), dim3(256), 0, s, coef,
+                                           step_ptr, ncoef, si, x0, xe, (TMX*)xe_op, xbar, d1, mprev, n4, split, noise, mprev2, guide, cx));
+    return hipGetLastError();
+  }); });
 }
 hipError_t launch_abs_quantile_items(const QuantArgs& q, const SolverItem* items, int n_items, float* thr, hipStream_t s) {
   if (!items || !q.v || !q.xe || !q.coef || !q.step_ptr || q.ncoef < 9 || !thr || n_items <= 0 || q.T <= 0 || q.ld <= 0 || (q.ld & 3) || q.nc <= 0 || q.nc > q.ld ||
       !(q.p >= 0.f && q.p <= 1.f) || (((uintptr_t)q.v | (uintptr_t)q.xe) & 15) || (size_t)q.T * (size_t)q.ld > 0x7FFFFFFFull || (q.scale && (q.half == 0 || (q.half & 3))))
     return hipErrorInvalidValue;
-  if (q.scale) hipLaunchKernelGGL(abs_quantile_items_kernel<2>, dim3(n_items), dim3(1024), 0, s, q, thr, items);
-  else hipLaunchKernelGGL(abs_quantile_items_kernel<1>, dim3(n_items), dim3(1024), 0, s, q, thr, items);
-  return hipGetLastError();
+  return with_int<1, 2>(q.scale ? 2 : 1, [&](auto src) {
+    hipLaunchKernelGGL(abs_quantile_items_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr, items);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_emb_items_from_table(const float* table, const int* step_ptr, const SolverItem* items, int n_items, const float* aug, float* emb,
                                        void* emb_act_op, int prec, int B, int edim, hipStream_t s) {

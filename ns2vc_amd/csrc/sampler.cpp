@@ -47,11 +47,9 @@ int ns2vc_sampler_load(ns2vc_unet* h, int steps, const float* coef_host) {
   h->steps = steps;
   h->temb_table_valid = false;
   h->next_step = -1;
-  bool stochastic = false;
-  for (int i = 0; i < steps; ++i) stochastic |= coef_host[(size_t)i * NS2VC_NCOEF + 9] != 0.f;
-  bool hist2 = false;
-  for (int i = 0; i < steps; ++i) hist2 |= coef_host[(size_t)i * NS2VC_NCOEF + 10] != 0.f || coef_host[(size_t)i * NS2VC_NCOEF + 11] != 0.f;
-  if (stochastic && hist2) { h->steps = 0; return fail("a solver table with both a noise column and history 2 (columns 10-11) is not supported"); }
+  const int form = solver_table_form(coef_host, steps);
+  const bool stochastic = (form & SOLVER_ITEM_NOISE) != 0, hist2 = (form & SOLVER_ITEM_HIST2) != 0;
+  if (form == SOLVER_ITEM_BOTH) { h->steps = 0; return fail("a solver table with both a noise column and history 2 (columns 10-11) is not supported"); }
   // (the update's noise arguments and its history-2 form are baked into the captured step graph)
   if (stochastic != h->stochastic || hist2 != h->hist2.on || h->items.on) drop_step_graph(h);      // (... and so is the per-item form, which a shared table switches off)
   h->stochastic = stochastic;
@@ -79,12 +77,8 @@ int ns2vc_sampler_load_items(ns2vc_unet* h, int n_tables, const int32_t* table_r
     row0[k] = (int)rows;
     rows += table_rows[k];
     if (rows > kMaxRows) return fail("the distinct solver tables of the batch hold more than %d rows together (the table's fixed capacity)", kMaxRows);
-    for (int i = 0; i < table_rows[k]; ++i) {
-      const float* r = coef_host + (size_t)(row0[k] + i) * NS2VC_NCOEF;
-      if (r[9] != 0.f) flags[k] |= SOLVER_ITEM_NOISE;
-      if (r[10] != 0.f || r[11] != 0.f) flags[k] |= SOLVER_ITEM_HIST2;
-    }
-    if (flags[k] == (SOLVER_ITEM_NOISE | SOLVER_ITEM_HIST2))
+    flags[k] = solver_table_form(coef_host + (size_t)row0[k] * NS2VC_NCOEF, table_rows[k]);
+    if (flags[k] == SOLVER_ITEM_BOTH)
       return fail("table %d has both a noise column and history 2 (columns 10-11): not supported", k);
   }
   std::vector<SolverItem> rec(n_items);
@@ -277,34 +271,26 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
   if (h->stochastic) {       // noise on the item's valid frames and real channels only (masked plan: level-0 lengths = the first B entries)
     nz.seeds = h->seeds.dev; nz.lens = h->lens.masked ? h->lens.dev : nullptr; nz.T = h->T; nz.ld = h->CP; nz.nc = h->cfg.latent_channels;
   }
+  if (h->items.on && h->items.n != h->loop_items())
+    return fail("per-item schedules for %d items, the loop has %d (load them again)", h->items.n, h->loop_items());
   SolverCorrect cx;
-  if (h->items.on) {         // per-item schedules: every item its own row, held items left alone (misc.hip solver_update_items_kernel)
-    if (h->items.n != h->loop_items()) return fail("per-item schedules for %d items, the loop has %d (load them again)", h->items.n, h->loop_items());
-    if (h->x0c.mode) {
-      cx.mode = h->x0c.mode; cx.max_val = h->x0c.max_val; cx.T = h->T; cx.ld = h->CP;
-      if (h->x0c.mode == 1) {
-        QuantArgs q;
-        q.v = h->x0; q.xe = h->xe; q.coef = h->coef_dev; q.step_ptr = h->step_dev; q.ncoef = NS2VC_NCOEF; q.scale = gd.scale; q.half = gd.scale ? n : 0;
-        q.lens = h->lens.masked ? h->lens.dev : nullptr; q.T = h->T; q.ld = h->CP; q.nc = h->cfg.latent_channels; q.p = h->x0c.ratio;
-        HIPCHK(launch_abs_quantile_items(q, h->items.dev, h->items.n, h->x0c.thr, s));
-        cx.thr = h->x0c.thr;
-      }
-    }
-    SolverItems si;
-    si.rec = h->items.dev; si.T = h->T; si.ld = h->CP;
-    HIPCHK(launch_solver_update_items(h->coef_dev, h->step_dev, NS2VC_NCOEF, si, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s,
-                                      h->pair_off(), nz, h->hist2.on ? h->hist2.mprev2 : nullptr, gd, cx));
-    return 0;
-  }
   if (h->x0c.mode) {         // (not with a stochastic table: ns2vc_sampler_begin refuses the pair)
     cx.mode = h->x0c.mode; cx.max_val = h->x0c.max_val; cx.T = h->T; cx.ld = h->CP;
     if (h->x0c.mode == 1) {  // the item's |m| quantile over its valid frames and real channels, from the update's own operands
       QuantArgs q;
       q.v = h->x0; q.xe = h->xe; q.coef = h->coef_dev; q.step_ptr = h->step_dev; q.ncoef = NS2VC_NCOEF; q.scale = gd.scale; q.half = gd.scale ? n : 0;
       q.lens = h->lens.masked ? h->lens.dev : nullptr; q.T = h->T; q.ld = h->CP; q.nc = h->cfg.latent_channels; q.p = h->x0c.ratio;
-      HIPCHK(launch_abs_quantile(q, h->loop_items(), h->x0c.thr, s));
+      if (h->items.on) HIPCHK(launch_abs_quantile_items(q, h->items.dev, h->items.n, h->x0c.thr, s));
+      else HIPCHK(launch_abs_quantile(q, h->loop_items(), h->x0c.thr, s));
       cx.thr = h->x0c.thr;
     }
+  }
+  if (h->items.on) {         // per-item schedules: every item its own row, held items left alone (misc.hip solver_update_items_kernel)
+    SolverItems si;
+    si.rec = h->items.dev; si.T = h->T; si.ld = h->CP;
+    HIPCHK(launch_solver_update_items(h->coef_dev, h->step_dev, NS2VC_NCOEF, si, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s,
+                                      h->pair_off(), nz, h->hist2.on ? h->hist2.mprev2 : nullptr, gd, cx));
+    return 0;
   }
   HIPCHK(launch_solver_update(h->coef_dev, h->step_dev, NS2VC_NCOEF, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s, h->pair_off(), nz,
                               h->hist2.on ? h->hist2.mprev2 : nullptr, gd, cx));
@@ -651,15 +637,11 @@ int ns2vc_sampler_admit(ns2vc_unet* h, int n, const int32_t* slots, const float*
     if (r[2] < h->next_step) return fail("slot %d: start %d lies in the past, the loop stands at step %d", b, r[2], h->next_step);
     if (r[2] > SOLVER_ITEM_NEVER - 1 - r[1])
       return fail("slot %d: loop steps %d + %d pass the end of the 32-bit step counter: drain the slots and call ns2vc_sampler_rebase", b, r[2], r[1]);
-    int flags = 0;
-    for (int i = 0; i < r[1]; ++i) {
-      const float* row = sl.coef.data() + (size_t)(r[0] + i) * NS2VC_NCOEF;
-      if (row[9] != 0.f) flags |= SOLVER_ITEM_NOISE;
-      if (row[10] != 0.f || row[11] != 0.f) flags |= SOLVER_ITEM_HIST2;
-      if (row[1] == 0.f) return fail("slot %d: row %d of the table was never written (ns2vc_sampler_write_rows)", b, r[0] + i);
-    }
+    for (int i = 0; i < r[1]; ++i)
+      if (sl.coef[(size_t)(r[0] + i) * NS2VC_NCOEF + 1] == 0.f) return fail("slot %d: row %d of the table was never written (ns2vc_sampler_write_rows)", b, r[0] + i);
+    const int flags = solver_table_form(sl.coef.data() + (size_t)r[0] * NS2VC_NCOEF, r[1]);
     if (flags != r[3]) return fail("slot %d: flags %d, its rows %d .. %d have the form %d (1 = history 2, 2 = noise)", b, r[3], r[0], r[0] + r[1] - 1, flags);
-    if (flags == (SOLVER_ITEM_NOISE | SOLVER_ITEM_HIST2)) return fail("slot %d: a table with both a noise column and history 2 is not supported", b);
+    if (flags == SOLVER_ITEM_BOTH) return fail("slot %d: a table with both a noise column and history 2 is not supported", b);
     if ((flags & SOLVER_ITEM_HIST2) && !h->hist2.on) return fail("slot %d runs history 2: the slot loop was opened without it (ns2vc_sampler_open history2 = 1)", b);
     if ((flags & SOLVER_ITEM_NOISE) && !h->stochastic) return fail("slot %d is stochastic: the slot loop was opened without noise (ns2vc_sampler_open noise = 1)", b);
     if (h->guide.on && h->lens.masked && h->lens.applied[b] != h->lens.applied[b + ni]) return fail("guided slot loop: lengths[%d] and lengths[%d] differ", b, b + ni);
