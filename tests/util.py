@@ -69,6 +69,35 @@ def tol_attention(prec):    # 16-bit: scaled Q, P and the output are rounded to 
     return 2e-5 if prec == 0 else 8 * eps16(prec)
 
 
+# ---- the position patterns of tests/attn_patterns.py (tests/test_attn_positions_*.py).  Derived, not tuned.
+def tol_attn_count(prec, n):
+    """COUNT: |out * n - 1| of a valid seam key among n equally weighted keys.  Every probability is the same power of two and V is 0 / 1, so the
+    numerator is exact and the denominator is n times that power: what is left is one reciprocal, one product and one rounding to the operand type
+    (2 eps16 covers the three for the 16-bit types; for fp32 eps16 is 2^-25), plus n * 2^-23 for an fp32 accumulation of n equal addends should
+    v_exp_f32 not return an exact power of two.  A key counted twice reads 2n / (n + 1), a dropped one 0; excluded positions must be exactly 0."""
+    return 2 * eps16(prec) + n * 2.0 ** -23
+
+
+def tol_attn_route(prec, pv_fp8=False, n=0):
+    """ROUTE: |out - ref64| per element (values in [0, 1]) against the fp64 attention of the same rounded operands, n keys.  16-bit: P, the
+    denominator's P and the result are rounded to the operand type, and the rounded scaled Q moves the weight of the non-matching keys (a few 1e-3 of
+    the row at the smallest gap) by a fraction of itself: 4 eps16.  fp8 PV form: one e4m3 rounding of P (2^-4 relative), mass at most 1.
+    fp32 (eps16 = 2^-25, so 4 eps16 is one ulp of 1): the rounding that bound leaves out is the fp32 ACCUMULATION of numerator and denominator.  Once
+    the match (p = 1 after the reference moved, or p = 2^gap on an unmoved reference when the gap is under THRESH) is in the accumulator, every later
+    addend -- 2^-gap or 1 for a seam key, 2^-6 of that for a background key -- is rounded to the accumulator's ulp as it is added: up to 2^-24 relative
+    per addition, n additions each for numerator and denominator, n 2^-23 in all -- the term tol_attn_count carries for the same reason.  The
+    background addends are all equal, so they round the same way and the drift grows with n, not sqrt(n).  Measured: 5.4e-7 at n = 65 (gap 11.5) and
+    9.5e-6 at n = 469 (gap 12.5), where 4 eps16 is 1.2e-7 and the bound with the term 7.9e-6 and 5.6e-5.  The 16-bit forms accumulate in fp32 too;
+    there the term (5.6e-5 at n = 469) is a few percent of 4 eps16 and is NOT added: they are held to 4 eps16 alone."""
+    if pv_fp8:
+        return 2.0 ** -4
+    return 4 * eps16(prec) + (n * 2.0 ** -23 if prec == 0 else 0.0)
+
+
+TOL_FFN_XATTN_ROW = {1: 5e-3, 2: 6e-4}      # fused feed-forward with the in-kernel cross-attention vs the two-launch path: the bound of
+#                                             test_ffn_fused_with_cross_attention, applied per row (max |fused - two-launch| over the row's RMS)
+
+
 def tol_ln_linear(prec):    # LayerNorm-by-linearity consumer (16-bit: the raw operand copy is rounded BEFORE normalisation)
     return 2e-5 if prec == 0 else 8 * eps16(prec)
 
