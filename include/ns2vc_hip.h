@@ -123,6 +123,9 @@ int ns2vc_unet_num_missing_weights(ns2vc_unet* h, char* first_missing, int bufle
  *                    transformer block (ns2vc_k_ffn with pre_a) and gives it the level's length table (ns2vc_ffn_args.lens) instead of the
  *                    attn2.to_out, norm3, ff.geglu, ff.out+proj_out launches and their mask_rows sweeps; independent of masked_fuse, masked_attn
  *                    and masked_rows; dense plans and the fp32 engine ignore it
+ *   "attn_resident" 1|0 (default 1) dense fp16 / bf16 attention at head dim 16 / 32 on the K/V-resident kernel (one workgroup per (item, head), the head's
+ *                    K/V staged once) where the key rows fit the LDS (<= 1024 / 640 keys) and B * heads >= the device's CUs; 0 = the tiled kernel everywhere.
+ *                    Bit-identical results either way.
  *   "masked_geglu" 1|0 (default 0) a plan built under per-item lengths keeps the token-stationary GEGLU launch of a dim-384 transformer block
  *                    (ns2vc_k_geglu) on a level of at least the dense crossover's rows and gives it the level's length table
  *                    (ns2vc_geglu_args.T, lens) with ln_stats = NULL -- the kernel takes the LayerNorm sums from the operand rows it holds --
@@ -578,6 +581,9 @@ int ns2vc_k_rowchain(const ns2vc_rowchain_args* a, int precision, void* stream);
 int ns2vc_debug_set_geglu_min_rows(int rows); /* tests / tuning: row count from which the planner picks ns2vc_k_geglu over the GEMM (default 4608; < 0 restores it); takes effect at the next plan build */
 int ns2vc_debug_set_attn_keys(int keys); /* tests / tuning: 128 selects the 128-key K/V tile kernels (16-bit precisions, hd 16 / 32); 0 or 64 = the default 64-key tiles */
 int ns2vc_debug_set_attn_optimistic(int on); /* tests: 0 = every attention workgroup takes the exact (per-tile maximum) pass only; 1 = default */
+int ns2vc_debug_set_attn_resident(int mode); /* tests / tuning: the K/V-resident attention kernel (dense fp16 / bf16, hd 16 / 32, <= 1024 / 640 keys): -1 = the rule (B * H >= the device's CUs; default), 0 = never, 1 = whenever the launch fits */
+unsigned long long ns2vc_debug_attn_resident_launches(void); /* tests: attention launches issued (or captured into a graph) on the resident kernel so far in this process */
+int ns2vc_debug_attnres_table(int* rows); /* rows of the resident attention kernel's table (not a family of ns2vc_debug_kernel_table); no HIP call */
 int ns2vc_debug_set_rowchain_tokens(int nt); /* tests: force 64-token (1) / 128-token (2, dim 128 only) workgroups; 0 = heuristic */
 
 /* operand-typed conversions for tests: fp32 host [n] -> device operand buffer and back */

@@ -13,6 +13,7 @@ hipError_t ns2vc::init_all_attributes() {
   hipError_t e = init_gemm_attributes();
   if (e == hipSuccess) e = init_convts_attributes();
   if (e == hipSuccess) e = init_attn_attributes();
+  if (e == hipSuccess) e = init_attnres_attributes();
   if (e == hipSuccess) e = init_ffn_attributes();
   if (e == hipSuccess) e = init_geglu_attributes();
   if (e == hipSuccess) e = init_rowchain_attributes();
@@ -239,6 +240,17 @@ int ns2vc_pack_rowchain_sliced(const float* w1_host, const float* w2_host, int d
 int ns2vc_debug_set_attn_keys(int keys) {
   if (keys != 0 && keys != 64 && keys != 128) return fail("attention K/V tile: 0 (heuristic), 64 or 128 keys");
   set_forced_attn_keys(keys);
+  return 0;
+}
+int ns2vc_debug_set_attn_resident(int mode) {
+  if (mode < -1 || mode > 1) return fail("resident attention: -1 (the rule), 0 (never) or 1 (whenever the launch fits)");
+  set_attn_resident_mode(mode);
+  return 0;
+}
+unsigned long long ns2vc_debug_attn_resident_launches(void) { return attn_resident_launches(); }
+int ns2vc_debug_attnres_table(int* rows) {
+  if (!rows) return fail("attnres table: rows not NULL");
+  *rows = attnres_kernel_table().n;
   return 0;
 }
 int ns2vc_debug_set_rowchain_tokens(int nt) {

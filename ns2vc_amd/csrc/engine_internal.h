@@ -231,6 +231,7 @@ struct ns2vc_unet {
   bool slice_rows = true;      // first row chain of a dim-384 block as two N-slices per token block (r4; see Planner::transformer)
   unsigned* ln_health = nullptr;
   bool attn_optimistic = true;   // attention without the per-tile maximum + exact fallback (attn.hip OPT); 0 = exact pass only, on every device
+  bool attn_resident = true;     // dense 16-bit attention at hd 16 / 32 on the K/V-resident kernel where launch_attention's rule selects it (attn_resident.hip); 0 = attn_kernel everywhere
   unsigned* attn_fallbacks = nullptr;     // device counter: workgroups that needed the fallback (ns2vc_unet_attn_fallbacks)
   unsigned long long coef_hash = 0;       // FNV-1a of the loaded solver table (handoff compares)
   std::vector<ns2vc::Tap> taps;

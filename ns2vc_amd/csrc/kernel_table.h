@@ -59,5 +59,7 @@ const KernelTable& attn_kernel_table();
 const KernelTable& ffn_kernel_table();
 const KernelTable& geglu_kernel_table();
 const KernelTable& rowchain_kernel_table();
+// (not a family of ns2vc_debug_kernel_table: ns2vc_debug_attnres_table)
+const KernelTable& attnres_kernel_table();
 
 }  // namespace ns2vc

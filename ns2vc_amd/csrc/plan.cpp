@@ -304,7 +304,8 @@ struct Planner {
       a.k_lens = cross_lens;
       if (!h->has_mask) a.bias = nullptr;
     }
-    add(name, [=](hipStream_t s) { return launch_attention(a, hd, pr, s); }, 2, 4.0 * B * a.H * (double)Lq * Lk * hd,
+    const bool resident = h->attn_resident;
+    add(name, [=](hipStream_t s) { return launch_attention(a, hd, pr, s, resident); }, 2, 4.0 * B * a.H * (double)Lq * Lk * hd,
         (double)opsz * B * a.H * hd * (2.0 * Lq + 2.0 * Lk));
     if (!self_mask) mask(name, out, ldo, a.H * hd, opsz, Lq);
   }

@@ -18,7 +18,7 @@ import sys
 import tempfile
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I../../include"]
-EXTRA = {"attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+EXTRA = {"attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "attn_resident.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _readelf():

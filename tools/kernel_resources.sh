@@ -6,8 +6,8 @@ cd "$(dirname "$0")/../ns2vc_amd/csrc"
 OUT=${1:-../../profiles/r06_kernel_resources.txt}
 {
 echo "# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage, every kernel of libns2vc_hip.so: VGPRs | AGPRs | scratch B/lane | waves/SIMD | spilled VGPRs"
-for f in gemm convts ffn geglu rowchain attn misc; do
-  flags=""; [ $f = attn ] && flags="-mllvm -amdgpu-mfma-vgpr-form"
+for f in gemm convts ffn geglu rowchain attn attn_resident misc; do
+  flags=""; case $f in attn*) flags="-mllvm -amdgpu-mfma-vgpr-form";; esac
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../include $flags -Rpass-analysis=kernel-resource-usage -c $f.hip -o /tmp/kres_$$.o 2>&1 |
     grep -E "Function Name|    VGPRs:|AGPRs:|ScratchSize|Occupancy|VGPRs Spill" | sed 's/.*remark: *//; s/ *\[-Rpass.*//; s/Function Name: //; s/.*: //' | paste - - - - - - |
     while IFS=$'\t' read -r name v a sc occ sp; do printf "%-8s %4s %4s %5s %2s %3s  %s\n" $f "$v" "$a" "$sc" "$occ" "$sp" "$(echo "$name" | c++filt | cut -c1-150)"; done
