@@ -261,6 +261,23 @@ int ns2vc_sampler_set_guidance(ns2vc_unet* h, const float* scale_host, int n, vo
  * update never runs in conv_out's epilogue under a correction (fuse_solver is ignored), ns2vc_unet_prepare leaves the setting alone, and
  * ns2vc_sampler_handoff carries that of `src` over to `dst`. */
 int ns2vc_sampler_set_x0_correction(ns2vc_unet* h, int mode, float ratio, float max_val);
+/* The correction as a per-item table (backward-compatible addition to ABI v7): loop item b is corrected by its own record
+ * (mode_host[b], ratio_host[b], max_val_host[b]) -- HOST arrays [n], n = the loop items (n, not 2n, under guidance), every record under the rules
+ * above (mode 0 .. 2, 0 <= ratio <= 1, max_val finite and > 0, also where the mode does not read them).  The records live in device memory and
+ * are copied on `stream` from pinned staging as the seeds and the scales are: new values replay the captured step graph.  All three pointers
+ * NULL = off.  What recaptures: switching the table on or off, a larger record buffer, and -- outside slot mode -- the first record in mode 1 or
+ * the last one gone (the quantile launch is issued only when a record needs it; a slot loop always issues it).  Item b ends on the bits it has
+ * when the same loop runs with ns2vc_sampler_set_x0_correction(mode_b, ratio_b, max_val_b); a held or idle item is not touched and its
+ * threshold is not written.
+ * The table and the loop-wide setting exclude each other: this call is refused while ns2vc_sampler_set_x0_correction has a mode != 0, and
+ * ns2vc_sampler_set_x0_correction(mode != 0) is refused while the table is on.  The table reads per-item records: ns2vc_sampler_begin on a
+ * shared table (ns2vc_sampler_load) is refused with the table on -- use ns2vc_sampler_load_items or a slot loop.  A stochastic item (ddim with
+ * eta > 0, ddpm) has no correction: a record with mode != 0 on an item whose table has a noise column is refused by
+ * ns2vc_sampler_load_items, ns2vc_sampler_begin and ns2vc_sampler_admit (and by this call for the busy slots of a slot loop), per item -- corrected and stochastic items may share a loop.
+ * Slot mode: ns2vc_sampler_open bakes in whether the table is on (set it, all modes 0, before opening) and allocates the thresholds; in
+ * mid-loop the call is a whole-vector copy under the rule for seeds and scales: change the entries of idle slots only.
+ * fuse_solver is ignored under the table, ns2vc_unet_prepare leaves it alone, ns2vc_sampler_handoff carries it over to `dst`. */
+int ns2vc_sampler_set_x0_correction_items(ns2vc_unet* h, const int32_t* mode_host, const float* ratio_host, const float* max_val_host, int n, void* stream);
 /* x_e of a loop in progress (the point the next evaluation is taken at) without ending the loop: what a precision self-check
  * evaluates two engines on (ns2vc_amd.pipeline.Denoiser) */
 int ns2vc_sampler_peek(ns2vc_unet* h, float* x_out_bct, void* stream);
@@ -667,6 +684,14 @@ int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t
                                 void* xe_op, int precision, float* xbar, float* d1, float* mprev, float* mprev2, size_t n, int ld, int T,
                                 const float* scale_dev, const uint64_t* seeds_dev, const int32_t* lens_dev, int nc, int mode, float ratio, float max_val,
                                 float* thr_dev, void* stream);
+/* The same step under a per-item x0 correction (backward-compatible addition to ABI v7; see ns2vc_sampler_set_x0_correction_items): the arguments of
+ * ns2vc_k_solver_update_items with mode, ratio, max_val replaced by HOST arrays [n_items] of each, validated as that call validates them (a
+ * stochastic item takes mode 0 only).  The two launches the loop makes: the per-item quantile when a record has mode 1 (thr_dev[b] is written for
+ * the active items in mode 1 and for no other), then the update, every active item by its own record.  thr_dev is always needed. */
+int ns2vc_k_solver_update_items_corrected(const float* coef_dev, int n_rows, const int32_t* step_dev, const int32_t* items_host, int n_items, const float* x0,
+                                          float* xe, void* xe_op, int precision, float* xbar, float* d1, float* mprev, float* mprev2, size_t n, int ld, int T,
+                                          const float* scale_dev, const uint64_t* seeds_dev, const int32_t* lens_dev, int nc, const int32_t* mode_host,
+                                          const float* ratio_host, const float* max_val_host, float* thr_dev, void* stream);
 
 /* ---- Slot loop: continuous batching (backward-compatible additions to ABI v7) --------------------------------------------------
  * A loop over a prepared (B, T, Lp) engine whose loop items (B; n under guidance) are SLOTS that are filled, run and emptied independently while
@@ -692,7 +717,8 @@ int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t
  * In slot mode ns2vc_sampler_steps is not bounded by a table length (idle steps are legal) and ns2vc_sampler_peek gives all loop items.
  * Legal in mid-loop, each a stream-ordered copy that replays the captured graph: ns2vc_unet_set_lengths and ns2vc_unet_set_prompt_lengths
  * (while they stay ON: switching either on or off rebuilds the plan and recaptures), ns2vc_sampler_set_seeds, ns2vc_sampler_set_guidance
- * (new scales; on / off ends the loop).  They take whole vectors: change the entries of idle slots only, or a running item changes course. */
+ * (new scales; on / off ends the loop), ns2vc_sampler_set_x0_correction_items (new records while the table is on: a loop opened with the table
+ * takes corrected and stochastic items side by side).  They take whole vectors: change the entries of idle slots only, or a running item changes course. */
 int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream);
 int ns2vc_sampler_rebase(ns2vc_unet* h, void* stream);
 /* rows [row0, row0 + nrows) of the 1024-row coefficient table <- coef_host [nrows][NS2VC_NCOEF] (finite), and the same rows of the

@@ -163,7 +163,8 @@ PROTOTYPES = {
     "ns2vc_sampler_set_seeds": (_I, [_P, _P, _P]),
     "ns2vc_sampler_set_guidance": (_I, [_P, _P, _I, _P]),
     "ns2vc_sampler_set_x0_correction": (_I, [_P, _I, C.c_float, C.c_float]),
-    "ns2vc_unet_attn_fallbacks": (_I, [_P, C.POINTER(C.c_ulonglong), _I, _P]),
+    "ns2vc_sampler_set_x0_correction_items": (_I, [_P, _P, _P, _P, _I, _P]),
+    "ns2vc_unet_attn_fallbacks":(_I, [_P, C.POINTER(C.c_ulonglong), _I, _P]),
     "ns2vc_unet_gn_coop_alone": (_I, [_P, C.POINTER(C.c_ulonglong), _I, _P]),
     "ns2vc_unet_graph_captures": (_I, [_P, C.POINTER(C.c_ulonglong)]),
     "ns2vc_unet_set_debug": (_I, [_P, _I]),
@@ -234,6 +235,8 @@ PROTOTYPES = {
     "ns2vc_k_solver_update_corrected": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P]),
     "ns2vc_k_solver_update_items": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _I, _P, _P, _P, _I, _I, C.c_float, C.c_float,
                                          _P, _P]),
+    "ns2vc_k_solver_update_items_corrected": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _I, _I, _P, _P, _P, _I, _P, _P, _P,
+                                                   _P, _P]),
     "ns2vc_sampler_open": (_I, [_P, _I, _I, _P]),
     "ns2vc_sampler_rebase": (_I, [_P, _P]),
     "ns2vc_sampler_write_rows": (_I, [_P, _I, _I, C.POINTER(C.c_float), _P]),

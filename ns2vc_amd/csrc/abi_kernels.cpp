@@ -476,6 +476,64 @@ int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t
   (void)hipFree(rec);
   return rc;
 }
+// the same step under a per-item x0 correction: HOST arrays [n_items] of mode, ratio and max_val in place of the three scalars; the two launches the
+// loop makes (the quantile only when a record has mode 1)
+int ns2vc_k_solver_update_items_corrected(const float* coef_dev, int n_rows, const int32_t* step_dev, const int32_t* items_host, int n_items, const float* x0,
+                                          float* xe, void* xe_op, int precision, float* xbar, float* d1, float* mprev, float* mprev2, size_t n, int ld, int T,
+                                          const float* scale_dev, const uint64_t* seeds_dev, const int32_t* lens_dev, int nc, const int32_t* mode_host,
+                                          const float* ratio_host, const float* max_val_host, float* thr_dev, void* stream) {
+  if (!coef_dev || !step_dev || !items_host || !x0 || !xe || !xe_op || !xbar || !d1 || !mprev) return fail("null argument");
+  if (!mode_host || !ratio_host || !max_val_host) return fail("items corrected update: the record table (mode, ratio, max_val) is needed");
+  if (!thr_dev) return fail("items corrected update: thr_dev is needed");
+  if (ld <= 0 || (ld & 3) || T <= 0 || n_items <= 0 || n != (size_t)n_items * T * ld)
+    return fail("n (%zu) must hold the %d items of T (%d) rows of ld (%d) columns, ld a multiple of 4", n, n_items, T, ld);
+  static_assert(sizeof(SolverItem) == 4 * sizeof(int32_t), "records are four 32-bit words");
+  std::vector<ItemCorrect> cr((size_t)n_items);
+  bool dyn = false;
+  for (int b = 0; b < n_items; ++b) {      // the records name rows of the table and buffers the launch reads: checked here, the kernels trust them
+    const int32_t* r = items_host + 4 * (size_t)b;
+    if (r[0] < 0 || r[1] <= 0 || r[2] < 0 || (long)r[0] + r[1] > n_rows) return fail("item %d: rows %d + %d outside the table of %d, or start %d < 0", b, r[0], r[1], n_rows, r[2]);
+    if ((r[3] & ~SOLVER_ITEM_BOTH) || r[3] == SOLVER_ITEM_BOTH) return fail("item %d: flags %d", b, r[3]);
+    if ((r[3] & SOLVER_ITEM_HIST2) && !mprev2) return fail("item %d runs history 2: mprev2 is needed", b);
+    if ((r[3] & SOLVER_ITEM_NOISE) && !seeds_dev) return fail("item %d is stochastic: seeds_dev is needed", b);
+    if (mode_host[b] < 0 || mode_host[b] > 2) return fail("item %d: mode %d must be 0 (off), 1 (dynamic thresholding) or 2 (clamp)", b, (int)mode_host[b]);
+    if (!(ratio_host[b] >= 0.f && ratio_host[b] <= 1.f)) return fail("item %d: ratio %g must be in [0, 1]", b, (double)ratio_host[b]);
+    if (!(std::isfinite(max_val_host[b]) && max_val_host[b] > 0.f)) return fail("item %d: max_val %g must be finite and > 0", b, (double)max_val_host[b]);
+    if ((r[3] & SOLVER_ITEM_NOISE) && mode_host[b] != 0) return fail("item %d is stochastic and has mode %d: ddim / ddpm have no correction", b, (int)mode_host[b]);
+    cr[(size_t)b] = ItemCorrect{(int)mode_host[b], ratio_host[b], max_val_host[b], 0};
+    dyn |= mode_host[b] == 1;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* dev = nullptr;      // [n_items] SolverItem, then [n_items] ItemCorrect (16 bytes each)
+  const size_t rb = (size_t)n_items * sizeof(SolverItem), cb = (size_t)n_items * sizeof(ItemCorrect);
+  HIPCHK(hipMalloc((void**)&dev, rb + cb));
+  int rc = 1;
+  if (hipMemcpy(dev, items_host, rb, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dev + rb, cr.data(), cb, hipMemcpyHostToDevice) == hipSuccess) {
+    const SolverItem* rec = reinterpret_cast<const SolverItem*>(dev);
+    const ItemCorrect* crd = reinterpret_cast<const ItemCorrect*>(dev + rb);
+    SolverItems si;
+    si.rec = rec; si.T = T; si.ld = ld;
+    SolverGuide gd;
+    if (scale_dev) { gd.scale = scale_dev; gd.T = T; gd.ld = ld; }
+    SolverNoise nz;
+    if (seeds_dev) { nz.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev); nz.lens = lens_dev; nz.T = T; nz.ld = ld; nz.nc = nc; }
+    rc = 0;
+    if (dyn) {
+      QuantArgs q;
+      q.v = x0; q.xe = xe; q.coef = coef_dev; q.step_ptr = step_dev; q.ncoef = NS2VC_NCOEF; q.scale = scale_dev; q.half = scale_dev ? n : 0;
+      q.lens = lens_dev; q.T = T; q.ld = ld; q.nc = nc;
+      rc = launched(launch_abs_quantile_mixed(q, rec, crd, n_items, thr_dev, s), "abs_quantile_mixed launch");
+    }
+    if (!rc)
+      rc = launched(launch_solver_update_mixed(coef_dev, step_dev, NS2VC_NCOEF, si, crd, thr_dev, x0, xe, xe_op, precision, xbar, d1, mprev, n, s,
+                                               precision != PREC_F32 ? ld : 0, nz, mprev2, gd), "mixed solver_update launch");
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("items corrected solver_update: stream synchronize failed");
+  } else {
+    (void)fail("items corrected solver_update: copy of the records failed");
+  }
+  (void)hipFree(dev);
+  return rc;
+}
 // a host slot list, checked (entries in [0, n_items), none twice), on the device for one hook call
 static int upload_slots(const int32_t* slots_host, int n, int n_items, int** out_dev) {
   if (!slots_host || n <= 0 || n_items <= 0 || n > n_items) return fail("a slot list needs 1 .. %d entries, got %d", n_items, n);

@@ -449,6 +449,14 @@ hipError_t launch_solver_update_items(const float* coef, const int* step_ptr, in
 hipError_t launch_abs_quantile_items(const QuantArgs& q, const SolverItem* items, int n_items, float* thr, hipStream_t s);
 hipError_t launch_emb_items_from_table(const float* table, const int* step_ptr, const SolverItem* items, int n_items, const float* aug, float* emb,
                                        void* emb_act_op, int prec, int B, int edim, hipStream_t s);
+// per-item x0 correction (ns2vc_sampler_set_x0_correction_items): cr = DEVICE [items] records beside the SolverItem records, validated by the host
+// (mode 0 = off, 1 = dynamic thresholding at the item's own ratio, 2 = clamp; max_val finite and > 0; mode 0 on a stochastic item).  The quantile
+// launch writes thr[b] of the active items in mode 1 and of no other; the update corrects every active item by its own record.
+struct ItemCorrect { int mode; float ratio, max_val; int reserved; };
+hipError_t launch_solver_update_mixed(const float* coef, const int* step_ptr, int ncoef, const SolverItems& items, const ItemCorrect* cr, const float* thr,
+                                      const float* x0, float* xe, void* xe_op, int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s,
+                                      int split, const SolverNoise& noise, float* mprev2, const SolverGuide& guide);
+hipError_t launch_abs_quantile_mixed(const QuantArgs& q, const SolverItem* items, const ItemCorrect* cr, int n_items, float* thr, hipStream_t s);
 // slot loop (misc.hip, the last section): one launch per list of n slots read from device memory; nslots = the loop items an entry may name
 hipError_t launch_sampler_admit(const float* x_T, int C, int T, int n, const int* slots, int nslots, const SolverItem* rec_in, SolverItem* rec, float* xe,
                                 void* xe_op, int prec, float* xbar, float* d1, float* mprev, float* mprev2, int ld, int split, const int* lens, int half,

@@ -328,6 +328,7 @@ struct ns2vc_unet {
     int n = 0, rows = 0;                   // loop items the records cover; rows of coef_dev in use
     ns2vc::SolverItem* dev = nullptr;
     int cap = 0;
+    std::vector<ns2vc::SolverItem> host;   // the records ns2vc_sampler_load_items sent (a slot loop's live in slots.rec)
     ns2vc::Staged stage;
   } items;
   // Slot loop (ns2vc_sampler_open): the per-item form with the loop items as SLOTS that are admitted and taken independently while the step
@@ -357,6 +358,19 @@ struct ns2vc_unet {
     float ratio = 0.995f, max_val = 1.0f;
     float* thr = nullptr;
     int cap = 0;
+    // The per-item form (ns2vc_sampler_set_x0_correction_items; not together with mode != 0 above): one record per loop item in a buffer of its
+    // own, filled from pinned staging like the seeds and the scales, so new values replay the captured step graph.  What the graph bakes in: the
+    // table being on, the two pointers, and whether the quantile launch is there (`quant`: a record in mode 1 exists, or a slot loop, whose
+    // admissions the host cannot foresee).  `host` mirrors the records for the per-item refusals (a corrected stochastic item).
+    struct Items {
+      bool on = false;
+      bool quant = false;
+      int n = 0;
+      ns2vc::ItemCorrect* dev = nullptr;
+      int cap = 0;
+      std::vector<ns2vc::ItemCorrect> host;
+      ns2vc::Staged stage;
+    } items;
   } x0c;
 
   // named persistent buffers
@@ -395,6 +409,7 @@ struct ns2vc_unet {
     if (guide.dev) (void)hipFree(guide.dev);
     if (hist2.mprev2) (void)hipFree(hist2.mprev2);
     if (x0c.thr) (void)hipFree(x0c.thr);
+    if (x0c.items.dev) (void)hipFree(x0c.items.dev);
     if (items.dev) (void)hipFree(items.dev);
     if (slots.list_dev) (void)hipFree(slots.list_dev);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);

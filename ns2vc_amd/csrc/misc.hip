@@ -746,6 +746,44 @@ __global__ __launch_bounds__(256) void solver_update_items_kernel(const float* _
   sweep(std::false_type{});
   if (mprev2) sweep(std::true_type{});                                            // (without the buffer no item of the batch has history 2)
 }
+// The same under a per-item x0 correction (ns2vc_sampler_set_x0_correction_items): item b also has a record cr[b] (common.h ItemCorrect) whose mode
+// is the TH of its quads, whose max_val is its cx.max_val and whose threshold is thr[b], left by abs_quantile_mixed_kernel in the launch before.
+// The form of a quad is now (H2, TH), both properties of its item, and every form keeps its straight line (the comment above solver_quad): one sweep
+// per form, six with an mprev2 buffer and three without, each a solver_quad of the items kernel's with a SolverCorrect filled from the record.  A
+// stochastic item has mode 0 (the host refuses every other pair), so the noise term stays in the form it has, H2 = false and TH = 0.
+template <typename TM, bool GD>
+__global__ __launch_bounds__(256) void solver_update_mixed_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
+                                                                  SolverItems si, const ItemCorrect* __restrict__ cr, const float* __restrict__ thr,
+                                                                  const float* __restrict__ x0, float* __restrict__ xe, TM* __restrict__ xe_op,
+                                                                  float* __restrict__ xbar, float* __restrict__ d1, float* __restrict__ mprev,
+                                                                  size_t n4, int split, SolverNoise nz, float* __restrict__ mprev2, SolverGuide gd) {
+  op_mode_init<TM>();
+  const int step = *step_ptr;
+  const auto sweep = [&](auto h2, auto th) {
+    constexpr bool H2 = decltype(h2)::value;
+    constexpr int TH = decltype(th)::value;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+      const int b = (int)(((4 * i) / (size_t)si.ld) / (size_t)si.T);
+      const SolverItem it = si.rec[b];
+      const ItemCorrect c = cr[b];
+      bool active;
+      const int row = solver_item_row(it, step, active);
+      if (!active || ((it.flags & SOLVER_ITEM_HIST2) != 0) != H2 || c.mode != TH) continue;      // held, or another sweep's form
+      const SolverRow kr = solver_row<H2>(coef + (size_t)row * ncoef, TH == 0 && (it.flags & SOLVER_ITEM_NOISE) != 0);
+      SolverCorrect cx;
+      cx.mode = TH; cx.thr = thr; cx.max_val = c.max_val; cx.T = si.T; cx.ld = si.ld;
+      solver_quad<TM, H2, GD, TH>(kr, row - it.row0, i, x0, xe, xe_op, xbar, d1, mprev, mprev2, n4, split, nz, gd, cx, si.T, si.ld, true);
+    }
+  };
+  sweep(std::false_type{}, std::integral_constant<int, 0>{});
+  sweep(std::false_type{}, std::integral_constant<int, 1>{});
+  sweep(std::false_type{}, std::integral_constant<int, 2>{});
+  if (mprev2) {                                                                   // (without the buffer no item of the batch has history 2)
+    sweep(std::true_type{}, std::integral_constant<int, 0>{});
+    sweep(std::true_type{}, std::integral_constant<int, 1>{});
+    sweep(std::true_type{}, std::integral_constant<int, 2>{});
+  }
+}
 // ---------------------------------------------------------------------------
 // Per-item quantile of |m| for the dynamic thresholding of the predicted x0 (sampler/dpm_solver.py:416-425, sampler/uni_pc.py:268-277:
 // torch.quantile(|x0|.reshape(B, -1), p, dim=1)).  EXACT: a radix select over the IEEE bit pattern of |m| (for non-negative floats the unsigned
@@ -884,6 +922,19 @@ __global__ __launch_bounds__(1024) void abs_quantile_items_kernel(QuantArgs q, f
   bool active;
   const int row = solver_item_row(items[blockIdx.x], *q.step_ptr, active);
   if (!active) return;                         // (block-uniform) a held item: nothing at all, thr[b] keeps its value
+  quant_item<SRC>(q, solver_coef(q.coef + (size_t)row * q.ncoef), blockIdx.x, thr);
+}
+// The same under a per-item x0 correction (common.h ItemCorrect): only an active item in mode 1 needs a threshold, at its OWN ratio (q.p is not
+// read); the workgroup of every other item returns at once and leaves thr[b] alone.
+template <int SRC>
+__global__ __launch_bounds__(1024) void abs_quantile_mixed_kernel(QuantArgs q, float* __restrict__ thr, const SolverItem* __restrict__ items,
+                                                                  const ItemCorrect* __restrict__ cr) {
+  static_assert(SRC == 1 || SRC == 2, "ready values have no table row");
+  bool active;
+  const int row = solver_item_row(items[blockIdx.x], *q.step_ptr, active);
+  const ItemCorrect c = cr[blockIdx.x];
+  if (!active || c.mode != 1) return;          // (block-uniform) held, uncorrected or clamped: nothing at all, thr[b] keeps its value
+  q.p = c.ratio;
   quant_item<SRC>(q, solver_coef(q.coef + (size_t)row * q.ncoef), blockIdx.x, thr);
 }
 // the normals of ns2vc_k_noise: one thread per (row, channel quad), the same philox_gauss4 the update adds
@@ -1136,6 +1187,33 @@ hipError_t launch_abs_quantile_items(const QuantArgs& q, const SolverItem* items
     return hipErrorInvalidValue;
   return with_int<1, 2>(q.scale ? 2 : 1, [&](auto src) {
     hipLaunchKernelGGL(abs_quantile_items_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr, items);
+    return hipGetLastError();
+  });
+}
+// the same two launches under a per-item x0 correction: cr = DEVICE [items] records the HOST has validated (mode 0 .. 2, ratio in [0, 1], max_val
+// finite and > 0, mode 0 on every stochastic item), thr = DEVICE [items] -- refused rather than run uncorrected
+hipError_t launch_solver_update_mixed(const float* coef, const int* step_ptr, int ncoef, const SolverItems& si, const ItemCorrect* cr, const float* thr,
+                                      const float* x0, float* xe, void* xe_op, int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s,
+                                      int split, const SolverNoise& noise, float* mprev2, const SolverGuide& guide) {
+  if (!cr || !thr) return hipErrorInvalidValue;
+  if (!si.rec || si.T <= 0 || si.ld <= 0 || (si.ld & 3) || n == 0 || n % ((size_t)si.T * si.ld) || ncoef < 12) return hipErrorInvalidValue;
+  if ((n & 3) || (split && (prec == PREC_F32 || split != si.ld))) return hipErrorInvalidValue;
+  if (noise.seeds && (noise.ld != si.ld || noise.T != si.T || noise.nc > noise.ld)) return hipErrorInvalidValue;
+  if (guide.scale && (guide.T != si.T || guide.ld != si.ld)) return hipErrorInvalidValue;
+  const size_t n4 = n >> 2;
+  const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+  return with_flag(guide.scale != nullptr, [&](auto gd) {
+    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_mixed_kernel<TMX, decltype(gd)::value>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, si, cr,
+                                           thr, x0, xe, (TMX*)xe_op, xbar, d1, mprev, n4, split, noise, mprev2, guide));
+    return hipGetLastError();
+  });
+}
+hipError_t launch_abs_quantile_mixed(const QuantArgs& q, const SolverItem* items, const ItemCorrect* cr, int n_items, float* thr, hipStream_t s) {
+  if (!cr || !items || !q.v || !q.xe || !q.coef || !q.step_ptr || q.ncoef < 9 || !thr || n_items <= 0 || q.T <= 0 || q.ld <= 0 || (q.ld & 3) || q.nc <= 0 ||
+      q.nc > q.ld || (((uintptr_t)q.v | (uintptr_t)q.xe) & 15) || (size_t)q.T * (size_t)q.ld > 0x7FFFFFFFull || (q.scale && (q.half == 0 || (q.half & 3))))
+    return hipErrorInvalidValue;
+  return with_int<1, 2>(q.scale ? 2 : 1, [&](auto src) {
+    hipLaunchKernelGGL(abs_quantile_mixed_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr, items, cr);
     return hipGetLastError();
   });
 }

@@ -11,7 +11,7 @@ using namespace ns2vc;
 // (same arithmetic, element for element: common.h solver_upd) -- x0 is never written, the state tensors are read and written once instead of twice
 bool ns2vc::solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
   if (h->guide.on) return false;                       // (the epilogue has no guided form: fuse_solver is ignored under guidance)
-  if (h->x0c.mode) return false;                       // (nor a corrected one: the threshold needs the whole x0 first)
+  if (h->x0c.mode || h->x0c.items.on) return false;   // (nor a corrected one: the threshold needs the whole x0 first)
   if (!h->fuse_solver || h->debug || h->conv_out_idx < 0 || h->conv_out_idx != (int)h->fwd_ops.size() - 1) return false;
   // (masked plan: the update must see x0 with its padded rows zeroed -- conv_out's epilogue has not zeroed them -- so it stays a launch of its own)
   if (h->lens.masked) return false;
@@ -24,6 +24,19 @@ bool ns2vc::solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
   g.sol_coef = h->coef_dev; g.sol_step = h->step_dev; g.sol_ncoef = NS2VC_NCOEF;
   g.sol_xe = h->xe; g.sol_xe_op = h->xe_op; g.sol_xbar = h->xbar; g.sol_d1 = h->d1; g.sol_mprev = h->mprev; g.sol_ld = h->CP; g.sol_op_pair = h->prec != PREC_F32;
   return gemm_uses_convts(g, h->conv_out_prec);
+}
+
+// Per-item x0 correction against per-item records: a stochastic item (SOLVER_ITEM_NOISE) has no correction, as in the reference, so a record with
+// mode != 0 on such an item is refused -- per item, the two may share a loop.  rec = the n records about to hold (the table off: nothing to check).
+static int item_corrections_fit(ns2vc_unet* h, const SolverItem* rec, int n) {
+  const auto& ic = h->x0c.items;
+  if (!ic.on || !rec) return 0;
+  if (ic.n != n) return fail("the per-item x0 correction holds %d records, the loop takes %d items: set it again (ns2vc_sampler_set_x0_correction_items)", ic.n, n);
+  for (int b = 0; b < n; ++b)
+    if ((rec[b].flags & SOLVER_ITEM_NOISE) && ic.host[(size_t)b].mode != 0)
+      return fail("item %d is stochastic and its x0 correction record has mode %d: ddim / ddpm have no correction (set the item's mode to 0)", b,
+                  ic.host[(size_t)b].mode);
+  return 0;
 }
 
 extern "C" {
@@ -93,6 +106,7 @@ int ns2vc_sampler_load_items(ns2vc_unet* h, int n_tables, const int32_t* table_r
     any_noise |= (flags[k] & SOLVER_ITEM_NOISE) != 0;
     any_h2 |= (flags[k] & SOLVER_ITEM_HIST2) != 0;
   }
+  if (item_corrections_fit(h, rec.data(), n_items)) return 1;
   hipStream_t s = (hipStream_t)stream;
   if (!h->coef_dev) HIPCHK(hipMalloc((void**)&h->coef_dev, (size_t)kMaxRows * NS2VC_NCOEF * sizeof(float)));
   if (!h->items.dev || h->items.cap < n_items) {      // a new records buffer invalidates the captured step graph (its launches hold the pointer)
@@ -122,6 +136,7 @@ int ns2vc_sampler_load_items(ns2vc_unet* h, int n_tables, const int32_t* table_r
   h->items.on = true;
   h->items.n = n_items;
   h->items.rows = (int)rows;
+  h->items.host = rec;
   h->steps = S;
   h->stochastic = any_noise;
   h->hist2.on = any_h2;
@@ -235,7 +250,63 @@ int ns2vc_sampler_set_x0_correction(ns2vc_unet* h, int mode, float ratio, float 
   if (mode < 0 || mode > 2) return fail("x0 correction mode %d: 0 (off), 1 (dynamic thresholding) or 2 (clamp)", mode);
   if (!(ratio >= 0.f && ratio <= 1.f)) return fail("dynamic thresholding ratio %g outside [0, 1]", (double)ratio);
   if (!(std::isfinite(max_val) && max_val > 0.f)) return fail("thresholding max_val %g must be finite and > 0", (double)max_val);
+  if (mode && h->x0c.items.on)
+    return fail("the per-item x0 correction is on (ns2vc_sampler_set_x0_correction_items): switch it off (NULL arrays) before the loop-wide "
+                "ns2vc_sampler_set_x0_correction(mode %d)", mode);
   return x0_correction_set(h, mode, ratio, max_val);
+}
+
+// The per-item form: one record per loop item, read by the step's two launches from device memory.  On / off, a new buffer and the presence of the
+// quantile launch recapture; new values replay.
+int ns2vc_sampler_set_x0_correction_items(ns2vc_unet* h, const int32_t* mode_host, const float* ratio_host, const float* max_val_host, int n, void* stream) {
+  if (check_ready(h, true)) return 1;
+  auto& ic = h->x0c.items;
+  if (!mode_host && !ratio_host && !max_val_host) {      // off
+    if (ic.on) drop_step_graph(h);
+    ic.on = false; ic.quant = false; ic.n = 0;
+    return 0;
+  }
+  if (!mode_host || !ratio_host || !max_val_host) return fail("per-item x0 correction: mode, ratio and max_val are given together (all NULL = off)");
+  if (h->x0c.mode)
+    return fail("the loop-wide x0 correction is on (ns2vc_sampler_set_x0_correction mode %d): switch it off (mode 0) before "
+                "ns2vc_sampler_set_x0_correction_items", h->x0c.mode);
+  if (n != h->loop_items())
+    return fail("per-item x0 correction for %d items, the loop takes %d (the prepared batch; n under guidance: set the guidance first)", n, h->loop_items());
+  std::vector<ItemCorrect> rec((size_t)n);
+  bool dyn = false;
+  for (int b = 0; b < n; ++b) {
+    if (mode_host[b] < 0 || mode_host[b] > 2) return fail("item %d: x0 correction mode %d: 0 (off), 1 (dynamic thresholding) or 2 (clamp)", b, (int)mode_host[b]);
+    if (!(ratio_host[b] >= 0.f && ratio_host[b] <= 1.f)) return fail("item %d: dynamic thresholding ratio %g outside [0, 1]", b, (double)ratio_host[b]);
+    if (!(std::isfinite(max_val_host[b]) && max_val_host[b] > 0.f)) return fail("item %d: thresholding max_val %g must be finite and > 0", b, (double)max_val_host[b]);
+    rec[(size_t)b] = ItemCorrect{(int)mode_host[b], ratio_host[b], max_val_host[b], 0};
+    dyn |= mode_host[b] == 1;
+  }
+  const bool slot_loop = h->in_slot_loop();
+  // a slot loop's admitted items are checked here (nothing looks at them again; an idle slot has no flags); closed schedules are checked when they
+  // load and when the loop begins, so the table and the schedules of a new batch may arrive in either order
+  if (slot_loop && (int)h->slots.rec.size() == n)
+    for (int b = 0; b < n; ++b)
+      if ((h->slots.rec[(size_t)b].flags & SOLVER_ITEM_NOISE) && rec[(size_t)b].mode != 0)
+        return fail("slot %d holds a stochastic item and its x0 correction record has mode %d: ddim / ddpm have no correction (set the slot's mode to 0)", b,
+                    rec[(size_t)b].mode);
+  hipStream_t s = (hipStream_t)stream;
+  if (!ic.dev || ic.cap < n) {      // a new records buffer invalidates the captured step graph (its launches hold the pointer)
+    drop_step_graph(h);
+    if (ic.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(ic.dev)); ic.dev = nullptr; ic.cap = 0; }
+    HIPCHK(hipMalloc((void**)&ic.dev, (size_t)n * sizeof(ItemCorrect)));
+    ic.cap = n;
+  }
+  if (ensure_thr(h, h->B)) return 1;
+  const size_t nb = (size_t)n * sizeof(ItemCorrect);
+  if (ic.stage.reserve(nb)) return 1;
+  memcpy(ic.stage.buf, rec.data(), nb);
+  HIPCHK(hipMemcpyAsync(ic.dev, ic.stage.buf, nb, hipMemcpyHostToDevice, s));
+  if (ic.stage.record(s)) return 1;
+  const bool quant = dyn || slot_loop;      // (a slot loop always has the launch: its admissions bring records the host cannot foresee)
+  if (!ic.on || quant != ic.quant) drop_step_graph(h);
+  ic.on = true; ic.quant = quant; ic.n = n;
+  ic.host = rec;
+  return 0;
 }
 
 // one evaluation + solver update
@@ -273,6 +344,22 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
   }
   if (h->items.on && h->items.n != h->loop_items())
     return fail("per-item schedules for %d items, the loop has %d (load them again)", h->items.n, h->loop_items());
+  if (h->x0c.items.on) {     // per-item x0 correction: every item's own record (misc.hip abs_quantile_mixed_kernel, solver_update_mixed_kernel)
+    const auto& ic = h->x0c.items;
+    if (!h->items.on) return fail("the per-item x0 correction runs on per-item records: load them (ns2vc_sampler_load_items) or open a slot loop");
+    if (ic.n != h->loop_items()) return fail("the per-item x0 correction holds %d records, the loop has %d items (set it again)", ic.n, h->loop_items());
+    if (ic.quant) {
+      QuantArgs q;
+      q.v = h->x0; q.xe = h->xe; q.coef = h->coef_dev; q.step_ptr = h->step_dev; q.ncoef = NS2VC_NCOEF; q.scale = gd.scale; q.half = gd.scale ? n : 0;
+      q.lens = h->lens.masked ? h->lens.dev : nullptr; q.T = h->T; q.ld = h->CP; q.nc = h->cfg.latent_channels;
+      HIPCHK(launch_abs_quantile_mixed(q, h->items.dev, ic.dev, ic.n, h->x0c.thr, s));
+    }
+    SolverItems si;
+    si.rec = h->items.dev; si.T = h->T; si.ld = h->CP;
+    HIPCHK(launch_solver_update_mixed(h->coef_dev, h->step_dev, NS2VC_NCOEF, si, ic.dev, h->x0c.thr, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev,
+                                      n, s, h->pair_off(), nz, h->hist2.on ? h->hist2.mprev2 : nullptr, gd));
+    return 0;
+  }
   SolverCorrect cx;
   if (h->x0c.mode) {         // (not with a stochastic table: ns2vc_sampler_begin refuses the pair)
     cx.mode = h->x0c.mode; cx.max_val = h->x0c.max_val; cx.T = h->T; cx.ld = h->CP;
@@ -314,6 +401,13 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
     return fail("the x0 correction (mode %d) does not apply to a stochastic table (ddpm, ddim with eta > 0): the reference's discrete samplers have none; "
                 "turn it off (ns2vc_sampler_set_x0_correction) or load a noise-free table", h->x0c.mode);
   if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
+  if (h->x0c.items.on) {
+    if (!h->items.on)
+      return fail("the per-item x0 correction (ns2vc_sampler_set_x0_correction_items) reads per-item records and this is a shared table (ns2vc_sampler_load): "
+                  "load the schedules with ns2vc_sampler_load_items, or switch the table off");
+    if (item_corrections_fit(h, h->items.host.data(), h->items.n)) return 1;
+    if (ensure_thr(h, h->B)) return 1;
+  }
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)h->B * h->T * h->CP;
   if (h->guide.on) {      // n items of x_T into the unconditional half, the same point into the conditional half
@@ -352,6 +446,8 @@ int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream)
   if (h->hist2.on && !h->hist2.mprev2) return fail("history-2 table without its m_prev2 buffer (begin the loop after loading the table)");
   if (h->stochastic && h->x0c.mode) return fail("the x0 correction does not apply to a stochastic table");
   if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
+  if (h->x0c.items.on && (!h->items.on || ensure_thr(h, h->B)))
+    return h->items.on ? 1 : fail("the per-item x0 correction reads per-item records: load them with ns2vc_sampler_load_items");
   if (slot_loop) {
     if (n_steps < 0 || n_steps > SOLVER_ITEM_NEVER - 1 - h->next_step)
       return fail("%d steps from loop step %d pass the end of the 32-bit step counter: drain the slots and call ns2vc_sampler_rebase", n_steps, h->next_step);
@@ -411,7 +507,27 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
     HIPCHK(launch_copy16(src->guide.dev, dst->guide.dev, (size_t)((src->guide.n + 3) & ~3) * sizeof(float), s));
   }
   guidance_onoff(dst, src->guide.on, src->guide.n);
-  if (x0_correction_set(dst, src->x0c.mode, src->x0c.ratio, src->x0c.max_val)) return 1;      // (the tail corrects as the head does)
+  {      // (the tail corrects as the head does: the loop-wide setting, or the per-item table and its records)
+    const auto& sc = src->x0c.items;
+    auto& dc = dst->x0c.items;
+    if (!sc.on) {
+      if (dc.on) drop_step_graph(dst);
+      dc.on = false; dc.quant = false; dc.n = 0;
+    }
+    if (x0_correction_set(dst, src->x0c.mode, src->x0c.ratio, src->x0c.max_val)) return 1;
+    if (sc.on) {
+      if (!dc.dev || dc.cap < sc.n) {
+        drop_step_graph(dst);
+        if (dc.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(dc.dev)); dc.dev = nullptr; dc.cap = 0; }
+        HIPCHK(hipMalloc((void**)&dc.dev, (size_t)sc.n * sizeof(ItemCorrect)));
+        dc.cap = sc.n;
+      }
+      if (ensure_thr(dst, dst->B)) return 1;
+      HIPCHK(launch_copy16(sc.dev, dc.dev, (size_t)sc.n * sizeof(ItemCorrect), s));
+      if (!dc.on || dc.quant != sc.quant) drop_step_graph(dst);
+      dc.on = true; dc.quant = sc.quant; dc.n = sc.n; dc.host = sc.host;
+    }
+  }
   HIPCHK(launch_copy16(src->xe, dst->xe, n * sizeof(float), s));
   HIPCHK(launch_copy16(src->xbar, dst->xbar, nh * sizeof(float), s));
   HIPCHK(launch_copy16(src->d1, dst->d1, nh * sizeof(float), s));
@@ -526,6 +642,13 @@ int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
   if (h2 && ensure_mprev2(h)) return 1;
   if (nz && ensure_seeds(h, n)) return 1;
   if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
+  if (h->x0c.items.on) {      // the per-item x0 correction is baked in beside history 2 and noise: every slot off until its admission brings a record
+    auto& ic = h->x0c.items;
+    if (ic.n != n) return fail("the per-item x0 correction holds %d records, the slot loop has %d slots: set it again (ns2vc_sampler_set_x0_correction_items)", ic.n, n);
+    if (ensure_thr(h, h->B)) return 1;
+    if (!ic.quant) drop_step_graph(h);      // (a slot loop always runs the quantile launch: the host cannot foresee its admissions)
+    ic.quant = true;
+  }
   // (which update runs, its noise arguments and its m_prev2 pointer are baked into the captured step graph)
   if (!h->items.on || nz != h->stochastic || h2 != h->hist2.on) drop_step_graph(h);
   // every slot idle, on finite data: a zero table (model time 0 in every row), zero state, zero condition, hoisted tensors rebuilt from it
@@ -551,6 +674,7 @@ int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
     h->temb_table_valid = true;
   }
   sl.rec.assign((size_t)n, solver_item_idle());
+  h->items.host = sl.rec;
   sl.busy.assign((size_t)n, 0);
   sl.coef.assign((size_t)kSlotRows * NS2VC_NCOEF, 0.f);
   {
@@ -645,6 +769,9 @@ int ns2vc_sampler_admit(ns2vc_unet* h, int n, const int32_t* slots, const float*
     if ((flags & SOLVER_ITEM_HIST2) && !h->hist2.on) return fail("slot %d runs history 2: the slot loop was opened without it (ns2vc_sampler_open history2 = 1)", b);
     if ((flags & SOLVER_ITEM_NOISE) && !h->stochastic) return fail("slot %d is stochastic: the slot loop was opened without noise (ns2vc_sampler_open noise = 1)", b);
     if (h->guide.on && h->lens.masked && h->lens.applied[b] != h->lens.applied[b + ni]) return fail("guided slot loop: lengths[%d] and lengths[%d] differ", b, b + ni);
+    if ((flags & SOLVER_ITEM_NOISE) && h->x0c.items.on && h->x0c.items.n == ni && h->x0c.items.host[(size_t)b].mode != 0)
+      return fail("slot %d is stochastic and its x0 correction record has mode %d: ddim / ddpm have no correction (set the slot's mode to 0 before "
+                  "admitting it: ns2vc_sampler_set_x0_correction_items)", b, h->x0c.items.host[(size_t)b].mode);
     rec[k] = SolverItem{r[0], r[1], r[2], r[3]};
   }
   hipStream_t s = (hipStream_t)stream;

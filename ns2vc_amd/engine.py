@@ -203,6 +203,7 @@ class Engine:
         self.prompt_lengths: Optional[np.ndarray] = None   # per-item prompt frames (set_prompt_lengths), None = every item Lp
         self.guidance: Optional[np.ndarray] = None      # per-item guidance scales (set_guidance), None = unguided
         self.x0_correction = None                       # (mode 1 | 2, ratio, max_val) of set_x0_correction, None = off
+        self.x0_corrections = None                      # (modes, ratios, max_vals) of set_x0_correction_items, None = off
         self.table: Optional[SolverTable] = None
         self.tables: Optional[ItemTables] = None        # per-item schedules (load_samplers); None = the shared table
         self._weights_ready = False
@@ -383,6 +384,29 @@ class Engine:
         check(self.lib.ns2vc_sampler_set_x0_correction(self.h, m, float(ratio), float(max_val)), "set_x0_correction")
         self.x0_correction = None if m == 0 else (m, float(np.float32(ratio)), float(np.float32(max_val)))
 
+    def set_x0_correction_items(self, modes=None, ratios=None, max_vals=None, stream=None) -> None:
+        """The x0 correction as a per-item table: loop item b is corrected by its own (modes[b], ratios[b], max_vals[b]) --
+        one entry per loop item (n under guidance: set the guidance first), ``modes`` the names or numbers ``set_x0_correction`` takes;
+        ``modes=None`` switches the table off.  Asynchronous on ``stream``: new values replay the captured step graph; on / off recaptures.
+        Item b ends on the bits it has under ``set_x0_correction(modes[b], ratios[b], max_vals[b])``.  Not together with the loop-wide
+        setting; needs per-item records (``load_samplers`` or a slot loop); a stochastic item takes mode None."""
+        if modes is None:
+            check(self.lib.ns2vc_sampler_set_x0_correction_items(self.h, None, None, None, 0, _stream_ptr(stream)), "set_x0_correction_items")
+            self.x0_corrections = None
+            return
+        modes = list(modes)
+        n = len(modes)
+        ratios = [0.995] * n if ratios is None else list(ratios)
+        max_vals = [1.0] * n if max_vals is None else list(max_vals)
+        if len(ratios) != n or len(max_vals) != n:
+            raise ValueError(f"{n} modes, {len(ratios)} ratios and {len(max_vals)} max_vals: one of each per loop item")
+        m = np.ascontiguousarray([check_x0_correction(modes[b], ratios[b], max_vals[b]) for b in range(n)], dtype=np.int32)
+        r = np.ascontiguousarray(ratios, dtype=np.float32)
+        v = np.ascontiguousarray(max_vals, dtype=np.float32)
+        check(self.lib.ns2vc_sampler_set_x0_correction_items(self.h, m.ctypes.data, r.ctypes.data, v.ctypes.data, n, _stream_ptr(stream)),
+              "set_x0_correction_items")
+        self.x0_corrections = (m.copy(), r.copy(), v.copy())
+
     def forward(self, x, t, out, stream=None) -> None:
         """x (B,100,T), t (B,) fp32, out (B,100,T): one denoiser evaluation."""
         check(self.lib.ns2vc_unet_forward(self.h, _ptr(x), _ptr(t), _ptr(out), _stream_ptr(stream)), "forward")
@@ -454,6 +478,7 @@ class Engine:
         check(self.lib.ns2vc_sampler_handoff(tail.h, self.h, sp), "sampler_handoff")
         tail.guidance = None if self.guidance is None else self.guidance.copy()      # (the hand-off carries the guidance over)
         tail.x0_correction = self.x0_correction                                        # (... and the x0 correction)
+        tail.x0_corrections = self.x0_corrections                                      # (... in either form)
         check(self.lib.ns2vc_sampler_steps(tail.h, k, int(use_graph), sp), "sampler_steps(tail)")
         check(self.lib.ns2vc_sampler_end(tail.h, _ptr(x_inout), sp), "sampler_end")
 
@@ -479,10 +504,19 @@ class Engine:
             raise ValueError("an empty slot list")
         return a
 
-    def open_slots(self, history2: bool = False, noise: bool = False, stream=None) -> None:
+    def open_slots(self, history2: bool = False, noise: bool = False, stream=None, item_corrections: bool = False) -> None:
         """Slot mode on the prepared shape: every loop item an idle slot on zero state and zero condition, the step counter running from 0.
         ``history2`` / ``noise``: order-3 / stochastic items may be admitted (fixed here: the captured step graph bakes them in, as it does
-        the guidance and the x0 correction set at this moment).  Opening again starts afresh (refused while slots are busy)."""
+        the guidance and the x0 correction set at this moment).  ``item_corrections``: the per-item x0 correction table is on, every slot off
+        until ``set_x0_correction_items`` gives it a record before its admission -- corrected and stochastic items may then share the loop;
+        False switches a table left on off.  Opening again starts afresh (refused while slots are busy)."""
+        if item_corrections:
+            if self.x0_correction is not None:
+                raise ValueError("item_corrections and the loop-wide x0 correction (set_x0_correction) exclude each other")
+            items = self.shape[0] if self.guidance is None else self.guidance.shape[0]
+            self.set_x0_correction_items([None] * items, stream=stream)
+        elif self.x0_corrections is not None:
+            self.set_x0_correction_items(None, stream=stream)
         check(self.lib.ns2vc_sampler_open(self.h, int(bool(history2)), int(bool(noise)), _stream_ptr(stream)), "sampler_open")
         self.table = self.tables = None
 

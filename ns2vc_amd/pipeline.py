@@ -75,6 +75,31 @@ def corrected_tail_min(precision: str, scales=None) -> int:
     return max(0, int(np.ceil(np.log(g * e1 / PARITY_BAR) / np.log(3.0) - 1e-9)))
 
 
+CORRECTION_KEYS = ("correcting_x0_fn", "thresholding_max_val", "dynamic_thresholding_ratio")
+
+
+def item_correction_entry(c, what: str = "correction"):
+    """One item's own x0 correction (``sample(corrections=)``, ``SlotLoop.admit(correction=)``, ``service.Segment.correction``): None or
+    ``dict(correcting_x0_fn=, thresholding_max_val=, dynamic_thresholding_ratio=)``, names only -> None (off) or (name, ratio, max_val);
+    ValueError naming ``what`` otherwise."""
+    if c is None:
+        return None
+    if callable(c):
+        raise ValueError(f"{what}: a callable cannot run inside the captured loop; pass None or a dict with correcting_x0_fn "
+                         f"'dynamic_thresholding' or 'clamp'")
+    if not isinstance(c, dict):
+        raise ValueError(f"{what} must be None or dict(correcting_x0_fn=, thresholding_max_val=, dynamic_thresholding_ratio=), got {c!r}")
+    extra = sorted(set(c) - set(CORRECTION_KEYS))
+    if extra:
+        raise ValueError(f"{what}: unknown keys {extra} (an x0 correction has {CORRECTION_KEYS})")
+    name, ratio, max_val = c.get("correcting_x0_fn"), c.get("dynamic_thresholding_ratio", 0.995), c.get("thresholding_max_val", 1.0)
+    try:
+        mode = check_x0_correction(name, ratio, max_val, names_only=True)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
+    return None if mode == 0 else (name, float(ratio), float(max_val))
+
+
 # LayerNorm-by-linearity guard thresholds on max |mean|/std (see Denoiser): 16-bit modes lose ~ratio * 2^-11 on a row,
 # fp32 loses ~ratio^2 * 2^-24 in the variance E[x^2] - mean^2
 LN_GUARD_DEFAULT = {"fp16": 8.0, "bf16": 8.0, "fp32": 32.0}
@@ -248,10 +273,28 @@ class Denoiser:
     @staticmethod
     def _x0_correction(eng, corr) -> None:
         """``corr`` = (correcting_x0_fn, ratio, max_val) or None on ``eng``; nothing reaches an engine that is off and stays off"""
+        if getattr(eng, "x0_corrections", None) is not None:      # (a per-item table left on by an earlier call: the two exclude each other)
+            eng.set_x0_correction_items(None)
         if corr is not None:
             eng.set_x0_correction(*corr)
         elif getattr(eng, "x0_correction", None) is not None:
             eng.set_x0_correction(None)
+
+    @staticmethod
+    def _x0_corrections(eng, entries, stream=None) -> None:
+        """the per-item table on ``eng``: ``entries`` = one None or (correcting_x0_fn, ratio, max_val) per loop item (set the guidance first)"""
+        if getattr(eng, "x0_correction", None) is not None:
+            eng.set_x0_correction(None)
+        eng.set_x0_correction_items([None if e is None else e[0] for e in entries], [0.995 if e is None else e[1] for e in entries],
+                                    [1.0 if e is None else e[2] for e in entries], stream=stream)
+
+    @staticmethod
+    def _check_corrections(corrections, B: int, what: str = "corrections"):
+        """the argument errors of a per-item correction list (ValueError, naming the item) -> one None or (name, ratio, max_val) per item"""
+        if not isinstance(corrections, (list, tuple)) or len(corrections) != B:
+            raise ValueError(f"{what} must be a list of one entry (dict or None) per item ({B}), got "
+                             f"{len(corrections) if isinstance(corrections, (list, tuple)) else type(corrections).__name__}")
+        return [item_correction_entry(c, f"{what}[{b}]") for b, c in enumerate(corrections)]
 
     def _betas_for(self, solver: str) -> np.ndarray:
         return self.betas64 if solver in DISCRETE_SOLVERS else self.betas
@@ -306,13 +349,18 @@ class Denoiser:
             self._tail_table_key = key
         return e
 
-    def _tail_items(self, tabs, n_tail: int, scales, stream) -> Optional[Engine]:
-        """``_tail`` under per-item schedules: the guidance goes first, the records cover the loop's items"""
+    def _tail_items(self, tabs, n_tail: int, scales, stream, corr=None, entries=None) -> Optional[Engine]:
+        """``_tail`` under per-item schedules: the guidance goes first, the records cover the loop's items; then the x0 correction in the form
+        the head has it (the schedules are checked against it when they load)"""
         if (n_tail <= 0 and not self.serving_fp32) or self.precision == "fp32":
             return None
         e = self._fp32_engine()
         if scales is not None or e.guidance is not None:
             e.set_guidance(scales, stream=stream)
+        if entries is not None:
+            self._x0_corrections(e, entries, stream)
+        else:
+            self._x0_correction(e, corr)
         key = ("items", tabs.keys, tuple(int(v) for v in tabs.start), None if scales is None else len(scales))
         if self._tail_table_key != key:
             e.load_samplers(tabs, stream=stream)
@@ -567,7 +615,7 @@ class Denoiser:
                use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None,
                prompt_lengths=None, guidance_scale=1.0, unconditional_prompt=None, unconditional_prompt_mask=None,
                unconditional_prompt_lengths=None, unconditional_content=None, correcting_x0_fn=None, thresholding_max_val: float = 1.0,
-               dynamic_thresholding_ratio: float = 0.995, schedules=None, **options):
+               dynamic_thresholding_ratio: float = 0.995, schedules=None, corrections=None, **options):
         """content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool; ``noise`` (B,100,T) = x_T (drawn with
         torch.randn like model.py:635 if None).  Returns the sampled latent (B,100,T) fp32.
         ``solver``: ``unipc`` | ``dpmsolver++`` (``order`` 1 | 2 | 3, multistep) or the reference's discrete samplers ``ddim`` (``eta`` =
@@ -598,7 +646,12 @@ class Denoiser:
         above, or None = this call's own -- served by ONE captured loop of max(evaluations) steps (``Engine.load_samplers``,
         ``schedule.run_tables_numpy``): the items are right-aligned, a shorter item is held (evaluated, not updated) until its turn, and every
         item ends on what its schedule gives it in a call of its own.  B equal schedules take the shared-table path of that schedule.  The
-        default ``tail_fp32`` is the largest any item's schedule asks for; the x0 correction stays one setting per call."""
+        default ``tail_fp32`` is the largest any item's schedule asks for.
+        ``corrections``: a list of B per-item x0 corrections -- None, or ``dict(correcting_x0_fn=, thresholding_max_val=,
+        dynamic_thresholding_ratio=)`` with the names above -- instead of the call-wide ``correcting_x0_fn=`` (both: ValueError).  Item b is
+        corrected by its own entry inside the one captured loop (``Engine.set_x0_correction_items``) and ends on the bits it has
+        when its entry is the call-wide setting; a ddim / ddpm item takes None and may share the batch with corrected items.  B equal
+        entries take the call-wide path of that entry.  The default ``tail_fp32`` counts the call as corrected when any item is."""
         import torch
         B, _, T = content.shape
         dev = content.device
@@ -606,7 +659,24 @@ class Denoiser:
                                          unconditional_prompt_lengths, unconditional_content, correcting_x0_fn, thresholding_max_val,
                                          dynamic_thresholding_ratio, **options)
         tabs = None
-        if schedules is not None:
+        entries = None
+        if corrections is not None:
+            if correcting_x0_fn is not None:
+                raise ValueError("corrections= (one x0 correction per item) and correcting_x0_fn= (one for the call) exclude each other")
+            entries = self._check_corrections(corrections, B)
+            if all(e == entries[0] for e in entries):      # one correction for everybody: today's call-wide setting, its kernels and its bits
+                e = entries[0]
+                kw = {} if e is None else dict(correcting_x0_fn=e[0], dynamic_thresholding_ratio=e[1], thresholding_max_val=e[2])
+                return self.sample(content, prompt, prompt_mask, noise, solver, steps, order, use_graph, generator, tail_fp32, lengths, eta, seeds,
+                                   prompt_lengths, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
+                                   unconditional_content, schedules=schedules, **kw, **options)
+            specs = self._check_schedules([None] * B if schedules is None else schedules, B, solver, steps, order, eta, None, options)
+            for b, sp in enumerate(specs):
+                if entries[b] is not None and schedule_key(sp, b)[0] in DISCRETE_SOLVERS:
+                    raise ValueError(f"corrections[{b}]: correcting_x0_fn applies to unipc / dpmsolver++ only (the reference's "
+                                     f"{schedule_key(sp, b)[0]} sampler has no correction: ddim / ddpm have no correction)")
+            tabs = build_tables(specs, self.betas, self.betas64)      # (the table reads item records: one schedule B times is deduplicated)
+        elif schedules is not None:
             specs = self._check_schedules(schedules, B, solver, steps, order, eta, correcting_x0_fn, options)
             keys = [schedule_key(sp, b) for b, sp in enumerate(specs)]
             if all(k == keys[0] for k in keys):      # one schedule for everybody: today's shared-table loop, its kernels and its bits
@@ -616,7 +686,7 @@ class Denoiser:
                                    dynamic_thresholding_ratio, **dict(keys[0][4]))
             tabs = build_tables(specs, self.betas, self.betas64)
         scales = self._guidance_scales(B, guidance_scale, unconditional_prompt)
-        guide_kw = dict(schedules=schedules, guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
+        guide_kw = dict(schedules=schedules, corrections=corrections, guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
                         unconditional_prompt_lengths=unconditional_prompt_lengths, unconditional_content=unconditional_content,
                         correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio)
         corr = (correcting_x0_fn, float(dynamic_thresholding_ratio), float(thresholding_max_val)) if correcting_x0_fn is not None else None
@@ -631,7 +701,10 @@ class Denoiser:
         self._prepare(rep * B, T, prompt.shape[1])
         if scales is not None or self.engine.guidance is not None:
             self.engine.set_guidance(scales, stream=torch.cuda.current_stream(dev))
-        self._x0_correction(self.engine, corr)
+        if entries is not None:
+            self._x0_corrections(self.engine, entries, torch.cuda.current_stream(dev))
+        else:
+            self._x0_correction(self.engine, corr)
         if tabs is not None:
             self._tables(tabs, torch.cuda.current_stream(dev))
         else:
@@ -644,7 +717,7 @@ class Denoiser:
                 if self.precision != "fp32" else 0
             if scales is not None and self.precision != "fp32":      # guidance multiplies the 16-bit rounding of the last evaluations
                 n_tail += guided_tail_extra(scales)
-            if corr is not None and self.precision != "fp32":        # ... and a correction lets it in twice (corrected_tail_min)
+            if (corr is not None or entries is not None) and self.precision != "fp32":      # ... and a correction lets it in twice (corrected_tail_min)
                 n_tail = max(n_tail, corrected_tail_min(self.precision, scales))
         n_tail = max(0, min(int(n_tail), nfe))
         if noise is None:
@@ -662,10 +735,10 @@ class Denoiser:
             self._condition(self.engine, c32, p32, mask, s, lengths, prompt_lengths)
             self._self_check(self._trajectory_points(x, use_graph, s, rep), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths,
                              prompt_lengths=prompt_lengths)
-        tail = self._tail(solver, steps, order, n_tail, eta, **options) if tabs is None else self._tail_items(tabs, n_tail, scales, s)
+        tail = self._tail(solver, steps, order, n_tail, eta, **options) if tabs is None else self._tail_items(tabs, n_tail, scales, s, corr, entries)
         if tabs is None and tail is not None and (scales is not None or tail.guidance is not None):
             tail.set_guidance(scales, stream=s)
-        if tail is not None:
+        if tail is not None and tabs is None:
             self._x0_correction(tail, corr)
         if tail is not None and stochastic:
             tail.set_seeds(seeds, stream=s)
@@ -691,15 +764,17 @@ class Denoiser:
 
     def open_slots(self, B: int, T: int, Lp: int, order3: bool = False, stochastic: bool = False, unconditional_prompt=None,
                    correcting_x0_fn=None, thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995,
-                   use_graph: bool = True, require_tail_free: bool = True) -> "SlotLoop":
+                   use_graph: bool = True, require_tail_free: bool = True, item_corrections: bool = False) -> "SlotLoop":
         """Continuous batching: a ``SlotLoop`` over an engine prepared for B slots of up to T frames and Lp prompt frames, whose slots are
         filled (``admit``), run (``run``) and emptied (``take``) independently while one captured step graph keeps replaying.  Fixed here,
         because the graph bakes them in: ``order3`` / ``stochastic`` (requests with order-3 / ddim-eta / ddpm schedules may come),
         ``unconditional_prompt`` (1, Lu <= Lp, C) (a guided loop: the engine runs 2 B items, every request brings its own scale) and the
-        x0 correction.  ``require_tail_free`` False admits requests that ``sample`` would give trailing fp32 evaluations anyway (previews: their
+        x0 correction -- either the loop-wide ``correcting_x0_fn=`` or ``item_corrections=True``: every request then brings its own
+        (``SlotLoop.admit(correction=)``), which also goes with ``stochastic=True`` and ``order3=True``; both: ValueError.
+        ``require_tail_free`` False admits requests that ``sample`` would give trailing fp32 evaluations anyway (previews: their
         latent carries the 16-bit rounding of its last evaluations).  See ``SlotLoop``."""
         return SlotLoop(self, B, T, Lp, order3, stochastic, unconditional_prompt, correcting_x0_fn, thresholding_max_val,
-                        dynamic_thresholding_ratio, use_graph, require_tail_free)
+                        dynamic_thresholding_ratio, use_graph, require_tail_free, item_corrections)
 
     def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, seeds=None, prompt_lengths=None, guidance_scale=1.0,
                        unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None, unconditional_content=None, **kw):
@@ -727,6 +802,10 @@ class Denoiser:
                 if len(kw["schedules"]) != n:
                     raise ValueError(f"schedules must be a list of one schedule (dict or None) per item ({n}), got {len(kw['schedules'])}")
                 kw = dict(kw, schedules=list(kw["schedules"][lo:hi]))
+            if kw.get("corrections") is not None:    # ... and so do the per-item x0 corrections
+                if len(kw["corrections"]) != n:
+                    raise ValueError(f"corrections must be a list of one entry (dict or None) per item ({n}), got {len(kw['corrections'])}")
+                kw = dict(kw, corrections=list(kw["corrections"][lo:hi]))
 
             def part(v):      # the per-item guidance arguments go with the batch; a scalar / one shared row goes to every rank whole
                 if isinstance(v, (list, tuple)):
@@ -830,8 +909,11 @@ class OverlappedPipeline:
                         v.record_stream(self.s_den)
                         if v.device != self.device:          # front end on another device: peer copy, ordered behind its event on the denoiser's stream
                             cond[k_] = v.to(self.device, non_blocking=True)
+                kw = self.kw
+                if cond.get("corrections") is not None:      # the batch's items bring their own x0 corrections: in place of the call-wide one
+                    kw = dict({k: v for k, v in kw.items() if k not in CORRECTION_KEYS}, corrections=cond["corrections"])
                 latent = self.denoiser.sample(cond["content"], cond["prompt"], cond.get("prompt_mask"), cond.get("noise"), lengths=cond.get("lengths"),
-                                              seeds=cond.get("seeds"), prompt_lengths=cond.get("prompt_lengths"), schedules=cond.get("schedules"), **self.kw)
+                                              seeds=cond.get("seeds"), prompt_lengths=cond.get("prompt_lengths"), schedules=cond.get("schedules"), **kw)
                 ev_den = torch.cuda.Event()
                 ev_den.record(self.s_den)
             with torch.cuda.device(self.post_device), torch.cuda.stream(self.s_post):
@@ -875,11 +957,16 @@ class SlotLoop:
     loop (a plan switch would end it).  The 32-bit loop step is rebased to 0 by ``admit`` whenever the loop is drained and has passed 2^30."""
 
     REBASE_AT = 1 << 30
+    item_corrections = False      # (set by open_slots(item_corrections=True): every request brings its own x0 correction)
 
     def __init__(self, den: "Denoiser", B: int, T: int, Lp: int, order3: bool, stochastic: bool, unconditional_prompt, correcting_x0_fn,
-                 thresholding_max_val: float, dynamic_thresholding_ratio: float, use_graph: bool, require_tail_free: bool = True):
+                 thresholding_max_val: float, dynamic_thresholding_ratio: float, use_graph: bool, require_tail_free: bool = True,
+                 item_corrections: bool = False):
         import torch
         self.require_tail_free = bool(require_tail_free)
+        self.item_corrections = bool(item_corrections)
+        if self.item_corrections and correcting_x0_fn is not None:
+            raise ValueError("item_corrections=True (every request brings its own x0 correction) and the loop-wide correcting_x0_fn= exclude each other")
         if min(int(B), int(T), int(Lp)) < 1:
             raise ValueError("open_slots needs B, T, Lp >= 1")
         self.den, self.B, self.T, self.Lp, self.use_graph = den, int(B), int(T), int(Lp), bool(use_graph)
@@ -903,6 +990,7 @@ class SlotLoop:
         self.plens = np.full((self.rep * self.B,), self.Lp, dtype=np.int32)
         self.seeds = np.zeros((self.B,), dtype=np.uint64)
         self.scales = np.ones((self.B,), dtype=np.float32)
+        self.corrections = [None] * self.B      # per slot: None or (name, ratio, max_val) (item_corrections)
         eng = den.engine
         den._guard_before()
         den._prepare(self.rep * self.B, self.T, self.Lp)
@@ -913,7 +1001,7 @@ class SlotLoop:
         if self.uncond is not None or eng.guidance is not None:
             eng.set_guidance(self.scales if self.uncond is not None else None, stream=s)
         den._x0_correction(eng, self.corr)
-        eng.open_slots(self.order3, self.stochastic, stream=s)
+        eng.open_slots(self.order3, self.stochastic, stream=s, item_corrections=self.item_corrections)
         if self.stochastic:
             eng.set_seeds(self.seeds, stream=s)
         den._table_key = None                    # (the engine's table belongs to the pool now)
@@ -931,8 +1019,12 @@ class SlotLoop:
             self._tables[key] = build_table(solver, steps, self.den._betas_for(solver), order, eta, **dict(opts))
         return self._tables[key]
 
-    def check_request(self, schedule, guidance_scale: float = 1.0):
-        """the errors of a request that can be seen without its tensors (ValueError); returns (key, table, flags)"""
+    def check_request(self, schedule, guidance_scale: float = 1.0, correction=None):
+        """the errors of a request that can be seen without its tensors (ValueError); returns (key, table, flags).  ``correction``: the
+        request's own x0 correction (a loop opened with ``item_corrections=True``)."""
+        own = item_correction_entry(correction, "correction")
+        if own is not None and not self.item_corrections:
+            raise ValueError("a request with its own x0 correction needs a slot loop opened with item_corrections=True")
         key = schedule_key(schedule)
         solver, steps, order, eta, _ = key
         if solver == "ddpm" and steps != len(self.den.betas64):
@@ -943,10 +1035,12 @@ class SlotLoop:
             raise ValueError("a guided request needs a slot loop opened with unconditional_prompt=")
         if self.corr is not None and solver in DISCRETE_SOLVERS:
             raise ValueError(f"correcting_x0_fn applies to unipc / dpmsolver++ only, not {solver!r}")
-        n_tail = slot_tail_needed(self.den.precision, solver, order, guidance_scale, self.corr is not None)
+        if own is not None and solver in DISCRETE_SOLVERS:
+            raise ValueError(f"correction: correcting_x0_fn applies to unipc / dpmsolver++ only, not {solver!r} (ddim / ddpm have no correction)")
+        n_tail = slot_tail_needed(self.den.precision, solver, order, guidance_scale, self.corr is not None or own is not None)
         if n_tail > 0 and self.require_tail_free:
             raise ValueError(f"this request ({solver}, order {order}, guidance scale {float(guidance_scale):g}"
-                             f"{', corrected' if self.corr is not None else ''}) needs {n_tail} trailing fp32 evaluation(s) at precision "
+                             f"{', corrected' if self.corr is not None or own is not None else ''}) needs {n_tail} trailing fp32 evaluation(s) at precision "
                              f"{self.den.precision!r}; a slot loop has no fp32 tail: open it on a Denoiser(precision=\"fp32\")")
         table = self._table(key)
         flags = table_flags(table)
@@ -958,15 +1052,17 @@ class SlotLoop:
 
     # -- the four calls ------------------------------------------------------------------------------------------------------
     def admit(self, slot: int, content, prompt, noise, length: Optional[int] = None, prompt_length: Optional[int] = None, schedule=None,
-              seed: int = 0, guidance_scale: float = 1.0) -> None:
+              seed: int = 0, guidance_scale: float = 1.0, correction=None) -> None:
         """one request into the idle ``slot`` at the current loop step: ``content`` (256, L), ``prompt`` (lp, 256), ``noise`` = x_T
         (100, L) on the GPU, L <= T and lp <= Lp frames (``length`` / ``prompt_length`` default to them; shorter values use the first
         frames), ``schedule`` = dict(solver=, steps=, order=, eta=, table options), ``seed`` of its noise stream (stochastic schedules),
-        ``guidance_scale`` (a guided loop)."""
+        ``guidance_scale`` (a guided loop), ``correction`` = the request's own x0 correction, None or ``dict(correcting_x0_fn=,
+        thresholding_max_val=, dynamic_thresholding_ratio=)`` (a loop opened with ``item_corrections=True``)."""
         self.admit_group([slot], [content], [prompt], [noise], None if length is None else [length],
-                         None if prompt_length is None else [prompt_length], [schedule], [seed], [guidance_scale])
+                         None if prompt_length is None else [prompt_length], [schedule], [seed], [guidance_scale], [correction])
 
-    def admit_group(self, slots, contents, prompts, noises, lengths=None, prompt_lengths=None, schedules=None, seeds=None, guidance_scales=None) -> None:
+    def admit_group(self, slots, contents, prompts, noises, lengths=None, prompt_lengths=None, schedules=None, seeds=None, guidance_scales=None,
+                    corrections=None) -> None:
         """``admit`` for several requests at once (lists of per-request tensors): one condition rebuild and one admit launch for all"""
         import torch
         n = len(slots)
@@ -981,12 +1077,15 @@ class SlotLoop:
         schedules = [None] * n if schedules is None else list(schedules)
         scales = [1.0] * n if guidance_scales is None else [float(g) for g in guidance_scales]
         seeds = [0] * n if seeds is None else [int(v) for v in seeds]
+        corrections = [None] * n if corrections is None else list(corrections)
+        if len(corrections) != n:
+            raise ValueError("admit_group needs one correction (dict or None) per slot")
         cfg = self.den.cfg
         reqs = []
         for k in range(n):
             if schedules[k] is None:
                 raise ValueError("a request needs its schedule: dict(solver=, steps=, ...)")
-            key, table, flags = self.check_request(schedules[k], scales[k])
+            key, table, flags = self.check_request(schedules[k], scales[k], corrections[k])
             c, p, x = contents[k], prompts[k], noises[k]
             if c.dim() != 2 or c.shape[0] != cfg.content_channels or p.dim() != 2 or p.shape[1] != cfg.cross_attention_dim or \
                     x.dim() != 2 or x.shape[0] != cfg.latent_channels:
@@ -1015,6 +1114,8 @@ class SlotLoop:
         for k, b in enumerate(slots):
             L, lp = reqs[k][3], reqs[k][4]
             self.lengths[b], self.plens[b], self.seeds[b], self.scales[b] = L, lp, seeds[k], scales[k]
+            if self.item_corrections:
+                self.corrections[b] = item_correction_entry(corrections[k])
             if self.rep == 2:      # (the unconditional half comes first)
                 self.lengths[b + self.B], self.plens[b], self.plens[b + self.B] = L, int(self.uncond.shape[1]), lp
         if self.den.precision_check is not None and not self.den._precision_checked and not any(it is not None for it in self.items):
@@ -1036,6 +1137,8 @@ class SlotLoop:
             eng.set_prompt_lengths(self.plens, stream=s)
             if self.stochastic:
                 eng.set_seeds(self.seeds, stream=s)
+            if self.item_corrections:      # (the whole vector: only the admitted slots' entries have changed)
+                self.den._x0_corrections(eng, self.corrections, s)
             if self.rep == 2:
                 eng.set_guidance(self.scales, stream=s)
                 u = torch.zeros((n, self.Lp, cfg.cross_attention_dim), dtype=torch.float32, device=dev)
@@ -1117,4 +1220,6 @@ class SlotLoop:
         for b in slots:
             self.pool.release(self.items[b]["key"])
             self.items[b] = None
+            if self.item_corrections:
+                self.corrections[b] = None      # (reaches the engine with the next admission's vector; an idle slot reads nothing)
         return out

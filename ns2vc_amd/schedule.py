@@ -506,7 +506,9 @@ def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray],
     its LOCAL row j, shaped like x_T[b] (``noise.gauss(seed_b, j, ...)``: the stream the item has alone).  ``guided_x0``: (B,) scales --
     ``x0_fn`` is then called on cat([x, x]) and cat([t, t]) (unconditional half first) and the halves are combined by
     ``schedule.guided_x0``.  ``correct_x0``: the keywords of ``schedule.correct_x0`` for the whole batch (``lengths`` per item); refused when
-    an item is stochastic."""
+    an item is stochastic.  A LIST instead is the per-item correction: one entry per item, None or such a dict for that item
+    alone (``lengths`` = its own frame count; ``item_correction``); item b is then corrected exactly as ``run_table_numpy(correct_x0=entry_b)``
+    corrects it alone, a stochastic item takes None, and corrected and stochastic items may share the batch."""
     f = np.float32
     B = x_T.shape[0]
     if tabs.index.shape[0] != B:
@@ -519,7 +521,10 @@ def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray],
     hist2 = [has_history2(tabs.table_of(b)) for b in range(B)]
     noisy = [bool((np.asarray(tabs.table_of(b).coef)[:, 9] != 0).any()) for b in range(B)]
     corr = None
-    if correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)):
+    per_item = None
+    if isinstance(correct_x0, (list, tuple)):
+        per_item = item_corrections(correct_x0, B, noisy)
+    elif correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)):
         if any(noisy):
             raise ValueError(f"the x0 correction does not apply to a batch with a stochastic item (items {[b for b in range(B) if noisy[b]]})")
         corr = dict(correct_x0)
@@ -542,6 +547,8 @@ def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray],
             m = (xe[sl] - sigma * eps) / alpha
             if corr is not None:
                 m = _correct_x0(m, lengths=None if lengths is None else [lengths[b]], **corr)
+            elif per_item is not None and per_item[b] is not None:
+                m = _correct_x0(m, **per_item[b])
             x = xbar[sl] - g0 * d1[sl] - g1 * (m - m_prev[sl])
             nb = A * x - Bc * m
             if c[9] != 0:
@@ -649,6 +656,37 @@ def correct_x0(m: np.ndarray, mode, ratio: float = 0.995, max_val: float = 1.0, 
 _correct_x0 = correct_x0      # (run_table_numpy has a keyword of that name)
 
 
+def item_correction(c, noisy: bool = False, what: str = "item") -> Optional[Dict[str, object]]:
+    """One item's entry of a per-item x0 correction -> the keywords of ``correct_x0`` for that item alone, or None where it is
+    off.  ``c``: None or ``dict(mode=, ratio=, max_val=, lengths=)`` as ``run_table_numpy(correct_x0=)`` takes it, ``lengths`` the item's
+    own frame count (a number or a one-entry list).  A stochastic item (``noisy``) takes None or mode 0 alone."""
+    if c is None:
+        return None
+    if not isinstance(c, dict):
+        raise ValueError(f"{what}: a per-item x0 correction is None or a dict(mode=, ratio=, max_val=, lengths=), got {c!r}")
+    extra = set(c) - {"mode", "ratio", "max_val", "lengths"}
+    if extra:
+        raise ValueError(f"{what}: unknown x0 correction keys {sorted(extra)}")
+    mode = check_x0_correction(c.get("mode"), c.get("ratio", 0.995), c.get("max_val", 1.0))
+    if mode == 0:
+        return None
+    if noisy:
+        raise ValueError(f"{what} is stochastic and asks for an x0 correction: ddim / ddpm have no correction")
+    L = c.get("lengths")
+    if L is not None:
+        L = [int(np.asarray(L).reshape(-1)[0])] if np.asarray(L).size == 1 else None
+        if L is None:
+            raise ValueError(f"{what}: lengths of a per-item x0 correction is the item's own frame count")
+    return dict(mode=mode, ratio=float(c.get("ratio", 0.995)), max_val=float(c.get("max_val", 1.0)), lengths=L)
+
+
+def item_corrections(entries, n: int, noisy: Optional[Sequence[bool]] = None) -> List[Optional[Dict[str, object]]]:
+    """``item_correction`` of a list of ``n`` entries (ValueError on another length); ``noisy[b]``: item b is stochastic"""
+    if len(entries) != n:
+        raise ValueError(f"{len(entries)} per-item x0 corrections for {n} items")
+    return [item_correction(c, bool(noisy[b]) if noisy is not None else False, f"item {b}") for b, c in enumerate(entries)]
+
+
 def has_history2(table: SolverTable) -> bool:
     """the table needs m_prev2 (some row of order 3): what the engine's ns2vc_sampler_load detects from columns 10-11"""
     return bool((np.asarray(table.coef)[:, 10:12] != 0).any())
@@ -720,24 +758,31 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
     writes).  A slot between items is HELD: evaluated -- at the clamped row of its last item, or at model time 0 while it has had none --,
     never updated.  ``x0_fn(x (B, ...), t (B,))`` must treat the items independently, as the engine does.  ``noise_fn(b, k, j)`` -> the
     normals of slot b's k-th item at its LOCAL row j.  Returns ``results[b][k]`` = x_e of that item after its last row: equal, bit for
-    bit, to the item run alone (``run_table_numpy``)."""
+    bit, to the item run alone (``run_table_numpy``).  ``correct_x0``: the keywords of ``schedule.correct_x0`` for every item of the loop.  A
+    request's OWN correction is a fourth tuple element instead, ``(table, start, x_T, correction)``: None or the dict
+    ``item_correction`` takes (``lengths`` = the item's own frame count); a stochastic item takes None; not together with ``correct_x0=``."""
     f = np.float32
     B = int(shape[0])
     if len(timeline) != B:
         raise ValueError(f"{len(timeline)} slot timelines for {B} slots")
     for b, items in enumerate(timeline):
         end = 0
-        for k, (tab, start, x_T) in enumerate(items):
+        for k, item in enumerate(items):
+            tab, start = item[0], item[1]
             if int(start) < end:
                 raise ValueError(f"slot {b}: item {k} starts at loop step {start}, the slot is busy until {end}")
             end = int(start) + tab.steps
+    own = [[item_correction(item[3], bool(table_flags(item[0]) & ITEM_NOISE), f"slot {b} item {k}") if len(item) > 3 else None
+            for k, item in enumerate(items)] for b, items in enumerate(timeline)]
+    if correct_x0 is not None and any(len(item) > 3 for items in timeline for item in items):
+        raise ValueError("run_slots_numpy: either correct_x0= for every item or a fourth tuple element per item, not both")
     corr = None
     if correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)):
         corr = dict(correct_x0)
     lengths = None if corr is None else corr.pop("lengths", None)
     xe = np.zeros(shape, f)
     xbar, d1, m_prev, m_prev2 = (np.zeros(shape, f) for _ in range(4))
-    S = max([int(st) + tab.steps for items in timeline for tab, st, _ in items], default=0)
+    S = max([int(item[1]) + item[0].steps for items in timeline for item in items], default=0)
     results = [[None] * len(items) for items in timeline]
     cur = [-1] * B          # the item slot b holds (the last one admitted)
     for r in range(S):
@@ -750,7 +795,7 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
                 xe[b], xbar[b] = x_T, x_T
                 d1[b], m_prev[b], m_prev2[b] = 0, 0, 0
             if cur[b] >= 0:
-                tab, start, _ = items[cur[b]]
+                tab, start = items[cur[b]][0], items[cur[b]][1]
                 j = r - int(start)
                 t[b] = f(tab.coef[min(max(j, 0), tab.steps - 1), 0])
                 if 0 <= j < tab.steps:
@@ -767,6 +812,8 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
             m = (xe[sl] - sigma * eps) / alpha
             if corr is not None:
                 m = _correct_x0(m, lengths=None if lengths is None else [lengths[b]], **corr)
+            elif own[b][cur[b]] is not None:
+                m = _correct_x0(m, **own[b][cur[b]])
             x = xbar[sl] - g0 * d1[sl] - g1 * (m - m_prev[sl])
             nb = A * x - Bc * m
             if c[9] != 0:

@@ -59,6 +59,10 @@ class Segment:
     # converter's.  Grouping ignores it: a group with different schedules runs as ONE batch (``Denoiser.sample(schedules=)``), and a
     # segment's result does not depend on its group
     schedule: Optional[dict] = None
+    # this segment's own x0 correction -- dict(correcting_x0_fn=, thresholding_max_val=, dynamic_thresholding_ratio=), names only -- or None =
+    # the converter's.  ``GroupedConverter`` serves a group whose segments differ through ``Denoiser.sample(corrections=)``,
+    # ``ContinuousConverter(item_corrections=True)`` gives every request its own; a segment's result does not depend on its group
+    correction: Optional[dict] = None
 
 
 def segment_from_audio(content_encoder, wav16k: torch.Tensor, samples_at_target_rate: int, refer_mel: torch.Tensor, hop: int = 256,
@@ -158,6 +162,10 @@ class GroupedConverter:
             sch = [getattr(segments[i], "schedule", None) for i in idx]
             if any(v is not None for v in sch):
                 cond["schedules"] = sch
+            own = {k: self.kw[k] for k in ("correcting_x0_fn", "thresholding_max_val", "dynamic_thresholding_ratio") if k in self.kw} or None
+            cor = [getattr(segments[i], "correction", None) for i in idx]
+            if any(v is not None for v in cor):
+                cond["corrections"] = [own if v is None else v for v in cor]
             return cond
 
         def dense_pre(idx):
@@ -222,8 +230,12 @@ class ContinuousConverter:
     def __init__(self, pre_model: PreModel, denoiser: Denoiser, decode_fn: Optional[Callable] = None, slots: int = 32, max_frames: int = 938,
                  max_prompt: int = 469, solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, eta: float = 0.0,
                  guidance_scale: float = 1.0, unconditional_prompt: Optional[torch.Tensor] = None, correcting_x0_fn=None,
-                 thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995, use_graph: bool = True, **options):
+                 thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995, use_graph: bool = True,
+                 item_corrections: bool = False, **options):
+        """``item_corrections``: ``Segment.correction`` is honoured -- the loop is opened with the per-item x0 correction table and every
+        segment is admitted with its own entry (None = uncorrected); not together with the loop-wide ``correcting_x0_fn=``."""
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
+        self.item_corrections = bool(item_corrections)
         self.slots, self.max_frames, self.max_prompt, self.seed, self.use_graph = int(slots), int(max_frames), int(max_prompt), seed, use_graph
         self.guided = unconditional_prompt is not None and float(guidance_scale) != 1.0
         self.scale = float(guidance_scale) if self.guided else 1.0
@@ -236,6 +248,8 @@ class ContinuousConverter:
         self.own = dict(solver=solver, steps=int(steps), order=order, eta=eta, **options)
         self.corr = dict(correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio) \
             if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True) else {}
+        if self.item_corrections and self.corr:
+            raise ValueError("item_corrections=True (Segment.correction) and the loop-wide correcting_x0_fn= exclude each other")
         self.last_plan = None          # (events of the last convert: tests, utilisation figures)
 
     def convert(self, segments: Sequence[Segment]) -> List[torch.Tensor]:
@@ -252,13 +266,14 @@ class ContinuousConverter:
             if k not in built:
                 built[k] = build_table(k[0], k[1], self.den._betas_for(k[0]), k[2], k[3], **dict(k[4]))
         tables = [built[schedule_key(sp)] for sp in specs]
+        cors = [getattr(s, "correction", None) if self.item_corrections else None for s in segments]
         loop = self.den.open_slots(self.slots, self.max_frames, self.max_prompt, order3=any(table_flags(t) & ITEM_HIST2 for t in tables),
                                    stochastic=any(table_flags(t) & ITEM_NOISE for t in tables), unconditional_prompt=self.uncond,
-                                   use_graph=self.use_graph, **self.corr)
+                                   use_graph=self.use_graph, item_corrections=self.item_corrections, **self.corr)
         loop._tables.update(built)
         try:
-            for sp in specs:               # every refusal before anything runs
-                loop.check_request(sp, self.scale)
+            for sp, cor in zip(specs, cors):      # every refusal before anything runs
+                loop.check_request(sp, self.scale, cor)
             events = plan_slots([t.steps for t in tables], self.slots)
             self.last_plan = events
             result: List[Optional[torch.Tensor]] = [None] * len(segments)
@@ -285,7 +300,8 @@ class ContinuousConverter:
                     # x_T per SEGMENT at its own length, seeded by its position in the input (as GroupedConverter): its result does not depend on its slot
                     noise = [torch.randn((nc, lens[k]), generator=torch.Generator().manual_seed(self.seed + i)).to(dev) for k, i in enumerate(idx)]
                     loop.admit_group([b for b, _ in admit], [content[k] for k in range(len(idx))], [prompt[k] for k in range(len(idx))], noise, lens, plens,
-                                     [specs[i] for i in idx], [int(derive_seed(self.seed, i)) for i in idx], [self.scale] * len(idx))
+                                     [specs[i] for i in idx], [int(derive_seed(self.seed, i)) for i in idx], [self.scale] * len(idx),
+                                     [cors[i] for i in idx])
             torch.cuda.current_stream(dev).synchronize()
         finally:                       # also after an error in mid-queue: no busy slot is left behind, the denoiser serves the next call
             loop.close()
