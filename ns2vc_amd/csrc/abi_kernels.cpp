@@ -378,24 +378,30 @@ int ns2vc_k_nct_to_btc(const float* src, int C, int T, int B, float* dst, int ld
 int ns2vc_k_btc_to_nct(const float* src, int lds, int C, int T, int B, float* dst, void* stream) {
   return launched(launch_btc_to_nct(src, lds, C, T, B, dst, (hipStream_t)stream), "btc_to_nct launch");
 }
+// The solver hooks: check the pointers, state the step (common.h SolverStep), launch.  hook_step fills what they all give
+static SolverStep hook_step(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar, float* d1,
+                            float* mprev, float* mprev2, size_t n, int ld) {
+  SolverStep st;
+  st.coef = coef_dev; st.step_ptr = step_dev; st.ncoef = NS2VC_NCOEF;
+  st.x0 = x0; st.xe = xe; st.xe_op = xe_op; st.prec = precision; st.xbar = xbar; st.d1 = d1; st.mprev = mprev; st.mprev2 = mprev2;
+  st.n = n; st.ld = ld; st.split = precision != PREC_F32 ? ld : 0;
+  return st;
+}
 int ns2vc_k_solver_update(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
                           float* d1, float* mprev, float* mprev2, size_t n, int ld, void* stream) {
   if (!coef_dev || !step_dev || !x0 || !xe || !xe_op || !xbar || !d1 || !mprev) return fail("null argument");
   if (ld <= 0 || (ld & 3) || n % (size_t)ld) return fail("n (%zu) must be a multiple of ld (%d), ld a multiple of 4", n, ld);
-  return launched(launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n, (hipStream_t)stream,
-                                      precision != PREC_F32 ? ld : 0, SolverNoise(), mprev2), "solver_update launch");
+  return launched(launch_solver_step(hook_step(coef_dev, step_dev, x0, xe, xe_op, precision, xbar, d1, mprev, mprev2, n, ld), (hipStream_t)stream),
+                  "solver_update launch");
 }
 int ns2vc_k_solver_update_guided(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
                                  float* d1, float* mprev, float* mprev2, size_t n_half, int ld, const float* scale_dev, int T, const uint64_t* seeds_dev,
                                  const int32_t* lens_dev, int nc, void* stream) {
   if (!coef_dev || !step_dev || !x0 || !xe || !xe_op || !xbar || !d1 || !mprev || !scale_dev) return fail("null argument");
   if (ld <= 0) return fail("ld (%d) must be positive", ld);
-  SolverGuide gd;
-  gd.scale = scale_dev; gd.T = T; gd.ld = ld;
-  SolverNoise nz;
-  if (seeds_dev) { nz.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev); nz.lens = lens_dev; nz.T = T; nz.ld = ld; nz.nc = nc; }
-  return launched(launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n_half, (hipStream_t)stream,
-                                      precision != PREC_F32 ? ld : 0, nz, mprev2, gd), "guided solver_update launch");
+  SolverStep st = hook_step(coef_dev, step_dev, x0, xe, xe_op, precision, xbar, d1, mprev, mprev2, n_half, ld);
+  st.T = T; st.nc = nc; st.lens = lens_dev; st.scale = scale_dev; st.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev);
+  return launched(launch_solver_step(st, (hipStream_t)stream), "guided solver_update launch");
 }
 int ns2vc_k_abs_quantile(const float* values, int n_items, int T, int ld, int nc, const int32_t* lens_dev, float p, float* thr, void* stream) {
   if (!values || !thr) return fail("null argument");
@@ -411,19 +417,28 @@ int ns2vc_k_solver_update_corrected(const float* coef_dev, const int32_t* step_d
   if (mode == 1 && !thr_dev) return fail("dynamic thresholding needs thr_dev");
   if (ld <= 0 || (ld & 3) || T <= 0 || n == 0 || n % ((size_t)T * ld)) return fail("n (%zu) must hold whole items of T (%d) rows of ld (%d) columns, ld a multiple of 4", n, T, ld);
   if (!(ratio >= 0.f && ratio <= 1.f) || !(max_val > 0.f)) return fail("ratio %g must be in [0, 1] and max_val %g > 0", (double)ratio, (double)max_val);
-  SolverGuide gd;
-  if (scale_dev) { gd.scale = scale_dev; gd.T = T; gd.ld = ld; }
-  SolverCorrect cx;
-  cx.mode = mode; cx.max_val = max_val; cx.T = T; cx.ld = ld;
-  if (mode == 1) {
-    QuantArgs q;
-    q.v = x0; q.xe = xe; q.coef = coef_dev; q.step_ptr = step_dev; q.ncoef = NS2VC_NCOEF; q.scale = scale_dev; q.half = scale_dev ? n : 0;
-    q.lens = lens_dev; q.T = T; q.ld = ld; q.nc = nc; q.p = ratio;
-    if (launched(launch_abs_quantile(q, (int)(n / ((size_t)T * ld)), thr_dev, (hipStream_t)stream), "abs_quantile launch")) return 1;
-    cx.thr = thr_dev;
+  SolverStep st = hook_step(coef_dev, step_dev, x0, xe, xe_op, precision, xbar, d1, mprev, mprev2, n, ld);
+  st.T = T; st.nc = nc; st.lens = lens_dev; st.scale = scale_dev; st.mode = mode; st.ratio = ratio; st.max_val = max_val; st.thr = thr_dev;
+  return launched(launch_solver_step(st, (hipStream_t)stream), "corrected solver_update launch");
+}
+// The two hooks with records: the n_items SolverItem records (and, with `cr`, as many ItemCorrect records behind them) go to the device for the
+// one call, the step runs on them, and the call returns when it is done
+static int run_items_step(SolverStep st, const int32_t* items_host, int n_items, const ItemCorrect* cr, hipStream_t s) {
+  static_assert(sizeof(SolverItem) == 4 * sizeof(int32_t) && sizeof(ItemCorrect) == sizeof(SolverItem), "records are four 32-bit words");
+  const size_t rb = (size_t)n_items * sizeof(SolverItem);
+  char* dev = nullptr;
+  HIPCHK(hipMalloc((void**)&dev, cr ? 2 * rb : rb));
+  int rc;
+  if (hipMemcpy(dev, items_host, rb, hipMemcpyHostToDevice) != hipSuccess || (cr && hipMemcpy(dev + rb, cr, rb, hipMemcpyHostToDevice) != hipSuccess)) {
+    rc = fail("items solver_update: copy of the records failed");
+  } else {
+    st.items = reinterpret_cast<const SolverItem*>(dev); st.n_items = n_items;
+    if (cr) st.item_correct = reinterpret_cast<const ItemCorrect*>(dev + rb);
+    rc = launched(launch_solver_step(st, s), "items solver_update launch");
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("items solver_update: stream synchronize failed");
   }
-  return launched(launch_solver_update(coef_dev, step_dev, NS2VC_NCOEF, x0, xe, xe_op, precision, xbar, d1, mprev, n, (hipStream_t)stream,
-                                      precision != PREC_F32 ? ld : 0, SolverNoise(), mprev2, gd, cx), "corrected solver_update launch");
+  (void)hipFree(dev);
+  return rc;
 }
 int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t* step_dev, const int32_t* items_host, int n_items, const float* x0, float* xe,
                                 void* xe_op, int precision, float* xbar, float* d1, float* mprev, float* mprev2, size_t n, int ld, int T,
@@ -435,46 +450,14 @@ int ns2vc_k_solver_update_items(const float* coef_dev, int n_rows, const int32_t
   if (ld <= 0 || (ld & 3) || T <= 0 || n_items <= 0 || n != (size_t)n_items * T * ld)
     return fail("n (%zu) must hold the %d items of T (%d) rows of ld (%d) columns, ld a multiple of 4", n, n_items, T, ld);
   if (mode && (!(ratio >= 0.f && ratio <= 1.f) || !(max_val > 0.f))) return fail("ratio %g must be in [0, 1] and max_val %g > 0", (double)ratio, (double)max_val);
-  static_assert(sizeof(SolverItem) == 4 * sizeof(int32_t), "records are four 32-bit words");
-  for (int b = 0; b < n_items; ++b) {      // the records name rows of the table and buffers the launch reads: checked here, the kernel trusts them
-    const int32_t* r = items_host + 4 * (size_t)b;
-    if (r[0] < 0 || r[1] <= 0 || r[2] < 0 || (long)r[0] + r[1] > n_rows) return fail("item %d: rows %d + %d outside the table of %d, or start %d < 0", b, r[0], r[1], n_rows, r[2]);
-    if ((r[3] & ~SOLVER_ITEM_BOTH) || r[3] == SOLVER_ITEM_BOTH) return fail("item %d: flags %d", b, r[3]);
-    if ((r[3] & SOLVER_ITEM_HIST2) && !mprev2) return fail("item %d runs history 2: mprev2 is needed", b);
-    if ((r[3] & SOLVER_ITEM_NOISE) && (!seeds_dev || mode)) return fail("item %d is stochastic: seeds_dev is needed and no correction applies", b);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  SolverItem* rec = nullptr;
-  HIPCHK(hipMalloc((void**)&rec, (size_t)n_items * sizeof(SolverItem)));
-  int rc = 1;
-  if (hipMemcpy(rec, items_host, (size_t)n_items * sizeof(SolverItem), hipMemcpyHostToDevice) == hipSuccess) {
-    SolverItems si;
-    si.rec = rec; si.T = T; si.ld = ld;
-    SolverGuide gd;
-    if (scale_dev) { gd.scale = scale_dev; gd.T = T; gd.ld = ld; }
-    SolverNoise nz;
-    if (seeds_dev) { nz.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev); nz.lens = lens_dev; nz.T = T; nz.ld = ld; nz.nc = nc; }
-    SolverCorrect cx;
-    rc = 0;
-    if (mode) {
-      cx.mode = mode; cx.max_val = max_val; cx.T = T; cx.ld = ld;
-      if (mode == 1) {
-        QuantArgs q;
-        q.v = x0; q.xe = xe; q.coef = coef_dev; q.step_ptr = step_dev; q.ncoef = NS2VC_NCOEF; q.scale = scale_dev; q.half = scale_dev ? n : 0;
-        q.lens = lens_dev; q.T = T; q.ld = ld; q.nc = nc; q.p = ratio;
-        rc = launched(launch_abs_quantile_items(q, rec, n_items, thr_dev, s), "abs_quantile_items launch");
-        cx.thr = thr_dev;
-      }
-    }
-    if (!rc)
-      rc = launched(launch_solver_update_items(coef_dev, step_dev, NS2VC_NCOEF, si, x0, xe, xe_op, precision, xbar, d1, mprev, n, s,
-                                               precision != PREC_F32 ? ld : 0, nz, mprev2, gd, cx), "items solver_update launch");
-    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("items solver_update: stream synchronize failed");
-  } else {
-    (void)fail("items solver_update: copy of the records failed");
-  }
-  (void)hipFree(rec);
-  return rc;
+  if (solver_items_fit("item", reinterpret_cast<const SolverItem*>(items_host), nullptr, n_items, n_rows, nullptr, mprev2 ? nullptr : "mprev2 is needed",
+                       seeds_dev ? nullptr : "seeds_dev is needed", mode, nullptr))
+    return 1;
+  SolverStep st = hook_step(coef_dev, step_dev, x0, xe, xe_op, precision, xbar, d1, mprev, mprev2, n, ld);
+  st.T = T; st.nc = nc; st.lens = lens_dev; st.scale = scale_dev; st.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev);
+  if (mode) { st.mode = mode; st.ratio = ratio; st.max_val = max_val; }
+  st.thr = thr_dev;
+  return run_items_step(st, items_host, n_items, nullptr, (hipStream_t)stream);
 }
 // the same step under a per-item x0 correction: HOST arrays [n_items] of mode, ratio and max_val in place of the three scalars; the two launches the
 // loop makes (the quantile only when a record has mode 1)
@@ -487,52 +470,14 @@ int ns2vc_k_solver_update_items_corrected(const float* coef_dev, int n_rows, con
   if (!thr_dev) return fail("items corrected update: thr_dev is needed");
   if (ld <= 0 || (ld & 3) || T <= 0 || n_items <= 0 || n != (size_t)n_items * T * ld)
     return fail("n (%zu) must hold the %d items of T (%d) rows of ld (%d) columns, ld a multiple of 4", n, n_items, T, ld);
-  static_assert(sizeof(SolverItem) == 4 * sizeof(int32_t), "records are four 32-bit words");
-  std::vector<ItemCorrect> cr((size_t)n_items);
-  bool dyn = false;
-  for (int b = 0; b < n_items; ++b) {      // the records name rows of the table and buffers the launch reads: checked here, the kernels trust them
-    const int32_t* r = items_host + 4 * (size_t)b;
-    if (r[0] < 0 || r[1] <= 0 || r[2] < 0 || (long)r[0] + r[1] > n_rows) return fail("item %d: rows %d + %d outside the table of %d, or start %d < 0", b, r[0], r[1], n_rows, r[2]);
-    if ((r[3] & ~SOLVER_ITEM_BOTH) || r[3] == SOLVER_ITEM_BOTH) return fail("item %d: flags %d", b, r[3]);
-    if ((r[3] & SOLVER_ITEM_HIST2) && !mprev2) return fail("item %d runs history 2: mprev2 is needed", b);
-    if ((r[3] & SOLVER_ITEM_NOISE) && !seeds_dev) return fail("item %d is stochastic: seeds_dev is needed", b);
-    if (mode_host[b] < 0 || mode_host[b] > 2) return fail("item %d: mode %d must be 0 (off), 1 (dynamic thresholding) or 2 (clamp)", b, (int)mode_host[b]);
-    if (!(ratio_host[b] >= 0.f && ratio_host[b] <= 1.f)) return fail("item %d: ratio %g must be in [0, 1]", b, (double)ratio_host[b]);
-    if (!(std::isfinite(max_val_host[b]) && max_val_host[b] > 0.f)) return fail("item %d: max_val %g must be finite and > 0", b, (double)max_val_host[b]);
-    if ((r[3] & SOLVER_ITEM_NOISE) && mode_host[b] != 0) return fail("item %d is stochastic and has mode %d: ddim / ddpm have no correction", b, (int)mode_host[b]);
-    cr[(size_t)b] = ItemCorrect{(int)mode_host[b], ratio_host[b], max_val_host[b], 0};
-    dyn |= mode_host[b] == 1;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  char* dev = nullptr;      // [n_items] SolverItem, then [n_items] ItemCorrect (16 bytes each)
-  const size_t rb = (size_t)n_items * sizeof(SolverItem), cb = (size_t)n_items * sizeof(ItemCorrect);
-  HIPCHK(hipMalloc((void**)&dev, rb + cb));
-  int rc = 1;
-  if (hipMemcpy(dev, items_host, rb, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dev + rb, cr.data(), cb, hipMemcpyHostToDevice) == hipSuccess) {
-    const SolverItem* rec = reinterpret_cast<const SolverItem*>(dev);
-    const ItemCorrect* crd = reinterpret_cast<const ItemCorrect*>(dev + rb);
-    SolverItems si;
-    si.rec = rec; si.T = T; si.ld = ld;
-    SolverGuide gd;
-    if (scale_dev) { gd.scale = scale_dev; gd.T = T; gd.ld = ld; }
-    SolverNoise nz;
-    if (seeds_dev) { nz.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev); nz.lens = lens_dev; nz.T = T; nz.ld = ld; nz.nc = nc; }
-    rc = 0;
-    if (dyn) {
-      QuantArgs q;
-      q.v = x0; q.xe = xe; q.coef = coef_dev; q.step_ptr = step_dev; q.ncoef = NS2VC_NCOEF; q.scale = scale_dev; q.half = scale_dev ? n : 0;
-      q.lens = lens_dev; q.T = T; q.ld = ld; q.nc = nc;
-      rc = launched(launch_abs_quantile_mixed(q, rec, crd, n_items, thr_dev, s), "abs_quantile_mixed launch");
-    }
-    if (!rc)
-      rc = launched(launch_solver_update_mixed(coef_dev, step_dev, NS2VC_NCOEF, si, crd, thr_dev, x0, xe, xe_op, precision, xbar, d1, mprev, n, s,
-                                               precision != PREC_F32 ? ld : 0, nz, mprev2, gd), "mixed solver_update launch");
-    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("items corrected solver_update: stream synchronize failed");
-  } else {
-    (void)fail("items corrected solver_update: copy of the records failed");
-  }
-  (void)hipFree(dev);
-  return rc;
+  std::vector<ItemCorrect> cr;
+  SolverStep st = hook_step(coef_dev, step_dev, x0, xe, xe_op, precision, xbar, d1, mprev, mprev2, n, ld);
+  if (item_corrections_from(mode_host, ratio_host, max_val_host, n_items, cr, st.quant) ||
+      solver_items_fit("item", reinterpret_cast<const SolverItem*>(items_host), nullptr, n_items, n_rows, nullptr, mprev2 ? nullptr : "mprev2 is needed",
+                       seeds_dev ? nullptr : "seeds_dev is needed", 0, cr.data()))
+    return 1;
+  st.T = T; st.nc = nc; st.lens = lens_dev; st.scale = scale_dev; st.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev); st.thr = thr_dev;
+  return run_items_step(st, items_host, n_items, cr.data(), (hipStream_t)stream);
 }
 // a host slot list, checked (entries in [0, n_items), none twice), on the device for one hook call
 static int upload_slots(const int32_t* slots_host, int n, int n_items, int** out_dev) {

@@ -383,7 +383,7 @@ hipError_t launch_gn_apply(const float* a0, int lda0, int c0, const float* a1, i
 hipError_t launch_mask_rows(void* dst, size_t ldd_bytes, size_t row_bytes, int B, int T, const int* lens, hipStream_t s, const void* src = nullptr,
                             size_t lds_bytes = 0, int Tsrc = 0, int up = 0);
 hipError_t launch_ln_apply_op(const float* x, int ldx, int M, int C, float eps, void* out_op, int prec, hipStream_t s);
-hipError_t launch_cast_op(const float* x, size_t n, void* out_op, int prec, hipStream_t s, int split = 0);   // split: as launch_solver_update
+hipError_t launch_cast_op(const float* x, size_t n, void* out_op, int prec, hipStream_t s, int split = 0);   // split: as SolverStep.split
 hipError_t launch_time_embed(const float* t_ptr, int t_stride, const int* step_ptr, int coef_stride,
                              const float* w1t, const float* b1, const float* w2t, const float* b2,
                              const float* aug, float* emb, void* emb_act_op, int prec, int B, int tdim, int edim, hipStream_t s);
@@ -415,15 +415,21 @@ hipError_t launch_pool_cls(float* seq, int B, int L, int C, const float* pos, hi
 hipError_t launch_pool_attn(const float* qkv, int B, int L1, int C, int heads, float* pooled, hipStream_t s, const int* plens = nullptr);
 hipError_t launch_pool_proj(const float* pooled, int B, int C, const float* wt, const float* b, int E,
                             const float* gamma, const float* beta, float eps, float* out, hipStream_t s);
-// noise (optional): column 9 of the table row; where it is nonzero, state element (b, t, c) of rows of `ld` columns gains noise * z with
+// ---- the solver step (misc.hip) ----
+// The kernels' argument structs, passed by value; launch_solver_step builds them from the one geometry of a SolverStep (below).
+// noise: column 9 of the table row; where it is nonzero, state element (b, t, c) of rows of `ld` columns gains noise * z with
 // z = philox_gauss4(seeds[b], t, c / 4, step), for c < nc and t < lens[b] (lens NULL: every t < T) -- the other elements get nothing
 struct SolverNoise { const unsigned long long* seeds = nullptr; const int* lens = nullptr; int T = 0, ld = 0, nc = 0; };
-// guidance (optional): scale = DEVICE [n] per-item scales of a guided engine of 2n items of T rows of ld columns.  n then counts the elements of
-// ONE half: x0, xe and xe_op cover both halves (unconditional rows first), xbar / d1 / mprev / mprev2 the first
+// guidance: scale = DEVICE [n] per-item scales of a guided engine of 2n items of T rows of ld columns
 struct SolverGuide { const float* scale = nullptr; int T = 0, ld = 0; };
-// x0 correction (optional; common.h solver_correct): mode 1 = dynamic thresholding by max(thr[b], max_val), thr = DEVICE [items] left by
-// launch_abs_quantile; mode 2 = clamp by max_val.  Items are T rows of ld columns (guided: those of one half).  Not together with noise
+// x0 correction (common.h solver_correct): mode 1 = dynamic thresholding by max(thr[b], max_val), thr = DEVICE [items] left by the quantile
+// launch; mode 2 = clamp by max_val
 struct SolverCorrect { int mode = 0; const float* thr = nullptr; float max_val = 1.0f; int T = 0, ld = 0; };
+// per-item rows: rec = DEVICE [items] records (SolverItem above)
+struct SolverItems { const SolverItem* rec = nullptr; int T = 0, ld = 0; };
+// per-item x0 correction (ns2vc_sampler_set_x0_correction_items): DEVICE [items] records beside the SolverItem records, validated by the host
+// (solver_items_fit: mode 0 = off, 1 = dynamic thresholding at the item's own ratio, 2 = clamp; max_val finite and > 0; mode 0 on a stochastic item)
+struct ItemCorrect { int mode; float ratio, max_val; int reserved; };
 // thr[b] = the p-quantile (torch.quantile's float32 rule) of |m| over rows t < lens[b] (NULL: T) and columns c < nc of item b's T rows of ld columns.
 // xe == NULL: `v` holds the values themselves.  Otherwise v = x0 and m is formed as the update forms it from row *step_ptr of the table; with
 // `scale` (DEVICE [items]) on guided_x0 of v and v + half (half = the elements of one half).  One workgroup per item, nothing shared between them
@@ -431,32 +437,32 @@ struct QuantArgs {
   const float* v = nullptr; const float* xe = nullptr; const float* coef = nullptr; const int* step_ptr = nullptr; int ncoef = 0;
   const float* scale = nullptr; size_t half = 0; const int* lens = nullptr; int T = 0, ld = 0, nc = 0; float p = 0.995f;
 };
-hipError_t launch_abs_quantile(const QuantArgs& q, int n_items, float* thr, hipStream_t s);
-hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0,
-                                float* xe, void* xe_op, int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s,
-                                int split = 0,                  // split > 0 (16-bit): xe_op rows are [hi(split) | lo(split)] of state rows of `split` columns
-                                const SolverNoise& noise = SolverNoise(),
-                                float* mprev2 = nullptr,        // non-NULL: the history-2 update (order-3 tables; m_{i-2} in, m_{i-1} out); no noise with it
-                                const SolverGuide& guide = SolverGuide(),
-                                const SolverCorrect& correct = SolverCorrect());
-// per-item schedules: rec = DEVICE [items] records (SolverItem above) of items of T rows of ld columns.  The update, the quantile and the time
-// embedding of a step then take every item's own table row; a held item is left alone (launch_solver_update_items, launch_abs_quantile_items: thr[b]
-// of a held item keeps its value) or evaluated at its clamped row (launch_emb_items_from_table: B engine rows read the n_items records B / n_items times)
-struct SolverItems { const SolverItem* rec = nullptr; int T = 0, ld = 0; };
-hipError_t launch_solver_update_items(const float* coef, const int* step_ptr, int ncoef, const SolverItems& items, const float* x0, float* xe, void* xe_op,
-                                      int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise,
-                                      float* mprev2, const SolverGuide& guide, const SolverCorrect& correct);
-hipError_t launch_abs_quantile_items(const QuantArgs& q, const SolverItem* items, int n_items, float* thr, hipStream_t s);
+// items (DEVICE [n_items] records): every item's m from the row of its own table, thr[b] of a held item keeps its value; with item_correct
+// (DEVICE [n_items]) only the active items in mode 1 get a threshold, at their own ratio (q.p is not read)
+hipError_t launch_abs_quantile(const QuantArgs& q, int n_items, float* thr, hipStream_t s, const SolverItem* items = nullptr,
+                               const ItemCorrect* item_correct = nullptr);
+// What one solver step is, every fact once.  All pointers DEVICE; the optional parts are off when NULL / 0.
+struct SolverStep {
+  const float* coef = nullptr; const int* step_ptr = nullptr; int ncoef = 0;      // the table, its row (shared) or loop step (items) read from *step_ptr
+  const float* x0 = nullptr; float* xe = nullptr; void* xe_op = nullptr; int prec = PREC_F32;      // the state; xe_op operand-typed by prec
+  float *xbar = nullptr, *d1 = nullptr, *mprev = nullptr;
+  float* mprev2 = nullptr;                 // the history-2 update (order-3 tables; m_{i-2} in, m_{i-1} out); under `items`, the buffer of the items that run it
+  // the geometry: n elements (guided: of ONE half -- x0, xe and xe_op cover both, unconditional rows first, the histories the first) in whole
+  // items of T rows of ld columns, nc of them real, lens[b] rows of item b valid (NULL: T).  T may stay 0 where no part below asks for items
+  size_t n = 0; int T = 0, ld = 0, nc = 0; const int* lens = nullptr;
+  int split = 0;                           // (16-bit) xe_op rows are the pair [hi(split) | lo(split)] of state rows of `split` columns
+  const float* scale = nullptr;            // guidance: [items] per-item scales
+  const unsigned long long* seeds = nullptr;      // noise: [items] seeds; no correction and (shared table) no history 2 with it
+  const SolverItem* items = nullptr; int n_items = 0;      // per-item rows: n covers exactly these items; a held item is left alone
+  int mode = 0; float ratio = 0.995f, max_val = 1.0f;      // loop-wide x0 correction, or ...
+  const ItemCorrect* item_correct = nullptr; bool quant = false;      // ... per-item records (with `items`); quant: a record in mode 1 may exist
+  float* thr = nullptr;                    // [items] thresholds: written by the quantile launch of mode 1 / quant, read by the update
+};
+// validates, issues the quantile launch where the form has one, then the update -- refused rather than run unguided, uncorrected or on the shared row
+hipError_t launch_solver_step(const SolverStep& st, hipStream_t s);
+// the time embedding under per-item rows: a held item is evaluated at its clamped row; B engine rows read the n_items records B / n_items times
 hipError_t launch_emb_items_from_table(const float* table, const int* step_ptr, const SolverItem* items, int n_items, const float* aug, float* emb,
                                        void* emb_act_op, int prec, int B, int edim, hipStream_t s);
-// per-item x0 correction (ns2vc_sampler_set_x0_correction_items): cr = DEVICE [items] records beside the SolverItem records, validated by the host
-// (mode 0 = off, 1 = dynamic thresholding at the item's own ratio, 2 = clamp; max_val finite and > 0; mode 0 on a stochastic item).  The quantile
-// launch writes thr[b] of the active items in mode 1 and of no other; the update corrects every active item by its own record.
-struct ItemCorrect { int mode; float ratio, max_val; int reserved; };
-hipError_t launch_solver_update_mixed(const float* coef, const int* step_ptr, int ncoef, const SolverItems& items, const ItemCorrect* cr, const float* thr,
-                                      const float* x0, float* xe, void* xe_op, int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s,
-                                      int split, const SolverNoise& noise, float* mprev2, const SolverGuide& guide);
-hipError_t launch_abs_quantile_mixed(const QuantArgs& q, const SolverItem* items, const ItemCorrect* cr, int n_items, float* thr, hipStream_t s);
 // slot loop (misc.hip, the last section): one launch per list of n slots read from device memory; nslots = the loop items an entry may name
 hipError_t launch_sampler_admit(const float* x_T, int C, int T, int n, const int* slots, int nslots, const SolverItem* rec_in, SolverItem* rec, float* xe,
                                 void* xe_op, int prec, float* xbar, float* d1, float* mprev, float* mprev2, int ld, int split, const int* lens, int half,

@@ -4,8 +4,10 @@
 #pragma once
 #include "common.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <string>
@@ -43,6 +45,46 @@ inline int solver_table_form(const float* rows, int n) {
     if (r[10] != 0.f || r[11] != 0.f) flags |= SOLVER_ITEM_HIST2;
   }
   return flags;
+}
+
+// "These SolverItem records are fit to launch" -- the one statement of what the step's kernels trust about them.  Record k is named `who`
+// index[k] (NULL: k) in the messages, and that is also its place in `correct`.  rows inside [0, n_rows) and a start >= 0; flags one form; with the
+// host's copy of the table (`table`, else NULL) flags = the form of the item's rows; history 2 needs the m_prev2 buffer and noise the seeds --
+// no_mprev2 / no_seeds are NULL when the buffer is there, else the caller's words for why it is not; a stochastic item takes no correction,
+// neither the loop-wide `mode` nor its own record in `correct` (NULL: none).
+inline int solver_items_fit(const char* who, const SolverItem* rec, const int32_t* index, int n, int n_rows, const float* table, const char* no_mprev2,
+                            const char* no_seeds, int mode, const ItemCorrect* correct) {
+  for (int k = 0; k < n; ++k) {
+    const SolverItem& r = rec[k];
+    const int b = index ? index[k] : k;
+    if (r.row0 < 0 || r.steps <= 0 || r.start < 0 || r.row0 > n_rows - r.steps)
+      return fail("%s %d: rows %d + %d outside the table of %d rows, or start %d < 0", who, b, r.row0, r.steps, n_rows, r.start);
+    if ((r.flags & ~SOLVER_ITEM_BOTH) || r.flags == SOLVER_ITEM_BOTH)
+      return fail("%s %d: flags %d (1 = history 2, 2 = noise; a table with both is not supported)", who, b, r.flags);
+    if (table && solver_table_form(table + (size_t)r.row0 * NS2VC_NCOEF, r.steps) != r.flags)
+      return fail("%s %d: flags %d, its rows %d .. %d have the form %d (1 = history 2, 2 = noise)", who, b, r.flags, r.row0, r.row0 + r.steps - 1,
+                  solver_table_form(table + (size_t)r.row0 * NS2VC_NCOEF, r.steps));
+    if ((r.flags & SOLVER_ITEM_HIST2) && no_mprev2) return fail("%s %d runs history 2: %s", who, b, no_mprev2);
+    if (!(r.flags & SOLVER_ITEM_NOISE)) continue;
+    if (no_seeds) return fail("%s %d is stochastic: %s", who, b, no_seeds);
+    const int m = correct ? correct[b].mode : mode;
+    if (m != 0)
+      return fail("%s %d is stochastic and its x0 correction has mode %d: ddim / ddpm have no correction (set the %s's mode to 0)", who, b, m, who);
+  }
+  return 0;
+}
+// the per-item x0 correction records from the ABI's three host arrays, every value checked; dyn: a record in mode 1 exists
+inline int item_corrections_from(const int32_t* mode, const float* ratio, const float* max_val, int n, std::vector<ItemCorrect>& rec, bool& dyn) {
+  rec.resize((size_t)n);
+  dyn = false;
+  for (int b = 0; b < n; ++b) {
+    if (mode[b] < 0 || mode[b] > 2) return fail("item %d: x0 correction mode %d: 0 (off), 1 (dynamic thresholding) or 2 (clamp)", b, (int)mode[b]);
+    if (!(ratio[b] >= 0.f && ratio[b] <= 1.f)) return fail("item %d: dynamic thresholding ratio %g outside [0, 1]", b, (double)ratio[b]);
+    if (!(std::isfinite(max_val[b]) && max_val[b] > 0.f)) return fail("item %d: thresholding max_val %g must be finite and > 0", b, (double)max_val[b]);
+    rec[(size_t)b] = ItemCorrect{(int)mode[b], ratio[b], max_val[b], 0};
+    dyn |= mode[b] == 1;
+  }
+  return 0;
 }
 
 struct HostTensor {
@@ -138,6 +180,39 @@ struct Staged {
     if (event) (void)hipEventDestroy(event);
     if (buf) (void)hipHostFree(buf);
   }
+};
+
+
+void drop_step_graph(::ns2vc_unet* h);      // plan.cpp
+
+// A device table of the sampling loop that lives outside the plan arena and grows on demand: the seeds, the guidance scales, the thresholds, the
+// per-item records, the m_{i-2} buffer.  The captured step graph holds its pointer, so a NEW buffer drops the graph; new values in the same buffer
+// are a copy from pinned staging on the caller's stream and replay it.  cap is kept a 16-byte multiple (launch_copy16 moves whole tables).
+template <typename T> struct StepTable {
+  T* dev = nullptr;
+  size_t cap = 0;      // elements
+  Staged stage;
+  static size_t rounded(size_t n) { return sizeof(T) >= 16 ? n : (n + 16 / sizeof(T) - 1) / (16 / sizeof(T)) * (16 / sizeof(T)); }
+  // room for n elements: nothing when they fit; else the step graph goes, the device drains, and a new buffer (zeroed with `clear`) replaces the old
+  int reserve(::ns2vc_unet* h, size_t n, bool clear) {
+    if (dev && cap >= n) return 0;
+    drop_step_graph(h);
+    if (dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(dev)); dev = nullptr; cap = 0; }
+    const size_t c = rounded(n);
+    HIPCHK(hipMalloc((void**)&dev, c * sizeof(T)));
+    if (clear) HIPCHK(hipMemset(dev, 0, c * sizeof(T)));
+    cap = c;
+    return 0;
+  }
+  // these n host values into the buffer (room made before), asynchronously on s
+  int send(const T* host, size_t n, hipStream_t s) {
+    const size_t nb = n * sizeof(T);
+    if (stage.reserve(nb)) return 1;
+    memcpy(stage.buf, host, nb);
+    HIPCHK(hipMemcpyAsync(dev, stage.buf, nb, hipMemcpyHostToDevice, s));
+    return stage.record(s);
+  }
+  ~StepTable() { if (dev) (void)hipFree(dev); }
 };
 
 }  // namespace ns2vc
@@ -294,42 +369,31 @@ struct ns2vc_unet {
   } plens;
   // Per-item noise seeds of the stochastic samplers (ns2vc_sampler_set_seeds): a buffer of its own (the captured step graph reads it, so new
   // seeds are a copy into it), pinned staging as for the lengths.
-  struct Seeds {
-    unsigned long long* dev = nullptr;
-    int cap = 0;
+  struct Seeds : ns2vc::StepTable<unsigned long long> {
     bool set = false;                      // set since the last prepare
-    ns2vc::Staged stage;
   } seeds;
   bool stochastic = false;                 // the loaded table has a nonzero noise column
   // Classifier-free guidance (ns2vc_sampler_set_guidance): the engine is prepared for B = 2n items, rows [0, n*T) the unconditional half and
   // [n*T, 2n*T) the conditional one; the loop's entry points take and give n items and the update combines the halves by the per-item scales.
   // The scales live in a buffer of their own as the seeds do (new values are a copy, the captured step graph stays valid).
-  struct Guidance {
+  struct Guidance : ns2vc::StepTable<float> {
     bool on = false;
     int n = 0;
-    float* dev = nullptr;
-    int cap = 0;
-    ns2vc::Staged stage;
   } guide;
   int loop_items() const { return guide.on ? guide.n : B; }      // items the sampling loop's entry points take and give
   // History 2 (order-3 tables: a nonzero column 10 or 11, detected by ns2vc_sampler_load): the update also keeps m_{i-2}, in a buffer
   // of its own outside the plan arena, allocated on the first loop that needs it -- the dense plan's layout and launches do not change.
-  struct History2 {
+  struct History2 : ns2vc::StepTable<float> {      // dev = m_{i-2}, B * T * CP floats
     bool on = false;
-    float* mprev2 = nullptr;
-    size_t n = 0;
   } hist2;
   // Per-item schedules (ns2vc_sampler_load_items): every loop item walks a solver table of its own (common.h SolverItem).  coef_dev then holds the
   // `rows` rows of the distinct tables, `steps` the loop's length S = max(start + steps), `stochastic` / `hist2.on` the UNION over the items (what
   // begin allocates and requires).  The records live in a buffer of their own outside the plan arena, filled from pinned staging (new schedules of
   // the same form are a copy: the captured step graph stays valid); on / off, and a change of either union flag, recapture.
-  struct ItemSchedules {
+  struct ItemSchedules : ns2vc::StepTable<ns2vc::SolverItem> {
     bool on = false;
     int n = 0, rows = 0;                   // loop items the records cover; rows of coef_dev in use
-    ns2vc::SolverItem* dev = nullptr;
-    int cap = 0;
     std::vector<ns2vc::SolverItem> host;   // the records ns2vc_sampler_load_items sent (a slot loop's live in slots.rec)
-    ns2vc::Staged stage;
   } items;
   // Slot loop (ns2vc_sampler_open): the per-item form with the loop items as SLOTS that are admitted and taken independently while the step
   // counter keeps running.  `rec` / `busy` are the host's mirror of the device records (busy = admitted and not yet taken); the forms the
@@ -356,20 +420,16 @@ struct ns2vc_unet {
   struct X0Correction {
     int mode = 0;
     float ratio = 0.995f, max_val = 1.0f;
-    float* thr = nullptr;
-    int cap = 0;
+    ns2vc::StepTable<float> thr;
     // The per-item form (ns2vc_sampler_set_x0_correction_items; not together with mode != 0 above): one record per loop item in a buffer of its
     // own, filled from pinned staging like the seeds and the scales, so new values replay the captured step graph.  What the graph bakes in: the
     // table being on, the two pointers, and whether the quantile launch is there (`quant`: a record in mode 1 exists, or a slot loop, whose
     // admissions the host cannot foresee).  `host` mirrors the records for the per-item refusals (a corrected stochastic item).
-    struct Items {
+    struct Items : ns2vc::StepTable<ns2vc::ItemCorrect> {
       bool on = false;
       bool quant = false;
       int n = 0;
-      ns2vc::ItemCorrect* dev = nullptr;
-      int cap = 0;
       std::vector<ns2vc::ItemCorrect> host;
-      ns2vc::Staged stage;
     } items;
   } x0c;
 
@@ -404,13 +464,7 @@ struct ns2vc_unet {
   int pair_width() const { return prec != ns2vc::PREC_F32 ? 2 * CP : CP; }
   int pair_off() const { return prec != ns2vc::PREC_F32 ? CP : 0; }
 
-  ~ns2vc_unet() {      // (the pinned staging of the lengths and the seeds releases itself after this: ns2vc::Staged)
-    if (seeds.dev) (void)hipFree(seeds.dev);
-    if (guide.dev) (void)hipFree(guide.dev);
-    if (hist2.mprev2) (void)hipFree(hist2.mprev2);
-    if (x0c.thr) (void)hipFree(x0c.thr);
-    if (x0c.items.dev) (void)hipFree(x0c.items.dev);
-    if (items.dev) (void)hipFree(items.dev);
+  ~ns2vc_unet() {      // (the step tables and the pinned staging release themselves after this: ns2vc::StepTable, ns2vc::Staged)
     if (slots.list_dev) (void)hipFree(slots.list_dev);
     if (step_graph) (void)hipGraphExecDestroy(step_graph);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
@@ -439,7 +493,6 @@ std::vector<int> level_lengths(int T, int n_levels);
 int build_plan(ns2vc_unet* h, bool sizing);
 int run_ops(const std::vector<Op>& ops, hipStream_t s, size_t first = 0, size_t last = (size_t)-1);
 bool temb_forks(const ns2vc_unet* h, size_t last);
-void drop_step_graph(ns2vc_unet* h);
 void drop_plan(ns2vc_unet* h);
 // engine.cpp
 int check_ready(ns2vc_unet* h, bool need_plan);

@@ -593,11 +593,12 @@ __global__ void prompt_bias_kernel(const uint8_t* __restrict__ mask, const int* 
 //       to both halves, so the next evaluation is an ordinary 2n-item forward.  xbar, d1, mprev, mprev2 live in the first half only.
 //   TH: the x0 correction (ns2vc_sampler_set_x0_correction; common.h solver_correct).  0 = none; 1 = by the item's threshold max(cx.thr[b],
 //       cx.max_val), which the quantile kernel left there in the launch before; 2 = by cx.max_val alone.
-//   noise (run time, only with H2 = false and TH = 0 -- the launchers refuse the other pairs): a row with a nonzero column 9 adds knz * z to xbar'
+//   noise (run time, only with H2 = false and TH = 0 -- launch_solver_step refuses the other pairs): a row with a nonzero column 9 adds knz * z to xbar'
 //       on the live elements, z = Philox normals keyed by the item's seed and (frame, channel quad, jrow).  knz == 0 is no term at all (adding 0 * z
 //       would turn -0 into +0), so every noise-free table keeps its bits.
-// Three kernels loop over the quads: solver_update_kernel (TH = 0) and solver_update_th_kernel (TH = 1 | 2) take the row `step` of a table all
-// items share; solver_update_items_kernel gives every item the row of its own table (per-item schedules, below).
+// The host states a step once, as a SolverStep (common.h), and launch_solver_step picks the kernel: solver_update_kernel (TH = 0) and
+// solver_update_th_kernel (TH = 1 | 2) on the row `step` of a table all items share, solver_update_items_kernel on every item's own row,
+// solver_update_mixed_kernel on every item's own row and correction record.
 // Every form's quad is a straight line from its loads to its stores, and a kernel that runs two forms (the items kernel: H2 is a property of the
 // item) sweeps the quads once per form.  One sweep that branched per quad and joined the two forms' results in front of common stores was one ulp
 // off on x_e' (seen on the device): the optimiser moves the last subtraction of the two forms into the block where they join, away from its
@@ -702,7 +703,7 @@ __global__ __launch_bounds__(256) void solver_update_kernel(const float* __restr
     solver_quad<TM, H2, GD, 0>(kr, step, i, x0, xe, xe_op, xbar, d1, mprev, mprev2, n4, split, nz, gd, SolverCorrect(), GD ? gd.T : nz.T,
                                GD ? gd.ld : nz.ld, false);
 }
-// the corrected update: no noise term (the reference's discrete samplers have no correction, the launcher refuses the pair); items are cx.T rows
+// the corrected update: no noise term (the reference's discrete samplers have no correction, launch_solver_step refuses the pair); items are cx.T rows
 // of cx.ld columns, under GD those of ONE half
 template <typename TM, bool H2, bool GD, int TH>
 __global__ __launch_bounds__(256) void solver_update_th_kernel(const float* __restrict__ coef, const int* __restrict__ step_ptr, int ncoef,
@@ -1121,100 +1122,82 @@ template <int LO, int HI, typename F> static hipError_t with_int(int v, F&& f) {
   if constexpr (LO < HI) { if (v != LO) return with_int<LO + 1, HI>(v, f); }
   return f(std::integral_constant<int, LO>{});
 }
-hipError_t launch_solver_update(const float* coef, const int* step_ptr, int ncoef, const float* x0, float* xe, void* xe_op, int prec,
-                                float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise, float* mprev2,
-                                const SolverGuide& guide, const SolverCorrect& cx) {
-  if ((n & 3) || (split && (prec == PREC_F32 || (split & 3) || n % (size_t)split))) return hipErrorInvalidValue;
-  if (noise.seeds && (noise.ld <= 0 || (noise.ld & 3) || noise.T <= 0 || noise.nc > noise.ld || n % ((size_t)noise.ld * noise.T))) return hipErrorInvalidValue;
-  if (mprev2 && (noise.seeds || ncoef < 12)) return hipErrorInvalidValue;
-  // guided (n = the elements of ONE half): whole items of T rows of ld columns per half, refused rather than run unguided
-  if (guide.scale && (guide.T <= 0 || guide.ld <= 0 || (guide.ld & 3) || n == 0 || n % ((size_t)guide.T * guide.ld) || (split && split != guide.ld) ||
-                      (noise.seeds && (noise.T != guide.T || noise.ld != guide.ld))))
+hipError_t launch_abs_quantile(const QuantArgs& q, int n_items, float* thr, hipStream_t s, const SolverItem* items, const ItemCorrect* item_correct) {
+  const bool formed = q.xe != nullptr;
+  if (!q.v || !thr || n_items <= 0 || q.T <= 0 || q.ld <= 0 || (q.ld & 3) || q.nc <= 0 || q.nc > q.ld || (size_t)q.T * (size_t)q.ld > 0x7FFFFFFFull ||
+      (((uintptr_t)q.v | (uintptr_t)q.xe) & 15) || (!item_correct && !(q.p >= 0.f && q.p <= 1.f)))
     return hipErrorInvalidValue;
-  // corrected: whole items of T rows of ld columns, a threshold table with mode 1, no noise term -- refused rather than run uncorrected
-  if (cx.mode && (cx.mode < 0 || cx.mode > 2 || noise.seeds || cx.T <= 0 || cx.ld <= 0 || (cx.ld & 3) || n == 0 || n % ((size_t)cx.T * cx.ld) ||
-                  (cx.mode == 1 && !cx.thr) || !(cx.max_val > 0.f) || !std::isfinite(cx.max_val) || (guide.scale && (guide.T != cx.T || guide.ld != cx.ld))))
+  if (formed && (!q.coef || !q.step_ptr || q.ncoef < 9)) return hipErrorInvalidValue;
+  if (q.scale && (!formed || q.half == 0 || (q.half & 3))) return hipErrorInvalidValue;
+  if ((items && !formed) || (item_correct && !items)) return hipErrorInvalidValue;      // (ready values have no table row; records go with rows)
+  if (!items)
+    return with_int<0, 2>(q.scale ? 2 : (formed ? 1 : 0), [&](auto src) {
+      hipLaunchKernelGGL(abs_quantile_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr);
+      return hipGetLastError();
+    });
+  return with_int<1, 2>(q.scale ? 2 : 1, [&](auto src) {
+    if (item_correct) hipLaunchKernelGGL(abs_quantile_mixed_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr, items, item_correct);
+    else hipLaunchKernelGGL(abs_quantile_items_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr, items);
+    return hipGetLastError();
+  });
+}
+hipError_t launch_solver_step(const SolverStep& st, hipStream_t s) {
+  const size_t n = st.n;
+  const int T = st.T, ld = st.ld, mode = st.mode;
+  if (!st.coef || !st.step_ptr || st.ncoef < 12 || !st.x0 || !st.xe || !st.xe_op || !st.xbar || !st.d1 || !st.mprev) return hipErrorInvalidValue;
+  if ((n & 3) || (st.split && (st.prec == PREC_F32 || (st.split & 3) || n % (size_t)st.split))) return hipErrorInvalidValue;
+  // a part that asks for a quad's item: whole items of T rows of ld columns, the operand pair split at ld
+  if ((st.scale || st.seeds || mode || st.items) && (T <= 0 || ld <= 0 || (ld & 3) || n == 0 || n % ((size_t)T * ld) || (st.split && st.split != ld)))
     return hipErrorInvalidValue;
+  if (st.seeds && (st.nc > ld || mode || (!st.items && st.mprev2))) return hipErrorInvalidValue;
+  if (mode && (mode < 0 || mode > 2 || st.item_correct || (mode == 1 && !st.thr) || !(st.max_val > 0.f) || !std::isfinite(st.max_val)))
+    return hipErrorInvalidValue;
+  if (st.items && n != (size_t)st.n_items * T * ld) return hipErrorInvalidValue;      // (records for every item of the launch)
+  if (st.item_correct && (!st.items || !st.thr)) return hipErrorInvalidValue;
+  // the kernels' arguments, from the one geometry; a part that is off keeps its empty struct
+  SolverNoise nz;
+  if (st.seeds) { nz.seeds = st.seeds; nz.lens = st.lens; nz.T = T; nz.ld = ld; nz.nc = st.nc; }
+  SolverGuide gd;
+  if (st.scale) { gd.scale = st.scale; gd.T = T; gd.ld = ld; }
+  SolverCorrect cx;
+  if (mode) { cx.mode = mode; cx.max_val = st.max_val; cx.T = T; cx.ld = ld; cx.thr = mode == 1 ? st.thr : nullptr; }
+  SolverItems si;
+  si.rec = st.items; si.T = T; si.ld = ld;
+  if (st.item_correct ? st.quant : mode == 1) {      // the item's |m| quantile over its valid frames and real channels, from the update's own operands
+    QuantArgs q;
+    q.v = st.x0; q.xe = st.xe; q.coef = st.coef; q.step_ptr = st.step_ptr; q.ncoef = st.ncoef; q.scale = st.scale; q.half = st.scale ? n : 0;
+    q.lens = st.lens; q.T = T; q.ld = ld; q.nc = st.nc;
+    if (!st.item_correct) q.p = st.ratio;
+    const hipError_t e = launch_abs_quantile(q, st.items ? st.n_items : (int)(n / ((size_t)T * ld)), st.thr, s, st.items, st.item_correct);
+    if (e != hipSuccess) return e;
+  }
   const size_t n4 = n >> 2;
-  const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  return with_flag(mprev2 != nullptr, [&](auto h2) { return with_flag(guide.scale != nullptr, [&](auto gd) {
-    constexpr bool H2 = decltype(h2)::value, GD = decltype(gd)::value;
-    if (cx.mode)
-      return with_int<1, 2>(cx.mode, [&](auto th) {
-        NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_th_kernel<TMX, H2, GD, decltype(th)::value>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef,
-                                               x0, xe, (TMX*)xe_op, xbar, d1, mprev, n4, split, mprev2, guide, cx));
+  const dim3 grid((unsigned)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048)), block(256);
+  return with_flag(st.scale != nullptr, [&](auto gdf) {
+    constexpr bool GD = decltype(gdf)::value;
+    if (st.item_correct) {
+      NS2VC_BY_PREC(st.prec, hipLaunchKernelGGL((solver_update_mixed_kernel<TMX, GD>), grid, block, 0, s, st.coef, st.step_ptr, st.ncoef, si, st.item_correct,
+                                                st.thr, st.x0, st.xe, (TMX*)st.xe_op, st.xbar, st.d1, st.mprev, n4, st.split, nz, st.mprev2, gd));
+      return hipGetLastError();
+    }
+    if (st.items)
+      return with_int<0, 2>(mode, [&](auto th) {
+        NS2VC_BY_PREC(st.prec, hipLaunchKernelGGL((solver_update_items_kernel<TMX, GD, decltype(th)::value>), grid, block, 0, s, st.coef, st.step_ptr, st.ncoef,
+                                                  si, st.x0, st.xe, (TMX*)st.xe_op, st.xbar, st.d1, st.mprev, n4, st.split, nz, st.mprev2, gd, cx));
         return hipGetLastError();
       });
-    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_kernel<TMX, H2, GD>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, x0, xe, (TMX*)xe_op,
-                                           xbar, d1, mprev, n4, split, noise, mprev2, guide));
-    return hipGetLastError();
-  }); });
-}
-hipError_t launch_abs_quantile(const QuantArgs& q, int n_items, float* thr, hipStream_t s) {
-  if (!q.v || !thr || n_items <= 0 || q.T <= 0 || q.ld <= 0 || (q.ld & 3) || q.nc <= 0 || q.nc > q.ld || !(q.p >= 0.f && q.p <= 1.f) ||
-      ((uintptr_t)q.v & 15) || (size_t)q.T * (size_t)q.ld > 0x7FFFFFFFull)
-    return hipErrorInvalidValue;
-  const bool formed = q.xe != nullptr;
-  if (formed && (!q.coef || !q.step_ptr || q.ncoef < 9 || ((uintptr_t)q.xe & 15))) return hipErrorInvalidValue;
-  if (q.scale && (!formed || q.half == 0 || (q.half & 3))) return hipErrorInvalidValue;
-  return with_int<0, 2>(q.scale ? 2 : (formed ? 1 : 0), [&](auto src) {
-    hipLaunchKernelGGL(abs_quantile_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr);
-    return hipGetLastError();
-  });
-}
-// the launches of a step under per-item schedules: whole items of si.T rows of si.ld columns, n = the elements of the n_items loop items (guided:
-// of one half), records for every one of them -- refused rather than run on the shared row
-hipError_t launch_solver_update_items(const float* coef, const int* step_ptr, int ncoef, const SolverItems& si, const float* x0, float* xe, void* xe_op,
-                                      int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s, int split, const SolverNoise& noise,
-                                      float* mprev2, const SolverGuide& guide, const SolverCorrect& cx) {
-  if (!si.rec || si.T <= 0 || si.ld <= 0 || (si.ld & 3) || n == 0 || n % ((size_t)si.T * si.ld) || ncoef < 12) return hipErrorInvalidValue;
-  if ((n & 3) || (split && (prec == PREC_F32 || split != si.ld))) return hipErrorInvalidValue;
-  if (noise.seeds && (noise.ld != si.ld || noise.T != si.T || noise.nc > noise.ld || cx.mode)) return hipErrorInvalidValue;
-  if (guide.scale && (guide.T != si.T || guide.ld != si.ld)) return hipErrorInvalidValue;
-  if (cx.mode && (cx.mode < 0 || cx.mode > 2 || cx.T != si.T || cx.ld != si.ld || (cx.mode == 1 && !cx.thr) || !(cx.max_val > 0.f) || !std::isfinite(cx.max_val)))
-    return hipErrorInvalidValue;
-  const size_t n4 = n >> 2;
-  const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  return with_flag(guide.scale != nullptr, [&](auto gd) { return with_int<0, 2>(cx.mode, [&](auto th) {
-    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_items_kernel<TMX, decltype(gd)::value, decltype(th)::value>), dim3(blocks), dim3(256), 0, s, coef,
-                                           step_ptr, ncoef, si, x0, xe, (TMX*)xe_op, xbar, d1, mprev, n4, split, noise, mprev2, guide, cx));
-    return hipGetLastError();
-  }); });
-}
-hipError_t launch_abs_quantile_items(const QuantArgs& q, const SolverItem* items, int n_items, float* thr, hipStream_t s) {
-  if (!items || !q.v || !q.xe || !q.coef || !q.step_ptr || q.ncoef < 9 || !thr || n_items <= 0 || q.T <= 0 || q.ld <= 0 || (q.ld & 3) || q.nc <= 0 || q.nc > q.ld ||
-      !(q.p >= 0.f && q.p <= 1.f) || (((uintptr_t)q.v | (uintptr_t)q.xe) & 15) || (size_t)q.T * (size_t)q.ld > 0x7FFFFFFFull || (q.scale && (q.half == 0 || (q.half & 3))))
-    return hipErrorInvalidValue;
-  return with_int<1, 2>(q.scale ? 2 : 1, [&](auto src) {
-    hipLaunchKernelGGL(abs_quantile_items_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr, items);
-    return hipGetLastError();
-  });
-}
-// the same two launches under a per-item x0 correction: cr = DEVICE [items] records the HOST has validated (mode 0 .. 2, ratio in [0, 1], max_val
-// finite and > 0, mode 0 on every stochastic item), thr = DEVICE [items] -- refused rather than run uncorrected
-hipError_t launch_solver_update_mixed(const float* coef, const int* step_ptr, int ncoef, const SolverItems& si, const ItemCorrect* cr, const float* thr,
-                                      const float* x0, float* xe, void* xe_op, int prec, float* xbar, float* d1, float* mprev, size_t n, hipStream_t s,
-                                      int split, const SolverNoise& noise, float* mprev2, const SolverGuide& guide) {
-  if (!cr || !thr) return hipErrorInvalidValue;
-  if (!si.rec || si.T <= 0 || si.ld <= 0 || (si.ld & 3) || n == 0 || n % ((size_t)si.T * si.ld) || ncoef < 12) return hipErrorInvalidValue;
-  if ((n & 3) || (split && (prec == PREC_F32 || split != si.ld))) return hipErrorInvalidValue;
-  if (noise.seeds && (noise.ld != si.ld || noise.T != si.T || noise.nc > noise.ld)) return hipErrorInvalidValue;
-  if (guide.scale && (guide.T != si.T || guide.ld != si.ld)) return hipErrorInvalidValue;
-  const size_t n4 = n >> 2;
-  const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  return with_flag(guide.scale != nullptr, [&](auto gd) {
-    NS2VC_BY_PREC(prec, hipLaunchKernelGGL((solver_update_mixed_kernel<TMX, decltype(gd)::value>), dim3(blocks), dim3(256), 0, s, coef, step_ptr, ncoef, si, cr,
-                                           thr, x0, xe, (TMX*)xe_op, xbar, d1, mprev, n4, split, noise, mprev2, guide));
-    return hipGetLastError();
-  });
-}
-hipError_t launch_abs_quantile_mixed(const QuantArgs& q, const SolverItem* items, const ItemCorrect* cr, int n_items, float* thr, hipStream_t s) {
-  if (!cr || !items || !q.v || !q.xe || !q.coef || !q.step_ptr || q.ncoef < 9 || !thr || n_items <= 0 || q.T <= 0 || q.ld <= 0 || (q.ld & 3) || q.nc <= 0 ||
-      q.nc > q.ld || (((uintptr_t)q.v | (uintptr_t)q.xe) & 15) || (size_t)q.T * (size_t)q.ld > 0x7FFFFFFFull || (q.scale && (q.half == 0 || (q.half & 3))))
-    return hipErrorInvalidValue;
-  return with_int<1, 2>(q.scale ? 2 : 1, [&](auto src) {
-    hipLaunchKernelGGL(abs_quantile_mixed_kernel<decltype(src)::value>, dim3(n_items), dim3(1024), 0, s, q, thr, items, cr);
-    return hipGetLastError();
+    return with_flag(st.mprev2 != nullptr, [&](auto h2f) {
+      constexpr bool H2 = decltype(h2f)::value;
+      if (mode)
+        return with_int<1, 2>(mode, [&](auto th) {
+          NS2VC_BY_PREC(st.prec, hipLaunchKernelGGL((solver_update_th_kernel<TMX, H2, GD, decltype(th)::value>), grid, block, 0, s, st.coef, st.step_ptr,
+                                                    st.ncoef, st.x0, st.xe, (TMX*)st.xe_op, st.xbar, st.d1, st.mprev, n4, st.split, st.mprev2, gd, cx));
+          return hipGetLastError();
+        });
+      NS2VC_BY_PREC(st.prec, hipLaunchKernelGGL((solver_update_kernel<TMX, H2, GD>), grid, block, 0, s, st.coef, st.step_ptr, st.ncoef, st.x0, st.xe,
+                                                (TMX*)st.xe_op, st.xbar, st.d1, st.mprev, n4, st.split, nz, st.mprev2, gd));
+      return hipGetLastError();
+    });
   });
 }
 hipError_t launch_emb_items_from_table(const float* table, const int* step_ptr, const SolverItem* items, int n_items, const float* aug, float* emb,

@@ -26,17 +26,13 @@ bool ns2vc::solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
   return gemm_uses_convts(g, h->conv_out_prec);
 }
 
-// Per-item x0 correction against per-item records: a stochastic item (SOLVER_ITEM_NOISE) has no correction, as in the reference, so a record with
-// mode != 0 on such an item is refused -- per item, the two may share a loop.  rec = the n records about to hold (the table off: nothing to check).
-static int item_corrections_fit(ns2vc_unet* h, const SolverItem* rec, int n) {
+// Per-item x0 correction against per-item records, per item: a corrected record on a stochastic one is refused, the two may share a loop.
+// rec = the n records about to hold, of a table of n_rows rows (the correction table off: nothing to check).
+static int item_corrections_fit(ns2vc_unet* h, const SolverItem* rec, int n, int n_rows) {
   const auto& ic = h->x0c.items;
   if (!ic.on || !rec) return 0;
   if (ic.n != n) return fail("the per-item x0 correction holds %d records, the loop takes %d items: set it again (ns2vc_sampler_set_x0_correction_items)", ic.n, n);
-  for (int b = 0; b < n; ++b)
-    if ((rec[b].flags & SOLVER_ITEM_NOISE) && ic.host[(size_t)b].mode != 0)
-      return fail("item %d is stochastic and its x0 correction record has mode %d: ddim / ddpm have no correction (set the item's mode to 0)", b,
-                  ic.host[(size_t)b].mode);
-  return 0;
+  return solver_items_fit("item", rec, nullptr, n, n_rows, nullptr, nullptr, nullptr, 0, ic.host.data());
 }
 
 extern "C" {
@@ -106,23 +102,14 @@ int ns2vc_sampler_load_items(ns2vc_unet* h, int n_tables, const int32_t* table_r
     any_noise |= (flags[k] & SOLVER_ITEM_NOISE) != 0;
     any_h2 |= (flags[k] & SOLVER_ITEM_HIST2) != 0;
   }
-  if (item_corrections_fit(h, rec.data(), n_items)) return 1;
+  if (item_corrections_fit(h, rec.data(), n_items, (int)rows)) return 1;
   hipStream_t s = (hipStream_t)stream;
   if (!h->coef_dev) HIPCHK(hipMalloc((void**)&h->coef_dev, (size_t)kMaxRows * NS2VC_NCOEF * sizeof(float)));
-  if (!h->items.dev || h->items.cap < n_items) {      // a new records buffer invalidates the captured step graph (its launches hold the pointer)
-    drop_step_graph(h);
-    if (h->items.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->items.dev)); h->items.dev = nullptr; h->items.cap = 0; }
-    HIPCHK(hipMalloc((void**)&h->items.dev, (size_t)n_items * sizeof(SolverItem)));
-    h->items.cap = n_items;
-  }
+  if (h->items.reserve(h, (size_t)n_items, false)) return 1;
   HIPCHK(hipDeviceSynchronize());   // a previous loop may still be reading the table
   HIPCHK(hipMemcpy(h->coef_dev, coef_host, (size_t)rows * NS2VC_NCOEF * sizeof(float), hipMemcpyHostToDevice));
-  Staged& st = h->items.stage;
+  if (h->items.send(rec.data(), (size_t)n_items, s)) return 1;
   const size_t nb = (size_t)n_items * sizeof(SolverItem);
-  if (st.reserve(nb)) return 1;
-  memcpy(st.buf, rec.data(), nb);
-  HIPCHK(hipMemcpyAsync(h->items.dev, st.buf, nb, hipMemcpyHostToDevice, s));
-  if (st.record(s)) return 1;
   {      // the hand-off's table hash covers the rows and the records
     unsigned long long hsh = 1469598103934665603ull;
     const unsigned char* pb = reinterpret_cast<const unsigned char*>(coef_host);
@@ -145,56 +132,19 @@ int ns2vc_sampler_load_items(ns2vc_unet* h, int n_tables, const int32_t* table_r
   return 0;
 }
 
-// the m_{i-2} buffer of history-2 tables for the prepared shape; a new one invalidates the captured step graph (its update reads the old pointer)
-static int ensure_mprev2(ns2vc_unet* h) {
-  const size_t n = (size_t)h->B * h->T * h->CP;
-  if (h->hist2.mprev2 && h->hist2.n >= n) return 0;
-  drop_step_graph(h);
-  if (h->hist2.mprev2) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->hist2.mprev2)); h->hist2.mprev2 = nullptr; h->hist2.n = 0; }
-  HIPCHK(hipMalloc((void**)&h->hist2.mprev2, n * sizeof(float)));
-  h->hist2.n = n;
-  return 0;
-}
-
-// a seeds buffer for at least n items; a new one invalidates the captured step graph (its update reads the old pointer)
-static int ensure_seeds(ns2vc_unet* h, int n) {
-  if (h->seeds.dev && h->seeds.cap >= n) return 0;
-  drop_step_graph(h);
-  if (h->seeds.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->seeds.dev)); h->seeds.dev = nullptr; h->seeds.cap = 0; }
-  const int cap = (n + 1) & ~1;            // 16-byte multiple (launch_copy16)
-  HIPCHK(hipMalloc((void**)&h->seeds.dev, (size_t)cap * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(h->seeds.dev, 0, (size_t)cap * sizeof(unsigned long long)));
-  h->seeds.cap = cap;
-  return 0;
-}
+// the m_{i-2} buffer of history-2 tables for the prepared shape
+static int ensure_mprev2(ns2vc_unet* h) { return h->hist2.reserve(h, (size_t)h->B * h->T * h->CP, false); }
 
 int ns2vc_sampler_set_seeds(ns2vc_unet* h, const uint64_t* seeds_b, void* stream) {
   if (check_ready(h, true)) return 1;
   if (!seeds_b) return fail("null seeds");
   hipStream_t s = (hipStream_t)stream;
   const int B = h->loop_items();      // (guided: n seeds, both halves get the same noise)
-  if (ensure_seeds(h, B)) return 1;
-  Staged& st = h->seeds.stage;
-  const size_t nb = (size_t)B * sizeof(uint64_t);
-  if (st.reserve(nb)) return 1;
-  memcpy(st.buf, seeds_b, nb);
-  HIPCHK(hipMemcpyAsync(h->seeds.dev, st.buf, nb, hipMemcpyHostToDevice, s));
-  if (st.record(s)) return 1;
+  if (h->seeds.reserve(h, (size_t)B, true) || h->seeds.send(reinterpret_cast<const unsigned long long*>(seeds_b), (size_t)B, s)) return 1;
   h->seeds.set = true;
   return 0;
 }
 
-// a scale buffer for at least n items; a new one invalidates the captured step graph (its update reads the old pointer)
-static int ensure_scales(ns2vc_unet* h, int n) {
-  if (h->guide.dev && h->guide.cap >= n) return 0;
-  drop_step_graph(h);
-  if (h->guide.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->guide.dev)); h->guide.dev = nullptr; h->guide.cap = 0; }
-  const int cap = (n + 3) & ~3;            // 16-byte multiple (launch_copy16)
-  HIPCHK(hipMalloc((void**)&h->guide.dev, (size_t)cap * sizeof(float)));
-  HIPCHK(hipMemset(h->guide.dev, 0, (size_t)cap * sizeof(float)));
-  h->guide.cap = cap;
-  return 0;
-}
 static int guidance_onoff(ns2vc_unet* h, bool on, int n) {
   if (on != h->guide.on) {
     drop_step_graph(h);      // (the step graph bakes in which update runs)
@@ -214,34 +164,19 @@ int ns2vc_sampler_set_guidance(ns2vc_unet* h, const float* scale_host, int n, vo
   for (int b = 0; b < n; ++b)
     if (!std::isfinite(scale_host[b])) return fail("guidance scale[%d] is not finite", b);
   hipStream_t s = (hipStream_t)stream;
-  if (ensure_scales(h, n)) return 1;
-  Staged& st = h->guide.stage;
-  const size_t nb = (size_t)n * sizeof(float);
-  if (st.reserve(nb)) return 1;
-  memcpy(st.buf, scale_host, nb);
-  HIPCHK(hipMemcpyAsync(h->guide.dev, st.buf, nb, hipMemcpyHostToDevice, s));
-  if (st.record(s)) return 1;
+  if (h->guide.reserve(h, (size_t)n, true) || h->guide.send(scale_host, (size_t)n, s)) return 1;
   return guidance_onoff(h, true, n);
 }
 
-// the threshold buffer of the dynamic thresholding for at least n items; a new one invalidates the captured step graph (its launches hold the pointer)
-static int ensure_thr(ns2vc_unet* h, int n) {
-  if (h->x0c.thr && h->x0c.cap >= n) return 0;
-  drop_step_graph(h);
-  if (h->x0c.thr) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->x0c.thr)); h->x0c.thr = nullptr; h->x0c.cap = 0; }
-  const int cap = (n + 3) & ~3;
-  HIPCHK(hipMalloc((void**)&h->x0c.thr, (size_t)cap * sizeof(float)));
-  HIPCHK(hipMemset(h->x0c.thr, 0, (size_t)cap * sizeof(float)));
-  h->x0c.cap = cap;
-  return 0;
-}
+// the threshold buffer of the dynamic thresholding: one float per batch item
+static int ensure_thr(ns2vc_unet* h) { return h->x0c.thr.reserve(h, (size_t)h->B, true); }
 static int x0_correction_set(ns2vc_unet* h, int mode, float ratio, float max_val) {
   // the step graph bakes in what the active mode passes to its launches: mode 1 the ratio (quantile launch) and max_val (update), mode 2 max_val alone,
   // mode 0 nothing -- a change of a value no launch takes recaptures nothing
   const bool same = mode == h->x0c.mode && (mode == 0 || (max_val == h->x0c.max_val && (mode == 2 || ratio == h->x0c.ratio)));
   if (!same) drop_step_graph(h);
   h->x0c.mode = mode; h->x0c.ratio = ratio; h->x0c.max_val = max_val;
-  if (mode == 1 && h->B > 0 && ensure_thr(h, h->B)) return 1;
+  if (mode == 1 && h->B > 0 && ensure_thr(h)) return 1;
   return 0;
 }
 
@@ -272,36 +207,16 @@ int ns2vc_sampler_set_x0_correction_items(ns2vc_unet* h, const int32_t* mode_hos
                 "ns2vc_sampler_set_x0_correction_items", h->x0c.mode);
   if (n != h->loop_items())
     return fail("per-item x0 correction for %d items, the loop takes %d (the prepared batch; n under guidance: set the guidance first)", n, h->loop_items());
-  std::vector<ItemCorrect> rec((size_t)n);
+  std::vector<ItemCorrect> rec;
   bool dyn = false;
-  for (int b = 0; b < n; ++b) {
-    if (mode_host[b] < 0 || mode_host[b] > 2) return fail("item %d: x0 correction mode %d: 0 (off), 1 (dynamic thresholding) or 2 (clamp)", b, (int)mode_host[b]);
-    if (!(ratio_host[b] >= 0.f && ratio_host[b] <= 1.f)) return fail("item %d: dynamic thresholding ratio %g outside [0, 1]", b, (double)ratio_host[b]);
-    if (!(std::isfinite(max_val_host[b]) && max_val_host[b] > 0.f)) return fail("item %d: thresholding max_val %g must be finite and > 0", b, (double)max_val_host[b]);
-    rec[(size_t)b] = ItemCorrect{(int)mode_host[b], ratio_host[b], max_val_host[b], 0};
-    dyn |= mode_host[b] == 1;
-  }
+  if (item_corrections_from(mode_host, ratio_host, max_val_host, n, rec, dyn)) return 1;
   const bool slot_loop = h->in_slot_loop();
   // a slot loop's admitted items are checked here (nothing looks at them again; an idle slot has no flags); closed schedules are checked when they
   // load and when the loop begins, so the table and the schedules of a new batch may arrive in either order
-  if (slot_loop && (int)h->slots.rec.size() == n)
-    for (int b = 0; b < n; ++b)
-      if ((h->slots.rec[(size_t)b].flags & SOLVER_ITEM_NOISE) && rec[(size_t)b].mode != 0)
-        return fail("slot %d holds a stochastic item and its x0 correction record has mode %d: ddim / ddpm have no correction (set the slot's mode to 0)", b,
-                    rec[(size_t)b].mode);
-  hipStream_t s = (hipStream_t)stream;
-  if (!ic.dev || ic.cap < n) {      // a new records buffer invalidates the captured step graph (its launches hold the pointer)
-    drop_step_graph(h);
-    if (ic.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(ic.dev)); ic.dev = nullptr; ic.cap = 0; }
-    HIPCHK(hipMalloc((void**)&ic.dev, (size_t)n * sizeof(ItemCorrect)));
-    ic.cap = n;
-  }
-  if (ensure_thr(h, h->B)) return 1;
-  const size_t nb = (size_t)n * sizeof(ItemCorrect);
-  if (ic.stage.reserve(nb)) return 1;
-  memcpy(ic.stage.buf, rec.data(), nb);
-  HIPCHK(hipMemcpyAsync(ic.dev, ic.stage.buf, nb, hipMemcpyHostToDevice, s));
-  if (ic.stage.record(s)) return 1;
+  if (slot_loop && (int)h->slots.rec.size() == n &&
+      solver_items_fit("slot", h->slots.rec.data(), nullptr, n, h->items.rows, nullptr, nullptr, nullptr, 0, rec.data()))
+    return 1;
+  if (ic.reserve(h, (size_t)n, false) || ensure_thr(h) || ic.send(rec.data(), (size_t)n, (hipStream_t)stream)) return 1;
   const bool quant = dyn || slot_loop;      // (a slot loop always has the launch: its admissions bring records the host cannot foresee)
   if (!ic.on || quant != ic.quant) drop_step_graph(h);
   ic.on = true; ic.quant = quant; ic.n = n;
@@ -335,52 +250,25 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
     HIPCHK(launch_gemm(g, h->conv_out_prec, s));
     return 0;
   }
-  const size_t n = (size_t)h->loop_items() * h->T * h->CP;      // (guided: the elements of one half)
-  SolverGuide gd;
-  if (h->guide.on) { gd.scale = h->guide.dev; gd.T = h->T; gd.ld = h->CP; }
-  SolverNoise nz;
-  if (h->stochastic) {       // noise on the item's valid frames and real channels only (masked plan: level-0 lengths = the first B entries)
-    nz.seeds = h->seeds.dev; nz.lens = h->lens.masked ? h->lens.dev : nullptr; nz.T = h->T; nz.ld = h->CP; nz.nc = h->cfg.latent_channels;
-  }
   if (h->items.on && h->items.n != h->loop_items())
     return fail("per-item schedules for %d items, the loop has %d (load them again)", h->items.n, h->loop_items());
-  if (h->x0c.items.on) {     // per-item x0 correction: every item's own record (misc.hip abs_quantile_mixed_kernel, solver_update_mixed_kernel)
-    const auto& ic = h->x0c.items;
-    if (!h->items.on) return fail("the per-item x0 correction runs on per-item records: load them (ns2vc_sampler_load_items) or open a slot loop");
-    if (ic.n != h->loop_items()) return fail("the per-item x0 correction holds %d records, the loop has %d items (set it again)", ic.n, h->loop_items());
-    if (ic.quant) {
-      QuantArgs q;
-      q.v = h->x0; q.xe = h->xe; q.coef = h->coef_dev; q.step_ptr = h->step_dev; q.ncoef = NS2VC_NCOEF; q.scale = gd.scale; q.half = gd.scale ? n : 0;
-      q.lens = h->lens.masked ? h->lens.dev : nullptr; q.T = h->T; q.ld = h->CP; q.nc = h->cfg.latent_channels;
-      HIPCHK(launch_abs_quantile_mixed(q, h->items.dev, ic.dev, ic.n, h->x0c.thr, s));
-    }
-    SolverItems si;
-    si.rec = h->items.dev; si.T = h->T; si.ld = h->CP;
-    HIPCHK(launch_solver_update_mixed(h->coef_dev, h->step_dev, NS2VC_NCOEF, si, ic.dev, h->x0c.thr, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev,
-                                      n, s, h->pair_off(), nz, h->hist2.on ? h->hist2.mprev2 : nullptr, gd));
-    return 0;
-  }
-  SolverCorrect cx;
-  if (h->x0c.mode) {         // (not with a stochastic table: ns2vc_sampler_begin refuses the pair)
-    cx.mode = h->x0c.mode; cx.max_val = h->x0c.max_val; cx.T = h->T; cx.ld = h->CP;
-    if (h->x0c.mode == 1) {  // the item's |m| quantile over its valid frames and real channels, from the update's own operands
-      QuantArgs q;
-      q.v = h->x0; q.xe = h->xe; q.coef = h->coef_dev; q.step_ptr = h->step_dev; q.ncoef = NS2VC_NCOEF; q.scale = gd.scale; q.half = gd.scale ? n : 0;
-      q.lens = h->lens.masked ? h->lens.dev : nullptr; q.T = h->T; q.ld = h->CP; q.nc = h->cfg.latent_channels; q.p = h->x0c.ratio;
-      if (h->items.on) HIPCHK(launch_abs_quantile_items(q, h->items.dev, h->items.n, h->x0c.thr, s));
-      else HIPCHK(launch_abs_quantile(q, h->loop_items(), h->x0c.thr, s));
-      cx.thr = h->x0c.thr;
-    }
-  }
-  if (h->items.on) {         // per-item schedules: every item its own row, held items left alone (misc.hip solver_update_items_kernel)
-    SolverItems si;
-    si.rec = h->items.dev; si.T = h->T; si.ld = h->CP;
-    HIPCHK(launch_solver_update_items(h->coef_dev, h->step_dev, NS2VC_NCOEF, si, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s,
-                                      h->pair_off(), nz, h->hist2.on ? h->hist2.mprev2 : nullptr, gd, cx));
-    return 0;
-  }
-  HIPCHK(launch_solver_update(h->coef_dev, h->step_dev, NS2VC_NCOEF, h->x0, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev, n, s, h->pair_off(), nz,
-                              h->hist2.on ? h->hist2.mprev2 : nullptr, gd, cx));
+  const auto& ic = h->x0c.items;
+  if (ic.on && !h->items.on) return fail("the per-item x0 correction runs on per-item records: load them (ns2vc_sampler_load_items) or open a slot loop");
+  if (ic.on && ic.n != h->loop_items()) return fail("the per-item x0 correction holds %d records, the loop has %d items (set it again)", ic.n, h->loop_items());
+  SolverStep st;
+  st.coef = h->coef_dev; st.step_ptr = h->step_dev; st.ncoef = NS2VC_NCOEF;
+  st.x0 = h->x0; st.xe = h->xe; st.xe_op = h->xe_op; st.prec = h->prec; st.xbar = h->xbar; st.d1 = h->d1; st.mprev = h->mprev;
+  if (h->hist2.on) st.mprev2 = h->hist2.dev;
+  st.n = (size_t)h->loop_items() * h->T * h->CP;      // (guided: the elements of one half)
+  st.T = h->T; st.ld = h->CP; st.nc = h->cfg.latent_channels; st.split = h->pair_off();
+  if (h->lens.masked) st.lens = h->lens.dev;      // the item's valid frames (level-0 lengths = the first B entries): what the noise and the quantile cover
+  if (h->guide.on) st.scale = h->guide.dev;
+  if (h->stochastic) st.seeds = h->seeds.dev;
+  if (h->items.on) { st.items = h->items.dev; st.n_items = h->items.n; }
+  if (ic.on) { st.item_correct = ic.dev; st.quant = ic.quant; }
+  else { st.mode = h->x0c.mode; st.ratio = h->x0c.ratio; st.max_val = h->x0c.max_val; }      // (not with a stochastic table: ns2vc_sampler_begin refuses the pair)
+  st.thr = h->x0c.thr.dev;
+  HIPCHK(launch_solver_step(st, s));
   return 0;
 }
 
@@ -400,13 +288,13 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   if (h->stochastic && h->x0c.mode)
     return fail("the x0 correction (mode %d) does not apply to a stochastic table (ddpm, ddim with eta > 0): the reference's discrete samplers have none; "
                 "turn it off (ns2vc_sampler_set_x0_correction) or load a noise-free table", h->x0c.mode);
-  if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
+  if (h->x0c.mode == 1 && ensure_thr(h)) return 1;
   if (h->x0c.items.on) {
     if (!h->items.on)
       return fail("the per-item x0 correction (ns2vc_sampler_set_x0_correction_items) reads per-item records and this is a shared table (ns2vc_sampler_load): "
                   "load the schedules with ns2vc_sampler_load_items, or switch the table off");
-    if (item_corrections_fit(h, h->items.host.data(), h->items.n)) return 1;
-    if (ensure_thr(h, h->B)) return 1;
+    if (item_corrections_fit(h, h->items.host.data(), h->items.n, h->items.rows)) return 1;
+    if (ensure_thr(h)) return 1;
   }
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)h->B * h->T * h->CP;
@@ -431,7 +319,7 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   HIPCHK(launch_zero(h->mprev, n * sizeof(float), s));
   if (h->hist2.on) {
     if (ensure_mprev2(h)) return 1;
-    HIPCHK(launch_zero(h->hist2.mprev2, n * sizeof(float), s));
+    HIPCHK(launch_zero(h->hist2.dev, n * sizeof(float), s));
   }
   HIPCHK(launch_fill_i32(h->step_dev, -1, s));      // the first launch of every step advances it (gn_stats.clear)
   h->next_step = 0;
@@ -443,10 +331,10 @@ int ns2vc_sampler_steps(ns2vc_unet* h, int n_steps, int use_graph, void* stream)
   const bool slot_loop = h->in_slot_loop();      // (no table length bounds a slot loop: S follows the admissions, idle steps are legal)
   if (!h->coef_dev || (h->steps <= 0 && !slot_loop)) return fail("no solver table loaded (call ns2vc_sampler_load)");
   if (h->next_step < 0) return fail("no sampling loop in progress (call ns2vc_sampler_begin or ns2vc_sampler_handoff)");
-  if (h->hist2.on && !h->hist2.mprev2) return fail("history-2 table without its m_prev2 buffer (begin the loop after loading the table)");
+  if (h->hist2.on && !h->hist2.dev) return fail("history-2 table without its m_prev2 buffer (begin the loop after loading the table)");
   if (h->stochastic && h->x0c.mode) return fail("the x0 correction does not apply to a stochastic table");
-  if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
-  if (h->x0c.items.on && (!h->items.on || ensure_thr(h, h->B)))
+  if (h->x0c.mode == 1 && ensure_thr(h)) return 1;
+  if (h->x0c.items.on && (!h->items.on || ensure_thr(h)))
     return h->items.on ? 1 : fail("the per-item x0 correction reads per-item records: load them with ns2vc_sampler_load_items");
   if (slot_loop) {
     if (n_steps < 0 || n_steps > SOLVER_ITEM_NEVER - 1 - h->next_step)
@@ -503,8 +391,8 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   const size_t n = (size_t)src->B * src->T * src->CP;
   const size_t nh = (size_t)src->loop_items() * src->T * src->CP;      // the histories' extent (guided: the first half)
   if (src->guide.on) {
-    if (ensure_scales(dst, src->guide.n)) return 1;
-    HIPCHK(launch_copy16(src->guide.dev, dst->guide.dev, (size_t)((src->guide.n + 3) & ~3) * sizeof(float), s));
+    if (dst->guide.reserve(dst, (size_t)src->guide.n, true)) return 1;
+    HIPCHK(launch_copy16(src->guide.dev, dst->guide.dev, dst->guide.rounded((size_t)src->guide.n) * sizeof(float), s));
   }
   guidance_onoff(dst, src->guide.on, src->guide.n);
   {      // (the tail corrects as the head does: the loop-wide setting, or the per-item table and its records)
@@ -516,13 +404,7 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
     }
     if (x0_correction_set(dst, src->x0c.mode, src->x0c.ratio, src->x0c.max_val)) return 1;
     if (sc.on) {
-      if (!dc.dev || dc.cap < sc.n) {
-        drop_step_graph(dst);
-        if (dc.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(dc.dev)); dc.dev = nullptr; dc.cap = 0; }
-        HIPCHK(hipMalloc((void**)&dc.dev, (size_t)sc.n * sizeof(ItemCorrect)));
-        dc.cap = sc.n;
-      }
-      if (ensure_thr(dst, dst->B)) return 1;
+      if (dc.reserve(dst, (size_t)sc.n, false) || ensure_thr(dst)) return 1;
       HIPCHK(launch_copy16(sc.dev, dc.dev, (size_t)sc.n * sizeof(ItemCorrect), s));
       if (!dc.on || dc.quant != sc.quant) drop_step_graph(dst);
       dc.on = true; dc.quant = sc.quant; dc.n = sc.n; dc.host = sc.host;
@@ -534,13 +416,13 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   HIPCHK(launch_copy16(src->mprev, dst->mprev, nh * sizeof(float), s));
   if (src->hist2.on) {          // (same table hash: dst->hist2.on too)
     if (ensure_mprev2(dst)) return 1;
-    HIPCHK(launch_copy16(src->hist2.mprev2, dst->hist2.mprev2, nh * sizeof(float), s));
+    HIPCHK(launch_copy16(src->hist2.dev, dst->hist2.dev, nh * sizeof(float), s));
   }
   HIPCHK(launch_cast_op(dst->xe, n, dst->xe_op, dst->prec, s, dst->pair_off()));
   if (src->seeds.set) {      // the tail continues the same noise stream
     const int ns = src->loop_items();
-    if (ensure_seeds(dst, ns)) return 1;
-    HIPCHK(launch_copy16(src->seeds.dev, dst->seeds.dev, (size_t)((ns + 1) & ~1) * sizeof(unsigned long long), s));
+    if (dst->seeds.reserve(dst, (size_t)ns, true)) return 1;
+    HIPCHK(launch_copy16(src->seeds.dev, dst->seeds.dev, dst->seeds.rounded((size_t)ns) * sizeof(unsigned long long), s));
     dst->seeds.set = true;
   }
   HIPCHK(launch_fill_i32(dst->step_dev, src->next_step - 1, s));
@@ -628,24 +510,19 @@ int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
   if (h->in_slot_loop() && sl.any_busy()) return fail("the slot loop is open and has busy slots: take them before opening again");
   const size_t tb = (size_t)kSlotRows * NS2VC_NCOEF * sizeof(float);
   if (!h->coef_dev) HIPCHK(hipMalloc((void**)&h->coef_dev, tb));
-  if (!h->items.dev || h->items.cap < n) {      // a new records buffer invalidates the captured step graph (its launches hold the pointer)
-    drop_step_graph(h);
-    if (h->items.dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(h->items.dev)); h->items.dev = nullptr; h->items.cap = 0; }
-    HIPCHK(hipMalloc((void**)&h->items.dev, (size_t)n * sizeof(SolverItem)));
-    h->items.cap = n;
-  }
+  if (h->items.reserve(h, (size_t)n, false)) return 1;
   if (!sl.list_dev || sl.cap < h->B) {      // the slot lists of every later call fit (B covers both halves of a guided engine): no call in mid-loop grows it
     if (sl.list_dev) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(sl.list_dev)); sl.list_dev = nullptr; sl.cap = 0; }
     HIPCHK(hipMalloc((void**)&sl.list_dev, (size_t)h->B * 5 * sizeof(int)));
     sl.cap = h->B;
   }
   if (h2 && ensure_mprev2(h)) return 1;
-  if (nz && ensure_seeds(h, n)) return 1;
-  if (h->x0c.mode == 1 && ensure_thr(h, h->B)) return 1;
+  if (nz && h->seeds.reserve(h, (size_t)n, true)) return 1;
+  if (h->x0c.mode == 1 && ensure_thr(h)) return 1;
   if (h->x0c.items.on) {      // the per-item x0 correction is baked in beside history 2 and noise: every slot off until its admission brings a record
     auto& ic = h->x0c.items;
     if (ic.n != n) return fail("the per-item x0 correction holds %d records, the slot loop has %d slots: set it again (ns2vc_sampler_set_x0_correction_items)", ic.n, n);
-    if (ensure_thr(h, h->B)) return 1;
+    if (ensure_thr(h)) return 1;
     if (!ic.quant) drop_step_graph(h);      // (a slot loop always runs the quantile launch: the host cannot foresee its admissions)
     ic.quant = true;
   }
@@ -659,7 +536,7 @@ int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
   HIPCHK(launch_zero(h->xbar, ne * sizeof(float), s));
   HIPCHK(launch_zero(h->d1, ne * sizeof(float), s));
   HIPCHK(launch_zero(h->mprev, ne * sizeof(float), s));
-  if (h2) HIPCHK(launch_zero(h->hist2.mprev2, ne * sizeof(float), s));
+  if (h2) HIPCHK(launch_zero(h->hist2.dev, ne * sizeof(float), s));
   {
     const auto& c = h->cfg;
     const size_t rows = (size_t)h->B * h->T;
@@ -677,15 +554,7 @@ int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
   h->items.host = sl.rec;
   sl.busy.assign((size_t)n, 0);
   sl.coef.assign((size_t)kSlotRows * NS2VC_NCOEF, 0.f);
-  {
-    Staged& st = sl.ring[sl.ring_next];
-    sl.ring_next = (sl.ring_next + 1) % ns2vc_unet::SlotLoop::kRing;
-    const size_t nb = (size_t)n * sizeof(SolverItem);
-    if (st.reserve(nb)) return 1;
-    memcpy(st.buf, sl.rec.data(), nb);
-    HIPCHK(hipMemcpyAsync(h->items.dev, st.buf, nb, hipMemcpyHostToDevice, s));
-    if (st.record(s)) return 1;
-  }
+  if (h->items.send(sl.rec.data(), (size_t)n, s)) return 1;
   if (nz) h->seeds.set = true;      // (the buffer holds finite seeds; ns2vc_sampler_set_seeds gives the slots theirs)
   h->items.on = true;
   h->items.n = n;
@@ -751,35 +620,34 @@ int ns2vc_sampler_admit(ns2vc_unet* h, int n, const int32_t* slots, const float*
   if (h->stochastic && !h->seeds.set) return fail("the slot loop takes stochastic items: set per-item seeds first (ns2vc_sampler_set_seeds)");
   if (!slots || n <= 0 || n > ni) return fail("a slot list needs 1 .. %d entries, got %d", ni, n);
   static_assert(sizeof(SolverItem) == 4 * sizeof(int32_t), "records are four 32-bit words");
-  std::vector<SolverItem> rec((size_t)n);
+  const SolverItem* rec = reinterpret_cast<const SolverItem*>(records);
   for (int k = 0; k < n; ++k) {
-    const int32_t* r = records + 4 * (size_t)k;
     const int b = slots[k];
     if (b < 0 || b >= ni) return fail("slots[%d] = %d outside [0, %d)", k, b, ni);
     if (sl.busy[b]) return fail("slot %d is busy (admitted at loop step %d for %d steps, not taken yet)", b, sl.rec[b].start, sl.rec[b].steps);
-    if (r[0] < 0 || r[1] <= 0 || r[0] > kSlotRows - r[1]) return fail("slot %d: rows %d + %d outside the table of %d rows", b, r[0], r[1], kSlotRows);
+  }
+  const auto& ic = h->x0c.items;
+  if (solver_items_fit("slot", rec, slots, n, kSlotRows, sl.coef.data(),
+                       h->hist2.on ? nullptr : "the slot loop was opened without it (ns2vc_sampler_open history2 = 1)",
+                       h->stochastic ? nullptr : "the slot loop was opened without noise (ns2vc_sampler_open noise = 1)", h->x0c.mode,
+                       ic.on && ic.n == ni ? ic.host.data() : nullptr))
+    return 1;
+  for (int k = 0; k < n; ++k) {      // what is the slot loop's own to say
+    const int32_t* r = records + 4 * (size_t)k;
+    const int b = slots[k];
     if (r[2] < h->next_step) return fail("slot %d: start %d lies in the past, the loop stands at step %d", b, r[2], h->next_step);
     if (r[2] > SOLVER_ITEM_NEVER - 1 - r[1])
       return fail("slot %d: loop steps %d + %d pass the end of the 32-bit step counter: drain the slots and call ns2vc_sampler_rebase", b, r[2], r[1]);
     for (int i = 0; i < r[1]; ++i)
       if (sl.coef[(size_t)(r[0] + i) * NS2VC_NCOEF + 1] == 0.f) return fail("slot %d: row %d of the table was never written (ns2vc_sampler_write_rows)", b, r[0] + i);
-    const int flags = solver_table_form(sl.coef.data() + (size_t)r[0] * NS2VC_NCOEF, r[1]);
-    if (flags != r[3]) return fail("slot %d: flags %d, its rows %d .. %d have the form %d (1 = history 2, 2 = noise)", b, r[3], r[0], r[0] + r[1] - 1, flags);
-    if (flags == SOLVER_ITEM_BOTH) return fail("slot %d: a table with both a noise column and history 2 is not supported", b);
-    if ((flags & SOLVER_ITEM_HIST2) && !h->hist2.on) return fail("slot %d runs history 2: the slot loop was opened without it (ns2vc_sampler_open history2 = 1)", b);
-    if ((flags & SOLVER_ITEM_NOISE) && !h->stochastic) return fail("slot %d is stochastic: the slot loop was opened without noise (ns2vc_sampler_open noise = 1)", b);
     if (h->guide.on && h->lens.masked && h->lens.applied[b] != h->lens.applied[b + ni]) return fail("guided slot loop: lengths[%d] and lengths[%d] differ", b, b + ni);
-    if ((flags & SOLVER_ITEM_NOISE) && h->x0c.items.on && h->x0c.items.n == ni && h->x0c.items.host[(size_t)b].mode != 0)
-      return fail("slot %d is stochastic and its x0 correction record has mode %d: ddim / ddpm have no correction (set the slot's mode to 0 before "
-                  "admitting it: ns2vc_sampler_set_x0_correction_items)", b, h->x0c.items.host[(size_t)b].mode);
-    rec[k] = SolverItem{r[0], r[1], r[2], r[3]};
   }
   hipStream_t s = (hipStream_t)stream;
   const int* slots_dev = nullptr;
   const SolverItem* rec_dev = nullptr;
-  if (stage_slot_list(h, n, slots, ni, rec.data(), s, &slots_dev, &rec_dev)) return 1;
+  if (stage_slot_list(h, n, slots, ni, rec, s, &slots_dev, &rec_dev)) return 1;
   HIPCHK(launch_sampler_admit(x_T_nct, h->cfg.latent_channels, h->T, n, slots_dev, ni, rec_dev, h->items.dev, h->xe, h->xe_op, h->prec, h->xbar, h->d1,
-                              h->mprev, h->hist2.on ? h->hist2.mprev2 : nullptr, h->CP, h->pair_off(), h->lens.masked ? h->lens.dev : nullptr,
+                              h->mprev, h->hist2.on ? h->hist2.dev : nullptr, h->CP, h->pair_off(), h->lens.masked ? h->lens.dev : nullptr,
                               h->guide.on ? ni : 0, s));
   for (int k = 0; k < n; ++k) {
     sl.rec[slots[k]] = rec[k];

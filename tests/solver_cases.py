@@ -1,6 +1,6 @@
 """Characterisation cases of the solver-update and quantile kernels (misc.hip): inputs from fixed numpy seeds, driven through the kernel hooks
-ns2vc_k_solver_update, _guided, _corrected, _items and ns2vc_k_abs_quantile of whichever library is handed in, every output array returned.
-tools/record_solver_bits.py hashes the arrays a PARENT library gives into tests/golden/solver_bits_v1.json; tests/test_solver_bits_gpu.py compares
+ns2vc_k_solver_update, _guided, _corrected, _items, _items_corrected and ns2vc_k_abs_quantile of whichever library is handed in, every output array returned.
+tools/record_solver_bits.py hashes the arrays a PARENT library gives into tests/golden/solver_bits_v2.json; tests/test_solver_bits_gpu.py compares
 the built library against that record.  Nothing here depends on the code under test but the hooks' signatures.
 
 CASES is the ordered list of case ids (no GPU needed to build it); run_case(lib, id) -> {array name: numpy array}."""
@@ -138,6 +138,42 @@ def _items(lib, case, prec, gd, mode, shape=(NI, T, LD), lens=LENS, items=None, 
     return _run(lib, st, np.full(ni, 0.25, np.float32), call)
 
 
+# ---- per-item x0 correction --------------------------------------------------------------------------------------------------------------
+# Per family member: the SolverItem records, the lengths, and per item (mode, ratio, max_val); loop step 4, the table of _items.  Across the three
+# every (history 2, mode) form has an active item with live elements:
+#   a: (H2 0, mode 1) | (H2 1, mode 2) | HELD in mode 1: thr keeps its 0.25 | (H2 1, mode 1) active with no elements: thr 0
+#   b: (H2 0, mode 2) | (H2 1, mode 1) | stochastic (row 17) in mode 0 beside the corrected ones | (H2 1, mode 0)
+#   c: (H2 0, mode 0) | (H2 1, mode 2) | (H2 0, mode 2) at row 0 | held, finished -- no record in mode 1: no quantile launch, thr untouched
+ITEM_CORRECT = {
+    "a": (np.array([[0, 6, 2, 0], [6, 10, 0, 1], [0, 6, 5, 0], [6, 10, 0, 1]], np.int32), LENS,
+          ((1, 0.9, 0.5), (2, 0.37, 0.8), (1, 0.5, 0.3), (1, 0.995, 1.0))),
+    "b": (np.array([[0, 6, 2, 0], [6, 10, 0, 1], [16, 4, 3, 2], [6, 10, 0, 1]], np.int32), np.array([7, 3, 2, 5], np.int32),
+          ((2, 0.9, 0.5), (1, 0.37, 0.8), (0, 0.5, 0.3), (0, 0.995, 1.0))),
+    "c": (np.array([[0, 6, 2, 0], [6, 10, 0, 1], [0, 6, 4, 0], [6, 4, 0, 1]], np.int32), LENS,
+          ((0, 0.9, 0.5), (2, 0.37, 0.8), (2, 0.5, 0.3), (0, 0.995, 1.0))),
+}
+
+
+def _items_corrected(lib, case, prec, gd, which):
+    rng = _rng(case)
+    n = NI * T * LD
+    coef = _table(rng, 20, hist2=range(6, 16), noise=range(16, 20))
+    st = _state(rng, n, gd)
+    items, lens, rec = ITEM_CORRECT[which]
+    noisy = bool((items[:, 3] & 2).any())
+    mode = np.array([r[0] for r in rec], np.int32)
+    ratio = np.array([r[1] for r in rec], np.float32)
+    max_val = np.array([r[2] for r in rec], np.float32)
+
+    def call(dev, p):
+        cf, sp = dev.put(coef), dev.put(np.array([ITEM_STEP, 0, 0, 0], np.int32))
+        return lib.ns2vc_k_solver_update_items_corrected(cf, coef.shape[0], sp, items.ctypes.data, NI, p["x0"], p["xe"], p["xe_op"], PRECS[prec], p["xbar"],
+                                                         p["d1"], p["mprev"], p["mprev2"], n, LD, T, dev.put(SCALES) if gd else None,
+                                                         dev.put(SEEDS) if noisy else None, dev.put(lens), NC, mode.ctypes.data, ratio.ctypes.data,
+                                                         max_val.ctypes.data, p["thr"], None)
+    return _run(lib, st, np.full(NI, 0.25, np.float32), call)
+
+
 # ---- quantile ----------------------------------------------------------------------------------------------------------------------------
 def _quant_values(rng):
     """four items of T x LD whose live elements (NC columns) make each branch of the select decide: 0 random normals (neighbours in rank differ in
@@ -227,6 +263,10 @@ def _build():
         cases[f"formed-items-gd{gd}"] = lambda lib, c, gd=gd: _formed(lib, c, gd, True)
     cases["stride-shared-f32"] = lambda lib, c: _shared(lib, c, "f32", 0, 0, 0, shape=BIG, lens=None)
     cases["stride-items-f32"] = lambda lib, c: _items(lib, c, "f32", 0, 0, shape=BIG, lens=None, items=BIG_ITEMS)
+    for prec in PRECS:
+        for gd in (0, 1):
+            for which in ITEM_CORRECT:
+                cases[f"itemcorr-{prec}-gd{gd}-{which}"] = lambda lib, c, a=(prec, gd, which): _items_corrected(lib, c, *a)
     return cases
 
 

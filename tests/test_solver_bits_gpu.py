@@ -1,4 +1,4 @@
-"""The solver-update and quantile kernels give the bits of the commit recorded in tests/golden/solver_bits_v1.json (tools/record_solver_bits.py ran
+"""The solver-update and quantile kernels give the bits of the commit recorded in tests/golden/solver_bits_v2.json (tools/record_solver_bits.py ran
 the cases of tests/solver_cases.py on that commit's library): every form, precision and branch of the family, by SHA-256 of every output array.
 The other GPU tests pin the forms to each other; a change that shifted all of them by the same ulp would pass those and fails here."""
 import json
@@ -9,7 +9,7 @@ import pytest
 import solver_cases
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solver_bits_v1.json")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solver_bits_v2.json")
 
 
 @pytest.fixture(scope="module")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Record what the solver-update and quantile kernels of a PARENT checkout compute on the cases of tests/solver_cases.py.
 
-    python tools/record_solver_bits.py --tree PARENT_CHECKOUT [--commit SHA] [--out tests/golden/solver_bits_v1.json]
+    python tools/record_solver_bits.py --tree PARENT_CHECKOUT [--commit SHA] [--out tests/golden/solver_bits_v2.json]
 
 Loads PARENT_CHECKOUT/ns2vc_amd/lib/libns2vc_hip.so through that tree's own binding (as tools/item_schedules_bench.py --tree does), building it
 with the tree's Makefile first when it is not there, runs every case and writes per case and array the shape, the dtype and the SHA-256 of the
@@ -20,7 +20,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", required=True, help="a checkout of the parent commit")
     ap.add_argument("--commit", default=None, help="the parent commit (default: git rev-parse HEAD in --tree)")
-    ap.add_argument("--out", default=os.path.join(HERE, "tests", "golden", "solver_bits_v1.json"))
+    ap.add_argument("--out", default=os.path.join(HERE, "tests", "golden", "solver_bits_v2.json"))
     a = ap.parse_args()
     tree = os.path.abspath(a.tree)
     if tree == HERE:
