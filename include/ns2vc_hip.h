@@ -278,6 +278,23 @@ int ns2vc_sampler_set_x0_correction(ns2vc_unet* h, int mode, float ratio, float 
  * mid-loop the call is a whole-vector copy under the rule for seeds and scales: change the entries of idle slots only.
  * fuse_solver is ignored under the table, ns2vc_unet_prepare leaves it alone, ns2vc_sampler_handoff carries it over to `dst`. */
 int ns2vc_sampler_set_x0_correction_items(ns2vc_unet* h, const int32_t* mode_host, const float* ratio_host, const float* max_val_host, int n, void* stream);
+/* Known frames (backward-compatible addition to ABI v7): per loop item b a set of frames K_b whose predicted x0 is a latent the
+ * caller supplies -- the fixed context of a chunked long utterance, or the part of an utterance that a partial re-synthesis keeps.  known_nct =
+ * DEVICE [n][latent_channels][T] fp32 (the whole tensor is read, on `stream`, into the engine's own rows; values off the mask are ignored), mask_nt = HOST [n][T] uint8 (nonzero = held), n = the loop items (n,
+ * not 2n, under guidance: set the guidance first).  At every evaluation, between the plan's last launch and the solver update, ONE launch writes
+ * x0[b, t, c] = known[b, c, t] for t in K_b and c < latent_channels and 0 for the pad columns of those rows, in both halves of a guided engine
+ * (the guided combination of two equal values is that value at every scale); every other row of x0 keeps every bit.  The update itself is
+ * unchanged and runs in fp32 on the fp32 x0 in every precision.  Every solver here is linear in the model value, so a held frame follows the
+ * forward marginal x_i = alpha_i k + sigma_i eps with the one eps of its start state; the caller forms x_T = alpha_0 k + sigma_0 noise there
+ * (ns2vc_amd.schedule.known_start).  The launch is sized by the held rows: their list and its count live in device memory beside the known rows,
+ * in buffers for the whole prepared shape, copied on `stream` from pinned staging -- new values and new masks replay the captured step graph,
+ * switching the hold on or off drops it.  NULL, NULL = off.  Refused: n other than the loop items; a held frame at or past the item's length
+ * (ns2vc_unet_set_lengths; set the lengths first, ns2vc_sampler_begin checks again); an x0 correction being on, in either form -- it would
+ * rescale the held frames -- and, the other way round, ns2vc_sampler_set_x0_correction (mode != 0) and ns2vc_sampler_set_x0_correction_items
+ * while a hold is on; a slot loop, and ns2vc_sampler_open while a hold is on.  ns2vc_sampler_handoff refuses two engines that disagree on
+ * whether a hold is set: set it on both.  The update never runs in conv_out's epilogue under a hold (fuse_solver is ignored);
+ * ns2vc_unet_prepare and a change of guidance on / off switch the hold off. */
+int ns2vc_sampler_set_known(ns2vc_unet* h, const float* known_nct, const uint8_t* mask_nt, int n, void* stream);
 /* x_e of a loop in progress (the point the next evaluation is taken at) without ending the loop: what a precision self-check
  * evaluates two engines on (ns2vc_amd.pipeline.Denoiser) */
 int ns2vc_sampler_peek(ns2vc_unet* h, float* x_out_bct, void* stream);
@@ -747,6 +764,12 @@ int ns2vc_unet_set_condition_items(ns2vc_unet* h, int n, const int32_t* slots, c
 int ns2vc_k_sampler_admit(const float* x_T, int C, int T, int n, const int32_t* slots_host, int n_items, float* xe, void* xe_op, int precision, float* xbar,
                           float* d1, float* mprev, float* mprev2, int ld, const int32_t* lens_dev, int guided, void* stream);
 int ns2vc_k_sampler_take(const float* xe, int ld, int C, int T, int n, const int32_t* slots_host, int n_items, float* out, void* stream);
+/* The hold launch of ns2vc_sampler_set_known on its own (backward-compatible addition to ABI v7; a test hook, waits for `stream`).  x0 = DEVICE
+ * fp32 rows [halves * n * T][ld], known_rows = DEVICE fp32 rows [n * T][ld] channels-last (ld % 4 == 0, both 16-byte aligned), mask_host = HOST
+ * [n][T] uint8.  Rows: row r = b * T + t with mask_host[b][t] != 0 is held, no other row is touched.  Columns: x0[r][c] = known_rows[r][c] bit for
+ * bit for c < nc; the pad columns nc <= c < ld of a held row are written as zero whatever known_rows holds there.  Halves: halves = 2 (a guided
+ * engine: n * T unconditional rows, then n * T conditional rows) writes the same values to rows r and r + n * T; halves = 1 to row r alone. */
+int ns2vc_k_hold_x0(float* x0, const float* known_rows, const uint8_t* mask_host, int n, int T, int ld, int nc, int halves, void* stream);
 
 #ifdef __cplusplus
 }

@@ -523,5 +523,28 @@ int ns2vc_k_sampler_take(const float* xe, int ld, int C, int T, int n, const int
 int ns2vc_k_noise(const uint64_t* seeds_dev, int B, int C, int T, int ld, int step, const int32_t* lens_dev, float* out, void* stream) {
   return launched(launch_noise(reinterpret_cast<const unsigned long long*>(seeds_dev), B, C, T, ld, step, lens_dev, out, (hipStream_t)stream), "noise launch");
 }
+// the hold launch of the loop on its own: the held-row list is built from the host mask as ns2vc_sampler_set_known builds it, lives on the device
+// for the one call, and the call returns when the launch is done
+int ns2vc_k_hold_x0(float* x0, const float* known_rows, const uint8_t* mask_host, int n, int T, int ld, int nc, int halves, void* stream) {
+  if (!x0 || !known_rows || !mask_host) return fail("null argument");
+  if (n <= 0 || T <= 0 || ld <= 0 || (ld & 3) || nc <= 0 || nc > ld || (halves != 1 && halves != 2) || (size_t)n * T > (size_t)0x7fffffff - HOLD_LIST_HEAD)
+    return fail("hold_x0: n (%d) and T (%d) positive, nc (%d) in 1 .. ld (%d), ld a multiple of 4, halves (%d) 1 or 2", n, T, nc, ld, halves);
+  std::vector<int> list;
+  std::vector<int32_t> last;
+  if (hold_list_from_mask(mask_host, n, T, nullptr, list, last)) return 1;
+  int* dev = nullptr;
+  const size_t nb = ((size_t)HOLD_LIST_HEAD + (size_t)n * T) * sizeof(int);
+  HIPCHK(hipMalloc((void**)&dev, nb));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if (hipMemset(dev, 0, nb) != hipSuccess || hipMemcpy(dev, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    rc = fail("hold_x0: copy of the row list failed");
+  } else {
+    rc = launched(launch_hold_x0(x0, known_rows, dev, n * T, ld, nc, halves, s), "hold_x0 launch");
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("hold_x0: stream synchronize failed");
+  }
+  (void)hipFree(dev);
+  return rc;
+}
 
 }  // extern "C"

@@ -460,6 +460,13 @@ struct SolverStep {
 };
 // validates, issues the quantile launch where the form has one, then the update -- refused rather than run unguided, uncorrected or on the shared row
 hipError_t launch_solver_step(const SolverStep& st, hipStream_t s);
+// Known frames (ns2vc_sampler_set_known): the rows of x0 the caller holds get the caller's latent in front of the solver step.
+// x0 = fp32 rows [halves * rows][ld], known = fp32 rows [rows][ld]; list = DEVICE ints, list[0] = the number of held rows and list[HOLD_LIST_HEAD + k]
+// the k-th of them, a row of ONE half in [0, rows).  Held row r: x0[r][c] = known[r][c] for c < nc and 0 for nc <= c < ld, in both halves where
+// halves == 2 (row r + rows); every other row keeps every bit.  The grid is sized by `rows`, the work by the count read on the device, so a captured
+// launch serves every later list; a count above `rows` is clamped and an entry outside [0, rows) skipped, never used as an index.
+constexpr int HOLD_LIST_HEAD = 4;
+hipError_t launch_hold_x0(float* x0, const float* known, const int* list, int rows, int ld, int nc, int halves, hipStream_t s);
 // the time embedding under per-item rows: a held item is evaluated at its clamped row; B engine rows read the n_items records B / n_items times
 hipError_t launch_emb_items_from_table(const float* table, const int* step_ptr, const SolverItem* items, int n_items, const float* aug, float* emb,
                                        void* emb_act_op, int prec, int B, int edim, hipStream_t s);

@@ -265,6 +265,9 @@ int ns2vc_unet_prepare(ns2vc_unet* h, int B, int T, int Lp) {
   h->seeds.set = false;      // ... and without noise seeds (ns2vc_sampler_set_seeds)
   h->guide.on = false;       // ... and unguided (ns2vc_sampler_set_guidance)
   h->guide.n = 0;
+  h->hold.on = false;        // ... and without known frames (ns2vc_sampler_set_known)
+  h->hold.n = 0;
+  h->hold.last.clear();
   h->plens.on = false;       // ... and with whole prompts (ns2vc_unet_set_prompt_lengths)
   h->plens.applied.clear();
   if (build_plan(h, true)) return 1;

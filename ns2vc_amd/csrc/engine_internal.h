@@ -87,6 +87,22 @@ inline int item_corrections_from(const int32_t* mode, const float* ratio, const 
   return 0;
 }
 
+// The held-row list of launch_hold_x0 from a HOST frame mask [n][T] (nonzero = held): list[0] = the count, the rows b * T + t behind the head in
+// ascending order; last[b] = item b's last held frame (-1: none).  lens (HOST [n], or NULL = all T): a held frame at or past lens[b] is refused.
+inline int hold_list_from_mask(const uint8_t* mask, int n, int T, const int32_t* lens, std::vector<int>& list, std::vector<int32_t>& last) {
+  list.assign((size_t)HOLD_LIST_HEAD, 0);
+  last.assign((size_t)n, -1);
+  for (int b = 0; b < n; ++b)
+    for (int t = 0; t < T; ++t) {
+      if (!mask[(size_t)b * T + t]) continue;
+      if (lens && t >= lens[b]) return fail("known frame %d of item %d lies at or past its length %d", t, b, (int)lens[b]);
+      list.push_back(b * T + t);
+      last[(size_t)b] = t;
+    }
+  list[0] = (int)list.size() - HOLD_LIST_HEAD;
+  return 0;
+}
+
 struct HostTensor {
   std::vector<float> data;
   std::vector<int64_t> shape;
@@ -432,6 +448,18 @@ struct ns2vc_unet {
       std::vector<ns2vc::ItemCorrect> host;
     } items;
   } x0c;
+
+  // Known frames (ns2vc_sampler_set_known): the rows of x0 that every step overwrites with the caller's latent in front of the
+  // solver update (launch_hold_x0).  The known rows, channels-last like x0, and the held-row list with its count live in buffers of their own
+  // outside the plan arena, allocated on first use for the whole prepared shape: new values and new masks are copies on the caller's stream and
+  // replay the captured step graph, on / off recaptures.  `last` mirrors each item's last held frame for the length check of ns2vc_sampler_begin.
+  struct Hold {
+    bool on = false;
+    int n = 0;                             // loop items the mask covered
+    ns2vc::StepTable<float> known;         // [n * T][CP]
+    ns2vc::StepTable<int> rows;            // [HOLD_LIST_HEAD + n * T]: the count, then the held rows of one half
+    std::vector<int32_t> last;
+  } hold;
 
   // named persistent buffers
   float *xe = nullptr, *xbar = nullptr, *d1 = nullptr, *mprev = nullptr, *x0 = nullptr;

@@ -1470,4 +1470,39 @@ hipError_t launch_condition_items(const float* content, int Cc, int T, const flo
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Known frames (ns2vc_sampler_set_known): common.h launch_hold_x0 states the rule.  One thread per channel quad of a held row; fp32 in,
+// fp32 out whatever the engine's precision, so it is no template.  A step without held rows costs the launch and one scalar load per workgroup.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hold_x0_kernel(float* __restrict__ x0, const float* __restrict__ known, const int* __restrict__ list, int rows,
+                                                      int ld, int nc, int halves) {
+  const int nq = ld >> 2;
+  const int count = min(max(list[0], 0), rows);
+  const size_t total = (size_t)count * nq;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t k = i / nq;
+    const int c = (int)(i - k * nq) * 4;
+    const int r = list[HOLD_LIST_HEAD + k];
+    if (r < 0 || r >= rows) continue;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < nc) {
+      v = *reinterpret_cast<const float4*>(known + (size_t)r * ld + c);
+      if (c + 1 >= nc) v.y = 0.f;
+      if (c + 2 >= nc) v.z = 0.f;
+      if (c + 3 >= nc) v.w = 0.f;
+    }
+    *reinterpret_cast<float4*>(x0 + (size_t)r * ld + c) = v;
+    if (halves == 2) *reinterpret_cast<float4*>(x0 + ((size_t)rows + r) * ld + c) = v;
+  }
+}
+hipError_t launch_hold_x0(float* x0, const float* known, const int* list, int rows, int ld, int nc, int halves, hipStream_t s) {
+  if (!x0 || !known || !list || rows <= 0 || ld <= 0 || (ld & 3) || nc <= 0 || nc > ld || (halves != 1 && halves != 2) ||
+      (((uintptr_t)x0 | (uintptr_t)known) & 15))
+    return hipErrorInvalidValue;
+  const size_t nth = (size_t)rows * (ld >> 2);
+  const unsigned blocks = (unsigned)std::min<size_t>((nth + 255) / 256, 512);
+  hipLaunchKernelGGL(hold_x0_kernel, dim3(blocks), dim3(256), 0, s, x0, known, list, rows, ld, nc, halves);
+  return hipGetLastError();
+}
+
 }  // namespace ns2vc

@@ -19,6 +19,7 @@ bool ns2vc::solver_in_conv_out(ns2vc_unet* h, GemmArgs& g) {
   if (h->stochastic) return false;                     // (the epilogue has no noise term: a stochastic table runs the stand-alone update)
   if (h->hist2.on) return false;                       // (nor an m_{i-2}: history-2 tables too)
   if (h->items.on) return false;                       // (nor per-item rows: per-item schedules too)
+  if (h->hold.on) return false;                        // (known frames overwrite x0, which the fold never writes)
   g = h->conv_out_g;
   g.out_f32 = nullptr;
   g.sol_coef = h->coef_dev; g.sol_step = h->step_dev; g.sol_ncoef = NS2VC_NCOEF;
@@ -151,6 +152,8 @@ static int guidance_onoff(ns2vc_unet* h, bool on, int n) {
     h->seeds.set = false;    // (B seeds are not the n seeds of a guided loop, nor the other way round)
     h->slots.on = false;     // (nor a slot loop: open it again)
     h->next_step = -1;       // (nor does a loop in progress survive the change)
+    h->hold.on = false;      // (nor known frames: their mask covered the other item count)
+    h->hold.n = 0;
   }
   h->guide.on = on;
   h->guide.n = on ? n : 0;
@@ -185,6 +188,9 @@ int ns2vc_sampler_set_x0_correction(ns2vc_unet* h, int mode, float ratio, float 
   if (mode < 0 || mode > 2) return fail("x0 correction mode %d: 0 (off), 1 (dynamic thresholding) or 2 (clamp)", mode);
   if (!(ratio >= 0.f && ratio <= 1.f)) return fail("dynamic thresholding ratio %g outside [0, 1]", (double)ratio);
   if (!(std::isfinite(max_val) && max_val > 0.f)) return fail("thresholding max_val %g must be finite and > 0", (double)max_val);
+  if (mode && h->hold.on)
+    return fail("known frames are held (ns2vc_sampler_set_known): an x0 correction would rescale them; switch the hold off (NULL, NULL) before "
+                "ns2vc_sampler_set_x0_correction(mode %d)", mode);
   if (mode && h->x0c.items.on)
     return fail("the per-item x0 correction is on (ns2vc_sampler_set_x0_correction_items): switch it off (NULL arrays) before the loop-wide "
                 "ns2vc_sampler_set_x0_correction(mode %d)", mode);
@@ -205,6 +211,9 @@ int ns2vc_sampler_set_x0_correction_items(ns2vc_unet* h, const int32_t* mode_hos
   if (h->x0c.mode)
     return fail("the loop-wide x0 correction is on (ns2vc_sampler_set_x0_correction mode %d): switch it off (mode 0) before "
                 "ns2vc_sampler_set_x0_correction_items", h->x0c.mode);
+  if (h->hold.on)
+    return fail("known frames are held (ns2vc_sampler_set_known): an x0 correction would rescale them; switch the hold off (NULL, NULL) before "
+                "ns2vc_sampler_set_x0_correction_items");
   if (n != h->loop_items())
     return fail("per-item x0 correction for %d items, the loop takes %d (the prepared batch; n under guidance: set the guidance first)", n, h->loop_items());
   std::vector<ItemCorrect> rec;
@@ -221,6 +230,37 @@ int ns2vc_sampler_set_x0_correction_items(ns2vc_unet* h, const int32_t* mode_hos
   if (!ic.on || quant != ic.quant) drop_step_graph(h);
   ic.on = true; ic.quant = quant; ic.n = n;
   ic.host = rec;
+  return 0;
+}
+
+// Known frames: the caller's latent on the masked frames of every loop item, written over x0 at every step.  On / off recaptures;
+// new values and new masks are copies into buffers that hold the whole prepared shape, so they replay.
+int ns2vc_sampler_set_known(ns2vc_unet* h, const float* known_nct, const uint8_t* mask_nt, int n, void* stream) {
+  if (check_ready(h, true)) return 1;
+  auto& k = h->hold;
+  if (!known_nct && !mask_nt) {      // off
+    if (k.on) drop_step_graph(h);
+    k.on = false; k.n = 0; k.last.clear();
+    return 0;
+  }
+  if (!known_nct || !mask_nt) return fail("known frames: the latent and the mask are given together (both NULL = off)");
+  if (n != h->loop_items())
+    return fail("known frames for %d items, the loop takes %d (the prepared batch; n under guidance: set the guidance first)", n, h->loop_items());
+  if (h->x0c.mode || h->x0c.items.on)
+    return fail("an x0 correction is on (ns2vc_sampler_set_x0_correction%s): it would rescale the known frames; switch it off before ns2vc_sampler_set_known",
+                h->x0c.mode ? "" : "_items");
+  if (h->in_slot_loop()) return fail("a slot loop is open (ns2vc_sampler_open): known frames run in closed loops only");
+  const size_t rows = (size_t)n * h->T;
+  if (rows > (size_t)0x7fffffff - HOLD_LIST_HEAD) return fail("known frames: %zu rows exceed the 32-bit row list", rows);
+  std::vector<int> list;
+  std::vector<int32_t> last;
+  if (hold_list_from_mask(mask_nt, n, h->T, h->lens.masked ? h->lens.applied.data() : nullptr, list, last)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (k.known.reserve(h, rows * h->CP, false) || k.rows.reserve(h, (size_t)HOLD_LIST_HEAD + rows, true)) return 1;
+  HIPCHK(launch_nct_to_btc(known_nct, h->cfg.latent_channels, h->T, n, k.known.dev, nullptr, PREC_F32, h->CP, h->CP, s));
+  if (k.rows.send(list.data(), list.size(), s)) return 1;
+  if (!k.on) drop_step_graph(h);
+  k.on = true; k.n = n; k.last = last;
   return 0;
 }
 
@@ -255,6 +295,10 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
   const auto& ic = h->x0c.items;
   if (ic.on && !h->items.on) return fail("the per-item x0 correction runs on per-item records: load them (ns2vc_sampler_load_items) or open a slot loop");
   if (ic.on && ic.n != h->loop_items()) return fail("the per-item x0 correction holds %d records, the loop has %d items (set it again)", ic.n, h->loop_items());
+  if (h->hold.on) {      // the known frames go over the x0 the plan's last launch wrote, in front of everything that reads it
+    if (h->hold.n != h->loop_items()) return fail("known frames for %d items, the loop has %d (set them again)", h->hold.n, h->loop_items());
+    HIPCHK(launch_hold_x0(h->x0, h->hold.known.dev, h->hold.rows.dev, h->hold.n * h->T, h->CP, h->cfg.latent_channels, h->guide.on ? 2 : 1, s));
+  }
   SolverStep st;
   st.coef = h->coef_dev; st.step_ptr = h->step_dev; st.ncoef = NS2VC_NCOEF;
   st.x0 = h->x0; st.xe = h->xe; st.xe_op = h->xe_op; st.prec = h->prec; st.xbar = h->xbar; st.d1 = h->d1; st.mprev = h->mprev;
@@ -295,6 +339,16 @@ int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
                   "load the schedules with ns2vc_sampler_load_items, or switch the table off");
     if (item_corrections_fit(h, h->items.host.data(), h->items.n, h->items.rows)) return 1;
     if (ensure_thr(h)) return 1;
+  }
+  if (h->hold.on) {
+    if (h->hold.n != h->loop_items())
+      return fail("known frames for %d items, the loop takes %d: set them again (ns2vc_sampler_set_known)", h->hold.n, h->loop_items());
+    if (h->x0c.mode || h->x0c.items.on) return fail("known frames do not run with an x0 correction: it would rescale them");
+    if (h->lens.masked)      // (lengths set after the mask)
+      for (int b = 0; b < h->hold.n; ++b)
+        if (h->hold.last[(size_t)b] >= h->lens.applied[(size_t)b])
+          return fail("known frame %d of item %d lies at or past its length %d: set the known frames after the lengths", (int)h->hold.last[(size_t)b], b,
+                      (int)h->lens.applied[(size_t)b]);
   }
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)h->B * h->T * h->CP;
@@ -386,6 +440,8 @@ int ns2vc_sampler_handoff(ns2vc_unet* dst, ns2vc_unet* src, void* stream) {
   if (!dst->coef_dev || dst->steps != src->steps) return fail("destination engine must hold the same solver table (%d vs %d steps)", dst->steps, src->steps);
   if (dst->items.on != src->items.on || (src->items.on && dst->items.n != src->items.n))
     return fail("destination engine must hold the same per-item schedules (ns2vc_sampler_load_items on both, or on neither)");
+  if (dst->hold.on != src->hold.on || (src->hold.on && dst->hold.n != src->hold.n))
+    return fail("the two engines disagree on known frames (ns2vc_sampler_set_known): set the same latent and mask on both, or on neither");
   if (dst->coef_hash != src->coef_hash) return fail("destination engine holds a DIFFERENT solver table with the same number of steps (solver / order / betas differ)");
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)src->B * src->T * src->CP;
@@ -501,6 +557,7 @@ int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
   auto& sl = h->slots;
   const int n = h->loop_items();
   const bool h2 = history2 != 0, nz = noise != 0;
+  if (h->hold.on) return fail("known frames are held (ns2vc_sampler_set_known): a slot loop does not run with them; switch the hold off (NULL, NULL) first");
   if (h->fuse_solver) return fail("option fuse_solver folds the shared-table update into conv_out: a slot loop does not run with it (set it to 0 and prepare again)");
   if (nz && h->x0c.mode)
     return fail("a slot loop with stochastic items does not run with the x0 correction (mode %d): turn one of them off before ns2vc_sampler_open", h->x0c.mode);

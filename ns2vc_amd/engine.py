@@ -204,6 +204,7 @@ class Engine:
         self.guidance: Optional[np.ndarray] = None      # per-item guidance scales (set_guidance), None = unguided
         self.x0_correction = None                       # (mode 1 | 2, ratio, max_val) of set_x0_correction, None = off
         self.x0_corrections = None                      # (modes, ratios, max_vals) of set_x0_correction_items, None = off
+        self.hold: Optional[np.ndarray] = None          # the (n, T) bool frame mask of set_known, None = no known frames
         self.table: Optional[SolverTable] = None
         self.tables: Optional[ItemTables] = None        # per-item schedules (load_samplers); None = the shared table
         self._weights_ready = False
@@ -283,6 +284,7 @@ class Engine:
         self.lengths = None
         self.prompt_lengths = None
         self.guidance = None
+        self.hold = None
 
     def workspace_bytes(self) -> int:
         n = C.c_size_t()
@@ -362,6 +364,8 @@ class Engine:
         turns it off."""
         if scales is None:
             check(self.lib.ns2vc_sampler_set_guidance(self.h, None, 0, _stream_ptr(stream)), "set_guidance")
+            if self.guidance is not None:
+                self.hold = None      # (on / off switches known frames off: their mask covered the other item count)
             self.guidance = None
             return
         if hasattr(scales, "detach"):
@@ -373,6 +377,8 @@ class Engine:
         if not np.all(np.isfinite(a)):
             raise ValueError("guidance scales must be finite")
         check(self.lib.ns2vc_sampler_set_guidance(self.h, a.ctypes.data, int(a.shape[0]), _stream_ptr(stream)), "set_guidance")
+        if self.guidance is None:
+            self.hold = None
         self.guidance = a.copy()
 
     def set_x0_correction(self, mode=None, ratio: float = 0.995, max_val: float = 1.0) -> None:
@@ -406,6 +412,31 @@ class Engine:
         check(self.lib.ns2vc_sampler_set_x0_correction_items(self.h, m.ctypes.data, r.ctypes.data, v.ctypes.data, n, _stream_ptr(stream)),
               "set_x0_correction_items")
         self.x0_corrections = (m.copy(), r.copy(), v.copy())
+
+    def set_known(self, known=None, mask=None, stream=None) -> None:
+        """Known frames of the sampling loop: ``known`` (n, latent, T) fp32 on the GPU, ``mask`` (n, T) bool on the host (array /
+        tensor), n the loop items (set the guidance first).  Every step then overwrites the predicted x0 of the masked frames with ``known``
+        in front of the solver update; start such a frame at ``schedule.known_start``.  Asynchronous on ``stream``: new values and new masks
+        replay the captured step graph, on / off recaptures.  ``None, None`` switches it off; so do ``prepare`` and a change of guidance
+        on / off.  Call after ``set_lengths`` (a held frame lies inside its item).  Not together with an x0 correction or a slot loop."""
+        if known is None and mask is None:
+            check(self.lib.ns2vc_sampler_set_known(self.h, None, None, 0, _stream_ptr(stream)), "set_known")
+            self.hold = None
+            return
+        if known is None or mask is None:
+            raise ValueError("known and mask are given together (None, None switches the hold off)")
+        if hasattr(mask, "detach"):
+            mask = mask.detach().cpu().numpy()
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        items = None if self.shape is None else (self.shape[0] if self.guidance is None else self.guidance.shape[0])
+        if self.shape is None or m.shape != (items, self.shape[1]):
+            raise ValueError(f"mask must be ({items}, {None if self.shape is None else self.shape[1]}) -- the loop's items and the prepared T --, got {m.shape}")
+        if hasattr(known, "shape") and tuple(known.shape) != (items, self.cfg.latent_channels, self.shape[1]):
+            raise ValueError(f"known must be ({items}, {self.cfg.latent_channels}, {self.shape[1]}), got {tuple(known.shape)}")
+        if hasattr(known, "dtype") and "float32" not in str(known.dtype):
+            raise ValueError(f"known must be float32, got {known.dtype}")
+        check(self.lib.ns2vc_sampler_set_known(self.h, _ptr(known), m.ctypes.data, int(m.shape[0]), _stream_ptr(stream)), "set_known")
+        self.hold = m.astype(bool)
 
     def forward(self, x, t, out, stream=None) -> None:
         """x (B,100,T), t (B,) fp32, out (B,100,T): one denoiser evaluation."""

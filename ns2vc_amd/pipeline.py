@@ -276,6 +276,8 @@ class Denoiser:
         if getattr(eng, "x0_corrections", None) is not None:      # (a per-item table left on by an earlier call: the two exclude each other)
             eng.set_x0_correction_items(None)
         if corr is not None:
+            if getattr(eng, "hold", None) is not None:            # (known frames left on by an earlier call: the engine refuses the pair)
+                eng.set_known(None, None)
             eng.set_x0_correction(*corr)
         elif getattr(eng, "x0_correction", None) is not None:
             eng.set_x0_correction(None)
@@ -285,6 +287,8 @@ class Denoiser:
         """the per-item table on ``eng``: ``entries`` = one None or (correcting_x0_fn, ratio, max_val) per loop item (set the guidance first)"""
         if getattr(eng, "x0_correction", None) is not None:
             eng.set_x0_correction(None)
+        if getattr(eng, "hold", None) is not None:
+            eng.set_known(None, None)
         eng.set_x0_correction_items([None if e is None else e[0] for e in entries], [0.995 if e is None else e[1] for e in entries],
                                     [1.0 if e is None else e[2] for e in entries], stream=stream)
 
@@ -295,6 +299,39 @@ class Denoiser:
             raise ValueError(f"{what} must be a list of one entry (dict or None) per item ({B}), got "
                              f"{len(corrections) if isinstance(corrections, (list, tuple)) else type(corrections).__name__}")
         return [item_correction_entry(c, f"{what}[{b}]") for b, c in enumerate(corrections)]
+
+    @staticmethod
+    def _hold(eng, known, mask, stream=None) -> None:
+        """the known frames of this call on ``eng`` (after its lengths): set, or switched off where an earlier call left them on"""
+        if known is not None:
+            eng.set_known(known, mask, stream=stream)
+        elif getattr(eng, "hold", None) is not None:
+            eng.set_known(None, None, stream=stream)
+
+    def _check_known(self, known, known_mask, B: int, T: int, lengths, correcting_x0_fn, corrections):
+        """the argument errors of ``sample(known=, known_mask=)`` (ValueError), raised before anything runs -> (known, mask (B, T) numpy bool), or
+        (None, None) where nothing is held: neither given, or an all-False mask"""
+        if known is None and known_mask is None:
+            return None, None
+        if known is None or known_mask is None:
+            raise ValueError("known= (the latent) and known_mask= (its frames) are given together")
+        m = known_mask.detach().cpu().numpy() if hasattr(known_mask, "detach") else np.asarray(known_mask)
+        if m.shape != (B, T) or m.dtype != np.bool_:
+            raise ValueError(f"known_mask must be a bool ({B}, {T}), got {m.dtype} {tuple(m.shape)}")
+        if tuple(known.shape) != (B, self.cfg.latent_channels, T):
+            raise ValueError(f"known must be ({B}, {self.cfg.latent_channels}, {T}), got {tuple(known.shape)}")
+        if not m.any():      # nothing held: the call without them, a correction included
+            return None, None
+        if correcting_x0_fn is not None or corrections is not None:
+            raise ValueError("known frames do not run with an x0 correction (correcting_x0_fn= / corrections=): it would rescale the held frames")
+        if lengths is not None:
+            L = np.asarray(lengths.detach().cpu() if hasattr(lengths, "detach") else lengths).reshape(-1)
+            if L.shape[0] != B:
+                raise ValueError(f"lengths must hold one entry per item ({B}), got {L.shape[0]}")
+            for b in range(B):
+                if m[b, max(int(L[b]), 0):].any():
+                    raise ValueError(f"known_mask[{b}] holds frame {int(np.nonzero(m[b])[0][-1])}, at or past lengths[{b}] = {int(L[b])}")
+        return known, np.ascontiguousarray(m)
 
     def _betas_for(self, solver: str) -> np.ndarray:
         return self.betas64 if solver in DISCRETE_SOLVERS else self.betas
@@ -615,7 +652,7 @@ class Denoiser:
                use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None,
                prompt_lengths=None, guidance_scale=1.0, unconditional_prompt=None, unconditional_prompt_mask=None,
                unconditional_prompt_lengths=None, unconditional_content=None, correcting_x0_fn=None, thresholding_max_val: float = 1.0,
-               dynamic_thresholding_ratio: float = 0.995, schedules=None, corrections=None, **options):
+               dynamic_thresholding_ratio: float = 0.995, schedules=None, corrections=None, known=None, known_mask=None, **options):
         """content (B,256,T), prompt (B,Lp,256), mask (B,Lp) bool; ``noise`` (B,100,T) = x_T (drawn with
         torch.randn like model.py:635 if None).  Returns the sampled latent (B,100,T) fp32.
         ``solver``: ``unipc`` | ``dpmsolver++`` (``order`` 1 | 2 | 3, multistep) or the reference's discrete samplers ``ddim`` (``eta`` =
@@ -651,13 +688,21 @@ class Denoiser:
         dynamic_thresholding_ratio=)`` with the names above -- instead of the call-wide ``correcting_x0_fn=`` (both: ValueError).  Item b is
         corrected by its own entry inside the one captured loop (``Engine.set_x0_correction_items``) and ends on the bits it has
         when its entry is the call-wide setting; a ddim / ddpm item takes None and may share the batch with corrected items.  B equal
-        entries take the call-wide path of that entry.  The default ``tail_fp32`` counts the call as corrected when any item is."""
+        entries take the call-wide path of that entry.  The default ``tail_fp32`` counts the call as corrected when any item is.
+        ``known`` (B,100,T) with ``known_mask`` (B,T) bool: known frames (``Engine.set_known``) -- on the frames of the mask the
+        predicted x0 of every evaluation IS ``known`` (values off the mask are ignored), inside the captured loop on the 16-bit engine and the
+        fp32 tail alike, under guidance in both halves.  x_T there is ``alpha_0 * known + sigma_0 * noise`` (``schedule.known_start``; under
+        ``schedules=`` each item's own first row), so a held frame ends on ``alpha_end * known + sigma_end * noise`` -- on ``known`` itself with
+        ``denoise_to_zero`` and for ddim -- while the free frames are generated next to it: the fixed context of ``sample_long``, or the part a
+        partial re-synthesis keeps.  An all-False mask is the call without them.  Refused (ValueError): one of the pair without the other,
+        wrong shapes, a held frame at or past ``lengths[b]``, and ``correcting_x0_fn=`` / ``corrections=``, which would rescale the held frames."""
         import torch
         B, _, T = content.shape
         dev = content.device
         steps = self._check_sampler_args(solver, steps, eta, B, seeds, order, guidance_scale, unconditional_prompt, unconditional_prompt_mask,
                                          unconditional_prompt_lengths, unconditional_content, correcting_x0_fn, thresholding_max_val,
                                          dynamic_thresholding_ratio, **options)
+        known, known_mask = self._check_known(known, known_mask, B, T, lengths, correcting_x0_fn, corrections)
         tabs = None
         entries = None
         if corrections is not None:
@@ -683,12 +728,13 @@ class Denoiser:
                 return self.sample(content, prompt, prompt_mask, noise, keys[0][0], keys[0][1], keys[0][2], use_graph, generator, tail_fp32, lengths,
                                    keys[0][3], seeds, prompt_lengths, guidance_scale, unconditional_prompt, unconditional_prompt_mask,
                                    unconditional_prompt_lengths, unconditional_content, correcting_x0_fn, thresholding_max_val,
-                                   dynamic_thresholding_ratio, **dict(keys[0][4]))
+                                   dynamic_thresholding_ratio, known=known, known_mask=known_mask, **dict(keys[0][4]))
             tabs = build_tables(specs, self.betas, self.betas64)
         scales = self._guidance_scales(B, guidance_scale, unconditional_prompt)
         guide_kw = dict(schedules=schedules, corrections=corrections, guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
                         unconditional_prompt_lengths=unconditional_prompt_lengths, unconditional_content=unconditional_content,
-                        correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio)
+                        correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio,
+                        known=known, known_mask=known_mask)
         corr = (correcting_x0_fn, float(dynamic_thresholding_ratio), float(thresholding_max_val)) if correcting_x0_fn is not None else None
         rep = 1
         if scales is not None:      # the engine's batch is cat([unconditional, conditional]); the loop still takes and gives B items
@@ -723,6 +769,13 @@ class Denoiser:
         if noise is None:
             noise = torch.randn((B, self.cfg.latent_channels, T), device=dev, generator=generator)
         x = noise.to(device=dev, dtype=torch.float32).contiguous().clone()
+        kn = None
+        if known is not None:      # x_T of the known frames: alpha_0 k + sigma_0 noise in float32, by each item's own first table row (schedule.known_start)
+            kn = known.to(device=dev, dtype=torch.float32).contiguous()
+            row0 = np.asarray(self.engine.table.coef[0] if tabs is None else np.stack([tabs.table_of(b).coef[0] for b in range(B)]), dtype=np.float32)
+            a0 = torch.from_numpy(np.array(np.broadcast_to(row0[..., 1], (B,)))).to(dev).view(B, 1, 1)
+            s0 = torch.from_numpy(np.array(np.broadcast_to(row0[..., 2], (B,)))).to(dev).view(B, 1, 1)
+            x = torch.where(torch.from_numpy(known_mask).to(dev).view(B, 1, T), a0 * kn + s0 * x, x).contiguous()
         s = torch.cuda.current_stream(dev)
         stochastic = bool((self.engine.table.coef[:, 9] != 0).any()) if tabs is None else bool((tabs.coef[:, 9] != 0).any())
         if stochastic:
@@ -733,6 +786,7 @@ class Denoiser:
         c32, p32 = content.float().contiguous(), prompt.float().contiguous()
         if self.precision_check is not None and not self._precision_checked:
             self._condition(self.engine, c32, p32, mask, s, lengths, prompt_lengths)
+            self._hold(self.engine, kn, known_mask, s)
             self._self_check(self._trajectory_points(x, use_graph, s, rep), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths,
                              prompt_lengths=prompt_lengths)
         tail = self._tail(solver, steps, order, n_tail, eta, **options) if tabs is None else self._tail_items(tabs, n_tail, scales, s, corr, entries)
@@ -744,11 +798,14 @@ class Denoiser:
             tail.set_seeds(seeds, stream=s)
         if self.serving_fp32:            # a failed precision check: the whole loop on the fp32 engine
             self._condition(tail, c32, p32, mask, s, lengths, prompt_lengths)
+            self._hold(tail, kn, known_mask, s)
             tail.sample(x, use_graph=use_graph, stream=s)
             return x
         self._condition(self.engine, c32, p32, mask, s, lengths, prompt_lengths)
+        self._hold(self.engine, kn, known_mask, s)
         if tail is not None:
             self._condition(tail, c32, p32, mask, s, lengths, prompt_lengths)
+            self._hold(tail, kn, known_mask, s)      # (the hand-off wants the two engines to agree, as on the seeds)
         first_attn = not self._attn_checked and self.attn_fallback_limit is not None
         if first_attn:
             self.engine.attn_fallbacks(reset=True, stream=s)      # count this loop alone (the self-check's evaluations are behind us)
@@ -761,6 +818,93 @@ class Denoiser:
         if first_attn and redone is None:
             self._attn_check(nfe - (n_tail if tail is not None else 0), s)      # (after the guard's read-out: a switch drops the plan)
         return x if redone is None else redone
+
+    def sample_long(self, content, prompt, prompt_mask=None, noise=None, chunk_frames: int = 938, overlap_frames: int = 64, lengths=None,
+                    **sample_kwargs):
+        """Utterances longer than one engine shape: content (B,256,Ttot) is cut per item by ``schedule.plan_chunks(lengths[b] or Ttot,
+        chunk_frames, overlap_frames)`` and chunk j + 1 is sampled with the last ``overlap_frames`` latent frames of chunk j as known frames
+        (``sample(known=, known_mask=)``), so the model generates every new chunk next to latents it already committed to.
+        Batch j holds the items that have a chunk j, padded to the longest of them; its ``lengths=`` are their chunk lengths (left out where
+        every item fills the batch and the call has no ``lengths=``: the dense plan).  Each item's x_T is its slice of the full-length ``noise``
+        (B,100,Ttot), drawn once from ``generator=`` if None.  Returns (B,100,Ttot): chunk 0 whole, then every later chunk from frame
+        ``overlap_frames`` on -- the overlap frames are the earlier chunk's, which the later one held --, zero past ``lengths``.  With
+        ``overlap_frames=0`` the chunks are independent; where no item has a second chunk this IS ``sample``.  ``sample_kwargs``: the call-wide
+        keywords of ``sample`` (solver, steps, guidance, ...) for every chunk, the per-item ones (``seeds``, ``prompt_lengths``, a per-item
+        ``guidance_scale``, the ``unconditional_*`` rows) sliced per batch, the seeds reused per chunk; ``schedules=``, ``corrections=``,
+        ``known=`` and ``known_mask=`` are refused."""
+        import torch
+        from .schedule import plan_chunks
+        B, _, Ttot = content.shape
+        dev = content.device
+        for k in ("schedules", "corrections", "known", "known_mask"):
+            if sample_kwargs.get(k) is not None:
+                raise ValueError(f"sample_long takes call-wide options only (plus per-item seeds): {k}= is refused")
+        kw = {k: v for k, v in sample_kwargs.items() if k not in ("schedules", "corrections", "known", "known_mask")}
+        seeds = kw.pop("seeds", None)
+        if seeds is not None:
+            seeds = np.asarray(seeds.detach().cpu() if hasattr(seeds, "detach") else seeds).reshape(-1)
+            if seeds.shape[0] != B:
+                raise ValueError(f"seeds must hold one seed per item ({B}), got {seeds.shape[0]}")
+        if lengths is None:
+            L = np.full((B,), Ttot, dtype=np.int64)
+        else:
+            L = np.asarray(lengths.detach().cpu() if hasattr(lengths, "detach") else lengths).reshape(-1).astype(np.int64)
+            if L.shape[0] != B or (L < 1).any() or (L > Ttot).any():
+                raise ValueError(f"lengths must hold {B} entries in [1, {Ttot}]")
+        V = int(overlap_frames)
+        chunks = [plan_chunks(int(L[b]), chunk_frames, V) for b in range(B)]
+        if noise is not None and tuple(noise.shape) != (B, self.cfg.latent_channels, Ttot):
+            raise ValueError(f"noise must be ({B}, {self.cfg.latent_channels}, {Ttot}), got {tuple(noise.shape)}")
+        if max(len(c) for c in chunks) == 1:      # nothing to chain: the plain call, its shapes and its bits
+            return self.sample(content, prompt, prompt_mask, noise, lengths=lengths, seeds=seeds, **kw)
+        if noise is None:
+            noise = torch.randn((B, self.cfg.latent_channels, Ttot), device=dev, generator=kw.get("generator"))
+        noise = noise.to(device=dev, dtype=torch.float32)
+        out = torch.zeros((B, self.cfg.latent_channels, Ttot), dtype=torch.float32, device=dev)
+        min_t = 2 ** (len(self.cfg.block_out_channels) - 1)      # (the shortest T the engine prepares)
+
+        def part(v, items):      # a per-item argument goes with its items; a scalar / one shared row goes to every batch whole
+            if isinstance(v, (list, tuple)):
+                v = np.asarray(v)
+            if v is None or np.ndim(v) == 0 or v.shape[0] != B:
+                return v
+            return v[torch.as_tensor(items, device=v.device)] if torch.is_tensor(v) else v[items]
+
+        for j in range(max(len(c) for c in chunks)):
+            items = [b for b in range(B) if len(chunks[b]) > j]
+            idx = torch.as_tensor(items, device=dev)
+            span = [chunks[b][j] for b in items]
+            Lj = [stop - start for start, stop in span]
+            Tj = max(max(Lj), min_t)
+            c_j = content.new_zeros((len(items), content.shape[1], Tj))
+            n_j = noise.new_zeros((len(items), self.cfg.latent_channels, Tj))
+            for i, (b, (start, stop)) in enumerate(zip(items, span)):
+                c_j[i, :, :stop - start] = content[b, :, start:stop]
+                n_j[i, :, :stop - start] = noise[b, :, start:stop]
+            kw_j = dict(kw)
+            for k in ("prompt_lengths", "guidance_scale", "unconditional_prompt", "unconditional_prompt_mask", "unconditional_prompt_lengths"):
+                if k in kw_j:
+                    kw_j[k] = part(kw_j[k], items)
+            uc = kw_j.get("unconditional_content")
+            if uc is not None:
+                u_j = uc.new_zeros((len(items), uc.shape[1], Tj))
+                for i, (b, (start, stop)) in enumerate(zip(items, span)):
+                    u_j[i, :, :stop - start] = uc[b, :, start:stop]
+                kw_j["unconditional_content"] = u_j
+            if j > 0 and V > 0:      # the frames the earlier chunk ended on, held at the head of this one
+                k_j = out.new_zeros((len(items), self.cfg.latent_channels, Tj))
+                m_j = np.zeros((len(items), Tj), dtype=bool)
+                for i, (b, (start, stop)) in enumerate(zip(items, span)):
+                    k_j[i, :, :V] = out[b, :, start:start + V]
+                    m_j[i, :V] = True
+                kw_j.update(known=k_j, known_mask=m_j)
+            ragged = lengths is not None or any(l != Tj for l in Lj)
+            x_j = self.sample(c_j, prompt[idx], None if prompt_mask is None else prompt_mask[idx], n_j,
+                              lengths=np.asarray(Lj, dtype=np.int32) if ragged else None, seeds=None if seeds is None else seeds[items], **kw_j)
+            for i, (b, (start, stop)) in enumerate(zip(items, span)):
+                keep = V if j > 0 else 0
+                out[b, :, start + keep:stop] = x_j[i, :, keep:stop - start]
+        return out
 
     def open_slots(self, B: int, T: int, Lp: int, order3: bool = False, stochastic: bool = False, unconditional_prompt=None,
                    correcting_x0_fn=None, thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995,
@@ -996,6 +1140,7 @@ class SlotLoop:
         den._prepare(self.rep * self.B, self.T, self.Lp)
         self.dev = torch.device("cuda", torch.cuda.current_device())
         s = torch.cuda.current_stream(self.dev)
+        den._hold(eng, None, None, s)            # (known frames left on by an earlier sample(known=): a slot loop does not run with them)
         eng.set_lengths(self.lengths, stream=s)
         eng.set_prompt_lengths(self.plens, stream=s)
         if self.uncond is not None or eng.guidance is not None:

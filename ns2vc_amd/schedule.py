@@ -47,6 +47,18 @@ rows of the same recurrence (g0 = g1 = d1c = pc = 0, so xe' = xbar' = A*xe - Bc*
   DDPM   A = posterior_mean_coef2[t], Bc = -posterior_mean_coef1[t], noise = exp(0.5*posterior_log_variance_clipped[t]) (0 at t = 0)
 
 A row with noise == 0 adds nothing at all (not 0*z), so every noise-free table keeps its bits.
+
+Known frames (``hold=`` of the two host loops, ``Engine.set_known``).  Per loop item b a frame mask K_b inside [0, L_b) -- L_b =
+lengths[b] or T -- and a known latent k_b.  At every evaluation, before anything reads the x0 the model wrote:
+
+    x0[b, c, t] = k_b[c, t]    for t in K_b, every latent channel c      (the engine's pad columns of such a row: 0; all other rows keep every bit)
+
+Under guidance both halves are overwritten; ``guided_x0(k, k, s)`` is k at every scale, so the update does not change.  The start state of a
+held frame is ``known_start``: x_T = alpha_0 k + sigma_0 noise in float32, alpha_0 and sigma_0 columns 1 and 2 of the item's first row.  The
+recurrence is linear in x0 and m is constant there, so the backward differences vanish and a held frame follows the forward marginal with that
+one noise at any order, for UniPC and DPM-Solver++ alike: x_i = alpha_i k + sigma_i eps, ending on alpha_end k + sigma_end eps -- on k itself
+where the last row returns x_start (``denoise_to_zero``, ddim).  Not together with an x0 correction, which would rescale the held frames.
+``plan_chunks`` cuts a long utterance into chunks that hold each other's last frames this way (``Denoiser.sample_long``).
 """
 from __future__ import annotations
 
@@ -498,7 +510,7 @@ def build_tables(specs, betas: Optional[np.ndarray] = None, discrete_betas: Opti
 
 def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarray], x_T: np.ndarray,
                      trace: Optional[List[np.ndarray]] = None, noise_fn: Optional[Callable[[int, int], np.ndarray]] = None,
-                     guided_x0: Optional[np.ndarray] = None, correct_x0: Optional[Dict[str, object]] = None) -> np.ndarray:
+                     guided_x0: Optional[np.ndarray] = None, correct_x0: Optional[Dict[str, object]] = None, hold=None) -> np.ndarray:
     """Host statement of the loop under per-item schedules (float32).  At loop step r item b has j = r - start_b: ACTIVE when
     0 <= j < rows_b -- it then takes row j of its own table through the recurrence of ``run_table_numpy``, history 2 where ITS table has a
     nonzero column 10 or 11 --, otherwise HELD: evaluated at the clamped row's model time, result ignored, state untouched.
@@ -508,9 +520,12 @@ def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray],
     ``schedule.guided_x0``.  ``correct_x0``: the keywords of ``schedule.correct_x0`` for the whole batch (``lengths`` per item); refused when
     an item is stochastic.  A LIST instead is the per-item correction: one entry per item, None or such a dict for that item
     alone (``lengths`` = its own frame count; ``item_correction``); item b is then corrected exactly as ``run_table_numpy(correct_x0=entry_b)``
-    corrects it alone, a stochastic item takes None, and corrected and stochastic items may share the batch."""
+    corrects it alone, a stochastic item takes None, and corrected and stochastic items may share the batch.
+    ``hold`` = (known, mask): known frames as in ``run_table_numpy`` -- applied at every loop step, also to an item its schedule holds there
+    (its x0 is ignored at that step anyway); not together with ``correct_x0``."""
     f = np.float32
     B = x_T.shape[0]
+    hold = _check_hold(hold, x_T.shape, correct_x0)
     if tabs.index.shape[0] != B:
         raise ValueError(f"{tabs.index.shape[0]} schedules for a batch of {B}")
     xbar = x_T.astype(f).copy()
@@ -536,6 +551,7 @@ def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray],
         else:
             both = np.asarray(x0_fn(np.concatenate([xe, xe], axis=0), np.concatenate([t, t]))).astype(f)
             x0 = _guided_x0(both[:B], both[B:], np.asarray(guided_x0, dtype=f))
+        x0 = hold_x0(x0, hold)
         rows, act = tabs.row_at(r), tabs.active_at(r)
         for b in range(B):
             if not act[b]:
@@ -687,6 +703,64 @@ def item_corrections(entries, n: int, noisy: Optional[Sequence[bool]] = None) ->
     return [item_correction(c, bool(noisy[b]) if noisy is not None else False, f"item {b}") for b, c in enumerate(entries)]
 
 
+# ---- known frames -----------------------------------------------------------------------------------------
+def _check_hold(hold, shape, correct_x0=None):
+    """``hold`` = None or (known, mask) -> None or (known float32 shaped ``shape`` = (B, C, T), mask (B, T) bool); ValueError otherwise"""
+    if hold is None:
+        return None
+    if not isinstance(hold, (tuple, list)) or len(hold) != 2 or hold[0] is None or hold[1] is None:
+        raise ValueError("hold is a pair (known, mask): the known latent and the frame mask are given together")
+    if correct_x0 is not None:
+        raise ValueError("known frames (hold=) do not run with an x0 correction (correct_x0=): it would rescale the held frames")
+    known, mask = np.asarray(hold[0], dtype=np.float32), np.asarray(hold[1])
+    if known.shape != tuple(shape):
+        raise ValueError(f"known must be shaped like x_T {tuple(shape)}, got {known.shape}")
+    if mask.shape != (shape[0], shape[-1]) or mask.dtype != np.bool_:
+        raise ValueError(f"the known-frame mask must be a bool array ({shape[0]}, {shape[-1]}), got {mask.dtype} {mask.shape}")
+    return known, mask
+
+
+def hold_x0(x0: np.ndarray, hold) -> np.ndarray:
+    """the engine's hold launch on the host: ``known`` on the masked frames of x0 (B, C, T), every other element unchanged; ``hold`` None: x0"""
+    if hold is None:
+        return x0
+    known, mask = hold
+    return np.where(mask[:, None, :], known, x0).astype(np.float32)
+
+
+def known_start(x_T: np.ndarray, known: np.ndarray, mask: np.ndarray, coef_row0) -> np.ndarray:
+    """The start state of a loop with known frames (float32): ``alpha * known + sigma * x_T`` on the masked frames, x_T elsewhere, with
+    alpha and sigma the float32 columns 1 and 2 of the item's first table row -- ``coef_row0`` is that row (NCOEF,), shared, or (B, NCOEF), one
+    per item (per-item schedules: each item's own row 0).  A held frame then stays on the forward marginal of ``known`` with the noise
+    x_T[b, :, t] all the way: x_i = alpha_i k + sigma_i eps."""
+    f = np.float32
+    x_T = np.asarray(x_T, dtype=f)
+    known, mask = _check_hold((known, mask), x_T.shape)
+    row = np.asarray(coef_row0, dtype=f)
+    if row.shape not in ((NCOEF,), (x_T.shape[0], NCOEF)):
+        raise ValueError(f"coef_row0 must be one table row ({NCOEF},) or one per item ({x_T.shape[0]}, {NCOEF}), got {row.shape}")
+    a = row[..., 1].reshape((-1,) + (1,) * (x_T.ndim - 1))
+    s = row[..., 2].reshape((-1,) + (1,) * (x_T.ndim - 1))
+    return np.where(mask[:, None, :], (a * known).astype(f) + (s * x_T).astype(f), x_T).astype(f)
+
+
+def plan_chunks(length: int, chunk_frames: int, overlap_frames: int) -> List[Tuple[int, int]]:
+    """The chunks [(start, stop)] that ``Denoiser.sample_long`` cuts an utterance of ``length`` frames into: at most ``chunk_frames`` long,
+    consecutive ones sharing exactly ``overlap_frames`` frames (0 <= overlap < chunk), which the later chunk holds as known frames.  The
+    starts are j * (chunk - overlap) for as long as start + overlap < length -- every chunk adds at least one new frame -- and
+    stop = min(start + chunk, length).  Chunk 0 always exists: an utterance no longer than the overlap is that one chunk."""
+    L, C, V = int(length), int(chunk_frames), int(overlap_frames)
+    if L < 1 or C < 1:
+        raise ValueError(f"length and chunk_frames must be >= 1, got {length}, {chunk_frames}")
+    if not 0 <= V < C:
+        raise ValueError(f"overlap_frames must be in [0, chunk_frames), got {overlap_frames} of {chunk_frames}")
+    out, start = [], 0
+    while start == 0 or start + V < L:
+        out.append((start, min(start + C, L)))
+        start += C - V
+    return out
+
+
 def has_history2(table: SolverTable) -> bool:
     """the table needs m_prev2 (some row of order 3): what the engine's ns2vc_sampler_load detects from columns 10-11"""
     return bool((np.asarray(table.coef)[:, 10:12] != 0).any())
@@ -694,13 +768,18 @@ def has_history2(table: SolverTable) -> bool:
 
 def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarray], x_T: np.ndarray,
                     trace: Optional[List[np.ndarray]] = None, noise_fn: Optional[Callable[[int], np.ndarray]] = None,
-                    correct_x0: Optional[Dict[str, object]] = None) -> np.ndarray:
+                    correct_x0: Optional[Dict[str, object]] = None, hold=None) -> np.ndarray:
     """Host executor of the unified recurrence (float32), used by CPU tests to pin
     the tables against the oracle samplers.  ``x0_fn(x, t_model[B]) -> x0``.  ``noise_fn(i)`` -> the standard normals of
     step i, shaped like x_T (ns2vc_amd.noise.gauss), for tables with a nonzero noise column.
     ``correct_x0``: None (off) or the keywords of ``schedule.correct_x0`` -- ``dict(mode=, ratio=, max_val=, lengths=)`` -- applied to m
-    in front of everything that uses it (the reference's ``data_prediction_fn``); not together with a noise column."""
+    in front of everything that uses it (the reference's ``data_prediction_fn``); not together with a noise column.
+    ``hold`` = (known, mask), the known frames of DESIGN 4.16: ``known`` shaped like x_T, ``mask`` (B, T) bool -- straight after ``x0_fn``,
+    before anything reads its result, ``x0[b, :, t] = known[b, :, t]`` wherever ``mask[b, t]`` (``hold_x0``); every other element keeps its
+    bits.  The update is linear in x0, so such a frame follows x_i = alpha_i k + sigma_i eps with the eps of its start state
+    (``known_start``).  Not together with ``correct_x0``, which would rescale the held frames."""
     f = np.float32
+    hold = _check_hold(hold, x_T.shape, correct_x0)
     xbar = x_T.astype(f).copy()
     xe = xbar.copy()
     d1 = np.zeros_like(xbar)
@@ -713,7 +792,7 @@ def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray]
         raise ValueError(f"the x0 correction does not apply to a stochastic {table.solver} table (the reference's discrete samplers have none)")
     for i in range(table.steps):
         t_model, alpha, sigma, g0, g1, A, Bc, d1c, pc = (f(v) for v in table.coef[i, :9])
-        x0 = x0_fn(xe, np.full((B,), t_model, dtype=f)).astype(f)
+        x0 = hold_x0(x0_fn(xe, np.full((B,), t_model, dtype=f)).astype(f), hold)
         eps = (xe - alpha * x0) / sigma
         m = (xe - sigma * eps) / alpha
         if correct_x0 is not None:
