@@ -8,6 +8,7 @@ captured hipGraph per step, and nothing synchronises with the host until the end
 from __future__ import annotations
 
 import warnings
+from dataclasses import replace
 from typing import Dict, Optional
 
 import numpy as np
@@ -15,9 +16,23 @@ import numpy as np
 from . import dist as _dist
 from .engine import DEFAULT_PRECISION, Engine
 from .noise import draw_seeds
-from .schedule import (DISCRETE_SOLVERS, ITEM_HIST2, ITEM_NOISE, SOLVERS, TablePool, build_table, build_tables, check_x0_correction, linear_betas,
-                       schedule_key, table_flags, table_options)
+from .request import CORRECTION_KEYS, SampleRequest, call_wide_kwargs, check_guidance, check_item_schedule, host_array, item_correction_entry
+from .schedule import (DISCRETE_SOLVERS, ITEM_HIST2, ITEM_NOISE, TablePool, build_table, check_x0_correction, linear_betas, schedule_key,
+                       table_flags, table_options)
 from .spec import UNetConfig, attention_workgroups_per_forward
+
+# The engine options that keep a ragged batch (``lengths=``) on its fused launches: each is a constructor parameter of ``Denoiser`` of the same
+# name (default off), reaches the 16-bit engine and the fp32 engine of the tail / self-check alike, and is independent of the others.
+MASKED_OPTIONS = (
+    "masked_fuse",      # the plan keeps its fused launches where the kernels mask their own rows
+    "masked_attn",      # the attention launches skip the keys and query tiles past an item's end themselves (no key-bias row, no sweeper launch)
+    "masked_rows",      # the transformer blocks keep their two row-chain launches, which zero the rows past an item's end themselves (the fp32
+                        # engine has no row chains and ignores it)
+    "masked_ffn",       # the dim-128 / 256 transformer blocks keep the pre-stage launch of the fused feed-forward, which zeroes the rows past an
+                        # item's end itself (the fp32 engine ignores it)
+    "masked_geglu",     # the dim-384 transformer blocks keep the token-stationary GEGLU launch, which takes the LayerNorm sums from its own
+                        # operand rows and zeroes the rows past an item's end itself
+)
 
 
 # default number of trailing fp32 evaluations of a 16-bit sampling loop, per solver (``Denoiser(tail_fp32=None)``):
@@ -75,30 +90,6 @@ def corrected_tail_min(precision: str, scales=None) -> int:
     return max(0, int(np.ceil(np.log(g * e1 / PARITY_BAR) / np.log(3.0) - 1e-9)))
 
 
-CORRECTION_KEYS = ("correcting_x0_fn", "thresholding_max_val", "dynamic_thresholding_ratio")
-
-
-def item_correction_entry(c, what: str = "correction"):
-    """One item's own x0 correction (``sample(corrections=)``, ``SlotLoop.admit(correction=)``, ``service.Segment.correction``): None or
-    ``dict(correcting_x0_fn=, thresholding_max_val=, dynamic_thresholding_ratio=)``, names only -> None (off) or (name, ratio, max_val);
-    ValueError naming ``what`` otherwise."""
-    if c is None:
-        return None
-    if callable(c):
-        raise ValueError(f"{what}: a callable cannot run inside the captured loop; pass None or a dict with correcting_x0_fn "
-                         f"'dynamic_thresholding' or 'clamp'")
-    if not isinstance(c, dict):
-        raise ValueError(f"{what} must be None or dict(correcting_x0_fn=, thresholding_max_val=, dynamic_thresholding_ratio=), got {c!r}")
-    extra = sorted(set(c) - set(CORRECTION_KEYS))
-    if extra:
-        raise ValueError(f"{what}: unknown keys {extra} (an x0 correction has {CORRECTION_KEYS})")
-    name, ratio, max_val = c.get("correcting_x0_fn"), c.get("dynamic_thresholding_ratio", 0.995), c.get("thresholding_max_val", 1.0)
-    try:
-        mode = check_x0_correction(name, ratio, max_val, names_only=True)
-    except ValueError as e:
-        raise ValueError(f"{what}: {e}") from None
-    return None if mode == 0 else (name, float(ratio), float(max_val))
-
 
 # LayerNorm-by-linearity guard thresholds on max |mean|/std (see Denoiser): 16-bit modes lose ~ratio * 2^-11 on a row,
 # fp32 loses ~ratio^2 * 2^-24 in the variance E[x^2] - mean^2
@@ -148,38 +139,17 @@ class Denoiser:
                  betas: Optional[np.ndarray] = None, ln_guard: Optional[float] = -1.0, tail_fp32: Optional[int] = None,
                  precision_check: Optional[float] = -1.0, attn_fallback_limit: Optional[float] = 0.10, masked_fuse: bool = False,
                  masked_attn: bool = False, masked_rows: bool = False, masked_ffn: bool = False, masked_geglu: bool = False):
+        given = locals()
         self.cfg = cfg
-        # engine option ``masked_fuse``: under ``lengths=`` the plan keeps its fused launches where the kernels mask their own rows; passed to
-        # the fp32 engine of the tail / self-check as well
-        self.masked_fuse = bool(masked_fuse)
-        # engine option ``masked_attn``: under ``lengths=`` the attention launches skip the keys and query tiles past an item's end themselves
-        # (no key-bias row, no sweeper launch behind them); independent of ``masked_fuse``, passed on the same way
-        self.masked_attn = bool(masked_attn)
-        # engine option ``masked_rows``: under ``lengths=`` the transformer blocks keep their two row-chain launches, which zero the rows past an
-        # item's end themselves; independent of the two above, passed on the same way (the fp32 engine has no row chains and ignores it)
-        self.masked_rows = bool(masked_rows)
-        # engine option ``masked_ffn``: under ``lengths=`` the dim-128 / 256 transformer blocks keep the pre-stage launch of the fused feed-forward,
-        # which zeroes the rows past an item's end itself; independent of the three above, passed on the same way (the fp32 engine ignores it)
-        self.masked_ffn = bool(masked_ffn)
-        # engine option ``masked_geglu``: under ``lengths=`` the dim-384 transformer blocks keep the token-stationary GEGLU launch, which takes the
-        # LayerNorm sums from its own operand rows and zeroes the rows past an item's end itself; independent of the four above, passed on the same way
-        self.masked_geglu = bool(masked_geglu)
+        for name in MASKED_OPTIONS:
+            setattr(self, name, bool(given[name]))
         self.attn_fallback_limit = attn_fallback_limit if precision not in ("fp32", "f32") else None
         self.attn_fallback_rate_seen: Optional[float] = None
         self._attn_checked = False
         self.precision = {"f32": "fp32", "f16": "fp16"}.get(precision, precision)
         self.engine = Engine(cfg, precision=precision)
         self.engine.load_state_dict(state)
-        if self.masked_fuse:
-            self.engine.set_option("masked_fuse", True)
-        if self.masked_attn:
-            self.engine.set_option("masked_attn", True)
-        if self.masked_rows:
-            self.engine.set_option("masked_rows", True)
-        if self.masked_ffn:
-            self.engine.set_option("masked_ffn", True)
-        if self.masked_geglu:
-            self.engine.set_option("masked_geglu", True)
+        self._masked_options(self.engine)
         self._state = state
         self.betas = linear_betas() if betas is None else np.asarray(betas, dtype=np.float32)
         # ddim / ddpm index the model's own float32 buffers, which the reference derives from the float64 betas
@@ -257,11 +227,16 @@ class Denoiser:
             self._ln_checked = False                # a new shape is a new set of rows: check synchronously once
             self._ln_pending = False
 
+    def _masked_options(self, eng) -> None:
+        for name in MASKED_OPTIONS:      # (the defaults reach no engine)
+            if getattr(self, name):
+                eng.set_option(name, True)
+
     def set_option(self, name: str, value: bool) -> None:
         """A plan option of the engine (``Engine.set_option``; e.g. ``gn_coop`` off for a pipeline that runs the denoiser on a CU partition).
         The plan and the sampler table are rebuilt by the next ``sample``."""
         self.engine.set_option(name, value)
-        if name in ("masked_fuse", "masked_attn", "masked_rows", "masked_ffn") or name == "masked_geglu":
+        if name in MASKED_OPTIONS:
             setattr(self, name, bool(value))
             if self.tail_engine is not None:
                 self.tail_engine.set_option(name, value)
@@ -271,83 +246,63 @@ class Denoiser:
         self._table_key = None
 
     @staticmethod
-    def _x0_correction(eng, corr) -> None:
-        """``corr`` = (correcting_x0_fn, ratio, max_val) or None on ``eng``; nothing reaches an engine that is off and stays off"""
-        if getattr(eng, "x0_corrections", None) is not None:      # (a per-item table left on by an earlier call: the two exclude each other)
-            eng.set_x0_correction_items(None)
-        if corr is not None:
-            if getattr(eng, "hold", None) is not None:            # (known frames left on by an earlier call: the engine refuses the pair)
-                eng.set_known(None, None)
-            eng.set_x0_correction(*corr)
-        elif getattr(eng, "x0_correction", None) is not None:
-            eng.set_x0_correction(None)
-
-    @staticmethod
-    def _x0_corrections(eng, entries, stream=None) -> None:
-        """the per-item table on ``eng``: ``entries`` = one None or (correcting_x0_fn, ratio, max_val) per loop item (set the guidance first)"""
-        if getattr(eng, "x0_correction", None) is not None:
-            eng.set_x0_correction(None)
-        if getattr(eng, "hold", None) is not None:
+    def _correct(eng, corr, entries=None, stream=None) -> None:
+        """The x0 correction on ``eng`` in the form the call has it: ``entries`` = the per-item table, one None or (correcting_x0_fn, ratio,
+        max_val) per loop item (set the guidance first), else ``corr`` = the loop-wide (correcting_x0_fn, ratio, max_val) or None.  The other
+        form goes off first (the two exclude each other), and so do known frames an earlier call left on (the engine refuses the pair);
+        nothing reaches an engine that is off and stays off."""
+        other = eng.x0_correction if entries is not None else eng.x0_corrections
+        if other is not None:
+            eng.set_x0_correction(None) if entries is not None else eng.set_x0_correction_items(None)
+        if (entries is not None or corr is not None) and eng.hold is not None:
             eng.set_known(None, None)
-        eng.set_x0_correction_items([None if e is None else e[0] for e in entries], [0.995 if e is None else e[1] for e in entries],
-                                    [1.0 if e is None else e[2] for e in entries], stream=stream)
+        if entries is not None:
+            eng.set_x0_correction_items([None if e is None else e[0] for e in entries], [0.995 if e is None else e[1] for e in entries],
+                                        [1.0 if e is None else e[2] for e in entries], stream=stream)
+        elif corr is not None:
+            eng.set_x0_correction(*corr)
+        elif eng.x0_correction is not None:
+            eng.set_x0_correction(None)
 
-    @staticmethod
-    def _check_corrections(corrections, B: int, what: str = "corrections"):
-        """the argument errors of a per-item correction list (ValueError, naming the item) -> one None or (name, ratio, max_val) per item"""
-        if not isinstance(corrections, (list, tuple)) or len(corrections) != B:
-            raise ValueError(f"{what} must be a list of one entry (dict or None) per item ({B}), got "
-                             f"{len(corrections) if isinstance(corrections, (list, tuple)) else type(corrections).__name__}")
-        return [item_correction_entry(c, f"{what}[{b}]") for b, c in enumerate(corrections)]
+    def _setup(self, eng, req: SampleRequest, stream, table_key_attr: str, seeds=None):
+        """The sampler state of ``req`` on ``eng`` -- the 16-bit head (``_table_key``) and the fp32 tail (``_tail_table_key``) alike, in the one
+        order the engine wants: guidance (the per-item records below cover the loop's items), x0 correction (the schedules are checked against
+        it when they load), table, seeds.  Returns the seeds of a stochastic loop (``seeds``, the request's, or drawn from its generator: pass
+        them to the other engine), None for a deterministic one."""
+        if req.scales is not None or eng.guidance is not None:
+            eng.set_guidance(req.scales, stream=stream)
+        self._correct(eng, req.corr, req.entries, stream)
+        key = req.table_key
+        if req.tabs is not None and eng is not self.engine:      # (the tail alone has always loaded its records again when the guidance came or went)
+            key += (None if req.scales is None else len(req.scales),)
+        if getattr(self, table_key_attr) != key:
+            if req.tabs is not None:
+                eng.load_samplers(req.tabs, stream=stream)
+            else:
+                solver, steps, order, eta, options = req.schedule
+                eng.load_sampler(solver, steps, self._betas_for(solver), order, eta, **dict(options))
+            setattr(self, table_key_attr, key)
+        if not (self._loop_table(eng).coef[:, 9] != 0).any():
+            return None
+        if seeds is None:
+            seeds = req.seeds if req.seeds is not None else draw_seeds(req.content.shape[0], req.generator)
+        eng.set_seeds(seeds, stream=stream)
+        return seeds
 
-    @staticmethod
-    def _hold(eng, known, mask, stream=None) -> None:
-        """the known frames of this call on ``eng`` (after its lengths): set, or switched off where an earlier call left them on"""
-        if known is not None:
-            eng.set_known(known, mask, stream=stream)
-        elif getattr(eng, "hold", None) is not None:
-            eng.set_known(None, None, stream=stream)
-
-    def _check_known(self, known, known_mask, B: int, T: int, lengths, correcting_x0_fn, corrections):
-        """the argument errors of ``sample(known=, known_mask=)`` (ValueError), raised before anything runs -> (known, mask (B, T) numpy bool), or
-        (None, None) where nothing is held: neither given, or an all-False mask"""
-        if known is None and known_mask is None:
-            return None, None
-        if known is None or known_mask is None:
-            raise ValueError("known= (the latent) and known_mask= (its frames) are given together")
-        m = known_mask.detach().cpu().numpy() if hasattr(known_mask, "detach") else np.asarray(known_mask)
-        if m.shape != (B, T) or m.dtype != np.bool_:
-            raise ValueError(f"known_mask must be a bool ({B}, {T}), got {m.dtype} {tuple(m.shape)}")
-        if tuple(known.shape) != (B, self.cfg.latent_channels, T):
-            raise ValueError(f"known must be ({B}, {self.cfg.latent_channels}, {T}), got {tuple(known.shape)}")
-        if not m.any():      # nothing held: the call without them, a correction included
-            return None, None
-        if correcting_x0_fn is not None or corrections is not None:
-            raise ValueError("known frames do not run with an x0 correction (correcting_x0_fn= / corrections=): it would rescale the held frames")
-        if lengths is not None:
-            L = np.asarray(lengths.detach().cpu() if hasattr(lengths, "detach") else lengths).reshape(-1)
-            if L.shape[0] != B:
-                raise ValueError(f"lengths must hold one entry per item ({B}), got {L.shape[0]}")
-            for b in range(B):
-                if m[b, max(int(L[b]), 0):].any():
-                    raise ValueError(f"known_mask[{b}] holds frame {int(np.nonzero(m[b])[0][-1])}, at or past lengths[{b}] = {int(L[b])}")
-        return known, np.ascontiguousarray(m)
+    def _bind(self, eng, cond, stream) -> None:
+        """the condition of a call on ``eng``: ``cond`` = (content, prompt, mask, lengths, prompt_lengths, known, known_mask).  The known frames
+        go behind the lengths: set, or switched off where an earlier call left them on"""
+        self._condition(eng, *cond[:3], stream, *cond[3:5])
+        if cond[5] is not None or eng.hold is not None:
+            eng.set_known(cond[5], cond[6], stream=stream)
 
     def _betas_for(self, solver: str) -> np.ndarray:
         return self.betas64 if solver in DISCRETE_SOLVERS else self.betas
 
-    def _table(self, solver: str, steps: int, order: int, eta: float = 0.0, **options) -> None:
-        key = (solver, steps, order, eta, table_options(options))
-        if self._table_key != key:
-            self.engine.load_sampler(solver, steps, self._betas_for(solver), order, eta, **options)
-            self._table_key = key
-
-    def _tables(self, tabs, stream) -> None:
-        """per-item schedules -> the engine (its guidance must be set: the records cover the loop's items)"""
-        key = ("items", tabs.keys, tuple(int(v) for v in tabs.start))
-        if self._table_key != key:
-            self.engine.load_samplers(tabs, stream=stream)
-            self._table_key = key
+    @staticmethod
+    def _loop_table(eng):
+        """the loaded loop of ``eng``: the per-item schedules, or the shared table"""
+        return eng.tables if eng.tables is not None else eng.table
 
     def _fp32_engine(self) -> Engine:
         """the exact-fp32 engine (tail of a 16-bit loop, precision self-check, fallback), prepared for the current shape"""
@@ -356,16 +311,7 @@ class Denoiser:
             self.tail_engine.load_state_dict(self._state)
             if self._ln_switched:
                 self.tail_engine.set_option("ln_linear", False)
-            if self.masked_fuse:
-                self.tail_engine.set_option("masked_fuse", True)
-            if self.masked_attn:
-                self.tail_engine.set_option("masked_attn", True)
-            if self.masked_rows:
-                self.tail_engine.set_option("masked_rows", True)
-            if self.masked_ffn:
-                self.tail_engine.set_option("masked_ffn", True)
-            if self.masked_geglu:
-                self.tail_engine.set_option("masked_geglu", True)
+            self._masked_options(self.tail_engine)
             self._tail_shape = None
             self._tail_table_key = None
         if self._tail_shape != self._shape:
@@ -375,34 +321,23 @@ class Denoiser:
             self._tail_shape = self._shape
         return self.tail_engine
 
-    def _tail(self, solver: str, steps: int, order: int, n_tail: int, eta: float = 0.0, **options) -> Optional[Engine]:
-        """the fp32 engine that finishes a 16-bit loop (or runs all of it after a failed precision check), with the table loaded"""
-        if (n_tail <= 0 and not self.serving_fp32) or self.precision == "fp32":
-            return None
-        e = self._fp32_engine()
-        key = (solver, steps, order, eta, table_options(options))
-        if self._tail_table_key != key:
-            e.load_sampler(solver, steps, self._betas_for(solver), order, eta, **options)
-            self._tail_table_key = key
-        return e
+    def _tail(self, n_tail: int) -> Optional[Engine]:
+        """the fp32 engine if a loop with ``n_tail`` trailing fp32 evaluations needs one -- to finish a 16-bit loop, or to run all of it after a
+        failed precision check --, else None"""
+        return self._fp32_engine() if (n_tail > 0 or self.serving_fp32) and self.precision != "fp32" else None
 
-    def _tail_items(self, tabs, n_tail: int, scales, stream, corr=None, entries=None) -> Optional[Engine]:
-        """``_tail`` under per-item schedules: the guidance goes first, the records cover the loop's items; then the x0 correction in the form
-        the head has it (the schedules are checked against it when they load)"""
-        if (n_tail <= 0 and not self.serving_fp32) or self.precision == "fp32":
-            return None
-        e = self._fp32_engine()
-        if scales is not None or e.guidance is not None:
-            e.set_guidance(scales, stream=stream)
-        if entries is not None:
-            self._x0_corrections(e, entries, stream)
-        else:
-            self._x0_correction(e, corr)
-        key = ("items", tabs.keys, tuple(int(v) for v in tabs.start), None if scales is None else len(scales))
-        if self._tail_table_key != key:
-            e.load_samplers(tabs, stream=stream)
-            self._tail_table_key = key
-        return e
+    def _default_tail(self, req: SampleRequest) -> int:
+        """trailing fp32 evaluations of ``req`` where neither the call nor the instance sets them: the largest tail any item's own schedule asks
+        for (right-aligned, the last k loop steps are every item's last); guidance multiplies the 16-bit rounding of the last evaluations
+        (``guided_tail_extra``), and a correction lets it in twice (``corrected_tail_min``)"""
+        if self.precision == "fp32":
+            return 0
+        n = max(default_tail_fp32(solver, order) for solver, order in req.solver_orders)
+        if req.scales is not None:
+            n += guided_tail_extra(req.scales)
+        if req.corr is not None or req.entries is not None:
+            n = max(n, corrected_tail_min(self.precision, req.scales))
+        return n
 
     def _attn_check(self, evals: int, stream) -> None:
         """once per set of weights: share of attention workgroups that needed the exact fallback during the last ``evals`` evaluations"""
@@ -474,7 +409,7 @@ class Denoiser:
         """(x_e, t) at the first, middle and last evaluation of the loaded table, from a preliminary loop on the 16-bit engine
         (its condition must be set).  ``rep`` = 2 under guidance: the loop gives B items, the evaluations take the point in both halves."""
         import torch
-        tabs = getattr(self.engine, "tables", None)      # per-item schedules: the points of the loop as run, t = every item's own model time there
+        tabs = self.engine.tables      # per-item schedules: the points of the loop as run, t = every item's own model time there
         tm = None if tabs is not None else np.asarray(self.engine.table.t_model, dtype=np.float32)
         n = tabs.steps if tabs is not None else len(tm)
         idx = sorted({0, n // 2, n - 1})
@@ -494,42 +429,6 @@ class Denoiser:
         return pts
 
     @staticmethod
-    def _guidance_scales(B: int, guidance_scale, unconditional_prompt) -> Optional[np.ndarray]:
-        """(B,) float32 scales of a guided call, or None where nothing guided runs: no unconditional prompt, or every scale 1
-        (the reference's short cut, sampler/uni_pc.py:222-223).  Raises for a wrong shape or a non-finite scale."""
-        g = guidance_scale.detach().cpu().numpy() if hasattr(guidance_scale, "detach") else np.asarray(guidance_scale)
-        if g.ndim > 1 or (g.ndim == 1 and g.shape[0] != B) or g.dtype.kind not in "fiu":
-            raise ValueError(f"guidance_scale must be a float or hold one scale per item ({B},), got shape {tuple(g.shape)}")
-        g = np.array(np.broadcast_to(g.astype(np.float32), (B,)))      # (a writable copy)
-        if not np.all(np.isfinite(g)):
-            raise ValueError("guidance_scale must be finite")
-        if unconditional_prompt is None or np.all(g == 1.0):
-            return None
-        return g
-
-    @staticmethod
-    def _check_guidance_args(B: int, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
-                             unconditional_content) -> Optional[np.ndarray]:
-        """the argument errors of the guidance keywords; returns ``_guidance_scales``"""
-        g = Denoiser._guidance_scales(B, guidance_scale, unconditional_prompt)
-        if unconditional_prompt is None:
-            if unconditional_prompt_mask is not None or unconditional_prompt_lengths is not None or unconditional_content is not None:
-                raise ValueError("unconditional_prompt_mask / _lengths / unconditional_content need an unconditional_prompt")
-            return g
-        if len(unconditional_prompt.shape) != 3 or unconditional_prompt.shape[0] not in (1, B):
-            raise ValueError(f"unconditional_prompt must be ({B} | 1, Lu, C), got {tuple(unconditional_prompt.shape)}")
-        if unconditional_prompt_mask is not None and (tuple(unconditional_prompt_mask.shape) not in
-                                                      ((1, unconditional_prompt.shape[1]), (B, unconditional_prompt.shape[1]))):
-            raise ValueError(f"unconditional_prompt_mask must be ({B} | 1, {unconditional_prompt.shape[1]}), got {tuple(unconditional_prompt_mask.shape)}")
-        if unconditional_prompt_lengths is not None:
-            ul = np.asarray(unconditional_prompt_lengths.detach().cpu() if hasattr(unconditional_prompt_lengths, "detach") else unconditional_prompt_lengths)
-            if ul.reshape(-1).shape[0] not in (1, B):
-                raise ValueError(f"unconditional_prompt_lengths must hold {B} (or 1) entries, got {ul.reshape(-1).shape[0]}")
-        if unconditional_content is not None and unconditional_content.shape[0] != B:
-            raise ValueError(f"unconditional_content must hold {B} items, got {unconditional_content.shape[0]}")
-        return g
-
-    @staticmethod
     def _guided_condition(content, prompt, prompt_mask, lengths, prompt_lengths, unconditional_prompt, unconditional_prompt_mask,
                           unconditional_prompt_lengths, unconditional_content):
         """The condition of a guided call on the engine of 2B items: cat([unconditional, conditional]) as the reference batches it
@@ -547,8 +446,7 @@ class Denoiser:
         def ints(v, n, fill):
             if v is None:
                 return np.full((n,), fill, dtype=np.int32)
-            v = np.asarray(v.detach().cpu() if hasattr(v, "detach") else v).reshape(-1).astype(np.int32)
-            return np.ascontiguousarray(np.broadcast_to(v, (n,)))
+            return np.ascontiguousarray(np.broadcast_to(host_array(v).reshape(-1).astype(np.int32), (n,)))
 
         up = unconditional_prompt.float().expand(B, -1, -1)
         prompt2 = torch.cat([pad(up, L), pad(prompt.float(), L)], dim=0).contiguous()
@@ -576,8 +474,7 @@ class Denoiser:
         cat([unconditional, conditional]) of 2B items and ``schedule.guided_x0`` of its halves in torch (see ``sample`` for the keywords)."""
         import torch
         B, _, T = x.shape
-        scales = self._check_guidance_args(B, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
-                                           unconditional_content)
+        scales = check_guidance(B, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths, unconditional_content)
         if scales is not None:
             c2, p2, m2, l2, pl2 = self._guided_condition(content, prompt, prompt_mask, lengths, prompt_lengths, unconditional_prompt,
                                                          unconditional_prompt_mask, unconditional_prompt_lengths, unconditional_content)
@@ -603,50 +500,6 @@ class Denoiser:
         if first_attn and redone is None:
             self._attn_check(1, s)                            # (after the guard's read-out: a switch drops the plan)
         return out if redone is None else redone
-
-    def _check_sampler_args(self, solver: str, steps: Optional[int], eta: float, B: int, seeds, order: int = 2, guidance_scale=1.0,
-                            unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None,
-                            unconditional_content=None, correcting_x0_fn=None, thresholding_max_val=1.0, dynamic_thresholding_ratio=0.995,
-                            **options) -> int:
-        """the argument errors of ``sample``, raised before anything runs; returns the step count"""
-        self._check_guidance_args(B, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
-                                  unconditional_content)
-        if solver not in SOLVERS:
-            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
-        if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True) and solver in DISCRETE_SOLVERS:
-            raise ValueError(f"correcting_x0_fn applies to unipc / dpmsolver++ only (the reference's {solver} sampler has no correction)")
-        table_options(options)                  # unknown option names
-        if eta != 0.0 and solver != "ddim":
-            raise ValueError(f"eta is DDIM's noise scale (ddim_sampling_eta); solver {solver!r} takes none")
-        if eta < 0.0:
-            raise ValueError(f"eta must be >= 0, got {eta}")
-        if steps is None:
-            steps = {"ddim": 100, "ddpm": len(self.betas64)}.get(solver, 20)   # model.py sample(): sampling_timesteps=100; p_sample_loop: every timestep
-        if solver == "ddpm" and steps != len(self.betas64):
-            raise ValueError(f"ddpm runs every timestep of the schedule: steps must be {len(self.betas64)} (or None), got {steps}")
-        if seeds is not None and np.asarray(seeds.detach().cpu() if hasattr(seeds, "detach") else seeds).reshape(-1).shape[0] != B:
-            raise ValueError(f"seeds must hold one seed per item ({B})")
-        if (options or order != 2) and (solver, int(steps), order, eta, table_options(options)) != self._table_key:
-            from .schedule import build_table      # the table's own checks (order, skip_type, ...) before anything runs, host only
-            build_table(solver, int(steps), self._betas_for(solver), order, eta, **options)
-        return int(steps)
-
-    def _check_schedules(self, schedules, B: int, solver: str, steps: int, order: int, eta: float, correcting_x0_fn, options):
-        """the argument errors of ``sample(schedules=)`` (ValueError, naming the item); returns the B schedule dicts with None filled in"""
-        if not isinstance(schedules, (list, tuple)) or len(schedules) != B:
-            raise ValueError(f"schedules must be a list of one schedule (dict or None) per item ({B}), got "
-                             f"{len(schedules) if isinstance(schedules, (list, tuple)) else type(schedules).__name__}")
-        own = dict(solver=solver, steps=steps, order=order, eta=eta, **options)
-        specs = []
-        for b, sp in enumerate(schedules):
-            sp = dict(own) if sp is None else sp
-            key = schedule_key(sp, b)
-            if correcting_x0_fn is not None and key[0] in DISCRETE_SOLVERS:
-                raise ValueError(f"schedules[{b}]: correcting_x0_fn applies to unipc / dpmsolver++ only (the reference's {key[0]} sampler has no correction)")
-            if key[0] == "ddpm" and key[1] != len(self.betas64):
-                raise ValueError(f"schedules[{b}]: ddpm runs every timestep of the schedule: steps must be {len(self.betas64)}, got {key[1]}")
-            specs.append(sp)
-        return specs
 
     def sample(self, content, prompt, prompt_mask=None, noise=None, solver: str = "unipc", steps: Optional[int] = None, order: int = 2,
                use_graph: bool = True, generator=None, tail_fp32: Optional[int] = None, lengths=None, eta: float = 0.0, seeds=None,
@@ -696,125 +549,60 @@ class Denoiser:
         ``denoise_to_zero`` and for ddim -- while the free frames are generated next to it: the fixed context of ``sample_long``, or the part a
         partial re-synthesis keeps.  An all-False mask is the call without them.  Refused (ValueError): one of the pair without the other,
         wrong shapes, a held frame at or past ``lengths[b]``, and ``correcting_x0_fn=`` / ``corrections=``, which would rescale the held frames."""
+        return self._run(SampleRequest.parse(
+            self, content, prompt, prompt_mask, noise, solver, steps, order, use_graph, generator, tail_fp32, lengths, eta, seeds, prompt_lengths,
+            guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths, unconditional_content, correcting_x0_fn,
+            thresholding_max_val, dynamic_thresholding_ratio, schedules, corrections, known, known_mask, **options))
+
+    def _run(self, req: SampleRequest):
+        """``sample`` behind its checks: guided condition, prepare, setup, x_T (noise, known start), self-check, tail, run, guard"""
         import torch
-        B, _, T = content.shape
-        dev = content.device
-        steps = self._check_sampler_args(solver, steps, eta, B, seeds, order, guidance_scale, unconditional_prompt, unconditional_prompt_mask,
-                                         unconditional_prompt_lengths, unconditional_content, correcting_x0_fn, thresholding_max_val,
-                                         dynamic_thresholding_ratio, **options)
-        known, known_mask = self._check_known(known, known_mask, B, T, lengths, correcting_x0_fn, corrections)
-        tabs = None
-        entries = None
-        if corrections is not None:
-            if correcting_x0_fn is not None:
-                raise ValueError("corrections= (one x0 correction per item) and correcting_x0_fn= (one for the call) exclude each other")
-            entries = self._check_corrections(corrections, B)
-            if all(e == entries[0] for e in entries):      # one correction for everybody: today's call-wide setting, its kernels and its bits
-                e = entries[0]
-                kw = {} if e is None else dict(correcting_x0_fn=e[0], dynamic_thresholding_ratio=e[1], thresholding_max_val=e[2])
-                return self.sample(content, prompt, prompt_mask, noise, solver, steps, order, use_graph, generator, tail_fp32, lengths, eta, seeds,
-                                   prompt_lengths, guidance_scale, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
-                                   unconditional_content, schedules=schedules, **kw, **options)
-            specs = self._check_schedules([None] * B if schedules is None else schedules, B, solver, steps, order, eta, None, options)
-            for b, sp in enumerate(specs):
-                if entries[b] is not None and schedule_key(sp, b)[0] in DISCRETE_SOLVERS:
-                    raise ValueError(f"corrections[{b}]: correcting_x0_fn applies to unipc / dpmsolver++ only (the reference's "
-                                     f"{schedule_key(sp, b)[0]} sampler has no correction: ddim / ddpm have no correction)")
-            tabs = build_tables(specs, self.betas, self.betas64)      # (the table reads item records: one schedule B times is deduplicated)
-        elif schedules is not None:
-            specs = self._check_schedules(schedules, B, solver, steps, order, eta, correcting_x0_fn, options)
-            keys = [schedule_key(sp, b) for b, sp in enumerate(specs)]
-            if all(k == keys[0] for k in keys):      # one schedule for everybody: today's shared-table loop, its kernels and its bits
-                return self.sample(content, prompt, prompt_mask, noise, keys[0][0], keys[0][1], keys[0][2], use_graph, generator, tail_fp32, lengths,
-                                   keys[0][3], seeds, prompt_lengths, guidance_scale, unconditional_prompt, unconditional_prompt_mask,
-                                   unconditional_prompt_lengths, unconditional_content, correcting_x0_fn, thresholding_max_val,
-                                   dynamic_thresholding_ratio, known=known, known_mask=known_mask, **dict(keys[0][4]))
-            tabs = build_tables(specs, self.betas, self.betas64)
-        scales = self._guidance_scales(B, guidance_scale, unconditional_prompt)
-        guide_kw = dict(schedules=schedules, corrections=corrections, guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
-                        unconditional_prompt_lengths=unconditional_prompt_lengths, unconditional_content=unconditional_content,
-                        correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio,
-                        known=known, known_mask=known_mask)
-        corr = (correcting_x0_fn, float(dynamic_thresholding_ratio), float(thresholding_max_val)) if correcting_x0_fn is not None else None
+        B, _, T = req.content.shape
+        dev = req.content.device
+        content, prompt, prompt_mask, lengths, prompt_lengths = req.content, req.prompt, req.prompt_mask, req.lengths, req.prompt_lengths
         rep = 1
-        if scales is not None:      # the engine's batch is cat([unconditional, conditional]); the loop still takes and gives B items
-            content_c, prompt_c, prompt_mask_c, lengths_c, prompt_lengths_c = content, prompt, prompt_mask, lengths, prompt_lengths
-            content, prompt, prompt_mask, lengths, prompt_lengths = self._guided_condition(
-                content, prompt, prompt_mask, lengths, prompt_lengths, unconditional_prompt, unconditional_prompt_mask, unconditional_prompt_lengths,
-                unconditional_content)
+        if req.scales is not None:      # the engine's batch is cat([unconditional, conditional]); the loop still takes and gives B items
+            content, prompt, prompt_mask, lengths, prompt_lengths = self._guided_condition(content, prompt, prompt_mask, lengths, prompt_lengths, *req.uncond)
             rep = 2
         self._guard_before()
         self._prepare(rep * B, T, prompt.shape[1])
-        if scales is not None or self.engine.guidance is not None:
-            self.engine.set_guidance(scales, stream=torch.cuda.current_stream(dev))
-        if entries is not None:
-            self._x0_corrections(self.engine, entries, torch.cuda.current_stream(dev))
-        else:
-            self._x0_correction(self.engine, corr)
-        if tabs is not None:
-            self._tables(tabs, torch.cuda.current_stream(dev))
-        else:
-            self._table(solver, steps, order, eta, **options)
-        nfe = self.engine.table.steps if tabs is None else tabs.steps      # (steps + 1 with denoise_to_zero; per-item schedules: the longest item's)
-        n_tail = tail_fp32 if tail_fp32 is not None else self.tail_fp32
-        if n_tail is None:
-            # (per-item schedules: the largest tail any item's own schedule asks for -- right-aligned, the last k loop steps are every item's last)
-            n_tail = max(default_tail_fp32(so, od) for so, od in ([(solver, order)] if tabs is None else [(k[0], k[2]) for k in tabs.keys])) \
-                if self.precision != "fp32" else 0
-            if scales is not None and self.precision != "fp32":      # guidance multiplies the 16-bit rounding of the last evaluations
-                n_tail += guided_tail_extra(scales)
-            if (corr is not None or entries is not None) and self.precision != "fp32":      # ... and a correction lets it in twice (corrected_tail_min)
-                n_tail = max(n_tail, corrected_tail_min(self.precision, scales))
-        n_tail = max(0, min(int(n_tail), nfe))
-        if noise is None:
-            noise = torch.randn((B, self.cfg.latent_channels, T), device=dev, generator=generator)
+        s = torch.cuda.current_stream(dev)
+        noise = req.noise if req.noise is not None else torch.randn((B, self.cfg.latent_channels, T), device=dev, generator=req.generator)
+        seeds = self._setup(self.engine, req, s, "_table_key")      # (drawn behind x_T, so ``generator=`` reproduces a run)
+        table = self._loop_table(self.engine)
+        nfe = table.steps      # (steps + 1 with denoise_to_zero; per-item schedules: the longest item's)
+        n_tail = req.tail_fp32 if req.tail_fp32 is not None else self.tail_fp32
+        n_tail = max(0, min(int(self._default_tail(req) if n_tail is None else n_tail), nfe))
         x = noise.to(device=dev, dtype=torch.float32).contiguous().clone()
         kn = None
-        if known is not None:      # x_T of the known frames: alpha_0 k + sigma_0 noise in float32, by each item's own first table row (schedule.known_start)
-            kn = known.to(device=dev, dtype=torch.float32).contiguous()
-            row0 = np.asarray(self.engine.table.coef[0] if tabs is None else np.stack([tabs.table_of(b).coef[0] for b in range(B)]), dtype=np.float32)
+        if req.known is not None:      # x_T of the known frames: alpha_0 k + sigma_0 noise in float32, by each item's own first table row (schedule.known_start)
+            kn = req.known.to(device=dev, dtype=torch.float32).contiguous()
+            row0 = np.asarray(table.coef[0] if req.tabs is None else np.stack([req.tabs.table_of(b).coef[0] for b in range(B)]), dtype=np.float32)
             a0 = torch.from_numpy(np.array(np.broadcast_to(row0[..., 1], (B,)))).to(dev).view(B, 1, 1)
             s0 = torch.from_numpy(np.array(np.broadcast_to(row0[..., 2], (B,)))).to(dev).view(B, 1, 1)
-            x = torch.where(torch.from_numpy(known_mask).to(dev).view(B, 1, T), a0 * kn + s0 * x, x).contiguous()
-        s = torch.cuda.current_stream(dev)
-        stochastic = bool((self.engine.table.coef[:, 9] != 0).any()) if tabs is None else bool((tabs.coef[:, 9] != 0).any())
-        if stochastic:
-            if seeds is None:
-                seeds = draw_seeds(B, generator)
-            self.engine.set_seeds(seeds, stream=s)
+            x = torch.where(torch.from_numpy(req.known_mask).to(dev).view(B, 1, T), a0 * kn + s0 * x, x).contiguous()
         mask = None if prompt_mask is None else prompt_mask.to(device=dev, dtype=torch.uint8).contiguous()
-        c32, p32 = content.float().contiguous(), prompt.float().contiguous()
+        cond = (content.float().contiguous(), prompt.float().contiguous(), mask, lengths, prompt_lengths, kn, req.known_mask)
         if self.precision_check is not None and not self._precision_checked:
-            self._condition(self.engine, c32, p32, mask, s, lengths, prompt_lengths)
-            self._hold(self.engine, kn, known_mask, s)
-            self._self_check(self._trajectory_points(x, use_graph, s, rep), c32, p32, mask, s, keep_fp32=n_tail > 0, lengths=lengths,
+            self._bind(self.engine, cond, s)
+            self._self_check(self._trajectory_points(x, req.use_graph, s, rep), *cond[:3], s, keep_fp32=n_tail > 0, lengths=lengths,
                              prompt_lengths=prompt_lengths)
-        tail = self._tail(solver, steps, order, n_tail, eta, **options) if tabs is None else self._tail_items(tabs, n_tail, scales, s, corr, entries)
-        if tabs is None and tail is not None and (scales is not None or tail.guidance is not None):
-            tail.set_guidance(scales, stream=s)
-        if tail is not None and tabs is None:
-            self._x0_correction(tail, corr)
-        if tail is not None and stochastic:
-            tail.set_seeds(seeds, stream=s)
-        if self.serving_fp32:            # a failed precision check: the whole loop on the fp32 engine
-            self._condition(tail, c32, p32, mask, s, lengths, prompt_lengths)
-            self._hold(tail, kn, known_mask, s)
-            tail.sample(x, use_graph=use_graph, stream=s)
-            return x
-        self._condition(self.engine, c32, p32, mask, s, lengths, prompt_lengths)
-        self._hold(self.engine, kn, known_mask, s)
+        tail = self._tail(n_tail)
         if tail is not None:
-            self._condition(tail, c32, p32, mask, s, lengths, prompt_lengths)
-            self._hold(tail, kn, known_mask, s)      # (the hand-off wants the two engines to agree, as on the seeds)
+            self._setup(tail, req, s, "_tail_table_key", seeds)
+        if self.serving_fp32:            # a failed precision check: the whole loop on the fp32 engine
+            self._bind(tail, cond, s)
+            tail.sample(x, use_graph=req.use_graph, stream=s)
+            return x
+        self._bind(self.engine, cond, s)
+        if tail is not None:
+            self._bind(tail, cond, s)      # (the hand-off wants the two engines to agree, as on the seeds)
         first_attn = not self._attn_checked and self.attn_fallback_limit is not None
         if first_attn:
             self.engine.attn_fallbacks(reset=True, stream=s)      # count this loop alone (the self-check's evaluations are behind us)
-        self.engine.sample(x, use_graph=use_graph, stream=s, tail=tail, tail_steps=n_tail if tail is not None else 0)
-        if scales is not None:      # (a redo starts from the caller's B-item arguments)
-            content, prompt, prompt_mask, lengths, prompt_lengths = content_c, prompt_c, prompt_mask_c, lengths_c, prompt_lengths_c
-        redone = self._guard_after(s, lambda: self.sample(content, prompt, prompt_mask, noise, solver, steps, order, use_graph,
-                                                          tail_fp32=tail_fp32, lengths=lengths, eta=eta, seeds=seeds, prompt_lengths=prompt_lengths,
-                                                          **guide_kw, **options))
+        self.engine.sample(x, use_graph=req.use_graph, stream=s, tail=tail, tail_steps=n_tail if tail is not None else 0)
+        # (a redo runs the same request from the same x_T and seeds)
+        redone = self._guard_after(s, lambda: self._run(replace(req, noise=noise, seeds=seeds if seeds is not None else req.seeds)))
         if first_attn and redone is None:
             self._attn_check(nfe - (n_tail if tail is not None else 0), s)      # (after the guard's read-out: a switch drops the plan)
         return x if redone is None else redone
@@ -836,19 +624,20 @@ class Denoiser:
         from .schedule import plan_chunks
         B, _, Ttot = content.shape
         dev = content.device
-        for k in ("schedules", "corrections", "known", "known_mask"):
+        refused = ("schedules", "corrections", "known", "known_mask")
+        for k in refused:
             if sample_kwargs.get(k) is not None:
                 raise ValueError(f"sample_long takes call-wide options only (plus per-item seeds): {k}= is refused")
-        kw = {k: v for k, v in sample_kwargs.items() if k not in ("schedules", "corrections", "known", "known_mask")}
+        kw = {k: v for k, v in sample_kwargs.items() if k not in refused}
         seeds = kw.pop("seeds", None)
         if seeds is not None:
-            seeds = np.asarray(seeds.detach().cpu() if hasattr(seeds, "detach") else seeds).reshape(-1)
+            seeds = host_array(seeds).reshape(-1)
             if seeds.shape[0] != B:
                 raise ValueError(f"seeds must hold one seed per item ({B}), got {seeds.shape[0]}")
         if lengths is None:
             L = np.full((B,), Ttot, dtype=np.int64)
         else:
-            L = np.asarray(lengths.detach().cpu() if hasattr(lengths, "detach") else lengths).reshape(-1).astype(np.int64)
+            L = host_array(lengths).reshape(-1).astype(np.int64)
             if L.shape[0] != B or (L < 1).any() or (L > Ttot).any():
                 raise ValueError(f"lengths must hold {B} entries in [1, {Ttot}]")
         V = int(overlap_frames)
@@ -863,16 +652,9 @@ class Denoiser:
         out = torch.zeros((B, self.cfg.latent_channels, Ttot), dtype=torch.float32, device=dev)
         min_t = 2 ** (len(self.cfg.block_out_channels) - 1)      # (the shortest T the engine prepares)
 
-        def part(v, items):      # a per-item argument goes with its items; a scalar / one shared row goes to every batch whole
-            if isinstance(v, (list, tuple)):
-                v = np.asarray(v)
-            if v is None or np.ndim(v) == 0 or v.shape[0] != B:
-                return v
-            return v[torch.as_tensor(items, device=v.device)] if torch.is_tensor(v) else v[items]
-
+        per_item = dict(kw, prompt=prompt, prompt_mask=prompt_mask, seeds=seeds)      # (the frames of content, noise and unconditional_content are cut below)
         for j in range(max(len(c) for c in chunks)):
             items = [b for b in range(B) if len(chunks[b]) > j]
-            idx = torch.as_tensor(items, device=dev)
             span = [chunks[b][j] for b in items]
             Lj = [stop - start for start, stop in span]
             Tj = max(max(Lj), min_t)
@@ -881,16 +663,12 @@ class Denoiser:
             for i, (b, (start, stop)) in enumerate(zip(items, span)):
                 c_j[i, :, :stop - start] = content[b, :, start:stop]
                 n_j[i, :, :stop - start] = noise[b, :, start:stop]
-            kw_j = dict(kw)
-            for k in ("prompt_lengths", "guidance_scale", "unconditional_prompt", "unconditional_prompt_mask", "unconditional_prompt_lengths"):
-                if k in kw_j:
-                    kw_j[k] = part(kw_j[k], items)
+            kw_j = SampleRequest.take(per_item, items, B)
             uc = kw_j.get("unconditional_content")
             if uc is not None:
-                u_j = uc.new_zeros((len(items), uc.shape[1], Tj))
-                for i, (b, (start, stop)) in enumerate(zip(items, span)):
-                    u_j[i, :, :stop - start] = uc[b, :, start:stop]
-                kw_j["unconditional_content"] = u_j
+                kw_j["unconditional_content"] = uc.new_zeros((len(items), uc.shape[1], Tj))
+                for i, (start, stop) in enumerate(span):
+                    kw_j["unconditional_content"][i, :, :stop - start] = uc[i, :, start:stop]
             if j > 0 and V > 0:      # the frames the earlier chunk ended on, held at the head of this one
                 k_j = out.new_zeros((len(items), self.cfg.latent_channels, Tj))
                 m_j = np.zeros((len(items), Tj), dtype=bool)
@@ -899,8 +677,7 @@ class Denoiser:
                     m_j[i, :V] = True
                 kw_j.update(known=k_j, known_mask=m_j)
             ragged = lengths is not None or any(l != Tj for l in Lj)
-            x_j = self.sample(c_j, prompt[idx], None if prompt_mask is None else prompt_mask[idx], n_j,
-                              lengths=np.asarray(Lj, dtype=np.int32) if ragged else None, seeds=None if seeds is None else seeds[items], **kw_j)
+            x_j = self.sample(c_j, noise=n_j, lengths=np.asarray(Lj, dtype=np.int32) if ragged else None, **kw_j)
             for i, (b, (start, stop)) in enumerate(zip(items, span)):
                 keep = V if j > 0 else 0
                 out[b, :, start + keep:stop] = x_j[i, :, keep:stop - start]
@@ -936,29 +713,16 @@ class Denoiser:
         if hi == lo:      # fewer utterances than ranks: this rank has nothing to denoise but must still join the collective
             local = torch.zeros((0, self.cfg.latent_channels, content.shape[2]), dtype=torch.float32, device=content.device)
         else:
-            pm = None if prompt_mask is None else prompt_mask[lo:hi]
-            ln = None if lengths is None else lengths[lo:hi]
             if seeds is None and kw.get("solver") in DISCRETE_SOLVERS:
                 seeds = draw_seeds(n, kw.get("generator"))
-            sd = None if seeds is None else seeds[lo:hi]
-            pl = None if prompt_lengths is None else prompt_lengths[lo:hi]
-            if kw.get("schedules") is not None:      # the per-item schedules go with the batch
-                if len(kw["schedules"]) != n:
-                    raise ValueError(f"schedules must be a list of one schedule (dict or None) per item ({n}), got {len(kw['schedules'])}")
-                kw = dict(kw, schedules=list(kw["schedules"][lo:hi]))
-            if kw.get("corrections") is not None:    # ... and so do the per-item x0 corrections
-                if len(kw["corrections"]) != n:
-                    raise ValueError(f"corrections must be a list of one entry (dict or None) per item ({n}), got {len(kw['corrections'])}")
-                kw = dict(kw, corrections=list(kw["corrections"][lo:hi]))
-
-            def part(v):      # the per-item guidance arguments go with the batch; a scalar / one shared row goes to every rank whole
-                if isinstance(v, (list, tuple)):
-                    v = np.asarray(v)
-                return v if v is None or np.ndim(v) == 0 or v.shape[0] != n else v[lo:hi]
-            local = self.sample(content[lo:hi], prompt[lo:hi], pm, noise[lo:hi], lengths=ln, seeds=sd, prompt_lengths=pl,
-                                guidance_scale=part(guidance_scale), unconditional_prompt=part(unconditional_prompt),
-                                unconditional_prompt_mask=part(unconditional_prompt_mask),
-                                unconditional_prompt_lengths=part(unconditional_prompt_lengths), unconditional_content=part(unconditional_content), **kw)
+            for k, entry in (("schedules", "schedule"), ("corrections", "entry")):      # (the global count: the slice would name the shard's)
+                if kw.get(k) is not None and len(kw[k]) != n:
+                    raise ValueError(f"{k} must be a list of one {entry} (dict or None) per item ({n}), got {len(kw[k])}")
+            # the per-item arguments go with the batch; a scalar / one shared row goes to every rank whole
+            local = self.sample(**SampleRequest.take(dict(
+                kw, content=content, prompt=prompt, prompt_mask=prompt_mask, noise=noise, lengths=lengths, seeds=seeds, prompt_lengths=prompt_lengths,
+                guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
+                unconditional_prompt_lengths=unconditional_prompt_lengths, unconditional_content=unconditional_content), slice(lo, hi), n))
         return _dist.gather_latents(local, n)
 
 
@@ -995,13 +759,8 @@ class OverlappedPipeline:
         self.denoiser, self.pre_fn, self.post_fn = denoiser, pre_fn, post_fn
         table_options(options)
         self.kw = dict(solver=solver, steps=steps, order=order, use_graph=use_graph, eta=eta, **options)
-        if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True):
-            if solver in DISCRETE_SOLVERS:
-                raise ValueError(f"correcting_x0_fn applies to unipc / dpmsolver++ only, not {solver!r}")
-            self.kw.update(correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio)
-        if unconditional_prompt is not None:
-            self.kw.update(guidance_scale=guidance_scale, unconditional_prompt=unconditional_prompt, unconditional_prompt_mask=unconditional_prompt_mask,
-                           unconditional_prompt_lengths=unconditional_prompt_lengths)
+        self.kw.update(call_wide_kwargs(solver, correcting_x0_fn, thresholding_max_val, dynamic_thresholding_ratio, guidance_scale, unconditional_prompt,
+                                        unconditional_prompt_mask=unconditional_prompt_mask, unconditional_prompt_lengths=unconditional_prompt_lengths))
         dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         self.pre_device = torch.device(pre_device) if pre_device is not None else dev
@@ -1140,12 +899,13 @@ class SlotLoop:
         den._prepare(self.rep * self.B, self.T, self.Lp)
         self.dev = torch.device("cuda", torch.cuda.current_device())
         s = torch.cuda.current_stream(self.dev)
-        den._hold(eng, None, None, s)            # (known frames left on by an earlier sample(known=): a slot loop does not run with them)
+        if eng.hold is not None:                 # (known frames left on by an earlier sample(known=): a slot loop does not run with them)
+            eng.set_known(None, None, stream=s)
         eng.set_lengths(self.lengths, stream=s)
         eng.set_prompt_lengths(self.plens, stream=s)
         if self.uncond is not None or eng.guidance is not None:
             eng.set_guidance(self.scales if self.uncond is not None else None, stream=s)
-        den._x0_correction(eng, self.corr)
+        den._correct(eng, self.corr)
         eng.open_slots(self.order3, self.stochastic, stream=s, item_corrections=self.item_corrections)
         if self.stochastic:
             eng.set_seeds(self.seeds, stream=s)
@@ -1172,16 +932,11 @@ class SlotLoop:
             raise ValueError("a request with its own x0 correction needs a slot loop opened with item_corrections=True")
         key = schedule_key(schedule)
         solver, steps, order, eta, _ = key
-        if solver == "ddpm" and steps != len(self.den.betas64):
-            raise ValueError(f"ddpm runs every timestep of the schedule: steps must be {len(self.den.betas64)}, got {steps}")
+        check_item_schedule(key, "correction" if own is not None else "slot", len(self.den.betas64), self.corr is not None or own is not None)
         if not np.isfinite(float(guidance_scale)):
             raise ValueError("guidance_scale must be finite")
         if float(guidance_scale) != 1.0 and self.uncond is None:
             raise ValueError("a guided request needs a slot loop opened with unconditional_prompt=")
-        if self.corr is not None and solver in DISCRETE_SOLVERS:
-            raise ValueError(f"correcting_x0_fn applies to unipc / dpmsolver++ only, not {solver!r}")
-        if own is not None and solver in DISCRETE_SOLVERS:
-            raise ValueError(f"correction: correcting_x0_fn applies to unipc / dpmsolver++ only, not {solver!r} (ddim / ddpm have no correction)")
         n_tail = slot_tail_needed(self.den.precision, solver, order, guidance_scale, self.corr is not None or own is not None)
         if n_tail > 0 and self.require_tail_free:
             raise ValueError(f"this request ({solver}, order {order}, guidance scale {float(guidance_scale):g}"
@@ -1283,7 +1038,7 @@ class SlotLoop:
             if self.stochastic:
                 eng.set_seeds(self.seeds, stream=s)
             if self.item_corrections:      # (the whole vector: only the admitted slots' entries have changed)
-                self.den._x0_corrections(eng, self.corrections, s)
+                self.den._correct(eng, None, self.corrections, s)
             if self.rep == 2:
                 eng.set_guidance(self.scales, stream=s)
                 u = torch.zeros((n, self.Lp, cfg.cross_attention_dim), dtype=torch.float32, device=dev)

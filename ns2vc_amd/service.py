@@ -44,8 +44,9 @@ import numpy as np
 
 from .frontend import PreModel
 from .noise import derive_seed
-from .pipeline import Denoiser, OverlappedPipeline
-from .schedule import DISCRETE_SOLVERS, ITEM_HIST2, ITEM_NOISE, build_table, check_x0_correction, plan_slots, schedule_key, table_flags, table_options
+from .pipeline import MASKED_OPTIONS, Denoiser, OverlappedPipeline
+from .request import CORRECTION_KEYS, call_wide_kwargs
+from .schedule import ITEM_HIST2, ITEM_NOISE, build_table, plan_slots, schedule_key, table_flags, table_options
 
 
 @dataclass
@@ -88,16 +89,10 @@ class GroupedConverter:
         ``guidance_scale`` with ``unconditional_prompt`` (1, Lu, 256), one for every segment: classifier-free guidance
         (``Denoiser.sample``).  The engine then runs two items per segment, so a batch holds at most ``max_batch // 2`` segments."""
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
-        if masked_fuse is not None and bool(masked_fuse) != denoiser.masked_fuse:     # the denoiser's engine option of that name (ragged batches only)
-            denoiser.set_option("masked_fuse", bool(masked_fuse))
-        if masked_attn is not None and bool(masked_attn) != denoiser.masked_attn:
-            denoiser.set_option("masked_attn", bool(masked_attn))
-        if masked_rows is not None and bool(masked_rows) != denoiser.masked_rows:
-            denoiser.set_option("masked_rows", bool(masked_rows))
-        if masked_ffn is not None and bool(masked_ffn) != denoiser.masked_ffn:
-            denoiser.set_option("masked_ffn", bool(masked_ffn))
-        if masked_geglu is not None and bool(masked_geglu) != denoiser.masked_geglu:
-            denoiser.set_option("masked_geglu", bool(masked_geglu))
+        given = locals()
+        for name in MASKED_OPTIONS:      # the denoiser's engine options of these names (ragged batches only); None leaves the denoiser's setting
+            if given[name] is not None and bool(given[name]) != getattr(denoiser, name):
+                denoiser.set_option(name, bool(given[name]))
         self.guided = unconditional_prompt is not None and float(guidance_scale) != 1.0
         if self.guided:
             if not np.isfinite(float(guidance_scale)):
@@ -111,12 +106,8 @@ class GroupedConverter:
             steps = None
         table_options(options)           # the keyword-only sampler options of Denoiser.sample (skip_type, denoise_to_zero, ...)
         self.kw = dict(solver=solver, steps=steps, order=order, eta=eta, **options)
-        if self.guided:
-            self.kw.update(guidance_scale=float(guidance_scale), unconditional_prompt=unconditional_prompt)
-        if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True):
-            if solver in DISCRETE_SOLVERS:
-                raise ValueError(f"correcting_x0_fn applies to unipc / dpmsolver++ only, not {solver!r}")
-            self.kw.update(correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio)
+        self.kw.update(call_wide_kwargs(solver, correcting_x0_fn, thresholding_max_val, dynamic_thresholding_ratio, float(guidance_scale),
+                                        unconditional_prompt if self.guided else None))
 
     def _seeds(self, idx) -> np.ndarray:
         """per-SEGMENT noise seeds of the stochastic samplers, from the converter's seed and the segment's position in the input"""
@@ -162,7 +153,7 @@ class GroupedConverter:
             sch = [getattr(segments[i], "schedule", None) for i in idx]
             if any(v is not None for v in sch):
                 cond["schedules"] = sch
-            own = {k: self.kw[k] for k in ("correcting_x0_fn", "thresholding_max_val", "dynamic_thresholding_ratio") if k in self.kw} or None
+            own = {k: self.kw[k] for k in CORRECTION_KEYS if k in self.kw} or None
             cor = [getattr(segments[i], "correction", None) for i in idx]
             if any(v is not None for v in cor):
                 cond["corrections"] = [own if v is None else v for v in cor]
@@ -246,8 +237,7 @@ class ContinuousConverter:
         if steps is None:
             steps = {"ddim": 100, "ddpm": len(denoiser.betas64)}.get(solver, 20)
         self.own = dict(solver=solver, steps=int(steps), order=order, eta=eta, **options)
-        self.corr = dict(correcting_x0_fn=correcting_x0_fn, thresholding_max_val=thresholding_max_val, dynamic_thresholding_ratio=dynamic_thresholding_ratio) \
-            if check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val, names_only=True) else {}
+        self.corr = call_wide_kwargs(None, correcting_x0_fn, thresholding_max_val, dynamic_thresholding_ratio)      # (the loop checks every request's solver)
         if self.item_corrections and self.corr:
             raise ValueError("item_corrections=True (Segment.correction) and the loop-wide correcting_x0_fn= exclude each other")
         self.last_plan = None          # (events of the last convert: tests, utilisation figures)

@@ -259,52 +259,43 @@ def test_new_kernels_use_no_scratch_and_the_old_counts_stand():
 
 
 # ---- the refusals in front of the C call (no device) ----------------------------------------------------------------
-class _NoEngine:
-    """every engine call is an error: what the checks below raise must come from the Python side"""
-    def __getattr__(self, name):
-        raise AssertionError(f"engine.{name} reached")
-
-
-def _loop(precision="fp16", order3=False, stochastic=False, corr=None, uncond=None, B=3, T=66, Lp=5):
-    from ns2vc_amd.pipeline import Denoiser, SlotLoop
-    from ns2vc_amd.spec import UNetConfig
-    den = Denoiser.__new__(Denoiser)
-    den.cfg, den.precision, den.betas, den.betas64, den.engine = UNetConfig(), precision, S.linear_betas(), B64, _NoEngine()
-    den.precision_check, den._precision_checked = None, True
-    lp = SlotLoop.__new__(SlotLoop)
-    lp.den, lp.B, lp.T, lp.Lp, lp.use_graph, lp.order3, lp.stochastic, lp.corr, lp.uncond = den, B, T, Lp, True, order3, stochastic, corr, uncond
-    lp.require_tail_free = True
-    lp.rep, lp.pool, lp._tables, lp.items, lp.step, lp.dev = (2 if uncond is not None else 1), S.TablePool(), {}, [None] * B, 0, torch.device("cpu")
-    lp.lengths, lp.plens = np.full((lp.rep * B,), T, np.int32), np.full((lp.rep * B,), Lp, np.int32)
-    lp.seeds, lp.scales = np.zeros((B,), np.uint64), np.ones((B,), np.float32)
+def _loop(monkeypatch, precision="fp16", order3=False, stochastic=False, corr=None, uncond=None, B=3, T=66, Lp=5):
+    """an open slot loop of the real constructors on the recording engine (tests/recording_engine.py), tensors on the host; the calls of opening it
+    dropped, so that what the checks below raise from the Python side leaves ``lp.rec.calls`` empty.  ``corr`` = (name, ratio, max_val)."""
+    import recording_engine
+    den, rec = recording_engine.denoiser(monkeypatch, precision)
+    kw = {} if corr is None else dict(correcting_x0_fn=corr[0], dynamic_thresholding_ratio=corr[1], thresholding_max_val=corr[2])
+    lp = den.open_slots(B, T, Lp, order3=order3, stochastic=stochastic, unconditional_prompt=uncond, **kw)
+    lp.dev, lp.rec = torch.device("cpu"), rec
+    rec.calls.clear()
     return lp
 
 
-def test_tail_refusal_names_fp32():
+def test_tail_refusal_names_fp32(monkeypatch):
     from ns2vc_amd.pipeline import slot_tail_needed
     assert slot_tail_needed("fp16", "unipc", 2) == 0 and slot_tail_needed("fp32", "dpmsolver++", 3, 7.0, True) == 0
     assert slot_tail_needed("fp16", "dpmsolver++", 2) == 2 and slot_tail_needed("fp16", "dpmsolver++", 3) == 4
     assert slot_tail_needed("fp16", "unipc", 3) == 1 and slot_tail_needed("fp16", "ddim", 2) == 1
     assert slot_tail_needed("fp16", "unipc", 2, 2.5) == 1            # guided_tail_extra
     assert slot_tail_needed("fp16", "unipc", 2, 1.0, True) == 1      # corrected_tail_min
-    lp = _loop("fp16", order3=True, stochastic=True)
+    lp = _loop(monkeypatch, "fp16", order3=True, stochastic=True)
     assert lp.check_request(U2_6)[0] == S.schedule_key(U2_6)         # the 16-bit default: UniPC order 2, unguided -- tail 0
     for spec in (D3_5, U3_4, DDIM_5, dict(solver="dpmsolver++", steps=6)):
         with pytest.raises(ValueError, match=r'precision="fp32"'):
             lp.check_request(spec)
     with pytest.raises(ValueError, match=r'precision="fp32"'):
-        _loop("fp16", corr=("clamp", 0.995, 1.0)).check_request(U2_6)
+        _loop(monkeypatch, "fp16", corr=("clamp", 0.995, 1.0)).check_request(U2_6)
     with pytest.raises(ValueError, match=r'precision="fp32"'):
-        _loop("fp16", uncond=torch.zeros(1, 2, 256)).check_request(U2_6, 2.5)
-    lp32 = _loop("fp32", order3=True, stochastic=True)
+        _loop(monkeypatch, "fp16", uncond=torch.zeros(1, 2, 256)).check_request(U2_6, 2.5)
+    lp32 = _loop(monkeypatch, "fp32", order3=True, stochastic=True)
     for spec in (U2_6, D3_5, U3_4, DDIM_5):
         key, table, flags = lp32.check_request(spec)
         assert flags == S.table_flags(_table(spec)) and table.steps == _table(spec).steps
     assert [S.table_flags(_table(s)) for s in (U2_6, D3_5, DDIM_5)] == [0, S.ITEM_HIST2, S.ITEM_NOISE]
 
 
-def test_forms_fixed_at_open_are_checked_per_request():
-    lp = _loop("fp32")
+def test_forms_fixed_at_open_are_checked_per_request(monkeypatch):
+    lp = _loop(monkeypatch, "fp32")
     with pytest.raises(ValueError, match="order3=True"):
         lp.check_request(D3_5)
     with pytest.raises(ValueError, match="stochastic=True"):
@@ -314,15 +305,20 @@ def test_forms_fixed_at_open_are_checked_per_request():
     with pytest.raises(ValueError, match="finite"):
         lp.check_request(U2_6, float("nan"))
     with pytest.raises(ValueError, match="ddpm"):
-        _loop("fp32", stochastic=True).check_request(dict(solver="ddpm", steps=10))
+        _loop(monkeypatch, "fp32", stochastic=True).check_request(dict(solver="ddpm", steps=10))
     with pytest.raises(ValueError, match="solver"):
         lp.check_request(dict(solver="heun", steps=4))
+    with pytest.raises(ValueError, match="unipc / dpmsolver"):      # (open_slots itself refuses the pair ...
+        _loop(monkeypatch, "fp32", stochastic=True, corr=("clamp", 0.995, 1.0))
+    both = _loop(monkeypatch, "fp32", stochastic=True)
+    both.corr = ("clamp", 0.995, 1.0)                                # ... and so does the request's own check)
     with pytest.raises(ValueError, match="unipc / dpmsolver"):
-        _loop("fp32", stochastic=True, corr=("clamp", 0.995, 1.0)).check_request(DDIM_5)
+        both.check_request(DDIM_5)
+    assert lp.rec.calls == [] and both.rec.calls == []
 
 
-def test_admit_argument_checks_reach_no_engine_call():
-    lp = _loop("fp32")
+def test_admit_argument_checks_reach_no_engine_call(monkeypatch):
+    lp = _loop(monkeypatch, "fp32")
     c, p, x = torch.zeros(256, 66), torch.zeros(5, 256), torch.zeros(100, 66)
     bad = [(dict(slot=3), "slots must be distinct"), (dict(schedule=None), "needs its schedule"), (dict(content=torch.zeros(256, 70)), "length 70 outside"),
            (dict(length=0), "length 0 outside"), (dict(length=67), "length 67 outside"), (dict(prompt_length=0), "prompt_length 0 outside"),
@@ -342,27 +338,26 @@ def test_admit_argument_checks_reach_no_engine_call():
         lp.take([0])                                                 # (idle)
     assert lp.idle() == [0, 2] and lp.finished() == [] and lp.run.__doc__
     assert lp.pool.rows_in_use() == 0                                # no refusal above left a table acquired
+    assert lp.rec.calls == []                                        # ... or reached the engine
 
 
-def test_continuous_converter_refuses_before_anything_runs():
+def test_continuous_converter_refuses_before_anything_runs(monkeypatch):
     from ns2vc_amd.service import ContinuousConverter, Segment
 
     class _Pre:
         def parameters(self):
             return iter([torch.zeros(1)])
 
-    lp = _loop("fp16")
+    lp = _loop(monkeypatch, "fp16")
     conv = ContinuousConverter(_Pre(), lp.den, slots=3, max_frames=66, max_prompt=5, solver="unipc", steps=4)
     with pytest.raises(ValueError, match="segment 0 has 70 frames"):
         conv.convert([Segment(torch.zeros(256, 70), torch.zeros(100, 5))])
-    assert Segment(torch.zeros(256, 4), torch.zeros(100, 4)).schedule is None and conv.own["steps"] == 4
+    assert Segment(torch.zeros(256, 4), torch.zeros(100, 4)).schedule is None and conv.own["steps"] == 4 and lp.rec.calls == []
 
 
 def test_a_failed_admission_gives_its_tables_back(monkeypatch):
     """whichever engine call of an admission fails -- the rows, the lengths, the condition, the admit itself --, the pool's user counts go back
     and the slot stays idle"""
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
-
     class _Failing:
         def __init__(self, bad):
             self.bad, self.calls = bad, []
@@ -376,12 +371,12 @@ def test_a_failed_admission_gives_its_tables_back(monkeypatch):
 
     c, p, x = torch.zeros(256, 66), torch.zeros(5, 256), torch.zeros(100, 66)
     for bad in ("write_sampler_rows", "set_lengths", "set_prompt_lengths", "set_condition_items", "admit"):
-        lp = _loop("fp32")
+        lp = _loop(monkeypatch, "fp32")
         lp.den.engine = _Failing(bad)
         with pytest.raises(RuntimeError, match=bad):
             lp.admit(0, c, p, x, schedule=U2_6)
         assert lp.den.engine.calls[-1] == bad and lp.pool.rows_in_use() == 0 and lp.idle() == [0, 1, 2], bad
-    lp = _loop("fp32")
+    lp = _loop(monkeypatch, "fp32")
     lp.den.engine = _Failing(None)
     lp.admit(0, c, p, x, schedule=U2_6)
     assert lp.pool.rows_in_use() == 6 and lp.idle() == [1, 2] and lp.den.engine.calls[-1] == "admit"

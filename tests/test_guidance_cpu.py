@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from ns2vc_amd import schedule as S
+from recording_engine import denoiser as _denoiser      # the real Denoiser constructor on the recording engine -> (denoiser, recording)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -106,46 +107,8 @@ def test_guided_x0_select_and_broadcast():
 
 
 # ---- Denoiser: argument errors before anything runs, routing --------------------------------------
-class _Recorder:
-    """stands in for an Engine: records what would reach the device"""
-
-    def __init__(self):
-        self.calls, self.guidance, self.table = [], None, None
-
-    def prepare(self, B, T, Lp):
-        self.calls.append(("prepare", B, T, Lp))
-
-    def set_guidance(self, scales, stream=None):
-        self.calls.append(("set_guidance", None if scales is None else tuple(float(v) for v in scales)))
-        self.guidance = scales
-
-    def load_sampler(self, solver, steps, betas, order, eta, **options):
-        self.table = S.build_table(solver, steps, betas, order, eta, **options)
-        return self.table
-
-    def set_lengths(self, v, stream=None):
-        self.calls.append(("set_lengths", None if v is None else tuple(int(x) for x in v)))
-
-    def set_prompt_lengths(self, v, stream=None):
-        self.calls.append(("set_prompt_lengths", None if v is None else tuple(int(x) for x in v)))
-
-    def set_condition(self, c, p, m, stream=None):
-        self.calls.append(("set_condition", tuple(c.shape), tuple(p.shape), None if m is None else tuple(m.shape)))
-
-    def sample(self, x, use_graph=True, stream=None, tail=None, tail_steps=0):
-        self.calls.append(("sample", tuple(x.shape)))
-
-
-def _denoiser(with_engine=False):
-    from ns2vc_amd.pipeline import Denoiser
-    from ns2vc_amd.spec import UNetConfig
-    d = Denoiser.__new__(Denoiser)
-    d.betas, d.betas64 = S.linear_betas(), S.linear_betas(1000, np.float64)
-    if with_engine:
-        d.cfg, d.engine, d.precision = UNetConfig(), _Recorder(), "fp32"
-        d._shape = d._table_key = d.ln_guard = d.precision_check = d.attn_fallback_limit = d.tail_fp32 = d.tail_engine = None
-        d._ln_pending, d._attn_checked, d.serving_fp32, d._precision_checked = False, True, False, True
-    return d
+def _shapes(args):
+    return tuple(None if v is None else tuple(v[1]) for v in args.values())
 
 
 BAD = [
@@ -163,57 +126,52 @@ BAD = [
 
 
 @pytest.mark.parametrize("kw,match", BAD, ids=[str(i) for i in range(len(BAD))])
-def test_bad_guidance_arguments_raise_before_any_engine_call(kw, match):
-    """an instance without an engine suffices: the checks run in _check_sampler_args, in front of everything"""
-    d = _denoiser()
+def test_bad_guidance_arguments_raise_before_any_engine_call(kw, match, monkeypatch):
+    """the checks run in ``SampleRequest.parse`` / ``check_guidance``, in front of everything: no engine call is recorded"""
+    from ns2vc_amd.request import SampleRequest
+    d, rec = _denoiser(monkeypatch)
     c, p = torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256))
     with pytest.raises(ValueError, match=match):
-        d._check_sampler_args("unipc", 5, 0.0, 2, None, 2, **kw)
+        SampleRequest.parse(d, c, p, solver="unipc", steps=5, **kw)
     with pytest.raises(ValueError, match=match):
         d.sample(c, p, solver="unipc", steps=5, **kw)
     with pytest.raises(ValueError, match=match):
         d.denoise(torch.zeros(2, 100, 16), torch.zeros(2), c, p, **kw)
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
+    assert rec.calls == []
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(guidance_scale=3.0), dict(guidance_scale=1.0, unconditional_prompt=torch.zeros(1, 3, 256)),
                                 dict(guidance_scale=[1.0, 1.0], unconditional_prompt=torch.zeros(2, 3, 256))],
                          ids=["default", "no-uncond", "scale-1", "all-scales-1"])
-def test_unguided_routes_never_prepare_2b(kw, no_device):
+def test_unguided_routes_never_prepare_2b(kw, monkeypatch):
     """every scale 1, or no unconditional prompt: today's B-item path (the reference's short cut, uni_pc.py:222-223)"""
-    d = _denoiser(with_engine=True)
+    d, rec = _denoiser(monkeypatch)
     c, p = torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256))
     y = d.sample(c, p, noise=torch.zeros(2, 100, 16), solver="unipc", steps=5, **kw)
     assert tuple(y.shape) == (2, 100, 16)
-    calls = d.engine.calls
-    assert [k for k in calls if k[0] == "prepare"] == [("prepare", 2, 16, 8)]
-    assert not [k for k in calls if k[0] == "set_guidance"]
-    assert ("set_condition", (2, 256, 16), (2, 8, 256), None) in calls and ("sample", (2, 100, 16)) in calls
+    assert rec.of("prepare") == [dict(B=2, T=16, Lp=8)]
+    assert not rec.of("set_guidance")
+    assert [_shapes(a) for a in rec.of("set_condition")] == [((2, 256, 16), (2, 8, 256), None)] and [a["x"][1] for a in rec.of("sample")] == [[2, 100, 16]]
 
 
-def test_guided_route_prepares_2b_and_builds_the_condition(no_device):
+def test_guided_route_prepares_2b_and_builds_the_condition(monkeypatch):
     """cat([unconditional, conditional]); Lu != Lp: zero-padded to the longer, every row its own frame count; B items in and out"""
-    d = _denoiser(with_engine=True)
+    d, rec = _denoiser(monkeypatch)
     c, p = torch.randn((2, 256, 16)), torch.randn((2, 8, 256))
     u = torch.randn((1, 3, 256))
     y = d.sample(c, p, noise=torch.zeros(2, 100, 16), solver="unipc", steps=5, guidance_scale=[2.5, 1.0], unconditional_prompt=u, lengths=[16, 9])
     assert tuple(y.shape) == (2, 100, 16)
-    calls = d.engine.calls
-    assert calls[0] == ("prepare", 4, 16, 8) and calls[1] == ("set_guidance", (2.5, 1.0))
-    assert ("set_lengths", (16, 9, 16, 9)) in calls and ("set_prompt_lengths", (3, 3, 8, 8)) in calls
-    assert ("set_condition", (4, 256, 16), (4, 8, 256), None) in calls and ("sample", (2, 100, 16)) in calls
+    assert rec.calls[0][1:] == ("prepare", dict(B=4, T=16, Lp=8)) and rec.calls[1][1:] == ("set_guidance", dict(scales=[2.5, 1.0]))
+    assert rec.of("set_lengths") == [dict(lengths=[16, 9, 16, 9])] and rec.of("set_prompt_lengths") == [dict(prompt_lengths=[3, 3, 8, 8])]
+    assert [_shapes(a) for a in rec.of("set_condition")] == [((4, 256, 16), (4, 8, 256), None)] and [a["x"][1] for a in rec.of("sample")] == [[2, 100, 16]]
     from ns2vc_amd.pipeline import Denoiser
     c2, p2, m2, l2, pl2 = Denoiser._guided_condition(c, p, None, None, [8, 5], u, torch.tensor([[True, True, False]]), None, None)
     assert torch.equal(c2, torch.cat([c, c])) and torch.equal(p2[2:], p) and torch.equal(p2[0, :3], u[0]) and not p2[:2, 3:].any()
     assert m2.tolist() == [[True, True, False] + [False] * 5] * 2 + [[True] * 8] * 2 and l2 is None and pl2.tolist() == [3, 3, 8, 5]
-    # a later unguided call on the same instance turns the engine's guidance off again
+    # a later unguided call on the same instance leaves the engine's guidance off again (the B-item prepare clears it, as Engine.prepare does)
+    assert rec.engines[0].guidance is not None
     d.sample(c, p, noise=torch.zeros(2, 100, 16), solver="unipc", steps=5)
-    assert ("set_guidance", None) in d.engine.calls and d.engine.calls[-1] == ("sample", (2, 100, 16))
+    assert rec.names()[-1] == "sample" and rec.engines[0].guidance is None and rec.of("prepare")[-1] == dict(B=2, T=16, Lp=8)
 
 
 def test_guided_tail_extra():

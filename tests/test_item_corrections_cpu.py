@@ -109,55 +109,35 @@ def test_host_statements_refuse_a_corrected_stochastic_item_and_keep_the_dict_fo
         S.run_slots_numpy([[(tabs.table_of(0), 0, x_T[0], SETTINGS[1])]], _x0, (1,) + ITEM, correct_x0=SETTINGS[3])
 
 
-# ---- routing and refusals without a device ------------------------------------------------------------------------
-class _NoEngine:
-    """every engine call is an error: what the checks below raise must come from the Python side"""
-    def __getattr__(self, name):
-        raise AssertionError(f"engine.{name} reached")
-
-
-def _den(precision="fp32"):
-    from ns2vc_amd.pipeline import Denoiser
-    from ns2vc_amd.spec import UNetConfig
-    den = Denoiser.__new__(Denoiser)
-    den.cfg, den.precision, den.betas, den.betas64, den.engine = UNetConfig(), precision, S.linear_betas(), B64, _NoEngine()
-    den.precision_check, den._precision_checked, den._table_key, den.ln_guard = None, True, None, None
-    den._prepare = lambda *a: den.engine.prepare(*a)
-    return den
+# ---- routing and refusals without a device (the recording engine of tests/recording_engine.py) ---------------------
+def _den(monkeypatch, precision="fp32"):
+    """the real constructor on the recording engine; ``den.rec`` is the recording: a refusal from the Python side leaves ``den.rec.calls`` empty"""
+    import recording_engine
+    return recording_engine.denoiser(monkeypatch, precision)[0]
 
 
 DYN = dict(correcting_x0_fn="dynamic_thresholding", thresholding_max_val=0.5, dynamic_thresholding_ratio=0.9)
 CLAMP = dict(correcting_x0_fn="clamp", thresholding_max_val=0.7)
 
 
-def test_sample_routes_equal_entries_to_the_loop_wide_path():
+def test_sample_routes_equal_entries_to_the_loop_wide_path(monkeypatch):
     """B equal entries: the call goes on as ``correcting_x0_fn=`` of that entry (and all None: as no correction at all)"""
-    den = _den()
-    seen = []
-    inner = type(den).sample
-
-    def spy(self, *a, **kw):
-        if "corrections" not in kw or kw["corrections"] is None:
-            seen.append(kw)
-            return "loop-wide"
-        return inner(self, *a, **kw)
-
-    type(den).sample, keep = spy, inner
-    try:
-        c, p = torch.zeros(3, 256, 66), torch.zeros(3, 5, 256)
-        assert den.sample(c, p, steps=4, corrections=[DYN, dict(DYN), DYN]) == "loop-wide"
-        assert seen[-1]["correcting_x0_fn"] == "dynamic_thresholding" and seen[-1]["thresholding_max_val"] == 0.5 and \
-            seen[-1]["dynamic_thresholding_ratio"] == 0.9
-        assert den.sample(c, p, steps=4, corrections=[None, None, None]) == "loop-wide"
-        assert "correcting_x0_fn" not in seen[-1]
-        with pytest.raises(AssertionError, match="engine"):      # different entries go on to the engine: the per-item path
-            den.sample(c, p, steps=4, corrections=[DYN, CLAMP, None])
-    finally:
-        type(den).sample = keep
+    den = _den(monkeypatch)
+    rec = den.rec
+    c, p = torch.zeros(3, 256, 66), torch.zeros(3, 5, 256)
+    den.sample(c, p, steps=4, corrections=[DYN, dict(DYN), DYN])
+    assert rec.of("set_x0_correction") == [dict(mode="dynamic_thresholding", ratio=0.9, max_val=0.5)]
+    assert not rec.of("set_x0_correction_items") and [m for m in rec.names() if m.startswith("load")] == ["load_sampler"]
+    den.sample(c, p, steps=4, corrections=[None, None, None])
+    assert rec.of("set_x0_correction")[1:] == [dict(mode=None, ratio=0.995, max_val=1.0)]      # (off again; nothing else)
+    assert not rec.of("set_x0_correction_items") and [m for m in rec.names() if m.startswith("load")] == ["load_sampler"]
+    den.sample(c, p, steps=4, corrections=[DYN, CLAMP, None])                                   # different entries go on to the engine: the per-item path
+    assert rec.of("set_x0_correction_items") == [dict(modes=["dynamic_thresholding", "clamp", None], ratios=[0.9, 0.995, 0.995], max_vals=[0.5, 0.7, 1.0])]
+    assert len(rec.of("set_x0_correction")) == 2 and [m for m in rec.names() if m.startswith("load")] == ["load_sampler", "load_samplers"]
 
 
-def test_sample_refusals_reach_no_engine_call():
-    den = _den()
+def test_sample_refusals_reach_no_engine_call(monkeypatch):
+    den = _den(monkeypatch)
     c, p = torch.zeros(3, 256, 66), torch.zeros(3, 5, 256)
     with pytest.raises(ValueError, match="exclude each other"):
         den.sample(c, p, steps=4, corrections=[DYN, None, None], correcting_x0_fn="clamp")
@@ -177,34 +157,37 @@ def test_sample_refusals_reach_no_engine_call():
         den.sample(c, p, steps=4, corrections=[None, dict(CLAMP, ratio=0.5), None])
     with pytest.raises(ValueError, match="ddim"):      # a corrected ddim call without schedules=
         den.sample(c, p, solver="ddim", steps=5, eta=1.0, corrections=[DYN, None, None])
+    assert den.rec.calls == []
 
 
-def _loop(precision="fp16", item_corrections=True, stochastic=True, order3=True, B=3, T=66, Lp=5):
-    from ns2vc_amd.pipeline import SlotLoop
-    lp = SlotLoop.__new__(SlotLoop)
-    lp.den, lp.B, lp.T, lp.Lp, lp.use_graph, lp.order3, lp.stochastic, lp.corr, lp.uncond = _den(precision), B, T, Lp, True, order3, stochastic, None, None
-    lp.require_tail_free, lp.item_corrections, lp.corrections = True, item_corrections, [None] * B
-    lp.rep, lp.pool, lp._tables, lp.items, lp.step, lp.dev = 1, S.TablePool(), {}, [None] * B, 0, torch.device("cpu")
+def _loop(monkeypatch, precision="fp16", item_corrections=True, stochastic=True, order3=True, B=3, T=66, Lp=5):
+    """an open slot loop on the recording engine (tensors on the host); the calls of opening it dropped"""
+    den = _den(monkeypatch, precision)
+    lp = den.open_slots(B, T, Lp, order3=order3, stochastic=stochastic, item_corrections=item_corrections)
+    lp.dev = torch.device("cpu")
+    den.rec.calls.clear()
     return lp
 
 
-def test_open_slots_refuses_item_corrections_with_the_loop_wide_setting():
+def test_open_slots_refuses_item_corrections_with_the_loop_wide_setting(monkeypatch):
+    den = _den(monkeypatch)
     with pytest.raises(ValueError, match="exclude each other"):
-        _den().open_slots(3, 66, 5, item_corrections=True, correcting_x0_fn="clamp")
+        den.open_slots(3, 66, 5, item_corrections=True, correcting_x0_fn="clamp")
     from ns2vc_amd.service import ContinuousConverter
     with pytest.raises(ValueError, match="exclude each other"):
-        ContinuousConverter(None, _den(), slots=3, max_frames=66, max_prompt=5, item_corrections=True, correcting_x0_fn="clamp")
+        ContinuousConverter(None, den, slots=3, max_frames=66, max_prompt=5, item_corrections=True, correcting_x0_fn="clamp")
+    assert den.rec.calls == []
 
 
-def test_slot_tail_needed_is_applied_per_request():
-    lp = _loop("fp16")
+def test_slot_tail_needed_is_applied_per_request(monkeypatch):
+    lp = _loop(monkeypatch, "fp16")
     assert lp.check_request(U2_4)[0] == S.schedule_key(U2_4)                       # uncorrected UniPC order 2 at fp16: no tail
     assert lp.check_request(U2_4, 1.0, None)[0] == S.schedule_key(U2_4)
     with pytest.raises(ValueError, match=r'corrected\) needs 1 trailing fp32 evaluation.*precision="fp32"'):
         lp.check_request(U2_4, 1.0, CLAMP)                                          # THIS request is corrected: corrected_tail_min
     lp.require_tail_free = False
     assert lp.check_request(U2_4, 1.0, CLAMP)[0] == S.schedule_key(U2_4)
-    lp32 = _loop("fp32")
+    lp32 = _loop(monkeypatch, "fp32")
     for spec in (U2_4, U3_5, D3_6):
         assert lp32.check_request(spec, 1.0, DYN)[2] == S.table_flags(lp32._table(S.schedule_key(spec)))
     assert lp32.check_request(DDIM_5, 1.0, None)[2] == S.ITEM_NOISE              # stochastic and corrected requests share the loop ...
@@ -213,13 +196,14 @@ def test_slot_tail_needed_is_applied_per_request():
     with pytest.raises(ValueError, match="callable"):
         lp32.check_request(U2_4, 1.0, lambda m: m)
     with pytest.raises(ValueError, match="item_corrections=True"):
-        _loop("fp32", item_corrections=False).check_request(U2_4, 1.0, CLAMP)
+        _loop(monkeypatch, "fp32", item_corrections=False).check_request(U2_4, 1.0, CLAMP)
+    lp32 = _loop(monkeypatch, "fp32")
     c, p, x = torch.zeros(256, 66), torch.zeros(5, 256), torch.zeros(100, 66)
     with pytest.raises(ValueError, match="ddim / ddpm have no correction"):       # through admit: no engine call is reached
         lp32.admit(0, c, p, x, schedule=DDIM_5, correction=CLAMP)
     with pytest.raises(ValueError, match="one correction"):
         lp32.admit_group([0, 1], [c, c], [p, p], [x, x], schedules=[U2_4, U2_4], corrections=[CLAMP])
-    assert lp32.pool.rows_in_use() == 0 and lp32.corrections == [None] * 3
+    assert lp32.pool.rows_in_use() == 0 and lp32.corrections == [None] * 3 and lp32.den.rec.calls == []
 
 
 def test_segment_correction_defaults_to_none():

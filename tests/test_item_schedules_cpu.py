@@ -12,6 +12,7 @@ import torch
 
 from ns2vc_amd import noise as N
 from ns2vc_amd import schedule as S
+from recording_engine import denoiser as _denoiser      # the real Denoiser constructor on the recording engine -> (denoiser, recording)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B64 = S.linear_betas(1000, np.float64)
@@ -99,55 +100,7 @@ def test_build_tables_dedupes_right_aligns_and_keeps_rows():
             S.build_tables([SPECS[0], bad])
 
 
-# ---- Denoiser.sample(schedules=): argument errors and routing (a recording engine, no device) -------------------------
-class _Recorder:
-    def __init__(self):
-        self.calls, self.guidance, self.table, self.tables, self.x0_correction = [], None, None, None, None
-
-    def prepare(self, B, T, Lp):
-        self.calls.append(("prepare", B, T, Lp))
-
-    def set_guidance(self, scales, stream=None):
-        self.guidance = scales
-
-    def load_sampler(self, solver, steps, betas, order, eta, **options):
-        self.calls.append(("load_sampler", solver, steps, order, eta, tuple(sorted(options.items()))))
-        self.table, self.tables = S.build_table(solver, steps, betas, order, eta, **options), None
-        return self.table
-
-    def load_samplers(self, tabs, stream=None):
-        self.calls.append(("load_samplers", tabs.keys))
-        self.tables, self.table = tabs, None
-        return tabs
-
-    def set_seeds(self, seeds, stream=None):
-        self.calls.append(("set_seeds", len(seeds)))
-
-    def set_lengths(self, v, stream=None):
-        pass
-
-    def set_prompt_lengths(self, v, stream=None):
-        pass
-
-    def set_condition(self, c, p, m, stream=None):
-        pass
-
-    def sample(self, x, use_graph=True, stream=None, tail=None, tail_steps=0):
-        self.calls.append(("sample", tuple(x.shape)))
-
-
-def _denoiser(with_engine=False):
-    from ns2vc_amd.pipeline import Denoiser
-    from ns2vc_amd.spec import UNetConfig
-    d = Denoiser.__new__(Denoiser)
-    d.betas, d.betas64 = S.linear_betas(), B64
-    if with_engine:
-        d.cfg, d.engine, d.precision = UNetConfig(), _Recorder(), "fp32"
-        d._shape = d._table_key = d.ln_guard = d.precision_check = d.attn_fallback_limit = d.tail_fp32 = d.tail_engine = None
-        d._ln_pending, d._attn_checked, d.serving_fp32, d._precision_checked = False, True, False, True
-    return d
-
-
+# ---- Denoiser.sample(schedules=): argument errors and routing (the recording engine of tests/recording_engine.py, no device) ---------
 BAD = [(dict(schedules=[SPECS[0]]), "one schedule .* per item"),
        (dict(schedules=SPECS[0]), "one schedule .* per item"),
        (dict(schedules=[SPECS[0], dict(solver="unipc", steps=5, stride=2)]), r"schedules\[1\].*stride"),
@@ -159,41 +112,40 @@ BAD = [(dict(schedules=[SPECS[0]]), "one schedule .* per item"),
 
 
 @pytest.mark.parametrize("kw,match", BAD, ids=[str(i) for i in range(len(BAD))])
-def test_bad_schedules_raise_before_any_engine_call(kw, match):
-    d = _denoiser()
+def test_bad_schedules_raise_before_any_engine_call(kw, match, monkeypatch):
+    d, rec = _denoiser(monkeypatch)
     with pytest.raises(ValueError, match=match):
         d.sample(torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256)), solver="unipc", steps=5, **kw)
+    assert rec.calls == []
 
 
-@pytest.fixture
-def no_device(monkeypatch):
-    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
+def _loads(rec):
+    return [(m, a) for _, m, a in rec.calls if m.startswith("load")]
 
 
-def test_equal_schedules_take_the_shared_table_path(no_device):
-    d = _denoiser(with_engine=True)
+def test_equal_schedules_take_the_shared_table_path(monkeypatch):
+    d, rec = _denoiser(monkeypatch)
     c, p, x = torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256)), torch.zeros(2, 100, 16)
     d.sample(c, p, noise=x, solver="unipc", steps=9, schedules=[SPECS[1], dict(SPECS[1])])
     d.sample(c, p, noise=x, solver="dpmsolver++", steps=5, order=3, skip_type="logSNR", schedules=[None, SPECS[1]])     # None = the call's own
-    loads = [k for k in d.engine.calls if k[0].startswith("load")]
-    assert loads == [("load_sampler", "dpmsolver++", 5, 3, 0.0, (("skip_type", "logSNR"),))]          # (the second call finds the table loaded)
-    assert d.engine.tables is None and [k for k in d.engine.calls if k[0] == "sample"] == [("sample", (2, 100, 16))] * 2
+    (name, a), = _loads(rec)                                                                                 # (the second call finds the table loaded)
+    assert (name, a["solver"], a["steps"], a["order"], a["eta"], a["options"]) == ("load_sampler", "dpmsolver++", 5, 3, 0.0, dict(skip_type="logSNR"))
+    assert rec.engines[0].tables is None and [a["x"][1] for a in rec.of("sample")] == [[2, 100, 16]] * 2
 
 
-def test_mixed_schedules_take_the_per_item_path(no_device):
-    d = _denoiser(with_engine=True)
+def test_mixed_schedules_take_the_per_item_path(monkeypatch):
+    d, rec = _denoiser(monkeypatch)
     c, p, x = torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256)), torch.zeros(2, 100, 16)
     d.sample(c, p, noise=x, solver="unipc", steps=6, schedules=[None, SPECS[3]], seeds=[1, 2])
-    calls = d.engine.calls
-    assert [k[0] for k in calls if k[0].startswith("load")] == ["load_samplers"] and ("set_seeds", 2) in calls and calls[-1] == ("sample", (2, 100, 16))
-    assert d.engine.tables.keys == (S.schedule_key(SPECS[0]), S.schedule_key(SPECS[3])) and d.engine.tables.start.tolist() == [0, 1]
+    assert [m for m, _ in _loads(rec)] == ["load_samplers"] and rec.of("set_seeds") == [dict(seeds=[1, 2])] and rec.names()[-1] == "sample"
+    eng = rec.engines[0]
+    assert eng.tables.keys == (S.schedule_key(SPECS[0]), S.schedule_key(SPECS[3])) and eng.tables.start.tolist() == [0, 1]
     d.sample(c, p, noise=x, solver="unipc", steps=6, schedules=[None, SPECS[3]], seeds=[1, 2])           # the same schedules: nothing is loaded again
     d.sample(c, p, noise=x, solver="unipc", steps=6)                                                      # and back to a shared table
-    assert [k[0] for k in d.engine.calls if k[0].startswith("load")] == ["load_samplers", "load_sampler"]
+    assert [m for m, _ in _loads(rec)] == ["load_samplers", "load_sampler"]
 
 
-def test_default_tail_is_the_largest_any_item_asks_for(no_device):
+def test_default_tail_is_the_largest_any_item_asks_for():
     from ns2vc_amd.pipeline import default_tail_fp32
     assert max(default_tail_fp32(k[0], k[2]) for k in S.build_tables(SPECS, None, B64).keys) == 4      # DPM-Solver++(3M)
     assert max(default_tail_fp32(k[0], k[2]) for k in S.build_tables([SPECS[0], SPECS[2]]).keys) == 1  # UniPC-3

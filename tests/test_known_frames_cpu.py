@@ -153,61 +153,11 @@ def test_plan_chunks_refuses_bad_arguments():
             S.plan_chunks(*args)
 
 
-# ---- Denoiser.sample on a stub engine ------------------------------------------------------------------------------------------------------
-class _Recorder:
-    """stands in for an Engine: records what would reach the device"""
-
-    def __init__(self):
-        self.calls, self.guidance, self.table, self.x0_correction, self.hold = [], None, None, None, None
-
-    def prepare(self, B, T, Lp):
-        self.calls.append(("prepare", B, T, Lp))
-
-    def set_guidance(self, scales, stream=None):
-        self.guidance = scales
-
-    def set_x0_correction(self, mode=None, ratio=0.995, max_val=1.0):
-        self.calls.append(("set_x0_correction", mode))
-        self.x0_correction = None if mode is None else (mode, ratio, max_val)
-
-    def set_known(self, known=None, mask=None, stream=None):
-        self.calls.append(("set_known", None if known is None else tuple(known.shape), None if mask is None else np.array(mask)))
-        self.hold = None if mask is None else np.array(mask)
-
-    def load_sampler(self, solver, steps, betas, order, eta, **options):
-        self.calls.append(("load_sampler", solver, steps))
-        self.table = S.build_table(solver, steps, betas, order, eta, **options)
-        return self.table
-
-    def set_lengths(self, v, stream=None):
-        self.calls.append(("set_lengths", None if v is None else tuple(int(i) for i in v)))
-
-    def set_prompt_lengths(self, v, stream=None):
-        pass
-
-    def set_condition(self, c, p, m, stream=None):
-        pass
-
-    def sample(self, x, use_graph=True, stream=None, tail=None, tail_steps=0):
-        self.calls.append(("sample", tuple(x.shape), x.clone()))
-
-    def open_slots(self, history2=False, noise=False, stream=None, item_corrections=False):
-        if self.hold is not None:      # (what ns2vc_sampler_open and ns2vc_sampler_set_x0_correction_items say while a hold is on)
-            raise RuntimeError("known frames are held (ns2vc_sampler_set_known): a slot loop does not run with them")
-        self.calls.append(("open_slots", item_corrections))
-
-
+# ---- Denoiser.sample on the recording engine (tests/recording_engine.py) ----------------------------------------------------------------
 def _denoiser(monkeypatch):
-    from ns2vc_amd.pipeline import Denoiser
-    from ns2vc_amd.spec import UNetConfig
-    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
-    d = Denoiser.__new__(Denoiser)
-    d.betas, d.betas64 = S.linear_betas(), S.linear_betas(1000, np.float64)
-    d.cfg, d.engine, d.precision = UNetConfig(), _Recorder(), "fp32"
-    d._shape = d._table_key = d.ln_guard = d.precision_check = d.attn_fallback_limit = d.tail_fp32 = d.tail_engine = None
-    d._ln_pending, d._attn_checked, d.serving_fp32, d._precision_checked = False, True, False, True
-    return d
+    """the real constructor on the recording engine; ``d.rec`` is the recording"""
+    import recording_engine
+    return recording_engine.denoiser(monkeypatch)[0]
 
 
 def _args(n=2, t=16):
@@ -237,48 +187,49 @@ def test_every_refusal_raises_before_any_engine_call(monkeypatch):
     for kw, match in bad:
         with pytest.raises(ValueError, match=match):
             d.sample(c, p, noise=x, solver="unipc", steps=5, **kw)
-    assert d.engine.calls == []
+    assert d.rec.calls == []
     d.sample(c, p, noise=x, solver="unipc", steps=5, known=k, known_mask=m, lengths=[3, 16])      # (the last held frame is the item's last)
-    assert any(call[0] == "set_known" for call in d.engine.calls)
+    assert d.rec.of("set_known")
 
 
 def test_an_all_false_mask_routes_to_the_plain_call(monkeypatch):
+    import recording_engine as R
     d = _denoiser(monkeypatch)
+    rec, eng = d.rec, d.engine
     c, p, x, k, m = _args()
     d.sample(c, p, noise=x, solver="unipc", steps=5, known=k, known_mask=np.zeros_like(m))
-    assert not [call for call in d.engine.calls if call[0] == "set_known"]
-    assert torch.equal(d.engine.calls[-1][2], x)                                      # x_T untouched
+    assert not rec.of("set_known")
+    assert rec.of("sample")[-1]["x"] == R.digest(x)                                     # x_T untouched
     # held: the mask reaches the engine after its lengths, x_T is known_start, and a later plain call switches the hold off again
     d.sample(c, p, noise=x, solver="unipc", steps=5, known=k, known_mask=m, lengths=[16, 9])
-    names = [call[0] for call in d.engine.calls]
+    names = rec.names()
     i = max(j for j, n in enumerate(names) if n == "set_known")
     assert "set_lengths" in names[:i] and names[i + 1] == "sample"
-    assert np.array_equal(d.engine.calls[i][2], m) and d.engine.calls[i][1] == (2, 100, 16)
-    want = S.known_start(x.numpy(), k.numpy(), m, d.engine.table.coef[0])
-    assert np.array_equal(d.engine.calls[-1][2].numpy(), want)
+    assert rec.calls[i][2]["mask"] == R.digest(m) and rec.calls[i][2]["known"][1] == [2, 100, 16]
+    want = S.known_start(x.numpy(), k.numpy(), m, eng.table.coef[0])
+    assert rec.of("sample")[-1]["x"] == R.digest(want)
     d.sample(c, p, noise=x, solver="unipc", steps=5)
-    assert d.engine.calls[-2][0] == "set_known" and d.engine.calls[-2][1] is None and d.engine.hold is None
+    assert rec.calls[-2][1:] == ("set_known", dict(known=None, mask=None)) and eng.hold is None
     # a correction after a hold: the hold goes first (the engine refuses the pair)
     d.sample(c, p, noise=x, solver="unipc", steps=5, known=k, known_mask=m)
     d.sample(c, p, noise=x, solver="unipc", steps=5, correcting_x0_fn="clamp")
-    names = [call[0] for call in d.engine.calls]
+    names = rec.names()
     j = max(q for q, n in enumerate(names) if n == "set_x0_correction")
-    assert names[j - 1] == "set_known" and d.engine.calls[j - 1][1] is None
+    assert rec.calls[j - 1][1:] == ("set_known", dict(known=None, mask=None))
 
 
 @pytest.mark.parametrize("item_corrections", [False, True])
 def test_open_slots_after_a_held_call_at_the_same_shape(monkeypatch, item_corrections):
     """the hold an earlier sample(known=) left in the engine is switched off before the slot loop opens (same shape: no prepare clears it)"""
     d = _denoiser(monkeypatch)
-    monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
     c, p, x, k, m = _args()
     d.sample(c, p, noise=x, solver="unipc", steps=5, known=k, known_mask=m)
     assert d.engine.hold is not None
     d.open_slots(2, 16, 8, item_corrections=item_corrections)
-    names = [call[0] for call in d.engine.calls]
+    names = d.rec.names()
     assert names[-1] == "open_slots" and d.engine.hold is None
     i = max(j for j, n in enumerate(names) if n == "set_known")
-    assert d.engine.calls[i][1] is None and i > names.index("sample")
+    assert d.rec.calls[i][2] == dict(known=None, mask=None) and i > names.index("sample")
     assert names.count("prepare") == 1                                                # (the shape did not change)
 
 
@@ -286,7 +237,7 @@ def test_an_all_false_mask_with_a_correction_is_the_corrected_call(monkeypatch):
     d = _denoiser(monkeypatch)
     c, p, x, k, m = _args()
     d.sample(c, p, noise=x, solver="unipc", steps=5, known=k, known_mask=np.zeros_like(m), correcting_x0_fn="clamp")
-    assert d.engine.x0_correction is not None and not [call for call in d.engine.calls if call[0] == "set_known"]
+    assert d.engine.x0_correction is not None and not d.rec.of("set_known")
 
 
 def test_sample_long_chains_the_chunks(monkeypatch):

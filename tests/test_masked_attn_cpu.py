@@ -94,10 +94,12 @@ def test_library_reports_attn_struct_size():
     assert lib.ns2vc_sizeof_attn_args() == C.sizeof(_lib.AttnArgs)
 
 
-def test_python_surface_passes_the_option_on():
+def test_python_surface_passes_the_option_on(monkeypatch):
     import inspect
+    import recording_engine
     from ns2vc_amd.pipeline import Denoiser
     from ns2vc_amd.service import GroupedConverter
     assert inspect.signature(Denoiser.__init__).parameters["masked_attn"].default is False
     assert inspect.signature(GroupedConverter.__init__).parameters["masked_attn"].default is None
+    recording_engine.check_masked_option(monkeypatch, "masked_attn")      # the constructor, set_option and the default, on both engines
     assert "--masked-attn" in open(os.path.join(ROOT, "tools", "ragged_bench.py")).read()

@@ -88,12 +88,12 @@ def test_library_reports_ffn_struct_size():
     assert lib.ns2vc_abi_version() == 7
 
 
-def test_python_surface_passes_the_option_on():
+def test_python_surface_passes_the_option_on(monkeypatch):
     import inspect
+    import recording_engine
     from ns2vc_amd.pipeline import Denoiser
     from ns2vc_amd.service import GroupedConverter
     assert inspect.signature(Denoiser.__init__).parameters["masked_ffn"].default is False
     assert inspect.signature(GroupedConverter.__init__).parameters["masked_ffn"].default is None
-    src = inspect.getsource(Denoiser)
-    assert '"masked_ffn")' in src and src.count('set_option("masked_ffn", True)') == 2      # set_option's list; the engine and the tail engine
+    recording_engine.check_masked_option(monkeypatch, "masked_ffn")      # the constructor, set_option and the default, on both engines
     assert "--masked-ffn" in open(os.path.join(ROOT, "tools", "ragged_bench.py")).read()

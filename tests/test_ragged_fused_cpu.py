@@ -77,3 +77,8 @@ def test_library_reports_struct_size():
     assert "ns2vc_sizeof_gemm_args" in open(src).read()
     lib = _lib.load()
     assert lib.ns2vc_sizeof_gemm_args() == C.sizeof(_lib.GemmArgs)
+
+
+def test_python_surface_passes_the_option_on(monkeypatch):
+    import recording_engine
+    recording_engine.check_masked_option(monkeypatch, "masked_fuse")

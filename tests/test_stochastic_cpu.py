@@ -161,11 +161,10 @@ def test_discrete_table_errors():
         S.run_table_numpy(t, synthetic_x0, np.zeros((1, 4, 3), np.float32))
 
 
-def test_denoiser_rejects_misuse_before_running():
-    """argument errors of Denoiser.sample surface before any device work (an instance without an engine suffices)"""
-    from ns2vc_amd.pipeline import Denoiser
-    d = Denoiser.__new__(Denoiser)
-    d.betas64 = S.linear_betas(1000, np.float64)
+def test_denoiser_rejects_misuse_before_running(monkeypatch):
+    """argument errors of Denoiser.sample surface before any device work: the recording engine (tests/recording_engine.py) sees no call"""
+    import recording_engine
+    d, rec = recording_engine.denoiser(monkeypatch)
     c, p = torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256))
     with pytest.raises(ValueError, match="ddpm"):
         d.sample(c, p, solver="ddpm", steps=50)
@@ -177,3 +176,4 @@ def test_denoiser_rejects_misuse_before_running():
         d.sample(c, p, solver="ddpm", seeds=[1, 2, 3])
     with pytest.raises(ValueError, match="solver"):
         d.sample(c, p, solver="euler")
+    assert rec.calls == []

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from ns2vc_amd import schedule as S
+from recording_engine import denoiser as _denoiser      # the real Denoiser constructor on the recording engine -> (denoiser, recording)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -230,31 +231,25 @@ BAD = [
 ]
 
 
-def _denoiser():
-    from ns2vc_amd.pipeline import Denoiser
-    d = Denoiser.__new__(Denoiser)
-    d.betas, d.betas64 = S.linear_betas(), S.linear_betas(1000, np.float64)
-    d._table_key = None
-    return d
-
-
 @pytest.mark.parametrize("kw,match", BAD, ids=[str(i) for i in range(len(BAD))])
-def test_bad_correction_keywords_raise_before_any_engine_call(kw, match):
-    """an instance without an engine suffices: the checks run in front of everything"""
-    d = _denoiser()
+def test_bad_correction_keywords_raise_before_any_engine_call(kw, match, monkeypatch):
+    """the checks run in front of everything: no engine call is recorded"""
+    d, rec = _denoiser(monkeypatch)
     c, p = torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256))
     with pytest.raises(ValueError, match=match):
         d.sample(c, p, solver="unipc", steps=5, **kw)
+    assert rec.calls == []
     with pytest.raises(ValueError, match=match):
         S.check_x0_correction(kw.get("correcting_x0_fn"), kw.get("dynamic_thresholding_ratio", 0.995), kw.get("thresholding_max_val", 1.0), names_only=True)
 
 
 @pytest.mark.parametrize("solver", ["ddim", "ddpm"])
-def test_correction_is_refused_for_the_discrete_samplers(solver):
-    d = _denoiser()
+def test_correction_is_refused_for_the_discrete_samplers(solver, monkeypatch):
+    d, rec = _denoiser(monkeypatch)
     c, p = torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256))
     with pytest.raises(ValueError, match="unipc / dpmsolver"):
         d.sample(c, p, solver=solver, steps=None if solver == "ddpm" else 5, correcting_x0_fn="clamp")
+    assert rec.calls == []
     from ns2vc_amd.pipeline import OverlappedPipeline                                       # noqa: F401  (needs a device to construct)
     from ns2vc_amd.service import GroupedConverter
     with pytest.raises(ValueError, match="unipc / dpmsolver"):
@@ -271,31 +266,19 @@ def test_corrected_tail_min_is_the_stated_rule():
         assert 2 * e1 / 3 ** n <= PARITY_BAR < 2 * e1 / 3 ** (n - 1)
 
 
-class _Tail:
-    def __init__(self):
-        self.steps = []
-
-
 def test_denoiser_raises_the_default_tail_under_a_correction(monkeypatch):
     """fp16 UniPC order 2: no default tail; 1 under a correction; tail_fp32= still overrides; DPM-Solver++(3M)'s 4 stay 4"""
-    from ns2vc_amd.spec import UNetConfig
-    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
-    d = _denoiser()
-    d.cfg, d.engine, d.precision = UNetConfig(), _Recorder(), "fp16"
-    d._shape = d._table_key = d.ln_guard = d.precision_check = d.attn_fallback_limit = d.tail_fp32 = d.tail_engine = None
-    d._ln_pending, d._attn_checked, d.serving_fp32, d._precision_checked = False, True, False, True
-    seen = []
-    d._tail = lambda solver, steps, order, n_tail, eta=0.0, **o: seen.append(n_tail)
+    d, rec = _denoiser(monkeypatch, "fp16")
     c, p, x = torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256)), torch.zeros(2, 100, 16)
     on = dict(correcting_x0_fn="dynamic_thresholding")
     d.sample(c, p, noise=x, solver="unipc", steps=6)
     d.sample(c, p, noise=x, solver="unipc", steps=6, **on)
     d.sample(c, p, noise=x, solver="unipc", steps=6, tail_fp32=0, **on)
     d.sample(c, p, noise=x, solver="dpmsolver++", steps=6, order=3, **on)
-    d.precision = "bf16"
+    d, rec16 = _denoiser(monkeypatch, "bf16")
     d.sample(c, p, noise=x, solver="unipc", steps=6, correcting_x0_fn="clamp")
-    assert seen == [0, 1, 0, 4, 3]
+    assert [a["tail_steps"] for a in rec.of("sample") + rec16.of("sample")] == [0, 1, 0, 4, 3]
+    assert [a["tail"] for a in rec.of("sample") + rec16.of("sample")] == [None, "tail", None, "tail", "tail"]
 
 
 def test_engine_set_x0_correction_validates_on_the_host():
@@ -307,61 +290,24 @@ def test_engine_set_x0_correction_validates_on_the_host():
             e.set_x0_correction(*a)
 
 
-class _Recorder:
-    """stands in for an Engine: records what would reach the device"""
-
-    def __init__(self):
-        self.calls, self.guidance, self.table, self.x0_correction = [], None, None, None
-
-    def prepare(self, B, T, Lp):
-        self.calls.append(("prepare", B, T, Lp))
-
-    def set_guidance(self, scales, stream=None):
-        self.guidance = scales
-
-    def set_x0_correction(self, mode=None, ratio=0.995, max_val=1.0):
-        m = S.check_x0_correction(mode, ratio, max_val)
-        self.calls.append(("set_x0_correction", mode, ratio, max_val))
-        self.x0_correction = None if m == 0 else (m, ratio, max_val)
-
-    def load_sampler(self, solver, steps, betas, order, eta, **options):
-        self.table = S.build_table(solver, steps, betas, order, eta, **options)
-        return self.table
-
-    def set_lengths(self, v, stream=None):
-        pass
-
-    def set_prompt_lengths(self, v, stream=None):
-        pass
-
-    def set_condition(self, c, p, m, stream=None):
-        pass
-
-    def sample(self, x, use_graph=True, stream=None, tail=None, tail_steps=0):
-        self.calls.append(("sample", tuple(x.shape)))
-
-
 def test_denoiser_routes_the_keywords_to_the_engine(monkeypatch):
     """on: set before the loop with the three values; the defaults reach nothing; a later call without the keywords turns it off again"""
-    from ns2vc_amd.spec import UNetConfig
-    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
-    d = _denoiser()
-    d.cfg, d.engine, d.precision = UNetConfig(), _Recorder(), "fp32"
-    d._shape = d._table_key = d.ln_guard = d.precision_check = d.attn_fallback_limit = d.tail_fp32 = d.tail_engine = None
-    d._ln_pending, d._attn_checked, d.serving_fp32, d._precision_checked = False, True, False, True
+    d, rec = _denoiser(monkeypatch)
     c, p, x = torch.zeros((2, 256, 16)), torch.zeros((2, 8, 256)), torch.zeros(2, 100, 16)
     d.sample(c, p, noise=x, solver="unipc", steps=5)
     d.sample(c, p, noise=x, solver="unipc", steps=5, thresholding_max_val=2.0, dynamic_thresholding_ratio=0.5)      # off: the values go nowhere
-    assert not [k for k in d.engine.calls if k[0] == "set_x0_correction"]
+    assert not rec.of("set_x0_correction")
     d.sample(c, p, noise=x, solver="dpmsolver++", steps=5, order=3, correcting_x0_fn="dynamic_thresholding", thresholding_max_val=2.0,
              dynamic_thresholding_ratio=0.9)
-    i = d.engine.calls.index(("set_x0_correction", "dynamic_thresholding", 0.9, 2.0))
-    assert d.engine.calls[i + 1] == ("sample", (2, 100, 16)) and d.engine.x0_correction == (1, 0.9, 2.0)
+    assert rec.of("set_x0_correction") == [dict(mode="dynamic_thresholding", ratio=0.9, max_val=2.0)]
+    names = rec.names()
+    assert names.index("set_x0_correction") < len(names) - 1 and names[-1] == "sample" and "sample" not in names[names.index("set_x0_correction"):-1]
+    assert rec.engines[0].x0_correction == (1, float(np.float32(0.9)), 2.0)
     d.sample(c, p, noise=x, solver="unipc", steps=5, correcting_x0_fn="clamp")
-    assert d.engine.x0_correction == (2, 0.995, 1.0)
+    assert rec.engines[0].x0_correction == (2, float(np.float32(0.995)), 1.0)
     d.sample(c, p, noise=x, solver="unipc", steps=5)
-    assert d.engine.calls[-2] == ("set_x0_correction", None, 0.995, 1.0) and d.engine.x0_correction is None
+    assert rec.of("set_x0_correction")[-1] == dict(mode=None, ratio=0.995, max_val=1.0) and rec.engines[0].x0_correction is None
+    assert "sample" not in rec.names()[len(rec.names()) - 1 - rec.names()[::-1].index("set_x0_correction"):-1]      # (off before the last loop ran)
 
 
 def test_grouped_converter_and_sharded_pass_the_keywords_through():
