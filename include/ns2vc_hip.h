@@ -771,6 +771,40 @@ int ns2vc_k_sampler_take(const float* xe, int ld, int C, int T, int n, const int
  * engine: n * T unconditional rows, then n * T conditional rows) writes the same values to rows r and r + n * T; halves = 1 to row r alone. */
 int ns2vc_k_hold_x0(float* x0, const float* known_rows, const uint8_t* mask_host, int n, int T, int ld, int nc, int halves, void* stream);
 
+/* ---- Known frames in a slot loop (backward-compatible additions to ABI v7) -----------------------------------------------------
+ * ns2vc_sampler_open_known: ns2vc_sampler_open, and in addition every SLOT gets known-frame state for the whole prepared shape, outside the plan
+ * arena: known rows [loop items * T][padded channels] fp32, channels-last like x0, and one mask byte per frame, all clear.  The captured step
+ * then has one more launch between the plan's last launch and the solver update: one wave per 64 consecutive rows b * T + t reads 64 mask bytes,
+ * returns when none is set, and otherwise copies the held rows from the known rows into x0 (pad columns zero, both halves of a guided engine) --
+ * ns2vc_sampler_set_known's rule, with the rows given by the mask instead of a list, so an admission changes its own slot's bytes only and never
+ * recaptures.  The form is part of the step graph: opening with it after a loop without it (or the other way round, by a later plain
+ * ns2vc_sampler_open) captures again.  Refused: a loop-wide x0 correction or the per-item correction table being on (a correction would rescale
+ * held frames; the two setters refuse while such a loop is open), and a closed-loop hold that is on (ns2vc_sampler_set_known), as
+ * ns2vc_sampler_open refuses it.  ns2vc_sampler_end ends the slots' known frames with the loop (the host mirror goes, the next open clears every
+ * mask) but leaves the form baked, so that the next ns2vc_sampler_open_known replays the step graph; a step run in between is refused.
+ * ns2vc_unet_prepare, ns2vc_sampler_load / _load_items / _begin (which leave slot mode) and a change of guidance on / off drop the form too,
+ * and with it the step graph.  ns2vc_sampler_handoff and option fuse_solver refuse slot loops as before.
+ *
+ * ns2vc_sampler_set_known_items: the known frames of n listed IDLE slots (HOST list, no repeats; n counts loop items under guidance).  known_nct =
+ * DEVICE fp32 [n][latent][T], mask_nt = HOST [n][T] bytes (nonzero = held).  The mask travels through the slot loop's pinned staging ring and ONE
+ * launch, which reads the slot list from device memory, transposes the latent into the slots' known rows and writes their mask bytes: the call
+ * never waits for the device and never allocates.  Both NULL clears the listed slots' masks.  Set the slots' lengths first.  Refused: no slot loop,
+ * or one opened without the form; a busy slot; a slot outside the range; a held frame at or past the slot's applied length (ns2vc_sampler_admit
+ * checks again, against a host mirror of each slot's last held frame, so lengths set afterwards are caught).  A slot's known frames last for
+ * exactly ONE request: in a loop of this form ns2vc_sampler_take clears the masks of the slots it takes, by a second launch in the same call. */
+int ns2vc_sampler_open_known(ns2vc_unet* h, int history2, int noise, void* stream);
+int ns2vc_sampler_set_known_items(ns2vc_unet* h, int n, const int32_t* slots, const float* known_nct, const uint8_t* mask_nt, void* stream);
+/* test hooks of the two kernels; both wait for `stream`.
+ * ns2vc_k_hold_slots: the step's launch alone.  x0 = DEVICE fp32 rows [halves * n * T][ld], known_rows = DEVICE fp32 rows [n * T][ld] (ld % 4 == 0,
+ * both 16-byte aligned), mask_host = HOST [n][T] bytes, copied to the device for the call.  Row r = b * T + t with a nonzero byte: x0[r][c] =
+ * known_rows[r][c] for c < nc, zero for nc <= c < ld, also in row r + n * T where halves = 2; every other byte of x0 is left alone.
+ * ns2vc_k_known_items: known_nct = DEVICE fp32 [n][C][T] and mask_host = HOST [n][T] bytes -> rows [slot * T, + T) of known_rows = DEVICE fp32
+ * [nslots * T][ld] (columns C .. ld zero) and of mask_dev = DEVICE [nslots * T] bytes (0 | 1) for slot = slots_host[k]; an entry outside
+ * [0, nslots) is skipped; known_nct = mask_host = NULL: the listed slots' bytes of mask_dev become zero and known_rows is not touched. */
+int ns2vc_k_hold_slots(float* x0, const float* known_rows, const uint8_t* mask_host, int n, int T, int ld, int nc, int halves, void* stream);
+int ns2vc_k_known_items(const float* known_nct, const uint8_t* mask_host, int C, int T, int n, const int32_t* slots_host, int nslots, float* known_rows,
+                        uint8_t* mask_dev, int ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,10 @@ PROTOTYPES = {
     "ns2vc_k_sampler_take": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P]),
     "ns2vc_sampler_set_known": (_I, [_P, _P, _P, _I, _P]),
     "ns2vc_k_hold_x0": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ns2vc_sampler_open_known": (_I, [_P, _I, _I, _P]),
+    "ns2vc_sampler_set_known_items": (_I, [_P, _I, _P, _P, _P, _P]),
+    "ns2vc_k_hold_slots": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ns2vc_k_known_items": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

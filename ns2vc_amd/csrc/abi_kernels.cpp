@@ -546,5 +546,46 @@ int ns2vc_k_hold_x0(float* x0, const float* known_rows, const uint8_t* mask_host
   (void)hipFree(dev);
   return rc;
 }
+// host bytes on the device for one hook call
+static int upload_bytes(const void* host, size_t nb, void** out_dev, const char* what) {
+  HIPCHK(hipMalloc(out_dev, nb));
+  if (hipMemcpy(*out_dev, host, nb, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(*out_dev);
+    *out_dev = nullptr;
+    return fail("%s: copy to the device failed", what);
+  }
+  return 0;
+}
+// the hold launch of a slot loop on its own: the host mask lives on the device for the one call
+int ns2vc_k_hold_slots(float* x0, const float* known_rows, const uint8_t* mask_host, int n, int T, int ld, int nc, int halves, void* stream) {
+  if (!x0 || !known_rows || !mask_host) return fail("null argument");
+  if (n <= 0 || T <= 0 || ld <= 0 || (ld & 3) || nc <= 0 || nc > ld || (halves != 1 && halves != 2) || (size_t)n * T > (size_t)0x7fffffff)
+    return fail("hold_slots: n (%d) and T (%d) positive, nc (%d) in 1 .. ld (%d), ld a multiple of 4, halves (%d) 1 or 2", n, T, nc, ld, halves);
+  void* md = nullptr;
+  if (upload_bytes(mask_host, (size_t)n * T, &md, "hold_slots")) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launched(launch_hold_slots(x0, known_rows, static_cast<const uint8_t*>(md), n * T, ld, nc, halves, s), "hold_slots launch");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("hold_slots: stream synchronize failed");
+  (void)hipFree(md);
+  return rc;
+}
+// the known-frame scatter of a slot loop on its own; the slot list goes to the device AS GIVEN (the kernel skips an entry outside [0, nslots))
+int ns2vc_k_known_items(const float* known_nct, const uint8_t* mask_host, int C, int T, int n, const int32_t* slots_host, int nslots, float* known_rows,
+                        uint8_t* mask_dev, int ld, void* stream) {
+  if (!slots_host || !mask_dev || !known_rows) return fail("null argument");
+  if ((known_nct != nullptr) != (mask_host != nullptr)) return fail("known_items: the latent and the mask are given together (both NULL = clear)");
+  if (C <= 0 || ld <= 0 || C > ld || T <= 0 || n <= 0 || nslots <= 0 || (size_t)nslots * T > (size_t)0x7fffffff)
+    return fail("known_items: C (%d) in 1 .. ld (%d), T (%d), n (%d) and nslots (%d) positive", C, ld, T, n, nslots);
+  void *sd = nullptr, *md = nullptr;
+  if (upload_bytes(slots_host, (size_t)n * sizeof(int), &sd, "known_items")) return 1;
+  if (mask_host && upload_bytes(mask_host, (size_t)n * T, &md, "known_items")) { (void)hipFree(sd); return 1; }
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launched(launch_known_items(known_nct, static_cast<const uint8_t*>(md), C, T, n, static_cast<const int*>(sd), nslots, known_rows, mask_dev, ld, s),
+                    "known_items launch");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("known_items: stream synchronize failed");
+  (void)hipFree(sd);
+  if (md) (void)hipFree(md);
+  return rc;
+}
 
 }  // extern "C"

@@ -467,6 +467,15 @@ hipError_t launch_solver_step(const SolverStep& st, hipStream_t s);
 // launch serves every later list; a count above `rows` is clamped and an entry outside [0, rows) skipped, never used as an index.
 constexpr int HOLD_LIST_HEAD = 4;
 hipError_t launch_hold_x0(float* x0, const float* known, const int* list, int rows, int ld, int nc, int halves, hipStream_t s);
+// Known frames of a slot loop (ns2vc_sampler_open_known): the same rule with the held rows given by a DEVICE byte mask [rows] (nonzero =
+// held) instead of a list, so a slot's frames change without touching its neighbours' bytes.  The grid is sized by `rows` (one wave per 64 rows);
+// a wave whose 64 bytes are all clear returns at once; a row index is a bit position of the wave's ballot, never a value read from memory.
+hipError_t launch_hold_slots(float* x0, const float* known, const uint8_t* mask, int rows, int ld, int nc, int halves, hipStream_t s);
+// known [n][C][T] fp32 and mask [n][T] bytes (both DEVICE) -> rows [slots[k] * T, + T) of known_rows [nslots * T][ld] (channels-last, columns C .. ld
+// zero) and of mask_dst [nslots * T] (0 | 1), one launch for the DEVICE list `slots` [n]; known == mask == NULL: the listed slots' mask bytes
+// become zero and nothing else is written.  An entry outside [0, nslots) is skipped, never used as an index.
+hipError_t launch_known_items(const float* known, const uint8_t* mask, int C, int T, int n, const int* slots, int nslots, float* known_rows,
+                              uint8_t* mask_dst, int ld, hipStream_t s);
 // the time embedding under per-item rows: a held item is evaluated at its clamped row; B engine rows read the n_items records B / n_items times
 hipError_t launch_emb_items_from_table(const float* table, const int* step_ptr, const SolverItem* items, int n_items, const float* aug, float* emb,
                                        void* emb_act_op, int prec, int B, int edim, hipStream_t s);

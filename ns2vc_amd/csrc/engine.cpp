@@ -268,6 +268,7 @@ int ns2vc_unet_prepare(ns2vc_unet* h, int B, int T, int Lp) {
   h->hold.on = false;        // ... and without known frames (ns2vc_sampler_set_known)
   h->hold.n = 0;
   h->hold.last.clear();
+  h->shold.drop(h);          // ... a slot loop's too (ns2vc_sampler_open_known)
   h->plens.on = false;       // ... and with whole prompts (ns2vc_unet_set_prompt_lengths)
   h->plens.applied.clear();
   if (build_plan(h, true)) return 1;

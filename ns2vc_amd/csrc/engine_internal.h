@@ -460,6 +460,23 @@ struct ns2vc_unet {
     ns2vc::StepTable<int> rows;            // [HOLD_LIST_HEAD + n * T]: the count, then the held rows of one half
     std::vector<int32_t> last;
   } hold;
+  // Known frames of a slot loop (ns2vc_sampler_open_known): per SLOT state for the whole prepared shape, allocated at open outside the
+  // plan arena -- the known rows channels-last like x0, one mask byte per frame (all clear at open) that launch_hold_slots reads at every step,
+  // and the device landing place of a call's host mask.  `on` is the form the captured step graph bakes in (the launch is there or not); an
+  // admission's frames are copies and one launch_known_items, a take clears its slots: neither recaptures.  `last` mirrors each slot's last held
+  // frame (-1: none) for the length check of ns2vc_sampler_admit.
+  struct SlotHold {
+    bool on = false;
+    ns2vc::StepTable<float> known;         // [loop_items * T][CP]
+    ns2vc::StepTable<uint8_t> mask;        // [loop_items * T]
+    ns2vc::StepTable<uint8_t> mask_in;     // [loop_items * T]: a call's mask [n][T] on its way to launch_known_items
+    std::vector<int32_t> last;
+    void drop(::ns2vc_unet* h) {           // the form goes (the loop ended, the shape or the item count changed): the next loop captures without it
+      if (on) ns2vc::drop_step_graph(h);
+      on = false;
+      last.clear();
+    }
+  } shold;
 
   // named persistent buffers
   float *xe = nullptr, *xbar = nullptr, *d1 = nullptr, *mprev = nullptr, *x0 = nullptr;
@@ -528,9 +545,10 @@ int load_state(ns2vc_unet* h, const float* x_bct, hipStream_t s, int items = 0);
 // sampler.cpp
 bool solver_in_conv_out(ns2vc_unet* h, GemmArgs& g);
 // a host list of n slots in [0, nslots) (no repeats) -> the engine's device list, asynchronously on `s`; with `rec` their n records behind it.
-// *slots_dev / *rec_dev point into h->slots.list_dev.  Fails on a bad list.
+// *slots_dev / *rec_dev point into h->slots.list_dev.  Fails on a bad list.  extra: `extra_bytes` more host bytes that travel in the same staging
+// buffer to `extra_dev` (a known-frame mask).
 int stage_slot_list(ns2vc_unet* h, int n, const int32_t* slots, int nslots, const SolverItem* rec, hipStream_t s, const int** slots_dev,
-                    const SolverItem** rec_dev);
+                    const SolverItem** rec_dev, const void* extra = nullptr, size_t extra_bytes = 0, void* extra_dev = nullptr);
 // abi_kernels.cpp
 hipError_t init_all_attributes();
 int xcd_round_robin_of_current_device();

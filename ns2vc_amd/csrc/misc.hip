@@ -1505,4 +1505,87 @@ hipError_t launch_hold_x0(float* x0, const float* known, const int* list, int ro
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Known frames of a slot loop (ns2vc_sampler_open_known): common.h launch_hold_slots / launch_known_items state the rules.
+// hold_slots_kernel: one wave per 64 consecutive rows b * T + t; a lane reads one mask byte, the ballot is the wave's set of held rows, an empty set
+// ends the wave.  Otherwise the wave walks the set bits, min(ld / 4, 64) lanes per row (ld = 128: two rows per pass), one float4 per lane and
+// quad.  A row index comes from a bit position alone -- never from memory -- and a bit is set only for a row < rows.  fp32 in and out: no template.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hold_slots_kernel(float* __restrict__ x0, const float* __restrict__ known, const uint8_t* __restrict__ mask,
+                                                         int rows, int ld, int nc, int halves) {
+  const int lane = threadIdx.x & 63;
+  const size_t base = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
+  const size_t mine = base + lane;
+  unsigned long long set = __ballot(mine < (size_t)rows && mask[mine] != 0);
+  if (!set) return;
+  const int nq = ld >> 2;
+  const int lpr = min(nq, 64), rpp = 64 / lpr;      // lanes per row, rows per pass
+  const int j = lane / lpr, q0 = lane - j * lpr;
+  while (set) {
+    int bit = -1;
+    for (int i = 0; i < rpp && set; ++i) {          // (uniform: `set` is the same in every lane)
+      const int f = __ffsll(set) - 1;
+      set &= set - 1;
+      if (i == j) bit = f;
+    }
+    if (bit < 0) continue;
+    const size_t r = base + bit;
+    for (int q = q0; q < nq; q += lpr) {
+      const int c = q * 4;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c < nc) {
+        v = *reinterpret_cast<const float4*>(known + r * ld + c);
+        if (c + 1 >= nc) v.y = 0.f;
+        if (c + 2 >= nc) v.z = 0.f;
+        if (c + 3 >= nc) v.w = 0.f;
+      }
+      *reinterpret_cast<float4*>(x0 + r * ld + c) = v;
+      if (halves == 2) *reinterpret_cast<float4*>(x0 + ((size_t)rows + r) * ld + c) = v;
+    }
+  }
+}
+hipError_t launch_hold_slots(float* x0, const float* known, const uint8_t* mask, int rows, int ld, int nc, int halves, hipStream_t s) {
+  if (!x0 || !known || !mask || rows <= 0 || ld <= 0 || (ld & 3) || nc <= 0 || nc > ld || (halves != 1 && halves != 2) ||
+      (((uintptr_t)x0 | (uintptr_t)known) & 15))
+    return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)(((size_t)rows + 255) / 256);      // four waves of 64 rows
+  hipLaunchKernelGGL(hold_slots_kernel, dim3(blocks), dim3(256), 0, s, x0, known, mask, rows, ld, nc, halves);
+  return hipGetLastError();
+}
+// known [n][C][T] -> the listed slots' known rows (channels-last, pad channels zero: sampler_admit_kernel's 32 x 33 tile) and mask [n][T] -> their
+// mask bytes (0 | 1), written by the blocks y = 0; known == NULL (the clear form, grid y = 1): the listed slots' mask bytes become zero, nothing else
+// is written.  An entry outside [0, nslots) is skipped, never used as an index.
+__global__ __launch_bounds__(256) void known_items_kernel(const float* __restrict__ known, const uint8_t* __restrict__ mask, int C, int T,
+                                                          const int* __restrict__ slots, int nslots, float* __restrict__ known_rows,
+                                                          uint8_t* __restrict__ mask_dst, int ld) {
+  __shared__ float tile[32][33];
+  const int k = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int slot = slots[k];
+  if (slot < 0 || slot >= nslots) return;                    // (uniform per block: in front of the barrier)
+  if (blockIdx.y == 0 && threadIdx.x < 32 && t0 + (int)threadIdx.x < T) {
+    const int t = t0 + threadIdx.x;
+    mask_dst[(size_t)slot * T + t] = (known && mask[(size_t)k * T + t]) ? (uint8_t)1 : (uint8_t)0;
+  }
+  if (!known) return;                                        // (uniform: a launch argument)
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;    // 32 x 8
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, t = t0 + tx;
+    tile[i][tx] = (c < C && t < T) ? known[((size_t)k * C + c) * T + t] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (t < T && c < ld) known_rows[((size_t)slot * T + t) * ld + c] = tile[tx][i];
+  }
+}
+hipError_t launch_known_items(const float* known, const uint8_t* mask, int C, int T, int n, const int* slots, int nslots, float* known_rows,
+                              uint8_t* mask_dst, int ld, hipStream_t s) {
+  if (!slots || !mask_dst || (known != nullptr) != (mask != nullptr) || (known && !known_rows) || n <= 0 || nslots <= 0 || T <= 0 || C <= 0 || ld <= 0 ||
+      C > ld)
+    return hipErrorInvalidValue;
+  const dim3 grid((T + 31) / 32, known ? (ld + 31) / 32 : 1, n);
+  hipLaunchKernelGGL(known_items_kernel, grid, dim3(256), 0, s, known, mask, C, T, slots, nslots, known_rows, mask_dst, ld);
+  return hipGetLastError();
+}
+
 }  // namespace ns2vc

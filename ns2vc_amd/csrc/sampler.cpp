@@ -45,6 +45,7 @@ int ns2vc_sampler_load(ns2vc_unet* h, int steps, const float* coef_host) {
   if (h->in_slot_loop() && h->slots.any_busy())
     return fail("a slot loop with busy slots is running (ns2vc_sampler_open): a shared table would end their items; take them first (ns2vc_sampler_take)");
   h->slots.on = false;      // (a shared table leaves slot mode)
+  h->shold.drop(h);
   if (!h->coef_dev) HIPCHK(hipMalloc((void**)&h->coef_dev, (size_t)kMaxSteps * NS2VC_NCOEF * sizeof(float)));
   HIPCHK(hipDeviceSynchronize());   // a previous loop may still be reading the table
   HIPCHK(hipMemcpy(h->coef_dev, coef_host, (size_t)steps * NS2VC_NCOEF * sizeof(float), hipMemcpyHostToDevice));
@@ -80,6 +81,7 @@ int ns2vc_sampler_load_items(ns2vc_unet* h, int n_tables, const int32_t* table_r
   if (h->in_slot_loop() && h->slots.any_busy())
     return fail("a slot loop with busy slots is running (ns2vc_sampler_open): new schedules would end their items; take them first (ns2vc_sampler_take)");
   h->slots.on = false;      // (closed per-item schedules leave slot mode)
+  h->shold.drop(h);
   std::vector<int> row0(n_tables), flags(n_tables, 0);
   long rows = 0;
   for (int k = 0; k < n_tables; ++k) {
@@ -154,6 +156,7 @@ static int guidance_onoff(ns2vc_unet* h, bool on, int n) {
     h->next_step = -1;       // (nor does a loop in progress survive the change)
     h->hold.on = false;      // (nor known frames: their mask covered the other item count)
     h->hold.n = 0;
+    h->shold.drop(h);      // (nor a slot loop's: its state covered the other item count)
   }
   h->guide.on = on;
   h->guide.n = on ? n : 0;
@@ -191,6 +194,9 @@ int ns2vc_sampler_set_x0_correction(ns2vc_unet* h, int mode, float ratio, float 
   if (mode && h->hold.on)
     return fail("known frames are held (ns2vc_sampler_set_known): an x0 correction would rescale them; switch the hold off (NULL, NULL) before "
                 "ns2vc_sampler_set_x0_correction(mode %d)", mode);
+  if (mode && h->shold.on && h->in_slot_loop())
+    return fail("the slot loop holds known frames (ns2vc_sampler_open_known): an x0 correction would rescale them; open the loop without them before "
+                "ns2vc_sampler_set_x0_correction(mode %d)", mode);
   if (mode && h->x0c.items.on)
     return fail("the per-item x0 correction is on (ns2vc_sampler_set_x0_correction_items): switch it off (NULL arrays) before the loop-wide "
                 "ns2vc_sampler_set_x0_correction(mode %d)", mode);
@@ -213,6 +219,9 @@ int ns2vc_sampler_set_x0_correction_items(ns2vc_unet* h, const int32_t* mode_hos
                 "ns2vc_sampler_set_x0_correction_items", h->x0c.mode);
   if (h->hold.on)
     return fail("known frames are held (ns2vc_sampler_set_known): an x0 correction would rescale them; switch the hold off (NULL, NULL) before "
+                "ns2vc_sampler_set_x0_correction_items");
+  if (h->shold.on && h->in_slot_loop())
+    return fail("the slot loop holds known frames (ns2vc_sampler_open_known): an x0 correction would rescale them; open the loop without them before "
                 "ns2vc_sampler_set_x0_correction_items");
   if (n != h->loop_items())
     return fail("per-item x0 correction for %d items, the loop takes %d (the prepared batch; n under guidance: set the guidance first)", n, h->loop_items());
@@ -299,6 +308,10 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
     if (h->hold.n != h->loop_items()) return fail("known frames for %d items, the loop has %d (set them again)", h->hold.n, h->loop_items());
     HIPCHK(launch_hold_x0(h->x0, h->hold.known.dev, h->hold.rows.dev, h->hold.n * h->T, h->CP, h->cfg.latent_channels, h->guide.on ? 2 : 1, s));
   }
+  if (h->shold.on) {     // a slot loop's known frames: the same place, the held rows by the per-slot byte mask
+    if ((int)h->shold.last.size() != h->loop_items()) return fail("the slot loop's known frames cover %d slots, the loop has %d (open it again)", (int)h->shold.last.size(), h->loop_items());
+    HIPCHK(launch_hold_slots(h->x0, h->shold.known.dev, h->shold.mask.dev, h->loop_items() * h->T, h->CP, h->cfg.latent_channels, h->guide.on ? 2 : 1, s));
+  }
   SolverStep st;
   st.coef = h->coef_dev; st.step_ptr = h->step_dev; st.ncoef = NS2VC_NCOEF;
   st.x0 = h->x0; st.xe = h->xe; st.xe_op = h->xe_op; st.prec = h->prec; st.xbar = h->xbar; st.d1 = h->d1; st.mprev = h->mprev;
@@ -321,6 +334,7 @@ static int run_step(ns2vc_unet* h, hipStream_t s, bool capturing = false) {
 int ns2vc_sampler_begin(ns2vc_unet* h, const float* x_T_bct, void* stream) {
   if (check_ready(h, true)) return 1;
   if (!x_T_bct) return fail("null tensor");
+  h->shold.drop(h);      // (a closed loop never runs a slot loop's hold launch)
   if (h->slots.on) {      // begin takes whole batches: it leaves slot mode, whose table rows and records belong to the slots' items
     h->slots.on = false; h->steps = 0; h->next_step = -1;
     return fail("the engine ran a slot loop (ns2vc_sampler_open), which this call has ended: load a table (ns2vc_sampler_load / _load_items) before ns2vc_sampler_begin");
@@ -499,6 +513,7 @@ int ns2vc_sampler_end(ns2vc_unet* h, float* x_out_bct, void* stream) {
   if (ns2vc_sampler_peek(h, x_out_bct, stream)) return 1;
   h->next_step = -1;
   h->slots.on = false;
+  h->shold.last.clear();      // (a slot loop's known frames end with it; the form stays baked until the next loop is opened or a table loaded)
   return 0;
 }
 
@@ -514,7 +529,7 @@ int ns2vc_sampler_run(ns2vc_unet* h, float* x_inout_bct, int use_graph, void* st
 static const int kSlotRows = 1024;      // the coefficient table's fixed capacity (ns2vc_sampler_load's)
 
 int ns2vc::stage_slot_list(ns2vc_unet* h, int n, const int32_t* slots, int nslots, const SolverItem* rec, hipStream_t s, const int** slots_dev,
-                           const SolverItem** rec_dev) {
+                           const SolverItem** rec_dev, const void* extra, size_t extra_bytes, void* extra_dev) {
   if (!slots || n <= 0 || n > nslots) return fail("a slot list needs 1 .. %d entries, got %d", nslots, n);
   std::vector<char> seen((size_t)nslots, 0);
   for (int k = 0; k < n; ++k) {
@@ -531,9 +546,13 @@ int ns2vc::stage_slot_list(ns2vc_unet* h, int n, const int32_t* slots, int nslot
   Staged& st = sl.ring[sl.ring_next];
   sl.ring_next = (sl.ring_next + 1) % ns2vc_unet::SlotLoop::kRing;
   const size_t lb = (size_t)n * sizeof(int), rb = rec ? (size_t)n * sizeof(SolverItem) : 0;
-  if (st.reserve(lb + rb)) return 1;
+  if (st.reserve(lb + rb + extra_bytes)) return 1;
   memcpy(st.buf, slots, lb);
   if (rec) memcpy(static_cast<char*>(st.buf) + lb, rec, rb);
+  if (extra_bytes) {
+    memcpy(static_cast<char*>(st.buf) + lb + rb, extra, extra_bytes);
+    HIPCHK(hipMemcpyAsync(extra_dev, static_cast<char*>(st.buf) + lb + rb, extra_bytes, hipMemcpyHostToDevice, s));
+  }
   HIPCHK(hipMemcpyAsync(sl.list_dev, st.buf, lb, hipMemcpyHostToDevice, s));
   SolverItem* rd = reinterpret_cast<SolverItem*>(sl.list_dev + sl.cap);
   if (rec) HIPCHK(hipMemcpyAsync(rd, static_cast<char*>(st.buf) + lb, rb, hipMemcpyHostToDevice, s));
@@ -551,7 +570,8 @@ static int need_slot_loop(ns2vc_unet* h) {
 
 extern "C" {
 
-int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
+// ns2vc_sampler_open and ns2vc_sampler_open_known (known != 0: the per-slot known-frame form)
+static int sampler_open(ns2vc_unet* h, int history2, int noise, int known, void* stream) {
   if (check_ready(h, true)) return 1;
   hipStream_t s = (hipStream_t)stream;
   auto& sl = h->slots;
@@ -565,6 +585,9 @@ int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
     for (int b = 0; b < n; ++b)
       if (h->lens.applied[b] != h->lens.applied[b + n]) return fail("guided slot loop: lengths[%d] and lengths[%d] differ", b, b + n);
   if (h->in_slot_loop() && sl.any_busy()) return fail("the slot loop is open and has busy slots: take them before opening again");
+  if (known && (h->x0c.mode || h->x0c.items.on))
+    return fail("an x0 correction is on (ns2vc_sampler_set_x0_correction%s): it would rescale the known frames; switch it off before ns2vc_sampler_open_known",
+                h->x0c.mode ? "" : "_items");
   const size_t tb = (size_t)kSlotRows * NS2VC_NCOEF * sizeof(float);
   if (!h->coef_dev) HIPCHK(hipMalloc((void**)&h->coef_dev, tb));
   if (h->items.reserve(h, (size_t)n, false)) return 1;
@@ -575,6 +598,15 @@ int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
   }
   if (h2 && ensure_mprev2(h)) return 1;
   if (nz && h->seeds.reserve(h, (size_t)n, true)) return 1;
+  auto& kh = h->shold;
+  if (known) {      // the per-slot state for the whole prepared shape, and staging room for the largest mask: no later call of the loop allocates
+    const size_t rows = (size_t)n * h->T;
+    if (rows > (size_t)0x7fffffff) return fail("known frames: %zu rows exceed the 32-bit row index", rows);
+    if (kh.known.reserve(h, rows * h->CP, true) || kh.mask.reserve(h, rows, true) || kh.mask_in.reserve(h, rows, true)) return 1;
+    for (Staged& st : sl.ring)
+      if (st.reserve((size_t)n * (sizeof(int) + sizeof(SolverItem)) + rows)) return 1;
+  }
+  if ((known != 0) != kh.on) drop_step_graph(h);      // (the hold launch is part of the captured step or it is not)
   if (h->x0c.mode == 1 && ensure_thr(h)) return 1;
   if (h->x0c.items.on) {      // the per-item x0 correction is baked in beside history 2 and noise: every slot off until its admission brings a record
     auto& ic = h->x0c.items;
@@ -623,6 +655,46 @@ int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) {
   HIPCHK(launch_fill_i32(h->step_dev, -1, s));      // the first launch of every step advances it (gn_stats.clear)
   h->next_step = 0;
   sl.on = true;
+  kh.on = known != 0;
+  kh.last.clear();
+  if (known) {      // no slot holds a frame
+    HIPCHK(launch_zero(kh.mask.dev, (size_t)n * h->T, s));
+    kh.last.assign((size_t)n, -1);
+  }
+  return 0;
+}
+
+int ns2vc_sampler_open(ns2vc_unet* h, int history2, int noise, void* stream) { return sampler_open(h, history2, noise, 0, stream); }
+int ns2vc_sampler_open_known(ns2vc_unet* h, int history2, int noise, void* stream) { return sampler_open(h, history2, noise, 1, stream); }
+
+// The known frames of the listed idle slots: the latent into the slots' known rows, the host mask through the staging ring into their
+// mask bytes -- one launch; both NULL clears the listed slots.  A slot's frames last for one request: ns2vc_sampler_take clears them.
+int ns2vc_sampler_set_known_items(ns2vc_unet* h, int n, const int32_t* slots, const float* known_nct, const uint8_t* mask_nt, void* stream) {
+  if (need_slot_loop(h)) return 1;
+  auto& kh = h->shold;
+  const int ni = h->loop_items(), T = h->T;
+  if (!kh.on) return fail("the slot loop was opened without known frames (ns2vc_sampler_open): open it with ns2vc_sampler_open_known");
+  if ((known_nct != nullptr) != (mask_nt != nullptr)) return fail("known frames: the latent and the mask are given together (both NULL = clear the slots)");
+  if ((int)kh.last.size() != ni || (int)h->slots.busy.size() != ni) return fail("the slot loop was opened for %d items, the loop has %d: open it again", (int)kh.last.size(), ni);
+  if (!slots || n <= 0 || n > ni) return fail("a slot list needs 1 .. %d entries, got %d", ni, n);
+  std::vector<int32_t> last((size_t)n, -1);
+  for (int k = 0; k < n; ++k) {
+    const int b = slots[k];
+    if (b < 0 || b >= ni) return fail("slots[%d] = %d outside [0, %d)", k, b, ni);
+    if (h->slots.busy[b]) return fail("slot %d is busy: the known frames of a running request do not change (take it first)", b);
+    if (!mask_nt) continue;
+    const int L = h->lens.masked ? (int)h->lens.applied[(size_t)b] : T;
+    for (int t = 0; t < T; ++t) {
+      if (!mask_nt[(size_t)k * T + t]) continue;
+      if (t >= L) return fail("known frame %d of slot %d lies at or past its length %d: set the lengths first", t, b, L);
+      last[(size_t)k] = t;
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int* slots_dev = nullptr;
+  if (stage_slot_list(h, n, slots, ni, nullptr, s, &slots_dev, nullptr, mask_nt, mask_nt ? (size_t)n * T : 0, kh.mask_in.dev)) return 1;
+  HIPCHK(launch_known_items(known_nct, mask_nt ? kh.mask_in.dev : nullptr, h->cfg.latent_channels, T, n, slots_dev, ni, kh.known.dev, kh.mask.dev, h->CP, s));
+  for (int k = 0; k < n; ++k) kh.last[(size_t)slots[k]] = last[(size_t)k];
   return 0;
 }
 
@@ -698,6 +770,9 @@ int ns2vc_sampler_admit(ns2vc_unet* h, int n, const int32_t* slots, const float*
     for (int i = 0; i < r[1]; ++i)
       if (sl.coef[(size_t)(r[0] + i) * NS2VC_NCOEF + 1] == 0.f) return fail("slot %d: row %d of the table was never written (ns2vc_sampler_write_rows)", b, r[0] + i);
     if (h->guide.on && h->lens.masked && h->lens.applied[b] != h->lens.applied[b + ni]) return fail("guided slot loop: lengths[%d] and lengths[%d] differ", b, b + ni);
+    if (h->shold.on && h->lens.masked && (int)h->shold.last.size() == ni && h->shold.last[(size_t)b] >= h->lens.applied[(size_t)b])      // (lengths set after the frames)
+      return fail("known frame %d of slot %d lies at or past its length %d: set the known frames after the lengths", (int)h->shold.last[(size_t)b], b,
+                  (int)h->lens.applied[(size_t)b]);
   }
   hipStream_t s = (hipStream_t)stream;
   const int* slots_dev = nullptr;
@@ -731,6 +806,10 @@ int ns2vc_sampler_take(ns2vc_unet* h, int n, const int32_t* slots, float* x_out_
   const int* slots_dev = nullptr;
   if (stage_slot_list(h, n, slots, ni, nullptr, s, &slots_dev, nullptr)) return 1;
   HIPCHK(launch_sampler_take(h->xe, h->CP, h->cfg.latent_channels, h->T, n, slots_dev, ni, x_out_nct, h->items.dev, s));
+  if (h->shold.on && (int)h->shold.last.size() == ni) {      // a slot's known frames last for one request: the same list, the clear form of the second launch
+    HIPCHK(launch_known_items(nullptr, nullptr, h->cfg.latent_channels, h->T, n, slots_dev, ni, h->shold.known.dev, h->shold.mask.dev, h->CP, s));
+    for (int k = 0; k < n; ++k) h->shold.last[(size_t)slots[k]] = -1;
+  }
   for (int k = 0; k < n; ++k) {
     sl.rec[slots[k]] = solver_item_idle();
     sl.busy[slots[k]] = 0;

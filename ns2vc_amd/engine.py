@@ -535,12 +535,17 @@ class Engine:
             raise ValueError("an empty slot list")
         return a
 
-    def open_slots(self, history2: bool = False, noise: bool = False, stream=None, item_corrections: bool = False) -> None:
+    def open_slots(self, history2: bool = False, noise: bool = False, stream=None, item_corrections: bool = False,
+                   known_frames: bool = False) -> None:
         """Slot mode on the prepared shape: every loop item an idle slot on zero state and zero condition, the step counter running from 0.
         ``history2`` / ``noise``: order-3 / stochastic items may be admitted (fixed here: the captured step graph bakes them in, as it does
         the guidance and the x0 correction set at this moment).  ``item_corrections``: the per-item x0 correction table is on, every slot off
         until ``set_x0_correction_items`` gives it a record before its admission -- corrected and stochastic items may then share the loop;
-        False switches a table left on off.  Opening again starts afresh (refused while slots are busy)."""
+        False switches a table left on off.  ``known_frames``: the per-slot known-frame form (``ns2vc_sampler_open_known``) -- every
+        slot gets known rows and a frame mask, all clear, and the step the hold launch; ``set_known_items`` then gives idle slots their frames;
+        not together with an x0 correction in either form.  Opening again starts afresh (refused while slots are busy)."""
+        if known_frames and (item_corrections or self.x0_correction is not None):
+            raise ValueError("known_frames and an x0 correction (set_x0_correction, item_corrections) exclude each other: it would rescale the held frames")
         if item_corrections:
             if self.x0_correction is not None:
                 raise ValueError("item_corrections and the loop-wide x0 correction (set_x0_correction) exclude each other")
@@ -548,8 +553,35 @@ class Engine:
             self.set_x0_correction_items([None] * items, stream=stream)
         elif self.x0_corrections is not None:
             self.set_x0_correction_items(None, stream=stream)
-        check(self.lib.ns2vc_sampler_open(self.h, int(bool(history2)), int(bool(noise)), _stream_ptr(stream)), "sampler_open")
+        if known_frames:
+            check(self.lib.ns2vc_sampler_open_known(self.h, int(bool(history2)), int(bool(noise)), _stream_ptr(stream)), "sampler_open_known")
+        else:
+            check(self.lib.ns2vc_sampler_open(self.h, int(bool(history2)), int(bool(noise)), _stream_ptr(stream)), "sampler_open")
         self.table = self.tables = None
+
+    def set_known_items(self, slots, known, mask, stream=None) -> None:
+        """Known frames of the idle ``slots`` of a slot loop opened with ``known_frames=True``: ``known`` (n, latent, T) fp32 on the GPU, ``mask``
+        (n, T) bool on the host (array / tensor); ``None, None`` clears the listed slots.  One launch, asynchronous on ``stream``, no recapture;
+        the frames last for one request (``take`` clears them).  Call after ``set_lengths`` (a held frame lies inside its slot's length) and
+        before ``admit``, whose x_T holds ``schedule.known_start`` on those frames."""
+        s = self._slot_list(slots)
+        if known is None and mask is None:
+            check(self.lib.ns2vc_sampler_set_known_items(self.h, int(s.shape[0]), s.ctypes.data, None, None, _stream_ptr(stream)), "set_known_items")
+            return
+        if known is None or mask is None:
+            raise ValueError("known and mask are given together (None, None clears the slots)")
+        if hasattr(mask, "detach"):
+            mask = mask.detach().cpu().numpy()
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        T = None if self.shape is None else self.shape[1]
+        if m.shape != (s.shape[0], T):
+            raise ValueError(f"mask must be ({s.shape[0]}, {T}) -- the listed slots and the prepared T --, got {m.shape}")
+        if hasattr(known, "shape") and tuple(known.shape) != (s.shape[0], self.cfg.latent_channels, T):
+            raise ValueError(f"known must be ({s.shape[0]}, {self.cfg.latent_channels}, {T}), got {tuple(known.shape)}")
+        if hasattr(known, "dtype") and "float32" not in str(known.dtype):
+            raise ValueError(f"known must be float32, got {known.dtype}")
+        check(self.lib.ns2vc_sampler_set_known_items(self.h, int(s.shape[0]), s.ctypes.data, _ptr(known), m.ctypes.data, _stream_ptr(stream)),
+              "set_known_items")
 
     def rebase_slots(self, stream=None) -> None:
         """the loop step of a drained slot loop (every slot idle) back to 0: the 32-bit counter does not bound a service's lifetime"""

@@ -685,7 +685,8 @@ class Denoiser:
 
     def open_slots(self, B: int, T: int, Lp: int, order3: bool = False, stochastic: bool = False, unconditional_prompt=None,
                    correcting_x0_fn=None, thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995,
-                   use_graph: bool = True, require_tail_free: bool = True, item_corrections: bool = False) -> "SlotLoop":
+                   use_graph: bool = True, require_tail_free: bool = True, item_corrections: bool = False,
+                   known_frames: bool = False) -> "SlotLoop":
         """Continuous batching: a ``SlotLoop`` over an engine prepared for B slots of up to T frames and Lp prompt frames, whose slots are
         filled (``admit``), run (``run``) and emptied (``take``) independently while one captured step graph keeps replaying.  Fixed here,
         because the graph bakes them in: ``order3`` / ``stochastic`` (requests with order-3 / ddim-eta / ddpm schedules may come),
@@ -693,9 +694,11 @@ class Denoiser:
         x0 correction -- either the loop-wide ``correcting_x0_fn=`` or ``item_corrections=True``: every request then brings its own
         (``SlotLoop.admit(correction=)``), which also goes with ``stochastic=True`` and ``order3=True``; both: ValueError.
         ``require_tail_free`` False admits requests that ``sample`` would give trailing fp32 evaluations anyway (previews: their
-        latent carries the 16-bit rounding of its last evaluations).  See ``SlotLoop``."""
+        latent carries the 16-bit rounding of its last evaluations).  ``known_frames=True``: requests may bring known frames
+        (``SlotLoop.admit(known=, known_mask=)``) -- the step gets the per-slot hold launch; with ``correcting_x0_fn=`` or
+        ``item_corrections=True``: ValueError (a correction would rescale held frames).  See ``SlotLoop``."""
         return SlotLoop(self, B, T, Lp, order3, stochastic, unconditional_prompt, correcting_x0_fn, thresholding_max_val,
-                        dynamic_thresholding_ratio, use_graph, require_tail_free, item_corrections)
+                        dynamic_thresholding_ratio, use_graph, require_tail_free, item_corrections, known_frames)
 
     def sample_sharded(self, content, prompt, prompt_mask, noise, lengths=None, seeds=None, prompt_lengths=None, guidance_scale=1.0,
                        unconditional_prompt=None, unconditional_prompt_mask=None, unconditional_prompt_lengths=None, unconditional_content=None, **kw):
@@ -861,13 +864,19 @@ class SlotLoop:
 
     REBASE_AT = 1 << 30
     item_corrections = False      # (set by open_slots(item_corrections=True): every request brings its own x0 correction)
+    known_frames = False          # (set by open_slots(known_frames=True): a request may bring known frames)
 
     def __init__(self, den: "Denoiser", B: int, T: int, Lp: int, order3: bool, stochastic: bool, unconditional_prompt, correcting_x0_fn,
                  thresholding_max_val: float, dynamic_thresholding_ratio: float, use_graph: bool, require_tail_free: bool = True,
-                 item_corrections: bool = False):
+                 item_corrections: bool = False, known_frames: bool = False):
         import torch
         self.require_tail_free = bool(require_tail_free)
         self.item_corrections = bool(item_corrections)
+        self.known_frames = bool(known_frames)
+        if self.known_frames and (self.item_corrections or check_x0_correction(correcting_x0_fn, dynamic_thresholding_ratio, thresholding_max_val,
+                                                                               names_only=True)):
+            raise ValueError("known_frames=True does not go with an x0 correction (correcting_x0_fn=, item_corrections=True): it would rescale "
+                             "the held frames")
         if self.item_corrections and correcting_x0_fn is not None:
             raise ValueError("item_corrections=True (every request brings its own x0 correction) and the loop-wide correcting_x0_fn= exclude each other")
         if min(int(B), int(T), int(Lp)) < 1:
@@ -906,7 +915,10 @@ class SlotLoop:
         if self.uncond is not None or eng.guidance is not None:
             eng.set_guidance(self.scales if self.uncond is not None else None, stream=s)
         den._correct(eng, self.corr)
-        eng.open_slots(self.order3, self.stochastic, stream=s, item_corrections=self.item_corrections)
+        if self.known_frames:      # (the keyword reaches the engine only when it is set: the default call is what it was)
+            eng.open_slots(self.order3, self.stochastic, stream=s, item_corrections=self.item_corrections, known_frames=True)
+        else:
+            eng.open_slots(self.order3, self.stochastic, stream=s, item_corrections=self.item_corrections)
         if self.stochastic:
             eng.set_seeds(self.seeds, stream=s)
         den._table_key = None                    # (the engine's table belongs to the pool now)
@@ -952,18 +964,26 @@ class SlotLoop:
 
     # -- the four calls ------------------------------------------------------------------------------------------------------
     def admit(self, slot: int, content, prompt, noise, length: Optional[int] = None, prompt_length: Optional[int] = None, schedule=None,
-              seed: int = 0, guidance_scale: float = 1.0, correction=None) -> None:
+              seed: int = 0, guidance_scale: float = 1.0, correction=None, known=None, known_mask=None) -> None:
         """one request into the idle ``slot`` at the current loop step: ``content`` (256, L), ``prompt`` (lp, 256), ``noise`` = x_T
         (100, L) on the GPU, L <= T and lp <= Lp frames (``length`` / ``prompt_length`` default to them; shorter values use the first
         frames), ``schedule`` = dict(solver=, steps=, order=, eta=, table options), ``seed`` of its noise stream (stochastic schedules),
         ``guidance_scale`` (a guided loop), ``correction`` = the request's own x0 correction, None or ``dict(correcting_x0_fn=,
-        thresholding_max_val=, dynamic_thresholding_ratio=)`` (a loop opened with ``item_corrections=True``)."""
+        thresholding_max_val=, dynamic_thresholding_ratio=)`` (a loop opened with ``item_corrections=True``).  ``known`` (100, L) on the GPU
+        with ``known_mask`` (L,) bool (a loop opened with ``known_frames=True``): on the frames of the mask, all inside the
+        request's length, the request holds ``known`` -- its x_T there is alpha_0 known + sigma_0 noise by its own first table row
+        (``schedule.known_start``) and every evaluation's x0 is overwritten there; an all-False mask is no hold.  The frames last for this
+        request: ``take`` clears the slot."""
+        if (known is None) != (known_mask is None):
+            raise ValueError("known and known_mask are given together")
         self.admit_group([slot], [content], [prompt], [noise], None if length is None else [length],
-                         None if prompt_length is None else [prompt_length], [schedule], [seed], [guidance_scale], [correction])
+                         None if prompt_length is None else [prompt_length], [schedule], [seed], [guidance_scale], [correction],
+                         None if known is None else [known], None if known_mask is None else [known_mask])
 
     def admit_group(self, slots, contents, prompts, noises, lengths=None, prompt_lengths=None, schedules=None, seeds=None, guidance_scales=None,
-                    corrections=None) -> None:
-        """``admit`` for several requests at once (lists of per-request tensors): one condition rebuild and one admit launch for all"""
+                    corrections=None, knowns=None, known_masks=None) -> None:
+        """``admit`` for several requests at once (lists of per-request tensors): one condition rebuild and one admit launch for all;
+        ``knowns`` / ``known_masks``: one entry per request, None for a request without known frames"""
         import torch
         n = len(slots)
         if n == 0 or not (len(contents) == len(prompts) == len(noises) == n):
@@ -998,6 +1018,7 @@ class SlotLoop:
             if not (1 <= lp <= min(self.Lp, int(p.shape[0]))):
                 raise ValueError(f"prompt_length {lp} outside [1, min(Lp = {self.Lp}, the prompt's {int(p.shape[0])} frames)]")
             reqs.append((key, table, flags, L, lp))
+        holds = self._check_known(n, knowns, known_masks, [r[3] for r in reqs])
         dev = self.dev
         s = torch.cuda.current_stream(dev)
         eng = self.den.engine
@@ -1011,6 +1032,21 @@ class SlotLoop:
             c_all[k, :, :L] = contents[k][:, :L].to(dev, torch.float32)
             p_all[k, :lp] = prompts[k][:lp].to(dev, torch.float32)
             x_all[k, :, :L] = noises[k][:, :L].to(dev, torch.float32)
+        k_all = m_all = None
+        if any(h is not None for h in holds):      # known rows and masks of the whole group (no hold: a clear mask), and x_T on the held frames
+            k_all = torch.zeros((n, cfg.latent_channels, self.T), dtype=torch.float32, device=dev)
+            m_all = np.zeros((n, self.T), dtype=bool)
+            for k, h in enumerate(holds):
+                if h is None:
+                    continue
+                kn, mk = h
+                Lk = mk.shape[0]
+                k_all[k, :, :Lk] = kn.to(dev, torch.float32)
+                m_all[k, :Lk] = mk
+            row0 = np.stack([np.asarray(r[1].coef[0], dtype=np.float32) for r in reqs])
+            a0 = torch.from_numpy(np.ascontiguousarray(row0[:, 1])).to(dev).view(n, 1, 1)
+            s0 = torch.from_numpy(np.ascontiguousarray(row0[:, 2])).to(dev).view(n, 1, 1)
+            x_all = torch.where(torch.from_numpy(m_all).to(dev).view(n, 1, self.T), a0 * k_all + s0 * x_all, x_all).contiguous()
         for k, b in enumerate(slots):
             L, lp = reqs[k][3], reqs[k][4]
             self.lengths[b], self.plens[b], self.seeds[b], self.scales[b] = L, lp, seeds[k], scales[k]
@@ -1026,6 +1062,7 @@ class SlotLoop:
             self.step = 0
         records = np.zeros((n, 4), dtype=np.int32)
         acquired = []
+        known_sent = False
         try:
             for k, (key, table, flags, L, lp) in enumerate(reqs):
                 row0, write = self.pool.acquire(key, table.coef)
@@ -1046,16 +1083,57 @@ class SlotLoop:
                 eng.set_condition_items(slots + [b + self.B for b in slots], torch.cat([c_all, c_all]), torch.cat([u, p_all]), None, stream=s)
             else:
                 eng.set_condition_items(slots, c_all, p_all, None, stream=s)
+            if k_all is not None:
+                eng.set_known_items(slots, k_all, m_all, stream=s)
+                known_sent = True
             eng.admit(slots, x_all, records, stream=s)
         except Exception:          # nothing was admitted: the tables' users go back (the slots stay idle)
             for key in acquired:
                 self.pool.release(key)
+            if known_sent:         # ... and hold no frames: a later request without known frames sends none and must find the slots clear
+                try:
+                    eng.set_known_items(slots, None, None, stream=s)
+                except Exception:      # noqa: BLE001 (the admission's own error is the one to report)
+                    pass
             raise
-        for t in (c_all, p_all, x_all):
+        for t in (c_all, p_all, x_all) + (() if k_all is None else (k_all,)):
             if t.is_cuda:
                 t.record_stream(s)
         for k, b in enumerate(slots):
             self.items[b] = dict(key=reqs[k][0], start=self.step, steps=reqs[k][1].steps, length=reqs[k][3])
+
+    def _check_known(self, n, knowns, known_masks, lengths):
+        """the known frames of an admission, checked before any engine call: per request None or (known (100, L') tensor, mask (L',) bool
+        array), L' <= T; an all-False mask is None"""
+        if knowns is None and known_masks is None:
+            return [None] * n
+        if knowns is None or known_masks is None or len(knowns) != n or len(known_masks) != n:
+            raise ValueError("knowns and known_masks are given together, one entry (or None) per slot")
+        nc = self.den.cfg.latent_channels
+        out = []
+        for k in range(n):
+            kn, mk = knowns[k], known_masks[k]
+            if kn is None and mk is None:
+                out.append(None)
+                continue
+            if kn is None or mk is None:
+                raise ValueError("known and known_mask are given together")
+            if not self.known_frames:
+                raise ValueError("a request with known frames needs a slot loop opened with known_frames=True")
+            if hasattr(mk, "detach"):
+                mk = mk.detach().cpu().numpy()
+            mk = np.asarray(mk)
+            if mk.dtype != np.bool_ or mk.ndim != 1:
+                raise ValueError(f"known_mask must be a bool array (L,), got {mk.dtype} {mk.shape}")
+            if not hasattr(kn, "dim") or kn.dim() != 2 or tuple(kn.shape) != (nc, mk.shape[0]) or mk.shape[0] > self.T:
+                raise ValueError(f"known must be a tensor ({nc}, L) with known_mask (L,), L <= T = {self.T}; got "
+                                 f"{tuple(kn.shape) if hasattr(kn, 'shape') else type(kn).__name__} and {mk.shape}")
+            if not kn.dtype.is_floating_point:
+                raise ValueError(f"known must be a floating-point tensor, got {kn.dtype}")
+            if mk.any() and int(np.nonzero(mk)[0][-1]) >= lengths[k]:
+                raise ValueError(f"known frame {int(np.nonzero(mk)[0][-1])} lies at or past the request's length {lengths[k]}")
+            out.append((kn, mk) if mk.any() else None)
+        return out
 
     def _self_check(self, slots, c_all, p_all, x_all, tables, s) -> None:
         """the Denoiser's precision self-check on the first fill: the admitted requests' first evaluation point, the other slots idle"""

@@ -839,7 +839,11 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
     normals of slot b's k-th item at its LOCAL row j.  Returns ``results[b][k]`` = x_e of that item after its last row: equal, bit for
     bit, to the item run alone (``run_table_numpy``).  ``correct_x0``: the keywords of ``schedule.correct_x0`` for every item of the loop.  A
     request's OWN correction is a fourth tuple element instead, ``(table, start, x_T, correction)``: None or the dict
-    ``item_correction`` takes (``lengths`` = the item's own frame count); a stochastic item takes None; not together with ``correct_x0=``."""
+    ``item_correction`` takes (``lengths`` = the item's own frame count); a stochastic item takes None; not together with ``correct_x0=``.
+    A request's known frames are a fifth element, ``(table, start, x_T, correction, hold)``: None or ``(known, mask)`` shaped
+    ``shape[1:]`` and ``(T,)`` bool.  ``hold_x0`` is applied to that slot's x0 at every evaluation while the item is the slot's current one --
+    from its admission until the next one, as the engine's per-slot mask stands until the slot is taken -- so the item equals
+    ``run_table_numpy(..., hold=)`` of it alone, bit for bit.  Refused together with a correction, in the same tuple or in ``correct_x0=``."""
     f = np.float32
     B = int(shape[0])
     if len(timeline) != B:
@@ -859,6 +863,17 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
     if correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)):
         corr = dict(correct_x0)
     lengths = None if corr is None else corr.pop("lengths", None)
+    holds = [[None] * len(items) for items in timeline]
+    for b, items in enumerate(timeline):
+        for k, item in enumerate(items):
+            if len(item) > 4 and item[4] is not None:
+                if item[3] is not None:
+                    raise ValueError(f"slot {b} item {k}: known frames do not run with an x0 correction: it would rescale the held frames")
+                h = item[4]
+                if isinstance(h, (tuple, list)) and len(h) == 2 and h[0] is not None and h[1] is not None:
+                    h = (np.asarray(h[0])[None], np.asarray(h[1])[None])      # (one item: the batch axis _check_hold expects)
+                hk, hm = _check_hold(h, (1,) + tuple(shape[1:]))
+                holds[b][k] = (hk[0], hm[0])
     xe = np.zeros(shape, f)
     xbar, d1, m_prev, m_prev2 = (np.zeros(shape, f) for _ in range(4))
     S = max([int(item[1]) + item[0].steps for items in timeline for item in items], default=0)
@@ -880,6 +895,9 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
                 if 0 <= j < tab.steps:
                     act[b] = (tab, j)
         x0 = np.asarray(x0_fn(xe, t)).astype(f)
+        for b in range(B):
+            if cur[b] >= 0 and holds[b][cur[b]] is not None:
+                x0[b] = hold_x0(x0[b:b + 1], (holds[b][cur[b]][0][None], holds[b][cur[b]][1][None]))[0]
         for b in range(B):
             if act[b] is None:
                 continue
@@ -1008,4 +1026,48 @@ def plan_slots(steps: Sequence[int], n_slots: int, arrivals: Optional[Sequence[i
         if not nexts:
             break
         r = min(nexts)          # (> r: what finished by r was taken, what had arrived by r and found a slot was admitted)
+    return events
+
+
+def plan_chains(chains: Sequence[Sequence[int]], n_slots: int):
+    """The scheduling of a slot loop that serves CHAINED requests, as a pure function.  ``chains[u]`` = the evaluation counts of
+    utterance u's chunks in order; chunk (u, j + 1) holds latent frames of chunk (u, j) and so becomes ready when (u, j) has finished.
+    Returns events ``(loop_step, take, admit)`` in ``plan_slots``'s format with request ids ``(u, j)``.  Greedy and work-conserving: at every
+    event step, after the takes, the ready requests go to the lowest free slots -- first the successors of finished chunks, in utterance
+    order (a started utterance finishes first, which bounds the latents kept for later chunks), then first chunks in queue order.  A take
+    frees the slot its successor needs, so a successor never waits.  With every chain of length 1 the events are those of
+    ``plan_slots([c[0] for c in chains], n_slots)`` with (u, 0) for u."""
+    chains = [[int(s) for s in c] for c in chains]
+    if n_slots < 1 or any(len(c) < 1 for c in chains) or any(s < 1 for c in chains for s in c):
+        raise ValueError("plan_chains needs n_slots >= 1, at least one chunk per chain and steps >= 1")
+    free_at = [0] * n_slots
+    holder = [None] * n_slots
+    events, nxt, r = [], 0, 0
+    waiting: List[Tuple[int, int]] = []          # successors that are ready and not admitted yet
+    while nxt < len(chains) or waiting or any(h is not None for h in holder):
+        take = [(b, holder[b]) for b in range(n_slots) if holder[b] is not None and free_at[b] <= r]
+        for b, (u, j) in take:
+            holder[b] = None
+            if j + 1 < len(chains[u]):
+                waiting.append((u, j + 1))
+        waiting.sort()
+        admit = []
+        for b in range(n_slots):
+            if holder[b] is not None:
+                continue
+            if waiting:
+                req = waiting.pop(0)
+            elif nxt < len(chains):
+                req = (nxt, 0)
+                nxt += 1
+            else:
+                break
+            holder[b], free_at[b] = req, r + chains[req[0]][req[1]]
+            admit.append((b, req))
+        if take or admit:
+            events.append((r, take, admit))
+        nexts = [free_at[b] for b in range(n_slots) if holder[b] is not None]
+        if not nexts:
+            break
+        r = min(nexts)
     return events

@@ -46,7 +46,7 @@ from .frontend import PreModel
 from .noise import derive_seed
 from .pipeline import MASKED_OPTIONS, Denoiser, OverlappedPipeline
 from .request import CORRECTION_KEYS, call_wide_kwargs
-from .schedule import ITEM_HIST2, ITEM_NOISE, build_table, plan_slots, schedule_key, table_flags, table_options
+from .schedule import ITEM_HIST2, ITEM_NOISE, build_table, plan_chains, plan_chunks, schedule_key, table_flags, table_options
 
 
 @dataclass
@@ -216,17 +216,28 @@ class ContinuousConverter:
     end runs per admitted group with exact lengths (``exact_lengths`` / ``exact_prompt_lengths``); x_T and the noise seed are per segment,
     drawn as ``GroupedConverter`` draws them, so a segment's result does not depend on its slot or its neighbours.  ``Segment.schedule``
     is honoured.  Options as ``GroupedConverter``'s; schedules that need an fp32 tail at the denoiser's precision are refused
-    (``SlotLoop``)."""
+    (``SlotLoop``).
+
+    ``overlap_frames=V`` (0 <= V < ``max_frames``): a segment longer than ``max_frames`` is no longer refused but cut by
+    ``schedule.plan_chunks(L, max_frames, V)``, and every chunk is a request of the same loop at its own length.  The front end runs once
+    per long segment on its whole length -- its content is sliced per chunk, its prompt shared --, x_T is the segment's full-length draw,
+    sliced, and the seed is reused per chunk, as in ``Denoiser.sample_long``.  Chunk j + 1 holds its first V frames at the last V latent
+    frames chunk j's ``take`` returned (a device-side slice on the loop's stream: the host never waits between chunks), and becomes ready
+    when chunk j has finished: the scheduling is ``schedule.plan_chains``, request ids ``(segment, chunk)`` in ``last_plan``.  The result is
+    chunk 0 whole, then every later chunk from frame V on.  Short segments ride along unchanged."""
 
     def __init__(self, pre_model: PreModel, denoiser: Denoiser, decode_fn: Optional[Callable] = None, slots: int = 32, max_frames: int = 938,
                  max_prompt: int = 469, solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, eta: float = 0.0,
                  guidance_scale: float = 1.0, unconditional_prompt: Optional[torch.Tensor] = None, correcting_x0_fn=None,
                  thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995, use_graph: bool = True,
-                 item_corrections: bool = False, **options):
+                 item_corrections: bool = False, overlap_frames: Optional[int] = None, **options):
         """``item_corrections``: ``Segment.correction`` is honoured -- the loop is opened with the per-item x0 correction table and every
         segment is admitted with its own entry (None = uncorrected); not together with the loop-wide ``correcting_x0_fn=``."""
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
         self.item_corrections = bool(item_corrections)
+        self.overlap = None if overlap_frames is None else int(overlap_frames)
+        if self.overlap is not None and not 0 <= self.overlap < int(max_frames):
+            raise ValueError(f"overlap_frames must be in [0, max_frames = {int(max_frames)}), got {overlap_frames}")
         self.slots, self.max_frames, self.max_prompt, self.seed, self.use_graph = int(slots), int(max_frames), int(max_prompt), seed, use_graph
         self.guided = unconditional_prompt is not None and float(guidance_scale) != 1.0
         self.scale = float(guidance_scale) if self.guided else 1.0
@@ -240,6 +251,9 @@ class ContinuousConverter:
         self.corr = call_wide_kwargs(None, correcting_x0_fn, thresholding_max_val, dynamic_thresholding_ratio)      # (the loop checks every request's solver)
         if self.item_corrections and self.corr:
             raise ValueError("item_corrections=True (Segment.correction) and the loop-wide correcting_x0_fn= exclude each other")
+        if self.overlap and (self.item_corrections or self.corr):
+            raise ValueError("overlap_frames > 0 (chunks that hold known frames) does not go with an x0 correction (correcting_x0_fn=, "
+                             "item_corrections=True): it would rescale the held frames")
         self.last_plan = None          # (events of the last convert: tests, utilisation figures)
 
     def convert(self, segments: Sequence[Segment]) -> List[torch.Tensor]:
@@ -247,7 +261,7 @@ class ContinuousConverter:
         dev = next(self.pre.parameters()).device
         specs = [s.schedule if getattr(s, "schedule", None) is not None else self.own for s in segments]
         for i, s in enumerate(segments):
-            if int(s.content.shape[-1]) > self.max_frames or int(s.refer.shape[-1]) > self.max_prompt:
+            if (int(s.content.shape[-1]) > self.max_frames and self.overlap is None) or int(s.refer.shape[-1]) > self.max_prompt:
                 raise ValueError(f"segment {i} has {int(s.content.shape[-1])} frames and {int(s.refer.shape[-1])} prompt frames: the slots take "
                                  f"{self.max_frames} and {self.max_prompt}")
         built = {}                     # one table per distinct schedule, shared with the loop
@@ -257,41 +271,87 @@ class ContinuousConverter:
                 built[k] = build_table(k[0], k[1], self.den._betas_for(k[0]), k[2], k[3], **dict(k[4]))
         tables = [built[schedule_key(sp)] for sp in specs]
         cors = [getattr(s, "correction", None) if self.item_corrections else None for s in segments]
+        V = self.overlap or 0
+        chunks = [plan_chunks(int(s.content.shape[-1]), self.max_frames, V) if self.overlap is not None else [(0, int(s.content.shape[-1]))]
+                  for s in segments]
+        chained = max((len(c) for c in chunks), default=1) > 1
+        kw = dict(self.corr, known_frames=True) if chained and V > 0 else self.corr      # (the form only where a chunk holds frames: else the plain loop)
         loop = self.den.open_slots(self.slots, self.max_frames, self.max_prompt, order3=any(table_flags(t) & ITEM_HIST2 for t in tables),
                                    stochastic=any(table_flags(t) & ITEM_NOISE for t in tables), unconditional_prompt=self.uncond,
-                                   use_graph=self.use_graph, item_corrections=self.item_corrections, **self.corr)
+                                   use_graph=self.use_graph, item_corrections=self.item_corrections, **kw)
         loop._tables.update(built)
         try:
             for sp, cor in zip(specs, cors):      # every refusal before anything runs
                 loop.check_request(sp, self.scale, cor)
-            events = plan_slots([t.steps for t in tables], self.slots)
-            self.last_plan = events
+            # requests are (segment, chunk); with one chunk per segment these are plan_slots' events, and last_plan shows them in its format
+            events = plan_chains([[tables[i].steps] * len(chunks[i]) for i in range(len(segments))], self.slots)
+            self.last_plan = events if chained else [(r, [(b, i) for b, (i, _) in take], [(b, i) for b, (i, _) in admit]) for r, take, admit in events]
             result: List[Optional[torch.Tensor]] = [None] * len(segments)
             nc = self.den.cfg.latent_channels
+            front: Dict[int, tuple] = {}        # long segment -> (content (256, L), prompt (lp, 256), x_T (100, L), latent (100, L)) until its last chunk
+            tails: Dict[int, torch.Tensor] = {}  # long segment -> the last V latent frames of its latest chunk, until the next chunk is admitted
+
+            def pre(idx):
+                """the front end on the whole length of the segments ``idx``, with exact lengths"""
+                lens = [int(segments[i].content.shape[-1]) for i in idx]
+                plens = [int(segments[i].refer.shape[-1]) for i in idx]
+                c = torch.zeros((len(idx), segments[idx[0]].content.shape[0], max(lens)), dtype=torch.float32, device=dev)
+                refer = torch.zeros((len(idx), segments[idx[0]].refer.shape[0], max(plens)), dtype=torch.float32, device=dev)
+                for k, i in enumerate(idx):
+                    c[k, :, :lens[k]] = segments[i].content.to(dev, torch.float32)
+                    refer[k, :, :plens[k]] = segments[i].refer.to(dev, torch.float32)
+                content, prompt, _ = self.pre.infer(c, refer, torch.tensor(lens, device=dev), torch.tensor(plens, device=dev), exact_lengths=True,
+                                                    exact_prompt_lengths=True)
+                return content, prompt
+
+            def draw(i):
+                # x_T per SEGMENT at its own length, seeded by its position in the input (as GroupedConverter): its result does not depend on its slot
+                return torch.randn((nc, int(segments[i].content.shape[-1])), generator=torch.Generator().manual_seed(self.seed + i)).to(dev)
+
             for r, take, admit in events:
                 if r > loop.step:
                     loop.run(r - loop.step)
                 if take:
                     lat = loop.take([b for b, _ in take])
-                    for k, (_, i) in enumerate(take):
-                        x = lat[k, :, :int(segments[i].content.shape[-1])]
+                    for k, (_, (i, j)) in enumerate(take):
+                        start, stop = chunks[i][j]
+                        x = lat[k, :, :stop - start]
+                        if len(chunks[i]) > 1:      # chunk 0 whole, every later chunk from frame V on
+                            keep = V if j > 0 else 0
+                            front[i][3][:, start + keep:stop] = x[:, keep:]
+                            if j + 1 < len(chunks[i]):
+                                if V > 0:
+                                    tails[i] = x[:, stop - start - V:]
+                                continue
+                            x = front.pop(i)[3]
                         result[i] = x if self.decode is None else self.decode(x[None])[0]
                 if admit:
-                    idx = [i for _, i in admit]
-                    lens = [int(segments[i].content.shape[-1]) for i in idx]
-                    plens = [int(segments[i].refer.shape[-1]) for i in idx]
-                    c = torch.zeros((len(idx), segments[idx[0]].content.shape[0], max(lens)), dtype=torch.float32, device=dev)
-                    refer = torch.zeros((len(idx), segments[idx[0]].refer.shape[0], max(plens)), dtype=torch.float32, device=dev)
-                    for k, i in enumerate(idx):
-                        c[k, :, :lens[k]] = segments[i].content.to(dev, torch.float32)
-                        refer[k, :, :plens[k]] = segments[i].refer.to(dev, torch.float32)
-                    content, prompt, _ = self.pre.infer(c, refer, torch.tensor(lens, device=dev), torch.tensor(plens, device=dev), exact_lengths=True,
-                                                        exact_prompt_lengths=True)
-                    # x_T per SEGMENT at its own length, seeded by its position in the input (as GroupedConverter): its result does not depend on its slot
-                    noise = [torch.randn((nc, lens[k]), generator=torch.Generator().manual_seed(self.seed + i)).to(dev) for k, i in enumerate(idx)]
-                    loop.admit_group([b for b, _ in admit], [content[k] for k in range(len(idx))], [prompt[k] for k in range(len(idx))], noise, lens, plens,
-                                     [specs[i] for i in idx], [int(derive_seed(self.seed, i)) for i in idx], [self.scale] * len(idx),
-                                     [cors[i] for i in idx])
+                    short = [i for _, (i, _) in admit if len(chunks[i]) == 1]
+                    if short:      # the short segments of the group in one front-end batch
+                        content, prompt = pre(short)
+                    cs, ps, xs, lens, plens, kns, kms = [], [], [], [], [], [], []
+                    for _, (i, j) in admit:
+                        L, lp = int(segments[i].content.shape[-1]), int(segments[i].refer.shape[-1])
+                        start, stop = chunks[i][j]
+                        if len(chunks[i]) == 1:
+                            c_i, p_i, x_i = content[short.index(i)], prompt[short.index(i)], draw(i)
+                        else:
+                            if i not in front:      # the front end once per long segment; x_T its full-length draw; the stitched latent
+                                c_w, p_w = pre([i])
+                                front[i] = (c_w[0, :, :L], p_w[0, :lp], draw(i), torch.zeros((nc, L), dtype=torch.float32, device=dev))
+                            c_i, p_i, x_i = front[i][0][:, start:stop], front[i][1], front[i][2][:, start:stop]
+                        kn = km = None
+                        if j > 0 and V > 0:      # the frames the earlier chunk ended on, held at the head of this one
+                            kn = torch.zeros((nc, stop - start), dtype=torch.float32, device=dev)
+                            kn[:, :V] = tails.pop(i)
+                            km = np.zeros((stop - start,), dtype=bool)
+                            km[:V] = True
+                        for lst, v in ((cs, c_i), (ps, p_i), (xs, x_i), (lens, stop - start), (plens, lp), (kns, kn), (kms, km)):
+                            lst.append(v)
+                    idx = [i for _, (i, _) in admit]
+                    hold = dict(knowns=kns, known_masks=kms) if any(k is not None for k in kns) else {}
+                    loop.admit_group([b for b, _ in admit], cs, ps, xs, lens, plens, [specs[i] for i in idx], [int(derive_seed(self.seed, i)) for i in idx],
+                                     [self.scale] * len(idx), [cors[i] for i in idx], **hold)
             torch.cuda.current_stream(dev).synchronize()
         finally:                       # also after an error in mid-queue: no busy slot is left behind, the denoiser serves the next call
             loop.close()
