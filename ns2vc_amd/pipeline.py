@@ -17,8 +17,8 @@ from . import dist as _dist
 from .engine import DEFAULT_PRECISION, Engine
 from .noise import draw_seeds
 from .request import CORRECTION_KEYS, SampleRequest, call_wide_kwargs, check_guidance, check_item_schedule, host_array, item_correction_entry
-from .schedule import (DISCRETE_SOLVERS, ITEM_HIST2, ITEM_NOISE, TablePool, build_table, check_x0_correction, linear_betas, schedule_key,
-                       table_flags, table_options)
+from .schedule import (DISCRETE_SOLVERS, ITEM_HIST2, ITEM_NOISE, TablePool, build_table, check_x0_correction, known_start_torch, linear_betas,
+                       schedule_key, table_flags, table_options)
 from .spec import UNetConfig, attention_workgroups_per_forward
 
 # The engine options that keep a ragged batch (``lengths=``) on its fused launches: each is a constructor parameter of ``Denoiser`` of the same
@@ -577,10 +577,7 @@ class Denoiser:
         kn = None
         if req.known is not None:      # x_T of the known frames: alpha_0 k + sigma_0 noise in float32, by each item's own first table row (schedule.known_start)
             kn = req.known.to(device=dev, dtype=torch.float32).contiguous()
-            row0 = np.asarray(table.coef[0] if req.tabs is None else np.stack([req.tabs.table_of(b).coef[0] for b in range(B)]), dtype=np.float32)
-            a0 = torch.from_numpy(np.array(np.broadcast_to(row0[..., 1], (B,)))).to(dev).view(B, 1, 1)
-            s0 = torch.from_numpy(np.array(np.broadcast_to(row0[..., 2], (B,)))).to(dev).view(B, 1, 1)
-            x = torch.where(torch.from_numpy(req.known_mask).to(dev).view(B, 1, T), a0 * kn + s0 * x, x).contiguous()
+            x = known_start_torch(x, kn, req.known_mask, table.coef[0] if req.tabs is None else np.stack([req.tabs.table_of(b).coef[0] for b in range(B)]))
         mask = None if prompt_mask is None else prompt_mask.to(device=dev, dtype=torch.uint8).contiguous()
         cond = (content.float().contiguous(), prompt.float().contiguous(), mask, lengths, prompt_lengths, kn, req.known_mask)
         if self.precision_check is not None and not self._precision_checked:
@@ -1043,10 +1040,7 @@ class SlotLoop:
                 Lk = mk.shape[0]
                 k_all[k, :, :Lk] = kn.to(dev, torch.float32)
                 m_all[k, :Lk] = mk
-            row0 = np.stack([np.asarray(r[1].coef[0], dtype=np.float32) for r in reqs])
-            a0 = torch.from_numpy(np.ascontiguousarray(row0[:, 1])).to(dev).view(n, 1, 1)
-            s0 = torch.from_numpy(np.ascontiguousarray(row0[:, 2])).to(dev).view(n, 1, 1)
-            x_all = torch.where(torch.from_numpy(m_all).to(dev).view(n, 1, self.T), a0 * k_all + s0 * x_all, x_all).contiguous()
+            x_all = known_start_torch(x_all, k_all, m_all, np.stack([r[1].coef[0] for r in reqs]))
         for k, b in enumerate(slots):
             L, lp = reqs[k][3], reqs[k][4]
             self.lengths[b], self.plens[b], self.seeds[b], self.scales[b] = L, lp, seeds[k], scales[k]

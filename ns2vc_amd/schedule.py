@@ -23,8 +23,9 @@ Unified recurrence executed by the engine after the i-th denoiser evaluation
     m_prev2' = m_prev ;  m_prev' = m
 
 with xbar = xe = x_T, d1 = m_prev = m_prev2 = 0 before the first evaluation.  After the
-last evaluation ``xe'`` is the sample.  Rows of order <= 2 have d2c = pe = 0 (columns 10-11): a table whose
-columns 10-11 are all zero runs without the m_prev2 history at all (the engine's update keeps its order-2 arithmetic).
+last evaluation ``xe'`` is the sample.  On the host ``solver_update`` is where this recurrence is stated (the twin of common.h ``solver_elem`` +
+``solver_xe``); ``run_table_numpy``, ``run_tables_numpy`` and ``run_slots_numpy`` drive it and contain none of it.
+Rows of order <= 2 have d2c = pe = 0 (columns 10-11): a table whose columns 10-11 are all zero runs without the m_prev2 history at all (the engine's update keeps its order-2 arithmetic).
 Update k (landing on t_k, computed by row k-1, corrected by row k), h = lam_k - lam_{k-1},
 rk_j = (lam_{k-1-j} - lam_{k-1}) / h:
   DPM-Solver++  g0 = previous pc, g1 = 0.  Order 2: d1c = 1/rk_1, pc = alpha_k*phi1/2 ('dpmsolver') or -alpha_k*(phi1/h + 1)
@@ -508,11 +509,73 @@ def build_tables(specs, betas: Optional[np.ndarray] = None, discrete_betas: Opti
     return ItemTables(tables, index, start, tuple(keys))
 
 
+# ---- the host statement of the sampler: ``solver_update`` states the recurrence, the three loops below drive it -----------------
+def solver_update(c, hist2: bool, x0, xe, xbar, d1, m_prev, m_prev2, correct: Optional[Dict[str, object]] = None, z=None):
+    """The update of ONE table row in float32, on state arrays of any leading shape: the host twin of common.h ``solver_elem`` + ``solver_xe``
+    and the only place where this module evaluates the recurrence of its docstring.  ``c``: the row (NCOEF columns); ``x0``: what the model
+    returned at ``xe`` (after guidance and hold).  ``hist2``: the item's TABLE has a row of order 3 (``has_history2``) -- a property of the
+    table, not of the row: every row of such a table takes the history-2 expressions and rotates ``m_prev2``, also one whose columns 10-11
+    are zero.  ``correct``: None or the keywords of ``correct_x0``, applied to m before anything reads it.  ``z``: standard normals shaped
+    like the state, read only where the row's noise column is not zero (a zero coefficient adds no term at all).
+    Returns the new ``(xe, xbar, d1, m_prev, m_prev2)`` as fresh arrays -- except ``m_prev2``, which is the ``m_prev`` it was given (history
+    2) or the ``m_prev2`` it was given (otherwise): a caller that writes the result back into those buffers stores ``m_prev2`` first."""
+    f = np.float32
+    _, alpha, sigma, g0, g1, A, Bc, d1c, pc = (f(v) for v in c[:9])
+    eps = (xe - alpha * x0) / sigma
+    m = (xe - sigma * eps) / alpha
+    if correct is not None:
+        m = _correct_x0(m, **correct)
+    x = xbar - g0 * d1 - g1 * (m - m_prev)
+    xbar = A * x - Bc * m
+    if c[9] != 0:
+        xbar = xbar + f(c[9]) * z
+    if hist2:
+        d2c, pe = f(c[10]), f(c[11])
+        d1 = d1c * (m_prev - m) + d2c * (m_prev2 - m)
+        xe = xbar - pc * d1 - pe * (m_prev2 - m)
+        m_prev2 = m_prev
+    else:
+        d1 = d1c * (m_prev - m)
+        xe = xbar - pc * d1
+    return xe, xbar, d1, m, m_prev2
+
+
+def _start_state(x_T: np.ndarray) -> List[np.ndarray]:
+    """the state in front of the first evaluation, [xe, xbar, d1, m_prev, m_prev2] = [x_T, x_T, 0, 0, 0]: five buffers of their own"""
+    return [x_T.copy(), x_T.copy()] + [np.zeros_like(x_T) for _ in range(3)]
+
+
+def _loop_correction(correct_x0) -> Optional[Dict[str, object]]:
+    """a loop's ``correct_x0=`` dict checked (ValueError) -> a copy of it, or None where the correction is off"""
+    if correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)):
+        return dict(correct_x0)
+    return None
+
+
+def _item_step(state, b: int, x0, table: SolverTable, j: int, hist2: bool, corr, own, noise_fn, noise_key, who: str) -> None:
+    """Row j of ``table`` on item b of the state of a per-item loop (``run_tables_numpy``, ``run_slots_numpy``), in place.  Its correction: the
+    loop-wide ``corr`` under ``lengths[b]``, else the item's ``own`` entry; its normals: ``noise_fn(*noise_key)``, shaped like one item."""
+    c = table.coef[j]
+    correct = own
+    if corr is not None:
+        lengths = corr.get("lengths")
+        correct = dict(corr, lengths=None if lengths is None else [lengths[b]])
+    z = None
+    if c[9] != 0:
+        if noise_fn is None:
+            raise ValueError(f"row {j} of {who}'s {table.solver} table adds noise: pass noise_fn")
+        z = np.asarray(noise_fn(*noise_key), dtype=np.float32)[None]
+    sl = slice(b, b + 1)
+    new = solver_update(c, hist2, x0[sl], *(a[sl] for a in state), correct, z)
+    for a, v in zip(reversed(state), reversed(new)):      # (m_prev2 may be the view of m_prev: stored before m_prev is)
+        a[sl] = v
+
+
 def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarray], x_T: np.ndarray,
                      trace: Optional[List[np.ndarray]] = None, noise_fn: Optional[Callable[[int, int], np.ndarray]] = None,
                      guided_x0: Optional[np.ndarray] = None, correct_x0: Optional[Dict[str, object]] = None, hold=None) -> np.ndarray:
     """Host statement of the loop under per-item schedules (float32).  At loop step r item b has j = r - start_b: ACTIVE when
-    0 <= j < rows_b -- it then takes row j of its own table through the recurrence of ``run_table_numpy``, history 2 where ITS table has a
+    0 <= j < rows_b -- it then takes row j of its own table through ``solver_update`` (``_item_step``), history 2 where ITS table has a
     nonzero column 10 or 11 --, otherwise HELD: evaluated at the clamped row's model time, result ignored, state untouched.
     ``x0_fn(x (B, ...), t_model (B,)) -> x0`` sees every item's own model time.  ``noise_fn(b, j)`` -> the standard normals of item b at
     its LOCAL row j, shaped like x_T[b] (``noise.gauss(seed_b, j, ...)``: the stream the item has alone).  ``guided_x0``: (B,) scales --
@@ -528,22 +591,18 @@ def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray],
     hold = _check_hold(hold, x_T.shape, correct_x0)
     if tabs.index.shape[0] != B:
         raise ValueError(f"{tabs.index.shape[0]} schedules for a batch of {B}")
-    xbar = x_T.astype(f).copy()
-    xe = xbar.copy()
-    d1 = np.zeros_like(xbar)
-    m_prev = np.zeros_like(xbar)
-    m_prev2 = np.zeros_like(xbar)
+    state = _start_state(x_T.astype(f))
+    xe = state[0]
     hist2 = [has_history2(tabs.table_of(b)) for b in range(B)]
     noisy = [bool((np.asarray(tabs.table_of(b).coef)[:, 9] != 0).any()) for b in range(B)]
     corr = None
-    per_item = None
+    per_item = [None] * B
     if isinstance(correct_x0, (list, tuple)):
         per_item = item_corrections(correct_x0, B, noisy)
-    elif correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)):
-        if any(noisy):
+    else:
+        corr = _loop_correction(correct_x0)
+        if corr is not None and any(noisy):
             raise ValueError(f"the x0 correction does not apply to a batch with a stochastic item (items {[b for b in range(B) if noisy[b]]})")
-        corr = dict(correct_x0)
-    lengths = None if corr is None else corr.pop("lengths", None)
     for r in range(tabs.steps):
         t = tabs.t_model_at(r)
         if guided_x0 is None:
@@ -554,32 +613,8 @@ def run_tables_numpy(tabs: ItemTables, x0_fn: Callable[[np.ndarray, np.ndarray],
         x0 = hold_x0(x0, hold)
         rows, act = tabs.row_at(r), tabs.active_at(r)
         for b in range(B):
-            if not act[b]:
-                continue
-            sl = slice(b, b + 1)
-            c = tabs.table_of(b).coef[rows[b]]
-            _, alpha, sigma, g0, g1, A, Bc, d1c, pc = (f(v) for v in c[:9])
-            eps = (xe[sl] - alpha * x0[sl]) / sigma
-            m = (xe[sl] - sigma * eps) / alpha
-            if corr is not None:
-                m = _correct_x0(m, lengths=None if lengths is None else [lengths[b]], **corr)
-            elif per_item is not None and per_item[b] is not None:
-                m = _correct_x0(m, **per_item[b])
-            x = xbar[sl] - g0 * d1[sl] - g1 * (m - m_prev[sl])
-            nb = A * x - Bc * m
-            if c[9] != 0:
-                if noise_fn is None:
-                    raise ValueError(f"row {rows[b]} of item {b}'s {tabs.table_of(b).solver} table adds noise: pass noise_fn")
-                nb = nb + f(c[9]) * np.asarray(noise_fn(b, int(rows[b])), dtype=f)[None]
-            if hist2[b]:
-                d2c, pe = f(c[10]), f(c[11])
-                nd = d1c * (m_prev[sl] - m) + d2c * (m_prev2[sl] - m)
-                ne = nb - pc * nd - pe * (m_prev2[sl] - m)
-                m_prev2[sl] = m_prev[sl]
-            else:
-                nd = d1c * (m_prev[sl] - m)
-                ne = nb - pc * nd
-            xbar[sl], d1[sl], xe[sl], m_prev[sl] = nb, nd, ne, m
+            if act[b]:
+                _item_step(state, b, x0, tabs.table_of(b), int(rows[b]), hist2[b], corr, per_item[b], noise_fn, (b, int(rows[b])), f"item {b}")
         if trace is not None:
             trace.append(xe.copy())
     return xe
@@ -744,6 +779,16 @@ def known_start(x_T: np.ndarray, known: np.ndarray, mask: np.ndarray, coef_row0)
     return np.where(mask[:, None, :], (a * known).astype(f) + (s * x_T).astype(f), x_T).astype(f)
 
 
+def known_start_torch(x_T, known, mask: np.ndarray, coef_row0):
+    """``known_start`` on float32 torch tensors (B, C, T) of one device, for the engine's callers: ``mask`` is the host bool array (B, T),
+    ``coef_row0`` one table row or one per item as above.  The arguments are the caller's checked ones; nothing is checked again."""
+    import torch
+    B, _, T = x_T.shape
+    row = np.asarray(coef_row0, dtype=np.float32)
+    a0, s0 = (torch.from_numpy(np.array(np.broadcast_to(row[..., k], (B,)))).to(x_T.device).view(B, 1, 1) for k in (1, 2))
+    return torch.where(torch.from_numpy(mask).to(x_T.device).view(B, 1, T), a0 * known + s0 * x_T, x_T).contiguous()
+
+
 def plan_chunks(length: int, chunk_frames: int, overlap_frames: int) -> List[Tuple[int, int]]:
     """The chunks [(start, stop)] that ``Denoiser.sample_long`` cuts an utterance of ``length`` frames into: at most ``chunk_frames`` long,
     consecutive ones sharing exactly ``overlap_frames`` frames (0 <= overlap < chunk), which the later chunk holds as known frames.  The
@@ -769,7 +814,7 @@ def has_history2(table: SolverTable) -> bool:
 def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarray], x_T: np.ndarray,
                     trace: Optional[List[np.ndarray]] = None, noise_fn: Optional[Callable[[int], np.ndarray]] = None,
                     correct_x0: Optional[Dict[str, object]] = None, hold=None) -> np.ndarray:
-    """Host executor of the unified recurrence (float32), used by CPU tests to pin
+    """Host executor of the unified recurrence (float32, one ``solver_update`` of the whole batch per row), used by CPU tests to pin
     the tables against the oracle samplers.  ``x0_fn(x, t_model[B]) -> x0``.  ``noise_fn(i)`` -> the standard normals of
     step i, shaped like x_T (ns2vc_amd.noise.gauss), for tables with a nonzero noise column.
     ``correct_x0``: None (off) or the keywords of ``schedule.correct_x0`` -- ``dict(mode=, ratio=, max_val=, lengths=)`` -- applied to m
@@ -780,41 +825,23 @@ def run_table_numpy(table: SolverTable, x0_fn: Callable[[np.ndarray, np.ndarray]
     (``known_start``).  Not together with ``correct_x0``, which would rescale the held frames."""
     f = np.float32
     hold = _check_hold(hold, x_T.shape, correct_x0)
-    xbar = x_T.astype(f).copy()
-    xe = xbar.copy()
-    d1 = np.zeros_like(xbar)
-    m_prev = np.zeros_like(xbar)
-    m_prev2 = np.zeros_like(xbar)
+    state = _start_state(x_T.astype(f))
     hist2 = has_history2(table)
     B = x_T.shape[0]
-    if correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)) \
-            and (np.asarray(table.coef)[:, 9] != 0).any():
+    if _loop_correction(correct_x0) is not None and (np.asarray(table.coef)[:, 9] != 0).any():
         raise ValueError(f"the x0 correction does not apply to a stochastic {table.solver} table (the reference's discrete samplers have none)")
     for i in range(table.steps):
-        t_model, alpha, sigma, g0, g1, A, Bc, d1c, pc = (f(v) for v in table.coef[i, :9])
-        x0 = hold_x0(x0_fn(xe, np.full((B,), t_model, dtype=f)).astype(f), hold)
-        eps = (xe - alpha * x0) / sigma
-        m = (xe - sigma * eps) / alpha
-        if correct_x0 is not None:
-            m = _correct_x0(m, **correct_x0)
-        x = xbar - g0 * d1 - g1 * (m - m_prev)
-        xbar = A * x - Bc * m
-        if table.coef[i, 9] != 0:
+        c = table.coef[i]
+        x0 = hold_x0(x0_fn(state[0], np.full((B,), f(c[0]), dtype=f)).astype(f), hold)
+        z = None
+        if c[9] != 0:
             if noise_fn is None:
                 raise ValueError(f"step {i} of this {table.solver} table adds noise: pass noise_fn")
-            xbar = xbar + f(table.coef[i, 9]) * np.asarray(noise_fn(i), dtype=f)
-        if hist2:
-            d2c, pe = f(table.coef[i, 10]), f(table.coef[i, 11])
-            d1 = d1c * (m_prev - m) + d2c * (m_prev2 - m)
-            xe = xbar - pc * d1 - pe * (m_prev2 - m)
-            m_prev2 = m_prev
-        else:
-            d1 = d1c * (m_prev - m)
-            xe = xbar - pc * d1
-        m_prev = m
+            z = np.asarray(noise_fn(i), dtype=f)
+        state = solver_update(c, hist2, x0, *state, correct_x0, z)
         if trace is not None:
-            trace.append(xe.copy())
-    return xe
+            trace.append(state[0].copy())
+    return state[0]
 
 
 # ---- slot loops: continuous batching (DESIGN 4.12) ---------------------------------------------------------------------
@@ -832,7 +859,7 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
                     noise_fn: Optional[Callable[[int, int, int], np.ndarray]] = None, correct_x0: Optional[Dict[str, object]] = None):
     """Host statement of a slot loop (float32).  ``timeline[b]`` = the consecutive items of slot b, each ``(table, start, x_T)`` with
     ``x_T`` shaped ``shape[1:]`` and ``start`` >= the previous item's start + rows; ``shape`` = (B, ...) of the loop's state.  At loop step r
-    the item of slot b with start <= r < start + rows is ACTIVE at its row r - start (``run_tables_numpy``'s update, history 2 where ITS
+    the item of slot b with start <= r < start + rows is ACTIVE at its row r - start (``run_tables_numpy``'s ``_item_step``, history 2 where ITS
     table has it); at r == start its state is loaded from x_T first (x_e = x_bar = x_T, d1 = m_prev = m_prev2 = 0: what an admission
     writes).  A slot between items is HELD: evaluated -- at the clamped row of its last item, or at model time 0 while it has had none --,
     never updated.  ``x0_fn(x (B, ...), t (B,))`` must treat the items independently, as the engine does.  ``noise_fn(b, k, j)`` -> the
@@ -859,10 +886,7 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
             for k, item in enumerate(items)] for b, items in enumerate(timeline)]
     if correct_x0 is not None and any(len(item) > 3 for items in timeline for item in items):
         raise ValueError("run_slots_numpy: either correct_x0= for every item or a fourth tuple element per item, not both")
-    corr = None
-    if correct_x0 is not None and check_x0_correction(correct_x0.get("mode"), correct_x0.get("ratio", 0.995), correct_x0.get("max_val", 1.0)):
-        corr = dict(correct_x0)
-    lengths = None if corr is None else corr.pop("lengths", None)
+    corr = _loop_correction(correct_x0)
     holds = [[None] * len(items) for items in timeline]
     for b, items in enumerate(timeline):
         for k, item in enumerate(items):
@@ -874,20 +898,21 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
                     h = (np.asarray(h[0])[None], np.asarray(h[1])[None])      # (one item: the batch axis _check_hold expects)
                 hk, hm = _check_hold(h, (1,) + tuple(shape[1:]))
                 holds[b][k] = (hk[0], hm[0])
-    xe = np.zeros(shape, f)
-    xbar, d1, m_prev, m_prev2 = (np.zeros(shape, f) for _ in range(4))
+    state = _start_state(np.zeros(shape, f))
+    xe = state[0]
     S = max([int(item[1]) + item[0].steps for items in timeline for item in items], default=0)
     results = [[None] * len(items) for items in timeline]
     cur = [-1] * B          # the item slot b holds (the last one admitted)
+    hist2 = [False] * B     # ... and whether its table has history 2
     for r in range(S):
         t = np.zeros((B,), f)
         act = [None] * B
         for b, items in enumerate(timeline):
             if cur[b] + 1 < len(items) and int(items[cur[b] + 1][1]) == r:      # admission
                 cur[b] += 1
-                x_T = np.asarray(items[cur[b]][2], dtype=f)
-                xe[b], xbar[b] = x_T, x_T
-                d1[b], m_prev[b], m_prev2[b] = 0, 0, 0
+                hist2[b] = has_history2(items[cur[b]][0])
+                for a, v in zip(state, _start_state(np.asarray(items[cur[b]][2], dtype=f))):
+                    a[b] = v
             if cur[b] >= 0:
                 tab, start = items[cur[b]][0], items[cur[b]][1]
                 j = r - int(start)
@@ -902,30 +927,7 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
             if act[b] is None:
                 continue
             tab, j = act[b]
-            sl = slice(b, b + 1)
-            c = tab.coef[j]
-            _, alpha, sigma, g0, g1, A, Bc, d1c, pc = (f(v) for v in c[:9])
-            eps = (xe[sl] - alpha * x0[sl]) / sigma
-            m = (xe[sl] - sigma * eps) / alpha
-            if corr is not None:
-                m = _correct_x0(m, lengths=None if lengths is None else [lengths[b]], **corr)
-            elif own[b][cur[b]] is not None:
-                m = _correct_x0(m, **own[b][cur[b]])
-            x = xbar[sl] - g0 * d1[sl] - g1 * (m - m_prev[sl])
-            nb = A * x - Bc * m
-            if c[9] != 0:
-                if noise_fn is None:
-                    raise ValueError(f"row {j} of slot {b}'s {tab.solver} table adds noise: pass noise_fn")
-                nb = nb + f(c[9]) * np.asarray(noise_fn(b, cur[b], j), dtype=f)[None]
-            if has_history2(tab):
-                d2c, pe = f(c[10]), f(c[11])
-                nd = d1c * (m_prev[sl] - m) + d2c * (m_prev2[sl] - m)
-                ne = nb - pc * nd - pe * (m_prev2[sl] - m)
-                m_prev2[sl] = m_prev[sl]
-            else:
-                nd = d1c * (m_prev[sl] - m)
-                ne = nb - pc * nd
-            xbar[sl], d1[sl], xe[sl], m_prev[sl] = nb, nd, ne, m
+            _item_step(state, b, x0, tab, j, hist2[b], corr, own[b][cur[b]], noise_fn, (b, cur[b], j), f"slot {b}")
             if j == tab.steps - 1:
                 results[b][cur[b]] = xe[b].copy()
         if trace is not None:

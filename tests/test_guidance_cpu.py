@@ -13,6 +13,7 @@ import torch
 
 from ns2vc_amd import schedule as S
 from recording_engine import denoiser as _denoiser      # the real Denoiser constructor on the recording engine -> (denoiser, recording)
+from util import synthetic_x0
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -38,13 +39,6 @@ def case_tag(solver, steps, order, skip, variant, scale):
 def rel_l2(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
-
-
-def synthetic_x0(x, t, cond):
-    """the closed-form conditional stand-in denoiser of make_golden_v7.py (float32)"""
-    f = np.float32
-    tt = np.asarray(t, f).reshape(-1, 1, 1)
-    return (f(0.9) * np.tanh((x.astype(f) + cond.astype(f)).astype(f)) + f(0.05) * np.cos(f(0.01) * tt)).astype(f)
 
 
 @pytest.fixture(scope="module")

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from ns2vc_amd import schedule as S
+from util import synthetic_x0
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "golden_v5.npz")
@@ -39,13 +40,6 @@ def case_tag(solver, steps, order, skip, lof, extra):
 def rel_l2(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
-
-
-def synthetic_x0(x, t):
-    """the closed-form stand-in denoiser of make_golden_v4.py / v5 (float32)"""
-    f = np.float32
-    tt = np.asarray(t, f).reshape(-1, 1, 1)
-    return (f(0.9) * np.tanh(x.astype(f)) + f(0.05) * np.cos(f(0.01) * tt)).astype(f)
 
 
 def table_of(case):

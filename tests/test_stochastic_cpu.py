@@ -8,6 +8,7 @@ import torch
 
 from ns2vc_amd import noise as N
 from ns2vc_amd import schedule as S
+from util import synthetic_x0
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "golden_v4.npz")
@@ -17,13 +18,6 @@ SYN_CASES = [("ddim", s, e) for s in (26, 30, 100, 1000) for e in (0.0, 0.5, 1.0
 def rel_l2(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
-
-
-def synthetic_x0(x, t):
-    """the closed-form stand-in denoiser of make_golden_v4.py (float32)"""
-    f = np.float32
-    tt = np.asarray(t, f).reshape(-1, 1, 1)
-    return (f(0.9) * np.tanh(x.astype(f)) + f(0.05) * np.cos(f(0.01) * tt)).astype(f)
 
 
 def case_tag(solver, steps, eta):

@@ -12,6 +12,7 @@ import torch
 
 from ns2vc_amd import schedule as S
 from recording_engine import denoiser as _denoiser      # the real Denoiser constructor on the recording engine -> (denoiser, recording)
+from util import synthetic_x0
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -43,14 +44,6 @@ def tag18(solver, order, skip, ratio, leg, scale):
 def rel_l2(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
-
-
-def synthetic_x0(x, t, cond=None):
-    """the closed-form stand-in denoisers of make_golden_v5.py (cond None) and make_golden_v7.py (float32)"""
-    f = np.float32
-    tt = np.asarray(t, f).reshape(-1, 1, 1)
-    xx = x.astype(f) if cond is None else (x.astype(f) + cond.astype(f)).astype(f)
-    return (f(0.9) * np.tanh(xx) + f(0.05) * np.cos(f(0.01) * tt)).astype(f)
 
 
 @pytest.fixture(scope="module")

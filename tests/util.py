@@ -122,6 +122,15 @@ def tol_ffn_xattn(prec):    # fused feed-forward with the in-kernel cross-attent
     return 4e-4 if prec == 2 else 3e-3
 
 
+def synthetic_x0(x, t, cond=None):
+    """the closed-form stand-in denoisers of the golden generators (float32): make_golden_v4.py / v5 (cond None) and make_golden_v7.py / v8, which
+    keep their own torch copies"""
+    f = np.float32
+    tt = np.asarray(t, f).reshape(-1, 1, 1)
+    xx = x.astype(f) if cond is None else (x.astype(f) + cond.astype(f)).astype(f)
+    return (f(0.9) * np.tanh(xx) + f(0.05) * np.cos(f(0.01) * tt)).astype(f)
+
+
 def silu(x):
     return x / (1.0 + np.exp(-x))
 
