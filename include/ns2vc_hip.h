@@ -805,6 +805,38 @@ int ns2vc_k_hold_slots(float* x0, const float* known_rows, const uint8_t* mask_h
 int ns2vc_k_known_items(const float* known_nct, const uint8_t* mask_host, int C, int T, int n, const int32_t* slots_host, int nslots, float* known_rows,
                         uint8_t* mask_dev, int ld, void* stream);
 
+/* ---- Suspend and resume of a slot's request (backward-compatible additions to ABI v7) -------------------------------------------
+ * A busy slot's request is its SOLVER STATE -- the engine's fp32 rows xe, xbar, d1, mprev and, in a loop opened with history2, mprev2: P = 4 or 5
+ * planes of T channels-last rows of ld = padded channels columns each (under guidance the first half's rows; xe of the second half is the same
+ * point) -- and its POSITION done = loop step - start = the rows of its table already run.  Condition, lengths, seed, scale, correction record and
+ * known frames are not state: the caller holds them and sets them again before a resume, exactly as before an admission.
+ * ns2vc_sampler_state_shape: P, T and ld of the open slot loop; a state buffer is DEVICE fp32 [n][P][T][ld], 16-byte aligned.
+ * ns2vc_sampler_suspend: the planes of n busy slots (HOST list, no repeats) -> state_out_dev bit for bit (pad columns and rows past the length
+ * included), done_out_host[k] = the slot's position, and the slots become idle (records; in a loop with known frames their masks are cleared, as
+ * ns2vc_sampler_take clears them).  Only a slot with 0 <= done < steps: an idle slot, one that has not started and one that has finished (take it)
+ * are refused.
+ * ns2vc_sampler_resume: state_in_dev -> n IDLE slots of this or another engine of the same T, ld and loop form, records = HOST [n][4] int32 {row0,
+ * steps, done, flags}, 0 <= done < steps.  ONE launch writes the planes back, rebuilds the operand copy of xe as the solver update stores it ([hi |
+ * lo] pair of 16-bit engines included), writes xe and its operand copy into slot + n of a guided engine and zeroes that item's xbar and history
+ * rows as ns2vc_sampler_admit does, and installs the record {row0, steps, start = loop step - done, flags}: the slot's next step runs row row0 +
+ * done, and a stochastic item continues its own noise stream (the Philox row word is the local row).  start lies in the past and may be negative
+ * after ns2vc_sampler_rebase.  The rows may sit at another row0 than before.  Refusals are those of ns2vc_sampler_admit (rows never written, flags
+ * that differ from the rows' form, a history-2 or stochastic record in a loop opened without it, guided halves of different lengths, a known frame
+ * at or past the length, a busy slot) plus done outside [0, steps).
+ * A request suspended at any done and resumed into the same slot index ends on the bits of the uninterrupted run, whatever the slot did in
+ * between; the other slots keep theirs.  Neither call recaptures the step graph, allocates, or waits for the device. */
+int ns2vc_sampler_state_shape(ns2vc_unet* h, int* planes, int* T, int* ld);
+int ns2vc_sampler_suspend(ns2vc_unet* h, int n, const int32_t* slots, float* state_out_dev, int32_t* done_out_host, void* stream);
+int ns2vc_sampler_resume(ns2vc_unet* h, int n, const int32_t* slots, const float* state_in_dev, const int32_t* records, void* stream);
+/* test hooks of the two kernels; both wait for `stream`.  Buffers as ns2vc_k_sampler_admit takes them (n_items items of T rows of ld fp32 columns,
+ * ld % 4 == 0, 16-byte aligned; guided != 0: 2 * n_items items); mprev2 = NULL: 4 planes, else 5.  slots_host = HOST [n], sent as given: an entry
+ * outside [0, n_items) is skipped.  rec_dev = DEVICE [n_items][4] int32 or NULL: suspend writes the idle record {0, 1, INT32_MAX, 0} of every listed
+ * slot there, resume the slot's row of records_host = HOST [n][4] {row0, steps, start, flags} (given together with rec_dev). */
+int ns2vc_k_sampler_suspend(const float* xe, const float* xbar, const float* d1, const float* mprev, const float* mprev2, int T, int ld, int n,
+                            const int32_t* slots_host, int n_items, float* state_out, int32_t* rec_dev, void* stream);
+int ns2vc_k_sampler_resume(const float* state_in, int T, int ld, int n, const int32_t* slots_host, int n_items, const int32_t* records_host, int32_t* rec_dev,
+                           float* xe, void* xe_op, int precision, float* xbar, float* d1, float* mprev, float* mprev2, int guided, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

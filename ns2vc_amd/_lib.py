@@ -252,6 +252,11 @@ PROTOTYPES = {
     "ns2vc_sampler_set_known_items": (_I, [_P, _I, _P, _P, _P, _P]),
     "ns2vc_k_hold_slots": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ns2vc_k_known_items": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P]),
+    "ns2vc_sampler_state_shape": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "ns2vc_sampler_suspend": (_I, [_P, _I, _P, _P, _P, _P]),
+    "ns2vc_sampler_resume": (_I, [_P, _I, _P, _P, _P, _P]),
+    "ns2vc_k_sampler_suspend": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "ns2vc_k_sampler_resume": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

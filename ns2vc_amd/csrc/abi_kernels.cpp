@@ -588,4 +588,37 @@ int ns2vc_k_known_items(const float* known_nct, const uint8_t* mask_host, int C,
   return rc;
 }
 
+// the suspend / resume launches on their own; the slot list goes to the device AS GIVEN (the kernels skip an entry outside [0, n_items)),
+// rec_dev (DEVICE [n_items][4], or NULL) is the record table the launches write
+int ns2vc_k_sampler_suspend(const float* xe, const float* xbar, const float* d1, const float* mprev, const float* mprev2, int T, int ld, int n,
+                            const int32_t* slots_host, int n_items, float* state_out, int32_t* rec_dev, void* stream) {
+  if (!xe || !xbar || !d1 || !mprev || !slots_host || !state_out) return fail("null argument");
+  if (T <= 0 || ld <= 0 || (ld & 3) || n <= 0 || n_items <= 0) return fail("sampler_suspend: T (%d), n (%d) and n_items (%d) positive, ld (%d) a positive multiple of 4", T, n, n_items, ld);
+  void* sd = nullptr;
+  if (upload_bytes(slots_host, (size_t)n * sizeof(int), &sd, "sampler_suspend")) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launched(launch_sampler_suspend(xe, xbar, d1, mprev, mprev2, T, ld, n, static_cast<const int*>(sd), n_items, state_out,
+                                           reinterpret_cast<SolverItem*>(rec_dev), s), "sampler_suspend launch");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("sampler_suspend: stream synchronize failed");
+  (void)hipFree(sd);
+  return rc;
+}
+int ns2vc_k_sampler_resume(const float* state_in, int T, int ld, int n, const int32_t* slots_host, int n_items, const int32_t* records_host, int32_t* rec_dev,
+                           float* xe, void* xe_op, int precision, float* xbar, float* d1, float* mprev, float* mprev2, int guided, void* stream) {
+  if (!state_in || !slots_host || !xe || !xe_op || !xbar || !d1 || !mprev) return fail("null argument");
+  if (T <= 0 || ld <= 0 || (ld & 3) || n <= 0 || n_items <= 0) return fail("sampler_resume: T (%d), n (%d) and n_items (%d) positive, ld (%d) a positive multiple of 4", T, n, n_items, ld);
+  if ((rec_dev != nullptr) != (records_host != nullptr)) return fail("sampler_resume: the records and their device table are given together (both NULL = none)");
+  void *sd = nullptr, *rd = nullptr;
+  if (upload_bytes(slots_host, (size_t)n * sizeof(int), &sd, "sampler_resume")) return 1;
+  if (records_host && upload_bytes(records_host, (size_t)n * sizeof(SolverItem), &rd, "sampler_resume")) { (void)hipFree(sd); return 1; }
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launched(launch_sampler_resume(state_in, T, ld, n, static_cast<const int*>(sd), n_items, static_cast<const SolverItem*>(rd),
+                                          reinterpret_cast<SolverItem*>(rec_dev), xe, xe_op, precision, xbar, d1, mprev, mprev2,
+                                          precision != PREC_F32 ? ld : 0, guided ? n_items : 0, s), "sampler_resume launch");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail("sampler_resume: stream synchronize failed");
+  (void)hipFree(sd);
+  if (rd) (void)hipFree(rd);
+  return rc;
+}
+
 }  // extern "C"

@@ -487,6 +487,14 @@ hipError_t launch_sampler_take(const float* xe, int ld, int C, int T, int n, con
 hipError_t launch_condition_items(const float* content, int Cc, int T, const float* prompt, int Lp, int Cx, const uint8_t* mask, int n, const int* slots,
                                   int nslots, void* content_op, int prec, int split, float* content_f32, const int* lens, float* prompt_dst,
                                   uint8_t* mask_dst, hipStream_t s);
+// Suspend / resume of a slot's request: the state of the listed slots as P planes of T rows of ld fp32 columns, [n][P][T][ld] -- xe,
+// xbar, d1, mprev and, with an mprev2 buffer, mprev2 (P = 5) -- copied bit for bit in float4 quads (every pointer 16-byte aligned, ld % 4 == 0).
+// Suspend also writes the slots' idle records; resume rebuilds xe_op from xe as the solver update stores it, writes xe / xe_op to item slot + half of
+// a guided engine as well and zeroes that item's histories, and installs rec_in[k] as the slot's record.
+hipError_t launch_sampler_suspend(const float* xe, const float* xbar, const float* d1, const float* mprev, const float* mprev2, int T, int ld, int n,
+                                  const int* slots, int nslots, float* dst, SolverItem* rec, hipStream_t s);
+hipError_t launch_sampler_resume(const float* src, int T, int ld, int n, const int* slots, int nslots, const SolverItem* rec_in, SolverItem* rec, float* xe,
+                                 void* xe_op, int prec, float* xbar, float* d1, float* mprev, float* mprev2, int split, int half, hipStream_t s);
 // the normals a stochastic update adds at table row `step` (ns2vc_k_noise): out rows [B*T][ld] fp32, zeros where no noise goes
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s);
 hipError_t launch_fill_i32(int* p, int v, hipStream_t s);

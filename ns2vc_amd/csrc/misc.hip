@@ -1588,4 +1588,89 @@ hipError_t launch_known_items(const float* known, const uint8_t* mask, int C, in
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Suspend / resume of a slot's request (ns2vc_sampler_suspend / _resume): the solver state of the listed slots as P = 4 planes
+// (xe, xbar, d1, mprev) or 5 (+ mprev2, a loop opened with history 2) of T rows of ld fp32 columns each, [n][P][T][ld] in the caller's buffer.  Both
+// kernels move float4 quads bit for bit -- pad columns, rows past the length and the sign of a zero included -- one launch per slot list, an entry
+// outside [0, nslots) skipped and never used as an index.  They sit behind the slot kernels: every earlier kernel keeps its code.
+// ---------------------------------------------------------------------------
+// the planes of the listed slots -> dst, and the slots' records -> idle.  Grid (x, plane, k).
+__global__ __launch_bounds__(256) void sampler_suspend_kernel(const float4* __restrict__ xe, const float4* __restrict__ xbar, const float4* __restrict__ d1,
+                                                              const float4* __restrict__ mprev, const float4* __restrict__ mprev2, int q4,
+                                                              const int* __restrict__ slots, int nslots, float4* __restrict__ dst,
+                                                              SolverItem* __restrict__ rec) {
+  const int k = blockIdx.z, p = blockIdx.y;
+  const int slot = slots[k];
+  if (slot < 0 || slot >= nslots) return;
+  const float4* const plane = p == 0 ? xe : p == 1 ? xbar : p == 2 ? d1 : p == 3 ? mprev : mprev2;
+  const float4* const src = plane + (size_t)slot * q4;
+  float4* const d = dst + ((size_t)k * gridDim.y + p) * q4;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < q4; i += gridDim.x * 256) d[i] = src[i];
+  if (rec && blockIdx.x == 0 && p == 0 && threadIdx.x == 0) rec[slot] = solver_item_idle();
+}
+// src [n][P][T][ld] -> the listed slots' state: xe with its operand copy as the update writes it (solver_store_xe: 16-bit types the [hi | lo] pair),
+// xbar, d1, mprev and (P = 5) mprev2, and the slot's record.  half > 0 (guided engine of 2 * half items): xe / xe_op also go to item slot + half,
+// whose xbar, d1, mprev, mprev2 rows become zero, as sampler_admit_kernel leaves them.  Grid (x, k).
+template <typename TM>
+__global__ __launch_bounds__(256) void sampler_resume_kernel(const float4* __restrict__ src, int q4, const int* __restrict__ slots, int nslots,
+                                                             const SolverItem* __restrict__ rec_in, SolverItem* __restrict__ rec,
+                                                             float* __restrict__ xe, TM* __restrict__ xe_op, float* __restrict__ xbar,
+                                                             float* __restrict__ d1, float* __restrict__ mprev, float* __restrict__ mprev2, int split,
+                                                             int half) {
+  op_mode_init<TM>();
+  const int k = blockIdx.y;
+  const int slot = slots[k];
+  if (slot < 0 || slot >= nslots) return;
+  const size_t P = mprev2 ? 5 : 4;
+  const float4* const s = src + (size_t)k * P * q4;
+  const size_t base = (size_t)slot * q4, base2 = (size_t)(slot + half) * q4;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < q4; i += gridDim.x * 256) {
+    const float4 vxe = s[i], vxb = s[(size_t)q4 + i], vd1 = s[2 * (size_t)q4 + i], vmp = s[3 * (size_t)q4 + i];
+    const size_t e = base + i;
+    solver_store_xe<TM>(xe, xe_op, e, split, vxe);
+    out_f4(xbar + 4 * e, vxb.x, vxb.y, vxb.z, vxb.w);
+    out_f4(d1 + 4 * e, vd1.x, vd1.y, vd1.z, vd1.w);
+    out_f4(mprev + 4 * e, vmp.x, vmp.y, vmp.z, vmp.w);
+    if (mprev2) {
+      const float4 vm2 = s[4 * (size_t)q4 + i];
+      out_f4(mprev2 + 4 * e, vm2.x, vm2.y, vm2.z, vm2.w);
+    }
+    if (half > 0) {
+      const size_t e2 = base2 + i;
+      solver_store_xe<TM>(xe, xe_op, e2, split, vxe);
+      out_f4(xbar + 4 * e2, 0.f, 0.f, 0.f, 0.f);
+      out_f4(d1 + 4 * e2, 0.f, 0.f, 0.f, 0.f);
+      out_f4(mprev + 4 * e2, 0.f, 0.f, 0.f, 0.f);
+      if (mprev2) out_f4(mprev2 + 4 * e2, 0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  if (rec && blockIdx.x == 0 && threadIdx.x == 0) rec[slot] = rec_in[k];
+}
+static bool slot_state_fits(int T, int ld, int n, int nslots) {
+  return n > 0 && nslots > 0 && T > 0 && ld > 0 && !(ld & 3) && (size_t)T * ld / 4 <= (size_t)0x7fffffff / 8;
+}
+hipError_t launch_sampler_suspend(const float* xe, const float* xbar, const float* d1, const float* mprev, const float* mprev2, int T, int ld, int n,
+                                  const int* slots, int nslots, float* dst, SolverItem* rec, hipStream_t s) {
+  if (!xe || !xbar || !d1 || !mprev || !slots || !dst || !slot_state_fits(T, ld, n, nslots) ||
+      (((uintptr_t)xe | (uintptr_t)xbar | (uintptr_t)d1 | (uintptr_t)mprev | (uintptr_t)mprev2 | (uintptr_t)dst) & 15))
+    return hipErrorInvalidValue;
+  const int q4 = T * ld / 4;
+  const dim3 grid((unsigned)std::min(64, (q4 + 255) / 256), mprev2 ? 5 : 4, n);
+  hipLaunchKernelGGL(sampler_suspend_kernel, grid, dim3(256), 0, s, (const float4*)xe, (const float4*)xbar, (const float4*)d1, (const float4*)mprev,
+                     (const float4*)mprev2, q4, slots, nslots, (float4*)dst, rec);
+  return hipGetLastError();
+}
+hipError_t launch_sampler_resume(const float* src, int T, int ld, int n, const int* slots, int nslots, const SolverItem* rec_in, SolverItem* rec, float* xe,
+                                 void* xe_op, int prec, float* xbar, float* d1, float* mprev, float* mprev2, int split, int half, hipStream_t s) {
+  if (!src || !slots || !xe || !xe_op || !xbar || !d1 || !mprev || !slot_state_fits(T, ld, n, nslots) || half < 0 || (rec && !rec_in) ||
+      (split && (prec == PREC_F32 || split != ld)) ||
+      (((uintptr_t)src | (uintptr_t)xe | (uintptr_t)xe_op | (uintptr_t)xbar | (uintptr_t)d1 | (uintptr_t)mprev | (uintptr_t)mprev2) & 15))
+    return hipErrorInvalidValue;
+  const int q4 = T * ld / 4;
+  const dim3 grid((unsigned)std::min(128, (q4 + 255) / 256), n);
+  NS2VC_BY_PREC(prec, hipLaunchKernelGGL(sampler_resume_kernel<TMX>, grid, dim3(256), 0, s, (const float4*)src, q4, slots, nslots, rec_in, rec, xe,
+                                         (TMX*)xe_op, xbar, d1, mprev, mprev2, split, half));
+  return hipGetLastError();
+}
+
 }  // namespace ns2vc

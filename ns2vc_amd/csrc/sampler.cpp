@@ -231,9 +231,11 @@ int ns2vc_sampler_set_x0_correction_items(ns2vc_unet* h, const int32_t* mode_hos
   const bool slot_loop = h->in_slot_loop();
   // a slot loop's admitted items are checked here (nothing looks at them again; an idle slot has no flags); closed schedules are checked when they
   // load and when the loop begins, so the table and the schedules of a new batch may arrive in either order
-  if (slot_loop && (int)h->slots.rec.size() == n &&
-      solver_items_fit("slot", h->slots.rec.data(), nullptr, n, h->items.rows, nullptr, nullptr, nullptr, 0, rec.data()))
-    return 1;
+  if (slot_loop && (int)h->slots.rec.size() == n) {
+    std::vector<SolverItem> cur = h->slots.rec;      // (a resumed request's start lies in the past, below 0 after a rebase: ns2vc_sampler_resume)
+    for (SolverItem& r : cur) r.start = std::max(r.start, 0);
+    if (solver_items_fit("slot", cur.data(), nullptr, n, h->items.rows, nullptr, nullptr, nullptr, 0, rec.data())) return 1;
+  }
   if (ic.reserve(h, (size_t)n, false) || ensure_thr(h) || ic.send(rec.data(), (size_t)n, (hipStream_t)stream)) return 1;
   const bool quant = dyn || slot_loop;      // (a slot loop always has the launch: its admissions bring records the host cannot foresee)
   if (!ic.on || quant != ic.quant) drop_step_graph(h);
@@ -813,6 +815,103 @@ int ns2vc_sampler_take(ns2vc_unet* h, int n, const int32_t* slots, float* x_out_
   for (int k = 0; k < n; ++k) {
     sl.rec[slots[k]] = solver_item_idle();
     sl.busy[slots[k]] = 0;
+  }
+  return 0;
+}
+
+// Suspend and resume of a running request.  The state of a slot is P planes of T rows of CP fp32 columns (xe, xbar, d1, mprev, and
+// mprev2 in a loop opened with history 2) and its position done = loop step - start; everything else the caller holds and sends again.
+int ns2vc_sampler_state_shape(ns2vc_unet* h, int* planes, int* T, int* ld) {
+  if (need_slot_loop(h)) return 1;
+  if (!planes || !T || !ld) return fail("null argument");
+  *planes = h->hist2.on ? 5 : 4;
+  *T = h->T;
+  *ld = h->CP;
+  return 0;
+}
+
+int ns2vc_sampler_suspend(ns2vc_unet* h, int n, const int32_t* slots, float* state_out_dev, int32_t* done_out_host, void* stream) {
+  if (need_slot_loop(h)) return 1;
+  if (!state_out_dev || !done_out_host) return fail("null argument");
+  if ((uintptr_t)state_out_dev & 15) return fail("the state buffer must be 16-byte aligned");
+  auto& sl = h->slots;
+  const int ni = h->loop_items();
+  if ((int)sl.rec.size() != ni) return fail("the slot loop was opened for %d items, the loop has %d: open it again", (int)sl.rec.size(), ni);
+  if (!slots || n <= 0 || n > ni) return fail("a slot list needs 1 .. %d entries, got %d", ni, n);
+  for (int k = 0; k < n; ++k) {
+    const int b = slots[k];
+    if (b < 0 || b >= ni) return fail("slots[%d] = %d outside [0, %d)", k, b, ni);
+    if (!sl.busy[b]) return fail("slot %d is idle: nothing to suspend", b);
+    const SolverItem& r = sl.rec[b];
+    if (h->next_step < r.start) return fail("slot %d has not started: it begins at loop step %d, the loop stands at %d (take nothing, admit it later instead)", b, r.start, h->next_step);
+    if (h->next_step - r.start >= r.steps)
+      return fail("slot %d has finished (loop step %d of %d + %d): take it (ns2vc_sampler_take)", b, h->next_step, r.start, r.steps);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int* slots_dev = nullptr;
+  if (stage_slot_list(h, n, slots, ni, nullptr, s, &slots_dev, nullptr)) return 1;
+  HIPCHK(launch_sampler_suspend(h->xe, h->xbar, h->d1, h->mprev, h->hist2.on ? h->hist2.dev : nullptr, h->T, h->CP, n, slots_dev, ni, state_out_dev,
+                                h->items.dev, s));
+  if (h->shold.on && (int)h->shold.last.size() == ni) {      // the request leaves with its known frames, as on a take: resume sends them again
+    HIPCHK(launch_known_items(nullptr, nullptr, h->cfg.latent_channels, h->T, n, slots_dev, ni, h->shold.known.dev, h->shold.mask.dev, h->CP, s));
+    for (int k = 0; k < n; ++k) h->shold.last[(size_t)slots[k]] = -1;
+  }
+  for (int k = 0; k < n; ++k) {
+    done_out_host[k] = h->next_step - sl.rec[slots[k]].start;
+    sl.rec[slots[k]] = solver_item_idle();
+    sl.busy[slots[k]] = 0;
+  }
+  return 0;
+}
+
+// records: n x {row0, steps, done, flags}; the slot continues at row row0 + done with the next step (start = loop step - done)
+int ns2vc_sampler_resume(ns2vc_unet* h, int n, const int32_t* slots, const float* state_in_dev, const int32_t* records, void* stream) {
+  if (need_slot_loop(h)) return 1;
+  if (!state_in_dev || !records) return fail("null argument");
+  if ((uintptr_t)state_in_dev & 15) return fail("the state buffer must be 16-byte aligned");
+  auto& sl = h->slots;
+  const int ni = h->loop_items();
+  if (h->items.n != ni || (int)sl.rec.size() != ni) return fail("the slot loop was opened for %d items, the loop has %d: open it again", h->items.n, ni);
+  if (h->stochastic && !h->seeds.set) return fail("the slot loop takes stochastic items: set per-item seeds first (ns2vc_sampler_set_seeds)");
+  if (!slots || n <= 0 || n > ni) return fail("a slot list needs 1 .. %d entries, got %d", ni, n);
+  const SolverItem* in = reinterpret_cast<const SolverItem*>(records);      // (.start holds `done`)
+  for (int k = 0; k < n; ++k) {
+    const int b = slots[k];
+    if (b < 0 || b >= ni) return fail("slots[%d] = %d outside [0, %d)", k, b, ni);
+    if (sl.busy[b]) return fail("slot %d is busy (admitted at loop step %d for %d steps, not taken yet): resume into an idle slot", b, sl.rec[b].start, sl.rec[b].steps);
+    if (in[k].steps > 0 && (in[k].start < 0 || in[k].start >= in[k].steps))
+      return fail("slot %d: done %d outside [0, %d): a request that has run all its rows is taken, not resumed", b, in[k].start, in[k].steps);
+  }
+  const auto& ic = h->x0c.items;
+  if (solver_items_fit("slot", in, slots, n, kSlotRows, sl.coef.data(),
+                       h->hist2.on ? nullptr : "the slot loop was opened without it (ns2vc_sampler_open history2 = 1)",
+                       h->stochastic ? nullptr : "the slot loop was opened without noise (ns2vc_sampler_open noise = 1)", h->x0c.mode,
+                       ic.on && ic.n == ni ? ic.host.data() : nullptr))
+    return 1;
+  std::vector<SolverItem> rec(in, in + n);
+  for (int k = 0; k < n; ++k) {
+    const int b = slots[k];
+    SolverItem& r = rec[(size_t)k];
+    r.start = h->next_step - in[k].start;      // in the past; below 0 after a rebase (done <= 1024: r - start cannot overflow)
+    if (r.start > SOLVER_ITEM_NEVER - 1 - r.steps)
+      return fail("slot %d: loop steps %d + %d pass the end of the 32-bit step counter: drain the slots and call ns2vc_sampler_rebase", b, r.start, r.steps);
+    for (int i = 0; i < r.steps; ++i)
+      if (sl.coef[(size_t)(r.row0 + i) * NS2VC_NCOEF + 1] == 0.f) return fail("slot %d: row %d of the table was never written (ns2vc_sampler_write_rows)", b, r.row0 + i);
+    if (h->guide.on && h->lens.masked && h->lens.applied[b] != h->lens.applied[b + ni]) return fail("guided slot loop: lengths[%d] and lengths[%d] differ", b, b + ni);
+    if (h->shold.on && h->lens.masked && (int)h->shold.last.size() == ni && h->shold.last[(size_t)b] >= h->lens.applied[(size_t)b])
+      return fail("known frame %d of slot %d lies at or past its length %d: set the known frames after the lengths", (int)h->shold.last[(size_t)b], b,
+                  (int)h->lens.applied[(size_t)b]);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int* slots_dev = nullptr;
+  const SolverItem* rec_dev = nullptr;
+  if (stage_slot_list(h, n, slots, ni, rec.data(), s, &slots_dev, &rec_dev)) return 1;
+  HIPCHK(launch_sampler_resume(state_in_dev, h->T, h->CP, n, slots_dev, ni, rec_dev, h->items.dev, h->xe, h->xe_op, h->prec, h->xbar, h->d1, h->mprev,
+                               h->hist2.on ? h->hist2.dev : nullptr, h->pair_off(), h->guide.on ? ni : 0, s));
+  for (int k = 0; k < n; ++k) {
+    sl.rec[slots[k]] = rec[(size_t)k];
+    sl.busy[slots[k]] = 1;
+    h->steps = std::max(h->steps, rec[(size_t)k].start + rec[(size_t)k].steps);
   }
   return 0;
 }

@@ -608,6 +608,32 @@ class Engine:
         s = self._slot_list(slots)
         check(self.lib.ns2vc_sampler_take(self.h, int(s.shape[0]), s.ctypes.data, _ptr(out), _stream_ptr(stream)), "sampler_take")
 
+    def state_shape(self) -> Tuple[int, int, int]:
+        """(planes, T, ld) of one slot's solver state in the open slot loop: xe, xbar, d1, mprev (+ mprev2 with history 2), fp32 rows"""
+        p, t, ld = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.ns2vc_sampler_state_shape(self.h, C.byref(p), C.byref(t), C.byref(ld)), "sampler_state_shape")
+        return int(p.value), int(t.value), int(ld.value)
+
+    def suspend(self, slots, state, stream=None) -> List[int]:
+        """the solver state of the running ``slots`` -> ``state`` (n, planes, T, ld) fp32 on the GPU, bit for bit; the slots become idle (in a
+        loop with known frames their frames are cleared); returns each slot's ``done`` = rows of its table already run.  One launch, no
+        recapture, no wait."""
+        s = self._slot_list(slots)
+        done = np.zeros((s.shape[0],), dtype=np.int32)
+        check(self.lib.ns2vc_sampler_suspend(self.h, int(s.shape[0]), s.ctypes.data, _ptr(state), done.ctypes.data, _stream_ptr(stream)),
+              "sampler_suspend")
+        return [int(d) for d in done]
+
+    def resume(self, slots, state, records, stream=None) -> None:
+        """idle ``slots`` take ``state`` (n, planes, T, ld) fp32 on the GPU and ``records`` (n, 4) int32 {row0, steps, done, flags}: each
+        continues at row ``done`` of its table with the next step.  Set the slots' lengths, condition, seed, scale, correction and known
+        frames first, as for ``admit``.  One launch."""
+        s = self._slot_list(slots)
+        r = np.ascontiguousarray(np.asarray(records), dtype=np.int32)
+        if r.shape != (s.shape[0], 4):
+            raise ValueError(f"records must be ({s.shape[0]}, 4) {{row0, steps, done, flags}}, got {r.shape}")
+        check(self.lib.ns2vc_sampler_resume(self.h, int(s.shape[0]), s.ctypes.data, _ptr(state), r.ctypes.data, _stream_ptr(stream)), "sampler_resume")
+
     def slot_step(self) -> int:
         """the loop step the next ``sample_steps`` of a slot loop starts at (-1: no slot loop)"""
         n = C.c_int()

@@ -845,6 +845,31 @@ def slot_tail_needed(precision: str, solver: str, order: int, scale: float = 1.0
     return n
 
 
+class Suspended:
+    """A request taken out of a running slot loop (``SlotLoop.suspend``): its solver ``state`` (planes, T, ld) fp32 -- xe, xbar,
+    d1, mprev and, in a loop opened with ``order3=True``, mprev2 --, its position ``done`` = rows of its table already run, and everything
+    ``SlotLoop.resume`` sends again as an admission sends it: the ``schedule`` with its pool ``key`` and ``table``, ``length`` and
+    ``prompt_length``, ``seed``, ``guidance_scale``, ``correction``, ``known`` / ``known_mask``, ``content`` and ``prompt``."""
+
+    FIELDS = ("state", "done", "schedule", "key", "table", "flags", "length", "prompt_length", "seed", "guidance_scale", "correction", "known",
+              "known_mask", "content", "prompt")
+
+    def __init__(self, **kw):
+        missing = [k for k in self.FIELDS if k not in kw]
+        if missing or len(kw) != len(self.FIELDS):
+            raise ValueError(f"Suspended takes exactly the fields {self.FIELDS}")
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+
+    @property
+    def steps(self) -> int:
+        return int(self.table.steps)
+
+    def to(self, device) -> "Suspended":
+        """the same request with its state tensor on ``device`` ("cpu": spilled to host memory; a CUDA device: ready for ``resume`` there)"""
+        return Suspended(**dict({k: getattr(self, k) for k in self.FIELDS}, state=self.state.to(device)))
+
+
 class SlotLoop:
     """A running loop of B slots (``Denoiser.open_slots``).  ``admit`` puts a request into an idle slot at the current loop
     step, ``run`` steps the loop until the next busy slot finishes (or by ``n`` steps), ``take`` fetches finished slots' latents and frees
@@ -1054,21 +1079,40 @@ class SlotLoop:
             self._self_check(slots, c_all, p_all, x_all, [r[1] for r in reqs], s)
             eng.rebase_slots(stream=s)
             self.step = 0
+        self._place(slots, [r[:3] for r in reqs], [self.step] * n, c_all, p_all, k_all, m_all, s,
+                    lambda records: eng.admit(slots, x_all, records, stream=s))
+        for t in (c_all, p_all, x_all) + (() if k_all is None else (k_all,)):
+            if t.is_cuda:
+                t.record_stream(s)
+        for k, b in enumerate(slots):
+            self.items[b] = dict(key=reqs[k][0], start=self.step, steps=reqs[k][1].steps, length=reqs[k][3],
+                                 req=dict(schedule=dict(schedules[k]), table=reqs[k][1], flags=reqs[k][2], prompt_length=reqs[k][4], seed=seeds[k],
+                                          guidance_scale=scales[k], correction=corrections[k], known=None if holds[k] is None else holds[k][0],
+                                          known_mask=None if holds[k] is None else holds[k][1], content=contents[k], prompt=prompts[k]))
+
+    def _place(self, slots, entries, position, c_all, p_all, k_all, m_all, s, launch) -> None:
+        """the engine calls that put requests into idle ``slots``, shared by ``admit_group`` and ``resume``: the tables' rows (``entries`` =
+        [(key, table, flags)]; written where the pool says so), the per-slot vectors (lengths, prompt lengths, seeds, corrections, guidance),
+        the condition, the known frames, then ``launch(records)`` with records {row0, steps, ``position[k]``, flags} -- the start of an
+        admission, the rows already run of a resume.  On any error the tables' users go back and the slots hold no frames."""
+        import torch
+        cfg, eng, n = self.den.cfg, self.den.engine, len(slots)
+        dev = c_all.device
         records = np.zeros((n, 4), dtype=np.int32)
         acquired = []
         known_sent = False
         try:
-            for k, (key, table, flags, L, lp) in enumerate(reqs):
+            for k, (key, table, flags) in enumerate(entries):
                 row0, write = self.pool.acquire(key, table.coef)
                 acquired.append(key)
                 if write:
                     eng.write_sampler_rows(row0, table.coef, stream=s)
-                records[k] = (row0, table.steps, self.step, flags)
+                records[k] = (row0, table.steps, position[k], flags)
             eng.set_lengths(self.lengths, stream=s)
             eng.set_prompt_lengths(self.plens, stream=s)
             if self.stochastic:
                 eng.set_seeds(self.seeds, stream=s)
-            if self.item_corrections:      # (the whole vector: only the admitted slots' entries have changed)
+            if self.item_corrections:      # (the whole vector: only the placed slots' entries have changed)
                 self.den._correct(eng, None, self.corrections, s)
             if self.rep == 2:
                 eng.set_guidance(self.scales, stream=s)
@@ -1080,21 +1124,130 @@ class SlotLoop:
             if k_all is not None:
                 eng.set_known_items(slots, k_all, m_all, stream=s)
                 known_sent = True
-            eng.admit(slots, x_all, records, stream=s)
-        except Exception:          # nothing was admitted: the tables' users go back (the slots stay idle)
+            launch(records)
+        except Exception:          # nothing was placed: the tables' users go back (the slots stay idle)
             for key in acquired:
                 self.pool.release(key)
             if known_sent:         # ... and hold no frames: a later request without known frames sends none and must find the slots clear
                 try:
                     eng.set_known_items(slots, None, None, stream=s)
-                except Exception:      # noqa: BLE001 (the admission's own error is the one to report)
+                except Exception:      # noqa: BLE001 (the placement's own error is the one to report)
                     pass
             raise
-        for t in (c_all, p_all, x_all) + (() if k_all is None else (k_all,)):
+
+    # -- suspend and resume ------------------------------------------------------------------------------------
+    def suspend(self, slots):
+        """takes the running requests of ``slots`` out of the loop: one ``Suspended`` per slot, in order, holding the solver state bit for bit
+        and the rows already run; the slots become idle and their tables' pool users are released.  Only a request with rows still to run
+        (a finished one is taken).  One launch, no recapture, nothing waits for the device."""
+        import torch
+        slots = [int(b) for b in slots]
+        if not slots or len(set(slots)) != len(slots) or any(b < 0 or b >= self.B for b in slots):
+            raise ValueError(f"slots must be distinct and in [0, {self.B}), got {slots}")
+        bad = [b for b in slots if self.items[b] is None or not 0 <= self.step - self.items[b]["start"] < self.items[b]["steps"]]
+        if bad:
+            raise ValueError(f"slot(s) {bad} hold no running request (an idle slot has none; a finished one is taken)")
+        norec = [b for b in slots if "req" not in self.items[b]]
+        if norec:
+            raise ValueError(f"slot(s) {norec} were not admitted through this loop: nothing to send again on resume")
+        eng = self.den.engine
+        s = torch.cuda.current_stream(self.dev)
+        P, T, ld = eng.state_shape()
+        state = torch.empty((len(slots), P, T, ld), dtype=torch.float32, device=self.dev)
+        done = eng.suspend(slots, state, stream=s)
+        if state.is_cuda:
+            state.record_stream(s)
+        out = []
+        for k, b in enumerate(slots):
+            it = self.items[b]
+            if int(done[k]) != self.step - it["start"]:
+                raise RuntimeError(f"slot {b}: the engine reports {int(done[k])} rows run, the loop {self.step - it['start']}")
+            out.append(Suspended(state=state[k], done=int(done[k]), key=it["key"], length=it["length"], **it["req"]))
+            self.pool.release(it["key"])
+            self.items[b] = None
+            if self.item_corrections:
+                self.corrections[b] = None
+        return out
+
+    def resume(self, slots, suspended) -> None:
+        """puts the ``suspended`` requests back into the idle ``slots`` of this loop -- or of another loop of the same T, padded channels and
+        form -- at the current loop step: ``admit_group``'s sequence (tables, lengths, seeds, corrections, guidance, condition, known frames)
+        with the saved state in place of x_T.  Each continues at row ``done`` and, in the slot index it left, ends on the bits of the
+        uninterrupted run.  Never runs the precision self-check: it raises while the denoiser's check is pending."""
+        import torch
+        slots = [int(b) for b in slots]
+        suspended = list(suspended)
+        n = len(slots)
+        if n == 0 or len(suspended) != n or any(not isinstance(q, Suspended) for q in suspended):
+            raise ValueError("resume needs one Suspended per slot")
+        if len(set(slots)) != n or any(b < 0 or b >= self.B for b in slots):
+            raise ValueError(f"slots must be distinct and in [0, {self.B}), got {slots}")
+        busy = [b for b in slots if self.items[b] is not None]
+        if busy:
+            raise ValueError(f"slot(s) {busy} are busy: take or suspend them first")
+        if self.den.precision_check is not None and not self.den._precision_checked:
+            raise RuntimeError("the precision self-check of this Denoiser is pending: it runs on an admission into an idle loop, never on a "
+                               "resume (admit a request first, or build the Denoiser with precision_check=None)")
+        cfg = self.den.cfg
+        eng = self.den.engine
+        shape = eng.state_shape()
+        for k, q in enumerate(suspended):
+            key, table, flags = self.check_request(q.schedule, q.guidance_scale, q.correction)
+            if key != q.key or flags != q.flags or table.steps != q.steps:
+                raise ValueError(f"suspended[{k}]: its schedule gives another table here (key {key}, {table.steps} rows) than where it ran "
+                                 f"(key {q.key}, {q.steps} rows)")
+            if not 0 <= int(q.done) < q.steps:
+                raise ValueError(f"suspended[{k}]: done {q.done} outside [0, {q.steps})")
+            if tuple(q.state.shape) != tuple(shape) or q.state.dtype != torch.float32:
+                raise ValueError(f"suspended[{k}]: state {tuple(q.state.shape)} {q.state.dtype}, this loop's is float32 {tuple(shape)} (planes, T, padded "
+                                 f"channels): resume into a loop of the same T and form")
+            if not (1 <= q.length <= self.T) or not (1 <= q.prompt_length <= self.Lp):
+                raise ValueError(f"suspended[{k}]: length {q.length} / prompt_length {q.prompt_length} outside this loop's T = {self.T} / Lp = {self.Lp}")
+            if q.known is not None and not self.known_frames:
+                raise ValueError("a request with known frames needs a slot loop opened with known_frames=True")
+        dev = self.dev
+        s = torch.cuda.current_stream(dev)
+        if not any(it is not None for it in self.items) and self.step >= self.REBASE_AT:
+            eng.rebase_slots(stream=s)
+            self.step = 0
+        c_all = torch.zeros((n, cfg.content_channels, self.T), dtype=torch.float32, device=dev)
+        p_all = torch.zeros((n, self.Lp, cfg.cross_attention_dim), dtype=torch.float32, device=dev)
+        for k, q in enumerate(suspended):
+            c_all[k, :, :q.length] = q.content[:, :q.length].to(dev, torch.float32)
+            p_all[k, :q.prompt_length] = q.prompt[:q.prompt_length].to(dev, torch.float32)
+        state = torch.stack([q.state.to(dev) for q in suspended]).contiguous()
+        k_all = m_all = None
+        if any(q.known is not None for q in suspended):
+            k_all = torch.zeros((n, cfg.latent_channels, self.T), dtype=torch.float32, device=dev)
+            m_all = np.zeros((n, self.T), dtype=bool)
+            for k, q in enumerate(suspended):
+                if q.known is not None:
+                    Lk = q.known_mask.shape[0]
+                    k_all[k, :, :Lk] = q.known.to(dev, torch.float32)
+                    m_all[k, :Lk] = q.known_mask
+        saved = (self.lengths.copy(), self.plens.copy(), self.seeds.copy(), self.scales.copy(), list(self.corrections))
+        for k, b in enumerate(slots):
+            q = suspended[k]
+            self.lengths[b], self.plens[b], self.seeds[b], self.scales[b] = q.length, q.prompt_length, q.seed, q.guidance_scale
+            if self.item_corrections:
+                self.corrections[b] = item_correction_entry(q.correction)
+            if self.rep == 2:
+                self.lengths[b + self.B], self.plens[b], self.plens[b + self.B] = q.length, int(self.uncond.shape[1]), q.prompt_length
+        try:
+            self._place(slots, [(q.key, q.table, q.flags) for q in suspended], [q.done for q in suspended], c_all, p_all, k_all, m_all, s,
+                        lambda records: eng.resume(slots, state, records, stream=s))
+        except Exception:          # nothing was resumed: the slots stay idle with the vectors they had, the requests stay with the caller
+            self.lengths, self.plens, self.seeds, self.scales, self.corrections = saved
+            raise
+        for t in (c_all, p_all, state) + (() if k_all is None else (k_all,)):
             if t.is_cuda:
                 t.record_stream(s)
         for k, b in enumerate(slots):
-            self.items[b] = dict(key=reqs[k][0], start=self.step, steps=reqs[k][1].steps, length=reqs[k][3])
+            q = suspended[k]
+            self.items[b] = dict(key=q.key, start=self.step - q.done, steps=q.steps, length=q.length,
+                                 req=dict(schedule=dict(q.schedule), table=q.table, flags=q.flags, prompt_length=q.prompt_length, seed=q.seed,
+                                          guidance_scale=q.guidance_scale, correction=q.correction, known=q.known, known_mask=q.known_mask,
+                                          content=q.content, prompt=q.prompt))
 
     def _check_known(self, n, knowns, known_masks, lengths):
         """the known frames of an admission, checked before any engine call: per request None or (known (100, L') tensor, mask (L',) bool

@@ -870,18 +870,36 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
     A request's known frames are a fifth element, ``(table, start, x_T, correction, hold)``: None or ``(known, mask)`` shaped
     ``shape[1:]`` and ``(T,)`` bool.  ``hold_x0`` is applied to that slot's x0 at every evaluation while the item is the slot's current one --
     from its admission until the next one, as the engine's per-slot mask stands until the slot is taken -- so the item equals
-    ``run_table_numpy(..., hold=)`` of it alone, bit for bit.  Refused together with a correction, in the same tuple or in ``correct_x0=``."""
+    ``run_table_numpy(..., hold=)`` of it alone, bit for bit.  Refused together with a correction, in the same tuple or in ``correct_x0=``.
+    A request run in PIECES (suspend and resume) is a sixth element, ``(table, start, x_T, correction, hold, (request, a, b))``:
+    this entry runs rows ``[a, b)`` of the table, 0 <= a < b <= rows, at loop steps start .. start + (b - a) - 1.  ``request`` is any hashable
+    name that the pieces of one request share; they may sit in the same slot or in different ones.  A piece with a == 0 loads its state from
+    x_T as an admission does; a piece with a > 0 loads the five state arrays the piece of the same request that ended at row a left (that piece
+    must have ended at an earlier loop step; its x_T is not read) -- what a resume writes.  A piece with b < rows saves the state after row
+    b - 1 and has the result None -- what a suspend copies out; the piece with b == rows gives the request's result.  Correction and hold are
+    sent with every piece, as the engine's caller sends them with every resume; ``noise_fn(b, k, j)`` gets the row j of the TABLE, so a
+    stochastic request continues its own stream when it keys the stream by j.  The result equals ``run_table_numpy`` of the request alone."""
     f = np.float32
     B = int(shape[0])
     if len(timeline) != B:
         raise ValueError(f"{len(timeline)} slot timelines for {B} slots")
+
+    def rows_of(item):      # the rows [a, b) of its table this timeline entry runs, and the request it is a piece of (None: a whole request)
+        if len(item) > 5 and item[5] is not None:
+            rid, a, e = item[5]
+            if not 0 <= int(a) < int(e) <= item[0].steps:
+                raise ValueError(f"a piece runs rows [a, b) with 0 <= a < b <= {item[0].steps}, got [{a}, {e})")
+            return int(a), int(e), rid
+        return 0, item[0].steps, None
+
     for b, items in enumerate(timeline):
         end = 0
         for k, item in enumerate(items):
-            tab, start = item[0], item[1]
+            start = item[1]
             if int(start) < end:
                 raise ValueError(f"slot {b}: item {k} starts at loop step {start}, the slot is busy until {end}")
-            end = int(start) + tab.steps
+            a, e, _ = rows_of(item)
+            end = int(start) + e - a
     own = [[item_correction(item[3], bool(table_flags(item[0]) & ITEM_NOISE), f"slot {b} item {k}") if len(item) > 3 else None
             for k, item in enumerate(items)] for b, items in enumerate(timeline)]
     if correct_x0 is not None and any(len(item) > 3 for items in timeline for item in items):
@@ -900,24 +918,33 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
                 holds[b][k] = (hk[0], hm[0])
     state = _start_state(np.zeros(shape, f))
     xe = state[0]
-    S = max([int(item[1]) + item[0].steps for items in timeline for item in items], default=0)
+    S = max([int(item[1]) + rows_of(item)[1] - rows_of(item)[0] for items in timeline for item in items], default=0)
     results = [[None] * len(items) for items in timeline]
     cur = [-1] * B          # the item slot b holds (the last one admitted)
     hist2 = [False] * B     # ... and whether its table has history 2
+    saved: Dict[object, tuple] = {}      # request -> (rows run, its five state arrays) left by its last piece
     for r in range(S):
         t = np.zeros((B,), f)
         act = [None] * B
         for b, items in enumerate(timeline):
-            if cur[b] + 1 < len(items) and int(items[cur[b] + 1][1]) == r:      # admission
+            if cur[b] + 1 < len(items) and int(items[cur[b] + 1][1]) == r:      # admission, or the resume of a later piece
                 cur[b] += 1
                 hist2[b] = has_history2(items[cur[b]][0])
-                for a, v in zip(state, _start_state(np.asarray(items[cur[b]][2], dtype=f))):
+                a0, _, rid = rows_of(items[cur[b]])
+                if a0 > 0:
+                    if rid not in saved or saved[rid][0] != a0:
+                        raise ValueError(f"slot {b} item {cur[b]}: no piece of request {rid!r} has ended at row {a0} before loop step {r}")
+                    first = saved.pop(rid)[1]
+                else:
+                    first = _start_state(np.asarray(items[cur[b]][2], dtype=f))
+                for a, v in zip(state, first):
                     a[b] = v
             if cur[b] >= 0:
                 tab, start = items[cur[b]][0], items[cur[b]][1]
-                j = r - int(start)
-                t[b] = f(tab.coef[min(max(j, 0), tab.steps - 1), 0])
-                if 0 <= j < tab.steps:
+                a0, e0, _ = rows_of(items[cur[b]])
+                j = a0 + r - int(start)
+                t[b] = f(tab.coef[min(max(j, a0), e0 - 1), 0])
+                if a0 <= j < e0:
                     act[b] = (tab, j)
         x0 = np.asarray(x0_fn(xe, t)).astype(f)
         for b in range(B):
@@ -928,8 +955,11 @@ def run_slots_numpy(timeline, x0_fn: Callable[[np.ndarray, np.ndarray], np.ndarr
                 continue
             tab, j = act[b]
             _item_step(state, b, x0, tab, j, hist2[b], corr, own[b][cur[b]], noise_fn, (b, cur[b], j), f"slot {b}")
+            _, e0, rid = rows_of(timeline[b][cur[b]])
             if j == tab.steps - 1:
                 results[b][cur[b]] = xe[b].copy()
+            elif j == e0 - 1:      # the end of a piece that is not the last: what a suspend copies out
+                saved[rid] = (e0, [a[b].copy() for a in state])
         if trace is not None:
             trace.append(xe.copy())
     return results
@@ -1028,6 +1058,76 @@ def plan_slots(steps: Sequence[int], n_slots: int, arrivals: Optional[Sequence[i
         if not nexts:
             break
         r = min(nexts)          # (> r: what finished by r was taken, what had arrived by r and found a slot was admitted)
+    return events
+
+
+def plan_slots_preemptive(steps: Sequence[int], n_slots: int, arrivals: Optional[Sequence[int]] = None, priorities: Optional[Sequence[int]] = None):
+    """``plan_slots`` for a loop whose running requests can be suspended and resumed, as a pure function.  ``priorities[i]``:
+    an int per request, higher = more urgent (default: all 0).  Returns events ``(loop_step, take, suspend, admit)`` in loop order: ``take`` =
+    [(slot, request)] finished at that step; ``suspend`` = [(slot, request, done)] -- the request leaves the slot with ``done`` of its rows
+    run --; ``admit`` = [(slot, request, done)], ``done`` = 0 an admission and ``done`` > 0 the resume of a suspended request at that row.
+    The policy at an event step: (1) take what has finished; (2) fill the free slots, lowest first, from the requests that have arrived and
+    wait, the suspended ones among them -- the higher priority first, then queue order; (3) while the best waiting request has a strictly
+    higher priority than some running one, suspend the running request of lowest priority -- among equals the one with most rows left, then the
+    highest slot --, never one placed at this same step, and give its slot to the waiting request.  Event steps are the steps at which a
+    request finishes or arrives.  With equal or no priorities nothing is ever suspended, and the ``(loop_step, take, admit)`` parts are
+    ``plan_slots``' events (with ``done`` = 0 added to every admission)."""
+    steps = [int(s) for s in steps]
+    n = len(steps)
+    if n_slots < 1 or any(s < 1 for s in steps):
+        raise ValueError("plan_slots_preemptive needs n_slots >= 1 and steps >= 1")
+    arr = [0] * n if arrivals is None else [int(a) for a in arrivals]
+    if len(arr) != n or any(a < 0 for a in arr) or any(arr[i] > arr[i + 1] for i in range(n - 1)):
+        raise ValueError("arrivals must hold one non-decreasing loop step >= 0 per request")
+    pri = [0] * n if priorities is None else [int(p) for p in priorities]
+    if len(pri) != n:
+        raise ValueError("priorities must hold one int per request")
+    done = [0] * n
+    holder = [None] * n_slots
+    since = [0] * n_slots             # loop step at which the slot's request was placed
+    finished = [False] * n
+    events, r = [], 0
+
+    def rows_run(b):
+        return done[holder[b]] + r - since[b]
+
+    while not all(finished):
+        take = []
+        for b in range(n_slots):
+            i = holder[b]
+            if i is not None and rows_run(b) >= steps[i]:
+                take.append((b, i))
+                holder[b], finished[i], done[i] = None, True, steps[i]
+        running = {h for h in holder if h is not None}
+        waiting = sorted((i for i in range(n) if not finished[i] and i not in running and arr[i] <= r), key=lambda i: (-pri[i], i))
+        admit, suspend, placed = [], [], set()
+        for b in range(n_slots):
+            if holder[b] is None and waiting:
+                i = waiting.pop(0)
+                holder[b], since[b] = i, r
+                admit.append((b, i, done[i]))
+                placed.add(b)
+        while waiting:
+            i = waiting[0]
+            victims = [b for b in range(n_slots) if b not in placed and holder[b] is not None and pri[holder[b]] < pri[i]]
+            if not victims:
+                break
+            b = min(victims, key=lambda v: (pri[holder[v]], -(steps[holder[v]] - rows_run(v)), -v))
+            j = holder[b]
+            done[j] = rows_run(b)
+            suspend.append((b, j, done[j]))
+            waiting.pop(0)
+            holder[b], since[b] = i, r
+            admit.append((b, i, done[i]))
+            placed.add(b)
+            waiting = sorted(waiting + [j], key=lambda q: (-pri[q], q))
+        if take or admit or suspend:
+            events.append((r, take, suspend, admit))
+        nexts = [since[b] + steps[holder[b]] - done[holder[b]] for b in range(n_slots) if holder[b] is not None]
+        nexts += [arr[i] for i in range(n) if arr[i] > r]
+        if not nexts:
+            break
+        r = min(nexts)
     return events
 
 

@@ -46,7 +46,8 @@ from .frontend import PreModel
 from .noise import derive_seed
 from .pipeline import MASKED_OPTIONS, Denoiser, OverlappedPipeline
 from .request import CORRECTION_KEYS, call_wide_kwargs
-from .schedule import ITEM_HIST2, ITEM_NOISE, build_table, plan_chains, plan_chunks, schedule_key, table_flags, table_options
+from .schedule import (ITEM_HIST2, ITEM_NOISE, build_table, plan_chains, plan_chunks, plan_slots, plan_slots_preemptive, schedule_key, table_flags,
+                       table_options)
 
 
 @dataclass
@@ -64,6 +65,8 @@ class Segment:
     # the converter's.  ``GroupedConverter`` serves a group whose segments differ through ``Denoiser.sample(corrections=)``,
     # ``ContinuousConverter(item_corrections=True)`` gives every request its own; a segment's result does not depend on its group
     correction: Optional[dict] = None
+    # ``ContinuousConverter(preempt=True)``: a waiting segment of strictly higher priority suspends a running one of lower priority
+    priority: int = 0
 
 
 def segment_from_audio(content_encoder, wav16k: torch.Tensor, samples_at_target_rate: int, refer_mel: torch.Tensor, hop: int = 256,
@@ -224,18 +227,28 @@ class ContinuousConverter:
     sliced, and the seed is reused per chunk, as in ``Denoiser.sample_long``.  Chunk j + 1 holds its first V frames at the last V latent
     frames chunk j's ``take`` returned (a device-side slice on the loop's stream: the host never waits between chunks), and becomes ready
     when chunk j has finished: the scheduling is ``schedule.plan_chains``, request ids ``(segment, chunk)`` in ``last_plan``.  The result is
-    chunk 0 whole, then every later chunk from frame V on.  Short segments ride along unchanged."""
+    chunk 0 whole, then every later chunk from frame V on.  Short segments ride along unchanged.
+
+    ``preempt=True``: the loop follows ``schedule.plan_slots_preemptive`` on ``Segment.priority`` -- when every slot is busy
+    and a segment of strictly higher priority has arrived, the running segment of lowest priority is suspended (``SlotLoop.suspend``: its
+    solver state is copied out, its slot freed) and resumed when a slot is free again (``SlotLoop.resume``), bit-exact where it returns to
+    the slot index it left.  ``last_plan`` then holds that planner's 4-tuples ``(loop_step, take, suspend, admit)``.  ``convert(segments,
+    arrivals=)`` replays a recorded arrival pattern: ``arrivals[i]`` = the loop step from which segment i may start (non-decreasing), as
+    ``plan_slots`` takes them; an online submit / poll front is not part of this class.  Not together with ``overlap_frames``."""
 
     def __init__(self, pre_model: PreModel, denoiser: Denoiser, decode_fn: Optional[Callable] = None, slots: int = 32, max_frames: int = 938,
                  max_prompt: int = 469, solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, eta: float = 0.0,
                  guidance_scale: float = 1.0, unconditional_prompt: Optional[torch.Tensor] = None, correcting_x0_fn=None,
                  thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995, use_graph: bool = True,
-                 item_corrections: bool = False, overlap_frames: Optional[int] = None, **options):
+                 item_corrections: bool = False, overlap_frames: Optional[int] = None, preempt: bool = False, **options):
         """``item_corrections``: ``Segment.correction`` is honoured -- the loop is opened with the per-item x0 correction table and every
         segment is admitted with its own entry (None = uncorrected); not together with the loop-wide ``correcting_x0_fn=``."""
         self.pre, self.den, self.decode = pre_model, denoiser, decode_fn
         self.item_corrections = bool(item_corrections)
         self.overlap = None if overlap_frames is None else int(overlap_frames)
+        self.preempt = bool(preempt)
+        if self.preempt and overlap_frames is not None:
+            raise ValueError("preempt=True does not go with overlap_frames (chained chunks are not suspended): use one or the other")
         if self.overlap is not None and not 0 <= self.overlap < int(max_frames):
             raise ValueError(f"overlap_frames must be in [0, max_frames = {int(max_frames)}), got {overlap_frames}")
         self.slots, self.max_frames, self.max_prompt, self.seed, self.use_graph = int(slots), int(max_frames), int(max_prompt), seed, use_graph
@@ -256,9 +269,13 @@ class ContinuousConverter:
                              "item_corrections=True): it would rescale the held frames")
         self.last_plan = None          # (events of the last convert: tests, utilisation figures)
 
-    def convert(self, segments: Sequence[Segment]) -> List[torch.Tensor]:
-        """returns one tensor per segment, in input order: audio (samples,) with a ``decode_fn``, else the latent (100, T_i)"""
+    def convert(self, segments: Sequence[Segment], arrivals: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+        """returns one tensor per segment, in input order: audio (samples,) with a ``decode_fn``, else the latent (100, T_i).  ``arrivals``:
+        None (all queued at once) or one non-decreasing loop step per segment from which it may start -- the replay of a recorded arrival
+        pattern; not with chained chunks (``overlap_frames`` and a segment longer than ``max_frames``)."""
         dev = next(self.pre.parameters()).device
+        if arrivals is not None and self.overlap is not None and any(int(s.content.shape[-1]) > self.max_frames for s in segments):
+            raise ValueError("arrivals= does not go with chained chunks (a segment longer than max_frames under overlap_frames)")
         specs = [s.schedule if getattr(s, "schedule", None) is not None else self.own for s in segments]
         for i, s in enumerate(segments):
             if (int(s.content.shape[-1]) > self.max_frames and self.overlap is None) or int(s.refer.shape[-1]) > self.max_prompt:
@@ -284,8 +301,19 @@ class ContinuousConverter:
             for sp, cor in zip(specs, cors):      # every refusal before anything runs
                 loop.check_request(sp, self.scale, cor)
             # requests are (segment, chunk); with one chunk per segment these are plan_slots' events, and last_plan shows them in its format
-            events = plan_chains([[tables[i].steps] * len(chunks[i]) for i in range(len(segments))], self.slots)
-            self.last_plan = events if chained else [(r, [(b, i) for b, (i, _) in take], [(b, i) for b, (i, _) in admit]) for r, take, admit in events]
+            if self.preempt:
+                self.last_plan = plan_slots_preemptive([t.steps for t in tables], self.slots, arrivals,
+                                                       [int(getattr(s, "priority", 0)) for s in segments])
+                plan = [(r, [(b, (i, 0)) for b, i in take], suspend, [(b, (i, 0), d) for b, i, d in admit]) for r, take, suspend, admit in self.last_plan]
+            else:
+                if arrivals is not None:
+                    events = [(r, [(b, (i, 0)) for b, i in take], [(b, (i, 0)) for b, i in admit])
+                              for r, take, admit in plan_slots([t.steps for t in tables], self.slots, arrivals)]
+                else:
+                    events = plan_chains([[tables[i].steps] * len(chunks[i]) for i in range(len(segments))], self.slots)
+                self.last_plan = events if chained else [(r, [(b, i) for b, (i, _) in take], [(b, i) for b, (i, _) in admit]) for r, take, admit in events]
+                plan = [(r, take, [], [(b, q, 0) for b, q in admit]) for r, take, admit in events]
+            held: Dict[int, object] = {}        # suspended segment -> its Suspended, until it is resumed
             result: List[Optional[torch.Tensor]] = [None] * len(segments)
             nc = self.den.cfg.latent_channels
             front: Dict[int, tuple] = {}        # long segment -> (content (256, L), prompt (lp, 256), x_T (100, L), latent (100, L)) until its last chunk
@@ -308,7 +336,7 @@ class ContinuousConverter:
                 # x_T per SEGMENT at its own length, seeded by its position in the input (as GroupedConverter): its result does not depend on its slot
                 return torch.randn((nc, int(segments[i].content.shape[-1])), generator=torch.Generator().manual_seed(self.seed + i)).to(dev)
 
-            for r, take, admit in events:
+            for r, take, suspend, placed in plan:
                 if r > loop.step:
                     loop.run(r - loop.step)
                 if take:
@@ -325,6 +353,13 @@ class ContinuousConverter:
                                 continue
                             x = front.pop(i)[3]
                         result[i] = x if self.decode is None else self.decode(x[None])[0]
+                if suspend:
+                    for (_, i, _), q in zip(suspend, loop.suspend([b for b, _, _ in suspend])):
+                        held[i] = q
+                back = [(b, i) for b, (i, _), d in placed if d > 0]
+                if back:
+                    loop.resume([b for b, _ in back], [held.pop(i) for _, i in back])
+                admit = [(b, q) for b, q, d in placed if d == 0]
                 if admit:
                     short = [i for _, (i, _) in admit if len(chunks[i]) == 1]
                     if short:      # the short segments of the group in one front-end batch
