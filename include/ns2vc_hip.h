@@ -837,6 +837,25 @@ int ns2vc_k_sampler_suspend(const float* xe, const float* xbar, const float* d1,
 int ns2vc_k_sampler_resume(const float* state_in, int T, int ld, int n, const int32_t* slots_host, int n_items, const int32_t* records_host, int32_t* rec_dev,
                            float* xe, void* xe_op, int precision, float* xbar, float* d1, float* mprev, float* mprev2, int guided, void* stream);
 
+/* ---- The flat solver step (backward-compatible addition to ABI v7) -------------------------------------------------------------
+ * One row of a solver table on a state that has no layout: n >= 1 fp32 elements in each of the planes xe, xbar, d1, mprev and (history 2) mprev2,
+ * updated in place by the recurrence of ns2vc_amd/schedule.py.  This is the update the top-level `sampler` package (the reference's DPM_Solver /
+ * UniPC classes) launches after every call of a model it cannot hand to the captured loop: ONE launch, enqueued on `stream`, no host wait.
+ * coef_dev = DEVICE [n_rows][NS2VC_NCOEF] (schedule.build_table); the CALLER states n_rows, and row must lie in [0, n_rows) -- the library keeps no
+ * record of a table it did not load.  model_out = what the model returned at xe, `kind` says what it is:
+ *   0 x_start: m = the float32 round trip eps = (xe - alpha x0) / sigma, m = (xe - sigma eps) / alpha -- every plane then has the bits
+ *     ns2vc_k_solver_update leaves in fp32;  1 noise: m = (xe - sigma eps) / alpha;  2 v: eps = alpha v + sigma xe;  3 score: eps = -sigma score;
+ *   4 data: m = model_out as given (an x0 that was corrected on the way).
+ * mprev2 = NULL: the order <= 2 update; non-NULL: the history-2 update of order-3 tables.  m_out non-NULL = FORM: m is written there and no
+ * state plane is written (FORM, a correction of m by the caller, then kind 4 on it is the corrected step; without a correction the three give
+ * the planes of the plain step bit for bit).  Pointers need 4-byte alignment only, each plane on a phase of its own: the kernel runs float4
+ * where all planes share a 16-byte phase (scalar head and tail around it) and scalar otherwise, and an element's bits do not depend on which.
+ * The grid has at most NS2VC_FLAT_MAX_BLOCKS blocks of 256 threads, so one trip covers NS2VC_FLAT_MAX_BLOCKS * 1024 elements.
+ * Refused: a null state pointer, coef_dev or model_out, n == 0, an unknown kind, a row outside the table, a pointer off 4-byte alignment. */
+#define NS2VC_FLAT_MAX_BLOCKS 1024
+int ns2vc_k_solver_step_flat(const float* coef_dev, int n_rows, int row, int kind, const float* model_out, float* xe, float* xbar, float* d1,
+                             float* mprev, float* mprev2 /* NULL: history 1 */, float* m_out /* non-NULL: FORM */, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -257,7 +257,11 @@ PROTOTYPES = {
     "ns2vc_sampler_resume": (_I, [_P, _I, _P, _P, _P, _P]),
     "ns2vc_k_sampler_suspend": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P]),
     "ns2vc_k_sampler_resume": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
+    # the flat solver step (sampler/ package): coef, n_rows, row, kind, model_out, xe, xbar, d1, mprev, mprev2 | None, m_out | None (FORM), n, stream
+    "ns2vc_k_solver_step_flat": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
 }
+FLAT_KINDS = {"x_start": 0, "noise": 1, "v": 2, "score": 3, "data": 4}      # `kind` of ns2vc_k_solver_step_flat
+FLAT_TRIP = 1024 * 1024      # elements one trip of its grid covers (NS2VC_FLAT_MAX_BLOCKS blocks of 256 threads, a quad each)
 
 _lib: Optional[C.CDLL] = None
 

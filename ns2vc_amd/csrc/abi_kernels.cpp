@@ -394,6 +394,19 @@ int ns2vc_k_solver_update(const float* coef_dev, const int32_t* step_dev, const 
   return launched(launch_solver_step(hook_step(coef_dev, step_dev, x0, xe, xe_op, precision, xbar, d1, mprev, mprev2, n, ld), (hipStream_t)stream),
                   "solver_update launch");
 }
+int ns2vc_k_solver_step_flat(const float* coef_dev, int n_rows, int row, int kind, const float* model_out, float* xe, float* xbar, float* d1,
+                             float* mprev, float* mprev2, float* m_out, size_t n, void* stream) {
+  if (!coef_dev || !model_out || !xe || !xbar || !d1 || !mprev) return fail("null argument");
+  if (n == 0) return fail("flat solver step: n must be at least 1");
+  if (kind < 0 || kind > 4) return fail("flat solver step: kind %d must be 0 (x_start), 1 (noise), 2 (v), 3 (score) or 4 (data)", kind);
+  if (n_rows <= 0 || row < 0 || row >= n_rows) return fail("flat solver step: row %d outside the table of %d rows", row, n_rows);
+  const uintptr_t bits = (uintptr_t)coef_dev | (uintptr_t)model_out | (uintptr_t)xe | (uintptr_t)xbar | (uintptr_t)d1 | (uintptr_t)mprev |
+                         (uintptr_t)mprev2 | (uintptr_t)m_out;
+  if (bits & 3) return fail("flat solver step: every pointer must be 4-byte aligned");
+  return launched(launch_solver_step_flat(coef_dev + (size_t)row * NS2VC_NCOEF, kind, model_out, xe, xbar, d1, mprev, mprev2, m_out, n,
+                                          (hipStream_t)stream),
+                  "solver_step_flat launch");
+}
 int ns2vc_k_solver_update_guided(const float* coef_dev, const int32_t* step_dev, const float* x0, float* xe, void* xe_op, int precision, float* xbar,
                                  float* d1, float* mprev, float* mprev2, size_t n_half, int ld, const float* scale_dev, int T, const uint64_t* seeds_dev,
                                  const int32_t* lens_dev, int nc, void* stream) {

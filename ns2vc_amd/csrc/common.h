@@ -258,6 +258,18 @@ __device__ __forceinline__ void solver_elem(const SolverCoef& k, float s, float 
   od1 = H2 ? k.d1c * (vmp - m) + d2c * (vmp2 - m) : k.d1c * (vmp - m);
   om = m;
 }
+// The element behind the formation of m, for the flat step (misc.hip solver_step_flat_kernel), which enters with an m it formed from a noise / v /
+// score output or was handed: the three lines of solver_elem, character for character.  (solver_elem calling this function instead of stating them
+// gave the dynamic-thresholding kernels other code (tools/kernel_code_diff.py), and every earlier kernel keeps its code; with
+// m = solver_m(vx0, vxe) the two give the same bits, which tests/test_sampler_pkg_gpu.py holds the flat kernel to.)
+template <bool H2>
+__device__ __forceinline__ void solver_elem_m(const SolverCoef& k, float d2c, float m, float vxb, float vd1, float vmp, float vmp2, float& oxb, float& od1,
+                                              float& om) {
+  const float x = vxb - k.g0 * vd1 - k.g1 * (m - vmp);
+  oxb = k.A * x - k.Bc * m;
+  od1 = H2 ? k.d1c * (vmp - m) + d2c * (vmp2 - m) : k.d1c * (vmp - m);
+  om = m;
+}
 template <bool H2>
 __device__ __forceinline__ float solver_xe(const SolverCoef& k, float pe, float oxb, float od1, float om, float vmp2) {
   return H2 ? oxb - k.pc * od1 - pe * (vmp2 - om) : oxb - k.pc * od1;
@@ -495,6 +507,13 @@ hipError_t launch_sampler_suspend(const float* xe, const float* xbar, const floa
                                   const int* slots, int nslots, float* dst, SolverItem* rec, hipStream_t s);
 hipError_t launch_sampler_resume(const float* src, int T, int ld, int n, const int* slots, int nslots, const SolverItem* rec_in, SolverItem* rec, float* xe,
                                  void* xe_op, int prec, float* xbar, float* d1, float* mprev, float* mprev2, int split, int half, hipStream_t s);
+// The flat solver step (ns2vc_k_solver_step_flat; the top-level sampler/ package's device path): row `crow` (NCOEF floats, DEVICE) on n elements of
+// five state planes of any 4-byte alignment.  kind 0 x_start | 1 noise | 2 v | 3 score | 4 data says what `out` holds; mprev2 NULL = history 1;
+// m_out non-NULL = FORM (m is written there, no state plane is touched).  FLAT_MAX_BLOCKS 256-thread blocks at most: one trip of the grid covers
+// FLAT_MAX_BLOCKS * 1024 elements, the rest comes in further trips of the grid-stride loop.
+constexpr unsigned FLAT_MAX_BLOCKS = 1024;
+hipError_t launch_solver_step_flat(const float* crow, int kind, const float* out, float* xe, float* xbar, float* d1, float* mprev, float* mprev2,
+                                   float* m_out, size_t n, hipStream_t s);
 // the normals a stochastic update adds at table row `step` (ns2vc_k_noise): out rows [B*T][ld] fp32, zeros where no noise goes
 hipError_t launch_noise(const unsigned long long* seeds, int B, int nc, int T, int ld, int step, const int* lens, float* out, hipStream_t s);
 hipError_t launch_fill_i32(int* p, int v, hipStream_t s);

@@ -1673,4 +1673,132 @@ hipError_t launch_sampler_resume(const float* src, int T, int ld, int n, const i
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// The flat solver step (ns2vc_k_solver_step_flat; the device path of the top-level sampler/ package): one table row on n elements of
+// the five fp32 state planes xe, xbar, d1, mprev, mprev2, with no layout at all -- no rows, no items, no operand copy -- so the planes may be torch
+// tensors of any shape, views and slices included.  It sits behind the suspend / resume kernels: every earlier kernel keeps its code.
+//   KIND (compile time): what `out`, the model's output at xe, is.  m, the predicted x0 the recurrence runs on, is
+//     0 x_start  solver_m(out, xe): the float32 round trip of the model wrapper, the bits of solver_update_kernel
+//     1 noise    (xe - sigma * out) / alpha
+//     2 v        eps = alpha * out + sigma * xe, then as noise          (sampler/dpm_solver.py:305-308)
+//     3 score    eps = -sigma * out, then as noise                      (sampler/dpm_solver.py:309-311)
+//     4 data     out itself (an m that was corrected on the way: FORM, torch, then this)
+//   H2: the history-2 form (mprev2 read and rotated), as in solver_quad.
+//   FORM: m goes to m_out and NO state plane is read but xe or written at all.
+// Behind m the element is common.h solver_elem_m + solver_xe, the functions solver_quad runs.  Alignment: the pointers need 4 bytes only.  The n
+// elements are cut into SLOTS of up to four: where all planes of the launch share one 16-byte phase, a head slot of 0..3 elements that brings them
+// to a 16-byte boundary, nq full quads loaded and stored as float4, and a tail slot; planes on different phases have no common quad, and every slot
+// (ceil(n / 4) of them) is loaded and stored element by element.  ONE loop body serves every slot -- loads (float4 or per element, absent lanes 0),
+// the four elements in a straight line, stores (float4 or per element) -- because two bodies did not give the same bits: a scalar loop beside the
+// float4 loop was one ulp off on x_e' in some elements (seen on the device; the compiler contracts multiply-adds per body, the comment above
+// solver_quad has the same finding), and an element's bits must not depend on the path that handled it.  The loop is grid-stride over size_t slot
+// indices.  Seven streams of 4 bytes per element and a dozen flops: bandwidth.
+// ---------------------------------------------------------------------------
+template <int KIND>
+__device__ __forceinline__ float flat_m(const SolverCoef& k, float out, float vxe) {
+  static_assert(KIND >= 0 && KIND <= 4, "0 x_start, 1 noise, 2 v, 3 score, 4 data");
+  if constexpr (KIND == 0) return solver_m(k, out, vxe);
+  if constexpr (KIND == 4) return out;
+  float eps = out;
+  if constexpr (KIND == 2) eps = k.alpha * out + k.sigma * vxe;
+  if constexpr (KIND == 3) eps = -k.sigma * out;
+  return (vxe - k.sigma * eps) / k.alpha;
+}
+template <int KIND, bool H2>
+__device__ __forceinline__ void flat_elem(const SolverRow& kr, float out, float vxe, float vxb, float vd1, float vmp, float vm2, float& oxe, float& oxb,
+                                          float& od1, float& om) {
+  solver_elem_m<H2>(kr.k, kr.d2c, flat_m<KIND>(kr.k, out, vxe), vxb, vd1, vmp, vm2, oxb, od1, om);
+  oxe = solver_xe<H2>(kr.k, kr.pe, oxb, od1, om, vm2);
+}
+// up to four elements from e0 on: one float4 (vec: the slot is full and 16-byte aligned) or cnt single loads, the absent lanes 0
+__device__ __forceinline__ float4 flat_load(const float* p, size_t e0, int cnt, bool vec) {
+  if (vec) return *reinterpret_cast<const float4*>(p + e0);
+  float4 v = make_float4(p[e0], 0.f, 0.f, 0.f);
+  if (cnt > 1) v.y = p[e0 + 1];
+  if (cnt > 2) v.z = p[e0 + 2];
+  if (cnt > 3) v.w = p[e0 + 3];
+  return v;
+}
+__device__ __forceinline__ void flat_store(float* p, size_t e0, int cnt, bool vec, const float4& v) {
+  if (vec) { out_f4(p + e0, v.x, v.y, v.z, v.w); return; }
+  p[e0] = v.x;
+  if (cnt > 1) p[e0 + 1] = v.y;
+  if (cnt > 2) p[e0 + 2] = v.z;
+  if (cnt > 3) p[e0 + 3] = v.w;
+}
+// Slot j of the launch: j < hs = the head slot ([0, head)), then nq quads from `head` on, then the tail slot.  vec: the quads are 16-byte aligned in
+// every plane.  (No __restrict__ on the planes: a model may hand back a view of the state it was given; a slot is loaded in full before it is stored.)
+template <int KIND, bool H2, bool FORM>
+__global__ __launch_bounds__(256) void solver_step_flat_kernel(const float* __restrict__ crow, const float* out, float* xe, float* xbar, float* d1,
+                                                               float* mprev, float* mprev2, float* m_out, size_t n, size_t head, size_t nq, int vec) {
+  const SolverRow kr = solver_row<H2>(crow, false);
+  const size_t hs = head ? 1 : 0, tail0 = head + 4 * nq, nslots = hs + nq + (tail0 < n ? 1 : 0);
+  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nslots; j += (size_t)gridDim.x * 256) {
+    size_t e0 = head + 4 * (j - hs);
+    int cnt = 4;
+    bool v4 = vec != 0;
+    if (j < hs) { e0 = 0; cnt = (int)head; v4 = false; }
+    else if (j >= hs + nq) { e0 = tail0; cnt = (int)(n - tail0); v4 = false; }
+    const float4 vo = flat_load(out, e0, cnt, v4);
+    float4 vxe = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (KIND != 4 || !FORM) vxe = flat_load(xe, e0, cnt, v4);
+    if constexpr (FORM) {
+      flat_store(m_out, e0, cnt, v4, make_float4(flat_m<KIND>(kr.k, vo.x, vxe.x), flat_m<KIND>(kr.k, vo.y, vxe.y), flat_m<KIND>(kr.k, vo.z, vxe.z),
+                                                 flat_m<KIND>(kr.k, vo.w, vxe.w)));
+    } else {
+      const float4 vxb = flat_load(xbar, e0, cnt, v4), vd1 = flat_load(d1, e0, cnt, v4), vmp = flat_load(mprev, e0, cnt, v4);
+      float4 vm2 = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (H2) vm2 = flat_load(mprev2, e0, cnt, v4);
+      float4 oxe, oxb, od1, om;
+      flat_elem<KIND, H2>(kr, vo.x, vxe.x, vxb.x, vd1.x, vmp.x, vm2.x, oxe.x, oxb.x, od1.x, om.x);
+      flat_elem<KIND, H2>(kr, vo.y, vxe.y, vxb.y, vd1.y, vmp.y, vm2.y, oxe.y, oxb.y, od1.y, om.y);
+      flat_elem<KIND, H2>(kr, vo.z, vxe.z, vxb.z, vd1.z, vmp.z, vm2.z, oxe.z, oxb.z, od1.z, om.z);
+      flat_elem<KIND, H2>(kr, vo.w, vxe.w, vxb.w, vd1.w, vmp.w, vm2.w, oxe.w, oxb.w, od1.w, om.w);
+      if constexpr (H2) flat_store(mprev2, e0, cnt, v4, vmp);
+      flat_store(xe, e0, cnt, v4, oxe);
+      flat_store(xbar, e0, cnt, v4, oxb);
+      flat_store(d1, e0, cnt, v4, od1);
+      flat_store(mprev, e0, cnt, v4, om);
+    }
+  }
+}
+template <int KIND>
+static void launch_flat_kind(dim3 grid, hipStream_t s, const float* crow, const float* out, float* xe, float* xbar, float* d1, float* mprev, float* mprev2,
+                             float* m_out, size_t n, size_t head, size_t nq, int vec) {
+  if (m_out)
+    hipLaunchKernelGGL((solver_step_flat_kernel<KIND, false, true>), grid, dim3(256), 0, s, crow, out, xe, xbar, d1, mprev, mprev2, m_out, n, head, nq, vec);
+  else if (mprev2)
+    hipLaunchKernelGGL((solver_step_flat_kernel<KIND, true, false>), grid, dim3(256), 0, s, crow, out, xe, xbar, d1, mprev, mprev2, m_out, n, head, nq, vec);
+  else
+    hipLaunchKernelGGL((solver_step_flat_kernel<KIND, false, false>), grid, dim3(256), 0, s, crow, out, xe, xbar, d1, mprev, mprev2, m_out, n, head, nq, vec);
+}
+hipError_t launch_solver_step_flat(const float* crow, int kind, const float* out, float* xe, float* xbar, float* d1, float* mprev, float* mprev2,
+                                   float* m_out, size_t n, hipStream_t s) {
+  if (!crow || !out || !xe || !xbar || !d1 || !mprev || n == 0 || kind < 0 || kind > 4) return hipErrorInvalidValue;
+  // the planes this launch touches: FORM reads out (and xe, unless m is out itself) and writes m_out alone
+  const uintptr_t form[3] = {(uintptr_t)out, (uintptr_t)m_out, kind == 4 ? (uintptr_t)out : (uintptr_t)xe};
+  const uintptr_t upd[6] = {(uintptr_t)out, (uintptr_t)xe, (uintptr_t)xbar, (uintptr_t)d1, (uintptr_t)mprev, mprev2 ? (uintptr_t)mprev2 : (uintptr_t)out};
+  const uintptr_t* const p = m_out ? form : upd;
+  const int np = m_out ? 3 : 6;
+  bool one_phase = true;
+  for (int i = 0; i < np; ++i) {
+    if (p[i] & 3) return hipErrorInvalidValue;
+    one_phase = one_phase && (p[i] & 15) == (p[0] & 15);
+  }
+  // one phase: a head slot up to the 16-byte boundary, float4 quads, a tail slot; otherwise quads from element 0 on, loaded element by element
+  const size_t head = one_phase ? std::min<size_t>(n, ((16 - (p[0] & 15)) & 15) / 4) : 0;
+  const size_t nq = (n - head) / 4;
+  const int vec = one_phase ? 1 : 0;
+  const size_t nslots = (head ? 1 : 0) + nq + (head + 4 * nq < n ? 1 : 0);
+  const dim3 grid((unsigned)std::min<size_t>(FLAT_MAX_BLOCKS, (nslots + 255) / 256));
+  switch (kind) {
+    case 0: launch_flat_kind<0>(grid, s, crow, out, xe, xbar, d1, mprev, mprev2, m_out, n, head, nq, vec); break;
+    case 1: launch_flat_kind<1>(grid, s, crow, out, xe, xbar, d1, mprev, mprev2, m_out, n, head, nq, vec); break;
+    case 2: launch_flat_kind<2>(grid, s, crow, out, xe, xbar, d1, mprev, mprev2, m_out, n, head, nq, vec); break;
+    case 3: launch_flat_kind<3>(grid, s, crow, out, xe, xbar, d1, mprev, mprev2, m_out, n, head, nq, vec); break;
+    default: launch_flat_kind<4>(grid, s, crow, out, xe, xbar, d1, mprev, mprev2, m_out, n, head, nq, vec); break;
+  }
+  return hipGetLastError();
+}
+
 }  // namespace ns2vc

@@ -93,6 +93,14 @@ class VPSchedule:
         self.N = int(self.log_alpha.shape[0])
         self.knots = np.linspace(0.0, 1.0, self.N + 1, dtype=np.float32)[1:].astype(np.float64)
 
+    @classmethod
+    def from_alphas_cumprod(cls, alphas_cumprod: np.ndarray) -> "VPSchedule":
+        """the schedule of ``NoiseScheduleVP(alphas_cumprod=)`` (dpm_solver.py:104-105): log alpha = log(alphas_cumprod) / 2 in float32"""
+        a32 = np.asarray(alphas_cumprod, dtype=np.float32).reshape(-1)
+        s = cls(np.zeros(a32.shape[0], dtype=np.float32))
+        s.log_alpha = (np.float32(0.5) * np.log(a32).astype(np.float32)).astype(np.float64)
+        return s
+
     def log_alpha_at(self, t: float) -> float:
         i = int(np.searchsorted(self.knots, t, side="left")) - 1
         i = min(max(i, 0), self.N - 2)
@@ -214,7 +222,7 @@ def build_table(solver: str, steps: int, betas: Optional[np.ndarray] = None, ord
         raise ValueError(f"variant must be 'bh1' or 'bh2' (UniPC only; vary_coeff is not served), got {variant!r} for {solver!r}")
     if solver_type not in ("dpmsolver", "taylor") or (solver != "dpmsolver++" and solver_type != "dpmsolver"):
         raise ValueError(f"solver_type must be 'dpmsolver' or 'taylor' (DPM-Solver++ only), got {solver_type!r} for {solver!r}")
-    sched = VPSchedule(linear_betas() if betas is None else betas)
+    sched = betas if isinstance(betas, VPSchedule) else VPSchedule(linear_betas() if betas is None else betas)      # (a ready schedule: sampler/)
     t_T = 1.0 if t_start is None else float(t_start)
     t_0 = 1.0 / sched.N if t_end is None else float(t_end)
     if not 0.0 < t_0 < t_T <= 1.0:
