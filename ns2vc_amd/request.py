@@ -100,6 +100,79 @@ def check_guidance(B: int, guidance_scale=1.0, unconditional_prompt=None, uncond
     return g
 
 
+# default number of trailing fp32 evaluations of a 16-bit sampling loop, per solver (``Denoiser(tail_fp32=None)``):
+# DPM-Solver++(2M) takes its LAST update at second order over the largest log-SNR step of the schedule (no lower_order_final
+# for steps >= 10, dpm_solver.py:1198-1201), which amplifies the rounding noise of the last two evaluations ~2.7x (50 steps:
+# fp16 1.7e-3 on the sampled latent, with the last two evaluations in fp32 ~2e-4); UniPC-bh2 ends at first order and keeps
+# the single-evaluation noise (8.6e-4 at 20 steps), so it stays pure 16-bit unless asked.  DDPM and DDIM end on x_start of their
+# last evaluation (weight ~1), so that evaluation's rounding is the latent's: at the bench shape fp16 DDPM-1000 / DDIM-100 are
+# 7.7e-4 from the fp32 engine with no tail (worst item 8.0e-4), 1.4e-4 / 1.3e-4 with one fp32 evaluation, 6.7e-5 / 7.5e-5 with two
+# (profiles/r08_stochastic.txt): one is the smallest tail that holds the 1e-3 bar with margin.
+DEFAULT_TAIL_FP32 = {"dpmsolver++": 2, "unipc": 0, "ddim": 1, "ddpm": 1}
+# ... and for order-3 tables, from tools/solver_bench.py at the bench shape, 20 steps, fp16 against the fp32 engine (profiles/r08_order3_solvers.txt).
+# UniPC-3 ends at first order like UniPC-2 and has its rounding: 7.6e-4 with no tail, but 1.4e-3 on the worst frame; one fp32 evaluation
+# gives 1.6e-4 (worst frame 3.6e-4), the smallest tail with margin, as for DDPM / DDIM.  DPM-Solver++(3M) takes its last updates at third
+# order over the largest log-SNR steps (no lower_order_final for steps >= 10, as the reference), and each extrapolates from three model
+# values, so the rounding of the last four evaluations reaches the latent: tail 0 / 1 / 2 / 3 / 4 give 7.6e-3 / 7.5e-3 / 4.5e-3 / 1.2e-3 /
+# 3.1e-4 (worst item 3.3e-4, worst frame 7.4e-4).  Four is the smallest tail inside the bar.
+DEFAULT_TAIL_FP32_ORDER3 = {"dpmsolver++": 4, "unipc": 1}
+
+
+def default_tail_fp32(solver: str, order: int) -> int:
+    """trailing fp32 evaluations of a 16-bit loop when the caller sets none"""
+    return (DEFAULT_TAIL_FP32_ORDER3 if order == 3 and solver in DEFAULT_TAIL_FP32_ORDER3 else DEFAULT_TAIL_FP32).get(solver, 0)
+
+
+def guided_tail_extra(scales) -> int:
+    """fp32 evaluations a guided 16-bit loop adds to its default tail.  A guided x0 is (1 - s) x0_u + s x0_c of two evaluations whose 16-bit
+    rounding errors are independent, so it carries g = sqrt((1 - s)^2 + s^2) times the error of one (2.9 at s = 2.5, 9.2 at s = 7; <= 1 for
+    s in [0, 1]), and the last evaluations set the error of the sampled latent (class docstring of ``Denoiser``).  Every fp32 evaluation at
+    the end of a loop lowers that error about threefold or more (1.12e-3 -> 3.5e-4 -> 8.2e-5 for UniPC at s = 2.5), so
+    ceil(log3 g) of them offset the gain of the largest scale."""
+    s = np.asarray(scales, dtype=np.float64).reshape(-1)
+    g = float(np.sqrt((1.0 - s) ** 2 + s ** 2).max()) if s.size else 1.0
+    return 0 if g <= 1.0 else int(np.ceil(np.log(g) / np.log(3.0) - 1e-9))
+
+
+# relative L2 of ONE evaluation of a 16-bit engine against the exact result at the bench shape (README "parity"; bf16: the upper end of the
+# 6.4e-3 .. 7.0e-3 that tests/test_engine_gpu.py measures), and the bar a sampled latent is held to
+EVALUATION_ERROR = {"fp16": 7.2e-4, "bf16": 7.0e-3}
+PARITY_BAR = 1e-3
+
+
+def corrected_tail_min(precision: str, scales=None) -> int:
+    """fewest trailing fp32 evaluations of a 16-bit loop that runs an x0 correction (``correcting_x0_fn``).  A corrected model value is
+    clamp(m, -s, s) / s with s an order statistic of the same evaluation's |m|, so the 16-bit rounding of an evaluation reaches it twice:
+    d(m / s) = dm / s - m ds / s^2, the element's own error and the threshold's, which moves every element of the item the same way and is not
+    averaged down over the item.  Each is bounded by one evaluation's relative error e1 (``EVALUATION_ERROR``), so a corrected last evaluation
+    carries up to g e1 with g = 2 (times sqrt((1 - s)^2 + s^2) of the largest guidance scale, as ``guided_tail_extra``), and every fp32
+    evaluation at the end of a loop lowers the latent's error about threefold (same docstring).  ceil(log3(g e1 / bar)) of them bring it under the
+    bar: 1 for fp16 (2 x 7.2e-4 = 1.44e-3), 3 for bf16 (1.4e-2).  It is a floor under the default tail (+ ``guided_tail_extra``), not an
+    addition: a default tail that already runs as many evaluations in fp32 needs no more."""
+    e1 = EVALUATION_ERROR.get(precision)
+    if e1 is None:
+        return 0
+    g = 2.0
+    if scales is not None:
+        s = np.asarray(scales, dtype=np.float64).reshape(-1)
+        g *= max(1.0, float(np.sqrt((1.0 - s) ** 2 + s ** 2).max())) if s.size else 1.0
+    return max(0, int(np.ceil(np.log(g * e1 / PARITY_BAR) / np.log(3.0) - 1e-9)))
+
+
+def slot_tail_needed(precision: str, solver: str, order: int, scale: float = 1.0, corrected: bool = False) -> int:
+    """trailing fp32 evaluations ``Denoiser.sample`` would give a request with this schedule at this precision (``default_tail_fp32`` +
+    ``guided_tail_extra``, floored by ``corrected_tail_min``); a slot loop serves a request only when this is 0"""
+    if precision == "fp32":
+        return 0
+    n = default_tail_fp32(solver, order)
+    guided = float(scale) != 1.0
+    if guided:
+        n += guided_tail_extra([scale])
+    if corrected:
+        n = max(n, corrected_tail_min(precision, [scale] if guided else None))
+    return n
+
+
 def _item_list(v, B: int, name: str, entry: str):
     if not isinstance(v, (list, tuple)) or len(v) != B:
         raise ValueError(f"{name} must be a list of one {entry} (dict or None) per item ({B}), got "

@@ -1,6 +1,7 @@
-"""A complete stand-in for ``ns2vc_amd.engine.Engine`` on the host: every method ``ns2vc_amd/pipeline.py`` calls, the attributes ``guidance``,
-``x0_correction``, ``x0_corrections``, ``hold``, ``table`` and ``tables`` kept as ``Engine`` keeps them, and one shared list of what would have
-reached the device.  ``install(monkeypatch, rec)`` puts it in place of ``pipeline.Engine`` so that tests run the real ``Denoiser.__init__``:
+"""A complete stand-in for ``ns2vc_amd.engine.Engine`` on the host: every method ``ns2vc_amd/pipeline.py`` and ``ns2vc_amd/slots.py`` call -- the
+slot loop's known frames (``set_known_items``, ``open_slots(known_frames=)``) and its ``state_shape`` / ``suspend`` / ``resume`` included, so one
+request can be held and suspended at once --, the attributes ``guidance``, ``x0_correction``, ``x0_corrections``, ``hold``, ``table`` and
+``tables`` kept as ``Engine`` keeps them, and one shared list of what would have reached the device.  ``install(monkeypatch, rec)`` puts it in place of ``pipeline.Engine`` so that tests run the real ``Denoiser.__init__``:
 
     rec = Recording()
     install(monkeypatch, rec)
@@ -95,6 +96,7 @@ class RecordingEngine:
         self.options = {}
         self._x = None                    # the state of a loop in parts
         self._slot_step = -1
+        self._planes, self._starts = 4, {}      # of a slot loop: the planes of one item's solver state; slot -> the loop step of its request's row 0
         self._note("__init__", precision=precision)
 
     def _note(self, method, **args):
@@ -300,12 +302,16 @@ class RecordingEngine:
         self._x, self._slot_step = None, -1
 
     # -- slot loop --------------------------------------------------------------------------------------------------------
-    def open_slots(self, history2=False, noise=False, stream=None, item_corrections=False):
+    def open_slots(self, history2=False, noise=False, stream=None, item_corrections=False, **kw):
+        assert set(kw) <= {"known_frames"}
         if self.hold is not None:      # (what ns2vc_sampler_open says while a hold is on)
             raise RuntimeError("known frames are held (ns2vc_sampler_set_known): a slot loop does not run with them")
         if item_corrections and self.x0_correction is not None:
             raise ValueError("item_corrections and the loop-wide x0 correction (set_x0_correction) exclude each other")
-        self._note("open_slots", history2=bool(history2), noise=bool(noise), item_corrections=bool(item_corrections))
+        if kw.get("known_frames") and (item_corrections or self.x0_correction is not None):
+            raise ValueError("known_frames and an x0 correction exclude each other")
+        self._note("open_slots", history2=bool(history2), noise=bool(noise), item_corrections=bool(item_corrections), **kw)      # (the keyword only when passed)
+        self._planes, self._starts = 5 if history2 else 4, {}
         n = self._items()
         self.x0_corrections = (np.zeros(n, np.int32), np.full(n, 0.995, np.float32), np.ones(n, np.float32)) if item_corrections else None
         self.table = self.tables = None
@@ -320,6 +326,24 @@ class RecordingEngine:
 
     def admit(self, slots, x_T, records, stream=None):
         self._note("admit", slots=list(slots), x=x_T, records=np.asarray(records, dtype=np.int32))
+        for b, r in zip(slots, np.asarray(records)):
+            self._starts[b] = int(r[2])
+
+    def set_known_items(self, slots, known, mask, stream=None):
+        self._note("set_known_items", slots=list(slots), known=known, mask=mask)
+
+    def state_shape(self):
+        return (self._planes, self.shape[1], 128)
+
+    def suspend(self, slots, state, stream=None):
+        self._note("suspend", slots=list(slots), state_shape=list(state.shape))
+        state.fill_(1.5)
+        return [self._slot_step - self._starts[b] for b in slots]
+
+    def resume(self, slots, state, records, stream=None):
+        self._note("resume", slots=list(slots), state=state, records=np.asarray(records, dtype=np.int32))
+        for b, r in zip(slots, np.asarray(records)):
+            self._starts[b] = self._slot_step - int(r[2])
 
     def take(self, slots, out, stream=None):
         self._note("take", slots=list(slots))

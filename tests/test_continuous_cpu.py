@@ -271,6 +271,14 @@ def _loop(monkeypatch, precision="fp16", order3=False, stochastic=False, corr=No
     return lp
 
 
+def _busy(lp, spec, start=0, length=66, prompt_length=5):
+    """what a slot of ``lp`` holds while a request of ``spec`` admitted at loop step ``start`` runs in it (no tensors)"""
+    from ns2vc_amd.slots import SlotRequest, _Busy
+    key, table, flags = lp.check_request(spec)
+    return _Busy(start, SlotRequest(schedule=dict(spec), key=key, table=table, flags=flags, length=length, prompt_length=prompt_length, seed=0,
+                                    guidance_scale=1.0, correction=None, known=None, known_mask=None, content=None, prompt=None))
+
+
 def test_tail_refusal_names_fp32(monkeypatch):
     from ns2vc_amd.pipeline import slot_tail_needed
     assert slot_tail_needed("fp16", "unipc", 2) == 0 and slot_tail_needed("fp32", "dpmsolver++", 3, 7.0, True) == 0
@@ -329,7 +337,7 @@ def test_admit_argument_checks_reach_no_engine_call(monkeypatch):
         args.update(kw)
         with pytest.raises(ValueError, match=match):
             lp.admit(**args)
-    lp.items[1] = dict(key=S.schedule_key(U2_6), start=0, steps=6, length=66)
+    lp.items[1] = _busy(lp, U2_6)
     with pytest.raises(ValueError, match=r"slot\(s\) \[1\] are busy"):
         lp.admit(1, c, p, x, schedule=U2_6)
     with pytest.raises(ValueError, match="no finished request"):
@@ -357,7 +365,7 @@ def test_continuous_converter_refuses_before_anything_runs(monkeypatch):
 
 def test_a_failed_admission_gives_its_tables_back(monkeypatch):
     """whichever engine call of an admission fails -- the rows, the lengths, the condition, the admit itself --, the pool's user counts go back
-    and the slot stays idle"""
+    and the slot stays idle with the per-slot vectors it had"""
     class _Failing:
         def __init__(self, bad):
             self.bad, self.calls = bad, []
@@ -373,9 +381,12 @@ def test_a_failed_admission_gives_its_tables_back(monkeypatch):
     for bad in ("write_sampler_rows", "set_lengths", "set_prompt_lengths", "set_condition_items", "admit"):
         lp = _loop(monkeypatch, "fp32")
         lp.den.engine = _Failing(bad)
+        before = [v.copy() for v in (lp.lengths, lp.plens, lp.seeds, lp.scales)]
         with pytest.raises(RuntimeError, match=bad):
-            lp.admit(0, c, p, x, schedule=U2_6)
+            lp.admit(0, c, p, x, schedule=U2_6, length=50, prompt_length=3, seed=9)      # (values the vectors do not hold yet)
         assert lp.den.engine.calls[-1] == bad and lp.pool.rows_in_use() == 0 and lp.idle() == [0, 1, 2], bad
+        for was, now in zip(before, (lp.lengths, lp.plens, lp.seeds, lp.scales)):
+            assert np.array_equal(was, now) and was.dtype == now.dtype, bad
     lp = _loop(monkeypatch, "fp32")
     lp.den.engine = _Failing(None)
     lp.admit(0, c, p, x, schedule=U2_6)

@@ -1,6 +1,6 @@
 """Known frames in the slot loop, host side: held items in ``schedule.run_slots_numpy`` against every item run alone and against the
-closed form, the properties of ``schedule.plan_chains``, the refusals of ``SlotLoop`` / ``Denoiser.open_slots`` in front of any engine call (on a
-subclass of the recording engine), the unchanged default call sequence, the exports, the register audit of the two new kernels, and the stitching
+closed form, the properties of ``schedule.plan_chains``, the refusals of ``SlotLoop`` / ``Denoiser.open_slots`` in front of any engine call (on
+the recording engine), the unchanged default call sequence, the exports, the register audit of the two new kernels, and the stitching
 of ``ContinuousConverter(overlap_frames=)`` on a stub loop."""
 import os
 import re
@@ -185,31 +185,7 @@ def test_plan_chains_serves_successors_first_and_refuses_bad_input():
 
 
 # ---- the Python surface on the recording engine ------------------------------------------------------------------------
-class KnownRecordingEngine(R.RecordingEngine):
-    """the recording engine with the two methods of DESIGN 4.17"""
-    slot_known = False
-
-    def open_slots(self, history2=False, noise=False, stream=None, item_corrections=False, **kw):
-        assert set(kw) <= {"known_frames"}
-        if kw.get("known_frames") and (item_corrections or self.x0_correction is not None):
-            raise ValueError("known_frames and an x0 correction exclude each other")
-        super().open_slots(history2, noise, stream, item_corrections)
-        if kw:      # (the keyword is recorded only when it was passed)
-            self.rec.calls[-1][2].update({k: R.digest(v) for k, v in kw.items()})
-        self.slot_known = bool(kw.get("known_frames"))
-
-    def set_known_items(self, slots, known, mask, stream=None):
-        self._note("set_known_items", slots=list(slots), known=known, mask=mask)
-
-
-class KnownRecording(R.Recording):
-    def engine(self, cfg=None, precision="fp16"):
-        e = KnownRecordingEngine(self, cfg, precision, "head" if not self.engines else "tail")
-        self.engines.append(e)
-        return e
-
-
-def _denoiser(monkeypatch, precision="fp32", rec_cls=KnownRecording):
+def _denoiser(monkeypatch, precision="fp32", rec_cls=R.Recording):
     from ns2vc_amd.pipeline import Denoiser
     rec = R.install(monkeypatch, rec_cls())
     d = Denoiser({}, precision=precision, ln_guard=None, precision_check=None, attn_fallback_limit=None)
@@ -217,7 +193,7 @@ def _denoiser(monkeypatch, precision="fp32", rec_cls=KnownRecording):
     return d, rec
 
 
-def _loop(monkeypatch, known_frames=True, rec_cls=KnownRecording, **kw):
+def _loop(monkeypatch, known_frames=True, rec_cls=R.Recording, **kw):
     den, rec = _denoiser(monkeypatch, rec_cls=rec_cls)
     extra = dict(known_frames=True) if known_frames else {}
     lp = den.open_slots(3, 66, 5, **extra, **kw)
@@ -297,7 +273,7 @@ def test_the_default_call_sequence_is_unchanged(monkeypatch):
     g = torch.Generator().manual_seed(4)
     c, p, x = torch.randn((256, 66), generator=g), torch.randn((5, 256), generator=g), torch.randn((100, 66), generator=g)
     seen = []
-    for rec_cls in (KnownRecording, R.Recording):
+    for rec_cls in (R.Recording, R.Recording):
         lp = _loop(monkeypatch, known_frames=False, rec_cls=rec_cls)
         lp.admit(1, c, p, x, schedule=U2_6)
         lp.run()

@@ -203,40 +203,7 @@ def test_preemptive_scheduler_worked_example():
 # ---- 3. SlotLoop.suspend / resume on the recording engine -----------------------------------------------------------------
 def _loop(monkeypatch, precision="fp32", **kw):
     import recording_engine
-
-    class Engine(recording_engine.RecordingEngine):
-        planes = 4
-
-        def open_slots(self, history2=False, noise=False, stream=None, item_corrections=False):
-            super().open_slots(history2, noise, stream, item_corrections)
-            self.planes = 5 if history2 else 4
-
-        def state_shape(self):
-            return (self.planes, self.shape[1], 128)
-
-        def suspend(self, slots, state, stream=None):
-            self._note("suspend", slots=list(slots), state_shape=list(state.shape))
-            state.fill_(1.5)
-            return [self._slot_step - self.starts[b] for b in slots]
-
-        def admit(self, slots, x_T, records, stream=None):
-            super().admit(slots, x_T, records, stream)
-            for b, r in zip(slots, np.asarray(records)):
-                self.starts[b] = int(r[2])
-
-        def resume(self, slots, state, records, stream=None):
-            self._note("resume", slots=list(slots), state=state, records=np.asarray(records, dtype=np.int32))
-            for b, r in zip(slots, np.asarray(records)):
-                self.starts[b] = self._slot_step - int(r[2])
-
     rec = recording_engine.Recording()
-
-    def make(cfg=None, precision="fp16"):
-        e = Engine(rec, cfg, precision, "head" if not rec.engines else "tail")
-        e.starts = {}
-        rec.engines.append(e)
-        return e
-    rec.engine = make
     recording_engine.install(monkeypatch, rec)
     from ns2vc_amd.pipeline import Denoiser
     den = Denoiser({}, precision=precision, **dict(dict(ln_guard=None, precision_check=None, attn_fallback_limit=None), **kw.pop("den", {})))
@@ -278,7 +245,7 @@ def test_suspend_and_resume_routing(monkeypatch):
     assert r["records"] == recording_engine.digest(np.array([[row0, 6, 2, S.ITEM_NOISE]], np.int32))
     assert lp.rec.of("set_lengths")[0]["lengths"][2] == 60 and lp.rec.of("set_prompt_lengths")[0]["prompt_lengths"][2] == 4
     assert lp.rec.of("set_seeds")[0]["seeds"][2] == 9
-    assert lp.items[2]["start"] == lp.step - 2 == 3 and lp.pool.rows_in_use() == 6
+    assert lp.items[2].start == lp.step - 2 == 3 and lp.pool.rows_in_use() == 6
     assert lp.finished() == [] and lp.run() == [2] and lp.step == 9   # 4 rows to go
     lp.take([2])
     assert lp.idle() == [0, 1, 2] and lp.pool.rows_in_use() == 0
