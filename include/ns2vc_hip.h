@@ -131,6 +131,9 @@ int ns2vc_unet_num_missing_weights(ns2vc_unet* h, char* first_missing, int bufle
  *                    (ns2vc_geglu_args.T, lens) with ln_stats = NULL -- the kernel takes the LayerNorm sums from the operand rows it holds --
  *                    instead of the norm3 launch and the plain GEGLU GEMM with its mask_rows sweep; attn2.to_out and ff.out+proj_out stay as
  *                    they are; independent of the four options above; dense plans and the fp32 engine ignore it
+ *   "masked_attn_resident" 1|0 (default 0) the attention launches that "masked_attn" has given a length table run on the K/V-resident kernel's masked
+ *                    form where "attn_resident" would take them without the table (fp16 / bf16, head dim 16 / 32, the PADDED key rows <= 1024 / 640,
+ *                    B * heads >= the device's CUs); bit-identical results, same launches.  Without "masked_attn" and "attn_resident" it does nothing
  * The environment variables NS2VC_LN_LINEAR / NS2VC_FOLD_FF / NS2VC_FUSE_FFN set the defaults at ns2vc_unet_create.
  *   "temb_join_skip" n  (tests, not a plan option) record the fork_temb join at the (n+1)-th reader of the time scale /
  *                    shift rows instead of the first; the plan build then refuses the fork (ns2vc_unet_op_info which = 2) */
@@ -618,6 +621,9 @@ int ns2vc_debug_set_attn_optimistic(int on); /* tests: 0 = every attention workg
 int ns2vc_debug_set_attn_resident(int mode); /* tests / tuning: the K/V-resident attention kernel (dense fp16 / bf16, hd 16 / 32, <= 1024 / 640 keys): -1 = the rule (B * H >= the device's CUs; default), 0 = never, 1 = whenever the launch fits */
 unsigned long long ns2vc_debug_attn_resident_launches(void); /* tests: attention launches issued (or captured into a graph) on the resident kernel so far in this process */
 int ns2vc_debug_attnres_table(int* rows); /* rows of the resident attention kernel's table (not a family of ns2vc_debug_kernel_table); no HIP call */
+int ns2vc_debug_set_attn_resident_lens(int mode); /* tests / tuning: the resident kernel's masked form for launches with q_lens / k_lens (fp16 / bf16, hd 16 / 32, padded Lk <= 1024 / 640): -1 = the rule (B * H >= the device's CUs; default), 0 = never, 1 = whenever the launch fits */
+unsigned long long ns2vc_debug_attn_resident_lens_launches(void); /* tests: attention launches issued (or captured into a graph) on the resident kernel's masked form so far in this process */
+int ns2vc_debug_attnres_lens_table(int* rows); /* rows of that form's table (not a family of ns2vc_debug_kernel_table); no HIP call */
 int ns2vc_debug_set_rowchain_tokens(int nt); /* tests: force 64-token (1) / 128-token (2, dim 128 only) workgroups; 0 = heuristic */
 
 /* operand-typed conversions for tests: fp32 host [n] -> device operand buffer and back */

@@ -219,6 +219,9 @@ PROTOTYPES = {
     "ns2vc_debug_set_attn_resident": (_I, [_I]),
     "ns2vc_debug_attnres_table": (_I, [C.POINTER(_I)]),
     "ns2vc_debug_attn_resident_launches": (C.c_ulonglong, []),
+    "ns2vc_debug_set_attn_resident_lens": (_I, [_I]),
+    "ns2vc_debug_attnres_lens_table": (_I, [C.POINTER(_I)]),
+    "ns2vc_debug_attn_resident_lens_launches": (C.c_ulonglong, []),
     "ns2vc_k_groupnorm_stats": (_I, [_P, _I, _I, _P, _I, _I, _I, C.c_float, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
     "ns2vc_k_groupnorm_stats2": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _I, C.c_float, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
     "ns2vc_k_groupnorm": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P]),

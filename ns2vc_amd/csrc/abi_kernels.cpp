@@ -253,6 +253,17 @@ int ns2vc_debug_attnres_table(int* rows) {
   *rows = attnres_kernel_table().n;
   return 0;
 }
+int ns2vc_debug_set_attn_resident_lens(int mode) {
+  if (mode < -1 || mode > 1) return fail("resident attention under lengths: -1 (the rule), 0 (never) or 1 (whenever the launch fits)");
+  set_attn_resident_lens_mode(mode);
+  return 0;
+}
+unsigned long long ns2vc_debug_attn_resident_lens_launches(void) { return attn_resident_lens_launches(); }
+int ns2vc_debug_attnres_lens_table(int* rows) {
+  if (!rows) return fail("attnres lens table: rows not NULL");
+  *rows = attnres_lens_kernel_table().n;
+  return 0;
+}
 int ns2vc_debug_set_rowchain_tokens(int nt) {
   if (nt < 0 || nt > 2) return fail("rowchain tokens: 0 (heuristic), 1 (64-token blocks) or 2 (128-token blocks)");
   set_forced_rowchain_tokens(nt);
@@ -311,7 +322,7 @@ int ns2vc_k_attention(const ns2vc_attn_args* a, int head_dim, int precision, voi
         if (host[b] < 1 || host[b] > t.max) return fail("attention: %s[%d]=%d outside 1..%d", t.name, b, host[b], t.max);
     }
   }
-  return launched(launch_attention(*a, head_dim, precision, (hipStream_t)stream), "launch_attention");
+  return launched(launch_attention(*a, head_dim, precision, (hipStream_t)stream, true, true), "launch_attention");      // (the hooks decide)
 }
 int ns2vc_k_groupnorm(const float* a0, int lda0, int c0, const float* a1, int lda1, int c1, int B, int T, int G, float eps,
                       const float* gamma, const float* beta, const float* temb, int ldtemb, int temb_off, int silu, void* out_op,

@@ -21,7 +21,8 @@
 // (<= 1024 / 640 keys) and whose grid fills the chip (B*H >= the CUs) therefore run on attnres_kernel (attn_resident.hip: one
 // 16-wave workgroup per head, K/V staged once, no barrier in the loop), chosen by launch_attention through
 // attention_resident_eligible; the tile arithmetic both kernels execute is AttnTile (attn_common.h), and their results are
-// bit-identical.  This kernel keeps fp32, the fp8 PV form, masked launches, hd 48 / 64, longer key rows and small grids.
+// bit-identical.  This kernel keeps fp32, the fp8 PV form, masked launches, hd 48 / 64, longer key rows and small grids.  (Masked launches of the
+// same shapes move to attnres_lens_kernel where the plan has the option masked_attn_resident on as well: attention_resident_lens_eligible.)
 // q/k/v/out are operand-typed tensors (bf16, or fp32 in parity mode): no conversions while staging.
 #include "attn_common.h"
 #include "kernel_table.h"
@@ -260,7 +261,7 @@ bool attention_masks_rows(const AttnArgs& a, int head_dim, int prec) {
   return find(k_attn_table, kernel_key(prec, head_dim, 64, a.pv_fp8 != 0, true)) != nullptr;
 }
 
-hipError_t launch_attention(const AttnArgs& a, int head_dim, int prec, hipStream_t s, bool resident) {
+hipError_t launch_attention(const AttnArgs& a, int head_dim, int prec, hipStream_t s, bool resident, bool resident_lens) {
   const int al = prec == PREC_F32 ? 3 : 7;       // rows must start 16-B aligned
   if (!a.q || !a.k || !a.v || !a.out) return hipErrorInvalidValue;
   const bool masked = a.q_lens || a.k_lens, fp8 = a.pv_fp8 != 0;
@@ -268,6 +269,8 @@ hipError_t launch_attention(const AttnArgs& a, int head_dim, int prec, hipStream
   if (a.Lq <= 0 || a.Lk <= 0 || (a.ldq & al) || (a.ldk & al) || (a.ldv & al) || (a.ldo & al)) return hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(a.out) & 15) return hipErrorInvalidValue;      // (results leave in 16-byte pieces)
   if (attention_resident_eligible(a, head_dim, prec, resident)) return launch_attention_resident(a, head_dim, prec, s);      // a head's K/V staged once
+  if (masked && attention_resident_lens_eligible(a, head_dim, prec, resident && resident_lens))                               // ... under length tables
+    return launch_attention_resident_lens(a, head_dim, prec, s);
   const int keys = !fp8 && g_force_keys == 128 && find(k_attn_table, kernel_key(prec, head_dim, 128, false, masked)) ? 128 : 64;
   const KernelRow* row = find(k_attn_table, kernel_key(prec, head_dim, keys, fp8, masked));      // (no row: fp8 PV at fp32, or masked)
   if (!row) return hipErrorInvalidValue;

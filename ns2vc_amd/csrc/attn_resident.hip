@@ -9,6 +9,9 @@
 // tile with the exact pass: nothing is restaged, so no other wave takes part).
 // Capacity follows from the layout and the 160 KB of LDS: hd 16 -> 16 tiles (1024 keys, 152 KiB), hd 32 -> 10 tiles (640 keys, 160 KiB).
 // Everything else (fp32, the fp8 PV form, masked launches, hd 48 / 64, more keys, small grids) keeps attn_kernel: attention_resident_eligible.
+// Launches under per-item length tables (AttnArgs.q_lens / k_lens) have the same kernel body with the item's own counts, attnres_lens_kernel, behind a plan
+// option of its own (masked_attn_resident, default 0) and its own predicate, attention_resident_lens_eligible: the bits and the fallback count are the
+// masked attn_kernel's.  Measured: profiles/r22_masked_attn_resident.txt, DESIGN.md 4.7.
 #include "attn_common.h"
 #include "kernel_table.h"
 #include <atomic>
@@ -30,8 +33,31 @@ template <typename TM, int HD> struct AttnResGeom {
   static_assert(1024 % G::NPIECE == 0 && MAXT * 64 <= 1024, "one thread per staged key row");
 };
 
-template <typename TM, int HD>
-__global__ __launch_bounds__(1024) void attnres_kernel(const AttnArgs a) {
+// the count of item b from a length table of the masked form, clamped to [lo, hi]; hi without a table and in the dense form
+template <bool MASKED> __device__ __forceinline__ int attnres_count(const int32_t* lens, int b, int lo, int hi) {
+  if constexpr (MASKED) {
+    if (lens) return min(max(lens[b], lo), hi);
+  }
+  return hi;
+}
+// exact zeros into rows row0 .. Lq-1 of head h of item b of `out` (16-B pieces, the whole workgroup): the rows behind an item's live query tiles (the
+// partial tile's own rows past the item's end leave through store_out)
+template <typename TM, int HD> __device__ __forceinline__ void attnres_zero_rows(const AttnArgs& a, int b, int h, int row0, int tid) {
+  constexpr int SZ = sizeof(TM), PPR = HD * SZ / 16;
+  char* zp = reinterpret_cast<char*>(a.out) + ((size_t)b * a.Lq * a.ldo + h * HD) * SZ;
+  for (int i = tid; i < (a.Lq - row0) * PPR; i += 1024) {
+    const int row = row0 + i / PPR, pc = i % PPR;
+    *reinterpret_cast<u32x4_t*>(zp + (size_t)row * a.ldo * SZ + pc * 16) = u32x4_t{0, 0, 0, 0};
+  }
+}
+
+// The body of both kernels.  MASKED: per-item query and key counts (AttnArgs.q_lens / k_lens), the rule of attn_kernel<..., MASKED>: the item's counts
+// Lqb / Lkb (workgroup-uniform, clamped to the tensor) stand wherever the dense form uses Lq / Lk, the row stride between items stays Lq / Lk.  Key side:
+// only the ceil(Lkb / 64) tiles the item has are staged, nothing of k / v at or past row Lkb is read.  Query side: only the ceil(Lqb / 32) live query
+// tiles are walked; the rows of the partial tile past Lqb enter as zeros, decide no repeat and leave as exact zeros, and every other row of [Lqb, Lq) is
+// stored as zeros by the whole workgroup without a fetch or an MFMA (an item with no query at all does that and returns before it stages anything).
+template <typename TM, int HD, bool MASKED>
+__device__ __forceinline__ void attnres_body(const AttnArgs& a) {
   op_mode_init<TM>();
   using R = AttnResGeom<TM, HD>;
   using G = typename R::G;
@@ -53,13 +79,21 @@ __global__ __launch_bounds__(1024) void attnres_kernel(const AttnArgs a) {
     h = swz - b * a.H;
   }
   const int Lq = a.Lq, Lk = a.Lk;
-  const int ntile = (Lk + KEYS - 1) / KEYS;           // <= MAXT (attention_resident_eligible)
+  // this item's query / key counts (clamped to the tensor: a bad table cannot send a fetch or a store outside it)
+  const int Lqb = attnres_count<MASKED>(a.q_lens, b, 0, Lq), Lkb = attnres_count<MASKED>(a.k_lens, b, 1, Lk);
+  if constexpr (MASKED) {
+    if (Lqb == 0) {                                   // nothing but padded queries: their zeros, and no K / V tile, no MFMA
+      attnres_zero_rows<TM, HD>(a, b, h, 0, tid);
+      return;
+    }
+  }
+  const int ntile = (Lkb + KEYS - 1) / KEYS;          // <= MAXT (attention_resident_eligible / attention_resident_lens_eligible)
   const float LOG2E = 1.4426950408889634f;
   const float sc2 = a.scale * LOG2E;                  // scores are kept in log2 units
 
   // ---- stage the whole head.  Every byte a fragment read touches is written exactly once, by one thread, so one barrier closes the prologue:
   //   K rows: HD elements by the K pieces; the aux slab {1, bias(key) | -inf, 0 ...} and the pad by the key's thread
-  //   V^T:    rows 0 .. HD-1 by the V pieces (all 64 key slots: rows past Lk are fetched from the last valid row, as in attn_kernel), the ones row by the
+  //   V^T:    rows 0 .. HD-1 by the V pieces (all 64 key slots: rows past the item's Lkb are fetched from its last valid row, as in attn_kernel), the ones row by the
   //           key's thread, rows HD+1 .. HDX-1 zeroed here (the row pads are never read)
   {
     const TM* kbase = reinterpret_cast<const TM*>(a.k) + (size_t)b * Lk * a.ldk + h * HD;
@@ -73,19 +107,19 @@ __global__ __launch_bounds__(1024) void attnres_kernel(const AttnArgs a) {
       if (t < ntile) {
         {
           const int key = u / PPR, pc = u - key * PPR;
-          const int kk = min(t * KEYS + key, Lk - 1);
+          const int kk = min(t * KEYS + key, Lkb - 1);
           kraw[i] = *reinterpret_cast<const u32x4_t*>(kbase + (size_t)kk * a.ldk + pc * EPC);
         }
         {
           const int key = u % KEYS, pc = u / KEYS;
-          const int kk = min(t * KEYS + key, Lk - 1);
+          const int kk = min(t * KEYS + key, Lkb - 1);
           vraw[i] = *reinterpret_cast<const u32x4_t*>(vbase + (size_t)kk * a.ldv + pc * EPC);
         }
       }
     }
     float braw = 0.f;
     const bool keyrow = tid < ntile * KEYS;           // thread tid owns key row tid of the head (stage tid / 64, row tid % 64)
-    if (keyrow && bias) braw = bias[min(tid, Lk - 1)];
+    if (keyrow && bias) braw = bias[min(tid, Lkb - 1)];
     constexpr int NZC = (HDX - HD - 1) * (KEYS * SZ / 16);        // 16-B chunks of one stage's V^T zero rows
     for (int i = tid; i < ntile * NZC; i += 1024) {
       const int t = i / NZC, r = i - t * NZC;
@@ -93,7 +127,7 @@ __global__ __launch_bounds__(1024) void attnres_kernel(const AttnArgs a) {
     }
     if (keyrow) {
       const int st = tid / KEYS, key = tid - st * KEYS;
-      const float bl = tid < Lk ? (bias ? braw * LOG2E : 0.f) : -INFINITY;       // bias(key) in log2 units; -inf for the keys past Lk
+      const float bl = tid < Lkb ? (bias ? braw * LOG2E : 0.f) : -INFINITY;      // bias(key) in log2 units; -inf for the keys past the item's Lkb
       char* aux = smem + st * STAGE + key * KROWB + HD * SZ;
       *reinterpret_cast<u32x4_t*>(aux) = aux_chunk<TM>(1.0f, bl);
       *reinterpret_cast<u32x4_t*>(aux + 16) = u32x4_t{0, 0, 0, 0};
@@ -113,13 +147,13 @@ __global__ __launch_bounds__(1024) void attnres_kernel(const AttnArgs a) {
 
   const bool cform_all = G::CINIT && !a.bias;
   const bool exact_only = !NS2VC_ATTN_OPT || g_attnres_exact_only || a.exact_only;
-  const int nqt = (Lq + 31) >> 5;
+  const int nqt = (Lqb + 31) >> 5;                               // the live query tiles
   for (int qt = wave; qt < nqt; qt += ATTNRES_WAVES) {          // a wave with no live query tile goes straight to the final barrier
     const int q = qt * 32 + l31;
     u32x4_t qf[NS];
     // (fetching the first tile's rows in front of the staging loads, and a round's rows under the loop of the round before, was measured and lost
     //  0.45 % of the step: profiles/r21_attn_resident.txt)
-    G::load_q(qf, reinterpret_cast<const TM*>(a.q) + ((size_t)(b * Lq + min(q, Lq - 1)) * a.ldq + h * HD), sc2, hi, q >= Lq);
+    G::load_q(qf, reinterpret_cast<const TM*>(a.q) + ((size_t)(b * Lq + min(q, Lqb - 1)) * a.ldq + h * HD), sc2, hi, q >= Lqb);
     float m_ref;
     u32x4_t qaux;
     f32x16_t cinit, o[DT];
@@ -135,14 +169,14 @@ __global__ __launch_bounds__(1024) void attnres_kernel(const AttnArgs a) {
       for (int r = 0; r < 16; ++r) cinit[r] = 0.f;
       for (int t = 0; t < ntile; ++t) {
         const char* Ks = smem + t * STAGE;
-        G::template step<O>(Ks, Ks + KBYTES, t, cform_all && (t + 1 < ntile || Lk % KEYS == 0), qf, qaux, cinit, m_ref, o, l31, hi);
+        G::template step<O>(Ks, Ks + KBYTES, t, cform_all && (t + 1 < ntile || Lkb % KEYS == 0), qf, qaux, cinit, m_ref, o, l31, hi);
       }
     };
     if (!exact_only) {
       run(OptTag<true>{});
       // the denominator check of attn_kernel, decided per wave: a failing row sends this wave's 32 queries through the exact pass
       const float lq = o[G::LB][G::LR];
-      const int bad = (hi == 0 && q < Lq && !(lq > 0.f && lq < 16384.f)) ? 1 : 0;
+      const int bad = (hi == 0 && q < Lqb && !(lq > 0.f && lq < 16384.f)) ? 1 : 0;
       if (__any(bad)) {
         if (lane == 0) *reinterpret_cast<uint32_t*>(smem + (qt >> 4) * KROWB + HD * SZ + 32 + ((qt >> 2) & 3) * 4) = 1u;      // block qt / 4: row blk / 4, word blk % 4
         run(OptTag<false>{});
@@ -151,20 +185,27 @@ __global__ __launch_bounds__(1024) void attnres_kernel(const AttnArgs a) {
       run(OptTag<false>{});
     }
     TM* op = reinterpret_cast<TM*>(a.out) + ((size_t)(b * Lq + min(q, Lq - 1)) * a.ldo + h * HD);
-    G::store_out(o, op, hi, q < Lq, false);
+    G::store_out(o, op, hi, q < Lq, MASKED && q >= Lqb);      // a row past the item's end (both lane halves agree): exact zeros
   }
+  if constexpr (MASKED) attnres_zero_rows<TM, HD>(a, b, h, nqt * 32, tid);      // (a wave with no live query tile begins here while the others compute)
 
   // ---- fallbacks: + 1 per 128-query block (query tiles 4j .. 4j+3) in which a row took the exact pass -- attn_kernel's unit, one workgroup there
   if (a.fallbacks && !exact_only) {         // (workgroup-uniform)
     __syncthreads();
     if (tid == 0) {
       unsigned n = 0;
-      const int nqb = (Lq + 127) >> 7;
+      const int nqb = (Lqb + 127) >> 7;                        // the live 128-query blocks
       for (int j = 0; j < nqb; ++j) n += *reinterpret_cast<const uint32_t*>(smem + (j >> 2) * KROWB + HD * SZ + 32 + (j & 3) * 4);
       if (n) atomicAdd(a.fallbacks, n);
     }
   }
 }
+
+template <typename TM, int HD>
+__global__ __launch_bounds__(1024) void attnres_kernel(const AttnArgs a) { attnres_body<TM, HD, false>(a); }
+// the same under per-item counts (options masked_attn + masked_attn_resident).  Its own template: the dense instantiations keep their instructions
+template <typename TM, int HD>
+__global__ __launch_bounds__(1024) void attnres_lens_kernel(const AttnArgs a) { attnres_body<TM, HD, true>(a); }
 
 #define NS2VC_ATTNRES_ROW(TM, PREC, HD) {kernel_key(PREC, HD), reinterpret_cast<const void*>(attnres_kernel<TM, HD>), (uint32_t)ATTNRES_LDS, 1024}
 static const KernelRow attnres_rows[] = {
@@ -174,11 +215,21 @@ static const KernelRow attnres_rows[] = {
 #undef NS2VC_ATTNRES_ROW
 static const KernelTable k_attnres_table(attnres_rows);
 const KernelTable& attnres_kernel_table() { return k_attnres_table; }
+#define NS2VC_ATTNRES_LENS_ROW(TM, PREC, HD) \
+  {kernel_key(PREC, HD), reinterpret_cast<const void*>(attnres_lens_kernel<TM, HD>), (uint32_t)ATTNRES_LDS, 1024}
+static const KernelRow attnres_lens_rows[] = {
+  NS2VC_ATTNRES_LENS_ROW(bf16_t, PREC_BF16, 16), NS2VC_ATTNRES_LENS_ROW(bf16_t, PREC_BF16, 32),
+  NS2VC_ATTNRES_LENS_ROW(f16_t, PREC_F16, 16), NS2VC_ATTNRES_LENS_ROW(f16_t, PREC_F16, 32),
+};
+#undef NS2VC_ATTNRES_LENS_ROW
+static const KernelTable k_attnres_lens_table(attnres_lens_rows);
+const KernelTable& attnres_lens_kernel_table() { return k_attnres_lens_table; }
 static int g_min_grid = 256;          // the rule's threshold: one workgroup per CU of the device (init_attnres_attributes)
 hipError_t init_attnres_attributes() {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) g_min_grid = cus;
-  return set_lds_all(k_attnres_table);
+  const hipError_t e = set_lds_all(k_attnres_table);
+  return e != hipSuccess ? e : set_lds_all(k_attnres_lens_table);
 }
 
 void set_attnres_optimistic(int on) { const int v = on ? 0 : 1; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attnres_exact_only), &v, sizeof(v)); }
@@ -203,6 +254,21 @@ bool attention_resident_eligible(const AttnArgs& a, int head_dim, int prec, bool
   return (long long)a.B * a.H >= g_min_grid;
 }
 
+static int g_resident_lens_mode = -1; // ns2vc_debug_set_attn_resident_lens: the same three modes for the launches under length tables
+void set_attn_resident_lens_mode(int mode) { g_resident_lens_mode = mode; }
+// does this launch run on attnres_lens_kernel?  A launch under q_lens / k_lens that attention_resident_eligible would take without them.  The capacity is
+// asked of the PADDED Lk (the tables live on the device: the host does not know the counts), and the rule is the dense one.  With B*H workgroups in one
+// round the launch lasts as long as its longest item; at lengths of 470 .. 938 frames it was still the faster kernel (profiles/r22_masked_attn_resident.txt),
+// a batch of a few long and many very short items was not measured.  `allow`: the plan has both attn_resident and masked_attn_resident on.
+bool attention_resident_lens_eligible(const AttnArgs& a, int head_dim, int prec, bool allow) {
+  if (!allow || g_resident_lens_mode == 0) return false;
+  if (!(a.q_lens || a.k_lens) || a.pv_fp8) return false;
+  if (!find(k_attnres_lens_table, kernel_key(prec, head_dim))) return false;
+  if ((a.Lk + 63) / 64 > resident_max_tiles(head_dim, prec) || (a.Lq + 127) / 128 > ATTNRES_MAX_QBLOCKS) return false;
+  if (g_resident_lens_mode == 1) return true;
+  return (long long)a.B * a.H >= g_min_grid;
+}
+
 static std::atomic<unsigned long long> g_resident_launches{0};      // launches issued (or captured) on attnres_kernel: what tests read to see the selection
 unsigned long long attn_resident_launches() { return g_resident_launches.load(); }
 
@@ -210,6 +276,16 @@ hipError_t launch_attention_resident(const AttnArgs& a, int head_dim, int prec, 
   const KernelRow* row = find(k_attnres_table, kernel_key(prec, head_dim));
   if (!row) return hipErrorInvalidValue;
   ++g_resident_launches;
+  return launch(*row, dim3(a.B * a.H), s, a);      // (const AttnArgs)
+}
+
+static std::atomic<unsigned long long> g_resident_lens_launches{0}; // ... on attnres_lens_kernel: a counter of its own, the dense one keeps its meaning
+unsigned long long attn_resident_lens_launches() { return g_resident_lens_launches.load(); }
+
+hipError_t launch_attention_resident_lens(const AttnArgs& a, int head_dim, int prec, hipStream_t s) {
+  const KernelRow* row = find(k_attnres_lens_table, kernel_key(prec, head_dim));
+  if (!row) return hipErrorInvalidValue;
+  ++g_resident_lens_launches;
   return launch(*row, dim3(a.B * a.H), s, a);      // (const AttnArgs)
 }
 

@@ -342,7 +342,8 @@ hipError_t launch_xattn_pack(const void* k, int ldk, const void* v, int ldv, int
 bool gemm_masks_rows(const GemmArgs& g, int prec);                        // ... on a kernel with a masked epilogue (GemmArgs.lens), were lens set?
 bool gemm_uses_convts(const GemmArgs& g, int prec);                        // would launch_gemm run this launch on the tap-sharing conv kernel (convts.hip)?
 int last_gemm_refusal_line();                                               // gemm.hip line of the argument check that refused the last launch on this thread (0: none), cleared by the call
-hipError_t launch_attention(const AttnArgs& a, int head_dim, int prec, hipStream_t s, bool resident = true);      // resident: the plan option attn_resident
+// resident: the plan option attn_resident; resident_lens: masked_attn_resident (asked for launches under q_lens / k_lens only, and only with `resident`)
+hipError_t launch_attention(const AttnArgs& a, int head_dim, int prec, hipStream_t s, bool resident = true, bool resident_lens = true);
 // K/V-resident attention (attn_resident.hip): dense 16-bit launches at hd 16 / 32 whose key tiles all fit the LDS
 bool attention_resident_eligible(const AttnArgs& a, int head_dim, int prec, bool allow);      // consulted by launch_attention only
 hipError_t launch_attention_resident(const AttnArgs& a, int head_dim, int prec, hipStream_t s);
@@ -350,6 +351,11 @@ hipError_t init_attnres_attributes();
 void set_attn_resident_mode(int mode);          // test / tuning hook: -1 = the rule (B*H >= CUs), 0 = never, 1 = whenever the launch fits
 unsigned long long attn_resident_launches();   // launches issued (or captured) on the resident kernel so far in this process
 void set_attnres_optimistic(int on);            // (set_attn_optimistic forwards to it)
+// ... under per-item length tables (attnres_lens_kernel): a predicate, a hook and a counter of their own
+bool attention_resident_lens_eligible(const AttnArgs& a, int head_dim, int prec, bool allow);      // consulted by launch_attention only, for masked launches
+hipError_t launch_attention_resident_lens(const AttnArgs& a, int head_dim, int prec, hipStream_t s);
+void set_attn_resident_lens_mode(int mode);     // test / tuning hook: -1 = the rule (B*H >= CUs), 0 = never, 1 = whenever the launch fits
+unsigned long long attn_resident_lens_launches();
 bool attention_masks_rows(const AttnArgs& a, int head_dim, int prec);      // ... on a masked instantiation (AttnArgs.q_lens / k_lens), were they set?
 hipError_t init_gemm_attributes();
 // tap-sharing k = 3 conv kernel (convts.hip)

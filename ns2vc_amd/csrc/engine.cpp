@@ -54,7 +54,8 @@ static const struct { const char* name; const char* env; bool ns2vc_unet::* memb
   {"split_io", "NS2VC_SPLIT_IO", &ns2vc_unet::split_io}, {"masked_fuse", "NS2VC_MASKED_FUSE", &ns2vc_unet::masked_fuse},
   {"masked_attn", "NS2VC_MASKED_ATTN", &ns2vc_unet::masked_attn}, {"masked_rows", "NS2VC_MASKED_ROWS", &ns2vc_unet::masked_rows},
   {"masked_ffn", "NS2VC_MASKED_FFN", &ns2vc_unet::masked_ffn}, {"masked_geglu", "NS2VC_MASKED_GEGLU", &ns2vc_unet::masked_geglu},
-  {"attn_resident", "NS2VC_ATTN_RESIDENT", &ns2vc_unet::attn_resident}};
+  {"attn_resident", "NS2VC_ATTN_RESIDENT", &ns2vc_unet::attn_resident},
+  {"masked_attn_resident", "NS2VC_MASKED_ATTN_RESIDENT", &ns2vc_unet::masked_attn_resident}};
 static bool* option_ptr(ns2vc_unet* h, const char* name) {
   for (const auto& o : kOptions)
     if (!strcmp(name, o.name)) return &(h->*o.member);

@@ -360,6 +360,10 @@ struct ns2vc_unet {
   // copy to qb) and ff.out+proj_out stay as they are.  Asked per launch (geglu_masks_rows).  Independent of the four options above; dense plans and
   // the fp32 engine ignore it.
   bool masked_geglu = false;
+  // Option masked_attn_resident (off): the attention launches that masked_attn has given a length table run on the K/V-resident kernel's masked form
+  // (attnres_lens_kernel) where launch_attention's rule selects it (attention_resident_lens_eligible: hd 16 / 32, 16-bit, the padded key rows fit the
+  // LDS, B * heads >= the CUs) and attn_resident is on.  Same bits, same launches.  On its own (masked_attn or attn_resident off, a dense plan) it does nothing.
+  bool masked_attn_resident = false;
   // Per-item valid lengths (ns2vc_unet_set_lengths).  `masked`: the plan was built for them -- GroupNorm statistics by their own pass over
   // rows whose padding is zero (no epilogue sums, so no fused GroupNorm prologue, row chain or LayerNorm by linearity), every activation's
   // rows past an item's end zeroed after the launch that writes them, the self-attention keys there masked by an additive bias row, the

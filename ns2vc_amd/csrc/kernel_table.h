@@ -61,5 +61,6 @@ const KernelTable& geglu_kernel_table();
 const KernelTable& rowchain_kernel_table();
 // (not a family of ns2vc_debug_kernel_table: ns2vc_debug_attnres_table)
 const KernelTable& attnres_kernel_table();
+const KernelTable& attnres_lens_kernel_table();      // (ns2vc_debug_attnres_lens_table)
 
 }  // namespace ns2vc

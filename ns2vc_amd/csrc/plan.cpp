@@ -304,8 +304,8 @@ struct Planner {
       a.k_lens = cross_lens;
       if (!h->has_mask) a.bias = nullptr;
     }
-    const bool resident = h->attn_resident;
-    add(name, [=](hipStream_t s) { return launch_attention(a, hd, pr, s, resident); }, 2, 4.0 * B * a.H * (double)Lq * Lk * hd,
+    const bool resident = h->attn_resident, resident_lens = h->masked_attn_resident;      // (the second: launches under q_lens / k_lens only)
+    add(name, [=](hipStream_t s) { return launch_attention(a, hd, pr, s, resident, resident_lens); }, 2, 4.0 * B * a.H * (double)Lq * Lk * hd,
         (double)opsz * B * a.H * hd * (2.0 * Lq + 2.0 * Lk));
     if (!self_mask) mask(name, out, ldo, a.H * hd, opsz, Lq);
   }

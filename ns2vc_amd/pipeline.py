@@ -35,6 +35,9 @@ MASKED_OPTIONS = (
                         # item's end itself (the fp32 engine ignores it)
     "masked_geglu",     # the dim-384 transformer blocks keep the token-stationary GEGLU launch, which takes the LayerNorm sums from its own
                         # operand rows and zeroes the rows past an item's end itself
+    "masked_attn_resident",     # the attention launches that masked_attn gave a length table run on the K/V-resident kernel's masked form where
+                        # the engine's rule selects it (head width 16 / 32, B * heads >= the CUs); without masked_attn it does nothing, and the
+                        # fp32 engine has no such kernel and ignores it
 )
 
 # LayerNorm-by-linearity guard thresholds on max |mean|/std (see Denoiser): 16-bit modes lose ~ratio * 2^-11 on a row,
@@ -84,7 +87,8 @@ class Denoiser:
     def __init__(self, state: Dict[str, object], cfg: UNetConfig = UNetConfig(), precision: str = DEFAULT_PRECISION,
                  betas: Optional[np.ndarray] = None, ln_guard: Optional[float] = -1.0, tail_fp32: Optional[int] = None,
                  precision_check: Optional[float] = -1.0, attn_fallback_limit: Optional[float] = 0.10, masked_fuse: bool = False,
-                 masked_attn: bool = False, masked_rows: bool = False, masked_ffn: bool = False, masked_geglu: bool = False):
+                 masked_attn: bool = False, masked_rows: bool = False, masked_ffn: bool = False, masked_geglu: bool = False,
+                 masked_attn_resident: bool = False):
         given = locals()
         self.cfg = cfg
         for name in MASKED_OPTIONS:

@@ -86,6 +86,7 @@ class GroupedConverter:
                  solver: str = "unipc", steps: Optional[int] = 30, order: int = 2, seed: int = 1234, ragged: bool = False, eta: float = 0.0,
                  masked_fuse: Optional[bool] = None, masked_attn: Optional[bool] = None,
                  masked_rows: Optional[bool] = None, masked_ffn: Optional[bool] = None, masked_geglu: Optional[bool] = None,
+                 masked_attn_resident: Optional[bool] = None,
                  ragged_prompts: bool = False, guidance_scale: float = 1.0, unconditional_prompt: Optional[torch.Tensor] = None,
                  correcting_x0_fn=None, thresholding_max_val: float = 1.0, dynamic_thresholding_ratio: float = 0.995, **options):
         """``correcting_x0_fn`` / ``thresholding_max_val`` / ``dynamic_thresholding_ratio``: the x0 correction of ``Denoiser.sample``, passed through.

@@ -7,6 +7,7 @@
 --masked-rows (with --masked-fuse --masked-attn) adds (b3) -- leg (b'') with the engine option masked_rows on as well -- to that rotation;
 --masked-ffn (with --masked-fuse --masked-attn --masked-rows) adds (b4) -- leg (b3) with the engine option masked_ffn on as well -- to that rotation;
 --masked-geglu (with --masked-fuse --masked-attn --masked-rows --masked-ffn) adds (b5) -- leg (b4) with the engine option masked_geglu on as well -- to that rotation;
+--masked-attn-resident (with the five above) adds (b6) -- leg (b5) with the engine option masked_attn_resident on as well -- to that rotation;
 --skip-per-shape leaves (c) out.
 Each figure is the median of `--reps` timed sampling loops (hipGraph replays, condition set outside the timing) after a warm-up loop.
 Usage: python tools/ragged_bench.py [--reps 5] [--out FILE]"""
@@ -33,6 +34,8 @@ def main():
     ap.add_argument("--masked-rows", action="store_true", help="with --masked-fuse --masked-attn: also run leg (b'') with the option masked_rows on")
     ap.add_argument("--masked-ffn", action="store_true", help="with --masked-fuse --masked-attn --masked-rows: also run leg (b3) with the option masked_ffn on")
     ap.add_argument("--masked-geglu", action="store_true", help="with --masked-fuse --masked-attn --masked-rows --masked-ffn: also run leg (b4) with the option masked_geglu on")
+    ap.add_argument("--masked-attn-resident", action="store_true",
+                    help="with --masked-fuse --masked-attn --masked-rows --masked-ffn --masked-geglu: also run leg (b5) with the option masked_attn_resident on")
     ap.add_argument("--alternate", type=int, default=3, help="repetitions of (a), (b), (b') in turn (with --masked-fuse)")
     ap.add_argument("--skip-per-shape", action="store_true")
     a = ap.parse_args()
@@ -45,9 +48,10 @@ def main():
     e = Engine(precision="fp16")
     e.load_state_dict(procedural_state_dict(seed=0))
     fused_now = attn_now = rows_now = ffn_now = geglu_now = False      # the engine's masked_fuse / masked_attn / masked_rows / masked_ffn / masked_geglu options as last set
+    ares_now = False                                                   # ... and masked_attn_resident
 
-    def loop_ms(bsz, tl, lengths=None, sl=slice(None), fuse=False, attn=False, rows=False, ffn=False, geglu=False):
-        nonlocal fused_now, attn_now, rows_now, ffn_now, geglu_now
+    def loop_ms(bsz, tl, lengths=None, sl=slice(None), fuse=False, attn=False, rows=False, ffn=False, geglu=False, ares=False):
+        nonlocal fused_now, attn_now, rows_now, ffn_now, geglu_now, ares_now
         if fused_now != fuse:
             e.set_option("masked_fuse", fuse)        # (drops the plan: prepared again below)
             fused_now = fuse
@@ -63,6 +67,9 @@ def main():
         if geglu_now != geglu:
             e.set_option("masked_geglu", geglu)
             geglu_now = geglu
+        if ares_now != ares:
+            e.set_option("masked_attn_resident", ares)
+            ares_now = ares
         if e.shape != (bsz, tl, Lp):
             e.prepare(bsz, tl, Lp)
             e.load_sampler("unipc", a.steps)
@@ -100,6 +107,9 @@ def main():
                     if a.masked_geglu:
                         legs["b_fused_attn_rows_ffn_geglu"] = lambda: loop_ms(B, T, lens, fuse=True, attn=True, rows=True, ffn=True, geglu=True)
                         order.append("b_fused_attn_rows_ffn_geglu")
+                        if a.masked_attn_resident:
+                            legs["b_all_attn_resident"] = lambda: loop_ms(B, T, lens, fuse=True, attn=True, rows=True, ffn=True, geglu=True, ares=True)
+                            order.append("b_all_attn_resident")
         for i in range(a.alternate):             # the order rotates, so that a drift of the clocks does not favour one leg
             k0 = i % len(order)
             rot = order[k0:] + order[:k0]
@@ -133,6 +143,10 @@ def main():
             r["fused"].update({"b_fused_attn_rows_ffn_geglu_ms": round(med["b_fused_attn_rows_ffn_geglu"], 3),
                                "b_fused_attn_rows_ffn_geglu_over_a": round(med["b_fused_attn_rows_ffn_geglu"] / med["a"], 3),
                                "b_fused_attn_rows_ffn_geglu_over_b_fused_attn_rows_ffn": round(med["b_fused_attn_rows_ffn_geglu"] / med["b_fused_attn_rows_ffn"], 3)})
+        if "b_all_attn_resident" in med:
+            r["fused"].update({"b_all_attn_resident_ms": round(med["b_all_attn_resident"], 3),
+                               "b_all_attn_resident_over_a": round(med["b_all_attn_resident"] / med["a"], 3),
+                               "b_all_attn_resident_over_b_fused_attn_rows_ffn_geglu": round(med["b_all_attn_resident"] / med["b_fused_attn_rows_ffn_geglu"], 3)})
     line = json.dumps(r)
     print(line)
     if a.out:
